@@ -19,6 +19,9 @@ Configurations (BASELINE.json `configs`):
   c4            Hex27 NeoHookean 50 x 50 x 80, hexahedron_gauss(3); roofline = fp64 matrix-core flops.
   c5            Hex8 linear elasticity 256^3 cut into N z-slabs (strong scaling; 32 layers per rank at N = 8).
 
+--dump-outputs DIR writes what the last timed step computed (the CSR values: every entry, or a fixed seeded sample of 2^21 on the large
+meshes) to DIR/*.npy; the inputs of a configuration are the same from run to run, so two builds can be compared entry for entry.
+
 Prints ONE JSON line on rank 0.  The default run (--config ns on one GPU) appends `secondary_vectors` (residual vector and energy of the
 headline mesh) and `secondary`: every other configuration
 (c2, c3, c4, c5 at N = 1, ns-perturbed) timed in the same process after the headline -- {ms, frac of its roofline, kernel}.
@@ -35,6 +38,8 @@ sys.path.insert(0, ROOT)
 
 PEAK_HBM_GBS = 8000.0     # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 PEAK_FP64_TFLOPS = 78.6   # MI355X fp64 vector = fp64 matrix-core peak
+DUMP_ENTRIES = 1 << 21    # --dump-outputs: CSR entries written, all ranks together (3 float64 arrays: 48 MiB)
+DUMP_SEED = 12345         # --dump-outputs: seed of the entry sample when the values array holds more entries than that
 
 
 def algorithmic_bytes(E, N, s, n, d, nnz, uses_u=False):
@@ -388,6 +393,27 @@ def probe_placement(eng, values, flags, torch, tries):
     return probe(eng, values, flags, tries)
 
 
+def dump_outputs(out_dir, eng, values, rank, world, np, torch):
+    """--dump-outputs DIR: what the last timed step left in the CSR values array -- the K a caller of the timed path receives -- as three
+    float64 arrays of equal length: values.npy (the entries), entry.npy (their positions in the values array) and row.npy (their CSR rows;
+    positions and rows stay below 2^53, exact in float64).  Every entry when the array holds at most DUMP_ENTRIES / world of them, else that
+    many positions drawn with DUMP_SEED (the same positions whenever nnz is the same).  N > 1: one set per rank, files prefixed rank<r>_."""
+    nnz = values.numel()
+    k = DUMP_ENTRIES // world
+    if nnz <= k:
+        pos = np.arange(nnz, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, nnz, size=k, dtype=np.int64))
+    vals = values[torch.as_tensor(pos, device=values.device)].cpu().numpy().astype(np.float64)
+    ro, _ = eng.pattern(want_cols=False)
+    rows = np.searchsorted(ro.astype(np.int64), pos, side="right") - 1
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in (("values", vals), ("entry", pos), ("row", rows)):
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    sys.stderr.write(f"[bench rank {rank}] --dump-outputs: {len(pos)} of {nnz} CSR entries written to {out_dir}\n")
+
+
 def settle_device(eng, values, flags, max_s=2.5, group=20):
     """fenris_amd/placement.py: untimed assemblies until a fresh device has reached its steady rate (part of the set-up, like the probe)"""
     from fenris_amd.placement import settle_device as settle
@@ -473,7 +499,11 @@ def main():
     ap.add_argument("--no-module-warmup", action="store_true",
                     help="skip the tiny assembly that loads the code objects before anything is timed (profiling runs: its dispatches would "
                          "enter the per-kernel averages)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the CSR values of the last one (a fixed seeded sample of at most 48 MiB) to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -680,6 +710,8 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     (slab_asm or eng).poll_status()
+    if args.dump_outputs:   # here, before the exchange timing and the secondary lines below touch the values again
+        dump_outputs(args.dump_outputs, eng, values, rank, world, np, torch)
     kernel_ms = sorted(a.elapsed_time(b) for a, b in ev)
     kernel_avg_ms = sum(kernel_ms) / len(kernel_ms)
     per_rank_ms = None
