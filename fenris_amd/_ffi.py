@@ -112,6 +112,11 @@ _SIGS = {
     "fh_spmv_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fh_cg_solve": (C.c_int, [C.c_void_p, f64p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_cg_solve_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, u64p]),
+    "fh_set_operator_dirichlet_nodes": (C.c_int, [C.c_void_p, u64p, C.c_uint64]),
+    "fh_apply_operator_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fh_operator_diagonal_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_cg_solve_matrix_free": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
+    "fh_cg_solve_matrix_free_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_estimate_L2_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),
     "fh_estimate_L2_error_squared_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, f64p]),
     "fh_estimate_H1_seminorm_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),

@@ -66,12 +66,14 @@ class Engine:
     # inputs
     def set_mesh(self, mesh: Mesh):
         self._mesh = mesh  # keep the host arrays alive
+        self._mf_bound = None  # fh_set_mesh clears the operator's Dirichlet nodes
         self._check(self._lib.fh_set_mesh(self._h, mesh.elem_kind, _ffi.fp(mesh.vertices), mesh.num_nodes(),
                                           _ffi.up(mesh.connectivity), mesh.num_elements()))
 
     def set_connectivity_ragged(self, sdim, num_nodes, elem_offsets, elem_nodes):
         eo, en = _ffi.as_u64(elem_offsets), _ffi.as_u64(elem_nodes)
         en_p = en if len(en) else np.zeros(1, dtype=np.uint64)
+        self._mf_bound = None
         self._check(self._lib.fh_set_connectivity_ragged(self._h, sdim, num_nodes, _ffi.up(eo), _ffi.up(en_p), len(eo) - 1))
 
     def set_active_elements(self, mask):
@@ -327,6 +329,31 @@ class Engine:
         out = np.zeros((count, ld, ld))
         self._check(self._lib.fh_assemble_element_matrices(self._h, first, count, _ffi.fp(out)))
         return out.transpose(0, 2, 1).copy()  # column-major blocks -> [e][row][col]
+
+    # matrix-free operator (FH_LAPLACE, FH_LINEAR_ELASTIC): no pattern, no values
+    def set_operator_dirichlet_nodes(self, nodes):
+        self._mf_bound = None   # (MatrixFreeOperator: no operator's nodes are bound any more)
+        nodes = _ffi.as_u64(nodes if nodes is not None else [])
+        self._check(self._lib.fh_set_operator_dirichlet_nodes(self._h, _ffi.up(nodes) if len(nodes) else None, len(nodes)))
+
+    def apply_operator_dev(self, x_t, y_t):
+        self._check(self._lib.fh_apply_operator_dev(self._h, C.c_void_p(x_t.data_ptr()), C.c_void_p(y_t.data_ptr())))
+
+    def operator_diagonal_dev(self, diag_t):
+        self._check(self._lib.fh_operator_diagonal_dev(self._h, C.c_void_p(diag_t.data_ptr())))
+
+    def cg_solve_matrix_free(self, b, x, preconditioner=1, rel_tol=1e-9, max_iter=0):
+        """fh_cg_solve_matrix_free(_dev): cg_solve with the matrix-free operator"""
+        it = C.c_uint64(0)
+        if _is_torch(b):
+            rc = self._lib.fh_cg_solve_matrix_free_dev(self._h, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), preconditioner,
+                                                       rel_tol, max_iter, C.byref(it))
+        else:
+            rc = self._lib.fh_cg_solve_matrix_free(self._h, _ffi.fp(b), _ffi.fp(x), preconditioner, rel_tol, max_iter, C.byref(it))
+        if rc in (7, 8, 9):
+            raise CgSolveError(rc, (self._lib.fh_last_error(self._h) or b"").decode(), int(it.value))
+        self._check(rc)
+        return int(it.value)
 
     def apply_dirichlet_csr_dev(self, values_t, nodes):
         nodes = _ffi.as_u64(nodes)
@@ -878,6 +905,58 @@ class IdentityOperator:
     """fenris-sparse/src/cg.rs:54-61"""
 
 
+class MatrixFreeOperator:
+    """A LinearOperator (fenris-sparse/src/cg.rs:16-51) of an element assembler whose operator is linear (Laplace, LinearElastic):
+    y = A x through the element pass of the residual, with neither pattern nor values.  With Dirichlet nodes, A is the matrix that
+    apply_homogeneous_dirichlet_bc_csr leaves of the assembled one.  The nodes belong to this object: they are handed to the
+    assembler's engine before every use, so several operators may share one assembler.  Vectors: numpy arrays or device tensors."""
+
+    def __init__(self, element_assembler):
+        self.element_assembler = element_assembler
+        self.engine = element_assembler.engine
+        self._nodes = None
+
+    def with_dirichlet_nodes(self, nodes):
+        self._nodes = None if nodes is None else _ffi.as_u64(nodes).copy()
+        self._bind(force=True)
+        return self
+
+    def _bind(self, force=False):
+        # (the engine keeps the nodes of the operator that used it last: handed over again only when another operator has used it since)
+        if force or getattr(self.engine, "_mf_bound", None) is not self:
+            self.engine.set_operator_dirichlet_nodes(self._nodes)
+            self.engine._mf_bound = self
+
+    def apply(self, y, x):
+        """y = A x (y overwritten, like LinearOperator::apply)"""
+        self._bind()
+        if _is_torch(x):
+            self.engine.apply_operator_dev(x, y)
+            return y
+        import torch
+
+        xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(f"cuda:{self.engine.device}")
+        yt = torch.empty_like(xt)
+        self.engine.apply_operator_dev(xt, yt)
+        y[...] = yt.cpu().numpy().reshape(np.shape(y))
+        return y
+
+    def diagonal(self, device=False):
+        """the diagonal of A (numpy array, or a device tensor when device=True)"""
+        import torch
+
+        self._bind()
+        n = self.element_assembler.solution_dim() * self.engine.num_nodes()
+        d = torch.empty(n, dtype=torch.float64, device=f"cuda:{self.engine.device}")
+        self.engine.operator_diagonal_dev(d)
+        return d if device else d.cpu().numpy()
+
+    def cg_solve(self, b, x, preconditioner=1, rel_tol=1e-9, max_iter=0):
+        """fh_cg_solve_matrix_free(_dev) on this operator; returns the iteration count"""
+        self._bind()
+        return self.engine.cg_solve_matrix_free(b, x, preconditioner, rel_tol, max_iter)
+
+
 class ConjugateGradient:
     """fenris-sparse/src/cg.rs:196-478, builder style.  The operator is the CSR matrix assembled by an element
     assembler of this package (its engine holds the pattern); values, right-hand side and solution may be numpy
@@ -890,8 +969,12 @@ class ConjugateGradient:
     def new(cls):
         return cls()
 
-    def with_operator(self, csr: "CsrMatrix", element_assembler):
-        self._csr, self._asm = csr, element_assembler
+    def with_operator(self, csr, element_assembler=None):
+        """(csr, element_assembler): the assembled matrix; or one MatrixFreeOperator"""
+        if isinstance(csr, MatrixFreeOperator):
+            self._csr, self._asm = csr, csr.element_assembler
+        else:
+            self._csr, self._asm = csr, element_assembler
         return self
 
     def with_preconditioner(self, preconditioner):
@@ -911,6 +994,8 @@ class ConjugateGradient:
         if self._csr is None or self._crit is None:
             raise ValueError("operator and stopping criterion are required")
         pre = 1 if isinstance(self._pre, JacobiPreconditioner) else 0
+        if isinstance(self._csr, MatrixFreeOperator):   # Jacobi: the matrix-free diagonal
+            return self._csr.cg_solve(b, x, pre, self._crit.tol, self._max_iter)
         return self._asm.engine.cg_solve(self._csr.values, b, x, pre, self._crit.tol, self._max_iter)
 
 

@@ -149,4 +149,15 @@ __device__ __forceinline__ void report_singular(DevStatus* st, long long e) {
 // hardware fp64 atomic add (global_atomic_add_f64 / ds_add_f64); never a CAS loop
 __device__ __forceinline__ void atomic_add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
 
+// matrix-free operator: the operand is scaled by 2^-e, e the binary exponent of |x|_inf (bits: that maximum as the bits of a non-negative
+// double; null, zero or not finite: e = 0), and the node sums by 2^e -- exact.  The LinearElastic element kernels form F = I + grad u^T,
+// which keeps ~eps / |grad u| of relative precision: a CG direction of size 1e-9 came back with 1e-7 relative errors (and Jacobi-PCG stalled).
+__device__ __forceinline__ int mf_exponent(const unsigned long long* bits) {
+    if (!bits) return 0;
+    const double m = __longlong_as_double((long long)*bits);
+    int e = 0;
+    if (m > 0.0 && m <= 1.7976931348623157e308) (void)frexp(m, &e);
+    return e;
+}
+
 }  // namespace fenris_hip

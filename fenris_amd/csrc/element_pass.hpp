@@ -756,6 +756,68 @@ __global__ void __launch_bounds__(256) k_vector_from_elements_soa(int num_nodes,
     }
 }
 
+// diagonal of one element matrix of a linear operator (the matrix-free Jacobi preconditioner, engine_vector.hip) from its vertex
+// coordinates, without the matrix: with g_a = J^-T ghat_a the physical gradient of basis function a and s = w |det J|, entry (a, i) is
+//   Laplace:        s |g_a|^2
+//   LinearElastic:  s (mu (|g_a|^2 + g_a,i^2) + lambda g_a,i^2)
+// the diagonal of the blocks that assemble_element_elliptic_matrix forms (src/assembly/local/elliptic.rs:407-455; laplace.rs,
+// materials.rs:71-123).  det J == 0 is reported like the residual reports it; such an element adds nothing.
+template <int D, int S, int N, int OP>
+__device__ __forceinline__ void diagonal_element_body(const KArgs& a, const long long e, bool live, const double (&X)[N][D], double (&f)[N][S]) {
+    static_assert(OP == FH_LAPLACE || OP == FH_LINEAR_ELASTIC, "linear operators only");
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) f[n][k] = 0.0;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    for (int q = 0; q < a.nq; ++q) {
+        const ep_table G = ep_const(a.gref) + (size_t)q * N * D;
+        double J[D][D], Ji[D][D];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) J[i][j] = 0.0;
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const double g = G[n * D + j];
+#pragma unroll
+                for (int i = 0; i < D; ++i) J[i][j] = fma(X[n][i], g, J[i][j]);
+            }
+        const double detJ = det_small<D>(J);
+        if (detJ == 0.0) {
+            if (live) report_singular(a.status, e);
+            continue;
+        }
+        inv_small(J, detJ, Ji);
+        const double s = ep_const(a.qw)[q] * fabs(detJ);
+        double mu = 0.0, lambda = 0.0;
+        if (OP != FH_LAPLACE) {
+            if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
+            else { mu = ep_const(a.qparams)[2 * q]; lambda = ep_const(a.qparams)[2 * q + 1]; }
+        }
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            double g[D], gg = 0.0;
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                double t = 0.0;
+#pragma unroll
+                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], G[n * D + m], t);
+                g[i] = t;
+                gg = fma(t, t, gg);
+            }
+            if constexpr (OP == FH_LAPLACE) {
+                f[n][0] = fma(s, gg, f[n][0]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < S; ++i) f[n][i] = fma(s, mu * (gg + g[i] * g[i]) + lambda * (g[i] * g[i]), f[n][i]);
+            }
+        }
+    }
+}
+
 // partial sums in index order by one workgroup: thread t takes the partials t, t + 256, ... in order, then the fixed tree
 static __global__ void __launch_bounds__(256) k_sum_partials(const double* partial, int n, double* out) {
     __shared__ double red[4];

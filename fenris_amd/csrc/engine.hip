@@ -544,6 +544,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     HIP_TRY(c, hipSetDevice(c->device));
     invalidate_pattern(c);
     c->has_mesh = false;
+    c->mf_num_dirichlet = 0;
     c->ragged = false;
     c->elem_kind = elem_kind;
     c->ei = ei;
@@ -625,6 +626,7 @@ int fh_update_vertices(fh_ctx* c, const double* vertices) {
     if (!vertices) return c->fail(FH_BAD_ARGUMENT, "fh_update_vertices: null pointer");
     HIP_TRY(c, hipMemcpyAsync(c->verts.p, vertices, sizeof(double) * c->N * c->ei.d, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    ++c->geom_gen;
     return classify_affine(c);
 }
 
@@ -638,6 +640,7 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     HIP_TRY(c, hipSetDevice(c->device));
     invalidate_pattern(c);
     c->has_mesh = false;
+    c->mf_num_dirichlet = 0;
     c->ragged = true;
     c->has_aff = false;
     c->row_lo = 0;

@@ -122,44 +122,24 @@ int fh_spmv_dev(fh_ctx* c, const double* values_dev, const double* x_dev, double
     return spmv_launch(c, values_dev, x_dev, y_dev, nullptr, 0, nullptr);
 }
 
-int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
-                    uint64_t max_iter, uint64_t* num_iterations) {
-    if (!c) return FH_BAD_ARGUMENT;
-    DevGuard dev_guard_(c->device);
-    if (num_iterations) *num_iterations = 0;
-    int rc = matrix_ready(c, "fh_cg_solve");
-    if (rc) return rc;
-    if (!values_dev || !b_dev || !x_dev) return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve: null argument");
-    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI)
-        return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve: unknown preconditioner");
-    const int S = c->S();
-    const int n = S * (int)c->N;
-    if (n == 0) return FH_OK;
+// ConjugateGradient::solve_with_guess (cg.rs:366-478) around an operator: apply(in, out, ranges) writes out = A in and, when ranges is
+// not null, leaves the partials of in . out summed over *ranges contiguous ranges in partial (a DevBuf<double> of at least 3 * max(gv, *ranges)
+// doubles: the caller sizes it); dinv: the Jacobi preconditioner or null.  Per iteration the host tests convergence (RelativeResidualCriterion).
+extern "C++" template <class Apply>
+static int cg_run(fh_ctx* c, int n, const double* b_dev, double* x_dev, const double* dinv, DevBuf<double>& partial, DevBuf<double>& wg_partial,
+                  double rel_tol, uint64_t max_iter, uint64_t* num_iterations, Apply&& apply) {
     const int gv = std::min(1024, (n + 255) / 256);                               // vector kernels: ranges of their per-workgroup partials
     const int gvb = std::max(1, (n + 255) / 256);                                 // ... and their workgroups: one entry per thread, short-lived (see spmv_launch)
-    const int gs = (int)std::min<uint64_t>(2048, (c->N + 3) / 4);                  // SpMV: ranges of its per-workgroup partials
-    DevBuf<double> r, z, p, Ap, dinv, partial, wg_partial;
+    DevBuf<double> r, z, p, Ap;
     HIP_TRY(c, r.alloc(n));
     HIP_TRY(c, z.alloc(n));
     HIP_TRY(c, p.alloc(n));
     HIP_TRY(c, Ap.alloc(n));
-    HIP_TRY(c, partial.alloc((size_t)3 * std::max(gv, gs)));
-    HIP_TRY(c, wg_partial.alloc((size_t)3 * gvb));
-    if (preconditioner == FH_PRECOND_JACOBI) {
-        HIP_TRY(c, dinv.alloc(n));
-        const int g = (n + 255) / 256;
-        switch (S) {
-            case 1: hipLaunchKernelGGL((k_inverse_diagonal<1>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
-            case 2: hipLaunchKernelGGL((k_inverse_diagonal<2>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
-            default: hipLaunchKernelGGL((k_inverse_diagonal<3>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
-        }
-        HIP_TRY(c, hipGetLastError());
-    }
-    c->last_kernel = (c->max_row <= 32 && !c->env("FENRIS_HIP_SPMV_WAVE_PER_NODE")) ? "k_spmv_blocked_half" : "k_spmv_blocked";
+    if (wg_partial.n < (size_t)3 * gvb) HIP_TRY(c, wg_partial.alloc((size_t)3 * gvb));
     // r = b - A x;  z = P r;  p = z   (cg.rs:388-404)
-    rc = spmv_launch(c, values_dev, x_dev, r.p, nullptr, 0, nullptr);
+    int rc = apply(x_dev, r.p, nullptr);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_cg_init, dim3(gvb), dim3(256), 0, c->stream, n, b_dev, dinv.p, r.p, z.p, p.p, wg_partial.p);
+    hipLaunchKernelGGL(k_cg_init, dim3(gvb), dim3(256), 0, c->stream, n, b_dev, dinv, r.p, z.p, p.p, wg_partial.p);
     hipLaunchKernelGGL(k_sum_partial_ranges<3>, dim3(gv), dim3(256), 0, c->stream, wg_partial.p, (long long)gvb, partial.p);
     HIP_TRY(c, hipGetLastError());
     double s3[3];
@@ -179,14 +159,15 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
         if (r_norm <= rel_tol * b_norm) break;  // RelativeResidualCriterion, cg.rs:108-124
         if (max_iter && it >= max_iter) { status = FH_CG_MAX_ITERATIONS; break; }
         double pAp;
-        rc = spmv_launch(c, values_dev, p.p, Ap.p, partial.p, gs, &wg_partial);
+        int ranges = 0;
+        rc = apply(p.p, Ap.p, &ranges);
         if (rc) return rc;
-        rc = sum_partials(c, partial.p, gs, 1, &pAp);
+        rc = sum_partials(c, partial.p, ranges, 1, &pAp);
         if (rc) return rc;
         if (pAp <= 0.0) { status = FH_CG_INDEFINITE_OPERATOR; break; }
         if (zTr <= 0.0) { status = FH_CG_INDEFINITE_PRECONDITIONER; break; }
         const double alpha = zTr / pAp;
-        hipLaunchKernelGGL(k_cg_update, dim3(gvb), dim3(256), 0, c->stream, n, alpha, p.p, Ap.p, dinv.p, x_dev, r.p, z.p, wg_partial.p);
+        hipLaunchKernelGGL(k_cg_update, dim3(gvb), dim3(256), 0, c->stream, n, alpha, p.p, Ap.p, dinv, x_dev, r.p, z.p, wg_partial.p);
         hipLaunchKernelGGL(k_sum_partial_ranges<2>, dim3(gv), dim3(256), 0, c->stream, wg_partial.p, (long long)gvb, partial.p);
         HIP_TRY(c, hipGetLastError());
         ++it;
@@ -207,6 +188,90 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
     return FH_OK;
 }
 
+int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
+                    uint64_t max_iter, uint64_t* num_iterations) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    if (num_iterations) *num_iterations = 0;
+    int rc = matrix_ready(c, "fh_cg_solve");
+    if (rc) return rc;
+    if (!values_dev || !b_dev || !x_dev) return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve: null argument");
+    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI)
+        return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve: unknown preconditioner");
+    const int S = c->S();
+    const int n = S * (int)c->N;
+    if (n == 0) return FH_OK;
+    const int gv = std::min(1024, (n + 255) / 256);
+    const int gs = (int)std::min<uint64_t>(2048, (c->N + 3) / 4);                  // SpMV: ranges of its per-workgroup partials
+    DevBuf<double> dinv, partial, wg_partial;
+    HIP_TRY(c, partial.alloc((size_t)3 * std::max(gv, gs)));
+    if (preconditioner == FH_PRECOND_JACOBI) {
+        HIP_TRY(c, dinv.alloc(n));
+        const int g = (n + 255) / 256;
+        switch (S) {
+            case 1: hipLaunchKernelGGL((k_inverse_diagonal<1>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
+            case 2: hipLaunchKernelGGL((k_inverse_diagonal<2>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
+            default: hipLaunchKernelGGL((k_inverse_diagonal<3>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
+        }
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->last_kernel = (c->max_row <= 32 && !c->env("FENRIS_HIP_SPMV_WAVE_PER_NODE")) ? "k_spmv_blocked_half" : "k_spmv_blocked";
+    return cg_run(c, n, b_dev, x_dev, dinv.p, partial, wg_partial, rel_tol, max_iter, num_iterations,
+                  [&](const double* in, double* out, int* ranges) {
+                      if (!ranges) return spmv_launch(c, values_dev, in, out, nullptr, 0, nullptr);
+                      *ranges = gs;
+                      return spmv_launch(c, values_dev, in, out, partial.p, gs, &wg_partial);
+                  });
+}
+
+// The same solver around the matrix-free operator (fh_apply_operator_dev): no pattern, no values.  The partials of p . Ap come from the
+// operator's node pass (or its last pass off the tiles), summed over at most 2048 ranges in a fixed order; Jacobi takes the matrix-free
+// diagonal.  The diagonal (and with it the scale of the Dirichlet rows) is formed once per solve.
+int fh_cg_solve_matrix_free_dev(fh_ctx* c, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
+                                uint64_t* num_iterations) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    if (num_iterations) *num_iterations = 0;
+    int rc = mf_ready(c, "fh_cg_solve_matrix_free");
+    if (rc) return rc;
+    if (!b_dev || !x_dev) return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve_matrix_free: null argument");
+    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI)
+        return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve_matrix_free: unknown preconditioner");
+    const int S = c->S();
+    const int n = S * (int)c->N;
+    if (n == 0) return FH_OK;
+    const int gv = std::min(1024, (n + 255) / 256);
+    const int gs_max = 2048;
+    DevBuf<double> dinv, partial, wg_partial;
+    HIP_TRY(c, partial.alloc((size_t)3 * std::max(gv, gs_max)));
+    if (preconditioner == FH_PRECOND_JACOBI || c->mf_num_dirichlet) {
+        HIP_TRY(c, dinv.alloc(n));
+        rc = mf_diagonal(c, dinv.p, true);
+        if (rc) return rc;
+        if (preconditioner == FH_PRECOND_JACOBI) {
+            hipLaunchKernelGGL(k_reciprocal, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dinv.p);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    rc = reset_status(c);
+    if (rc) return rc;
+    const int rcg = cg_run(c, n, b_dev, x_dev, preconditioner == FH_PRECOND_JACOBI ? dinv.p : nullptr, partial, wg_partial, rel_tol, max_iter,
+                           num_iterations, [&](const double* in, double* out, int* ranges) {
+                               if (!ranges) return mf_apply(c, in, out, nullptr, nullptr);
+                               int count = 0;
+                               int r = mf_apply(c, in, out, &wg_partial, &count);
+                               if (r) return r;
+                               *ranges = std::min(gs_max, count);
+                               hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(*ranges), dim3(256), 0, c->stream, wg_partial.p, (long long)count, partial.p);
+                               HIP_TRY(c, hipGetLastError());
+                               return (int)FH_OK;
+                           });
+    // a singular Jacobian shows in the operator's first application already (and in the diagonal): report it over the solver's status
+    rc = read_status(c, nullptr);
+    if (rc) return rc;
+    return rcg;
+}
+
 int fh_cg_solve(fh_ctx* c, const double* values, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter,
                 uint64_t* num_iterations) {
     if (!c) return FH_BAD_ARGUMENT;
@@ -223,6 +288,26 @@ int fh_cg_solve(fh_ctx* c, const double* values, const double* b, double* x, int
     HIP_TRY(c, hipMemcpyAsync(db.p, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     rc = fh_cg_solve_dev(c, dv.p, db.p, dx.p, preconditioner, rel_tol, max_iter, num_iterations);
+    // like the reference's SolveError, the iterate reached so far is handed back on failure
+    HIP_TRY(c, hipMemcpyAsync(x, dx.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+int fh_cg_solve_matrix_free(fh_ctx* c, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    if (num_iterations) *num_iterations = 0;
+    int rc = mf_ready(c, "fh_cg_solve_matrix_free");
+    if (rc) return rc;
+    if (!b || !x) return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve_matrix_free: null argument");
+    const size_t n = (size_t)c->S() * c->N;
+    DevBuf<double> db, dx;
+    HIP_TRY(c, db.alloc(n + 1));
+    HIP_TRY(c, dx.alloc(n + 1));
+    HIP_TRY(c, hipMemcpyAsync(db.p, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    rc = fh_cg_solve_matrix_free_dev(c, db.p, dx.p, preconditioner, rel_tol, max_iter, num_iterations);
     // like the reference's SolveError, the iterate reached so far is handed back on failure
     HIP_TRY(c, hipMemcpyAsync(x, dx.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -517,3 +517,274 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
 
 // ---- Dirichlet helpers
 }  // extern "C"
+
+// ---- matrix-free operator: y = A x of the linear operators (LinearOperator::apply, fenris-sparse/src/cg.rs:16-18) and their diagonal,
+// without a pattern or values.  For FH_LAPLACE and FH_LINEAR_ELASTIC the element vector is linear in u, so the residual of the
+// operand IS  K x:  the element pass of the residual, fed x in place of the context's u.  On the tiles (Hex8, Tet4, Quad4, Tri3 without a
+// rule-set table) the node pass overwrites y, applies the Dirichlet rows on store and leaves the partials of x . y for CG; elsewhere the
+// residual kernels accumulate into a zeroed y and one more pass over y does the same.  Homogeneous Dirichlet nodes make the operator the
+// one fh_apply_dirichlet_csr_dev leaves (global.rs:379-451): the element pass reads x with their entries zeroed (their columns vanish),
+// their rows are  scale x.  LinearElastic: the element pass reads x 2^-e with |x 2^-e|_inf in [1/2, 1) (mf_exponent, device_common.hpp).
+int mf_ready(fh_ctx* c, const char* who) {
+    if (c->op > FH_LINEAR_ELASTIC)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": the matrix-free operator covers FH_LAPLACE and FH_LINEAR_ELASTIC only");
+    const int rc = check_ready(c, who, false);
+    if (rc) return rc;
+    if (c->S() < 1 || c->S() > 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": solution dim must be 1..3");
+    return FH_OK;
+}
+
+static bool mf_tiles(fh_ctx* c) {
+    return !c->rs.active && element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->env("FENRIS_HIP_NO_VECTOR_TILES");
+}
+
+// what the scale of the Dirichlet rows depends on: mesh, vertices, operator, quadrature table and parameters, element mask (the setters of
+// the last three move struct_gen) -- not on which nodes are constrained
+static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[3]) {
+    k[0] = c->struct_gen;
+    k[1] = c->topo_gen;
+    k[2] = c->geom_gen;
+}
+
+// the scale of the Dirichlet rows into c->mf_scale, from the unmodified diagonal (diag_dev)
+static int mf_scale_from(fh_ctx* c, const double* diag_dev) {
+    const int n = c->S() * (int)c->N;
+    DevBuf<unsigned long long> first;
+    HIP_TRY(c, first.alloc(1));
+    if (!c->mf_scale.p) HIP_TRY(c, c->mf_scale.alloc(1));
+    HIP_TRY(c, hipMemsetAsync(first.p, 0xff, sizeof(unsigned long long), c->stream));
+    if (n) hipLaunchKernelGGL(k_mf_first_nonzero, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, diag_dev, first.p);
+    hipLaunchKernelGGL(k_mf_scale, dim3(1), dim3(64), 0, c->stream, diag_dev, first.p, c->mf_scale.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (first is released on return)
+    return FH_OK;
+}
+
+// one quadrature table (or one group of a rule-set table): the element diagonals ADDED to out
+static int mf_diagonal_single(fh_ctx* c, double* out, uint64_t* failed) {
+    int rc = reset_status(c);
+    if (rc) return rc;
+    if (c->E == 0) return FH_OK;
+    KArgs a;
+    fill_common(c, a);
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    const int S = c->S();
+    if (element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->env("FENRIS_HIP_NO_VECTOR_TILES")) {
+        rc = ensure_vector_tiles(c);
+        if (rc) return rc;
+        if (!c->vt_bad) {
+            const size_t need = (size_t)c->vt.v.npartials * S;
+            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+            if (vector_tiles_diagonal_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p) == 0) {
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, out));
+                return read_status(c, failed);
+            }
+        }
+    }
+    // any element kind: element diagonals by local node, then one thread per node over its (element, local node) entries in order
+    rc = build_source_adjacency(c);
+    if (rc) return rc;
+    DevBuf<double> fe;
+    HIP_TRY(c, fe.alloc((size_t)c->E * c->ei.n * S));
+    const int grid = (int)((c->E + 255) / 256);
+    const int D = c->ei.d;
+#define DG(DV, SV, OPV) hipLaunchKernelGGL((k_mf_diagonal_elements<DV, SV, OPV>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe.p)
+    if (c->op == FH_LAPLACE) { if (D == 2) DG(2, 1, FH_LAPLACE); else DG(3, 1, FH_LAPLACE); }
+    else { if (D == 2) DG(2, 2, FH_LINEAR_ELASTIC); else DG(3, 3, FH_LINEAR_ELASTIC); }
+#undef DG
+    HIP_TRY(c, hipGetLastError());
+    rc = launch_vector_from_elements_soa(c, S, fe.p, out, c->src_n2e_off.p, c->src_n2e.p);
+    if (rc) return rc;
+    return read_status(c, failed);   // (synchronises: fe is released on return)
+}
+
+// the diagonal of A into diag_dev; with_scale: and, with Dirichlet nodes set, the scale of their rows (c->mf_scale) and their diagonal = scale
+int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale) {
+    const int n = c->S() * (int)c->N;
+    HIP_TRY(c, hipMemsetAsync(diag_dev, 0, sizeof(double) * (size_t)n, c->stream));
+    uint64_t failed = 0;
+    int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_diagonal_single(c, diag_dev, f); })
+                          : mf_diagonal_single(c, diag_dev, &failed);
+    if (rc) return rc;
+    if (c->mf_num_dirichlet && with_scale) {
+        rc = mf_scale_from(c, diag_dev);
+        if (rc) return rc;
+        mf_scale_key_now(c, c->mf_scale_key);
+        hipLaunchKernelGGL(k_mf_dirichlet_diag, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->S(), c->mf_dmask.p, c->mf_scale.p, diag_dev);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FH_OK;
+}
+
+// one quadrature table (or one group of a rule-set table): the element vectors of the operand xin ADDED to y -- the tiles where they
+// exist (the residual's element pass fed xin), else k_mf_apply_elements by local node and one thread per node over its entries in order
+static int mf_apply_single(fh_ctx* c, const double* xin, double* y, uint64_t* failed) {
+    int rc = reset_status(c);
+    if (rc) return rc;
+    if (c->E == 0) return FH_OK;
+    KArgs a;
+    fill_common(c, a);
+    a.u = xin;
+    a.work_begin = 0;
+    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    const int S = c->S();
+    if (element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->env("FENRIS_HIP_NO_VECTOR_TILES")) {
+        rc = ensure_vector_tiles(c);
+        if (rc) return rc;
+        if (!c->vt_bad) {
+            const size_t need = (size_t)c->vt.v.npartials * S;
+            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+            if (vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p) == 0) {
+                HIP_TRY(c, hipGetLastError());
+                c->last_kernel = "k_element_pass_tiled + k_vector_from_partials";
+                HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, y));
+                return read_status(c, failed);
+            }
+        }
+    }
+    rc = build_source_adjacency(c);
+    if (rc) return rc;
+    const size_t need = (size_t)c->E * c->ei.n * S;
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    const int grid = (int)((c->E + 255) / 256);
+    const int D = c->ei.d;
+#define AP(DV, SV, OPV) hipLaunchKernelGGL((k_mf_apply_elements<DV, SV, OPV>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, xin, c->fe_scratch.p)
+    if (c->op == FH_LAPLACE) { if (D == 2) AP(2, 1, FH_LAPLACE); else AP(3, 1, FH_LAPLACE); }
+    else { if (D == 2) AP(2, 2, FH_LINEAR_ELASTIC); else AP(3, 3, FH_LINEAR_ELASTIC); }
+#undef AP
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_mf_apply_elements + k_vector_from_elements_soa";
+    rc = launch_vector_from_elements_soa(c, S, c->fe_scratch.p, y, c->src_n2e_off.p, c->src_n2e.p);
+    if (rc) return rc;
+    return read_status(c, failed);
+}
+
+// y = A x.  The scale of the Dirichlet rows must be in c->mf_scale (mf_diagonal).  dot_scratch != null: per-workgroup partials of x . y
+// go to it (*partials of them, in order).  Singular Jacobians land in the status slot: the caller resets and reads it.
+int mf_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials) {
+    const int S = c->S(), N = (int)c->N, n = S * N;
+    const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
+    const double* xin = x;
+    const unsigned long long* xbits = nullptr;
+    if (c->op == FH_LINEAR_ELASTIC) {   // the operand scaled to |x|_inf in [1/2, 1) over the free entries (mf_exponent)
+        if (!c->mf_bits.p) HIP_TRY(c, c->mf_bits.alloc(1));
+        HIP_TRY(c, hipMemsetAsync(c->mf_bits.p, 0, sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_mf_absmax, dim3(std::max(1, std::min(1024, (n + 255) / 256))), dim3(256), 0, c->stream, n, S, x, dmask, c->mf_bits.p);
+        xbits = c->mf_bits.p;
+    }
+    if (dmask || xbits) {
+        if (c->mf_xm.n < (size_t)n) HIP_TRY(c, c->mf_xm.alloc((size_t)n));
+        hipLaunchKernelGGL(k_mf_operand, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, S, x, dmask, xbits, c->mf_xm.p);
+        HIP_TRY(c, hipGetLastError());
+        xin = c->mf_xm.p;
+    }
+    if (c->E > 0 && mf_tiles(c)) {
+        int rc = ensure_vector_tiles(c);
+        if (rc) return rc;
+        if (!c->vt_bad) {
+            const size_t need = (size_t)c->vt.v.npartials * S;
+            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+            KArgs a;
+            fill_common(c, a);
+            a.u = xin;
+            a.work_begin = 0;
+            a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
+            if (vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, c->has_mask ? c->active.p : nullptr, c->fe_scratch.p) == 0) {
+                HIP_TRY(c, hipGetLastError());
+                const int g = vector_tiles_operator_partials(N);
+                double* dp = nullptr;
+                if (dot_scratch) {
+                    if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+                    dp = dot_scratch->p;
+                    *partials = g;
+                }
+                c->last_kernel = "k_element_pass_tiled + k_operator_from_partials";
+                HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp));
+                return FH_OK;
+            }
+        }
+    }
+    // elsewhere (kinds outside the tiles, rule-set groups, no tile tables): the element vectors of the operand accumulated into y = 0 without
+    // atomics, group by group; then the scale, the Dirichlet rows and the partials of x . y
+    HIP_TRY(c, hipMemsetAsync(y, 0, sizeof(double) * (size_t)n, c->stream));
+    uint64_t failed = 0;
+    const int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_apply_single(c, xin, y, f); })
+                                : mf_apply_single(c, xin, y, &failed);
+    if (rc) return rc;
+    const int g = (n + 255) / 256;
+    double* dp = nullptr;
+    if (dot_scratch) {
+        if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+        dp = dot_scratch->p;
+        *partials = g;
+    }
+    if (dmask || dp || xbits) {
+        hipLaunchKernelGGL(k_mf_finish, dim3(g), dim3(256), 0, c->stream, n, S, x, dmask, c->mf_scale.p, xbits, y, dp);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FH_OK;
+}
+
+extern "C" {
+
+int fh_set_operator_dirichlet_nodes(fh_ctx* c, const uint64_t* nodes, uint64_t num_nodes) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, "fh_set_operator_dirichlet_nodes: no finite element mesh set");
+    if (num_nodes && !nodes) return c->fail(FH_BAD_ARGUMENT, "fh_set_operator_dirichlet_nodes: null node list");
+    for (uint64_t i = 0; i < num_nodes; ++i)
+        if (nodes[i] >= c->N) return c->fail(FH_BAD_ARGUMENT, "Dirichlet node out of range");
+    c->mf_num_dirichlet = 0;   // (the scale does not depend on which nodes are constrained: mf_scale stays valid)
+    if (!nodes || num_nodes == 0) return FH_OK;
+    DevBuf<unsigned long long> dn;
+    HIP_TRY(c, c->mf_dmask.alloc((size_t)c->N + 1));
+    HIP_TRY(c, dn.alloc((size_t)num_nodes));
+    HIP_TRY(c, hipMemsetAsync(c->mf_dmask.p, 0, (size_t)c->N + 1, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dn.p, nodes, sizeof(uint64_t) * num_nodes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_mark_nodes, dim3(grid_for((long long)num_nodes, 256, 1 << 30)), dim3(256), 0, c->stream, dn.p, (long long)num_nodes, c->mf_dmask.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dn is released on return)
+    c->mf_num_dirichlet = num_nodes;
+    return FH_OK;
+}
+
+int fh_apply_operator_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    int rc = mf_ready(c, "fh_apply_operator_dev");
+    if (rc) return rc;
+    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, "fh_apply_operator_dev: null argument");
+    if (c->N == 0) return FH_OK;
+    unsigned long long key[3];
+    mf_scale_key_now(c, key);
+    if (c->mf_num_dirichlet && (key[0] != c->mf_scale_key[0] || key[1] != c->mf_scale_key[1] || key[2] != c->mf_scale_key[2])) {
+        // the scale of the Dirichlet rows comes from the diagonal: formed again only when what it depends on has changed
+        DevBuf<double> diag;
+        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
+        rc = mf_diagonal(c, diag.p, true);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    rc = reset_status(c);
+    if (rc) return rc;
+    rc = mf_apply(c, x_dev, y_dev, nullptr, nullptr);
+    if (rc) return rc;
+    return read_status(c, nullptr);
+}
+
+int fh_operator_diagonal_dev(fh_ctx* c, double* diag_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    int rc = mf_ready(c, "fh_operator_diagonal_dev");
+    if (rc) return rc;
+    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, "fh_operator_diagonal_dev: null argument");
+    if (c->N == 0) return FH_OK;
+    rc = mf_diagonal(c, diag_dev, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FH_OK;
+}
+
+}  // extern "C"

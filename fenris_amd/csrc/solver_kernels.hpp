@@ -297,4 +297,217 @@ __global__ void __launch_bounds__(256) k_error_squared(const KArgs a, const Sour
     block_sum_store<1>(s, partial + blockIdx.x);
 }
 
+// ---- matrix-free operator (engine_vector.hip): the generic parts; the tiles' passes are in vector_tiles.hip
+
+// d = 1 / d (the matrix-free Jacobi preconditioner)
+static __global__ void __launch_bounds__(256) k_reciprocal(int n, double* d) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) d[i] = 1.0 / d[i];
+}
+
+// |x|_inf over the entries the element pass sees (those of Dirichlet nodes excluded; dmask may be null) as the bits of a non-negative
+// double (an integer maximum: order-free); *bits must be zero on entry
+static __global__ void __launch_bounds__(256) k_mf_absmax(int n, int S, const double* x, const unsigned char* dmask, unsigned long long* bits) {
+    __shared__ unsigned long long red[256];
+    unsigned long long m = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        if (!dmask || !dmask[i / S]) m = max(m, (unsigned long long)__double_as_longlong(fabs(x[i])));
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = max(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicMax(bits, red[0]);
+}
+
+// the operand of the element pass: x 2^-e (mf_exponent), the entries of the Dirichlet nodes (dmask may be null) zeroed so that their columns vanish
+static __global__ void __launch_bounds__(256) k_mf_operand(int n, int S, const double* x, const unsigned char* dmask, const unsigned long long* bits,
+                                                           double* xm) {
+    const int e = mf_exponent(bits);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        xm[i] = (dmask && dmask[i / S]) ? 0.0 : ldexp(x[i], -e);
+}
+
+// node sums times 2^e (mf_exponent), rows of the Dirichlet nodes = scale x (dmask may be null), and the per-workgroup partials of x . y (dot_partial may be null)
+static __global__ void __launch_bounds__(256) k_mf_finish(int n, int S, const double* x, const unsigned char* dmask, const double* scale,
+                                                          const unsigned long long* bits, double* y, double* dot_partial) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double d[1] = {0.0};
+    if (i < n) {
+        const double yv = (dmask && dmask[i / S]) ? *scale * x[i] : ldexp(y[i], mf_exponent(bits));
+        y[i] = yv;
+        d[0] = x[i] * yv;
+    }
+    if (dot_partial) block_sum_store<1>(d, dot_partial + blockIdx.x);
+}
+
+// the scale of the Dirichlet rows, as apply_homogeneous_dirichlet_bc_csr takes it (global.rs:379-451): |first nonzero diagonal entry| in row
+// order, or 1.  First pass: the lowest row with a nonzero entry (an integer minimum: order-free); second: the scale
+static __global__ void __launch_bounds__(256) k_mf_first_nonzero(int n, const double* diag, unsigned long long* first) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && diag[i] != 0.0) atomicMin(first, (unsigned long long)i);
+}
+static __global__ void k_mf_scale(const double* diag, const unsigned long long* first, double* scale) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *scale = *first == ~0ull ? 1.0 : fabs(diag[*first]);
+}
+static __global__ void __launch_bounds__(256) k_mf_dirichlet_diag(int n, int S, const unsigned char* dmask, const double* scale, double* diag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && dmask[i / S]) diag[i] = *scale;
+}
+
+// diagonal of the element matrices of any element kind (the kinds outside the tiles: Hex27, Tet10, Quad9, Tri6, Hex20, Tet20), one
+// thread per element, the tables walked at run time like k_error_squared: J from the geometry vertices, g_a = J^-T ghat_a, entries as
+// diagonal_element_body (element_pass.hpp).  fe[a][e][c] for k_vector_from_elements_soa; inactive elements (active[e] == 0) write zeros.
+template <int D, int S, int OP>
+__global__ void __launch_bounds__(256) k_mf_diagonal_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.num_elements) return;
+    const bool live = !active || active[e] != 0;
+    const int* nodes = a.conn + (size_t)e * N;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    for (int n = 0; n < N; ++n) {
+        double acc[S];
+#pragma unroll
+        for (int k = 0; k < S; ++k) acc[k] = 0.0;
+        for (int q = 0; q < a.nq && live; ++q) {
+            double J[D][D];
+#pragma unroll
+            for (int r = 0; r < D; ++r)
+#pragma unroll
+                for (int c = 0; c < D; ++c) J[r][c] = 0.0;
+            for (int g = 0; g < NG; ++g) {
+                const double* v = a.verts + (size_t)nodes[g] * D;
+                const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
+#pragma unroll
+                for (int r = 0; r < D; ++r)
+#pragma unroll
+                    for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
+            }
+            const double detJ = det_small<D>(J);
+            if (detJ == 0.0) {
+                if (n == 0) report_singular(a.status, e);
+                continue;
+            }
+            double Ji[D][D];
+            inv_small(J, detJ, Ji);
+            const double s = a.qw[q] * fabs(detJ);
+            double mu = 0.0, lambda = 0.0;
+            if (OP != FH_LAPLACE) {
+                if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
+                else { mu = a.qparams[2 * q]; lambda = a.qparams[2 * q + 1]; }
+            }
+            const double* gr = a.gref + ((size_t)q * N + n) * D;
+            double g[D], gsq = 0.0;
+#pragma unroll
+            for (int r = 0; r < D; ++r) {
+                double t = 0.0;
+#pragma unroll
+                for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
+                g[r] = t;
+                gsq = fma(t, t, gsq);
+            }
+            if constexpr (OP == FH_LAPLACE) {
+                acc[0] = fma(s, gsq, acc[0]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < S; ++k) acc[k] = fma(s, mu * (gsq + g[k] * g[k]) + lambda * (g[k] * g[k]), acc[k]);
+            }
+        }
+        double* dst = fe + ((size_t)n * (size_t)a.num_elements + (size_t)e) * S;
+#pragma unroll
+        for (int k = 0; k < S; ++k) dst[k] = acc[k];
+    }
+}
+
+// y = A x for any element kind, deterministic (the kinds outside the tiles, rule-set groups, a mesh without tile tables): one thread per
+// element, the tables walked at run time like k_mf_diagonal_elements; grad u = J^-T sum_n ghat_n u_n^T, the linear stress formed from grad u
+// directly (Laplace: grad u; LinearElastic: 2 mu sym(grad u) + lambda tr(grad u) I -- the terms of material_point without F), element
+// vectors f_n = w |det J| P g_n by local node, fe[a][e][c], for k_vector_from_elements_soa.  Inactive elements write zeros.
+template <int D, int S, int OP>
+__global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N, int NG, const unsigned char* active, const double* x, double* fe) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.num_elements) return;
+    const bool live = !active || active[e] != 0;
+    const int* nodes = a.conn + (size_t)e * N;
+    auto out = [&](int n) { return fe + ((size_t)n * (size_t)a.num_elements + (size_t)e) * S; };
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) out(n)[k] = 0.0;
+    if (!live) return;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    for (int q = 0; q < a.nq; ++q) {
+        double J[D][D];
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+            for (int c = 0; c < D; ++c) J[r][c] = 0.0;
+        for (int g = 0; g < NG; ++g) {
+            const double* v = a.verts + (size_t)nodes[g] * D;
+            const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
+#pragma unroll
+            for (int r = 0; r < D; ++r)
+#pragma unroll
+                for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
+        }
+        const double detJ = det_small<D>(J);
+        if (detJ == 0.0) {
+            report_singular(a.status, e);
+            continue;
+        }
+        double Ji[D][D];
+        inv_small(J, detJ, Ji);
+        const double s = a.qw[q] * fabs(detJ);
+        auto grad = [&](int n, double (&g)[D]) {
+            const double* gr = a.gref + ((size_t)q * N + n) * D;
+#pragma unroll
+            for (int r = 0; r < D; ++r) {
+                double t = 0.0;
+#pragma unroll
+                for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
+                g[r] = t;
+            }
+        };
+        double gu[D][S];
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+            for (int k = 0; k < S; ++k) gu[r][k] = 0.0;
+        for (int n = 0; n < N; ++n) {
+            double g[D];
+            grad(n, g);
+#pragma unroll
+            for (int r = 0; r < D; ++r)
+#pragma unroll
+                for (int k = 0; k < S; ++k) gu[r][k] = fma(g[r], x[(size_t)nodes[n] * S + k], gu[r][k]);
+        }
+        double P[S][D];
+        if constexpr (OP == FH_LAPLACE) {
+#pragma unroll
+            for (int r = 0; r < D; ++r) P[0][r] = gu[r][0];
+        } else {
+            const double mu = par_e ? par_e[2 * q] : a.qparams[2 * q], lambda = par_e ? par_e[2 * q + 1] : a.qparams[2 * q + 1];
+            double tr = 0.0;
+#pragma unroll
+            for (int i = 0; i < D; ++i) tr += gu[i][i];
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) P[i][j] = mu * (gu[i][j] + gu[j][i]) + (i == j ? lambda * tr : 0.0);
+        }
+        for (int n = 0; n < N; ++n) {
+            double g[D];
+            grad(n, g);
+            double* o = out(n);
+#pragma unroll
+            for (int i = 0; i < S; ++i) {
+                double t = 0.0;
+#pragma unroll
+                for (int r = 0; r < D; ++r) t = fma(P[i][r], g[r], t);
+                o[i] = fma(s, t, o[i]);
+            }
+        }
+    }
+}
+
 }  // namespace fenris_hip

@@ -418,6 +418,81 @@ __global__ void __launch_bounds__(256) k_vector_from_partials(int num_nodes, con
     }
 }
 
+// diagonal of a linear operator (diagonal_element_body) over the tiles: the tile's node sums, partials; k_vector_from_partials adds them
+template <int EK, int OP, int TS>
+__global__ void __launch_bounds__(TS) k_diagonal_tiled(const KArgs a, const VecTiles t, const unsigned char* active, double* partial) {
+    constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
+    __shared__ double stage[N * S * TS];
+    __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
+    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
+    if (tile >= t.ntiles) return;
+    const int el = t.elem[(size_t)tile * TS + tid];
+    const bool live = el >= 0 && (!active || active[el] != 0);
+    TileSums<N, TS> ts;
+    ts.request(t, tile, tid);
+    double X[N][D];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
+#pragma unroll
+        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
+    }
+    double f[N][S];
+    diagonal_element_body<D, S, N, OP>(a, el >= 0 ? el : 0, live, X, f);
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
+    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+}
+
+// node pass of the matrix-free operator y = A x: y[S node + c] = sum of the node's partials in ascending order, OVERWRITTEN (not added).
+// dmask (may be null): homogeneous Dirichlet nodes, whose rows hold  scale x  (the element pass saw x with those entries zeroed, so
+// their columns are zero already); the element pass saw x 2^-e (xbits: mf_exponent), the sums are scaled back.  dot_partial (may be null): per workgroup  x . y  over its nodes, in a fixed tree.
+template <int S>
+__global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* partial,
+                                                                const double* x, const unsigned char* dmask, const double* scale,
+                                                                const unsigned long long* xbits, double* y, double* dot_partial) {
+    __shared__ double red[4];
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    const int ex = mf_exponent(xbits);
+    double dot = 0.0;
+    if (node < num_nodes) {
+        double acc[S];
+#pragma unroll
+        for (int c = 0; c < S; ++c) acc[c] = 0.0;
+        const unsigned k0 = np_off[node], k1 = np_off[node + 1];
+        for (unsigned kb = k0; kb < k1; kb += 4) {     // (k_vector_from_partials' loads: four partials in flight, the additions in order)
+            unsigned v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
+            double xp[4][S];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int c = 0; c < S; ++c) xp[j][c] = partial[(size_t)v[j] * S + c];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (kb + j < k1) {
+#pragma unroll
+                    for (int c = 0; c < S; ++c) acc[c] += xp[j][c];
+                }
+        }
+        const bool fixed = dmask && dmask[node];
+#pragma unroll
+        for (int c = 0; c < S; ++c) {
+            const double xv = x[(size_t)node * S + c];
+            const double yv = fixed ? *scale * xv : ldexp(acc[c], ex);
+            y[(size_t)node * S + c] = yv;
+            dot = fma(xv, yv, dot);
+        }
+    }
+    if (dot_partial) {
+        const double tot = block_sum_256(dot, red);
+        if (threadIdx.x == 0) dot_partial[blockIdx.x] = tot;
+    }
+}
+
 template <typename T>
 hipError_t vt_alloc(VecTilesStore* st, int slot, T** p, size_t count) {
     hipError_t e = hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (count ? count : 1));
@@ -640,6 +715,34 @@ hipError_t vector_tiles_node_pass(hipStream_t stream, int S, int num_nodes, cons
     if (S == 1) hipLaunchKernelGGL((k_vector_from_partials<1, 0>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out);
     else if (S == 2) hipLaunchKernelGGL((k_vector_from_partials<2, 0>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out);
     else hipLaunchKernelGGL((k_vector_from_partials<3, 0>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out);
+    return hipGetLastError();
+}
+
+int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial) {
+    const dim3 g(8 * ((t.ntiles + 7) / 8));
+#define VT_DG(EKC)                                                                                                                   \
+    switch (op) {                                                                                                                    \
+        case FH_LAPLACE: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_LAPLACE, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
+        case FH_LINEAR_ELASTIC: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_LINEAR_ELASTIC, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
+        default: return -1;                                                                                                          \
+    }
+    switch (elem_kind) {
+        case FH_QUAD4: VT_DG(FH_QUAD4)
+        case FH_TRI3: VT_DG(FH_TRI3)
+        case FH_TET4: VT_DG(FH_TET4)
+        case FH_HEX8: VT_DG(FH_HEX8)
+        default: return -1;
+    }
+#undef VT_DG
+}
+
+hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
+                                           const unsigned char* dmask, const double* scale, const unsigned long long* xbits, double* y,
+                                           double* dot_partial) {
+    const int grid = vector_tiles_operator_partials(num_nodes);
+    if (S == 1) hipLaunchKernelGGL((k_operator_from_partials<1>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, xbits, y, dot_partial);
+    else if (S == 2) hipLaunchKernelGGL((k_operator_from_partials<2>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, xbits, y, dot_partial);
+    else hipLaunchKernelGGL((k_operator_from_partials<3>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, xbits, y, dot_partial);
     return hipGetLastError();
 }
 

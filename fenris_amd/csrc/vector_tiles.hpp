@@ -52,4 +52,16 @@ int vector_tiles_source_pass(int D, int sdim, int n, bool fact, hipStream_t stre
 hipError_t vector_tiles_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, double* out,
                                   const double* scaled_g = nullptr);
 
+// diagonal of the linear operators (FH_LAPLACE, FH_LINEAR_ELASTIC; diagonal_element_body) over the tiles into partial[P][S]; the
+// caller sums them with vector_tiles_node_pass.  Returns -1 when (elem_kind, op) is not covered.
+int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial);
+
+// node pass of the matrix-free operator: y = the node sums of the partials, OVERWRITTEN; rows of the nodes with dmask[node] != 0
+// (dmask, scale: device, may be null / unused) are  *scale x; the other rows are multiplied by 2^e (xbits: mf_exponent, may be null).  dot_partial (may be null): one partial of x . y per workgroup
+// (vector_tiles_operator_partials of them), to be summed in index order.
+inline int vector_tiles_operator_partials(int num_nodes) { return (num_nodes + 255) / 256; }
+hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
+                                           const unsigned char* dmask, const double* scale, const unsigned long long* xbits, double* y,
+                                           double* dot_partial);
+
 }  // namespace fenris_hip

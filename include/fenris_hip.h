@@ -376,6 +376,31 @@ int fh_cg_solve(fh_ctx*, const double* values, const double* b, double* x, int p
                 uint64_t max_iter, uint64_t* num_iterations);
 int fh_cg_solve_dev(fh_ctx*, const double* values_dev, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
                     uint64_t max_iter, uint64_t* num_iterations);
+/* ---- matrix-free operator: LinearOperator (fenris-sparse/src/cg.rs:16-51) for FH_LAPLACE and FH_LINEAR_ELASTIC without a pattern
+ * or values.  The element vector of these operators is linear in u, so the residual's element pass fed x gives  A x = K x;  it honours
+ * the context's operator, quadrature table (uniform, per-point, compact, rule sets), element mask (fh_set_active_elements) and every
+ * element kind.  Other operators: FH_UNSUPPORTED.  Missing mesh, operator or quadrature table: FH_INVALID_STATE.
+ *
+ * fh_set_operator_dirichlet_nodes: homogeneous Dirichlet nodes of the operator (membership flags on the device; NULL / 0 clears them, and
+ * so does fh_set_mesh*).  With them, A is the matrix fh_apply_dirichlet_csr_dev leaves of the assembled K (global.rs:379-451): the rows and
+ * columns of the constrained dofs are zero and their diagonal is scale = |first nonzero diagonal entry| in row order, or 1. */
+int fh_set_operator_dirichlet_nodes(fh_ctx*, const uint64_t* nodes, uint64_t num_nodes);
+/* y = A x, both s N doubles on the device.  y is OVERWRITTEN (LinearOperator::apply, cg.rs:16-18); x may hold anything on the constrained
+ * dofs; the context's u (fh_set_u*) is neither read nor changed.  FH_SINGULAR_JACOBIAN as the residual reports it.  Deterministic
+ * on every element kind (no floating-point atomics: element vectors summed per node in a fixed order).  With Dirichlet nodes set, the
+ * scale comes from the diagonal, formed again only after the mesh, vertices, operator, table or element mask have changed. */
+int fh_apply_operator_dev(fh_ctx*, const double* x_dev, double* y_dev);
+/* the diagonal of A (s N doubles on the device), after the Dirichlet modification when nodes are set, without forming A: per point
+ * w |det J| |g_a|^2 (Laplace) or w |det J| (mu (|g_a|^2 + g_a,i^2) + lambda g_a,i^2) (LinearElastic) for dof (a, i), g_a the physical
+ * gradient of basis function a, summed in a fixed order like the residual. */
+int fh_operator_diagonal_dev(fh_ctx*, double* diag_dev);
+/* fh_cg_solve(_dev) with A the matrix-free operator: the same contract (RelativeResidualCriterion, error codes, the iterate handed back
+ * on failure, ordered reductions, bitwise reproducible); FH_PRECOND_JACOBI takes the inverse of fh_operator_diagonal_dev.  On the element
+ * kinds of the tiles (Hex8, Tet4, Quad4, Tri3) it allocates no pattern and no values. */
+int fh_cg_solve_matrix_free(fh_ctx*, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter,
+                            uint64_t* num_iterations);
+int fh_cg_solve_matrix_free_dev(fh_ctx*, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
+                                uint64_t* num_iterations);
 /* estimate_L2_error_squared / estimate_H1_seminorm_error_squared (src/error.rs:287-372):
  *   sum_e sum_q w |det J| |u_h(x_q) - u(x_q)|^2      resp.   |grad u_h(x_q) - grad u(x_q)|_F^2
  * with the quadrature table of the context.  The reference solution is arbitrary code in the reference; here the
