@@ -117,6 +117,10 @@ _SIGS = {
     "fh_operator_diagonal_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_cg_solve_matrix_free": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_cg_solve_matrix_free_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, u64p]),
+    "fh_apply_tangent_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fh_tangent_diagonal_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_cg_solve_tangent": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
+    "fh_cg_solve_tangent_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_estimate_L2_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),
     "fh_estimate_L2_error_squared_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, f64p]),
     "fh_estimate_H1_seminorm_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),

@@ -344,12 +344,26 @@ class Engine:
 
     def cg_solve_matrix_free(self, b, x, preconditioner=1, rel_tol=1e-9, max_iter=0):
         """fh_cg_solve_matrix_free(_dev): cg_solve with the matrix-free operator"""
+        return self._cg_solve_free("matrix_free", b, x, preconditioner, rel_tol, max_iter)
+
+    # matrix-free tangent T(u) = dr/du at the engine's u (every material), on the operator's Dirichlet nodes
+    def apply_tangent_dev(self, x_t, y_t):
+        self._check(self._lib.fh_apply_tangent_dev(self._h, C.c_void_p(x_t.data_ptr()), C.c_void_p(y_t.data_ptr())))
+
+    def tangent_diagonal_dev(self, diag_t):
+        self._check(self._lib.fh_tangent_diagonal_dev(self._h, C.c_void_p(diag_t.data_ptr())))
+
+    def cg_solve_tangent(self, b, x, preconditioner=1, rel_tol=1e-9, max_iter=0):
+        """fh_cg_solve_tangent(_dev): cg_solve with the matrix-free tangent"""
+        return self._cg_solve_free("tangent", b, x, preconditioner, rel_tol, max_iter)
+
+    def _cg_solve_free(self, which, b, x, preconditioner, rel_tol, max_iter):
         it = C.c_uint64(0)
         if _is_torch(b):
-            rc = self._lib.fh_cg_solve_matrix_free_dev(self._h, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), preconditioner,
-                                                       rel_tol, max_iter, C.byref(it))
+            rc = getattr(self._lib, f"fh_cg_solve_{which}_dev")(self._h, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), preconditioner,
+                                                                rel_tol, max_iter, C.byref(it))
         else:
-            rc = self._lib.fh_cg_solve_matrix_free(self._h, _ffi.fp(b), _ffi.fp(x), preconditioner, rel_tol, max_iter, C.byref(it))
+            rc = getattr(self._lib, f"fh_cg_solve_{which}")(self._h, _ffi.fp(b), _ffi.fp(x), preconditioner, rel_tol, max_iter, C.byref(it))
         if rc in (7, 8, 9):
             raise CgSolveError(rc, (self._lib.fh_last_error(self._h) or b"").decode(), int(it.value))
         self._check(rc)
@@ -931,13 +945,13 @@ class MatrixFreeOperator:
         """y = A x (y overwritten, like LinearOperator::apply)"""
         self._bind()
         if _is_torch(x):
-            self.engine.apply_operator_dev(x, y)
+            self._apply_dev(x, y)
             return y
         import torch
 
         xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(f"cuda:{self.engine.device}")
         yt = torch.empty_like(xt)
-        self.engine.apply_operator_dev(xt, yt)
+        self._apply_dev(xt, yt)
         y[...] = yt.cpu().numpy().reshape(np.shape(y))
         return y
 
@@ -948,13 +962,38 @@ class MatrixFreeOperator:
         self._bind()
         n = self.element_assembler.solution_dim() * self.engine.num_nodes()
         d = torch.empty(n, dtype=torch.float64, device=f"cuda:{self.engine.device}")
-        self.engine.operator_diagonal_dev(d)
+        self._diagonal_dev(d)
         return d if device else d.cpu().numpy()
 
     def cg_solve(self, b, x, preconditioner=1, rel_tol=1e-9, max_iter=0):
         """fh_cg_solve_matrix_free(_dev) on this operator; returns the iteration count"""
         self._bind()
+        return self._cg_solve(b, x, preconditioner, rel_tol, max_iter)
+
+    def _apply_dev(self, x_t, y_t):
+        self.engine.apply_operator_dev(x_t, y_t)
+
+    def _diagonal_dev(self, d_t):
+        self.engine.operator_diagonal_dev(d_t)
+
+    def _cg_solve(self, b, x, preconditioner, rel_tol, max_iter):
         return self.engine.cg_solve_matrix_free(b, x, preconditioner, rel_tol, max_iter)
+
+
+class MatrixFreeTangent(MatrixFreeOperator):
+    """The tangent T(u) = dr/du of an element assembler's residual at its current u (any material: Laplace, LinearElastic, NeoHookean,
+    StVK), applied without pattern or values: the matrix assemble_matrix forms for the same u, without forming it.  The interface of
+    MatrixFreeOperator (Dirichlet nodes owned by the object, apply on numpy arrays or device tensors, diagonal, cg_solve); its Jacobi
+    preconditioner takes the tangent's diagonal.  Changing the assembler's u (with_u) changes the operator."""
+
+    def _apply_dev(self, x_t, y_t):
+        self.engine.apply_tangent_dev(x_t, y_t)
+
+    def _diagonal_dev(self, d_t):
+        self.engine.tangent_diagonal_dev(d_t)
+
+    def _cg_solve(self, b, x, preconditioner, rel_tol, max_iter):
+        return self.engine.cg_solve_tangent(b, x, preconditioner, rel_tol, max_iter)
 
 
 class ConjugateGradient:
@@ -970,7 +1009,7 @@ class ConjugateGradient:
         return cls()
 
     def with_operator(self, csr, element_assembler=None):
-        """(csr, element_assembler): the assembled matrix; or one MatrixFreeOperator"""
+        """(csr, element_assembler): the assembled matrix; or one MatrixFreeOperator / MatrixFreeTangent"""
         if isinstance(csr, MatrixFreeOperator):
             self._csr, self._asm = csr, csr.element_assembler
         else:
@@ -994,7 +1033,7 @@ class ConjugateGradient:
         if self._csr is None or self._crit is None:
             raise ValueError("operator and stopping criterion are required")
         pre = 1 if isinstance(self._pre, JacobiPreconditioner) else 0
-        if isinstance(self._csr, MatrixFreeOperator):   # Jacobi: the matrix-free diagonal
+        if isinstance(self._csr, MatrixFreeOperator):   # Jacobi: the matrix-free diagonal (of the tangent for a MatrixFreeTangent)
             return self._csr.cg_solve(b, x, pre, self._crit.tol, self._max_iter)
         return self._asm.engine.cg_solve(self._csr.values, b, x, pre, self._crit.tol, self._max_iter)
 

@@ -818,6 +818,438 @@ __device__ __forceinline__ void diagonal_element_body(const KArgs& a, const long
     }
 }
 
+// ---- tangent of the residual, T(u) = dr/du at the context's u, applied without the matrix (engine_vector.hip).  Per point the element vector
+// of the operand x is  y_a += w |det J| dP(F)[H] g_a  with F = I + grad u^T, H = grad x^T (x enters linearly: I + grad x is never formed):
+//   Laplace        h
+//   LinearElastic  mu (H + H^T) + lambda tr(H) I
+//   NeoHookean     mu H + lambda tr(F^-1 H) F^-T + (mu - lambda ln J) F^-T H^T F^-T        (J <= 0: NaN, materials.rs:297-300)
+//   StVK           H S + F (lambda tr(dE) I + 2 mu dE),  S = lambda tr(E) I + 2 mu E,  dE = sym(F^T H)
+// which is  sum_b C(F; g_a, g_b) x_b  with C the stress contraction the assembled K(u) is made of (materials.rs:287-315 and 417-439).
+// TangentLin holds what depends on u alone (formed once per point); tangent_apply is linear in grad x.
+template <int OP, int D>
+struct TangentLin {
+    double mu, lambda, beta;   // NeoHookean: beta = mu - lambda ln J
+    double F[D][D];            // NeoHookean: F^-1; StVK: F
+    double Sg[D][D];           // StVK: the second Piola-Kirchhoff stress S
+};
+template <int OP, int D, int S>
+__device__ __forceinline__ void tangent_lin(const double (&gu)[D][S], double mu, double lambda, TangentLin<OP, D>& L) {
+    L.mu = mu;
+    L.lambda = lambda;
+    if constexpr (OP == FH_NEO_HOOKEAN || OP == FH_STVK) {
+        double F[D][D];   // F = I + (grad u)^T  (fenris-solid/src/lib.rs:20-29)
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + gu[j][i];
+        if constexpr (OP == FH_NEO_HOOKEAN) {
+            const double Jd = det_small<D>(F);
+            if (Jd <= 0.0) {
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j < D; ++j) L.F[i][j] = __builtin_nan("");
+                L.beta = __builtin_nan("");
+            } else {
+                inv_small(F, Jd, L.F);
+                L.beta = mu - lambda * log(Jd);
+            }
+        } else {
+            double trE = 0.0;
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) t = fma(F[k][i], F[k][j], t);
+                    L.Sg[i][j] = (t - (i == j ? 1.0 : 0.0)) * 0.5;   // E (green_strain_tensor)
+                    L.F[i][j] = F[i][j];
+                }
+#pragma unroll
+            for (int i = 0; i < D; ++i) trE += L.Sg[i][i];
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) L.Sg[i][j] = L.Sg[i][j] * 2.0 * mu + (i == j ? lambda * trE : 0.0);
+        }
+    }
+}
+// dP (s x d) from gx = grad x (d x s, gx[i][k] = d x_k / d X_i)
+template <int OP, int D, int S>
+__device__ __forceinline__ void tangent_apply(const TangentLin<OP, D>& L, const double (&gx)[D][S], double (&dP)[S][D]) {
+    if constexpr (OP == FH_LAPLACE) {
+#pragma unroll
+        for (int r = 0; r < D; ++r) dP[0][r] = gx[r][0];
+    } else if constexpr (OP == FH_LINEAR_ELASTIC) {
+        double tr = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) tr += gx[i][i];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) dP[i][j] = L.mu * (gx[j][i] + gx[i][j]) + (i == j ? L.lambda * tr : 0.0);
+    } else if constexpr (OP == FH_NEO_HOOKEAN) {
+        double A[D][D], tr = 0.0;   // A = F^-1 H
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) t = fma(L.F[i][k], gx[j][k], t);
+                A[i][j] = t;
+            }
+#pragma unroll
+        for (int i = 0; i < D; ++i) tr += A[i][i];
+        const double lt = L.lambda * tr;
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double b = 0.0;   // (F^-1 H F^-1)[j][i]
+#pragma unroll
+                for (int k = 0; k < D; ++k) b = fma(A[j][k], L.F[k][i], b);
+                dP[i][j] = fma(L.beta, b, fma(lt, L.F[j][i], L.mu * gx[j][i]));
+            }
+    } else {   // StVK
+        double C[D][D];   // F^T H
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) t = fma(L.F[k][i], gx[j][k], t);
+                C[i][j] = t;
+            }
+        double tr = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) tr += C[i][i];
+        double T[D][D];   // lambda tr(dE) I + 2 mu dE
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) T[i][j] = L.mu * (C[i][j] + C[j][i]) + (i == j ? L.lambda * tr : 0.0);
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) t = fma(gx[k][i], L.Sg[k][j], fma(L.F[i][k], T[k][j], t));
+                dP[i][j] = t;
+            }
+    }
+}
+template <int OP, int D, int S>
+__device__ __forceinline__ void tangent_params(const KArgs& a, const double* par_e, int q, double& mu, double& lambda) {
+    mu = 0.0;
+    lambda = 0.0;
+    if (OP != FH_LAPLACE) {
+        if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
+        else { mu = ep_const(a.qparams)[2 * q]; lambda = ep_const(a.qparams)[2 * q + 1]; }
+    }
+}
+
+// the tangent's element vector of one small iso-parametric element in the registers of one thread: vertex coordinates X, u (U) and the
+// operand (V) of its nodes; J per point from the reference-gradient table (the generic body's sums, elliptic.rs:398-422).  det J == 0 is
+// reported like the residual reports it and adds nothing.
+template <int D, int S, int N, int OP>
+__device__ __forceinline__ void tangent_element_body(const KArgs& a, const long long e, bool live, const double (&X)[N][D], const double (&U)[N][S],
+                                                     const double (&V)[N][S], double (&f)[N][S]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) f[n][k] = 0.0;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    for (int q = 0; q < a.nq; ++q) {
+        const ep_table G = ep_const(a.gref) + (size_t)q * N * D;
+        double J[D][D], Ji[D][D], Ru[D][S], Rv[D][S];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) J[i][j] = 0.0;
+#pragma unroll
+            for (int k = 0; k < S; ++k) { Ru[i][k] = 0.0; Rv[i][k] = 0.0; }
+        }
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const double g = G[n * D + j];
+#pragma unroll
+                for (int i = 0; i < D; ++i) J[i][j] = fma(X[n][i], g, J[i][j]);
+#pragma unroll
+                for (int k = 0; k < S; ++k) {
+                    Ru[j][k] = fma(g, U[n][k], Ru[j][k]);
+                    Rv[j][k] = fma(g, V[n][k], Rv[j][k]);
+                }
+            }
+        const double detJ = det_small<D>(J);
+        if (detJ == 0.0) {
+            if (live) report_singular(a.status, e);
+            continue;
+        }
+        inv_small(J, detJ, Ji);
+        const double s = ep_const(a.qw)[q] * fabs(detJ);
+        double gu[D][S], gx[D][S];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                double t = 0.0, t2 = 0.0;
+#pragma unroll
+                for (int m = 0; m < D; ++m) { t = fma(Ji[m][i], Ru[m][k], t); t2 = fma(Ji[m][i], Rv[m][k], t2); }
+                gu[i][k] = t;
+                gx[i][k] = t2;
+            }
+        double mu, lambda;
+        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        TangentLin<OP, D> L;
+        tangent_lin<OP, D, S>(gu, mu, lambda, L);
+        double dP[S][D], M[S][D];   // M = s dP J^-T
+        tangent_apply<OP, D, S>(L, gx, dP);
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int m = 0; m < D; ++m) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) t = fma(dP[i][k], Ji[m][k], t);
+                M[i][m] = s * t;
+            }
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int m = 0; m < D; ++m) {
+                const double g = G[n * D + m];
+#pragma unroll
+                for (int i = 0; i < S; ++i) f[n][i] = fma(M[i][m], g, f[n][i]);
+            }
+    }
+}
+
+// the tangent on Hex8 in the monomial basis (element_pass_body_hex8): both fields as monomial coefficients (9 FMAs per field and point for
+// the reference gradients), the output as the 21 moment sums and one synthesis butterfly per component.  AFF: every element of the mesh is a
+// parallelepiped (J once, the map's mixed coefficients dropped); otherwise J is formed once when every element of the wavefront is affine.
+// (The quadrature-free moment form does not apply: the integrand is not linear in u.)
+template <int OP, bool AFF>
+__device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long long e, const bool live, const double (&X)[8][3], const double (&U)[8][OpT<OP, 3>::S],
+                                                  const double (&V)[8][OpT<OP, 3>::S], double (&f)[8][OpT<OP, 3>::S]) {
+    constexpr int D = 3, N = 8, S = OpT<OP, 3>::S;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    double cx[D][8], cu[S][8], cv[S][8];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+        for (int n = 0; n < N; ++n) cx[i][hex8_bin(n)] = X[n][i];
+        hex8_wht(cx[i]);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) cx[i][k] *= 0.125;
+        if constexpr (AFF) { cx[i][3] = 0.0; cx[i][5] = 0.0; cx[i][6] = 0.0; cx[i][7] = 0.0; }
+    }
+#pragma unroll
+    for (int k2 = 0; k2 < S; ++k2) {
+#pragma unroll
+        for (int n = 0; n < N; ++n) { cu[k2][hex8_bin(n)] = U[n][k2]; cv[k2][hex8_bin(n)] = V[n][k2]; }
+        hex8_wht(cu[k2]);
+        hex8_wht(cv[k2]);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) { cu[k2][k] *= 0.125; cv[k2][k] *= 0.125; }
+    }
+    bool const_j = AFF;
+    if constexpr (!AFF) {
+        double len = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) len += fabs(X[1][i] - X[0][i]) + fabs(X[3][i] - X[0][i]) + fabs(X[4][i] - X[0][i]);
+        const double tol = len * 0x1p-46 * 0.125;
+        bool aff = true;
+#pragma unroll
+        for (int i = 0; i < D; ++i) aff = aff && fabs(cx[i][3]) <= tol && fabs(cx[i][5]) <= tol && fabs(cx[i][6]) <= tol && fabs(cx[i][7]) <= tol;
+        const_j = __all(aff ? 1 : 0) != 0;
+    }
+    auto grad = [](const double (&c)[8], double xi, double eta, double zeta, double ez, double xz, double xe, double (&g)[3]) {
+        g[0] = fma(c[7], ez, fma(c[5], zeta, fma(c[3], eta, c[1])));
+        g[1] = fma(c[7], xz, fma(c[6], zeta, fma(c[3], xi, c[2])));
+        g[2] = fma(c[7], xe, fma(c[6], eta, fma(c[5], xi, c[4])));
+    };
+    double J[D][D], Ji[D][D], adet = 0.0;
+    double dk[S][8];
+#pragma unroll
+    for (int i = 0; i < S; ++i)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) dk[i][t] = 0.0;
+    auto point = [&](int q, auto need_j_tag) {
+        constexpr bool need_j = decltype(need_j_tag)::value;
+        const ep_table Q = ep_const(a.qmono) + (size_t)q * 8;
+        const double xi = Q[0], eta = Q[1], zeta = Q[2], ez = Q[3], xz = Q[4], xe = Q[5];
+        if constexpr (need_j) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) grad(cx[i], xi, eta, zeta, ez, xz, xe, J[i]);
+            const double detJ = det_small<D>(J);
+            if (detJ == 0.0) {
+                if (live) report_singular(a.status, e);
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j < D; ++j) Ji[i][j] = 0.0;
+            } else {
+                inv_small(J, detJ, Ji);
+            }
+            adet = fabs(detJ);
+        }
+        double gu[D][S], gx[D][S];
+        {
+            double Ru[D][S], Rv[D][S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                double g[3], h[3];
+                grad(cu[k], xi, eta, zeta, ez, xz, xe, g);
+                grad(cv[k], xi, eta, zeta, ez, xz, xe, h);
+#pragma unroll
+                for (int j = 0; j < D; ++j) { Ru[j][k] = g[j]; Rv[j][k] = h[j]; }
+            }
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int k = 0; k < S; ++k) {
+                    double t = 0.0, t2 = 0.0;
+#pragma unroll
+                    for (int m = 0; m < D; ++m) { t = fma(Ji[m][i], Ru[m][k], t); t2 = fma(Ji[m][i], Rv[m][k], t2); }
+                    gu[i][k] = t;
+                    gx[i][k] = t2;
+                }
+        }
+        const double s = ep_const(a.qw)[q] * adet;
+        double mu, lambda;
+        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        TangentLin<OP, D> L;
+        tangent_lin<OP, D, S>(gu, mu, lambda, L);
+        double dP[S][D];
+        tangent_apply<OP, D, S>(L, gx, dP);
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            double Mi[D];
+#pragma unroll
+            for (int m = 0; m < D; ++m) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) t = fma(dP[i][k], Ji[m][k], t);
+                Mi[m] = s * t;
+            }
+            dk[i][1] += Mi[0];
+            dk[i][2] += Mi[1];
+            dk[i][4] += Mi[2];
+            dk[i][3] = fma(Mi[1], xi, fma(Mi[0], eta, dk[i][3]));
+            dk[i][5] = fma(Mi[2], xi, fma(Mi[0], zeta, dk[i][5]));
+            dk[i][6] = fma(Mi[2], eta, fma(Mi[1], zeta, dk[i][6]));
+            dk[i][7] = fma(Mi[2], xe, fma(Mi[1], xz, fma(Mi[0], ez, dk[i][7])));
+        }
+    };
+    if (const_j) {   // uniform over the wavefront
+        point(0, std::true_type{});
+        for (int q = 1; q < a.nq; ++q) point(q, std::false_type{});
+    } else {
+        for (int q = 0; q < a.nq; ++q) point(q, std::true_type{});
+    }
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        double d[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) d[t] = dk[i][t];
+#pragma unroll
+        for (int ax = 1; ax < 8; ax <<= 1)
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                if (!(b & ax)) {
+                    const double ev = d[b], od = d[b | ax];
+                    d[b] = ev - od;
+                    d[b | ax] = ev + od;
+                }
+#pragma unroll
+        for (int n = 0; n < N; ++n) f[n][i] = 0.125 * d[hex8_bin(n)];
+    }
+}
+
+// diagonal of one element's tangent: entry (a, i) = s (dP(F)[e_i g_a^T] g_a)_i per point, e.g. NeoHookean s ((lambda - alpha) (F^-T g_a)_i^2 +
+// mu |g_a|^2) with alpha = -mu + lambda ln J.  det J == 0 as in diagonal_element_body.
+template <int D, int S, int N, int OP>
+__device__ __forceinline__ void tangent_diagonal_body(const KArgs& a, const long long e, bool live, const double (&X)[N][D], const double (&U)[N][S],
+                                                      double (&f)[N][S]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) f[n][k] = 0.0;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    for (int q = 0; q < a.nq; ++q) {
+        const ep_table G = ep_const(a.gref) + (size_t)q * N * D;
+        double J[D][D], Ji[D][D], Ru[D][S];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) J[i][j] = 0.0;
+#pragma unroll
+            for (int k = 0; k < S; ++k) Ru[i][k] = 0.0;
+        }
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const double g = G[n * D + j];
+#pragma unroll
+                for (int i = 0; i < D; ++i) J[i][j] = fma(X[n][i], g, J[i][j]);
+#pragma unroll
+                for (int k = 0; k < S; ++k) Ru[j][k] = fma(g, U[n][k], Ru[j][k]);
+            }
+        const double detJ = det_small<D>(J);
+        if (detJ == 0.0) {
+            if (live) report_singular(a.status, e);
+            continue;
+        }
+        inv_small(J, detJ, Ji);
+        const double s = ep_const(a.qw)[q] * fabs(detJ);
+        double gu[D][S];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                double t = 0.0;
+#pragma unroll
+                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], Ru[m][k], t);
+                gu[i][k] = t;
+            }
+        double mu, lambda;
+        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        TangentLin<OP, D> L;
+        tangent_lin<OP, D, S>(gu, mu, lambda, L);
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            double g[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                double t = 0.0;
+#pragma unroll
+                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], G[n * D + m], t);
+                g[i] = t;
+            }
+#pragma unroll
+            for (int c = 0; c < S; ++c) {
+                double gx[D][S], dP[S][D];
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int k = 0; k < S; ++k) gx[i][k] = k == c ? g[i] : 0.0;
+                tangent_apply<OP, D, S>(L, gx, dP);
+                double t = 0.0;
+#pragma unroll
+                for (int r = 0; r < D; ++r) t = fma(dP[c][r], g[r], t);
+                f[n][c] = fma(s, t, f[n][c]);
+            }
+        }
+    }
+}
+
 // partial sums in index order by one workgroup: thread t takes the partials t, t + 256, ... in order, then the fixed tree
 static __global__ void __launch_bounds__(256) k_sum_partials(const double* partial, int n, double* out) {
     __shared__ double red[4];

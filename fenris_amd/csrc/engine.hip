@@ -1082,6 +1082,7 @@ int fh_quadrature_rule_groups(const fh_ctx* c, uint64_t* num_groups) {
 
 static int set_u_common(fh_ctx* c, const double* u, hipMemcpyKind kind) {
     if (!c->has_mesh || c->ragged || c->op < 0) return c->fail(FH_INVALID_STATE, "fh_set_u: set mesh and operator first");
+    ++c->u_gen;
     if (!u) { c->has_u = false; return FH_OK; }
     const size_t len = (size_t)c->S() * c->N;
     if (c->u.n < len) HIP_TRY(c, c->u.alloc(len));

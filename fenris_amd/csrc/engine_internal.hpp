@@ -450,6 +450,10 @@ struct fh_ctx {
     DevBuf<unsigned long long> mf_bits;   // |operand|_inf (k_mf_absmax)
     unsigned long long mf_scale_key[3] = {~0ull, ~0ull, ~0ull};   // (struct_gen, topo_gen, geom_gen) mf_scale was formed for
     unsigned long long geom_gen = 0;   // counts fh_update_vertices calls
+    // matrix-free tangent (engine_vector.hip): the scale of the Dirichlet rows of T(u), kept apart from mf_scale (it depends on u too)
+    DevBuf<double> mt_scale;           // 1 double
+    unsigned long long mt_scale_key[4] = {~0ull, ~0ull, ~0ull, ~0ull};   // (struct_gen, topo_gen, geom_gen, u_gen) mt_scale was formed for
+    unsigned long long u_gen = 0;      // counts fh_set_u* calls
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -533,6 +537,10 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
 int mf_ready(fh_ctx* c, const char* who);
 int mf_apply(fh_ctx* c, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
 int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
+// matrix-free tangent T(u) = dr/du at the context's u (engine_vector.hip): the same three for it
+int mt_ready(fh_ctx* c, const char* who);
+int mt_apply(fh_ctx* c, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
+int mt_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
 
 // dispatch over (element kind, operator kind) -> template instantiation
 #define FH_FOR_ELEM_OP(EKV, OPV, CALL)                                             \

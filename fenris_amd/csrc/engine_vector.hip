@@ -788,3 +788,217 @@ int fh_operator_diagonal_dev(fh_ctx* c, double* diag_dev) {
 }
 
 }  // extern "C"
+
+// ---- matrix-free tangent: y = T(u) x with T(u) = dr/du at the context's u (the matrix fh_assemble_matrix forms for the same context), and
+// its diagonal, without a pattern or values, for every material.  The element pass gathers u and the operand per element and forms
+// dP(F)[grad x^T] per point (tangent_lin / tangent_apply, element_pass.hpp): x enters linearly, so no scaling of the operand is needed.
+// Same machinery as the operator above: tiles with k_operator_from_partials where they exist, else one thread per element and ordered
+// node sums; the operator's Dirichlet nodes, with the scale taken from the tangent's own diagonal (mt_scale, keyed on u as well).
+int mt_ready(fh_ctx* c, const char* who) {
+    if (c->op > FH_STVK)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": the matrix-free tangent covers FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN and FH_STVK");
+    const int rc = check_ready(c, who, false);
+    if (rc) return rc;
+    if (c->S() < 1 || c->S() > 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": solution dim must be 1..3");
+    return FH_OK;
+}
+
+static void mt_scale_key_now(const fh_ctx* c, unsigned long long (&k)[4]) {
+    k[0] = c->struct_gen;
+    k[1] = c->topo_gen;
+    k[2] = c->geom_gen;
+    k[3] = c->u_gen;
+}
+
+#define MT_FOR_OP(OPV, CALL)                                      \
+    switch (OPV) {                                                \
+        case FH_LAPLACE: CALL(FH_LAPLACE); break;                 \
+        case FH_LINEAR_ELASTIC: CALL(FH_LINEAR_ELASTIC); break;   \
+        case FH_NEO_HOOKEAN: CALL(FH_NEO_HOOKEAN); break;         \
+        default: CALL(FH_STVK); break;                            \
+    }
+
+// one quadrature table (or one group of a rule-set table): the element diagonals of the tangent ADDED to out
+static int mt_diagonal_single(fh_ctx* c, double* out, uint64_t* failed) {
+    int rc = reset_status(c);
+    if (rc) return rc;
+    if (c->E == 0) return FH_OK;
+    KArgs a;
+    fill_common(c, a);
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    const int S = c->S();
+    if (mf_tiles(c)) {
+        rc = ensure_vector_tiles(c);
+        if (rc) return rc;
+        if (!c->vt_bad) {
+            const size_t need = (size_t)c->vt.v.npartials * S;
+            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+            if (vector_tiles_tangent_diagonal_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p) == 0) {
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, out));
+                return read_status(c, failed);
+            }
+        }
+    }
+    rc = build_source_adjacency(c);
+    if (rc) return rc;
+    DevBuf<double> fe;
+    HIP_TRY(c, fe.alloc((size_t)c->E * c->ei.n * S));
+    const int grid = (int)((c->E + 255) / 256);
+    const int D = c->ei.d;
+#define MT_DG(OPC)                                                                                                                                      \
+    if (D == 2) hipLaunchKernelGGL((k_mf_tangent_diagonal_elements<2, OpT<OPC, 2>::S, OPC>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe.p); \
+    else hipLaunchKernelGGL((k_mf_tangent_diagonal_elements<3, OpT<OPC, 3>::S, OPC>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe.p)
+    MT_FOR_OP(c->op, MT_DG)
+#undef MT_DG
+    HIP_TRY(c, hipGetLastError());
+    rc = launch_vector_from_elements_soa(c, S, fe.p, out, c->src_n2e_off.p, c->src_n2e.p);
+    if (rc) return rc;
+    return read_status(c, failed);   // (synchronises: fe is released on return)
+}
+
+// the diagonal of T(u) into diag_dev; with_scale: and, with Dirichlet nodes set, the scale of their rows (c->mt_scale) and their diagonal = scale
+int mt_diagonal(fh_ctx* c, double* diag_dev, bool with_scale) {
+    const int n = c->S() * (int)c->N;
+    HIP_TRY(c, hipMemsetAsync(diag_dev, 0, sizeof(double) * (size_t)n, c->stream));
+    uint64_t failed = 0;
+    int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mt_diagonal_single(c, diag_dev, f); })
+                          : mt_diagonal_single(c, diag_dev, &failed);
+    if (rc) return rc;
+    if (c->mf_num_dirichlet && with_scale) {
+        DevBuf<unsigned long long> first;
+        HIP_TRY(c, first.alloc(1));
+        if (!c->mt_scale.p) HIP_TRY(c, c->mt_scale.alloc(1));
+        HIP_TRY(c, hipMemsetAsync(first.p, 0xff, sizeof(unsigned long long), c->stream));
+        if (n) hipLaunchKernelGGL(k_mf_first_nonzero, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, diag_dev, first.p);
+        hipLaunchKernelGGL(k_mf_scale, dim3(1), dim3(64), 0, c->stream, diag_dev, first.p, c->mt_scale.p);
+        hipLaunchKernelGGL(k_mf_dirichlet_diag, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->S(), c->mf_dmask.p, c->mt_scale.p, diag_dev);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (first is released on return)
+        mt_scale_key_now(c, c->mt_scale_key);
+    }
+    return FH_OK;
+}
+
+// one quadrature table (or one group of a rule-set table) off the tiles: the tangent's element vectors of the operand xin ADDED to y
+static int mt_apply_single(fh_ctx* c, const double* xin, double* y, uint64_t* failed) {
+    int rc = reset_status(c);
+    if (rc) return rc;
+    if (c->E == 0) return FH_OK;
+    KArgs a;
+    fill_common(c, a);
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    const int S = c->S();
+    rc = build_source_adjacency(c);
+    if (rc) return rc;
+    const size_t need = (size_t)c->E * c->ei.n * S;
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    const int grid = (int)((c->E + 255) / 256);
+    const int D = c->ei.d;
+#define MT_AP(OPC)                                                                                                                                      \
+    if (D == 2) hipLaunchKernelGGL((k_mf_tangent_elements<2, OpT<OPC, 2>::S, OPC>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, xin, c->fe_scratch.p); \
+    else hipLaunchKernelGGL((k_mf_tangent_elements<3, OpT<OPC, 3>::S, OPC>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, xin, c->fe_scratch.p)
+    MT_FOR_OP(c->op, MT_AP)
+#undef MT_AP
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_mf_tangent_elements + k_vector_from_elements_soa";
+    rc = launch_vector_from_elements_soa(c, S, c->fe_scratch.p, y, c->src_n2e_off.p, c->src_n2e.p);
+    if (rc) return rc;
+    return read_status(c, failed);
+}
+#undef MT_FOR_OP
+
+// y = T(u) x.  The scale of the Dirichlet rows must be in c->mt_scale (mt_diagonal).  dot_scratch != null: per-workgroup partials of x . y
+// go to it (*partials of them, in order).  Singular Jacobians land in the status slot: the caller resets and reads it.
+int mt_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials) {
+    const int S = c->S(), N = (int)c->N, n = S * N;
+    const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
+    const double* xin = x;
+    if (dmask) {   // the columns of the Dirichlet nodes vanish: their entries of the operand are zeroed
+        if (c->mf_xm.n < (size_t)n) HIP_TRY(c, c->mf_xm.alloc((size_t)n));
+        hipLaunchKernelGGL(k_mf_operand, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, S, x, dmask, nullptr, c->mf_xm.p);
+        HIP_TRY(c, hipGetLastError());
+        xin = c->mf_xm.p;
+    }
+    if (c->E > 0 && mf_tiles(c)) {
+        int rc = ensure_vector_tiles(c);
+        if (rc) return rc;
+        if (!c->vt_bad) {
+            const size_t need = (size_t)c->vt.v.npartials * S;
+            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+            KArgs a;
+            fill_common(c, a);
+            if (vector_tiles_tangent_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, c->has_mask ? c->active.p : nullptr, xin, c->fe_scratch.p) == 0) {
+                HIP_TRY(c, hipGetLastError());
+                const int g = vector_tiles_operator_partials(N);
+                double* dp = nullptr;
+                if (dot_scratch) {
+                    if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+                    dp = dot_scratch->p;
+                    *partials = g;
+                }
+                c->last_kernel = "k_tangent_tiled + k_operator_from_partials";
+                HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mt_scale.p, nullptr, y, dp));
+                return FH_OK;
+            }
+        }
+    }
+    HIP_TRY(c, hipMemsetAsync(y, 0, sizeof(double) * (size_t)n, c->stream));
+    uint64_t failed = 0;
+    const int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mt_apply_single(c, xin, y, f); })
+                                : mt_apply_single(c, xin, y, &failed);
+    if (rc) return rc;
+    const int g = (n + 255) / 256;
+    double* dp = nullptr;
+    if (dot_scratch) {
+        if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+        dp = dot_scratch->p;
+        *partials = g;
+    }
+    if (dmask || dp) {
+        hipLaunchKernelGGL(k_mf_finish, dim3(g), dim3(256), 0, c->stream, n, S, x, dmask, c->mt_scale.p, nullptr, y, dp);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return FH_OK;
+}
+
+extern "C" {
+
+int fh_apply_tangent_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    int rc = mt_ready(c, "fh_apply_tangent_dev");
+    if (rc) return rc;
+    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, "fh_apply_tangent_dev: null argument");
+    if (c->N == 0) return FH_OK;
+    unsigned long long key[4];
+    mt_scale_key_now(c, key);
+    if (c->mf_num_dirichlet && (key[0] != c->mt_scale_key[0] || key[1] != c->mt_scale_key[1] || key[2] != c->mt_scale_key[2] ||
+                                key[3] != c->mt_scale_key[3])) {
+        // the scale of the Dirichlet rows comes from the diagonal of T(u): formed again when what it depends on, u included, has changed
+        DevBuf<double> diag;
+        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
+        rc = mt_diagonal(c, diag.p, true);
+        if (rc) return rc;
+    }
+    rc = reset_status(c);
+    if (rc) return rc;
+    rc = mt_apply(c, x_dev, y_dev, nullptr, nullptr);
+    if (rc) return rc;
+    return read_status(c, nullptr);
+}
+
+int fh_tangent_diagonal_dev(fh_ctx* c, double* diag_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    int rc = mt_ready(c, "fh_tangent_diagonal_dev");
+    if (rc) return rc;
+    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, "fh_tangent_diagonal_dev: null argument");
+    if (c->N == 0) return FH_OK;
+    rc = mt_diagonal(c, diag_dev, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FH_OK;
+}
+
+}  // extern "C"

@@ -8,6 +8,7 @@
 
 #include "assemble_kernels.hpp"
 #include "device_common.hpp"
+#include "element_pass.hpp"
 
 namespace fenris_hip {
 
@@ -505,6 +506,177 @@ __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N,
 #pragma unroll
                 for (int r = 0; r < D; ++r) t = fma(P[i][r], g[r], t);
                 o[i] = fma(s, t, o[i]);
+            }
+        }
+    }
+}
+
+// tangent of the residual T(u) x for any element kind, deterministic (the kinds outside the tiles, rule-set groups, a mesh without tile
+// tables): k_mf_apply_elements with u (a.u, may be null: zero) and the operand x both gathered, grad u and grad x per point, y_n += s dP(F)[H] g_n
+// (tangent_lin / tangent_apply, element_pass.hpp), fe[a][e][c] for k_vector_from_elements_soa.  Inactive elements write zeros.
+template <int D, int S, int OP>
+__global__ void __launch_bounds__(256) k_mf_tangent_elements(const KArgs a, int N, int NG, const unsigned char* active, const double* x, double* fe) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.num_elements) return;
+    const bool live = !active || active[e] != 0;
+    const int* nodes = a.conn + (size_t)e * N;
+    auto out = [&](int n) { return fe + ((size_t)n * (size_t)a.num_elements + (size_t)e) * S; };
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) out(n)[k] = 0.0;
+    if (!live) return;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    for (int q = 0; q < a.nq; ++q) {
+        double J[D][D];
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+            for (int c = 0; c < D; ++c) J[r][c] = 0.0;
+        for (int g = 0; g < NG; ++g) {
+            const double* v = a.verts + (size_t)nodes[g] * D;
+            const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
+#pragma unroll
+            for (int r = 0; r < D; ++r)
+#pragma unroll
+                for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
+        }
+        const double detJ = det_small<D>(J);
+        if (detJ == 0.0) {
+            report_singular(a.status, e);
+            continue;
+        }
+        double Ji[D][D];
+        inv_small(J, detJ, Ji);
+        const double s = a.qw[q] * fabs(detJ);
+        auto grad = [&](int n, double (&g)[D]) {
+            const double* gr = a.gref + ((size_t)q * N + n) * D;
+#pragma unroll
+            for (int r = 0; r < D; ++r) {
+                double t = 0.0;
+#pragma unroll
+                for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
+                g[r] = t;
+            }
+        };
+        double gu[D][S], gx[D][S];
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+            for (int k = 0; k < S; ++k) { gu[r][k] = 0.0; gx[r][k] = 0.0; }
+        for (int n = 0; n < N; ++n) {
+            double g[D];
+            grad(n, g);
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                const double uv = a.u ? a.u[(size_t)nodes[n] * S + k] : 0.0, xv = x[(size_t)nodes[n] * S + k];
+#pragma unroll
+                for (int r = 0; r < D; ++r) {
+                    gu[r][k] = fma(g[r], uv, gu[r][k]);
+                    gx[r][k] = fma(g[r], xv, gx[r][k]);
+                }
+            }
+        }
+        double mu = 0.0, lambda = 0.0;
+        if (OP != FH_LAPLACE) { mu = par_e ? par_e[2 * q] : a.qparams[2 * q]; lambda = par_e ? par_e[2 * q + 1] : a.qparams[2 * q + 1]; }
+        TangentLin<OP, D> L;
+        tangent_lin<OP, D, S>(gu, mu, lambda, L);
+        double dP[S][D];
+        tangent_apply<OP, D, S>(L, gx, dP);
+        for (int n = 0; n < N; ++n) {
+            double g[D];
+            grad(n, g);
+            double* o = out(n);
+#pragma unroll
+            for (int i = 0; i < S; ++i) {
+                double t = 0.0;
+#pragma unroll
+                for (int r = 0; r < D; ++r) t = fma(dP[i][r], g[r], t);
+                o[i] = fma(s, t, o[i]);
+            }
+        }
+    }
+}
+
+// diagonal of the tangent for any element kind (tangent_diagonal_body's entries, the tables walked like k_mf_tangent_elements)
+template <int D, int S, int OP>
+__global__ void __launch_bounds__(256) k_mf_tangent_diagonal_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.num_elements) return;
+    const bool live = !active || active[e] != 0;
+    const int* nodes = a.conn + (size_t)e * N;
+    auto out = [&](int n) { return fe + ((size_t)n * (size_t)a.num_elements + (size_t)e) * S; };
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) out(n)[k] = 0.0;
+    if (!live) return;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    for (int q = 0; q < a.nq; ++q) {
+        double J[D][D];
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+            for (int c = 0; c < D; ++c) J[r][c] = 0.0;
+        for (int g = 0; g < NG; ++g) {
+            const double* v = a.verts + (size_t)nodes[g] * D;
+            const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
+#pragma unroll
+            for (int r = 0; r < D; ++r)
+#pragma unroll
+                for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
+        }
+        const double detJ = det_small<D>(J);
+        if (detJ == 0.0) {
+            report_singular(a.status, e);
+            continue;
+        }
+        double Ji[D][D];
+        inv_small(J, detJ, Ji);
+        const double s = a.qw[q] * fabs(detJ);
+        auto grad = [&](int n, double (&g)[D]) {
+            const double* gr = a.gref + ((size_t)q * N + n) * D;
+#pragma unroll
+            for (int r = 0; r < D; ++r) {
+                double t = 0.0;
+#pragma unroll
+                for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
+                g[r] = t;
+            }
+        };
+        double gu[D][S];
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+            for (int k = 0; k < S; ++k) gu[r][k] = 0.0;
+        for (int n = 0; n < N; ++n) {
+            double g[D];
+            grad(n, g);
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                const double uv = a.u ? a.u[(size_t)nodes[n] * S + k] : 0.0;
+#pragma unroll
+                for (int r = 0; r < D; ++r) gu[r][k] = fma(g[r], uv, gu[r][k]);
+            }
+        }
+        double mu = 0.0, lambda = 0.0;
+        if (OP != FH_LAPLACE) { mu = par_e ? par_e[2 * q] : a.qparams[2 * q]; lambda = par_e ? par_e[2 * q + 1] : a.qparams[2 * q + 1]; }
+        TangentLin<OP, D> L;
+        tangent_lin<OP, D, S>(gu, mu, lambda, L);
+        for (int n = 0; n < N; ++n) {
+            double g[D];
+            grad(n, g);
+            double* o = out(n);
+#pragma unroll
+            for (int c = 0; c < S; ++c) {
+                double gx[D][S], dP[S][D];
+#pragma unroll
+                for (int r = 0; r < D; ++r)
+#pragma unroll
+                    for (int k = 0; k < S; ++k) gx[r][k] = k == c ? g[r] : 0.0;
+                tangent_apply<OP, D, S>(L, gx, dP);
+                double t = 0.0;
+#pragma unroll
+                for (int r = 0; r < D; ++r) t = fma(dP[c][r], g[r], t);
+                o[c] = fma(s, t, o[c]);
             }
         }
     }

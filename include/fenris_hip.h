@@ -401,6 +401,32 @@ int fh_cg_solve_matrix_free(fh_ctx*, const double* b, double* x, int preconditio
                             uint64_t* num_iterations);
 int fh_cg_solve_matrix_free_dev(fh_ctx*, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
                                 uint64_t* num_iterations);
+/* ---- matrix-free tangent: T(u) = dr/du at the context's u (fh_set_u*; zeros when none is set), r the residual of fh_assemble_vector
+ * (elliptic.rs:457-605).  T(u) is the matrix fh_assemble_matrix assembles for the same context, K_IJ = sum_q w |det J| C(F_q; g_I, g_J) with C
+ * the stress contraction (fenris-solid/src/materials.rs); for FH_LAPLACE and FH_LINEAR_ELASTIC it is the operator above.  Per point the
+ * element vector of x is  y_a += w |det J| dP(F)[H] g_a,  F = I + grad u^T, H = grad x^T:
+ *   Laplace h;  LinearElastic mu (H + H^T) + lambda tr(H) I;
+ *   NeoHookean mu H + lambda tr(F^-1 H) F^-T + (mu - lambda ln J) F^-T H^T F^-T;
+ *   StVK H S + F (lambda tr(dE) I + 2 mu dE), S = lambda tr(E) I + 2 mu E, dE = sym(F^T H).
+ * x enters linearly.  A point of an active element with J <= 0 puts NaN into that element's rows (like the assembled K(u)); masked elements
+ * add zero.  It honours the quadrature table (uniform, per-point, compact, rule sets), the element mask and every element kind.  Errors:
+ * FH_UNSUPPORTED for the mass operators and FH_TENSOR; FH_INVALID_STATE for a missing mesh, operator or table; FH_SINGULAR_JACOBIAN as the
+ * residual reports it.  Dirichlet nodes: those of fh_set_operator_dirichlet_nodes, with the same meaning as for fh_apply_operator_dev (the
+ * matrix fh_apply_dirichlet_csr_dev leaves of the assembled K(u); scale = |first nonzero diagonal entry| of K(u) in row order, or 1).  The scale
+ * is cached apart from the operator's and formed again after the mesh, vertices, operator, table, element mask or u have changed.
+ *
+ * y = T(u) x, both s N doubles on the device; y is OVERWRITTEN, u is read and not changed.  Deterministic on every element kind (no
+ * floating-point atomics). */
+int fh_apply_tangent_dev(fh_ctx*, const double* x_dev, double* y_dev);
+/* the diagonal of T(u) (s N doubles on the device), after the Dirichlet modification when nodes are set, formed per element without forming
+ * T: entry (a, i) = sum_q w |det J| (dP(F)[e_i g_a^T] g_a)_i, e.g. NeoHookean sum w |det J| ((lambda - alpha) (F^-T g_a)_i^2 + mu |g_a|^2),
+ * alpha = -mu + lambda ln J. */
+int fh_tangent_diagonal_dev(fh_ctx*, double* diag_dev);
+/* fh_cg_solve_matrix_free(_dev) with A = T(u): the same contract and error codes, the iterate handed back on failure, bitwise reproducible;
+ * FH_PRECOND_JACOBI takes the inverse of fh_tangent_diagonal_dev. */
+int fh_cg_solve_tangent(fh_ctx*, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations);
+int fh_cg_solve_tangent_dev(fh_ctx*, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
+                            uint64_t* num_iterations);
 /* estimate_L2_error_squared / estimate_H1_seminorm_error_squared (src/error.rs:287-372):
  *   sum_e sum_q w |det J| |u_h(x_q) - u(x_q)|^2      resp.   |grad u_h(x_q) - grad u(x_q)|_F^2
  * with the quadrature table of the context.  The reference solution is arbitrary code in the reference; here the

@@ -1,0 +1,409 @@
+"""Matrix-free tangent T(u) = dr/du (fh_apply_tangent_dev, fh_tangent_diagonal_dev, fh_cg_solve_tangent) for every material:
+against the K(u) the CSR path (or the oracle) assembles for the same u, |y - y_ref|_inf <= 1e-12 | |K| |x| |_inf, against central
+differences of the residual, and in a Newton loop."""
+import os
+
+import numpy as np
+import pytest
+
+import fenris_amd as fa
+from fenris_amd import _ffi, quadrature
+from conftest import GOLDEN
+
+LAME = fa.LameParameters.from_young_poisson(fa.YoungPoisson(1e6, 0.3))
+KINDS = ["QUAD4", "TRI3", "HEX8", "TET4", "QUAD9", "TRI6", "HEX20", "HEX27", "TET10", "TET20"]
+OPS = ["laplace", "elastic", "neo_hookean", "stvk"]
+NEW = ("fh_apply_tangent_dev", "fh_tangent_diagonal_dev", "fh_cg_solve_tangent", "fh_cg_solve_tangent_dev")
+
+
+@pytest.fixture()
+def engine():
+    eng = fa.Engine(0)
+    yield eng
+    eng.close()
+
+
+def _mesh(kind, res=3, seed=0, perturb=0.0):
+    box3 = fa.procedural.create_unit_box_uniform_hex_mesh_3d
+    tet3 = fa.procedural.create_unit_box_uniform_tet_mesh_3d
+    quad2 = fa.procedural.create_unit_square_uniform_quad_mesh_2d
+    tri2 = fa.procedural.create_unit_square_uniform_tri_mesh_2d
+    make = {
+        "QUAD4": (lambda: quad2(res), quadrature.tensor.quadrilateral_gauss(2)),
+        "QUAD9": (lambda: fa.quad9_mesh_from_quad4(quad2(res)), quadrature.tensor.quadrilateral_gauss(3)),
+        "TRI3": (lambda: tri2(res), quadrature.total_order.triangle(1)),
+        "TRI6": (lambda: fa.tri6_mesh_from_tri3(tri2(res)), quadrature.total_order.triangle(2)),
+        "HEX8": (lambda: box3(res), quadrature.tensor.hexahedron_gauss(2)),
+        "HEX20": (lambda: fa.hex20_mesh_from_hex8(box3(2)), quadrature.tensor.hexahedron_gauss(3)),
+        "HEX27": (lambda: fa.hex27_mesh_from_hex8(box3(2)), quadrature.tensor.hexahedron_gauss(3)),
+        "TET4": (lambda: tet3(res), quadrature.total_order.tetrahedron(1)),
+        "TET10": (lambda: fa.tet10_mesh_from_tet4(tet3(2)), quadrature.total_order.tetrahedron(2)),
+        "TET20": (lambda: fa.tet20_mesh_from_tet4(tet3(1)), quadrature.total_order.tetrahedron(4)),
+    }
+    gen, (w, p) = make[kind]
+    m = gen()
+    if perturb:
+        rng = np.random.default_rng(seed)
+        m = fa.Mesh(m.vertices + perturb * rng.uniform(-1, 1, m.vertices.shape), m.connectivity, m.elem_kind)
+    return m, np.asarray(w), np.asarray(p)
+
+
+def _operator(op):
+    return {"laplace": fa.LaplaceOperator(),
+            "elastic": fa.MaterialEllipticOperator(fa.LinearElasticMaterial()),
+            "neo_hookean": fa.MaterialEllipticOperator(fa.NeoHookeanMaterial()),
+            "stvk": fa.MaterialEllipticOperator(fa.StVKMaterial())}[op]
+
+
+def _sdim(m, op):
+    return 1 if op == "laplace" else m.vertices.shape[1]
+
+
+def _smooth_u(m, op, amp=0.05, seed=0):
+    """a smooth deformation that keeps J > 0: a few low Fourier modes of the coordinates"""
+    rng = np.random.default_rng(seed)
+    x = m.vertices
+    s = _sdim(m, op)
+    u = np.zeros((len(x), s))
+    for k in range(s):
+        a = rng.uniform(-1, 1, 3)
+        u[:, k] = amp * (a[0] * np.sin(np.pi * x[:, 0]) * np.cos(0.5 * np.pi * x[:, 1]) + a[1] * np.sin(np.pi * x[:, 1])
+                         + a[2] * np.cos(np.pi * x.sum(axis=1)))
+    return u.reshape(-1)
+
+
+def _uniform(op, w, p):
+    qt = fa.UniformQuadratureTable.from_points_and_weights(p, w)
+    return qt if op == "laplace" else qt.with_uniform_data(LAME)
+
+
+def _assembler(engine, m, op, qt, u=None):
+    s = _sdim(m, op)
+    return (fa.ElementEllipticAssemblerBuilder(engine).with_finite_element_space(m).with_operator(_operator(op))
+            .with_quadrature_table(qt).with_u(np.zeros(s * m.num_nodes()) if u is None else u).build())
+
+
+def _check_against_spmv(engine, asm, rng, dirichlet=None, x=None):
+    """tangent vs fh_spmv_dev on the assembled K(u) (with Dirichlet nodes: as apply_homogeneous_dirichlet_bc_csr leaves it)"""
+    import torch
+
+    k = fa.CsrAssembler(fa.SCATTER_GATHER).assemble(asm, device_values=True)
+    s = asm.solution_dim()
+    if dirichlet is not None:
+        fa.apply_homogeneous_dirichlet_bc_csr(k, dirichlet, s, asm)
+    n = s * asm.engine.num_nodes()
+    if x is None:
+        x = torch.from_numpy(rng.standard_normal(n)).cuda()
+    y_ref = torch.zeros(n, dtype=torch.float64, device="cuda")
+    engine.spmv(k.values, x, y_ref)
+    op = fa.MatrixFreeTangent(asm)
+    if dirichlet is not None:
+        op.with_dirichlet_nodes(dirichlet)
+    y = torch.full((n,), float("nan"), dtype=torch.float64, device="cuda")   # overwritten: no NaN survives
+    op.apply(y, x)
+    ks = fa.CsrMatrix(k.row_offsets, k.col_indices, k.values.cpu().numpy()).to_scipy()
+    bound = np.abs(abs(ks) @ np.abs(x.cpu().numpy())).max()
+    err = np.abs(y.cpu().numpy() - y_ref.cpu().numpy()).max()
+    assert np.isfinite(err) and err <= 1e-12 * bound, (err, bound, engine.last_kernel_name())
+    return op, k, ks
+
+
+def test_tangent_entry_points_are_declared():
+    """no GPU: the new entry points are in the header, the ctypes table and the Rust bindings"""
+    root = os.path.join(os.path.dirname(GOLDEN), "..")
+    hdr = open(os.path.join(root, "include", "fenris_hip.h")).read()
+    rs = open(os.path.join(root, "bindings", "fenris_hip_sys.rs")).read()
+    for name in NEW:
+        assert name + "(" in hdr and name in _ffi.exported_symbols() and name in rs
+    assert issubclass(fa.MatrixFreeTangent, fa.MatrixFreeOperator)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("op", OPS)
+def test_tangent_matches_assembled_k_of_u_on_every_kind(engine, kind, op):
+    rng = np.random.default_rng(KINDS.index(kind))
+    m, w, p = _mesh(kind, perturb=0.02 if kind in ("HEX8", "QUAD4") else 0.0, seed=3)
+    u = _smooth_u(m, op, seed=KINDS.index(kind))
+    asm = _assembler(engine, m, op, _uniform(op, w, p), u)
+    if kind == "HEX27":   # the oracle's K(u) (the MFMA-assembled Hex27 matrix holds only 1e-11 under deformation)
+        import torch
+        from oracle import oracle
+
+        s = _sdim(m, op)
+        oop = {"laplace": oracle.LAPLACE, "elastic": oracle.LINEAR_ELASTIC, "neo_hookean": oracle.NEO_HOOKEAN, "stvk": oracle.STVK}[op]
+        ref = oracle.ElementAssembler(oracle.HEX27, oop, m.vertices, m.connectivity, w, p,
+                                      params=(LAME.as_pair() if op != "laplace" else None), u=u)
+        st, _, ro, ci, vals = oracle.assemble(ref)
+        assert st == 0
+        ks = fa.CsrMatrix(ro, ci, vals).to_scipy()
+        x = rng.standard_normal(s * m.num_nodes())
+        y = torch.full((len(x),), float("nan"), dtype=torch.float64, device="cuda")
+        fa.MatrixFreeTangent(asm).apply(y, torch.from_numpy(x).cuda())
+        bound = np.abs(abs(ks) @ np.abs(x)).max()
+        assert np.abs(y.cpu().numpy() - ks @ x).max() <= 1e-12 * bound
+        return
+    _check_against_spmv(engine, asm, rng)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("perturb", [0.0, 0.03])   # all-affine box (constant J, monomial form) and general hexahedra
+@pytest.mark.parametrize("table", ["uniform", "per_point", "compact", "rule_set"])
+def test_tangent_hex8_tables(engine, perturb, table):
+    m, w, p = _mesh("HEX8", res=5, perturb=perturb, seed=5)
+    nq = len(w)
+    if table == "uniform":
+        qt = _uniform("elastic", w, p)
+    elif table == "per_point":
+        qt = fa.UniformQuadratureTable.from_points_and_weights(p, w).with_data(
+            [fa.LameParameters(1e5 * (1 + q), 2e5 * (2 + q % 3)) for q in range(nq)])
+    else:
+        emap = (np.arange(m.num_elements()) % 3 == 0).astype(np.uint64)
+        if table == "compact":
+            rules = [(w, p, [fa.LameParameters(1e5 * (r + 1), 3e5 + q) for q in range(nq)]) for r in range(2)]
+        else:
+            w2, p2 = (np.asarray(a) for a in quadrature.tensor.hexahedron_gauss(3))
+            rules = [(w, p, [LAME] * nq), (w2, p2, [fa.LameParameters(2e5, 7e5)] * len(w2))]
+        qt = fa.compact_quadrature_table([r[1] for r in rules], [r[0] for r in rules], [r[2] for r in rules], emap)
+    for op in ("neo_hookean", "stvk"):
+        asm = _assembler(engine, m, op, qt, _smooth_u(m, op, seed=2))
+        t, _, ks = _check_against_spmv(engine, asm, np.random.default_rng(7))
+        d_ref = ks.diagonal()
+        assert np.abs(t.diagonal() - d_ref).max() <= 1e-12 * np.abs(d_ref).max()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["HEX8", "TET4", "HEX27"])
+@pytest.mark.parametrize("op", ["neo_hookean", "stvk"])
+def test_tangent_under_element_mask_and_dirichlet(engine, kind, op):
+    rng = np.random.default_rng(21)
+    m, w, p = _mesh(kind)
+    asm = _assembler(engine, m, op, _uniform(op, w, p), _smooth_u(m, op, seed=4))
+    engine.set_active_elements(rng.random(m.num_elements()) < 0.6)
+    bc = np.where(m.vertices[:, 0] < 1e-9)[0]
+    t, _, ks = _check_against_spmv(engine, asm, rng, dirichlet=bc)
+    d_ref = ks.diagonal()
+    assert np.abs(t.diagonal() - d_ref).max() <= 1e-12 * np.abs(d_ref).max()
+
+
+def _residual(asm, u):
+    asm.engine.set_u(u)
+    return fa.VectorAssembler().assemble_vector(asm)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["HEX8", "TET4"])
+@pytest.mark.parametrize("op", ["neo_hookean", "stvk"])
+def test_tangent_is_the_derivative_of_the_residual(engine, kind, op):
+    """independent of assembly: (r(u + eps x) - r(u - eps x)) / 2 eps from fh_assemble_vector"""
+    m, w, p = _mesh(kind, perturb=0.02 if kind == "HEX8" else 0.0, seed=9)
+    u = _smooth_u(m, op, amp=0.1, seed=6)
+    asm = _assembler(engine, m, op, _uniform(op, w, p), u)
+    x = np.random.default_rng(1).standard_normal(len(u)) * 0.1
+    y = np.zeros_like(u)
+    fa.MatrixFreeTangent(asm).apply(y, x)
+    eps = 1e-5
+    fd = (_residual(asm, u + eps * x) - _residual(asm, u - eps * x)) / (2 * eps)
+    assert np.abs(y - fd).max() <= 1e-7 * np.abs(y).max(), np.abs(y - fd).max() / np.abs(y).max()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["HEX8", "TET4", "TET10"])
+@pytest.mark.parametrize("op", ["laplace", "elastic"])
+def test_linear_tangent_is_the_operator_for_any_u(engine, kind, op):
+    m, w, p = _mesh(kind, perturb=0.02 if kind == "HEX8" else 0.0, seed=2)
+    asm = _assembler(engine, m, op, _uniform(op, w, p), _smooth_u(m, op, amp=0.3, seed=8))
+    bc = np.where(m.vertices[:, 0] < 1e-9)[0]
+    x = np.random.default_rng(3).standard_normal(_sdim(m, op) * m.num_nodes())
+    y_t, y_o = np.zeros_like(x), np.zeros_like(x)
+    fa.MatrixFreeTangent(asm).with_dirichlet_nodes(bc).apply(y_t, x)
+    fa.MatrixFreeOperator(asm).with_dirichlet_nodes(bc).apply(y_o, x)
+    assert np.abs(y_t - y_o).max() <= 1e-12 * np.abs(y_o).max()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["HEX8", "TET10"])
+def test_tangent_diagonal_and_dirichlet_scale_follow_u(engine, kind):
+    """diag(K(u)) after the Dirichlet modification; a new u moves the scale of the Dirichlet rows (no scale cached across u)"""
+    import torch
+
+    m, w, p = _mesh(kind)
+    op = "neo_hookean"
+    bc = np.where(m.vertices[:, 0] < 1e-9)[0]
+    asm = _assembler(engine, m, op, _uniform(op, w, p), _smooth_u(m, op, amp=0.05, seed=1))
+    t = fa.MatrixFreeTangent(asm).with_dirichlet_nodes(bc)
+    rng = np.random.default_rng(5)
+    x = torch.from_numpy(rng.standard_normal(3 * m.num_nodes())).cuda()
+    for seed, amp in ((1, 0.05), (2, 0.1)):
+        u = _smooth_u(m, op, amp=amp, seed=seed) + amp   # (a shift: node 0 moves, and with it the first diagonal entry)
+        engine.set_u(u)
+        t.apply(torch.empty_like(x), x)   # an apply before the diagonal: the cached scale must not outlive u
+        _, k, ks = _check_against_spmv(engine, asm, rng, dirichlet=bc, x=x)
+        d_ref = ks.diagonal()
+        assert np.abs(t.diagonal() - d_ref).max() <= 1e-12 * np.abs(d_ref).max()
+        y = torch.empty_like(x)
+        t.apply(y, x)
+        rows = (bc[:, None] * 3 + np.arange(3)).reshape(-1)
+        assert np.abs(y.cpu().numpy()[rows] - d_ref[rows] * x.cpu().numpy()[rows]).max() <= 1e-12 * np.abs(d_ref).max() * np.abs(
+            x.cpu().numpy()).max()
+
+
+@pytest.mark.gpu
+def test_tangent_contract(engine):
+    import torch
+
+    m, w, p = _mesh("HEX8", res=4, perturb=0.02, seed=1)
+    op = "neo_hookean"
+    u = _smooth_u(m, op, seed=3)
+    asm = _assembler(engine, m, op, _uniform(op, w, p), u)
+    t = fa.MatrixFreeTangent(asm)
+    n = len(u)
+    rng = np.random.default_rng(0)
+    x = torch.from_numpy(rng.standard_normal(n)).cuda()
+    r0 = fa.VectorAssembler().assemble_vector(asm)
+    y1 = torch.full((n,), 7.0, dtype=torch.float64, device="cuda")
+    y2 = torch.full((n,), -3.0, dtype=torch.float64, device="cuda")
+    t.apply(y1, x)
+    t.apply(y2, x)
+    assert torch.equal(y1, y2)                                                       # overwritten, the same bits
+    assert np.array_equal(fa.VectorAssembler().assemble_vector(asm), r0)             # u read, not changed
+    yh = np.zeros(n)
+    t.apply(yh, x.cpu().numpy())
+    assert np.array_equal(yh, y1.cpu().numpy())                                      # host arrays
+    xs = x * 1e-9                                                                    # small operands keep the bound (x enters linearly)
+    _check_against_spmv(engine, asm, rng, x=xs)
+    for other in (_ffi.MASS_SCALAR, _ffi.MASS_VECTOR, _ffi.TENSOR):
+        e2 = fa.Engine(0)
+        try:
+            e2.set_mesh(m)
+            e2.set_operator(other)
+            z = torch.zeros(n, dtype=torch.float64, device="cuda")
+            for call in (lambda: e2.apply_tangent_dev(z, z.clone()), lambda: e2.tangent_diagonal_dev(z)):
+                with pytest.raises(fa.FenrisError) as exc:
+                    call()
+                assert exc.value.code == _ffi.FH_UNSUPPORTED
+        finally:
+            e2.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["HEX8", "TET4", "TET10"])
+def test_inverted_element_gives_nan_where_the_assembled_k_does(engine, kind):
+    import torch
+
+    m, w, p = _mesh(kind)
+    op = "neo_hookean"
+    n = 3 * m.num_nodes()
+    u = np.zeros(n)
+    e0 = m.connectivity[m.num_elements() // 2]
+    c = m.vertices[e0].mean(axis=0)
+    for v in e0:   # reflect one element through its centre: J < 0 there
+        u[3 * v:3 * v + 3] = 2.0 * (c - m.vertices[v])
+    asm = _assembler(engine, m, op, _uniform(op, w, p), u)
+    k = fa.CsrAssembler(fa.SCATTER_GATHER).assemble(asm, device_values=True)
+    x = torch.from_numpy(np.random.default_rng(2).standard_normal(n)).cuda()
+    y_ref = torch.zeros(n, dtype=torch.float64, device="cuda")
+    engine.spmv(k.values, x, y_ref)
+    y = torch.empty_like(x)
+    fa.MatrixFreeTangent(asm).apply(y, x)
+    nan_ref = torch.isnan(y_ref).cpu().numpy()
+    assert nan_ref.any() and np.array_equal(torch.isnan(y).cpu().numpy(), nan_ref)
+    # masked: the elements around the moved nodes (the reflected one and its neighbours) contribute nothing
+    touched = np.isin(m.connectivity, e0).any(axis=1)
+    engine.set_active_elements(~touched)
+    fa.MatrixFreeTangent(asm).apply(y, x)
+    assert torch.isfinite(y).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,op", [("HEX8", "neo_hookean"), ("TET4", "stvk"), ("TET10", "neo_hookean")])
+def test_pcg_on_tangent_matches_pcg_on_assembled(engine, kind, op):
+    import torch
+
+    m, w, p = _mesh(kind, res=5 if kind != "TET10" else 3)
+    asm = _assembler(engine, m, op, _uniform(op, w, p), _smooth_u(m, op, amp=0.01, seed=11))   # (small u: T(u) stays definite)
+    bc = np.where(m.vertices[:, 0] < 1e-9)[0]
+    s, n = 3, 3 * m.num_nodes()
+    k = fa.CsrAssembler(fa.SCATTER_GATHER).assemble(asm, device_values=True)
+    fa.apply_homogeneous_dirichlet_bc_csr(k, bc, s, asm)
+    b = np.random.default_rng(4).standard_normal(n)
+    fa.apply_homogeneous_dirichlet_bc_rhs(b, bc, s)
+    xa = torch.zeros(n, dtype=torch.float64, device="cuda")
+    it_a = (fa.ConjugateGradient.new().with_operator(k, asm).with_preconditioner(fa.JacobiPreconditioner())
+            .with_stopping_criterion(fa.RelativeResidualCriterion(1e-11)).solve_with_guess(torch.from_numpy(b).cuda(), xa))
+    t = fa.MatrixFreeTangent(asm).with_dirichlet_nodes(bc)
+    xm = torch.zeros(n, dtype=torch.float64, device="cuda")
+    it_m = (fa.ConjugateGradient.new().with_operator(t).with_preconditioner(fa.JacobiPreconditioner())
+            .with_stopping_criterion(fa.RelativeResidualCriterion(1e-11)).solve_with_guess(torch.from_numpy(b).cuda(), xm))
+    assert abs(it_a - it_m) <= 1, (it_a, it_m)
+    xa, xm = xa.cpu().numpy(), xm.cpu().numpy()
+    assert np.abs(xa - xm).max() <= 1e-9 * np.abs(xa).max()
+    xh = np.zeros(n)   # host form: the same iterate
+    t.cg_solve(b, xh, 1, 1e-11)
+    assert np.array_equal(xh, xm)
+
+
+def _newton(mesh, w, p, matrix_free, max_steps=30, check_reproducible=False):
+    """NeoHookean under gravity, face x = 0 clamped: Newton steps with the tangent solved by Jacobi-PCG"""
+    import torch
+
+    e_k, e_b = fa.Engine(0), fa.Engine(0)
+    try:
+        n = 3 * mesh.num_nodes()
+        asm = _assembler(e_k, mesh, "neo_hookean", _uniform("neo_hookean", w, p))
+        src = (fa.ElementSourceAssemblerBuilder.new(e_b).with_finite_element_space(mesh).with_source(fa.GravitySource([0.0, 0.0, -9.81]))
+               .with_quadrature_table(fa.UniformQuadratureTable.from_points_and_weights(p, w).with_uniform_data(fa.Density(3e3))).build())
+        f = fa.VectorAssembler().assemble_vector(src)
+        bc = np.where(mesh.vertices[:, 0] < 1e-9)[0]
+        fa.apply_homogeneous_dirichlet_bc_rhs(f, bc, 3)
+        u = np.zeros(n)
+        tangent = fa.MatrixFreeTangent(asm).with_dirichlet_nodes(bc)
+        norms, iterates = [], []
+        for _ in range(max_steps):
+            e_k.set_u(u)
+            g = fa.VectorAssembler().assemble_vector(asm) - f
+            fa.apply_homogeneous_dirichlet_bc_rhs(g, bc, 3)
+            norms.append(np.linalg.norm(g))
+            if norms[-1] <= 1e-10 * norms[0]:
+                break
+            du = torch.zeros(n, dtype=torch.float64, device="cuda")
+            rhs = torch.from_numpy(-g).cuda()
+            cg = fa.ConjugateGradient.new().with_preconditioner(fa.JacobiPreconditioner()).with_stopping_criterion(
+                fa.RelativeResidualCriterion(1e-12)).with_max_iter(20000)
+            if matrix_free:
+                cg.with_operator(tangent)
+            else:
+                k = fa.CsrAssembler(fa.SCATTER_GATHER).assemble(asm, device_values=True)
+                fa.apply_homogeneous_dirichlet_bc_csr(k, bc, 3, asm)
+                cg.with_operator(k, asm)
+            cg.solve_with_guess(rhs, du)
+            if check_reproducible:   # the same solve again: the same bits
+                du2 = torch.zeros_like(du)
+                cg.solve_with_guess(rhs, du2)
+                assert torch.equal(du, du2)
+            u = u + du.cpu().numpy()
+            iterates.append(u.copy())
+        return norms, iterates
+    finally:
+        e_k.close(), e_b.close()
+
+
+@pytest.mark.gpu
+def test_newton_neo_hookean_matrix_free_against_assembled():
+    m, w, p = _mesh("HEX8", res=8)
+    nm, um = _newton(m, w, p, True)
+    na, ua = _newton(m, w, p, False)
+    assert len(nm) == len(na) and nm[-1] <= 1e-10 * nm[0] and na[-1] <= 1e-10 * na[0], (nm, na)
+    assert np.abs(um[-1] - ua[-1]).max() <= 1e-8 * np.abs(ua[-1]).max()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["TET10", "HEX27"])
+def test_newton_outside_the_tiles_converges_with_reproducible_solves(kind):
+    """off the tiles every tangent solve of the loop gives the same bits twice (the residual of these kinds is summed with atomics,
+    so whole loops are not compared); the loop converges like the assembled one"""
+    m, w, p = _mesh(kind)
+    nm, um = _newton(m, w, p, True, check_reproducible=True)
+    na, ua = _newton(m, w, p, False)
+    assert nm[-1] <= 1e-10 * nm[0] and len(nm) == len(na)
+    assert np.abs(um[-1] - ua[-1]).max() <= 1e-8 * np.abs(ua[-1]).max()
