@@ -441,18 +441,16 @@ struct fh_ctx {
     DevBuf<unsigned long long> trace;
     bool defer_status = false;   // fh_assemble_vector_async_dev: the launches are only enqueued, fh_poll_status reports their errors
     bool keep_status = false;    // ... over a rule-set table: the status slot is reset once in front of the group walk, not per group
-    // matrix-free operator (engine_vector.hip): homogeneous Dirichlet nodes (fh_set_operator_dirichlet_nodes; fh_set_mesh* clears them),
+    // matrix-free map (engine_vector.hip): homogeneous Dirichlet nodes (fh_set_operator_dirichlet_nodes; fh_set_mesh* clears them),
     // the scale of their rows (valid for mf_scale_key), the operand the element pass reads
     DevBuf<unsigned char> mf_dmask;    // N membership flags
     uint64_t mf_num_dirichlet = 0;
     DevBuf<double> mf_scale;           // 1 double
     DevBuf<double> mf_xm;              // S N
     DevBuf<unsigned long long> mf_bits;   // |operand|_inf (k_mf_absmax)
-    unsigned long long mf_scale_key[3] = {~0ull, ~0ull, ~0ull};   // (struct_gen, topo_gen, geom_gen) mf_scale was formed for
+    // (struct_gen, topo_gen, geom_gen, u_gen) mf_scale was formed for; u_gen is 0 for the linear operators (their scale does not depend on u)
+    unsigned long long mf_scale_key[4] = {~0ull, ~0ull, ~0ull, ~0ull};
     unsigned long long geom_gen = 0;   // counts fh_update_vertices calls
-    // matrix-free tangent (engine_vector.hip): the scale of the Dirichlet rows of T(u), kept apart from mf_scale (it depends on u too)
-    DevBuf<double> mt_scale;           // 1 double
-    unsigned long long mt_scale_key[4] = {~0ull, ~0ull, ~0ull, ~0ull};   // (struct_gen, topo_gen, geom_gen, u_gen) mt_scale was formed for
     unsigned long long u_gen = 0;      // counts fh_set_u* calls
 
     int S() const {
@@ -533,14 +531,11 @@ int assemble_two_pass(fh_ctx* c, double* values_dev, int overwrite);
 size_t two_pass_dense_doubles(fh_ctx* c);   // doubles of the element-matrix buffer between the two passes (depends on the first pass's layout)
 int hex8_tune_lanes_now(fh_ctx* c);
 int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset = true);
-// matrix-free operator (engine_vector.hip): checks, y = A x (+ per-workgroup partials of x . y; *partials: their number), the diagonal
-int mf_ready(fh_ctx* c, const char* who);
+// matrix-free map (engine_vector.hip): checks (max_op: FH_LINEAR_ELASTIC for the operator, FH_STVK for the tangent), y = T(u) x (+ per-workgroup
+// partials of x . y; *partials: their number), the diagonal
+int mf_ready(fh_ctx* c, const char* who, int max_op);
 int mf_apply(fh_ctx* c, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
 int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
-// matrix-free tangent T(u) = dr/du at the context's u (engine_vector.hip): the same three for it
-int mt_ready(fh_ctx* c, const char* who);
-int mt_apply(fh_ctx* c, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
-int mt_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
 
 // dispatch over (element kind, operator kind) -> template instantiation
 #define FH_FOR_ELEM_OP(EKV, OPV, CALL)                                             \

@@ -224,18 +224,15 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
                   });
 }
 
-// The same solver around the matrix-free operator (fh_apply_operator_dev): no pattern, no values.  The partials of p . Ap come from the
-// operator's node pass (or its last pass off the tiles), summed over at most 2048 ranges in a fixed order; Jacobi takes the matrix-free
-// diagonal.  The diagonal (and with it the scale of the Dirichlet rows) is formed once per solve.
-typedef int (*free_ready_fn)(fh_ctx*, const char*);
-typedef int (*free_diagonal_fn)(fh_ctx*, double*, bool);
-typedef int (*free_apply_fn)(fh_ctx*, const double*, double*, DevBuf<double>*, int*);
-static int cg_solve_free_dev(fh_ctx* c, const char* who, free_ready_fn ready, free_diagonal_fn diagonal, free_apply_fn apply, const double* b_dev,
-                             double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations) {
+// The same solver around the matrix-free map (fh_apply_operator_dev, fh_apply_tangent_dev; max_op as mf_ready): no pattern, no values.  The
+// partials of p . Ap come from the map's node pass (or its last pass off the tiles), summed over at most 2048 ranges in a fixed order; Jacobi
+// takes the matrix-free diagonal.  The diagonal (and with it the scale of the Dirichlet rows) is formed once per solve.
+static int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
+                             uint64_t max_iter, uint64_t* num_iterations) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     if (num_iterations) *num_iterations = 0;
-    int rc = ready(c, who);
+    int rc = mf_ready(c, who, max_op);
     if (rc) return rc;
     if (!b_dev || !x_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI)
@@ -249,7 +246,7 @@ static int cg_solve_free_dev(fh_ctx* c, const char* who, free_ready_fn ready, fr
     HIP_TRY(c, partial.alloc((size_t)3 * std::max(gv, gs_max)));
     if (preconditioner == FH_PRECOND_JACOBI || c->mf_num_dirichlet) {
         HIP_TRY(c, dinv.alloc(n));
-        rc = diagonal(c, dinv.p, true);
+        rc = mf_diagonal(c, dinv.p, true);
         if (rc) return rc;
         if (preconditioner == FH_PRECOND_JACOBI) {
             hipLaunchKernelGGL(k_reciprocal, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dinv.p);
@@ -260,16 +257,16 @@ static int cg_solve_free_dev(fh_ctx* c, const char* who, free_ready_fn ready, fr
     if (rc) return rc;
     const int rcg = cg_run(c, n, b_dev, x_dev, preconditioner == FH_PRECOND_JACOBI ? dinv.p : nullptr, partial, wg_partial, rel_tol, max_iter,
                            num_iterations, [&](const double* in, double* out, int* ranges) {
-                               if (!ranges) return apply(c, in, out, nullptr, nullptr);
+                               if (!ranges) return mf_apply(c, in, out, nullptr, nullptr);
                                int count = 0;
-                               int r = apply(c, in, out, &wg_partial, &count);
+                               int r = mf_apply(c, in, out, &wg_partial, &count);
                                if (r) return r;
                                *ranges = std::min(gs_max, count);
                                hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(*ranges), dim3(256), 0, c->stream, wg_partial.p, (long long)count, partial.p);
                                HIP_TRY(c, hipGetLastError());
                                return (int)FH_OK;
                            });
-    // a singular Jacobian shows in the operator's first application already (and in the diagonal): report it over the solver's status
+    // a singular Jacobian shows in the map's first application already (and in the diagonal): report it over the solver's status
     rc = read_status(c, nullptr);
     if (rc) return rc;
     return rcg;
@@ -277,15 +274,11 @@ static int cg_solve_free_dev(fh_ctx* c, const char* who, free_ready_fn ready, fr
 
 int fh_cg_solve_matrix_free_dev(fh_ctx* c, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
                                 uint64_t* num_iterations) {
-    return cg_solve_free_dev(c, "fh_cg_solve_matrix_free", mf_ready, mf_diagonal, mf_apply, b_dev, x_dev, preconditioner, rel_tol, max_iter,
-                             num_iterations);
+    return cg_solve_free_dev(c, "fh_cg_solve_matrix_free", FH_LINEAR_ELASTIC, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations);
 }
-
-// ... and around the matrix-free tangent T(u) at the context's u (fh_apply_tangent_dev); Jacobi takes fh_tangent_diagonal_dev
 int fh_cg_solve_tangent_dev(fh_ctx* c, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
                             uint64_t* num_iterations) {
-    return cg_solve_free_dev(c, "fh_cg_solve_tangent", mt_ready, mt_diagonal, mt_apply, b_dev, x_dev, preconditioner, rel_tol, max_iter,
-                             num_iterations);
+    return cg_solve_free_dev(c, "fh_cg_solve_tangent", FH_STVK, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations);
 }
 
 int fh_cg_solve(fh_ctx* c, const double* values, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter,
@@ -310,13 +303,12 @@ int fh_cg_solve(fh_ctx* c, const double* values, const double* b, double* x, int
     return rc;
 }
 
-static int cg_solve_free_host(fh_ctx* c, const char* who, free_ready_fn ready,
-                              int (*solve_dev)(fh_ctx*, const double*, double*, int, double, uint64_t, uint64_t*), const double* b, double* x,
-                              int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations) {
+static int cg_solve_free_host(fh_ctx* c, const char* who, int max_op, const double* b, double* x, int preconditioner, double rel_tol,
+                              uint64_t max_iter, uint64_t* num_iterations) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     if (num_iterations) *num_iterations = 0;
-    int rc = ready(c, who);
+    int rc = mf_ready(c, who, max_op);
     if (rc) return rc;
     if (!b || !x) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     const size_t n = (size_t)c->S() * c->N;
@@ -325,7 +317,7 @@ static int cg_solve_free_host(fh_ctx* c, const char* who, free_ready_fn ready,
     HIP_TRY(c, dx.alloc(n + 1));
     HIP_TRY(c, hipMemcpyAsync(db.p, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    rc = solve_dev(c, db.p, dx.p, preconditioner, rel_tol, max_iter, num_iterations);
+    rc = cg_solve_free_dev(c, who, max_op, db.p, dx.p, preconditioner, rel_tol, max_iter, num_iterations);
     // like the reference's SolveError, the iterate reached so far is handed back on failure
     HIP_TRY(c, hipMemcpyAsync(x, dx.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -333,12 +325,10 @@ static int cg_solve_free_host(fh_ctx* c, const char* who, free_ready_fn ready,
 }
 
 int fh_cg_solve_matrix_free(fh_ctx* c, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations) {
-    return cg_solve_free_host(c, "fh_cg_solve_matrix_free", mf_ready, fh_cg_solve_matrix_free_dev, b, x, preconditioner, rel_tol, max_iter,
-                              num_iterations);
+    return cg_solve_free_host(c, "fh_cg_solve_matrix_free", FH_LINEAR_ELASTIC, b, x, preconditioner, rel_tol, max_iter, num_iterations);
 }
-
 int fh_cg_solve_tangent(fh_ctx* c, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations) {
-    return cg_solve_free_host(c, "fh_cg_solve_tangent", mt_ready, fh_cg_solve_tangent_dev, b, x, preconditioner, rel_tol, max_iter, num_iterations);
+    return cg_solve_free_host(c, "fh_cg_solve_tangent", FH_STVK, b, x, preconditioner, rel_tol, max_iter, num_iterations);
 }
 
 static int error_squared(fh_ctx* c, int which, uint32_t sdim, const double* uh_dev, const double* exact_dev, double* out) {

@@ -518,32 +518,35 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
 // ---- Dirichlet helpers
 }  // extern "C"
 
-// ---- matrix-free operator: y = A x of the linear operators (LinearOperator::apply, fenris-sparse/src/cg.rs:16-18) and their diagonal,
-// without a pattern or values.  For FH_LAPLACE and FH_LINEAR_ELASTIC the element vector is linear in u, so the residual of the
-// operand IS  K x:  the element pass of the residual, fed x in place of the context's u.  On the tiles (Hex8, Tet4, Quad4, Tri3 without a
-// rule-set table) the node pass overwrites y, applies the Dirichlet rows on store and leaves the partials of x . y for CG; elsewhere the
-// residual kernels accumulate into a zeroed y and one more pass over y does the same.  Homogeneous Dirichlet nodes make the operator the
-// one fh_apply_dirichlet_csr_dev leaves (global.rs:379-451): the element pass reads x with their entries zeroed (their columns vanish),
-// their rows are  scale x.  LinearElastic: the element pass reads x 2^-e with |x 2^-e|_inf in [1/2, 1) (mf_exponent, device_common.hpp).
-int mf_ready(fh_ctx* c, const char* who) {
-    if (c->op > FH_LINEAR_ELASTIC)
-        return c->fail(FH_UNSUPPORTED, std::string(who) + ": the matrix-free operator covers FH_LAPLACE and FH_LINEAR_ELASTIC only");
+// ---- the matrix-free map: y = T(u) x with T(u) = dr/du at the context's u (the matrix fh_assemble_matrix forms for the same context), and
+// its diagonal, without a pattern or values.  For FH_LAPLACE and FH_LINEAR_ELASTIC the element vector is linear in u, so T(u) is the
+// operator A of LinearOperator::apply (fenris-sparse/src/cg.rs:16-18) for every u, and the residual of the operand IS  A x:  the element pass
+// of the residual, fed x in place of the context's u.  For FH_NEO_HOOKEAN and FH_STVK the element pass gathers u and the operand per
+// element and forms dP(F)[grad x^T] per point (tangent_lin / tangent_apply, element_pass.hpp).  On the tiles (Hex8, Tet4, Quad4, Tri3
+// without a rule-set table) the node pass overwrites y, applies the Dirichlet rows on store and leaves the partials of x . y for CG;
+// otherwise every group of a rule-set table takes the tiles where they cover it, else the per-element kernels, all accumulating into a
+// zeroed y, and one more pass over y does the same.  Homogeneous Dirichlet nodes make the map the one fh_apply_dirichlet_csr_dev leaves
+// (global.rs:379-451): the element pass reads x with their entries zeroed (their columns vanish), their rows are  scale x.
+// LinearElastic: the element pass reads x 2^-e with |x 2^-e|_inf in [1/2, 1) (mf_exponent, device_common.hpp).
+// max_op: FH_LINEAR_ELASTIC for the operator's entry points, FH_STVK for the tangent's.
+int mf_ready(fh_ctx* c, const char* who, int max_op) {
+    if (c->op > max_op)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + (max_op == FH_LINEAR_ELASTIC
+                                                               ? ": the matrix-free operator covers FH_LAPLACE and FH_LINEAR_ELASTIC only"
+                                                               : ": the matrix-free tangent covers FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN and FH_STVK"));
     const int rc = check_ready(c, who, false);
     if (rc) return rc;
     if (c->S() < 1 || c->S() > 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": solution dim must be 1..3");
     return FH_OK;
 }
 
-static bool mf_tiles(fh_ctx* c) {
-    return !c->rs.active && element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->env("FENRIS_HIP_NO_VECTOR_TILES");
-}
-
 // what the scale of the Dirichlet rows depends on: mesh, vertices, operator, quadrature table and parameters, element mask (the setters of
-// the last three move struct_gen) -- not on which nodes are constrained
-static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[3]) {
+// the last three move struct_gen), u for the nonlinear operators -- not on which nodes are constrained
+static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[4]) {
     k[0] = c->struct_gen;
     k[1] = c->topo_gen;
     k[2] = c->geom_gen;
+    k[3] = c->op <= FH_LINEAR_ELASTIC ? 0 : c->u_gen;
 }
 
 // the scale of the Dirichlet rows into c->mf_scale, from the unmodified diagonal (diag_dev)
@@ -557,111 +560,104 @@ static int mf_scale_from(fh_ctx* c, const double* diag_dev) {
     hipLaunchKernelGGL(k_mf_scale, dim3(1), dim3(64), 0, c->stream, diag_dev, first.p, c->mf_scale.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // (first is released on return)
+    mf_scale_key_now(c, c->mf_scale_key);
     return FH_OK;
 }
 
-// one quadrature table (or one group of a rule-set table): the element diagonals ADDED to out
-static int mf_diagonal_single(fh_ctx* c, double* out, uint64_t* failed) {
+// the element pass of the map over the tiles into c->fe_scratch (one partial per distinct node of a tile): the diagonal (xin null), the
+// residual's element pass fed xin (linear operators), or k_tangent_tiled at the context's u.  *done = false: the tiles do not cover it.
+static int mf_tiles_pass(fh_ctx* c, KArgs& a, const double* xin, bool* done) {
+    *done = false;
+    if (!element_pass_covers(c) || c->env("FENRIS_HIP_VECTOR_ATOMICS") || c->env("FENRIS_HIP_NO_VECTOR_TILES")) return FH_OK;
+    const int rc = ensure_vector_tiles(c);
+    if (rc || c->vt_bad) return rc;
+    const size_t need = (size_t)c->vt.v.npartials * c->S();
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    int rt;
+    if (!xin) {
+        rt = vector_tiles_diagonal_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p);
+    } else if (c->op <= FH_LINEAR_ELASTIC) {
+        a.u = xin;
+        rt = vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p);
+    } else {
+        rt = vector_tiles_tangent_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, xin, c->fe_scratch.p);
+    }
+    if (rt != 0) return FH_OK;
+    HIP_TRY(c, hipGetLastError());
+    *done = true;
+    return FH_OK;
+}
+
+// the per-element kernels of the map (solver_kernels.hpp) for the context's operator: the element diagonals (x null) or the element vectors
+// of x into fe[a][e][c]
+template <int OP>
+static void mf_elements_launch(fh_ctx* c, const KArgs& a, const unsigned char* active, const double* x, double* fe) {
+    const dim3 grid((unsigned)((c->E + 255) / 256));
+    if (c->ei.d == 2) {
+        if (x) hipLaunchKernelGGL((k_mf_apply_elements<2, OpT<OP, 2>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, x, fe);
+        else hipLaunchKernelGGL((k_mf_diagonal_elements<2, OpT<OP, 2>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+    } else {
+        if (x) hipLaunchKernelGGL((k_mf_apply_elements<3, OpT<OP, 3>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, x, fe);
+        else hipLaunchKernelGGL((k_mf_diagonal_elements<3, OpT<OP, 3>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+    }
+}
+
+// one quadrature table (or one group of a rule-set table): the element diagonals (xin null) or the element vectors of the operand xin ADDED
+// to out -- the tiles where they cover it, else the per-element kernels and one thread per node over its (element, local node) entries in order
+static int mf_single(fh_ctx* c, const double* xin, double* out, uint64_t* failed) {
     int rc = reset_status(c);
     if (rc) return rc;
     if (c->E == 0) return FH_OK;
     KArgs a;
     fill_common(c, a);
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    a.work_begin = 0;
+    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
     const int S = c->S();
-    if (element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->env("FENRIS_HIP_NO_VECTOR_TILES")) {
-        rc = ensure_vector_tiles(c);
-        if (rc) return rc;
-        if (!c->vt_bad) {
-            const size_t need = (size_t)c->vt.v.npartials * S;
-            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-            if (vector_tiles_diagonal_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p) == 0) {
-                HIP_TRY(c, hipGetLastError());
-                HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, out));
-                return read_status(c, failed);
-            }
-        }
+    bool done;
+    rc = mf_tiles_pass(c, a, xin, &done);
+    if (rc) return rc;
+    if (done) {
+        if (xin) c->last_kernel = c->op <= FH_LINEAR_ELASTIC ? "k_element_pass_tiled + k_vector_from_partials" : "k_tangent_tiled + k_vector_from_partials";
+        HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, out));
+        return read_status(c, failed);
     }
-    // any element kind: element diagonals by local node, then one thread per node over its (element, local node) entries in order
     rc = build_source_adjacency(c);
     if (rc) return rc;
-    DevBuf<double> fe;
-    HIP_TRY(c, fe.alloc((size_t)c->E * c->ei.n * S));
-    const int grid = (int)((c->E + 255) / 256);
-    const int D = c->ei.d;
-#define DG(DV, SV, OPV) hipLaunchKernelGGL((k_mf_diagonal_elements<DV, SV, OPV>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe.p)
-    if (c->op == FH_LAPLACE) { if (D == 2) DG(2, 1, FH_LAPLACE); else DG(3, 1, FH_LAPLACE); }
-    else { if (D == 2) DG(2, 2, FH_LINEAR_ELASTIC); else DG(3, 3, FH_LINEAR_ELASTIC); }
-#undef DG
+    const size_t need = (size_t)c->E * c->ei.n * S;
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    switch (c->op) {
+        case FH_LAPLACE: mf_elements_launch<FH_LAPLACE>(c, a, active, xin, c->fe_scratch.p); break;
+        case FH_LINEAR_ELASTIC: mf_elements_launch<FH_LINEAR_ELASTIC>(c, a, active, xin, c->fe_scratch.p); break;
+        case FH_NEO_HOOKEAN: mf_elements_launch<FH_NEO_HOOKEAN>(c, a, active, xin, c->fe_scratch.p); break;
+        default: mf_elements_launch<FH_STVK>(c, a, active, xin, c->fe_scratch.p); break;
+    }
     HIP_TRY(c, hipGetLastError());
-    rc = launch_vector_from_elements_soa(c, S, fe.p, out, c->src_n2e_off.p, c->src_n2e.p);
+    if (xin) c->last_kernel = "k_mf_apply_elements + k_vector_from_elements_soa";
+    rc = launch_vector_from_elements_soa(c, S, c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
     if (rc) return rc;
-    return read_status(c, failed);   // (synchronises: fe is released on return)
+    return read_status(c, failed);
 }
 
-// the diagonal of A into diag_dev; with_scale: and, with Dirichlet nodes set, the scale of their rows (c->mf_scale) and their diagonal = scale
+// the diagonal into diag_dev; with_scale: and, with Dirichlet nodes set, the scale of their rows (c->mf_scale) and their diagonal = scale
 int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale) {
     const int n = c->S() * (int)c->N;
     HIP_TRY(c, hipMemsetAsync(diag_dev, 0, sizeof(double) * (size_t)n, c->stream));
     uint64_t failed = 0;
-    int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_diagonal_single(c, diag_dev, f); })
-                          : mf_diagonal_single(c, diag_dev, &failed);
+    int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_single(c, nullptr, diag_dev, f); })
+                          : mf_single(c, nullptr, diag_dev, &failed);
     if (rc) return rc;
     if (c->mf_num_dirichlet && with_scale) {
         rc = mf_scale_from(c, diag_dev);
         if (rc) return rc;
-        mf_scale_key_now(c, c->mf_scale_key);
         hipLaunchKernelGGL(k_mf_dirichlet_diag, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->S(), c->mf_dmask.p, c->mf_scale.p, diag_dev);
         HIP_TRY(c, hipGetLastError());
     }
     return FH_OK;
 }
 
-// one quadrature table (or one group of a rule-set table): the element vectors of the operand xin ADDED to y -- the tiles where they
-// exist (the residual's element pass fed xin), else k_mf_apply_elements by local node and one thread per node over its entries in order
-static int mf_apply_single(fh_ctx* c, const double* xin, double* y, uint64_t* failed) {
-    int rc = reset_status(c);
-    if (rc) return rc;
-    if (c->E == 0) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
-    a.u = xin;
-    a.work_begin = 0;
-    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    const int S = c->S();
-    if (element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->env("FENRIS_HIP_NO_VECTOR_TILES")) {
-        rc = ensure_vector_tiles(c);
-        if (rc) return rc;
-        if (!c->vt_bad) {
-            const size_t need = (size_t)c->vt.v.npartials * S;
-            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-            if (vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p) == 0) {
-                HIP_TRY(c, hipGetLastError());
-                c->last_kernel = "k_element_pass_tiled + k_vector_from_partials";
-                HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, y));
-                return read_status(c, failed);
-            }
-        }
-    }
-    rc = build_source_adjacency(c);
-    if (rc) return rc;
-    const size_t need = (size_t)c->E * c->ei.n * S;
-    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-    const int grid = (int)((c->E + 255) / 256);
-    const int D = c->ei.d;
-#define AP(DV, SV, OPV) hipLaunchKernelGGL((k_mf_apply_elements<DV, SV, OPV>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, xin, c->fe_scratch.p)
-    if (c->op == FH_LAPLACE) { if (D == 2) AP(2, 1, FH_LAPLACE); else AP(3, 1, FH_LAPLACE); }
-    else { if (D == 2) AP(2, 2, FH_LINEAR_ELASTIC); else AP(3, 3, FH_LINEAR_ELASTIC); }
-#undef AP
-    HIP_TRY(c, hipGetLastError());
-    c->last_kernel = "k_mf_apply_elements + k_vector_from_elements_soa";
-    rc = launch_vector_from_elements_soa(c, S, c->fe_scratch.p, y, c->src_n2e_off.p, c->src_n2e.p);
-    if (rc) return rc;
-    return read_status(c, failed);
-}
-
-// y = A x.  The scale of the Dirichlet rows must be in c->mf_scale (mf_diagonal).  dot_scratch != null: per-workgroup partials of x . y
+// y = T(u) x.  The scale of the Dirichlet rows must be in c->mf_scale (mf_diagonal).  dot_scratch != null: per-workgroup partials of x . y
 // go to it (*partials of them, in order).  Singular Jacobians land in the status slot: the caller resets and reads it.
 int mf_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials) {
     const int S = c->S(), N = (int)c->N, n = S * N;
@@ -680,38 +676,33 @@ int mf_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch,
         HIP_TRY(c, hipGetLastError());
         xin = c->mf_xm.p;
     }
-    if (c->E > 0 && mf_tiles(c)) {
-        int rc = ensure_vector_tiles(c);
+    if (c->E > 0 && !c->rs.active) {
+        KArgs a;
+        fill_common(c, a);
+        a.work_begin = 0;
+        a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
+        bool done;
+        int rc = mf_tiles_pass(c, a, xin, &done);
         if (rc) return rc;
-        if (!c->vt_bad) {
-            const size_t need = (size_t)c->vt.v.npartials * S;
-            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-            KArgs a;
-            fill_common(c, a);
-            a.u = xin;
-            a.work_begin = 0;
-            a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-            if (vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, c->has_mask ? c->active.p : nullptr, c->fe_scratch.p) == 0) {
-                HIP_TRY(c, hipGetLastError());
-                const int g = vector_tiles_operator_partials(N);
-                double* dp = nullptr;
-                if (dot_scratch) {
-                    if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
-                    dp = dot_scratch->p;
-                    *partials = g;
-                }
-                c->last_kernel = "k_element_pass_tiled + k_operator_from_partials";
-                HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp));
-                return FH_OK;
+        if (done) {
+            const int g = vector_tiles_operator_partials(N);
+            double* dp = nullptr;
+            if (dot_scratch) {
+                if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+                dp = dot_scratch->p;
+                *partials = g;
             }
+            c->last_kernel = c->op <= FH_LINEAR_ELASTIC ? "k_element_pass_tiled + k_operator_from_partials" : "k_tangent_tiled + k_operator_from_partials";
+            HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp));
+            return FH_OK;
         }
     }
     // elsewhere (kinds outside the tiles, rule-set groups, no tile tables): the element vectors of the operand accumulated into y = 0 without
     // atomics, group by group; then the scale, the Dirichlet rows and the partials of x . y
     HIP_TRY(c, hipMemsetAsync(y, 0, sizeof(double) * (size_t)n, c->stream));
     uint64_t failed = 0;
-    const int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_apply_single(c, xin, y, f); })
-                                : mf_apply_single(c, xin, y, &failed);
+    const int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_single(c, xin, y, f); })
+                                : mf_single(c, xin, y, &failed);
     if (rc) return rc;
     const int g = (n + 255) / 256;
     double* dp = nullptr;
@@ -724,6 +715,43 @@ int mf_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch,
         hipLaunchKernelGGL(k_mf_finish, dim3(g), dim3(256), 0, c->stream, n, S, x, dmask, c->mf_scale.p, xbits, y, dp);
         HIP_TRY(c, hipGetLastError());
     }
+    return FH_OK;
+}
+
+// the entry points: y = T(u) x (the scale of the Dirichlet rows formed again only when what it depends on has changed), and the diagonal
+static int mf_apply_entry(fh_ctx* c, const char* who, int max_op, const double* x_dev, double* y_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    int rc = mf_ready(c, who, max_op);
+    if (rc) return rc;
+    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    if (c->N == 0) return FH_OK;
+    unsigned long long key[4];
+    mf_scale_key_now(c, key);
+    if (c->mf_num_dirichlet && !std::equal(key, key + 4, c->mf_scale_key)) {
+        DevBuf<double> diag;
+        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
+        rc = mf_diagonal(c, diag.p, true);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    rc = reset_status(c);
+    if (rc) return rc;
+    rc = mf_apply(c, x_dev, y_dev, nullptr, nullptr);
+    if (rc) return rc;
+    return read_status(c, nullptr);
+}
+
+static int mf_diagonal_entry(fh_ctx* c, const char* who, int max_op, double* diag_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    int rc = mf_ready(c, who, max_op);
+    if (rc) return rc;
+    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    if (c->N == 0) return FH_OK;
+    rc = mf_diagonal(c, diag_dev, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FH_OK;
 }
 
@@ -751,254 +779,12 @@ int fh_set_operator_dirichlet_nodes(fh_ctx* c, const uint64_t* nodes, uint64_t n
 }
 
 int fh_apply_operator_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
-    if (!c) return FH_BAD_ARGUMENT;
-    DevGuard dev_guard_(c->device);
-    int rc = mf_ready(c, "fh_apply_operator_dev");
-    if (rc) return rc;
-    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, "fh_apply_operator_dev: null argument");
-    if (c->N == 0) return FH_OK;
-    unsigned long long key[3];
-    mf_scale_key_now(c, key);
-    if (c->mf_num_dirichlet && (key[0] != c->mf_scale_key[0] || key[1] != c->mf_scale_key[1] || key[2] != c->mf_scale_key[2])) {
-        // the scale of the Dirichlet rows comes from the diagonal: formed again only when what it depends on has changed
-        DevBuf<double> diag;
-        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
-        rc = mf_diagonal(c, diag.p, true);
-        if (rc) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    rc = reset_status(c);
-    if (rc) return rc;
-    rc = mf_apply(c, x_dev, y_dev, nullptr, nullptr);
-    if (rc) return rc;
-    return read_status(c, nullptr);
+    return mf_apply_entry(c, "fh_apply_operator_dev", FH_LINEAR_ELASTIC, x_dev, y_dev);
 }
-
-int fh_operator_diagonal_dev(fh_ctx* c, double* diag_dev) {
-    if (!c) return FH_BAD_ARGUMENT;
-    DevGuard dev_guard_(c->device);
-    int rc = mf_ready(c, "fh_operator_diagonal_dev");
-    if (rc) return rc;
-    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, "fh_operator_diagonal_dev: null argument");
-    if (c->N == 0) return FH_OK;
-    rc = mf_diagonal(c, diag_dev, true);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FH_OK;
-}
-
-}  // extern "C"
-
-// ---- matrix-free tangent: y = T(u) x with T(u) = dr/du at the context's u (the matrix fh_assemble_matrix forms for the same context), and
-// its diagonal, without a pattern or values, for every material.  The element pass gathers u and the operand per element and forms
-// dP(F)[grad x^T] per point (tangent_lin / tangent_apply, element_pass.hpp): x enters linearly, so no scaling of the operand is needed.
-// Same machinery as the operator above: tiles with k_operator_from_partials where they exist, else one thread per element and ordered
-// node sums; the operator's Dirichlet nodes, with the scale taken from the tangent's own diagonal (mt_scale, keyed on u as well).
-int mt_ready(fh_ctx* c, const char* who) {
-    if (c->op > FH_STVK)
-        return c->fail(FH_UNSUPPORTED, std::string(who) + ": the matrix-free tangent covers FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN and FH_STVK");
-    const int rc = check_ready(c, who, false);
-    if (rc) return rc;
-    if (c->S() < 1 || c->S() > 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": solution dim must be 1..3");
-    return FH_OK;
-}
-
-static void mt_scale_key_now(const fh_ctx* c, unsigned long long (&k)[4]) {
-    k[0] = c->struct_gen;
-    k[1] = c->topo_gen;
-    k[2] = c->geom_gen;
-    k[3] = c->u_gen;
-}
-
-#define MT_FOR_OP(OPV, CALL)                                      \
-    switch (OPV) {                                                \
-        case FH_LAPLACE: CALL(FH_LAPLACE); break;                 \
-        case FH_LINEAR_ELASTIC: CALL(FH_LINEAR_ELASTIC); break;   \
-        case FH_NEO_HOOKEAN: CALL(FH_NEO_HOOKEAN); break;         \
-        default: CALL(FH_STVK); break;                            \
-    }
-
-// one quadrature table (or one group of a rule-set table): the element diagonals of the tangent ADDED to out
-static int mt_diagonal_single(fh_ctx* c, double* out, uint64_t* failed) {
-    int rc = reset_status(c);
-    if (rc) return rc;
-    if (c->E == 0) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    const int S = c->S();
-    if (mf_tiles(c)) {
-        rc = ensure_vector_tiles(c);
-        if (rc) return rc;
-        if (!c->vt_bad) {
-            const size_t need = (size_t)c->vt.v.npartials * S;
-            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-            if (vector_tiles_tangent_diagonal_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p) == 0) {
-                HIP_TRY(c, hipGetLastError());
-                HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, out));
-                return read_status(c, failed);
-            }
-        }
-    }
-    rc = build_source_adjacency(c);
-    if (rc) return rc;
-    DevBuf<double> fe;
-    HIP_TRY(c, fe.alloc((size_t)c->E * c->ei.n * S));
-    const int grid = (int)((c->E + 255) / 256);
-    const int D = c->ei.d;
-#define MT_DG(OPC)                                                                                                                                      \
-    if (D == 2) hipLaunchKernelGGL((k_mf_tangent_diagonal_elements<2, OpT<OPC, 2>::S, OPC>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe.p); \
-    else hipLaunchKernelGGL((k_mf_tangent_diagonal_elements<3, OpT<OPC, 3>::S, OPC>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe.p)
-    MT_FOR_OP(c->op, MT_DG)
-#undef MT_DG
-    HIP_TRY(c, hipGetLastError());
-    rc = launch_vector_from_elements_soa(c, S, fe.p, out, c->src_n2e_off.p, c->src_n2e.p);
-    if (rc) return rc;
-    return read_status(c, failed);   // (synchronises: fe is released on return)
-}
-
-// the diagonal of T(u) into diag_dev; with_scale: and, with Dirichlet nodes set, the scale of their rows (c->mt_scale) and their diagonal = scale
-int mt_diagonal(fh_ctx* c, double* diag_dev, bool with_scale) {
-    const int n = c->S() * (int)c->N;
-    HIP_TRY(c, hipMemsetAsync(diag_dev, 0, sizeof(double) * (size_t)n, c->stream));
-    uint64_t failed = 0;
-    int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mt_diagonal_single(c, diag_dev, f); })
-                          : mt_diagonal_single(c, diag_dev, &failed);
-    if (rc) return rc;
-    if (c->mf_num_dirichlet && with_scale) {
-        DevBuf<unsigned long long> first;
-        HIP_TRY(c, first.alloc(1));
-        if (!c->mt_scale.p) HIP_TRY(c, c->mt_scale.alloc(1));
-        HIP_TRY(c, hipMemsetAsync(first.p, 0xff, sizeof(unsigned long long), c->stream));
-        if (n) hipLaunchKernelGGL(k_mf_first_nonzero, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, diag_dev, first.p);
-        hipLaunchKernelGGL(k_mf_scale, dim3(1), dim3(64), 0, c->stream, diag_dev, first.p, c->mt_scale.p);
-        hipLaunchKernelGGL(k_mf_dirichlet_diag, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->S(), c->mf_dmask.p, c->mt_scale.p, diag_dev);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (first is released on return)
-        mt_scale_key_now(c, c->mt_scale_key);
-    }
-    return FH_OK;
-}
-
-// one quadrature table (or one group of a rule-set table) off the tiles: the tangent's element vectors of the operand xin ADDED to y
-static int mt_apply_single(fh_ctx* c, const double* xin, double* y, uint64_t* failed) {
-    int rc = reset_status(c);
-    if (rc) return rc;
-    if (c->E == 0) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    const int S = c->S();
-    rc = build_source_adjacency(c);
-    if (rc) return rc;
-    const size_t need = (size_t)c->E * c->ei.n * S;
-    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-    const int grid = (int)((c->E + 255) / 256);
-    const int D = c->ei.d;
-#define MT_AP(OPC)                                                                                                                                      \
-    if (D == 2) hipLaunchKernelGGL((k_mf_tangent_elements<2, OpT<OPC, 2>::S, OPC>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, xin, c->fe_scratch.p); \
-    else hipLaunchKernelGGL((k_mf_tangent_elements<3, OpT<OPC, 3>::S, OPC>), dim3(grid), dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, xin, c->fe_scratch.p)
-    MT_FOR_OP(c->op, MT_AP)
-#undef MT_AP
-    HIP_TRY(c, hipGetLastError());
-    c->last_kernel = "k_mf_tangent_elements + k_vector_from_elements_soa";
-    rc = launch_vector_from_elements_soa(c, S, c->fe_scratch.p, y, c->src_n2e_off.p, c->src_n2e.p);
-    if (rc) return rc;
-    return read_status(c, failed);
-}
-#undef MT_FOR_OP
-
-// y = T(u) x.  The scale of the Dirichlet rows must be in c->mt_scale (mt_diagonal).  dot_scratch != null: per-workgroup partials of x . y
-// go to it (*partials of them, in order).  Singular Jacobians land in the status slot: the caller resets and reads it.
-int mt_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials) {
-    const int S = c->S(), N = (int)c->N, n = S * N;
-    const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
-    const double* xin = x;
-    if (dmask) {   // the columns of the Dirichlet nodes vanish: their entries of the operand are zeroed
-        if (c->mf_xm.n < (size_t)n) HIP_TRY(c, c->mf_xm.alloc((size_t)n));
-        hipLaunchKernelGGL(k_mf_operand, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, S, x, dmask, nullptr, c->mf_xm.p);
-        HIP_TRY(c, hipGetLastError());
-        xin = c->mf_xm.p;
-    }
-    if (c->E > 0 && mf_tiles(c)) {
-        int rc = ensure_vector_tiles(c);
-        if (rc) return rc;
-        if (!c->vt_bad) {
-            const size_t need = (size_t)c->vt.v.npartials * S;
-            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-            KArgs a;
-            fill_common(c, a);
-            if (vector_tiles_tangent_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, c->has_mask ? c->active.p : nullptr, xin, c->fe_scratch.p) == 0) {
-                HIP_TRY(c, hipGetLastError());
-                const int g = vector_tiles_operator_partials(N);
-                double* dp = nullptr;
-                if (dot_scratch) {
-                    if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
-                    dp = dot_scratch->p;
-                    *partials = g;
-                }
-                c->last_kernel = "k_tangent_tiled + k_operator_from_partials";
-                HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mt_scale.p, nullptr, y, dp));
-                return FH_OK;
-            }
-        }
-    }
-    HIP_TRY(c, hipMemsetAsync(y, 0, sizeof(double) * (size_t)n, c->stream));
-    uint64_t failed = 0;
-    const int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mt_apply_single(c, xin, y, f); })
-                                : mt_apply_single(c, xin, y, &failed);
-    if (rc) return rc;
-    const int g = (n + 255) / 256;
-    double* dp = nullptr;
-    if (dot_scratch) {
-        if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
-        dp = dot_scratch->p;
-        *partials = g;
-    }
-    if (dmask || dp) {
-        hipLaunchKernelGGL(k_mf_finish, dim3(g), dim3(256), 0, c->stream, n, S, x, dmask, c->mt_scale.p, nullptr, y, dp);
-        HIP_TRY(c, hipGetLastError());
-    }
-    return FH_OK;
-}
-
-extern "C" {
-
+int fh_operator_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_operator_diagonal_dev", FH_LINEAR_ELASTIC, diag_dev); }
 int fh_apply_tangent_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
-    if (!c) return FH_BAD_ARGUMENT;
-    DevGuard dev_guard_(c->device);
-    int rc = mt_ready(c, "fh_apply_tangent_dev");
-    if (rc) return rc;
-    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, "fh_apply_tangent_dev: null argument");
-    if (c->N == 0) return FH_OK;
-    unsigned long long key[4];
-    mt_scale_key_now(c, key);
-    if (c->mf_num_dirichlet && (key[0] != c->mt_scale_key[0] || key[1] != c->mt_scale_key[1] || key[2] != c->mt_scale_key[2] ||
-                                key[3] != c->mt_scale_key[3])) {
-        // the scale of the Dirichlet rows comes from the diagonal of T(u): formed again when what it depends on, u included, has changed
-        DevBuf<double> diag;
-        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
-        rc = mt_diagonal(c, diag.p, true);
-        if (rc) return rc;
-    }
-    rc = reset_status(c);
-    if (rc) return rc;
-    rc = mt_apply(c, x_dev, y_dev, nullptr, nullptr);
-    if (rc) return rc;
-    return read_status(c, nullptr);
+    return mf_apply_entry(c, "fh_apply_tangent_dev", FH_STVK, x_dev, y_dev);
 }
-
-int fh_tangent_diagonal_dev(fh_ctx* c, double* diag_dev) {
-    if (!c) return FH_BAD_ARGUMENT;
-    DevGuard dev_guard_(c->device);
-    int rc = mt_ready(c, "fh_tangent_diagonal_dev");
-    if (rc) return rc;
-    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, "fh_tangent_diagonal_dev: null argument");
-    if (c->N == 0) return FH_OK;
-    rc = mt_diagonal(c, diag_dev, true);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FH_OK;
-}
+int fh_tangent_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_tangent_diagonal_dev", FH_STVK, diag_dev); }
 
 }  // extern "C"

@@ -357,74 +357,47 @@ static __global__ void __launch_bounds__(256) k_mf_dirichlet_diag(int n, int S, 
     if (i < n && dmask[i / S]) diag[i] = *scale;
 }
 
-// diagonal of the element matrices of any element kind (the kinds outside the tiles: Hex27, Tet10, Quad9, Tri6, Hex20, Tet20), one
-// thread per element, the tables walked at run time like k_error_squared: J from the geometry vertices, g_a = J^-T ghat_a, entries as
-// diagonal_element_body (element_pass.hpp).  fe[a][e][c] for k_vector_from_elements_soa; inactive elements (active[e] == 0) write zeros.
-template <int D, int S, int OP>
-__global__ void __launch_bounds__(256) k_mf_diagonal_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= a.num_elements) return;
-    const bool live = !active || active[e] != 0;
-    const int* nodes = a.conn + (size_t)e * N;
-    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
-    for (int n = 0; n < N; ++n) {
-        double acc[S];
+// ---- the matrix-free map off the tiles (the kinds outside them: Hex27, Tet10, Quad9, Tri6, Hex20, Tet20; a mesh without tile tables):
+// one thread per element, the tables walked at run time like k_error_squared, fe[a][e][c] for k_vector_from_elements_soa.
+// Point q of element e: J from the geometry vertices, J^-1 and s = w |det J| (false: det J == 0, the caller reports it) ...
+template <int D>
+__device__ __forceinline__ bool mf_point(const KArgs& a, const int* nodes, int NG, int q, double (&Ji)[D][D], double& s) {
+    double J[D][D];
 #pragma unroll
-        for (int k = 0; k < S; ++k) acc[k] = 0.0;
-        for (int q = 0; q < a.nq && live; ++q) {
-            double J[D][D];
+    for (int r = 0; r < D; ++r)
 #pragma unroll
-            for (int r = 0; r < D; ++r)
+        for (int c = 0; c < D; ++c) J[r][c] = 0.0;
+    for (int g = 0; g < NG; ++g) {
+        const double* v = a.verts + (size_t)nodes[g] * D;
+        const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
 #pragma unroll
-                for (int c = 0; c < D; ++c) J[r][c] = 0.0;
-            for (int g = 0; g < NG; ++g) {
-                const double* v = a.verts + (size_t)nodes[g] * D;
-                const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
+        for (int r = 0; r < D; ++r)
 #pragma unroll
-                for (int r = 0; r < D; ++r)
+            for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
+    }
+    const double detJ = det_small<D>(J);
+    if (detJ == 0.0) return false;
+    inv_small(J, detJ, Ji);
+    s = a.qw[q] * fabs(detJ);
+    return true;
+}
+// ... and g_n = J^-T ghat_n, the physical gradient of basis function n there
+template <int D>
+__device__ __forceinline__ void mf_grad(const KArgs& a, int N, int q, int n, const double (&Ji)[D][D], double (&g)[D]) {
+    const double* gr = a.gref + ((size_t)q * N + n) * D;
 #pragma unroll
-                    for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
-            }
-            const double detJ = det_small<D>(J);
-            if (detJ == 0.0) {
-                if (n == 0) report_singular(a.status, e);
-                continue;
-            }
-            double Ji[D][D];
-            inv_small(J, detJ, Ji);
-            const double s = a.qw[q] * fabs(detJ);
-            double mu = 0.0, lambda = 0.0;
-            if (OP != FH_LAPLACE) {
-                if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
-                else { mu = a.qparams[2 * q]; lambda = a.qparams[2 * q + 1]; }
-            }
-            const double* gr = a.gref + ((size_t)q * N + n) * D;
-            double g[D], gsq = 0.0;
+    for (int r = 0; r < D; ++r) {
+        double t = 0.0;
 #pragma unroll
-            for (int r = 0; r < D; ++r) {
-                double t = 0.0;
-#pragma unroll
-                for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
-                g[r] = t;
-                gsq = fma(t, t, gsq);
-            }
-            if constexpr (OP == FH_LAPLACE) {
-                acc[0] = fma(s, gsq, acc[0]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < S; ++k) acc[k] = fma(s, mu * (gsq + g[k] * g[k]) + lambda * (g[k] * g[k]), acc[k]);
-            }
-        }
-        double* dst = fe + ((size_t)n * (size_t)a.num_elements + (size_t)e) * S;
-#pragma unroll
-        for (int k = 0; k < S; ++k) dst[k] = acc[k];
+        for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
+        g[r] = t;
     }
 }
 
-// y = A x for any element kind, deterministic (the kinds outside the tiles, rule-set groups, a mesh without tile tables): one thread per
-// element, the tables walked at run time like k_mf_diagonal_elements; grad u = J^-T sum_n ghat_n u_n^T, the linear stress formed from grad u
-// directly (Laplace: grad u; LinearElastic: 2 mu sym(grad u) + lambda tr(grad u) I -- the terms of material_point without F), element
-// vectors f_n = w |det J| P g_n by local node, fe[a][e][c], for k_vector_from_elements_soa.  Inactive elements write zeros.
+// y = T(u) x (= A x for FH_LAPLACE and FH_LINEAR_ELASTIC) for any element kind, deterministic: grad x = J^-T sum_n ghat_n x_n^T per point (and
+// grad u from a.u, may be null: zero, for the nonlinear operators only), dP(F)[grad x^T] by tangent_lin / tangent_apply (element_pass.hpp;
+// for the linear operators the stress of material_point without F), element vectors f_n = w |det J| dP g_n by local node.  Inactive elements
+// write zeros.
 template <int D, int S, int OP>
 __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N, int NG, const unsigned char* active, const double* x, double* fe) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -438,126 +411,11 @@ __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N,
     if (!live) return;
     const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
     for (int q = 0; q < a.nq; ++q) {
-        double J[D][D];
-#pragma unroll
-        for (int r = 0; r < D; ++r)
-#pragma unroll
-            for (int c = 0; c < D; ++c) J[r][c] = 0.0;
-        for (int g = 0; g < NG; ++g) {
-            const double* v = a.verts + (size_t)nodes[g] * D;
-            const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
-#pragma unroll
-            for (int r = 0; r < D; ++r)
-#pragma unroll
-                for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
-        }
-        const double detJ = det_small<D>(J);
-        if (detJ == 0.0) {
+        double Ji[D][D], s;
+        if (!mf_point<D>(a, nodes, NG, q, Ji, s)) {
             report_singular(a.status, e);
             continue;
         }
-        double Ji[D][D];
-        inv_small(J, detJ, Ji);
-        const double s = a.qw[q] * fabs(detJ);
-        auto grad = [&](int n, double (&g)[D]) {
-            const double* gr = a.gref + ((size_t)q * N + n) * D;
-#pragma unroll
-            for (int r = 0; r < D; ++r) {
-                double t = 0.0;
-#pragma unroll
-                for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
-                g[r] = t;
-            }
-        };
-        double gu[D][S];
-#pragma unroll
-        for (int r = 0; r < D; ++r)
-#pragma unroll
-            for (int k = 0; k < S; ++k) gu[r][k] = 0.0;
-        for (int n = 0; n < N; ++n) {
-            double g[D];
-            grad(n, g);
-#pragma unroll
-            for (int r = 0; r < D; ++r)
-#pragma unroll
-                for (int k = 0; k < S; ++k) gu[r][k] = fma(g[r], x[(size_t)nodes[n] * S + k], gu[r][k]);
-        }
-        double P[S][D];
-        if constexpr (OP == FH_LAPLACE) {
-#pragma unroll
-            for (int r = 0; r < D; ++r) P[0][r] = gu[r][0];
-        } else {
-            const double mu = par_e ? par_e[2 * q] : a.qparams[2 * q], lambda = par_e ? par_e[2 * q + 1] : a.qparams[2 * q + 1];
-            double tr = 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i) tr += gu[i][i];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) P[i][j] = mu * (gu[i][j] + gu[j][i]) + (i == j ? lambda * tr : 0.0);
-        }
-        for (int n = 0; n < N; ++n) {
-            double g[D];
-            grad(n, g);
-            double* o = out(n);
-#pragma unroll
-            for (int i = 0; i < S; ++i) {
-                double t = 0.0;
-#pragma unroll
-                for (int r = 0; r < D; ++r) t = fma(P[i][r], g[r], t);
-                o[i] = fma(s, t, o[i]);
-            }
-        }
-    }
-}
-
-// tangent of the residual T(u) x for any element kind, deterministic (the kinds outside the tiles, rule-set groups, a mesh without tile
-// tables): k_mf_apply_elements with u (a.u, may be null: zero) and the operand x both gathered, grad u and grad x per point, y_n += s dP(F)[H] g_n
-// (tangent_lin / tangent_apply, element_pass.hpp), fe[a][e][c] for k_vector_from_elements_soa.  Inactive elements write zeros.
-template <int D, int S, int OP>
-__global__ void __launch_bounds__(256) k_mf_tangent_elements(const KArgs a, int N, int NG, const unsigned char* active, const double* x, double* fe) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= a.num_elements) return;
-    const bool live = !active || active[e] != 0;
-    const int* nodes = a.conn + (size_t)e * N;
-    auto out = [&](int n) { return fe + ((size_t)n * (size_t)a.num_elements + (size_t)e) * S; };
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int k = 0; k < S; ++k) out(n)[k] = 0.0;
-    if (!live) return;
-    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
-    for (int q = 0; q < a.nq; ++q) {
-        double J[D][D];
-#pragma unroll
-        for (int r = 0; r < D; ++r)
-#pragma unroll
-            for (int c = 0; c < D; ++c) J[r][c] = 0.0;
-        for (int g = 0; g < NG; ++g) {
-            const double* v = a.verts + (size_t)nodes[g] * D;
-            const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
-#pragma unroll
-            for (int r = 0; r < D; ++r)
-#pragma unroll
-                for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
-        }
-        const double detJ = det_small<D>(J);
-        if (detJ == 0.0) {
-            report_singular(a.status, e);
-            continue;
-        }
-        double Ji[D][D];
-        inv_small(J, detJ, Ji);
-        const double s = a.qw[q] * fabs(detJ);
-        auto grad = [&](int n, double (&g)[D]) {
-            const double* gr = a.gref + ((size_t)q * N + n) * D;
-#pragma unroll
-            for (int r = 0; r < D; ++r) {
-                double t = 0.0;
-#pragma unroll
-                for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
-                g[r] = t;
-            }
-        };
         double gu[D][S], gx[D][S];
 #pragma unroll
         for (int r = 0; r < D; ++r)
@@ -565,26 +423,28 @@ __global__ void __launch_bounds__(256) k_mf_tangent_elements(const KArgs a, int 
             for (int k = 0; k < S; ++k) { gu[r][k] = 0.0; gx[r][k] = 0.0; }
         for (int n = 0; n < N; ++n) {
             double g[D];
-            grad(n, g);
+            mf_grad<D>(a, N, q, n, Ji, g);
 #pragma unroll
             for (int k = 0; k < S; ++k) {
-                const double uv = a.u ? a.u[(size_t)nodes[n] * S + k] : 0.0, xv = x[(size_t)nodes[n] * S + k];
+                const double xv = x[(size_t)nodes[n] * S + k];
+                double uv = 0.0;
+                if constexpr (OP >= FH_NEO_HOOKEAN) uv = a.u ? a.u[(size_t)nodes[n] * S + k] : 0.0;
 #pragma unroll
                 for (int r = 0; r < D; ++r) {
-                    gu[r][k] = fma(g[r], uv, gu[r][k]);
+                    if constexpr (OP >= FH_NEO_HOOKEAN) gu[r][k] = fma(g[r], uv, gu[r][k]);
                     gx[r][k] = fma(g[r], xv, gx[r][k]);
                 }
             }
         }
-        double mu = 0.0, lambda = 0.0;
-        if (OP != FH_LAPLACE) { mu = par_e ? par_e[2 * q] : a.qparams[2 * q]; lambda = par_e ? par_e[2 * q + 1] : a.qparams[2 * q + 1]; }
+        double mu, lambda;
+        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
         tangent_lin<OP, D, S>(gu, mu, lambda, L);
         double dP[S][D];
         tangent_apply<OP, D, S>(L, gx, dP);
         for (int n = 0; n < N; ++n) {
             double g[D];
-            grad(n, g);
+            mf_grad<D>(a, N, q, n, Ji, g);
             double* o = out(n);
 #pragma unroll
             for (int i = 0; i < S; ++i) {
@@ -597,9 +457,11 @@ __global__ void __launch_bounds__(256) k_mf_tangent_elements(const KArgs a, int 
     }
 }
 
-// diagonal of the tangent for any element kind (tangent_diagonal_body's entries, the tables walked like k_mf_tangent_elements)
+// the diagonal of the same map: entry (n, k) = sum_q s (dP[e_k g_n^T] g_n)_k, in ascending q.  The linear operators in closed form, as
+// diagonal_element_body (element_pass.hpp):  Laplace  s |g_n|^2,  LinearElastic  s (mu (|g_n|^2 + g_n,k^2) + lambda g_n,k^2); the nonlinear
+// ones by tangent_apply on the unit directions, as tangent_diagonal_body.
 template <int D, int S, int OP>
-__global__ void __launch_bounds__(256) k_mf_tangent_diagonal_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
+__global__ void __launch_bounds__(256) k_mf_diagonal_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.num_elements) return;
     const bool live = !active || active[e] != 0;
@@ -611,71 +473,56 @@ __global__ void __launch_bounds__(256) k_mf_tangent_diagonal_elements(const KArg
     if (!live) return;
     const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
     for (int q = 0; q < a.nq; ++q) {
-        double J[D][D];
-#pragma unroll
-        for (int r = 0; r < D; ++r)
-#pragma unroll
-            for (int c = 0; c < D; ++c) J[r][c] = 0.0;
-        for (int g = 0; g < NG; ++g) {
-            const double* v = a.verts + (size_t)nodes[g] * D;
-            const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
-#pragma unroll
-            for (int r = 0; r < D; ++r)
-#pragma unroll
-                for (int c = 0; c < D; ++c) J[r][c] = fma(v[r], gg[c], J[r][c]);
-        }
-        const double detJ = det_small<D>(J);
-        if (detJ == 0.0) {
+        double Ji[D][D], s;
+        if (!mf_point<D>(a, nodes, NG, q, Ji, s)) {
             report_singular(a.status, e);
             continue;
         }
-        double Ji[D][D];
-        inv_small(J, detJ, Ji);
-        const double s = a.qw[q] * fabs(detJ);
-        auto grad = [&](int n, double (&g)[D]) {
-            const double* gr = a.gref + ((size_t)q * N + n) * D;
-#pragma unroll
-            for (int r = 0; r < D; ++r) {
-                double t = 0.0;
-#pragma unroll
-                for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
-                g[r] = t;
-            }
-        };
         double gu[D][S];
 #pragma unroll
         for (int r = 0; r < D; ++r)
 #pragma unroll
             for (int k = 0; k < S; ++k) gu[r][k] = 0.0;
-        for (int n = 0; n < N; ++n) {
-            double g[D];
-            grad(n, g);
+        if constexpr (OP >= FH_NEO_HOOKEAN) {
+            for (int n = 0; n < N; ++n) {
+                double g[D];
+                mf_grad<D>(a, N, q, n, Ji, g);
 #pragma unroll
-            for (int k = 0; k < S; ++k) {
-                const double uv = a.u ? a.u[(size_t)nodes[n] * S + k] : 0.0;
+                for (int k = 0; k < S; ++k) {
+                    const double uv = a.u ? a.u[(size_t)nodes[n] * S + k] : 0.0;
 #pragma unroll
-                for (int r = 0; r < D; ++r) gu[r][k] = fma(g[r], uv, gu[r][k]);
+                    for (int r = 0; r < D; ++r) gu[r][k] = fma(g[r], uv, gu[r][k]);
+                }
             }
         }
-        double mu = 0.0, lambda = 0.0;
-        if (OP != FH_LAPLACE) { mu = par_e ? par_e[2 * q] : a.qparams[2 * q]; lambda = par_e ? par_e[2 * q + 1] : a.qparams[2 * q + 1]; }
+        double mu, lambda;
+        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
         tangent_lin<OP, D, S>(gu, mu, lambda, L);
         for (int n = 0; n < N; ++n) {
-            double g[D];
-            grad(n, g);
+            double g[D], gsq = 0.0;
+            mf_grad<D>(a, N, q, n, Ji, g);
+#pragma unroll
+            for (int r = 0; r < D; ++r) gsq = fma(g[r], g[r], gsq);
             double* o = out(n);
 #pragma unroll
             for (int c = 0; c < S; ++c) {
-                double gx[D][S], dP[S][D];
+                double t;
+                if constexpr (OP == FH_LAPLACE) {
+                    t = gsq;
+                } else if constexpr (OP == FH_LINEAR_ELASTIC) {
+                    t = mu * (gsq + g[c] * g[c]) + lambda * (g[c] * g[c]);
+                } else {
+                    double gx[D][S], dP[S][D];
 #pragma unroll
-                for (int r = 0; r < D; ++r)
+                    for (int r = 0; r < D; ++r)
 #pragma unroll
-                    for (int k = 0; k < S; ++k) gx[r][k] = k == c ? g[r] : 0.0;
-                tangent_apply<OP, D, S>(L, gx, dP);
-                double t = 0.0;
+                        for (int k = 0; k < S; ++k) gx[r][k] = k == c ? g[r] : 0.0;
+                    tangent_apply<OP, D, S>(L, gx, dP);
+                    t = 0.0;
 #pragma unroll
-                for (int r = 0; r < D; ++r) t = fma(dP[c][r], g[r], t);
+                    for (int r = 0; r < D; ++r) t = fma(dP[c][r], g[r], t);
+                }
                 o[c] = fma(s, t, o[c]);
             }
         }

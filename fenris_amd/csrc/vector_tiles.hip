@@ -418,10 +418,12 @@ __global__ void __launch_bounds__(256) k_vector_from_partials(int num_nodes, con
     }
 }
 
-// diagonal of a linear operator (diagonal_element_body) over the tiles: the tile's node sums, partials; k_vector_from_partials adds them
+// diagonal of the matrix-free map over the tiles (diagonal_element_body for the linear operators; tangent_diagonal_body, with u gathered
+// (a.u, may be null: zero), for the nonlinear ones): the tile's node sums, partials; k_vector_from_partials adds them
 template <int EK, int OP, int TS>
 __global__ void __launch_bounds__(TS) k_diagonal_tiled(const KArgs a, const VecTiles t, const unsigned char* active, double* partial) {
     constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
+    constexpr bool lin = OP <= FH_LINEAR_ELASTIC;
     __shared__ double stage[N * S * TS];
     __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
     const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
@@ -430,15 +432,20 @@ __global__ void __launch_bounds__(TS) k_diagonal_tiled(const KArgs a, const VecT
     const bool live = el >= 0 && (!active || active[el] != 0);
     TileSums<N, TS> ts;
     ts.request(t, tile, tid);
-    double X[N][D];
+    double X[N][D], Uv[lin ? 1 : N][S];
 #pragma unroll
     for (int n = 0; n < N; ++n) {
         const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
 #pragma unroll
         for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
+        if constexpr (!lin) {
+#pragma unroll
+            for (int k = 0; k < S; ++k) Uv[n][k] = a.u ? a.u[(size_t)nd * S + k] : 0.0;
+        }
     }
     double f[N][S];
-    diagonal_element_body<D, S, N, OP>(a, el >= 0 ? el : 0, live, X, f);
+    if constexpr (lin) diagonal_element_body<D, S, N, OP>(a, el >= 0 ? el : 0, live, X, f);
+    else tangent_diagonal_body<D, S, N, OP>(a, el >= 0 ? el : 0, live, X, Uv, f);
 #pragma unroll
     for (int n = 0; n < N; ++n)
 #pragma unroll
@@ -446,9 +453,9 @@ __global__ void __launch_bounds__(TS) k_diagonal_tiled(const KArgs a, const VecT
     ts.template sum<S>(t, tile, tid, stage, ents, partial);
 }
 
-// tangent of the residual T(u) x over the tiles (matrix-free, engine_vector.hip): the element pass with both u (a.u, may be null: zero)
-// and the operand x gathered per element; MONO = 1 / 2: Hex8 in the monomial basis (2: every element affine).  The tile's node sums,
-// partials; k_operator_from_partials overwrites y with them.
+// tangent of the residual T(u) x of the nonlinear operators over the tiles (matrix-free, engine_vector.hip): the element pass with both u
+// (a.u, may be null: zero) and the operand x gathered per element; MONO = 1 / 2: Hex8 in the monomial basis (2: every element affine).  The
+// tile's node sums, partials; k_operator_from_partials overwrites y with them.
 template <int EK, int OP, int TS, int MONO = 0>
 __global__ void __launch_bounds__(TS) k_tangent_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const double* x, double* partial) {
     constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
@@ -479,36 +486,6 @@ __global__ void __launch_bounds__(TS) k_tangent_tiled(const KArgs a, const VecTi
     for (int n = 0; n < N; ++n)
 #pragma unroll
         for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;   // (select: a skipped element may hold NaN)
-    ts.template sum<S>(t, tile, tid, stage, ents, partial);
-}
-
-// diagonal of the tangent (tangent_diagonal_body) over the tiles: partials for k_vector_from_partials
-template <int EK, int OP, int TS>
-__global__ void __launch_bounds__(TS) k_tangent_diagonal_tiled(const KArgs a, const VecTiles t, const unsigned char* active, double* partial) {
-    constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
-    __shared__ double stage[N * S * TS];
-    __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    double X[N][D], Uv[N][S];
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
-#pragma unroll
-        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
-#pragma unroll
-        for (int k = 0; k < S; ++k) Uv[n][k] = a.u ? a.u[(size_t)nd * S + k] : 0.0;
-    }
-    double f[N][S];
-    tangent_diagonal_body<D, S, N, OP>(a, el >= 0 ? el : 0, live, X, Uv, f);
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
     ts.template sum<S>(t, tile, tid, stage, ents, partial);
 }
 
@@ -790,6 +767,8 @@ int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const 
     switch (op) {                                                                                                                    \
         case FH_LAPLACE: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_LAPLACE, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
         case FH_LINEAR_ELASTIC: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_LINEAR_ELASTIC, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
+        case FH_NEO_HOOKEAN: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_NEO_HOOKEAN, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
+        case FH_STVK: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_STVK, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
         default: return -1;                                                                                                          \
     }
     switch (elem_kind) {
@@ -818,8 +797,6 @@ int vector_tiles_tangent_pass(int elem_kind, int op, hipStream_t stream, const K
 #define VT_TG1(EKC, OPC, M) hipLaunchKernelGGL((k_tangent_tiled<EKC, OPC, VT_TS, M>), g, dim3(VT_TS), 0, stream, a, t, active, x, partial)
 #define VT_TG(EKC, M)                                                              \
     switch (op) {                                                                  \
-        case FH_LAPLACE: VT_TG1(EKC, FH_LAPLACE, M); return 0;                     \
-        case FH_LINEAR_ELASTIC: VT_TG1(EKC, FH_LINEAR_ELASTIC, M); return 0;       \
         case FH_NEO_HOOKEAN: VT_TG1(EKC, FH_NEO_HOOKEAN, M); return 0;             \
         case FH_STVK: VT_TG1(EKC, FH_STVK, M); return 0;                           \
         default: return -1;                                                        \
@@ -837,29 +814,6 @@ int vector_tiles_tangent_pass(int elem_kind, int op, hipStream_t stream, const K
     }
 #undef VT_TG
 #undef VT_TG1
-}
-
-int vector_tiles_tangent_diagonal_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active,
-                                       double* partial) {
-    const dim3 g(8 * ((t.ntiles + 7) / 8));
-#define VT_TD1(EKC, OPC) hipLaunchKernelGGL((k_tangent_diagonal_tiled<EKC, OPC, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial)
-#define VT_TD(EKC)                                                                 \
-    switch (op) {                                                                  \
-        case FH_LAPLACE: VT_TD1(EKC, FH_LAPLACE); return 0;                        \
-        case FH_LINEAR_ELASTIC: VT_TD1(EKC, FH_LINEAR_ELASTIC); return 0;          \
-        case FH_NEO_HOOKEAN: VT_TD1(EKC, FH_NEO_HOOKEAN); return 0;                \
-        case FH_STVK: VT_TD1(EKC, FH_STVK); return 0;                              \
-        default: return -1;                                                        \
-    }
-    switch (elem_kind) {
-        case FH_QUAD4: VT_TD(FH_QUAD4)
-        case FH_TRI3: VT_TD(FH_TRI3)
-        case FH_TET4: VT_TD(FH_TET4)
-        case FH_HEX8: VT_TD(FH_HEX8)
-        default: return -1;
-    }
-#undef VT_TD
-#undef VT_TD1
 }
 
 }  // namespace fenris_hip

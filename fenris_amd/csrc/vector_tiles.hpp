@@ -52,16 +52,15 @@ int vector_tiles_source_pass(int D, int sdim, int n, bool fact, hipStream_t stre
 hipError_t vector_tiles_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, double* out,
                                   const double* scaled_g = nullptr);
 
-// diagonal of the linear operators (FH_LAPLACE, FH_LINEAR_ELASTIC; diagonal_element_body) over the tiles into partial[P][S]; the
-// caller sums them with vector_tiles_node_pass.  Returns -1 when (elem_kind, op) is not covered.
+// diagonal of the matrix-free map (FH_LAPLACE, FH_LINEAR_ELASTIC: diagonal_element_body; FH_NEO_HOOKEAN, FH_STVK: tangent_diagonal_body at
+// a.u) over the tiles into partial[P][S]; the caller sums them with vector_tiles_node_pass.  Returns -1 when (elem_kind, op) is not covered.
 int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial);
 
-// tangent of the residual at a.u applied to x (k_tangent_tiled), resp. its diagonal, over the tiles into partial[P][S]; every operator.
-// The caller sums them with vector_tiles_operator_node_pass (xbits null), resp. vector_tiles_node_pass.  Returns -1 when elem_kind is not covered.
+// tangent of the residual of FH_NEO_HOOKEAN and FH_STVK at a.u applied to x (k_tangent_tiled) over the tiles into partial[P][S] (the linear
+// operators take vector_tiles_element_pass fed x); the caller sums them with vector_tiles_operator_node_pass (xbits null).  Returns -1 when
+// (elem_kind, op) is not covered.
 int vector_tiles_tangent_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* x,
                               double* partial);
-int vector_tiles_tangent_diagonal_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active,
-                                       double* partial);
 
 // node pass of the matrix-free operator: y = the node sums of the partials, OVERWRITTEN; rows of the nodes with dmask[node] != 0
 // (dmask, scale: device, may be null / unused) are  *scale x; the other rows are multiplied by 2^e (xbits: mf_exponent, may be null).  dot_partial (may be null): one partial of x . y per workgroup

@@ -403,8 +403,9 @@ int fh_cg_solve_matrix_free_dev(fh_ctx*, const double* b_dev, double* x_dev, int
                                 uint64_t* num_iterations);
 /* ---- matrix-free tangent: T(u) = dr/du at the context's u (fh_set_u*; zeros when none is set), r the residual of fh_assemble_vector
  * (elliptic.rs:457-605).  T(u) is the matrix fh_assemble_matrix assembles for the same context, K_IJ = sum_q w |det J| C(F_q; g_I, g_J) with C
- * the stress contraction (fenris-solid/src/materials.rs); for FH_LAPLACE and FH_LINEAR_ELASTIC it is the operator above.  Per point the
- * element vector of x is  y_a += w |det J| dP(F)[H] g_a,  F = I + grad u^T, H = grad x^T:
+ * the stress contraction (fenris-solid/src/materials.rs); for FH_LAPLACE and FH_LINEAR_ELASTIC it is the operator above, bit for bit (the
+ * same kernels and the same Dirichlet scale).  Per point the element vector of x is  y_a += w |det J| dP(F)[H] g_a,  F = I + grad u^T,
+ * H = grad x^T:
  *   Laplace h;  LinearElastic mu (H + H^T) + lambda tr(H) I;
  *   NeoHookean mu H + lambda tr(F^-1 H) F^-T + (mu - lambda ln J) F^-T H^T F^-T;
  *   StVK H S + F (lambda tr(dE) I + 2 mu dE), S = lambda tr(E) I + 2 mu E, dE = sym(F^T H).
@@ -413,7 +414,8 @@ int fh_cg_solve_matrix_free_dev(fh_ctx*, const double* b_dev, double* x_dev, int
  * FH_UNSUPPORTED for the mass operators and FH_TENSOR; FH_INVALID_STATE for a missing mesh, operator or table; FH_SINGULAR_JACOBIAN as the
  * residual reports it.  Dirichlet nodes: those of fh_set_operator_dirichlet_nodes, with the same meaning as for fh_apply_operator_dev (the
  * matrix fh_apply_dirichlet_csr_dev leaves of the assembled K(u); scale = |first nonzero diagonal entry| of K(u) in row order, or 1).  The scale
- * is cached apart from the operator's and formed again after the mesh, vertices, operator, table, element mask or u have changed.
+ * is the operator's cache, formed again after the mesh, vertices, operator, table or element mask have changed, and for FH_NEO_HOOKEAN and
+ * FH_STVK also after u has changed.
  *
  * y = T(u) x, both s N doubles on the device; y is OVERWRITTEN, u is read and not changed.  Deterministic on every element kind (no
  * floating-point atomics). */
