@@ -121,6 +121,12 @@ _SIGS = {
     "fh_tangent_diagonal_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_cg_solve_tangent": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_cg_solve_tangent_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, u64p]),
+    "fh_set_mass_density": (C.c_int, [C.c_void_p, f64p, C.c_uint64]),
+    "fh_apply_shifted_tangent_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "fh_shifted_tangent_diagonal_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
+    "fh_cg_solve_shifted_tangent": (C.c_int, [C.c_void_p, C.c_double, C.c_double, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
+    "fh_cg_solve_shifted_tangent_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64,
+                                                  u64p]),
     "fh_estimate_L2_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),
     "fh_estimate_L2_error_squared_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, f64p]),
     "fh_estimate_H1_seminorm_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),

@@ -67,6 +67,7 @@ class Engine:
     def set_mesh(self, mesh: Mesh):
         self._mesh = mesh  # keep the host arrays alive
         self._mf_bound = None  # fh_set_mesh clears the operator's Dirichlet nodes
+        self._mass_bound = None  # ... and the mass density
         self._check(self._lib.fh_set_mesh(self._h, mesh.elem_kind, _ffi.fp(mesh.vertices), mesh.num_nodes(),
                                           _ffi.up(mesh.connectivity), mesh.num_elements()))
 
@@ -74,6 +75,7 @@ class Engine:
         eo, en = _ffi.as_u64(elem_offsets), _ffi.as_u64(elem_nodes)
         en_p = en if len(en) else np.zeros(1, dtype=np.uint64)
         self._mf_bound = None
+        self._mass_bound = None
         self._check(self._lib.fh_set_connectivity_ragged(self._h, sdim, num_nodes, _ffi.up(eo), _ffi.up(en_p), len(eo) - 1))
 
     def set_active_elements(self, mask):
@@ -356,6 +358,32 @@ class Engine:
     def cg_solve_tangent(self, b, x, preconditioner=1, rel_tol=1e-9, max_iter=0):
         """fh_cg_solve_tangent(_dev): cg_solve with the matrix-free tangent"""
         return self._cg_solve_free("tangent", b, x, preconditioner, rel_tol, max_iter)
+
+    # the shifted map (alpha M + beta T(u)) x with the mass of the density set here (one for the mesh, or one per element)
+    def set_mass_density(self, rho):
+        rho = np.ascontiguousarray(np.atleast_1d(np.asarray(rho, dtype=np.float64)).ravel())
+        self._check(self._lib.fh_set_mass_density(self._h, _ffi.fp(rho), len(rho)))
+
+    def apply_shifted_tangent_dev(self, alpha, beta, x_t, y_t):
+        self._check(self._lib.fh_apply_shifted_tangent_dev(self._h, float(alpha), float(beta), C.c_void_p(x_t.data_ptr()),
+                                                           C.c_void_p(y_t.data_ptr())))
+
+    def shifted_tangent_diagonal_dev(self, alpha, beta, diag_t):
+        self._check(self._lib.fh_shifted_tangent_diagonal_dev(self._h, float(alpha), float(beta), C.c_void_p(diag_t.data_ptr())))
+
+    def cg_solve_shifted_tangent(self, alpha, beta, b, x, preconditioner=1, rel_tol=1e-9, max_iter=0):
+        """fh_cg_solve_shifted_tangent(_dev): cg_solve with alpha M + beta T(u)"""
+        it = C.c_uint64(0)
+        if _is_torch(b):
+            rc = self._lib.fh_cg_solve_shifted_tangent_dev(self._h, float(alpha), float(beta), C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()),
+                                                           preconditioner, rel_tol, max_iter, C.byref(it))
+        else:
+            rc = self._lib.fh_cg_solve_shifted_tangent(self._h, float(alpha), float(beta), _ffi.fp(b), _ffi.fp(x), preconditioner, rel_tol,
+                                                       max_iter, C.byref(it))
+        if rc in (7, 8, 9):
+            raise CgSolveError(rc, (self._lib.fh_last_error(self._h) or b"").decode(), int(it.value))
+        self._check(rc)
+        return int(it.value)
 
     def _cg_solve_free(self, which, b, x, preconditioner, rel_tol, max_iter):
         it = C.c_uint64(0)
@@ -996,6 +1024,68 @@ class MatrixFreeTangent(MatrixFreeOperator):
         return self.engine.cg_solve_tangent(b, x, preconditioner, rel_tol, max_iter)
 
 
+class MatrixFreeShiftedTangent(MatrixFreeOperator):
+    """alpha M + beta T(u) of an element assembler (Laplace, LinearElastic, NeoHookean, StVK), the system of an implicit time step (backward
+    Euler: alpha = 1, beta = dt^2), applied without pattern or values.  M is the mass matrix the assembled mass operator forms on the same
+    mesh and quadrature table with this object's density (a scalar for the whole mesh, or one value per element), the scalar mass for
+    Laplace and the vector mass for the materials; T(u) is MatrixFreeTangent's map at the assembler's current u.  Density, coefficients and
+    Dirichlet nodes belong to this object and are handed to the engine before every use, so several such objects may share one assembler.
+    The interface of MatrixFreeOperator (apply, diagonal, cg_solve; ConjugateGradient.with_operator accepts it)."""
+
+    def __init__(self, element_assembler, density, alpha, beta):
+        super().__init__(element_assembler)
+        self._rho = np.ascontiguousarray(np.atleast_1d(np.asarray(density, dtype=np.float64)).ravel()).copy()
+        self.alpha, self.beta = float(alpha), float(beta)
+        self.engine.set_mass_density(self._rho)   # (checks the count now)
+        self.engine._mass_bound = self
+
+    def with_coefficients(self, alpha, beta):
+        """new alpha, beta (e.g. another dt between steps); returns self"""
+        self.alpha, self.beta = float(alpha), float(beta)
+        return self
+
+    def _bind(self, force=False):
+        super()._bind(force)
+        if force or getattr(self.engine, "_mass_bound", None) is not self:
+            self.engine.set_mass_density(self._rho)
+            self.engine._mass_bound = self
+
+    def _apply_dev(self, x_t, y_t):
+        self.engine.apply_shifted_tangent_dev(self.alpha, self.beta, x_t, y_t)
+
+    def _diagonal_dev(self, d_t):
+        self.engine.shifted_tangent_diagonal_dev(self.alpha, self.beta, d_t)
+
+    def _cg_solve(self, b, x, preconditioner, rel_tol, max_iter):
+        return self.engine.cg_solve_shifted_tangent(self.alpha, self.beta, b, x, preconditioner, rel_tol, max_iter)
+
+
+class MatrixFreeMass(MatrixFreeShiftedTangent):
+    """The mass matrix M of MatrixFreeShiftedTangent alone (alpha = 1, beta = 0: u is not read), plus its row-sum lumping."""
+
+    def __init__(self, element_assembler, density):
+        super().__init__(element_assembler, density, 1.0, 0.0)
+
+    def lumped(self, device=False):
+        """M 1 without Dirichlet rows: the row-sum lumped mass for explicit stepping, in one application.  As for any row-sum lumping, some
+        entries can be zero or negative on quadratic kinds (the vertex rows of Tet10 and Tri6, for example)."""
+        import torch
+
+        saved = self._nodes
+        self._nodes = None
+        self._bind(force=True)
+        try:
+            n = self.element_assembler.solution_dim() * self.engine.num_nodes()
+            dev = f"cuda:{self.engine.device}"
+            ones = torch.ones(n, dtype=torch.float64, device=dev)
+            y = torch.empty_like(ones)
+            self.engine.apply_shifted_tangent_dev(1.0, 0.0, ones, y)
+        finally:
+            self._nodes = saved
+            self._bind(force=True)
+        return y if device else y.cpu().numpy()
+
+
 class ConjugateGradient:
     """fenris-sparse/src/cg.rs:196-478, builder style.  The operator is the CSR matrix assembled by an element
     assembler of this package (its engine holds the pattern); values, right-hand side and solution may be numpy
@@ -1009,7 +1099,7 @@ class ConjugateGradient:
         return cls()
 
     def with_operator(self, csr, element_assembler=None):
-        """(csr, element_assembler): the assembled matrix; or one MatrixFreeOperator / MatrixFreeTangent"""
+        """(csr, element_assembler): the assembled matrix; or one MatrixFreeOperator / MatrixFreeTangent / MatrixFreeShiftedTangent"""
         if isinstance(csr, MatrixFreeOperator):
             self._csr, self._asm = csr, csr.element_assembler
         else:

@@ -77,6 +77,15 @@ struct GatherHdr {
     int u_off, U;    // offset into gt_elems, number of unique adjacent elements
 };
 
+// the mass term of the shifted map alpha M + beta T(u) (element_pass.hpp, hex8_mass_point)
+struct MassTerm {
+    double alpha, beta;
+    const double* rho;   // 1 or E densities
+    int per_elem;
+    const double* mom;   // the rule's moments (fh_ctx::qmom: [0] sum w, xi^2, eta^2, zeta^2, eta^2 zeta^2, xi^2 zeta^2, xi^2 eta^2, xi^2 eta^2 zeta^2)
+                         // when the rule is coordinate-symmetric and every element affine, else null
+};
+
 // kernel arguments (plain struct, passed by value)
 struct KArgs {
     // mesh

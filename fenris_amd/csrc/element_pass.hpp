@@ -229,14 +229,62 @@ __device__ __forceinline__ void hex8_wht(double (&v)[8]) {
 // seven squares survive: seven applications of the linear map L to sparse matrices -- and of each result only the columns that meet a
 // non-vanishing moment -- instead of eight full point evaluations: ~640 instead of ~1 200 vector instructions per element.  The same sums as
 // elliptic.rs:506-527 in another order (like the affine stiffness kernel: equal to rounding, checked against the oracle at 1e-12).
-template <int OP, int WHAT, int AFFM = 0, class UAcc>
+// ---- the mass term of the shifted map alpha M + beta T(u) in the monomial basis (engine_vector.hip; the MASS instantiations only).  With
+// x = sum_t c_t m_t (c_0 = the butterfly's sum / 8, the others as above) and N_n = (1/8) sum_t W_tn m_t, the element term
+// y_n = sum_q w |det J| rho N_n(xi_q) x(xi_q) is one more set of moment sums, dk[t] += w |det J| rho x(xi_q) m_t(xi_q), into the SAME
+// accumulators as the stiffness (dk[0] is otherwise zero) and the same synthesis butterfly.  For an affine element and a coordinate-symmetric
+// rule the monomials are orthogonal, sum_q w m_s m_t = mu_t delta_st, so the term is  dk[t] = |det J| rho mu_t c_t: eight multiplies per
+// component.  The stiffness part is scaled by beta.
+// the monomials in binary order (bit 0 xi, bit 1 eta, bit 2 zeta) -> their moment's slot in MassTerm::mom
+__device__ __forceinline__ constexpr int hex8_mom_slot(int t) { return t == 3 ? 6 : t == 4 ? 3 : t == 6 ? 4 : t; }
+// dk[t] += sm x(xi_q) m_t(xi_q), c: the coefficients of x with c[0] not yet divided by 8
+template <int S>
+__device__ __forceinline__ void hex8_mass_point(const double (&c)[S][8], double sm, double xi, double eta, double zeta, double ez, double xz,
+                                                double xe, double (&dk)[S][8]) {
+    const double xez = xi * ez;
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        double xq = 0.125 * c[i][0];
+        xq = fma(c[i][1], xi, xq);
+        xq = fma(c[i][2], eta, xq);
+        xq = fma(c[i][3], xe, xq);
+        xq = fma(c[i][4], zeta, xq);
+        xq = fma(c[i][5], xz, xq);
+        xq = fma(c[i][6], ez, xq);
+        xq = fma(c[i][7], xez, xq);
+        const double v = sm * xq;
+        dk[i][0] += v;
+        dk[i][1] = fma(v, xi, dk[i][1]);
+        dk[i][2] = fma(v, eta, dk[i][2]);
+        dk[i][3] = fma(v, xe, dk[i][3]);
+        dk[i][4] = fma(v, zeta, dk[i][4]);
+        dk[i][5] = fma(v, xz, dk[i][5]);
+        dk[i][6] = fma(v, ez, dk[i][6]);
+        dk[i][7] = fma(v, xez, dk[i][7]);
+    }
+}
+// affine element, symmetric rule: dk[t] = beta dk[t] + sm mu_t c_t  (sm = alpha rho |det J|)
+template <int S>
+__device__ __forceinline__ void hex8_mass_moments(const double (&c)[S][8], double sm, double beta, const double* mom, double (&dk)[S][8]) {
+    const ep_table mq = ep_const(mom);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const double st = sm * mq[hex8_mom_slot(t)];
+#pragma unroll
+        for (int i = 0; i < S; ++i) dk[i][t] = fma(st, t == 0 ? 0.125 * c[i][0] : c[i][t], beta * dk[i][t]);
+    }
+}
+
+template <int OP, int WHAT, int AFFM = 0, class UAcc, bool MASS = false>
 __device__ __forceinline__ void element_pass_body_hex8(const KArgs& a, const long long e, const bool live, const long long ec,
                                                        const double (&X)[8][3], const UAcc& U,
-                                                       double (&f)[EPDims<FH_HEX8, OP, WHAT>::NF][EPDims<FH_HEX8, OP, WHAT>::S], double& energy) {
+                                                       double (&f)[EPDims<FH_HEX8, OP, WHAT>::NF][EPDims<FH_HEX8, OP, WHAT>::S], double& energy,
+                                                       const MassTerm& mt = MassTerm{}) {
     using O = OpT<OP, 3>;
     constexpr int D = 3, N = 8, S = O::S;
     constexpr bool AFF = AFFM != 0;
     constexpr bool POLY = AFFM == 2 && (OP == FH_LAPLACE || OP == FH_LINEAR_ELASTIC);   // (the energy too: a quadratic form, its cross moments vanish likewise)
+    static_assert(!MASS || WHAT == EP_VECTOR, "the mass term is a vector term");
     energy = 0.0;
     const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[ec] * a.nq * 2 : nullptr;
     // coefficients of the coordinate map and of u (c0 is not needed: only gradients enter)
@@ -287,6 +335,8 @@ __device__ __forceinline__ void element_pass_body_hex8(const KArgs& a, const lon
 #pragma unroll
             for (int t = 0; t < 8; ++t) dk[i][t] = 0.0;
     }
+    double arho = 0.0;   // alpha rho of the element (MASS)
+    if constexpr (MASS) arho = mt.alpha * mt.rho[mt.per_elem ? ec : 0];
     auto point = [&](int q, auto need_j_tag) {
         constexpr bool need_j = decltype(need_j_tag)::value;
         const ep_table Q = ep_const(a.qmono) + (size_t)q * 8;   // uniform over the wavefront: scalar loads
@@ -314,7 +364,11 @@ __device__ __forceinline__ void element_pass_body_hex8(const KArgs& a, const lon
 #pragma unroll
             for (int j = 0; j < D; ++j) R[j][k] = g[j];
         }
-        const double s = ep_const(a.qw)[q] * adet;   // w |det J| (elliptic.rs:422)
+        double s = ep_const(a.qw)[q] * adet;   // w |det J| (elliptic.rs:422)
+        if constexpr (MASS) {
+            hex8_mass_point<S>(cu, s * arho, xi, eta, zeta, ez, xz, xe, dk);
+            s *= mt.beta;
+        }
         double gu[D][S];                             // grad u = J^-T R
 #pragma unroll
         for (int i = 0; i < D; ++i)
@@ -434,6 +488,7 @@ __device__ __forceinline__ void element_pass_body_hex8(const KArgs& a, const lon
             dk[i][6] = fma(sy, My[i][2], sz * Mz[i][1]);
             dk[i][7] = fma(sxy, Mxy[i][2], fma(sxz, Mxz[i][1], syz * Myz[i][0]));
         }
+        if constexpr (MASS) hex8_mass_moments<S>(cu, arho * adet, mt.beta, mt.mom, dk);
     } else if constexpr (AFF) {
         point(0, std::true_type{});
         for (int q = 1; q < a.nq; ++q) point(q, std::false_type{});
@@ -1035,9 +1090,10 @@ __device__ __forceinline__ void tangent_element_body(const KArgs& a, const long 
 // the reference gradients), the output as the 21 moment sums and one synthesis butterfly per component.  AFF: every element of the mesh is a
 // parallelepiped (J once, the map's mixed coefficients dropped); otherwise J is formed once when every element of the wavefront is affine.
 // (The quadrature-free moment form does not apply: the integrand is not linear in u.)
-template <int OP, bool AFF>
+template <int OP, bool AFF, bool MASS = false>
 __device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long long e, const bool live, const double (&X)[8][3], const double (&U)[8][OpT<OP, 3>::S],
-                                                  const double (&V)[8][OpT<OP, 3>::S], double (&f)[8][OpT<OP, 3>::S]) {
+                                                  const double (&V)[8][OpT<OP, 3>::S], double (&f)[8][OpT<OP, 3>::S],
+                                                  const MassTerm& mt = MassTerm{}) {
     static_assert(OP == FH_NEO_HOOKEAN || OP == FH_STVK, "nonlinear operators only: the linear ones take the residual's element pass");
     constexpr int D = 3, N = 8, S = OpT<OP, 3>::S;
     const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
@@ -1082,6 +1138,12 @@ __device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long lon
     for (int i = 0; i < S; ++i)
 #pragma unroll
         for (int t = 0; t < 8; ++t) dk[i][t] = 0.0;
+    double arho = 0.0;   // alpha rho of the element (MASS); the mass by moments after the loop when mt.mom is set (AFF only)
+    bool mass_mom = false;
+    if constexpr (MASS) {
+        arho = mt.alpha * mt.rho[mt.per_elem ? e : 0];
+        mass_mom = AFF && mt.mom != nullptr;
+    }
     auto point = [&](int q, auto need_j_tag) {
         constexpr bool need_j = decltype(need_j_tag)::value;
         const ep_table Q = ep_const(a.qmono) + (size_t)q * 8;
@@ -1123,7 +1185,11 @@ __device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long lon
                     gx[i][k] = t2;
                 }
         }
-        const double s = ep_const(a.qw)[q] * adet;
+        double s = ep_const(a.qw)[q] * adet;
+        if constexpr (MASS) {
+            if (!mass_mom) hex8_mass_point<S>(cv, s * arho, xi, eta, zeta, ez, xz, xe, dk);
+            s *= mt.beta;
+        }
         double mu, lambda;
         tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
@@ -1154,6 +1220,9 @@ __device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long lon
         for (int q = 1; q < a.nq; ++q) point(q, std::false_type{});
     } else {
         for (int q = 0; q < a.nq; ++q) point(q, std::true_type{});
+    }
+    if constexpr (MASS) {   // (the stiffness sums carry beta already: the moments add to them unscaled)
+        if (mass_mom) hex8_mass_moments<S>(cv, arho * adet, 1.0, mt.mom, dk);
     }
 #pragma unroll
     for (int i = 0; i < S; ++i) {
@@ -1260,6 +1329,132 @@ static __global__ void __launch_bounds__(256) k_sum_partials(const double* parti
     for (int i = threadIdx.x; i < n; i += 256) v += partial[i];
     const double tot = block_sum_256(v, red);
     if (threadIdx.x == 0) *out = tot;
+}
+
+// ---- the mass term of the shifted map (alpha M + beta T(u)) x, engine_vector.hip.  M is what the assembled mass forms on the same table
+// (mass.rs:243-270): M_IJ = I_s sum_q w |det J| rho phi_I phi_J, rho one density for the mesh or one per element (rho[per_elem ? e : 0]).
+// Point q of an element with geometry vertices X: w |det J| (zero for det J == 0: the mass needs no inverse)
+// the mass term alone on Hex8 (beta == 0: no stiffness, u not read), in the monomial basis: AFF with mt.mom, |det J| once and the moments;
+// otherwise the point loop.  f_n = alpha (M x)_n.
+template <int S, bool AFF>
+__device__ __forceinline__ void mass_body_hex8(const KArgs& a, const long long e, const double (&X)[8][3], const double (&V)[8][S], const MassTerm& mt,
+                                               double (&f)[8][S]) {
+    constexpr int D = 3;
+    double cx[D][8], cv[S][8];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+        for (int n = 0; n < 8; ++n) cx[i][hex8_bin(n)] = X[n][i];
+        hex8_wht(cx[i]);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) cx[i][k] *= 0.125;
+        if constexpr (AFF) { cx[i][3] = 0.0; cx[i][5] = 0.0; cx[i][6] = 0.0; cx[i][7] = 0.0; }
+    }
+#pragma unroll
+    for (int k2 = 0; k2 < S; ++k2) {
+#pragma unroll
+        for (int n = 0; n < 8; ++n) cv[k2][hex8_bin(n)] = V[n][k2];
+        hex8_wht(cv[k2]);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) cv[k2][k] *= 0.125;
+    }
+    double dk[S][8];
+#pragma unroll
+    for (int i = 0; i < S; ++i)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) dk[i][t] = 0.0;
+    const double arho = mt.alpha * mt.rho[mt.per_elem ? e : 0];
+    auto grad = [](const double (&c)[8], double xi, double eta, double zeta, double ez, double xz, double xe, double (&g)[3]) {
+        g[0] = fma(c[7], ez, fma(c[5], zeta, fma(c[3], eta, c[1])));
+        g[1] = fma(c[7], xz, fma(c[6], zeta, fma(c[3], xi, c[2])));
+        g[2] = fma(c[7], xe, fma(c[6], eta, fma(c[5], xi, c[4])));
+    };
+    if (AFF && mt.mom) {
+        double J[D][D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) { J[i][0] = cx[i][1]; J[i][1] = cx[i][2]; J[i][2] = cx[i][4]; }
+        hex8_mass_moments<S>(cv, arho * fabs(det_small<D>(J)), 1.0, mt.mom, dk);
+    } else {
+        for (int q = 0; q < a.nq; ++q) {
+            const ep_table Q = ep_const(a.qmono) + (size_t)q * 8;
+            const double xi = Q[0], eta = Q[1], zeta = Q[2], ez = Q[3], xz = Q[4], xe = Q[5];
+            double J[D][D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) grad(cx[i], xi, eta, zeta, ez, xz, xe, J[i]);
+            hex8_mass_point<S>(cv, ep_const(a.qw)[q] * fabs(det_small<D>(J)) * arho, xi, eta, zeta, ez, xz, xe, dk);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        double d[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) d[t] = dk[i][t];
+#pragma unroll
+        for (int ax = 1; ax < 8; ax <<= 1)
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                if (!(b & ax)) {
+                    const double ev = d[b], od = d[b | ax];
+                    d[b] = ev - od;
+                    d[b | ax] = ev + od;
+                }
+#pragma unroll
+        for (int n = 0; n < 8; ++n) f[n][i] = 0.125 * d[hex8_bin(n)];
+    }
+}
+
+template <int D, int NG>
+__device__ __forceinline__ double mass_point_weight(const KArgs& a, const double (&X)[NG][D], int q) {
+    double J[D][D];
+#pragma unroll
+    for (int r = 0; r < D; ++r)
+#pragma unroll
+        for (int c = 0; c < D; ++c) J[r][c] = 0.0;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const double* gg = a.ggeom + ((size_t)q * NG + g) * D;
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+            for (int c = 0; c < D; ++c) J[r][c] = fma(X[g][r], gg[c], J[r][c]);
+    }
+    return a.qw[q] * fabs(det_small<D>(J));
+}
+
+// the element mass vector of one element: f_n = sum_q s rho phi_n (sum_m phi_m x_m) with s = w |det J|, or (DIAG, x unused) the diagonal
+// f_n = sum_q s rho phi_n^2 in every component.  xv(m, k): entry k of the element's node m (Dirichlet entries already zero).
+template <int D, int S, int N, int NG, bool DIAG, class XV>
+__device__ __forceinline__ void mass_element_body(const KArgs& a, double rho, const double (&X)[NG][D], XV&& xv, double (&f)[N][S]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) f[n][k] = 0.0;
+    for (int q = 0; q < a.nq; ++q) {
+        const double s = mass_point_weight<D, NG>(a, X, q) * rho;
+        const double* phi = a.phiref + (size_t)q * N;
+        if constexpr (DIAG) {
+#pragma unroll
+            for (int n = 0; n < N; ++n) {
+                const double t = s * phi[n] * phi[n];
+#pragma unroll
+                for (int k = 0; k < S; ++k) f[n][k] += t;
+            }
+        } else {
+            double xq[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) xq[k] = 0.0;
+#pragma unroll
+            for (int n = 0; n < N; ++n)
+#pragma unroll
+                for (int k = 0; k < S; ++k) xq[k] = fma(phi[n], xv(n, k), xq[k]);
+#pragma unroll
+            for (int n = 0; n < N; ++n) {
+                const double t = s * phi[n];
+#pragma unroll
+                for (int k = 0; k < S; ++k) f[n][k] = fma(t, xq[k], f[n][k]);
+            }
+        }
+    }
 }
 
 }  // namespace fenris_hip

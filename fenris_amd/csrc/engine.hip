@@ -545,6 +545,8 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     invalidate_pattern(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
+    c->mass_rho_n = 0;   // (the density belongs to the mesh)
+    ++c->density_gen;
     c->ragged = false;
     c->elem_kind = elem_kind;
     c->ei = ei;
@@ -641,6 +643,8 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     invalidate_pattern(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
+    c->mass_rho_n = 0;   // (the density belongs to the mesh)
+    ++c->density_gen;
     c->ragged = true;
     c->has_aff = false;
     c->row_lo = 0;
@@ -822,7 +826,7 @@ int fh_set_quadrature_uniform(fh_ctx* c, const double* w, const double* pts, uin
             for (uint32_t q = 1; q < nq && ok; ++q)
                 if (params[2 * q] != params[0] || params[2 * q + 1] != params[1]) ok = false;
         c->qmom_ok = ok;
-        const double qm8[8] = {mom[0][0][0], mom[2][0][0], mom[0][2][0], mom[0][0][2], mom[0][2][2], mom[2][0][2], mom[2][2][0], 0.0};
+        const double qm8[8] = {mom[0][0][0], mom[2][0][0], mom[0][2][0], mom[0][0][2], mom[0][2][2], mom[2][0][2], mom[2][2][0], mom[2][2][2]};
         HIP_TRY(c, c->qmom.alloc(8));
         HIP_TRY(c, hipMemcpy(c->qmom.p, qm8, sizeof qm8, hipMemcpyHostToDevice));
     } else {

@@ -448,8 +448,16 @@ struct fh_ctx {
     DevBuf<double> mf_scale;           // 1 double
     DevBuf<double> mf_xm;              // S N
     DevBuf<unsigned long long> mf_bits;   // |operand|_inf (k_mf_absmax)
-    // (struct_gen, topo_gen, geom_gen, u_gen) mf_scale was formed for; u_gen is 0 for the linear operators (their scale does not depend on u)
-    unsigned long long mf_scale_key[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+    // (struct_gen, topo_gen, geom_gen, u_gen, alpha, beta, density_gen) mf_scale was formed for: u_gen is 0 for the linear operators (their
+    // scale does not depend on u) and when beta == 0; alpha and beta as bits (the plain map: 0 and 1); density_gen 0 unless alpha != 0.  One
+    // slot: calls that alternate between the shifted and the plain map form the scale again.
+    unsigned long long mf_scale_key[7] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
+    // the density of the shifted map's mass term (fh_set_mass_density): 1 (the whole mesh) or E (per element) doubles, none when 0;
+    // density_gen counts the calls; mf_mass: S N, M x or the mass diagonal off the tiles
+    DevBuf<double> mass_rho;
+    uint64_t mass_rho_n = 0;
+    unsigned long long density_gen = 0;
+    DevBuf<double> mf_mass;
     unsigned long long geom_gen = 0;   // counts fh_update_vertices calls
     unsigned long long u_gen = 0;      // counts fh_set_u* calls
 
@@ -536,6 +544,11 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
 int mf_ready(fh_ctx* c, const char* who, int max_op);
 int mf_apply(fh_ctx* c, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
 int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
+// the shifted map alpha M + beta T(u) (fh_apply_shifted_tangent_dev): checks (alpha != 0 needs the density), y and its partials of x . y as
+// mf_apply, the diagonal as mf_diagonal.  alpha == 0, beta == 1 is the plain map.
+int mf_shift_ready(fh_ctx* c, const char* who, double alpha, double beta);
+int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
+int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bool with_scale);
 
 // dispatch over (element kind, operator kind) -> template instantiation
 #define FH_FOR_ELEM_OP(EKV, OPV, CALL)                                             \

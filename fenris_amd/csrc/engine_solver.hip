@@ -224,15 +224,16 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
                   });
 }
 
-// The same solver around the matrix-free map (fh_apply_operator_dev, fh_apply_tangent_dev; max_op as mf_ready): no pattern, no values.  The
-// partials of p . Ap come from the map's node pass (or its last pass off the tiles), summed over at most 2048 ranges in a fixed order; Jacobi
-// takes the matrix-free diagonal.  The diagonal (and with it the scale of the Dirichlet rows) is formed once per solve.
+// The same solver around the matrix-free map (fh_apply_operator_dev, fh_apply_tangent_dev; max_op as mf_ready), or around the shifted map
+// alpha M + beta T(u) (fh_apply_shifted_tangent_dev; the plain map is alpha = 0, beta = 1): no pattern, no values.  The partials of p . Ap
+// come from the map's node pass (or its last pass off the tiles), summed over at most 2048 ranges in a fixed order; Jacobi takes the
+// matrix-free diagonal.  The diagonal (and with it the scale of the Dirichlet rows) is formed once per solve.
 static int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
-                             uint64_t max_iter, uint64_t* num_iterations) {
+                             uint64_t max_iter, uint64_t* num_iterations, double alpha = 0.0, double beta = 1.0) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     if (num_iterations) *num_iterations = 0;
-    int rc = mf_ready(c, who, max_op);
+    int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, max_op) : mf_shift_ready(c, who, alpha, beta);
     if (rc) return rc;
     if (!b_dev || !x_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI)
@@ -246,7 +247,7 @@ static int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const doubl
     HIP_TRY(c, partial.alloc((size_t)3 * std::max(gv, gs_max)));
     if (preconditioner == FH_PRECOND_JACOBI || c->mf_num_dirichlet) {
         HIP_TRY(c, dinv.alloc(n));
-        rc = mf_diagonal(c, dinv.p, true);
+        rc = mf_shift_diagonal(c, alpha, beta, dinv.p, true);
         if (rc) return rc;
         if (preconditioner == FH_PRECOND_JACOBI) {
             hipLaunchKernelGGL(k_reciprocal, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dinv.p);
@@ -257,9 +258,9 @@ static int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const doubl
     if (rc) return rc;
     const int rcg = cg_run(c, n, b_dev, x_dev, preconditioner == FH_PRECOND_JACOBI ? dinv.p : nullptr, partial, wg_partial, rel_tol, max_iter,
                            num_iterations, [&](const double* in, double* out, int* ranges) {
-                               if (!ranges) return mf_apply(c, in, out, nullptr, nullptr);
+                               if (!ranges) return mf_shift_apply(c, alpha, beta, in, out, nullptr, nullptr);
                                int count = 0;
-                               int r = mf_apply(c, in, out, &wg_partial, &count);
+                               int r = mf_shift_apply(c, alpha, beta, in, out, &wg_partial, &count);
                                if (r) return r;
                                *ranges = std::min(gs_max, count);
                                hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(*ranges), dim3(256), 0, c->stream, wg_partial.p, (long long)count, partial.p);
@@ -279,6 +280,10 @@ int fh_cg_solve_matrix_free_dev(fh_ctx* c, const double* b_dev, double* x_dev, i
 int fh_cg_solve_tangent_dev(fh_ctx* c, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
                             uint64_t* num_iterations) {
     return cg_solve_free_dev(c, "fh_cg_solve_tangent", FH_STVK, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations);
+}
+int fh_cg_solve_shifted_tangent_dev(fh_ctx* c, double alpha, double beta, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
+                                    uint64_t max_iter, uint64_t* num_iterations) {
+    return cg_solve_free_dev(c, "fh_cg_solve_shifted_tangent", FH_STVK, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
 }
 
 int fh_cg_solve(fh_ctx* c, const double* values, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter,
@@ -304,11 +309,11 @@ int fh_cg_solve(fh_ctx* c, const double* values, const double* b, double* x, int
 }
 
 static int cg_solve_free_host(fh_ctx* c, const char* who, int max_op, const double* b, double* x, int preconditioner, double rel_tol,
-                              uint64_t max_iter, uint64_t* num_iterations) {
+                              uint64_t max_iter, uint64_t* num_iterations, double alpha = 0.0, double beta = 1.0) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     if (num_iterations) *num_iterations = 0;
-    int rc = mf_ready(c, who, max_op);
+    int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, max_op) : mf_shift_ready(c, who, alpha, beta);
     if (rc) return rc;
     if (!b || !x) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     const size_t n = (size_t)c->S() * c->N;
@@ -317,7 +322,7 @@ static int cg_solve_free_host(fh_ctx* c, const char* who, int max_op, const doub
     HIP_TRY(c, dx.alloc(n + 1));
     HIP_TRY(c, hipMemcpyAsync(db.p, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    rc = cg_solve_free_dev(c, who, max_op, db.p, dx.p, preconditioner, rel_tol, max_iter, num_iterations);
+    rc = cg_solve_free_dev(c, who, max_op, db.p, dx.p, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
     // like the reference's SolveError, the iterate reached so far is handed back on failure
     HIP_TRY(c, hipMemcpyAsync(x, dx.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -329,6 +334,10 @@ int fh_cg_solve_matrix_free(fh_ctx* c, const double* b, double* x, int precondit
 }
 int fh_cg_solve_tangent(fh_ctx* c, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations) {
     return cg_solve_free_host(c, "fh_cg_solve_tangent", FH_STVK, b, x, preconditioner, rel_tol, max_iter, num_iterations);
+}
+int fh_cg_solve_shifted_tangent(fh_ctx* c, double alpha, double beta, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter,
+                                uint64_t* num_iterations) {
+    return cg_solve_free_host(c, "fh_cg_solve_shifted_tangent", FH_STVK, b, x, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
 }
 
 static int error_squared(fh_ctx* c, int which, uint32_t sdim, const double* uh_dev, const double* exact_dev, double* out) {

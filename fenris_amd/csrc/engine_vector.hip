@@ -541,16 +541,20 @@ int mf_ready(fh_ctx* c, const char* who, int max_op) {
 }
 
 // what the scale of the Dirichlet rows depends on: mesh, vertices, operator, quadrature table and parameters, element mask (the setters of
-// the last three move struct_gen), u for the nonlinear operators -- not on which nodes are constrained
-static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[4]) {
+// the last three move struct_gen), u for the nonlinear operators, and for the shifted map alpha M + beta T(u) its coefficients and (alpha != 0)
+// the density -- not on which nodes are constrained.  The plain map is alpha = 0, beta = 1.
+static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[7], double alpha = 0.0, double beta = 1.0) {
     k[0] = c->struct_gen;
     k[1] = c->topo_gen;
     k[2] = c->geom_gen;
-    k[3] = c->op <= FH_LINEAR_ELASTIC ? 0 : c->u_gen;
+    k[3] = (c->op <= FH_LINEAR_ELASTIC || beta == 0.0) ? 0 : c->u_gen;
+    std::memcpy(&k[4], &alpha, sizeof(double));
+    std::memcpy(&k[5], &beta, sizeof(double));
+    k[6] = alpha != 0.0 ? c->density_gen : 0;
 }
 
-// the scale of the Dirichlet rows into c->mf_scale, from the unmodified diagonal (diag_dev)
-static int mf_scale_from(fh_ctx* c, const double* diag_dev) {
+// the scale of the Dirichlet rows into c->mf_scale, from the unmodified diagonal (diag_dev) of alpha M + beta T(u)
+static int mf_scale_from(fh_ctx* c, const double* diag_dev, double alpha = 0.0, double beta = 1.0) {
     const int n = c->S() * (int)c->N;
     DevBuf<unsigned long long> first;
     HIP_TRY(c, first.alloc(1));
@@ -560,7 +564,7 @@ static int mf_scale_from(fh_ctx* c, const double* diag_dev) {
     hipLaunchKernelGGL(k_mf_scale, dim3(1), dim3(64), 0, c->stream, diag_dev, first.p, c->mf_scale.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // (first is released on return)
-    mf_scale_key_now(c, c->mf_scale_key);
+    mf_scale_key_now(c, c->mf_scale_key, alpha, beta);
     return FH_OK;
 }
 
@@ -726,9 +730,9 @@ static int mf_apply_entry(fh_ctx* c, const char* who, int max_op, const double* 
     if (rc) return rc;
     if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (c->N == 0) return FH_OK;
-    unsigned long long key[4];
+    unsigned long long key[7];
     mf_scale_key_now(c, key);
-    if (c->mf_num_dirichlet && !std::equal(key, key + 4, c->mf_scale_key)) {
+    if (c->mf_num_dirichlet && !std::equal(key, key + 7, c->mf_scale_key)) {
         DevBuf<double> diag;
         HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
         rc = mf_diagonal(c, diag.p, true);
@@ -752,6 +756,234 @@ static int mf_diagonal_entry(fh_ctx* c, const char* who, int max_op, double* dia
     rc = mf_diagonal(c, diag_dev, true);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FH_OK;
+}
+
+// ---- the shifted map  y = (alpha M + beta T(u)) x: the mass M of the assembled FH_MASS_SCALAR / FH_MASS_VECTOR on the same mesh and table
+// (I_s sum_q w |det J| rho phi_I phi_J, s the context operator's solution dim) with the density of fh_set_mass_density, and T(u) the map
+// above.  The mass term is a pass of its own over the same tiles (k_mass_tiled; off the tiles k_mass_elements), after the tangent's kernels,
+// which stay as they are; on the tiles one node pass sums the mass partials, adds beta T(u) x and writes the Dirichlet rows and the partials
+// of x . y.  beta == 0 runs no stiffness work and does not read u; alpha == 0 runs the tangent alone.  Dirichlet nodes: the matrix
+// fh_apply_dirichlet_csr_dev leaves of the assembled alpha M + beta K(u) (its scale from the shifted diagonal).
+int mf_shift_ready(fh_ctx* c, const char* who, double alpha, double beta) {
+    const int rc = mf_ready(c, who, FH_STVK);
+    if (rc) return rc;
+    if (!std::isfinite(alpha) || !std::isfinite(beta)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": alpha and beta must be finite");
+    if (alpha != 0.0 && c->mass_rho_n == 0) return c->fail(FH_INVALID_STATE, std::string(who) + ": alpha != 0 needs fh_set_mass_density");
+    return FH_OK;
+}
+
+// the mass partials of the current table over the tiles into c->fe_scratch (x null: the diagonal); *done = false: the tiles do not cover it
+static int mass_tiles_pass(fh_ctx* c, const double* x, const unsigned char* dmask, bool* done) {
+    *done = false;
+    if (!element_pass_covers(c) || c->ei.ng != c->ei.n || c->env("FENRIS_HIP_VECTOR_ATOMICS") || c->env("FENRIS_HIP_NO_VECTOR_TILES")) return FH_OK;
+    const int rc = ensure_vector_tiles(c);
+    if (rc || c->vt_bad) return rc;
+    const size_t need = (size_t)c->vt.v.npartials * c->S();
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    KArgs a;
+    fill_common(c, a);
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    if (vector_tiles_mass_pass(c->elem_kind, c->S(), c->stream, a, c->vt.v, active, c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, x, dmask,
+                               c->fe_scratch.p) != 0)
+        return FH_OK;
+    HIP_TRY(c, hipGetLastError());
+    *done = true;
+    return FH_OK;
+}
+
+template <int D, int S, int N, int NG>
+static void mass_elements_launch(fh_ctx* c, const KArgs& a, const unsigned char* active, const double* x, const unsigned char* dmask) {
+    hipLaunchKernelGGL((k_mass_elements<D, S, N, NG>), dim3((unsigned)((c->E + 255) / 256)), dim3(256), 0, c->stream, a, active, c->mass_rho.p,
+                       c->mass_rho_n > 1 ? 1 : 0, x, dmask, c->fe_scratch.p);
+}
+template <int D, int N, int NG>
+static void mass_elements_launch_s(fh_ctx* c, const KArgs& a, const unsigned char* active, const double* x, const unsigned char* dmask) {
+    if (c->S() == 1) mass_elements_launch<D, 1, N, NG>(c, a, active, x, dmask);
+    else mass_elements_launch<D, D, N, NG>(c, a, active, x, dmask);
+}
+
+// M x (x null: the diagonal of M) of the current table ADDED to out: the tiles where they cover it, else k_mass_elements and the ordered node sums
+static int mass_single(fh_ctx* c, const double* x, const unsigned char* dmask, double* out) {
+    if (c->E == 0 || (c->has_mask && c->num_active == 0)) return FH_OK;
+    bool done;
+    int rc = mass_tiles_pass(c, x, dmask, &done);
+    if (rc) return rc;
+    if (done) {
+        HIP_TRY(c, vector_tiles_node_pass(c->stream, c->S(), (int)c->N, c->vt.v, c->fe_scratch.p, out));
+        return FH_OK;
+    }
+    rc = build_source_adjacency(c);
+    if (rc) return rc;
+    const size_t need = (size_t)c->E * c->ei.n * c->S();
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    KArgs a;
+    fill_common(c, a);
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    switch (c->elem_kind) {
+        case FH_QUAD4: mass_elements_launch_s<2, 4, 4>(c, a, active, x, dmask); break;
+        case FH_TRI3: mass_elements_launch_s<2, 3, 3>(c, a, active, x, dmask); break;
+        case FH_QUAD9: mass_elements_launch_s<2, 9, 4>(c, a, active, x, dmask); break;
+        case FH_TRI6: mass_elements_launch_s<2, 6, 3>(c, a, active, x, dmask); break;
+        case FH_HEX8: mass_elements_launch_s<3, 8, 8>(c, a, active, x, dmask); break;
+        case FH_TET4: mass_elements_launch_s<3, 4, 4>(c, a, active, x, dmask); break;
+        case FH_HEX27: mass_elements_launch_s<3, 27, 8>(c, a, active, x, dmask); break;
+        case FH_TET10: mass_elements_launch_s<3, 10, 4>(c, a, active, x, dmask); break;
+        case FH_HEX20: mass_elements_launch_s<3, 20, 8>(c, a, active, x, dmask); break;
+        case FH_TET20: mass_elements_launch_s<3, 20, 4>(c, a, active, x, dmask); break;
+        default: return c->fail(FH_UNSUPPORTED, "the shifted map: unknown element kind");
+    }
+    HIP_TRY(c, hipGetLastError());
+    return launch_vector_from_elements_soa(c, c->S(), c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
+}
+
+// M x (x null: its diagonal) over every group of the table into out (S N doubles)
+static int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* out) {
+    const size_t n = (size_t)c->S() * c->N;
+    HIP_TRY(c, hipMemsetAsync(out, 0, sizeof(double) * n, c->stream));
+    if (c->rs.active) return rs_walk_accumulating(c, nullptr, [&](uint64_t*) { return mass_single(c, x, dmask, out); });
+    return mass_single(c, x, dmask, out);
+}
+
+int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bool with_scale) {
+    if (alpha == 0.0 && beta == 1.0) return mf_diagonal(c, diag_dev, with_scale);
+    const int n = c->S() * (int)c->N;
+    int rc;
+    if (beta != 0.0) {
+        rc = mf_diagonal(c, diag_dev, false);
+        if (rc) return rc;
+    }
+    DevBuf<double> md;   // (once per solve: released on return, so that the solve holds no more than the apply)
+    if (alpha != 0.0) {
+        HIP_TRY(c, md.alloc((size_t)n + 1));
+        rc = mass_full(c, nullptr, nullptr, md.p);
+        if (rc) return rc;
+    }
+    if (n) {
+        hipLaunchKernelGGL(k_mf_shift_combine, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->S(), alpha, alpha != 0.0 ? md.p : nullptr,
+                           beta, beta != 0.0 ? diag_dev : nullptr, nullptr, nullptr, nullptr, diag_dev, nullptr);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (c->mf_num_dirichlet && with_scale) {
+        rc = mf_scale_from(c, diag_dev, alpha, beta);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_mf_dirichlet_diag, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->S(), c->mf_dmask.p, c->mf_scale.p, diag_dev);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (md.p) HIP_TRY(c, hipStreamSynchronize(c->stream));   // (md is released on return)
+    return FH_OK;
+}
+
+// Hex8 on the tiles with the monomial table: the mass term fused into the element pass (vector_tiles_shifted_hex8_pass: beta T(u) x + alpha M x
+// in one pass, or alpha M x alone for beta == 0), then the operator's node pass -- y overwritten, the Dirichlet rows, the partials of x . y.
+// The operand as mf_apply prepares it (Dirichlet entries zeroed, LinearElastic scaled by 2^-e: M is linear, the node pass scales back).
+// *done = false: not covered, nothing was run.
+static int shift_hex8_fused(fh_ctx* c, double alpha, double beta, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials, bool* done) {
+    *done = false;
+    if (c->elem_kind != FH_HEX8 || !element_pass_covers(c) || c->env("FENRIS_HIP_VECTOR_ATOMICS") ||
+        c->env("FENRIS_HIP_NO_VECTOR_TILES"))
+        return FH_OK;
+    KArgs a;
+    fill_common(c, a);
+    if (!a.qmono) return FH_OK;
+    int rc = ensure_vector_tiles(c);
+    if (rc || c->vt_bad) return rc;
+    const int S = c->S(), N = (int)c->N, n = S * N;
+    const size_t need = (size_t)c->vt.v.npartials * S;
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
+    const double* xin = x;
+    const unsigned long long* xbits = nullptr;
+    if (beta != 0.0) {   // (the mass alone reads x and dmask itself)
+        if (c->op == FH_LINEAR_ELASTIC) {
+            if (!c->mf_bits.p) HIP_TRY(c, c->mf_bits.alloc(1));
+            HIP_TRY(c, hipMemsetAsync(c->mf_bits.p, 0, sizeof(unsigned long long), c->stream));
+            hipLaunchKernelGGL(k_mf_absmax, dim3(std::max(1, std::min(1024, (n + 255) / 256))), dim3(256), 0, c->stream, n, S, x, dmask, c->mf_bits.p);
+            xbits = c->mf_bits.p;
+        }
+        if (dmask || xbits) {
+            if (c->mf_xm.n < (size_t)n) HIP_TRY(c, c->mf_xm.alloc((size_t)n));
+            hipLaunchKernelGGL(k_mf_operand, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, S, x, dmask, xbits, c->mf_xm.p);
+            HIP_TRY(c, hipGetLastError());
+            xin = c->mf_xm.p;
+        }
+        if (c->op <= FH_LINEAR_ELASTIC) a.u = xin;
+    }
+    a.work_begin = 0;
+    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
+    MassTerm mt;
+    mt.alpha = alpha;
+    mt.beta = beta;
+    mt.rho = c->mass_rho.p;
+    mt.per_elem = c->mass_rho_n > 1 ? 1 : 0;
+    mt.mom = (a.all_affine && c->qmom_ok && c->qmom.p && !c->has_rules) ? c->qmom.p : nullptr;
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    if (vector_tiles_shifted_hex8_pass(c->op, c->stream, a, c->vt.v, active, beta != 0.0 ? xin : x, dmask, mt, c->fe_scratch.p) != 0) return FH_OK;
+    HIP_TRY(c, hipGetLastError());
+    const int g = vector_tiles_operator_partials(N);
+    double* dp = nullptr;
+    if (dot_scratch) {
+        if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+        dp = dot_scratch->p;
+        *partials = g;
+    }
+    c->last_kernel = beta == 0.0 ? "k_mass_hex8_tiled + k_operator_from_partials"
+                     : c->op <= FH_LINEAR_ELASTIC ? "k_shifted_pass_tiled + k_operator_from_partials" : "k_shifted_tangent_tiled + k_operator_from_partials";
+    HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp));
+    *done = true;
+    return FH_OK;
+}
+
+// y = (alpha M + beta T(u)) x.  The scale of the Dirichlet rows must be in c->mf_scale (mf_shift_diagonal); dot_scratch, partials as mf_apply
+int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials) {
+    if (alpha == 0.0 && beta == 1.0) return mf_apply(c, x, y, dot_scratch, partials);
+    const int S = c->S(), N = (int)c->N, n = S * N;
+    const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
+    if (dmask && !c->mf_scale.p) HIP_TRY(c, c->mf_scale.alloc(1));
+    int rc;
+    if (alpha != 0.0 && c->E > 0 && !c->rs.active) {
+        bool done;
+        rc = shift_hex8_fused(c, alpha, beta, x, y, dot_scratch, partials, &done);
+        if (rc || done) return rc;
+    }
+    if (beta != 0.0) {   // beta T(u) x into y (its Dirichlet rows are written again below)
+        rc = mf_apply(c, x, y, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    if (alpha != 0.0 && c->E > 0 && !c->rs.active) {
+        bool done;
+        rc = mass_tiles_pass(c, x, dmask, &done);
+        if (rc) return rc;
+        if (done) {
+            const int g = vector_tiles_operator_partials(N);
+            double* dp = nullptr;
+            if (dot_scratch) {
+                if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+                dp = dot_scratch->p;
+                *partials = g;
+            }
+            HIP_TRY(c, vector_tiles_shift_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, alpha, beta,
+                                                    beta != 0.0 ? y : nullptr, y, dp));
+            return FH_OK;
+        }
+    }
+    if (alpha != 0.0) {
+        if (c->mf_mass.n < (size_t)n) HIP_TRY(c, c->mf_mass.alloc((size_t)n));
+        rc = mass_full(c, x, dmask, c->mf_mass.p);
+        if (rc) return rc;
+    }
+    const int g = (n + 255) / 256;
+    double* dp = nullptr;
+    if (dot_scratch) {
+        if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+        dp = dot_scratch->p;
+        *partials = g;
+    }
+    if (n) {
+        hipLaunchKernelGGL(k_mf_shift_combine, dim3(g), dim3(256), 0, c->stream, n, S, alpha, alpha != 0.0 ? c->mf_mass.p : nullptr, beta,
+                           beta != 0.0 ? y : nullptr, x, dmask, c->mf_scale.p, y, dp);
+        HIP_TRY(c, hipGetLastError());
+    }
     return FH_OK;
 }
 
@@ -786,5 +1018,60 @@ int fh_apply_tangent_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
     return mf_apply_entry(c, "fh_apply_tangent_dev", FH_STVK, x_dev, y_dev);
 }
 int fh_tangent_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_tangent_diagonal_dev", FH_STVK, diag_dev); }
+
+int fh_set_mass_density(fh_ctx* c, const double* rho, uint64_t count) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, "fh_set_mass_density: no finite element mesh set");
+    if (!rho) return c->fail(FH_BAD_ARGUMENT, "fh_set_mass_density: null density");
+    if (count != 1 && count != c->E) return c->fail(FH_BAD_ARGUMENT, "fh_set_mass_density: count must be 1 or the number of elements");
+    c->mass_rho_n = 0;
+    HIP_TRY(c, c->mass_rho.alloc((size_t)count));
+    HIP_TRY(c, hipMemcpyAsync(c->mass_rho.p, rho, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->mass_rho_n = count;
+    ++c->density_gen;
+    return FH_OK;
+}
+
+int fh_apply_shifted_tangent_dev(fh_ctx* c, double alpha, double beta, const double* x_dev, double* y_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    const char* who = "fh_apply_shifted_tangent_dev";
+    if (alpha == 0.0 && beta == 1.0) return mf_apply_entry(c, who, FH_STVK, x_dev, y_dev);
+    DevGuard dev_guard_(c->device);
+    int rc = mf_shift_ready(c, who, alpha, beta);
+    if (rc) return rc;
+    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    if (c->N == 0) return FH_OK;
+    unsigned long long key[7];
+    mf_scale_key_now(c, key, alpha, beta);
+    if (c->mf_num_dirichlet && !std::equal(key, key + 7, c->mf_scale_key)) {
+        DevBuf<double> diag;
+        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
+        rc = mf_shift_diagonal(c, alpha, beta, diag.p, true);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    rc = reset_status(c);
+    if (rc) return rc;
+    rc = mf_shift_apply(c, alpha, beta, x_dev, y_dev, nullptr, nullptr);
+    if (rc) return rc;
+    return read_status(c, nullptr);
+}
+
+int fh_shifted_tangent_diagonal_dev(fh_ctx* c, double alpha, double beta, double* diag_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    const char* who = "fh_shifted_tangent_diagonal_dev";
+    if (alpha == 0.0 && beta == 1.0) return mf_diagonal_entry(c, who, FH_STVK, diag_dev);
+    DevGuard dev_guard_(c->device);
+    int rc = mf_shift_ready(c, who, alpha, beta);
+    if (rc) return rc;
+    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    if (c->N == 0) return FH_OK;
+    rc = mf_shift_diagonal(c, alpha, beta, diag_dev, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FH_OK;
+}
 
 }  // extern "C"

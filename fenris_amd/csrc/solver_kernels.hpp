@@ -529,4 +529,72 @@ __global__ void __launch_bounds__(256) k_mf_diagonal_elements(const KArgs a, int
     }
 }
 
+
+// ---- the mass term of the shifted map (alpha M + beta T(u)) x, engine_vector.hip (mass_element_body: element_pass.hpp).
+// the mass term off the tiles (every kind, rule-set groups): one thread per element, fe[a][e][c] for k_vector_from_elements_soa; x null: the
+// diagonal.  dmask (may be null): the entries of the Dirichlet nodes read as zero.  Inactive elements write zeros.
+template <int D, int S, int N, int NG>
+__global__ void __launch_bounds__(256) k_mass_elements(const KArgs a, const unsigned char* active, const double* rho, int rho_per_elem,
+                                                       const double* x, const unsigned char* dmask, double* fe) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.num_elements) return;
+    const int* nodes = a.conn + (size_t)e * N;
+    auto out = [&](int n) { return fe + ((size_t)n * (size_t)a.num_elements + (size_t)e) * S; };
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) out(n)[k] = 0.0;
+    if (active && active[e] == 0) return;
+    double X[NG][D];
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+        for (int r = 0; r < D; ++r) X[g][r] = a.verts[(size_t)nodes[g] * D + r];
+    auto xv = [&](int n, int k) {
+        const int nd = nodes[n];
+        return (dmask && dmask[nd]) ? 0.0 : x[(size_t)nd * S + k];
+    };
+    // (mass_element_body's arithmetic, accumulated in fe rather than in registers: f[27][3] does not fit beside the rest)
+    const double r = rho[rho_per_elem ? e : 0];
+    for (int q = 0; q < a.nq; ++q) {
+        const double s = mass_point_weight<D, NG>(a, X, q) * r;
+        const double* phi = a.phiref + (size_t)q * N;
+        if (!x) {
+            for (int n = 0; n < N; ++n) {
+                const double t = s * phi[n] * phi[n];
+#pragma unroll
+                for (int k = 0; k < S; ++k) out(n)[k] += t;
+            }
+            continue;
+        }
+        double xq[S];
+#pragma unroll
+        for (int k = 0; k < S; ++k) xq[k] = 0.0;
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int k = 0; k < S; ++k) xq[k] = fma(phi[n], xv(n, k), xq[k]);
+        for (int n = 0; n < N; ++n) {
+            const double t = s * phi[n];
+            double* o = out(n);
+#pragma unroll
+            for (int k = 0; k < S; ++k) o[k] = fma(t, xq[k], o[k]);
+        }
+    }
+}
+
+// y = alpha m + beta t (m, t: may be null = zero; t may be y), rows of the Dirichlet nodes = scale x (dmask may be null), and the
+// per-workgroup partials of x . y (dot_partial may be null; x may be null without dmask and dot_partial: the diagonal)
+static __global__ void __launch_bounds__(256) k_mf_shift_combine(int n, int S, double alpha, const double* m, double beta, const double* t,
+                                                                 const double* x, const unsigned char* dmask, const double* scale, double* y,
+                                                                 double* dot_partial) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double d[1] = {0.0};
+    if (i < n) {
+        const double v = m ? alpha * m[i] : 0.0;
+        const double yv = (dmask && dmask[i / S]) ? *scale * x[i] : (t ? fma(beta, t[i], v) : v);
+        y[i] = yv;
+        if (dot_partial) d[0] = x[i] * yv;
+    }
+    if (dot_partial) block_sum_store<1>(d, dot_partial + blockIdx.x);
+}
+
 }  // namespace fenris_hip

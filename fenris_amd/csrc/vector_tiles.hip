@@ -536,6 +536,188 @@ __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, c
     }
 }
 
+// the mass term of the shifted map alpha M + beta T(u) (engine_vector.hip) over the tiles: the element pass of mass_element_body (x null: the
+// diagonal) with the operand gathered per element, the entries of the Dirichlet nodes (dmask, may be null) read as zero; the tile's node sums,
+// partials.  A pass of its own: the tangent's element passes stay as they are.
+template <int D, int N, int S, bool DIAG, int TS>
+__global__ void __launch_bounds__(TS) k_mass_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const double* rho, int rho_per_elem,
+                                                   const double* x, const unsigned char* dmask, double* partial) {
+    __shared__ double stage[N * S * TS];
+    __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
+    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
+    if (tile >= t.ntiles) return;
+    const int el = t.elem[(size_t)tile * TS + tid];
+    const bool live = el >= 0 && (!active || active[el] != 0);
+    TileSums<N, TS> ts;
+    ts.request(t, tile, tid);
+    double X[N][D], Vv[DIAG ? 1 : N][S];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
+#pragma unroll
+        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
+        if constexpr (!DIAG) {
+            const bool fixed = dmask && dmask[nd];
+#pragma unroll
+            for (int k = 0; k < S; ++k) Vv[n][k] = fixed ? 0.0 : x[(size_t)nd * S + k];
+        }
+    }
+    double f[N][S];
+    const double r = rho[rho_per_elem ? (el >= 0 ? el : 0) : 0];
+    mass_element_body<D, S, N, N, DIAG>(a, r, X, [&](int n, int k) { return Vv[DIAG ? 0 : n][k]; }, f);
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
+    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+}
+
+// the shifted map fused on Hex8 (the monomial form of element_pass.hpp, MASS instantiations): one element pass forms
+// beta T(u) x + alpha M x into the partials, k_operator_from_partials sums them.  Linear operators: the residual's body fed the operand
+// (a.u = x, scaled like the operator's); AFFM as k_element_pass_tiled's MONO - 1.
+template <int OP, int TS, int AFFM>
+__global__ void __launch_bounds__(TS) k_shifted_pass_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const MassTerm mt, double* partial) {
+    constexpr int N = 8, S = OpT<OP, 3>::S, D = 3;
+    __shared__ double stage[N * S * TS];
+    __shared__ unsigned short ents[TS * N];
+    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
+    if (tile >= t.ntiles) return;
+    const int el = t.elem[(size_t)tile * TS + tid];
+    const bool live = el >= 0 && (!active || active[el] != 0);
+    const long long ec = el >= 0 ? el : 0;
+    TileSums<N, TS> ts;
+    ts.request(t, tile, tid);
+    double X[N][D], Uv[N][S];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
+#pragma unroll
+        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
+#pragma unroll
+        for (int k = 0; k < S; ++k) Uv[n][k] = a.u[(size_t)nd * S + k];
+    }
+    double f[N][S], energy;
+    element_pass_body_hex8<OP, EP_VECTOR, AFFM, EPRegU<N, S>, true>(a, el, live, ec, X, EPRegU<N, S>{Uv}, f, energy, mt);
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
+    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+}
+
+// ... the nonlinear operators: tangent_body_hex8 with the mass term (x: the tangent's operand)
+template <int OP, int TS, bool AFF>
+__global__ void __launch_bounds__(TS) k_shifted_tangent_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const double* x, const MassTerm mt,
+                                                             double* partial) {
+    constexpr int N = 8, S = 3, D = 3;
+    __shared__ double stage[N * S * TS];
+    __shared__ unsigned short ents[TS * N];
+    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
+    if (tile >= t.ntiles) return;
+    const int el = t.elem[(size_t)tile * TS + tid];
+    const bool live = el >= 0 && (!active || active[el] != 0);
+    TileSums<N, TS> ts;
+    ts.request(t, tile, tid);
+    double X[N][D], Uv[N][S], Vv[N][S];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
+#pragma unroll
+        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+            Uv[n][k] = a.u ? a.u[(size_t)nd * S + k] : 0.0;
+            Vv[n][k] = x[(size_t)nd * S + k];
+        }
+    }
+    double f[N][S];
+    tangent_body_hex8<OP, AFF, true>(a, el >= 0 ? el : 0, live, X, Uv, Vv, f, mt);
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
+    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+}
+
+// ... and the mass alone (beta == 0: u is not read): x with the Dirichlet entries (dmask, may be null) read as zero
+template <int S, int TS, bool AFF>
+__global__ void __launch_bounds__(TS) k_mass_hex8_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const double* x,
+                                                       const unsigned char* dmask, const MassTerm mt, double* partial) {
+    constexpr int N = 8, D = 3;
+    __shared__ double stage[N * S * TS];
+    __shared__ unsigned short ents[TS * N];
+    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
+    if (tile >= t.ntiles) return;
+    const int el = t.elem[(size_t)tile * TS + tid];
+    const bool live = el >= 0 && (!active || active[el] != 0);
+    TileSums<N, TS> ts;
+    ts.request(t, tile, tid);
+    double X[N][D], Vv[N][S];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
+#pragma unroll
+        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
+        const bool fixed = dmask && dmask[nd];
+#pragma unroll
+        for (int k = 0; k < S; ++k) Vv[n][k] = fixed ? 0.0 : x[(size_t)nd * S + k];
+    }
+    double f[N][S];
+    mass_body_hex8<S, AFF>(a, el >= 0 ? el : 0, X, Vv, mt, f);
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
+    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+}
+
+// node pass of the shifted map: y = alpha (node sums of the mass partials, in ascending order) + beta t, OVERWRITTEN (t: the tangent's y,
+// may be y itself, or null = zero); rows of the Dirichlet nodes (dmask, may be null) = *scale x; dot_partial (may be null): per workgroup
+// x . y over its nodes in a fixed tree (k_operator_from_partials' layout)
+template <int S>
+__global__ void __launch_bounds__(256) k_shift_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* partial,
+                                                             const double* x, const unsigned char* dmask, const double* scale, double alpha,
+                                                             double beta, const double* tv, double* y, double* dot_partial) {
+    __shared__ double red[4];
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    double dot = 0.0;
+    if (node < num_nodes) {
+        double acc[S];
+#pragma unroll
+        for (int c = 0; c < S; ++c) acc[c] = 0.0;
+        const unsigned k0 = np_off[node], k1 = np_off[node + 1];
+        for (unsigned kb = k0; kb < k1; kb += 4) {
+            unsigned v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
+            double xp[4][S];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int c = 0; c < S; ++c) xp[j][c] = partial[(size_t)v[j] * S + c];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (kb + j < k1) {
+#pragma unroll
+                    for (int c = 0; c < S; ++c) acc[c] += xp[j][c];
+                }
+        }
+        const bool fixed = dmask && dmask[node];
+#pragma unroll
+        for (int c = 0; c < S; ++c) {
+            const size_t i = (size_t)node * S + c;
+            const double xv = x[i], m = alpha * acc[c];
+            const double yv = fixed ? *scale * xv : (tv ? fma(beta, tv[i], m) : m);
+            y[i] = yv;
+            dot = fma(xv, yv, dot);
+        }
+    }
+    if (dot_partial) {
+        const double tot = block_sum_256(dot, red);
+        if (threadIdx.x == 0) dot_partial[blockIdx.x] = tot;
+    }
+}
+
 template <typename T>
 hipError_t vt_alloc(VecTilesStore* st, int slot, T** p, size_t count) {
     hipError_t e = hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (count ? count : 1));
@@ -814,6 +996,78 @@ int vector_tiles_tangent_pass(int elem_kind, int op, hipStream_t stream, const K
     }
 #undef VT_TG
 #undef VT_TG1
+}
+
+int vector_tiles_mass_pass(int elem_kind, int S, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* rho,
+                           int rho_per_elem, const double* x, const unsigned char* dmask, double* partial) {
+    const dim3 g(8 * ((t.ntiles + 7) / 8));
+#define VT_MS1(DV, NV, SV)                                                                                                                           \
+    do {                                                                                                                                             \
+        if (x) hipLaunchKernelGGL((k_mass_tiled<DV, NV, SV, false, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, rho, rho_per_elem, x, dmask, partial); \
+        else hipLaunchKernelGGL((k_mass_tiled<DV, NV, SV, true, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, rho, rho_per_elem, x, dmask, partial);   \
+    } while (0)
+#define VT_MS(DV, NV)                        \
+    do {                                     \
+        if (S == 1) VT_MS1(DV, NV, 1);       \
+        else if (S == DV) VT_MS1(DV, NV, DV); \
+        else return -1;                      \
+    } while (0)
+    switch (elem_kind) {
+        case FH_QUAD4: VT_MS(2, 4); return 0;
+        case FH_TRI3: VT_MS(2, 3); return 0;
+        case FH_TET4: VT_MS(3, 4); return 0;
+        case FH_HEX8: VT_MS(3, 8); return 0;
+        default: return -1;
+    }
+#undef VT_MS
+#undef VT_MS1
+}
+
+hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
+                                        const unsigned char* dmask, const double* scale, double alpha, double beta, const double* tv, double* y,
+                                        double* dot_partial) {
+    const int grid = vector_tiles_operator_partials(num_nodes);
+    if (S == 1) hipLaunchKernelGGL((k_shift_from_partials<1>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
+    else if (S == 2) hipLaunchKernelGGL((k_shift_from_partials<2>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
+    else hipLaunchKernelGGL((k_shift_from_partials<3>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
+    return hipGetLastError();
+}
+
+int vector_tiles_shifted_hex8_pass(int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* x,
+                                   const unsigned char* dmask, const MassTerm& mt, double* partial) {
+    if (!a.qmono) return -1;
+    const dim3 g(8 * ((t.ntiles + 7) / 8));
+    const bool aff = a.all_affine != 0;
+    if (mt.beta == 0.0) {   // the mass alone
+        if (op == FH_LAPLACE) {
+            if (aff) hipLaunchKernelGGL((k_mass_hex8_tiled<1, VT_TS, true>), g, dim3(VT_TS), 0, stream, a, t, active, x, dmask, mt, partial);
+            else hipLaunchKernelGGL((k_mass_hex8_tiled<1, VT_TS, false>), g, dim3(VT_TS), 0, stream, a, t, active, x, dmask, mt, partial);
+        } else {
+            if (aff) hipLaunchKernelGGL((k_mass_hex8_tiled<3, VT_TS, true>), g, dim3(VT_TS), 0, stream, a, t, active, x, dmask, mt, partial);
+            else hipLaunchKernelGGL((k_mass_hex8_tiled<3, VT_TS, false>), g, dim3(VT_TS), 0, stream, a, t, active, x, dmask, mt, partial);
+        }
+        return 0;
+    }
+#define VT_SH(OPC)                                                                                                                                   \
+    do {                                                                                                                                             \
+        if (aff && a.qmom) hipLaunchKernelGGL((k_shifted_pass_tiled<OPC, VT_TS, 2>), g, dim3(VT_TS), 0, stream, a, t, active, mt, partial);          \
+        else if (aff) hipLaunchKernelGGL((k_shifted_pass_tiled<OPC, VT_TS, 1>), g, dim3(VT_TS), 0, stream, a, t, active, mt, partial);               \
+        else hipLaunchKernelGGL((k_shifted_pass_tiled<OPC, VT_TS, 0>), g, dim3(VT_TS), 0, stream, a, t, active, mt, partial);                        \
+    } while (0)
+    switch (op) {
+        case FH_LAPLACE: VT_SH(FH_LAPLACE); return 0;
+        case FH_LINEAR_ELASTIC: VT_SH(FH_LINEAR_ELASTIC); return 0;
+        case FH_NEO_HOOKEAN:
+            if (aff) hipLaunchKernelGGL((k_shifted_tangent_tiled<FH_NEO_HOOKEAN, VT_TS, true>), g, dim3(VT_TS), 0, stream, a, t, active, x, mt, partial);
+            else hipLaunchKernelGGL((k_shifted_tangent_tiled<FH_NEO_HOOKEAN, VT_TS, false>), g, dim3(VT_TS), 0, stream, a, t, active, x, mt, partial);
+            return 0;
+        case FH_STVK:
+            if (aff) hipLaunchKernelGGL((k_shifted_tangent_tiled<FH_STVK, VT_TS, true>), g, dim3(VT_TS), 0, stream, a, t, active, x, mt, partial);
+            else hipLaunchKernelGGL((k_shifted_tangent_tiled<FH_STVK, VT_TS, false>), g, dim3(VT_TS), 0, stream, a, t, active, x, mt, partial);
+            return 0;
+        default: return -1;
+    }
+#undef VT_SH
 }
 
 }  // namespace fenris_hip

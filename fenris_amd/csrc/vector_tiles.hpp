@@ -70,4 +70,22 @@ hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_no
                                            const unsigned char* dmask, const double* scale, const unsigned long long* xbits, double* y,
                                            double* dot_partial);
 
+// the mass term of the shifted map (engine_vector.hip) over the tiles into partial[P][S]: M x (x null: the diagonal of M), rho[rho_per_elem ? e : 0]
+// the density, the entries of the nodes with dmask[node] != 0 read as zero (dmask may be null).  Returns -1 when (elem_kind, S) is not covered.
+int vector_tiles_mass_pass(int elem_kind, int S, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* rho,
+                           int rho_per_elem, const double* x, const unsigned char* dmask, double* partial);
+
+// node pass of the shifted map: y = alpha (node sums of the mass partials) + beta tv, OVERWRITTEN (tv: may be y, or null = zero); the Dirichlet
+// rows and dot_partial as vector_tiles_operator_node_pass
+hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
+                                        const unsigned char* dmask, const double* scale, double alpha, double beta, const double* tv, double* y,
+                                        double* dot_partial);
+
+// the shifted map fused on Hex8 with the monomial table (a.qmono; -1 otherwise): partial[P][S] of beta T(u) x + alpha M x in ONE element pass
+// (k_shifted_pass_tiled for the linear operators, which read the operand from a.u; k_shifted_tangent_tiled for NeoHookean / StVK, operand x),
+// or with mt.beta == 0 of alpha M x alone (k_mass_hex8_tiled, x read with the Dirichlet entries of dmask as zero; u not read).  The caller sums
+// them with vector_tiles_operator_node_pass.
+int vector_tiles_shifted_hex8_pass(int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* x,
+                                   const unsigned char* dmask, const MassTerm& mt, double* partial);
+
 }  // namespace fenris_hip

@@ -429,6 +429,31 @@ int fh_tangent_diagonal_dev(fh_ctx*, double* diag_dev);
 int fh_cg_solve_tangent(fh_ctx*, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations);
 int fh_cg_solve_tangent_dev(fh_ctx*, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
                             uint64_t* num_iterations);
+/* ---- matrix-free shifted tangent for implicit time stepping: (alpha M + beta T(u)) Delta = b, e.g. backward Euler alpha = 1, beta = dt^2.
+ * M is the mass matrix the assembled FH_MASS_SCALAR / FH_MASS_VECTOR form on the same mesh and quadrature table, M_IJ = I_s sum_q w |det J|
+ * rho phi_I phi_J with s the context operator's solution dim (Laplace: the scalar mass, the materials: the vector mass), rho the density of
+ * fh_set_mass_density; T(u) is fh_apply_tangent_dev's map.  Operators: FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK (mass operators
+ * and FH_TENSOR: FH_UNSUPPORTED).  alpha != 0 without a density: FH_INVALID_STATE; alpha and beta not finite: FH_BAD_ARGUMENT.  alpha == 0
+ * runs the tangent's kernels alone (alpha == 0, beta == 1: exactly fh_apply_tangent_dev); beta == 0 runs no stiffness work and does not read
+ * u.  It honours every element kind, every table form, the element mask and the Dirichlet nodes of fh_set_operator_dirichlet_nodes, with the
+ * same meaning as for the tangent: the matrix fh_apply_dirichlet_csr_dev leaves of the assembled alpha M + beta K(u), scale = |first nonzero
+ * diagonal entry of alpha M + beta K(u)| in row order, or 1.  The scale shares the tangent's one-entry cache, keyed also on alpha, beta and
+ * the density: calls that alternate between the shifted map and the plain one (or between two pairs of coefficients) form it again each
+ * time.  Deterministic (no floating-point atomics).
+ *
+ * fh_set_mass_density: count == 1, one density for the whole mesh; count == E, one per element (by element id).  Other counts or a null
+ * pointer: FH_BAD_ARGUMENT.  fh_set_mesh* drops the density. */
+int fh_set_mass_density(fh_ctx*, const double* rho, uint64_t count);
+/* y = (alpha M + beta T(u)) x, both s N doubles on the device; y is OVERWRITTEN. */
+int fh_apply_shifted_tangent_dev(fh_ctx*, double alpha, double beta, const double* x_dev, double* y_dev);
+/* its diagonal alpha sum_q w |det J| rho phi_a^2 + beta diag T(u), after the Dirichlet modification when nodes are set. */
+int fh_shifted_tangent_diagonal_dev(fh_ctx*, double alpha, double beta, double* diag_dev);
+/* fh_cg_solve_tangent(_dev) with A = alpha M + beta T(u): the same contract and error codes, the iterate handed back on failure, bitwise
+ * reproducible; FH_PRECOND_JACOBI takes the inverse of fh_shifted_tangent_diagonal_dev. */
+int fh_cg_solve_shifted_tangent(fh_ctx*, double alpha, double beta, const double* b, double* x, int preconditioner, double rel_tol,
+                                uint64_t max_iter, uint64_t* num_iterations);
+int fh_cg_solve_shifted_tangent_dev(fh_ctx*, double alpha, double beta, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
+                                    uint64_t max_iter, uint64_t* num_iterations);
 /* estimate_L2_error_squared / estimate_H1_seminorm_error_squared (src/error.rs:287-372):
  *   sum_e sum_q w |det J| |u_h(x_q) - u(x_q)|^2      resp.   |grad u_h(x_q) - grad u(x_q)|_F^2
  * with the quadrature table of the context.  The reference solution is arbitrary code in the reference; here the
