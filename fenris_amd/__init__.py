@@ -12,7 +12,8 @@ from .assembly import (CsrAssembler, CsrMatrix, CsrParAssembler, DisjointSubsets
                        compact_quadrature_table,
                        VectorAssembler, VectorParAssembler, apply_homogeneous_dirichlet_bc_csr,
                        apply_homogeneous_dirichlet_bc_rhs, assemble_scalar, color_nodes, CgSolveError, ConjugateGradient,
-                       IdentityOperator, JacobiPreconditioner, MatrixFreeMass, MatrixFreeOperator, MatrixFreeShiftedTangent, MatrixFreeTangent, RelativeResidualCriterion, estimate_H1_seminorm_error,
+                       IdentityOperator, JacobiPreconditioner, MatrixFreeMass, MatrixFreeNewton, NewtonSettings, NoLineSearch,
+                       BacktrackingLineSearch, NewtonError, NewtonResult, MaximumIterationsReached, JacobianError, LineSearchError, MatrixFreeOperator, MatrixFreeShiftedTangent, MatrixFreeTangent, RelativeResidualCriterion, estimate_H1_seminorm_error,
                        estimate_H1_seminorm_error_squared, estimate_L2_error, estimate_L2_error_squared)
 from .compose import (AggregateElementAssembler, MapElementNodes, TransformElementMatrix, TransformElementScalar,
                       TransformElementVector)

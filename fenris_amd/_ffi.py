@@ -17,6 +17,9 @@ FH_OK, FH_SINGULAR_JACOBIAN, FH_BAD_ARGUMENT, FH_HIP_ERROR, FH_OUT_OF_MEMORY, FH
 QUAD4, HEX8, TET4, HEX27, TRI3, TET10, QUAD9, TRI6, HEX20, TET20 = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 LAPLACE, LINEAR_ELASTIC, NEO_HOOKEAN, STVK, MASS_SCALAR, MASS_VECTOR, TENSOR = 0, 1, 2, 3, 4, 5, 6
 SCATTER_ATOMIC, SCATTER_COLORED, SCATTER_GATHER = 0, 1, 2
+FH_CG_MAX_ITERATIONS, FH_CG_INDEFINITE_OPERATOR, FH_CG_INDEFINITE_PRECONDITIONER = 7, 8, 9
+FH_NEWTON_MAX_ITERATIONS, FH_NEWTON_JACOBIAN_ERROR, FH_NEWTON_LINE_SEARCH_FAILED = 10, 11, 12
+NEWTON_NO_LINE_SEARCH, NEWTON_BACKTRACKING = 0, 1
 ASSEMBLE_OVERWRITE = 0x100
 ASSEMBLE_REPRODUCIBLE = 0x200
 
@@ -127,6 +130,10 @@ _SIGS = {
     "fh_cg_solve_shifted_tangent": (C.c_int, [C.c_void_p, C.c_double, C.c_double, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_cg_solve_shifted_tangent_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64,
                                                   u64p]),
+    "fh_newton_solve": (C.c_int, [C.c_void_p, C.c_double, C.c_double, f64p, f64p, f64p, C.c_double, C.c_uint64, C.c_int, C.c_int, C.c_double,
+                                  C.c_uint64, u64p, f64p]),
+    "fh_newton_solve_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_int,
+                                      C.c_int, C.c_double, C.c_uint64, u64p, f64p]),
     "fh_estimate_L2_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),
     "fh_estimate_L2_error_squared_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, f64p]),
     "fh_estimate_H1_seminorm_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),

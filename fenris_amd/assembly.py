@@ -397,6 +397,24 @@ class Engine:
         self._check(rc)
         return int(it.value)
 
+    def newton_solve(self, alpha, beta, f, u_ref, u, tolerance, max_iterations=0, line_search=1, preconditioner=1, linear_rel_tol=1e-8,
+                     linear_max_iter=0):
+        """fh_newton_solve(_dev) on the operator's Dirichlet nodes and the density set here: u is the guess on entry and the iterate on return
+        (numpy array, or a device tensor with f and u_ref tensors too; f, u_ref may be None).  Returns (status, stats[4], norms[3]): the
+        Newton codes 10-12 are returned, not raised (MatrixFreeNewton raises them); every other error raises."""
+        stats = np.zeros(4, dtype=np.uint64)
+        norms = np.zeros(3)
+        args = (float(alpha), float(beta))
+        tail = (float(tolerance), int(max_iterations), int(line_search), int(preconditioner), float(linear_rel_tol), int(linear_max_iter),
+                _ffi.up(stats), _ffi.fp(norms))
+        if _is_torch(u):
+            rc = self._lib.fh_newton_solve_dev(self._h, *args, _ptr(f), _ptr(u_ref), C.c_void_p(u.data_ptr()), *tail)
+        else:
+            rc = self._lib.fh_newton_solve(self._h, *args, _ffi.fp(f), _ffi.fp(u_ref), _ffi.fp(u), *tail)
+        if rc not in (_ffi.FH_NEWTON_MAX_ITERATIONS, _ffi.FH_NEWTON_JACOBIAN_ERROR, _ffi.FH_NEWTON_LINE_SEARCH_FAILED):
+            self._check(rc)
+        return rc, stats, norms
+
     def apply_dirichlet_csr_dev(self, values_t, nodes):
         nodes = _ffi.as_u64(nodes)
         self._check(self._lib.fh_apply_dirichlet_csr_dev(self._h, C.c_void_p(values_t.data_ptr()), _ffi.up(nodes), len(nodes)))
@@ -1084,6 +1102,151 @@ class MatrixFreeMass(MatrixFreeShiftedTangent):
             self._nodes = saved
             self._bind(force=True)
         return y if device else y.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ Newton (fenris-optimize/src/newton.rs)
+@dataclass
+class NewtonSettings:
+    """NewtonSettings { max_iterations, tolerance } (newton.rs:20-24): converged when ||F||_2 <= tolerance; max_iterations None: no limit"""
+
+    max_iterations: Optional[int] = None
+    tolerance: float = 1e-8
+
+
+class NoLineSearch:
+    """the full Newton step (newton.rs:140-163)"""
+
+    kind = _ffi.NEWTON_NO_LINE_SEARCH
+
+
+class BacktrackingLineSearch:
+    """Armijo backtracking with c = 1e-4 and step lengths 1, 0.75, 0.5, 0.25, 0.0625, ... down to 1e-6 (newton.rs:165-249)"""
+
+    kind = _ffi.NEWTON_BACKTRACKING
+
+
+@dataclass
+class NewtonResult:
+    """what fh_newton_solve reports: Newton iterations, residual evaluations, PCG iterations summed, the last PCG's status, ||F(u_0)||,
+    ||F|| at return and the last accepted step length (0: none)"""
+
+    iterations: int
+    residual_evaluations: int
+    linear_iterations: int
+    linear_status: int
+    initial_residual_norm: float
+    residual_norm: float
+    step_length: float
+
+
+class NewtonError(FenrisError):
+    """NewtonError (newton.rs:25-34); `result` holds the NewtonResult of the failed solve, whose u is the reference's x at the failure"""
+
+    def __init__(self, code, message, result):
+        super().__init__(code, message)
+        self.result = result
+
+
+class MaximumIterationsReached(NewtonError):
+    """NewtonError::MaximumIterationsReached(iterations)"""
+
+    @property
+    def iterations(self):
+        return self.result.iterations
+
+
+class JacobianError(NewtonError):
+    """NewtonError::JacobianError: the inner PCG failed; cg_code is its status (7-9, see CgSolveError)"""
+
+    @property
+    def cg_code(self):
+        return self.result.linear_status
+
+
+class LineSearchError(NewtonError):
+    """NewtonError::LineSearchError: no step length above 1e-6 passed, or (a deviation from newton.rs) an accepted state's ||F|| is not finite"""
+
+
+class MatrixFreeNewton:
+    """newton_line_search (fenris-optimize/src/newton.rs:77-130) on the device for F(u) = alpha M (u - u_ref) + beta (r(u) - f), r the
+    element assembler's residual and M the mass of MatrixFreeShiftedTangent; the Jacobian is alpha M + beta T(u) and each Newton step is a
+    matrix-free Jacobi-PCG solve on it.  Static equilibrium (alpha = 0, beta = 1) or a backward-Euler step (with_inertia(rho, 1, dt^2, u_ref)).
+    Dirichlet nodes, load, density and coefficients belong to this object and are handed to the engine before every solve.  The assembler's
+    u is the solution afterwards."""
+
+    def __init__(self, element_assembler):
+        self.element_assembler = element_assembler
+        self.engine = element_assembler.engine
+        self._nodes, self._f, self._u_ref, self._rho = None, None, None, None
+        self.alpha, self.beta = 0.0, 1.0
+
+    def with_dirichlet_nodes(self, nodes):
+        """the nodes held at the values u has on entry to solve (None: none); returns self"""
+        self._nodes = None if nodes is None else _ffi.as_u64(nodes).copy()
+        self._bind(force=True)
+        return self
+
+    def with_load(self, f):
+        """the load f of r(u) = f (numpy array or device tensor; None: zero); returns self"""
+        self._f = f
+        return self
+
+    def with_inertia(self, density, alpha, beta, u_ref=None):
+        """density (one value or one per element), coefficients and u_ref (None: zero) of the mass term; returns self"""
+        self._rho = np.ascontiguousarray(np.atleast_1d(np.asarray(density, dtype=np.float64)).ravel()).copy()
+        self.alpha, self.beta, self._u_ref = float(alpha), float(beta), u_ref
+        self.engine.set_mass_density(self._rho)   # (checks the count now)
+        self.engine._mass_bound = self
+        return self
+
+    def with_coefficients(self, alpha, beta):
+        self.alpha, self.beta = float(alpha), float(beta)
+        return self
+
+    def _bind(self, force=False):
+        # (the engine keeps the Dirichlet nodes and the density of the object that used it last, as for MatrixFreeOperator)
+        if force or getattr(self.engine, "_mf_bound", None) is not self:
+            self.engine.set_operator_dirichlet_nodes(self._nodes)
+            self.engine._mf_bound = self
+        if self._rho is not None and (force or getattr(self.engine, "_mass_bound", None) is not self):
+            self.engine.set_mass_density(self._rho)
+            self.engine._mass_bound = self
+
+    def solve(self, u, settings: NewtonSettings = NewtonSettings(), line_search=None, preconditioner=1, linear_rel_tol=1e-8, linear_max_iter=0):
+        """u: the guess with the Dirichlet values (numpy array or device tensor), overwritten by the solution.  Returns a NewtonResult;
+        raises MaximumIterationsReached, JacobianError or LineSearchError with u holding the reference's x at the failure."""
+        self._bind()
+        ls = BacktrackingLineSearch() if line_search is None else line_search
+        f, u_ref = self._f, self._u_ref
+        n = self.element_assembler.solution_dim() * self.engine.num_nodes()
+        if _is_torch(u):
+            import torch
+
+            # (written in place through its pointer: exactly n contiguous doubles on the engine's device)
+            if u.dtype != torch.float64 or not u.is_contiguous() or u.numel() != n or u.device != torch.device(f"cuda:{self.engine.device}"):
+                raise ValueError(f"u must be a contiguous float64 tensor of {n} entries on cuda:{self.engine.device}")
+            dev = u.device
+            f = None if f is None else torch.as_tensor(f, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+            u_ref = None if u_ref is None else torch.as_tensor(u_ref, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+            uu = u
+        else:
+            if np.size(u) != n:
+                raise ValueError(f"u must hold {n} entries")
+            f = None if f is None else _ffi.as_f64(f.cpu().numpy() if _is_torch(f) else f).reshape(-1)
+            u_ref = None if u_ref is None else _ffi.as_f64(u_ref.cpu().numpy() if _is_torch(u_ref) else u_ref).reshape(-1)
+            uu = _ffi.as_f64(u).reshape(-1)
+        for name, v in (("f", f), ("u_ref", u_ref)):
+            if v is not None and (v.numel() if _is_torch(v) else v.size) != n:
+                raise ValueError(f"{name} must hold {n} entries")
+        rc, st, nm = self.engine.newton_solve(self.alpha, self.beta, f, u_ref, uu, settings.tolerance, settings.max_iterations or 0, ls.kind,
+                                              preconditioner, linear_rel_tol, linear_max_iter)
+        if not _is_torch(u) and not np.shares_memory(uu, u):
+            u[...] = uu.reshape(np.shape(u))
+        res = NewtonResult(int(st[0]), int(st[1]), int(st[2]), int(st[3]), float(nm[0]), float(nm[1]), float(nm[2]))
+        if rc != _ffi.FH_OK:
+            cls = {_ffi.FH_NEWTON_MAX_ITERATIONS: MaximumIterationsReached, _ffi.FH_NEWTON_JACOBIAN_ERROR: JacobianError}.get(rc, LineSearchError)
+            raise cls(rc, self.engine.last_error(), res)
+        return res
 
 
 class ConjugateGradient:

@@ -549,6 +549,20 @@ int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
 int mf_shift_ready(fh_ctx* c, const char* who, double alpha, double beta);
 int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
 int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bool with_scale);
+// Jacobi-PCG on the matrix-free map (engine_solver.hip; alpha == 0, beta == 1: the plain map of max_op), and the ordered host sum of
+// per-workgroup partials (stride K)
+int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
+                      uint64_t max_iter, uint64_t* num_iterations, double alpha = 0.0, double beta = 1.0);
+int sum_partials(fh_ctx* c, const double* dev, int blocks, int K, double* out);
+// the Newton residual F = alpha M d + beta (r(u) - f) at the context's u, the rows of the operator's Dirichlet nodes zero, and |F|^2
+// (engine_vector.hip; f may be null, d = u - u_ref is read when alpha != 0).  The scratch lives for one solve.
+struct NewtonScratch {
+    DevBuf<double> F;                 // S N: the residual
+    DevBuf<double> rpart, mpart;      // tile partials of r(u) and of M d
+    DevBuf<double> r, m;              // S N each: r(u) and M d off the tiles
+    DevBuf<double> wg, sums;          // per-workgroup partials of |F|^2, and their ordered range sums
+};
+int newton_residual(fh_ctx* c, double alpha, double beta, const double* f_dev, const double* d_dev, NewtonScratch& ns, double* norm2);
 
 // dispatch over (element kind, operator kind) -> template instantiation
 #define FH_FOR_ELEM_OP(EKV, OPV, CALL)                                             \

@@ -58,7 +58,7 @@ int fh_apply_dirichlet_rhs_dev(fh_ctx* c, double* rhs_dev, const uint64_t* nodes
 
 // ---- callers that keep K on the device: CG and the error integrals ---------------------------------
 // sum of per-workgroup partials (stride K) in workgroup order: deterministic
-static int sum_partials(fh_ctx* c, const double* dev, int blocks, int K, double* out) {
+extern "C++" int sum_partials(fh_ctx* c, const double* dev, int blocks, int K, double* out) {
     std::vector<double> h((size_t)blocks * K);
     HIP_TRY(c, hipMemcpyAsync(h.data(), dev, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -228,8 +228,8 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
 // alpha M + beta T(u) (fh_apply_shifted_tangent_dev; the plain map is alpha = 0, beta = 1): no pattern, no values.  The partials of p . Ap
 // come from the map's node pass (or its last pass off the tiles), summed over at most 2048 ranges in a fixed order; Jacobi takes the
 // matrix-free diagonal.  The diagonal (and with it the scale of the Dirichlet rows) is formed once per solve.
-static int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
-                             uint64_t max_iter, uint64_t* num_iterations, double alpha = 0.0, double beta = 1.0) {
+extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
+                                   uint64_t max_iter, uint64_t* num_iterations, double alpha, double beta) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     if (num_iterations) *num_iterations = 0;

@@ -987,6 +987,107 @@ int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x, double
     return FH_OK;
 }
 
+// r(u) of the current table (or one group of a rule-set table) ADDED to out without atomics, on every element kind: k_residual_elements and
+// the ordered node sums (the Newton residual off the tiles; fh_assemble_vector_dev scatters with fp64 atomics on the quadratic and cubic kinds)
+template <int OP>
+static void residual_elements_launch(fh_ctx* c, const KArgs& a, const unsigned char* active, double* fe) {
+    const dim3 grid((unsigned)((c->E + 255) / 256));
+    if (c->ei.d == 2) hipLaunchKernelGGL((k_residual_elements<2, OpT<OP, 2>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+    else hipLaunchKernelGGL((k_residual_elements<3, OpT<OP, 3>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+}
+static int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed) {
+    int rc = reset_status(c);
+    if (rc) return rc;
+    if (c->E == 0 || (c->has_mask && c->num_active == 0)) return FH_OK;
+    rc = build_source_adjacency(c);
+    if (rc) return rc;
+    const size_t need = (size_t)c->E * c->ei.n * c->S();
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    KArgs a;
+    fill_common(c, a);
+    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    switch (c->op) {
+        case FH_LAPLACE: residual_elements_launch<FH_LAPLACE>(c, a, active, c->fe_scratch.p); break;
+        case FH_LINEAR_ELASTIC: residual_elements_launch<FH_LINEAR_ELASTIC>(c, a, active, c->fe_scratch.p); break;
+        case FH_NEO_HOOKEAN: residual_elements_launch<FH_NEO_HOOKEAN>(c, a, active, c->fe_scratch.p); break;
+        default: residual_elements_launch<FH_STVK>(c, a, active, c->fe_scratch.p); break;
+    }
+    HIP_TRY(c, hipGetLastError());
+    rc = launch_vector_from_elements_soa(c, c->S(), c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
+    if (rc) return rc;
+    return read_status(c, failed);
+}
+
+// ---- the Newton residual  F = alpha M (u - u_ref) + beta (r(u) - f)  at the context's u with the rows of the operator's Dirichlet nodes zero,
+// and |F|^2 (fh_newton_solve_dev, engine_newton.hip).  On the tiles (Hex8, Tet4, Quad4, Tri3 without a rule-set table) the residual's element
+// pass and, for alpha != 0, k_mass_tiled on d (all of it: the mass term of F sees the Dirichlet entries of d) leave their partials, and ONE
+// node pass (k_newton_from_partials) forms F and the |F|^2 partials.  Elsewhere the residual (k_residual_elements and the ordered node sums,
+// residual_ordered_single) and M d (mass_full) land in scratch and k_newton_combine does the rest.  The partials are summed in a fixed order: bitwise reproducible.  Errors: those of the
+// residual (FH_SINGULAR_JACOBIAN).  A point with det F <= 0 of NeoHookean makes F NaN, not an error.
+int newton_residual(fh_ctx* c, double alpha, double beta, const double* f, const double* d, NewtonScratch& ns, double* norm2) {
+    const int S = c->S(), N = (int)c->N, n = S * N;
+    const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
+    int count = 0;   // per-workgroup partials of |F|^2 in ns.wg
+    int rc;
+    if (ns.F.n < (size_t)n) HIP_TRY(c, ns.F.alloc((size_t)n));
+    if (c->E > 0 && !c->rs.active && element_pass_covers(c) && (alpha == 0.0 || c->ei.ng == c->ei.n) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") &&
+        !c->env("FENRIS_HIP_NO_VECTOR_TILES")) {
+        rc = ensure_vector_tiles(c);
+        if (rc) return rc;
+        if (!c->vt_bad) {
+            const size_t need = (size_t)c->vt.v.npartials * S;
+            if (ns.rpart.n < need) HIP_TRY(c, ns.rpart.alloc(need));
+            if (alpha != 0.0 && ns.mpart.n < need) HIP_TRY(c, ns.mpart.alloc(need));
+            rc = reset_status(c);
+            if (rc) return rc;
+            KArgs a;
+            fill_common(c, a);
+            a.work_begin = 0;
+            a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
+            a.labels = nullptr;
+            const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+            bool ok = vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, ns.rpart.p) == FH_OK;
+            if (ok && alpha != 0.0)
+                ok = vector_tiles_mass_pass(c->elem_kind, S, c->stream, a, c->vt.v, active, c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, d, nullptr,
+                                            ns.mpart.p) == 0;
+            HIP_TRY(c, hipGetLastError());
+            if (ok) {
+                count = vector_tiles_operator_partials(N);
+                if (ns.wg.n < (size_t)count) HIP_TRY(c, ns.wg.alloc((size_t)count));
+                HIP_TRY(c, vector_tiles_newton_node_pass(c->stream, S, N, c->vt.v, ns.rpart.p, alpha != 0.0 ? ns.mpart.p : nullptr, f, dmask, alpha,
+                                                         beta, ns.F.p, ns.wg.p));
+                c->last_kernel = alpha != 0.0 ? "k_element_pass_tiled + k_mass_tiled + k_newton_from_partials"
+                                              : "k_element_pass_tiled + k_newton_from_partials";
+                rc = read_status(c, nullptr);
+                if (rc) return rc;
+            }
+        }
+    }
+    if (!count) {   // every other route: the residual and M d composed into scratch
+        if (ns.r.n < (size_t)n) HIP_TRY(c, ns.r.alloc((size_t)n));
+        HIP_TRY(c, hipMemsetAsync(ns.r.p, 0, sizeof(double) * (size_t)n, c->stream));
+        rc = c->rs.active ? rs_walk_accumulating(c, nullptr, [&](uint64_t* fl) { return residual_ordered_single(c, ns.r.p, fl); })
+                          : residual_ordered_single(c, ns.r.p, nullptr);
+        if (rc) return rc;
+        if (alpha != 0.0) {
+            if (ns.m.n < (size_t)n) HIP_TRY(c, ns.m.alloc((size_t)n));
+            rc = mass_full(c, d, nullptr, ns.m.p);
+            if (rc) return rc;
+        }
+        count = std::max(1, (n + 255) / 256);
+        if (ns.wg.n < (size_t)count) HIP_TRY(c, ns.wg.alloc((size_t)count));
+        hipLaunchKernelGGL(k_newton_combine, dim3(count), dim3(256), 0, c->stream, n, S, alpha, alpha != 0.0 ? ns.m.p : nullptr, beta, ns.r.p, f,
+                           dmask, ns.F.p, ns.wg.p);
+        HIP_TRY(c, hipGetLastError());
+        c->last_kernel = "k_residual_elements + k_vector_from_elements_soa + k_newton_combine";
+    }
+    const int ranges = std::min(2048, count);
+    if (ns.sums.n < (size_t)ranges) HIP_TRY(c, ns.sums.alloc(2048));
+    hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(ranges), dim3(256), 0, c->stream, ns.wg.p, (long long)count, ns.sums.p);
+    HIP_TRY(c, hipGetLastError());
+    return sum_partials(c, ns.sums.p, ranges, 1, norm2);
+}
+
 extern "C" {
 
 int fh_set_operator_dirichlet_nodes(fh_ctx* c, const uint64_t* nodes, uint64_t num_nodes) {

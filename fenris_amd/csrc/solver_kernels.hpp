@@ -457,6 +457,62 @@ __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N,
     }
 }
 
+// the residual r(u) of any element kind without atomics (the Newton residual off the tiles, engine_vector.hip): per point grad u = J^-T
+// sum_n ghat_n u_n^T (a.u, may be null: zero), the stress P of material_point, element vectors f_n = w |det J| P g_n by local node into
+// fe[a][e][c] for the ordered node sums of k_vector_from_elements_soa.  Inactive elements write zeros; det J == 0 is reported like the residual.
+template <int D, int S, int OP>
+__global__ void __launch_bounds__(256) k_residual_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.num_elements) return;
+    const bool live = !active || active[e] != 0;
+    const int* nodes = a.conn + (size_t)e * N;
+    auto out = [&](int n) { return fe + ((size_t)n * (size_t)a.num_elements + (size_t)e) * S; };
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < S; ++k) out(n)[k] = 0.0;
+    if (!live) return;
+    const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
+    for (int q = 0; q < a.nq; ++q) {
+        double Ji[D][D], s;
+        if (!mf_point<D>(a, nodes, NG, q, Ji, s)) {
+            report_singular(a.status, e);
+            continue;
+        }
+        double gu[D][S];
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+            for (int k = 0; k < S; ++k) gu[r][k] = 0.0;
+        if (a.u)
+            for (int n = 0; n < N; ++n) {
+                double g[D];
+                mf_grad<D>(a, N, q, n, Ji, g);
+#pragma unroll
+                for (int k = 0; k < S; ++k) {
+                    const double uv = a.u[(size_t)nodes[n] * S + k];
+#pragma unroll
+                    for (int r = 0; r < D; ++r) gu[r][k] = fma(g[r], uv, gu[r][k]);
+                }
+            }
+        double mu, lambda;
+        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        double P[S][D], psi;
+        material_point<OP, D, S, EP_VECTOR>(gu, mu, lambda, P, psi);
+        for (int n = 0; n < N; ++n) {
+            double g[D];
+            mf_grad<D>(a, N, q, n, Ji, g);
+            double* o = out(n);
+#pragma unroll
+            for (int i = 0; i < S; ++i) {
+                double t = 0.0;
+#pragma unroll
+                for (int r = 0; r < D; ++r) t = fma(P[i][r], g[r], t);
+                o[i] = fma(s, t, o[i]);
+            }
+        }
+    }
+}
+
 // the diagonal of the same map: entry (n, k) = sum_q s (dP[e_k g_n^T] g_n)_k, in ascending q.  The linear operators in closed form, as
 // diagonal_element_body (element_pass.hpp):  Laplace  s |g_n|^2,  LinearElastic  s (mu (|g_n|^2 + g_n,k^2) + lambda g_n,k^2); the nonlinear
 // ones by tangent_apply on the unit directions, as tangent_diagonal_body.
@@ -595,6 +651,34 @@ static __global__ void __launch_bounds__(256) k_mf_shift_combine(int n, int S, d
         if (dot_partial) d[0] = x[i] * yv;
     }
     if (dot_partial) block_sum_store<1>(d, dot_partial + blockIdx.x);
+}
+
+// the Newton residual off the tiles (engine_newton.hip): F = alpha m + beta (r - f) (m null: alpha = 0; f null: zero) with the rows of the
+// Dirichlet nodes (dmask, may be null) zero, and the per-workgroup partials of |F|^2 -- the same arithmetic as k_newton_from_partials
+static __global__ void __launch_bounds__(256) k_newton_combine(int n, int S, double alpha, const double* m, double beta, const double* r,
+                                                               const double* f, const unsigned char* dmask, double* F, double* norm_partial) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double sq[1] = {0.0};
+    if (i < n) {
+        const double rf = f ? r[i] - f[i] : r[i];
+        const double v = (dmask && dmask[i / S]) ? 0.0 : (m ? fma(beta, rf, alpha * m[i]) : beta * rf);
+        F[i] = v;
+        sq[0] = v * v;
+    }
+    block_sum_store<1>(sq, norm_partial + blockIdx.x);
+}
+
+// the line-search move of the Newton solve, in place on the context's u: u += da p with p = -q (q: the PCG solution of J q = F; null: no
+// move), and d = u - u_ref (u_ref null: zero) in the same sweep when d is given (the operand of the next mass term)
+static __global__ void __launch_bounds__(256) k_newton_move(int n, double da, const double* q, double* u, const double* u_ref, double* d) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double v = u[i];
+    if (q) {
+        v = fma(da, -q[i], v);
+        u[i] = v;
+    }
+    if (d) d[i] = u_ref ? v - u_ref[i] : v;
 }
 
 }  // namespace fenris_hip

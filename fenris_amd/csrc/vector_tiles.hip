@@ -718,6 +718,58 @@ __global__ void __launch_bounds__(256) k_shift_from_partials(int num_nodes, cons
     }
 }
 
+// node pass of the Newton residual (engine_newton.hip): F = alpha (node sums of the mass partials of d = u - u_ref) + beta (node sums of the
+// residual partials - f), OVERWRITTEN, both sums in ascending order as k_vector_from_partials forms them (mpart null: alpha = 0; f null: zero);
+// rows of the Dirichlet nodes (dmask, may be null) are zero.  norm_partial: per workgroup |F|^2 over its nodes, in a fixed tree
+// (k_operator_from_partials' layout), summed in index order by the caller.
+template <int S>
+__global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
+                                                              const double* mpart, const double* f, const unsigned char* dmask, double alpha,
+                                                              double beta, double* F, double* norm_partial) {
+    __shared__ double red[4];
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    double sq = 0.0;
+    if (node < num_nodes) {
+        double racc[S], macc[S];
+#pragma unroll
+        for (int c = 0; c < S; ++c) racc[c] = macc[c] = 0.0;
+        const unsigned k0 = np_off[node], k1 = np_off[node + 1];
+        for (unsigned kb = k0; kb < k1; kb += 4) {     // (k_vector_from_partials' loads: four partials in flight, the additions in order)
+            unsigned v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
+            double rp[4][S], mp[4][S];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int c = 0; c < S; ++c) {
+                    rp[j][c] = rpart[(size_t)v[j] * S + c];
+                    mp[j][c] = mpart ? mpart[(size_t)v[j] * S + c] : 0.0;
+                }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (kb + j < k1) {
+#pragma unroll
+                    for (int c = 0; c < S; ++c) {
+                        racc[c] += rp[j][c];
+                        macc[c] += mp[j][c];
+                    }
+                }
+        }
+        const bool fixed = dmask && dmask[node];
+#pragma unroll
+        for (int c = 0; c < S; ++c) {
+            const size_t i = (size_t)node * S + c;
+            const double r = f ? racc[c] - f[i] : racc[c];
+            const double v = fixed ? 0.0 : (mpart ? fma(beta, r, alpha * macc[c]) : beta * r);
+            F[i] = v;
+            sq = fma(v, v, sq);
+        }
+    }
+    const double tot = block_sum_256(sq, red);
+    if (threadIdx.x == 0) norm_partial[blockIdx.x] = tot;
+}
+
 template <typename T>
 hipError_t vt_alloc(VecTilesStore* st, int slot, T** p, size_t count) {
     hipError_t e = hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (count ? count : 1));
@@ -1030,6 +1082,15 @@ hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes
     if (S == 1) hipLaunchKernelGGL((k_shift_from_partials<1>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
     else if (S == 2) hipLaunchKernelGGL((k_shift_from_partials<2>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
     else hipLaunchKernelGGL((k_shift_from_partials<3>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
+    return hipGetLastError();
+}
+
+hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const double* mpart,
+                                         const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial) {
+    const int grid = vector_tiles_operator_partials(num_nodes);
+    if (S == 1) hipLaunchKernelGGL((k_newton_from_partials<1>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f, dmask, alpha, beta, F, norm_partial);
+    else if (S == 2) hipLaunchKernelGGL((k_newton_from_partials<2>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f, dmask, alpha, beta, F, norm_partial);
+    else hipLaunchKernelGGL((k_newton_from_partials<3>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f, dmask, alpha, beta, F, norm_partial);
     return hipGetLastError();
 }
 

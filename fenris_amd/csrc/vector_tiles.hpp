@@ -81,6 +81,13 @@ hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes
                                         const unsigned char* dmask, const double* scale, double alpha, double beta, const double* tv, double* y,
                                         double* dot_partial);
 
+// node pass of the Newton residual: F = alpha (node sums of mpart) + beta (node sums of rpart - f), OVERWRITTEN, with rpart the residual's
+// partials (vector_tiles_element_pass) and mpart the mass partials of d = u - u_ref (vector_tiles_mass_pass; null when alpha == 0), f null: zero;
+// the rows of the nodes with dmask[node] != 0 are zero.  norm_partial: one partial of |F|^2 per workgroup (vector_tiles_operator_partials of
+// them), to be summed in index order.
+hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const double* mpart,
+                                         const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial);
+
 // the shifted map fused on Hex8 with the monomial table (a.qmono; -1 otherwise): partial[P][S] of beta T(u) x + alpha M x in ONE element pass
 // (k_shifted_pass_tiled for the linear operators, which read the operand from a.u; k_shifted_tangent_tiled for NeoHookean / StVK, operand x),
 // or with mt.beta == 0 of alpha M x alone (k_mass_hex8_tiled, x read with the Dirichlet entries of dmask as zero; u not read).  The caller sums

@@ -52,7 +52,12 @@ enum {
     /* SolveErrorKind of the conjugate-gradient solver (fenris-sparse/src/cg.rs:277-286) */
     FH_CG_MAX_ITERATIONS = 7,
     FH_CG_INDEFINITE_OPERATOR = 8,
-    FH_CG_INDEFINITE_PRECONDITIONER = 9
+    FH_CG_INDEFINITE_PRECONDITIONER = 9,
+    /* NewtonError of Newton's method (fenris-optimize/src/newton.rs:25-34): MaximumIterationsReached, JacobianError (an error of the inner
+     * PCG: fh_newton_solve's stats[3] holds its code), LineSearchError */
+    FH_NEWTON_MAX_ITERATIONS = 10,
+    FH_NEWTON_JACOBIAN_ERROR = 11,
+    FH_NEWTON_LINE_SEARCH_FAILED = 12
 };
 
 /* element kinds: Quad4d2Element (src/element/quadrilateral.rs:70-142), Hex8Element
@@ -454,6 +459,39 @@ int fh_cg_solve_shifted_tangent(fh_ctx*, double alpha, double beta, const double
                                 uint64_t max_iter, uint64_t* num_iterations);
 int fh_cg_solve_shifted_tangent_dev(fh_ctx*, double alpha, double beta, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
                                     uint64_t max_iter, uint64_t* num_iterations);
+/* ---- Newton's method for F(u) = 0 with F(u) = alpha M (u - u_ref) + beta (r(u) - f) and the Jacobian J(u) = alpha M + beta T(u), the map of
+ * fh_apply_shifted_tangent_dev: alpha = 0, beta = 1 is static equilibrium r(u) = f; alpha = 1, beta = dt^2 a backward-Euler step on positions
+ * (u_ref = u_n + dt v_n).  newton_line_search (fenris-optimize/src/newton.rs:77-130) step for step:
+ *   - converged when ||F||_2 <= tolerance (absolute), tested before every iteration: a guess that satisfies it returns after 0 iterations;
+ *   - MaximumIterationsReached when the iteration count has reached max_iterations (0: no limit) before convergence (newton.rs:99-106);
+ *   - the Newton step: J (-dx) = F by fh_cg_solve_shifted_tangent_dev's Jacobi-PCG (preconditioner, RelativeResidualCriterion(linear_rel_tol),
+ *     linear_max_iter; 0: no limit) from a zero guess, p = -(-dx) (newton.rs:108-117); any error of that solve (the FH_CG_* codes, or what
+ *     the map reports, e.g. FH_SINGULAR_JACOBIAN) gives FH_NEWTON_JACOBIAN_ERROR with the inner code in stats[3];
+ *   - FH_NEWTON_NO_LINE_SEARCH: u += p (NoLineSearch, newton.rs:140-163);
+ *   - FH_NEWTON_BACKTRACKING: BacktrackingLineSearch (newton.rs:165-249), c = 1e-4, alpha_min = 1e-6: trial step lengths a = 1, 0.75, 0.5,
+ *     0.25, 0.0625, ... (0.25 each time), u += (a - a_prev) p, accepted when g <= (1 - c a) g_0 with g = ||F||^2 / 2; after a trial with
+ *     a < alpha_min that is not accepted: FH_NEWTON_LINE_SEARCH_FAILED.  A trial state whose residual is NaN (NeoHookean with det F <= 0 at
+ *     a quadrature point) compares false and the search backtracks past it.
+ * One deliberate deviation: newton.rs:98 leaves its loop on a NaN norm and reports success; here a non-finite ||F|| of an ACCEPTED state (the
+ * guess, or any state under FH_NEWTON_NO_LINE_SEARCH) ends the solve with FH_NEWTON_LINE_SEARCH_FAILED.
+ * Dirichlet dofs: the nodes of fh_set_operator_dirichlet_nodes, held at the values u has on entry (inhomogeneous values allowed): F is zero on
+ * their rows and so is the step, so those entries of u come back bit for bit.  f_dev (the load) and u_ref_dev: S N doubles, or null for zero.
+ * u_dev: the guess on entry (with the Dirichlet values); on return the iterate the reference leaves in x -- the solution, or on failure the
+ * last iterate (for FH_NEWTON_LINE_SEARCH_FAILED from the search: the last trial).  The context's u (fh_set_u*) holds the same on return and
+ * u_gen has moved.  Operators: FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK (mass operators, FH_TENSOR: FH_UNSUPPORTED); alpha != 0
+ * without fh_set_mass_density: FH_INVALID_STATE; alpha, beta or tolerance not finite, a null u, an unknown line search or preconditioner:
+ * FH_BAD_ARGUMENT.  It honours the element kinds, table forms and element masks of the residual.  The residual and its norm come from one node
+ * pass over the tile partials on Hex8, Tet4, Quad4 and Tri3 (no rule-set table); elsewhere from element vectors summed per node in a fixed
+ * order and the mass term, composed.  No floating-point atomics on either route: a solve repeats bit for bit on every element kind.
+ * stats (may be null): [0] Newton iterations, [1] residual evaluations, [2] PCG iterations summed, [3] status of the last PCG;
+ * norms (may be null): [0] ||F(u_0)||, [1] ||F|| at return, [2] the last accepted step length (0: none). */
+enum { FH_NEWTON_NO_LINE_SEARCH = 0, FH_NEWTON_BACKTRACKING = 1 };
+int fh_newton_solve_dev(fh_ctx*, double alpha, double beta, const double* f_dev, const double* u_ref_dev, double* u_dev, double tolerance,
+                        uint64_t max_iterations, int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter,
+                        uint64_t* stats, double* norms);
+/* the same with host arrays */
+int fh_newton_solve(fh_ctx*, double alpha, double beta, const double* f, const double* u_ref, double* u, double tolerance, uint64_t max_iterations,
+                    int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter, uint64_t* stats, double* norms);
 /* estimate_L2_error_squared / estimate_H1_seminorm_error_squared (src/error.rs:287-372):
  *   sum_e sum_q w |det J| |u_h(x_q) - u(x_q)|^2      resp.   |grad u_h(x_q) - grad u(x_q)|_F^2
  * with the quadrature table of the context.  The reference solution is arbitrary code in the reference; here the
