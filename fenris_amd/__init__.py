@@ -3,9 +3,9 @@
 Python host layer over the C ABI of libfenris_hip.so (include/fenris_hip.h).  Only the hot path of
 fenris -- global stiffness / residual assembly -- lives here; see DESIGN.md.
 """
-from . import _ffi, assembly, io, mesh, operators, quadrature, reorder
+from . import _ffi, assembly, io, mesh, multigrid, operators, quadrature, refinement, reorder
 from ._ffi import (ASSEMBLE_OVERWRITE, ASSEMBLE_REPRODUCIBLE, HEX8, HEX27, LAPLACE, LINEAR_ELASTIC, NEO_HOOKEAN, QUAD4, SCATTER_ATOMIC,
-                   SCATTER_COLORED, SCATTER_GATHER, STVK, TET4, TRI3, TET10, QUAD9, TRI6, HEX20, TET20, MASS_SCALAR, MASS_VECTOR, FenrisError, SingularJacobianError)
+                   SCATTER_COLORED, SCATTER_GATHER, STVK, PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, TET4, TRI3, TET10, QUAD9, TRI6, HEX20, TET20, MASS_SCALAR, MASS_VECTOR, FenrisError, SingularJacobianError)
 from .assembly import (CsrAssembler, CsrMatrix, CsrParAssembler, DisjointSubsetsColors, ElementEllipticAssembler, ElementMassAssembler,
                        ElementEllipticAssemblerBuilder, ElementSourceAssembler, ElementSourceAssemblerBuilder, Engine,
                        MockElementAssembler, UniformQuadratureTable, CompactQuadratureTable, GeneralQuadratureTable,
@@ -17,6 +17,9 @@ from .assembly import (CsrAssembler, CsrMatrix, CsrParAssembler, DisjointSubsets
                        estimate_H1_seminorm_error_squared, estimate_L2_error, estimate_L2_error_squared)
 from .compose import (AggregateElementAssembler, MapElementNodes, TransformElementMatrix, TransformElementScalar,
                       TransformElementVector)
+from .multigrid import GeometricMultigrid
+from .refinement import (Transfer, permute_transfer, refine_uniformly, refine_uniformly_repeat, refine_uniformly_repeat_with_transfers,
+                         refine_uniformly_with_transfer)
 from .mesh import Mesh, hex20_mesh_from_hex8, hex27_mesh_from_hex8, procedural, quad9_mesh_from_quad4, tet10_mesh_from_tet4, tet20_mesh_from_tet4, tri6_mesh_from_tri3
 from .operators import (Density, GravitySource, SourceFunction, LameParameters, LaplaceOperator, LinearElasticMaterial, MaterialEllipticOperator,
                         NeoHookeanMaterial, StVKMaterial, TensorEllipticOperator, YoungPoisson)

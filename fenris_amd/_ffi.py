@@ -20,6 +20,7 @@ SCATTER_ATOMIC, SCATTER_COLORED, SCATTER_GATHER = 0, 1, 2
 FH_CG_MAX_ITERATIONS, FH_CG_INDEFINITE_OPERATOR, FH_CG_INDEFINITE_PRECONDITIONER = 7, 8, 9
 FH_NEWTON_MAX_ITERATIONS, FH_NEWTON_JACOBIAN_ERROR, FH_NEWTON_LINE_SEARCH_FAILED = 10, 11, 12
 NEWTON_NO_LINE_SEARCH, NEWTON_BACKTRACKING = 0, 1
+PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID = 0, 1, 2
 ASSEMBLE_OVERWRITE = 0x100
 ASSEMBLE_REPRODUCIBLE = 0x200
 
@@ -134,6 +135,13 @@ _SIGS = {
                                   C.c_uint64, u64p, f64p]),
     "fh_newton_solve_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_int,
                                       C.c_int, C.c_double, C.c_uint64, u64p, f64p]),
+    "fh_mg_create": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(u64p), C.POINTER(u64p), C.POINTER(f64p),
+                               C.POINTER(C.c_void_p)]),
+    "fh_mg_destroy": (None, [C.c_void_p]),
+    "fh_set_multigrid": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_mg_set_smoother": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint32]),
+    "fh_mg_level_info": (C.c_int, [C.c_void_p, C.c_uint32, f64p, u64p]),
+    "fh_mg_apply_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "fh_estimate_L2_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),
     "fh_estimate_L2_error_squared_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, f64p]),
     "fh_estimate_H1_seminorm_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),
@@ -157,6 +165,7 @@ _SIGS = {
     "fh_refine_to_quadratic": (C.c_int, [C.c_int, f64p, C.c_uint64, u64p, C.c_uint64, f64p, u64p, u64p]),
     "fh_cuthill_mckee": (C.c_int, [C.c_uint64, u64p, u64p, u64p]),
     "fh_reorder_mesh": (C.c_int, [C.c_uint64, C.c_uint64, u64p, C.c_uint64, u64p, u64p]),
+    "fh_refine_hex8_uniform": (C.c_int, [f64p, C.c_uint64, u64p, C.c_uint64, f64p, u64p, u64p, u64p, u64p, f64p, u64p]),
     "fh_lame_from_young_poisson": (C.c_int, [C.c_double, C.c_double, f64p, f64p]),
     "fh_morton_partition": (C.c_int, [C.c_uint32, f64p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
     "fh_partition_create": (C.c_void_p, [C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),

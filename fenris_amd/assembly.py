@@ -975,11 +975,20 @@ class MatrixFreeOperator:
         self.element_assembler = element_assembler
         self.engine = element_assembler.engine
         self._nodes = None
+        self._mg = None
 
     def with_dirichlet_nodes(self, nodes):
         self._nodes = None if nodes is None else _ffi.as_u64(nodes).copy()
         self._bind(force=True)
         return self
+
+    def with_multigrid(self, mg):
+        """a GeometricMultigrid (fenris_amd.multigrid) over this operator's assembler: cg_solve then defaults to PRECOND_MULTIGRID"""
+        self._mg = mg
+        return self
+
+    def _mg_density(self):
+        return None
 
     def _bind(self, force=False):
         # (the engine keeps the nodes of the operator that used it last: handed over again only when another operator has used it since)
@@ -1011,9 +1020,14 @@ class MatrixFreeOperator:
         self._diagonal_dev(d)
         return d if device else d.cpu().numpy()
 
-    def cg_solve(self, b, x, preconditioner=1, rel_tol=1e-9, max_iter=0):
-        """fh_cg_solve_matrix_free(_dev) on this operator; returns the iteration count"""
+    def cg_solve(self, b, x, preconditioner=None, rel_tol=1e-9, max_iter=0):
+        """fh_cg_solve_matrix_free(_dev) on this operator; returns the iteration count.  preconditioner None: PRECOND_MULTIGRID with a
+        hierarchy (with_multigrid), else Jacobi"""
         self._bind()
+        if preconditioner is None:
+            preconditioner = _ffi.PRECOND_MULTIGRID if self._mg is not None else _ffi.PRECOND_JACOBI
+        if preconditioner == _ffi.PRECOND_MULTIGRID and self._mg is not None:
+            self._mg._bind(self._nodes, self._mg_density())
         return self._cg_solve(b, x, preconditioner, rel_tol, max_iter)
 
     def _apply_dev(self, x_t, y_t):
@@ -1061,6 +1075,9 @@ class MatrixFreeShiftedTangent(MatrixFreeOperator):
         """new alpha, beta (e.g. another dt between steps); returns self"""
         self.alpha, self.beta = float(alpha), float(beta)
         return self
+
+    def _mg_density(self):
+        return self._rho if self.alpha != 0.0 else None
 
     def _bind(self, force=False):
         super()._bind(force)
@@ -1179,6 +1196,12 @@ class MatrixFreeNewton:
         self.engine = element_assembler.engine
         self._nodes, self._f, self._u_ref, self._rho = None, None, None, None
         self.alpha, self.beta = 0.0, 1.0
+        self._mg = None
+
+    def with_multigrid(self, mg):
+        """a GeometricMultigrid (fenris_amd.multigrid) over this assembler: solve then defaults to PRECOND_MULTIGRID; returns self"""
+        self._mg = mg
+        return self
 
     def with_dirichlet_nodes(self, nodes):
         """the nodes held at the values u has on entry to solve (None: none); returns self"""
@@ -1212,10 +1235,15 @@ class MatrixFreeNewton:
             self.engine.set_mass_density(self._rho)
             self.engine._mass_bound = self
 
-    def solve(self, u, settings: NewtonSettings = NewtonSettings(), line_search=None, preconditioner=1, linear_rel_tol=1e-8, linear_max_iter=0):
+    def solve(self, u, settings: NewtonSettings = NewtonSettings(), line_search=None, preconditioner=None, linear_rel_tol=1e-8, linear_max_iter=0):
         """u: the guess with the Dirichlet values (numpy array or device tensor), overwritten by the solution.  Returns a NewtonResult;
-        raises MaximumIterationsReached, JacobianError or LineSearchError with u holding the reference's x at the failure."""
+        raises MaximumIterationsReached, JacobianError or LineSearchError with u holding the reference's x at the failure.  preconditioner
+        None: PRECOND_MULTIGRID with a hierarchy (with_multigrid), else Jacobi."""
         self._bind()
+        if preconditioner is None:
+            preconditioner = _ffi.PRECOND_MULTIGRID if self._mg is not None else _ffi.PRECOND_JACOBI
+        if preconditioner == _ffi.PRECOND_MULTIGRID and self._mg is not None:
+            self._mg._bind(self._nodes, self._rho if self.alpha != 0.0 else None)
         ls = BacktrackingLineSearch() if line_search is None else line_search
         f, u_ref = self._f, self._u_ref
         n = self.element_assembler.solution_dim() * self.engine.num_nodes()

@@ -460,6 +460,8 @@ struct fh_ctx {
     DevBuf<double> mf_mass;
     unsigned long long geom_gen = 0;   // counts fh_update_vertices calls
     unsigned long long u_gen = 0;      // counts fh_set_u* calls
+    unsigned long long dirichlet_gen = 0;   // counts fh_set_operator_dirichlet_nodes calls
+    fh_mg* mg = nullptr;               // the multigrid hierarchy of FH_PRECOND_MULTIGRID (fh_set_multigrid; not owned)
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -554,6 +556,16 @@ int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bo
 int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
                       uint64_t max_iter, uint64_t* num_iterations, double alpha = 0.0, double beta = 1.0);
 int sum_partials(fh_ctx* c, const double* dev, int blocks, int K, double* out);
+// FH_PRECOND_MULTIGRID (engine_mg.hip) on c->mg: per solve the injection of u into the nonlinear coarse levels and the per-level diagonal,
+// eigenvalue estimate and coarsest factor (each formed again only when its key changed); one V-cycle z = B r; the coarse levels' status
+int mg_setup(fh_ctx* fine, double alpha, double beta);
+int mg_precondition(fh_ctx* fine, double alpha, double beta, const double* r, double* z);
+int mg_finish(fh_ctx* fine);
+void mg_orphan(fh_mg* mg);   // its fine context is going away: fh_mg_destroy will not touch it
+// PCG with the V-cycle (engine_solver.hip): x += alpha p, r -= alpha Ap, partials of r . r into slot 1 of 2 per workgroup; partials of
+// z . r into slot 0 of K, and p = z when p is given.  `blocks` workgroups of 256.
+void mg_cg_update(hipStream_t st, int blocks, int n, double alpha, const double* p, const double* Ap, double* x, double* r, double* partial);
+void mg_cg_zr(hipStream_t st, int blocks, int n, int K, const double* z, const double* r, double* p, double* partial);
 // the Newton residual F = alpha M d + beta (r(u) - f) at the context's u, the rows of the operator's Dirichlet nodes zero, and |F|^2
 // (engine_vector.hip; f may be null, d = u - u_ref is read when alpha != 0).  The scratch lives for one solve.
 struct NewtonScratch {

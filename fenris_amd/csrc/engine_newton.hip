@@ -106,7 +106,7 @@ static int newton_solve_dev(fh_ctx* c, double alpha, double beta, const double* 
     if (!u_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": u is null");
     if (line_search != FH_NEWTON_NO_LINE_SEARCH && line_search != FH_NEWTON_BACKTRACKING)
         return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown line search");
-    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI)
+    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI && preconditioner != FH_PRECOND_MULTIGRID)
         return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown preconditioner");
     if (c->N == 0) return FH_OK;
     rc = fh_set_u_dev(c, u_dev);   // the iterate lives in the context's u

@@ -1,4 +1,6 @@
 // Dirichlet rows, SpMV, Jacobi-PCG, error integrals: C ABI
+#include <functional>
+
 #include "engine_internal.hpp"
 
 extern "C" {
@@ -125,9 +127,11 @@ int fh_spmv_dev(fh_ctx* c, const double* values_dev, const double* x_dev, double
 // ConjugateGradient::solve_with_guess (cg.rs:366-478) around an operator: apply(in, out, ranges) writes out = A in and, when ranges is
 // not null, leaves the partials of in . out summed over *ranges contiguous ranges in partial (a DevBuf<double> of at least 3 * max(gv, *ranges)
 // doubles: the caller sizes it); dinv: the Jacobi preconditioner or null.  Per iteration the host tests convergence (RelativeResidualCriterion).
+// precond (FH_PRECOND_MULTIGRID, dinv null): z = B r as a call of its own after each update of r, and z . r from k_mg_cg_zr.
 extern "C++" template <class Apply>
 static int cg_run(fh_ctx* c, int n, const double* b_dev, double* x_dev, const double* dinv, DevBuf<double>& partial, DevBuf<double>& wg_partial,
-                  double rel_tol, uint64_t max_iter, uint64_t* num_iterations, Apply&& apply) {
+                  double rel_tol, uint64_t max_iter, uint64_t* num_iterations, Apply&& apply,
+                  const std::function<int(const double*, double*)>& precond = {}) {
     const int gv = std::min(1024, (n + 255) / 256);                               // vector kernels: ranges of their per-workgroup partials
     const int gvb = std::max(1, (n + 255) / 256);                                 // ... and their workgroups: one entry per thread, short-lived (see spmv_launch)
     DevBuf<double> r, z, p, Ap;
@@ -153,6 +157,15 @@ static int cg_run(fh_ctx* c, int n, const double* b_dev, double* x_dev, const do
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return FH_OK;
     }
+    if (precond) {   // z = B r, p = z, and z . r
+        rc = precond(r.p, z.p);
+        if (rc) return rc;
+        mg_cg_zr(c->stream, gvb, n, 1, z.p, r.p, p.p, wg_partial.p);
+        hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(gv), dim3(256), 0, c->stream, wg_partial.p, (long long)gvb, partial.p);
+        HIP_TRY(c, hipGetLastError());
+        rc = sum_partials(c, partial.p, gv, 1, &zTr);
+        if (rc) return rc;
+    }
     uint64_t it = 0;
     int status = FH_OK;
     for (;;) {
@@ -167,7 +180,14 @@ static int cg_run(fh_ctx* c, int n, const double* b_dev, double* x_dev, const do
         if (pAp <= 0.0) { status = FH_CG_INDEFINITE_OPERATOR; break; }
         if (zTr <= 0.0) { status = FH_CG_INDEFINITE_PRECONDITIONER; break; }
         const double alpha = zTr / pAp;
-        hipLaunchKernelGGL(k_cg_update, dim3(gvb), dim3(256), 0, c->stream, n, alpha, p.p, Ap.p, dinv, x_dev, r.p, z.p, wg_partial.p);
+        if (precond) {
+            mg_cg_update(c->stream, gvb, n, alpha, p.p, Ap.p, x_dev, r.p, wg_partial.p);
+            rc = precond(r.p, z.p);
+            if (rc) return rc;
+            mg_cg_zr(c->stream, gvb, n, 2, z.p, r.p, nullptr, wg_partial.p);
+        } else {
+            hipLaunchKernelGGL(k_cg_update, dim3(gvb), dim3(256), 0, c->stream, n, alpha, p.p, Ap.p, dinv, x_dev, r.p, z.p, wg_partial.p);
+        }
         hipLaunchKernelGGL(k_sum_partial_ranges<2>, dim3(gv), dim3(256), 0, c->stream, wg_partial.p, (long long)gvb, partial.p);
         HIP_TRY(c, hipGetLastError());
         ++it;
@@ -236,8 +256,10 @@ extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const
     int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, max_op) : mf_shift_ready(c, who, alpha, beta);
     if (rc) return rc;
     if (!b_dev || !x_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
-    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI)
+    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI && preconditioner != FH_PRECOND_MULTIGRID)
         return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown preconditioner");
+    const bool multigrid = preconditioner == FH_PRECOND_MULTIGRID;
+    if (multigrid && !c->mg) return c->fail(FH_INVALID_STATE, std::string(who) + ": FH_PRECOND_MULTIGRID needs a hierarchy (fh_set_multigrid)");
     const int S = c->S();
     const int n = S * (int)c->N;
     if (n == 0) return FH_OK;
@@ -245,7 +267,10 @@ extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const
     const int gs_max = 2048;
     DevBuf<double> dinv, partial, wg_partial;
     HIP_TRY(c, partial.alloc((size_t)3 * std::max(gv, gs_max)));
-    if (preconditioner == FH_PRECOND_JACOBI || c->mf_num_dirichlet) {
+    if (multigrid) {   // (the fine level's diagonal forms the scale of its Dirichlet rows)
+        rc = mg_setup(c, alpha, beta);
+        if (rc) return rc;
+    } else if (preconditioner == FH_PRECOND_JACOBI || c->mf_num_dirichlet) {
         HIP_TRY(c, dinv.alloc(n));
         rc = mf_shift_diagonal(c, alpha, beta, dinv.p, true);
         if (rc) return rc;
@@ -266,10 +291,16 @@ extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const
                                hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(*ranges), dim3(256), 0, c->stream, wg_partial.p, (long long)count, partial.p);
                                HIP_TRY(c, hipGetLastError());
                                return (int)FH_OK;
-                           });
+                           },
+                           multigrid ? std::function<int(const double*, double*)>([&](const double* r, double* z) { return mg_precondition(c, alpha, beta, r, z); })
+                                     : std::function<int(const double*, double*)>());
     // a singular Jacobian shows in the map's first application already (and in the diagonal): report it over the solver's status
     rc = read_status(c, nullptr);
     if (rc) return rc;
+    if (multigrid) {
+        rc = mg_finish(c);
+        if (rc) return rc;
+    }
     return rcg;
 }
 

@@ -1098,6 +1098,7 @@ int fh_set_operator_dirichlet_nodes(fh_ctx* c, const uint64_t* nodes, uint64_t n
     for (uint64_t i = 0; i < num_nodes; ++i)
         if (nodes[i] >= c->N) return c->fail(FH_BAD_ARGUMENT, "Dirichlet node out of range");
     c->mf_num_dirichlet = 0;   // (the scale does not depend on which nodes are constrained: mf_scale stays valid)
+    ++c->dirichlet_gen;
     if (!nodes || num_nodes == 0) return FH_OK;
     DevBuf<unsigned long long> dn;
     HIP_TRY(c, c->mf_dmask.alloc((size_t)c->N + 1));

@@ -324,6 +324,95 @@ void hex8_to_hex27(const double* verts, const uint64_t* hex8, uint64_t ncells, d
     *out_nv = next;
 }
 
+// Uniform Hex8 refinement: every hexahedron splits into 8 children on the 3x3x3 lattice of its reference cube (lattice coordinate
+// i - 1 in {-1, 0, 1} per axis).  A lattice point is the average of the corners that agree with it on its nonzero axes: 1 corner (the
+// coarse vertex, weight 1), 2 (edge midpoint, 1/2), 4 (face centre, 1/4) or 8 (cell centre, 1/8) -- the trilinear map at that point, and
+// the trilinear interpolation of any coarse field.  Coarse vertices keep their indices; the new vertices follow in order of first
+// appearance while sweeping the cells in order, and within a cell the lattice points in x-fastest order.  Child (cx, cy, cz) takes the
+// lattice points (cx, cy, cz) + corner offset of each Hex8 node, so it keeps the parent's node order and orientation.  The transfer rows
+// (fine node -> coarse parents) list the parents in ascending index.  Sizes only when out_c is null.
+static const int HEX8_SGN[8][3] = {{-1, -1, -1}, {1, -1, -1}, {1, 1, -1}, {-1, 1, -1}, {-1, -1, 1}, {1, -1, 1}, {1, 1, 1}, {-1, 1, 1}};
+
+static void refine_hex8_uniform(const double* verts, const uint64_t* hex8, uint64_t nv, uint64_t ncells, double* out_v, uint64_t* out_nv,
+                         uint64_t* out_c, uint64_t* t_off, uint64_t* t_idx, double* t_w, uint64_t* out_nnz) {
+    const uint64_t NONE = ~0ull;
+    std::unordered_map<ParentKey, uint64_t, ParentKeyHash> label;
+    label.reserve(static_cast<size_t>(ncells) * 8);
+    std::vector<ParentKey> parents;   // of the new vertices, in order
+    uint64_t next = nv;
+    for (uint64_t e = 0; e < ncells; ++e) {
+        const uint64_t* g = hex8 + 8 * e;
+        uint64_t lat[27];
+        for (int k = 0; k < 3; ++k)
+            for (int j = 0; j < 3; ++j)
+                for (int i = 0; i < 3; ++i) {
+                    const int L[3] = {i - 1, j - 1, k - 1};
+                    ParentKey key;
+                    key.p.fill(NONE);
+                    int cnt = 0;
+                    for (int a = 0; a < 8; ++a) {
+                        bool ok = true;
+                        for (int r = 0; r < 3; ++r) ok = ok && (L[r] == 0 || HEX8_SGN[a][r] == L[r]);
+                        if (ok) key.p[cnt++] = g[a];
+                    }
+                    std::sort(key.p.begin(), key.p.end());
+                    uint64_t id;
+                    if (cnt == 1) {
+                        id = key.p[0];
+                    } else {
+                        auto it = label.find(key);
+                        if (it == label.end()) {
+                            id = next++;
+                            label.emplace(key, id);
+                            parents.push_back(key);
+                        } else {
+                            id = it->second;
+                        }
+                    }
+                    lat[i + 3 * j + 9 * k] = id;
+                }
+        if (out_c)
+            for (int cz = 0; cz < 2; ++cz)
+                for (int cy = 0; cy < 2; ++cy)
+                    for (int cx = 0; cx < 2; ++cx) {
+                        uint64_t* child = out_c + 8 * (8 * e + (uint64_t)(cx + 2 * cy + 4 * cz));
+                        for (int a = 0; a < 8; ++a) {
+                            const int i = cx + (HEX8_SGN[a][0] + 1) / 2, j = cy + (HEX8_SGN[a][1] + 1) / 2, k = cz + (HEX8_SGN[a][2] + 1) / 2;
+                            child[a] = lat[i + 3 * j + 9 * k];
+                        }
+                    }
+    }
+    uint64_t nnz = nv;
+    for (const auto& k : parents) nnz += (uint64_t)(std::find(k.p.begin(), k.p.end(), NONE) - k.p.begin());
+    *out_nv = next;
+    *out_nnz = nnz;
+    if (!out_c) return;
+    for (uint64_t i = 0; i < nv; ++i) {
+        for (int r = 0; r < 3; ++r) out_v[3 * i + r] = verts[3 * i + r];
+        t_off[i] = i;
+        t_idx[i] = i;
+        t_w[i] = 1.0;
+    }
+    uint64_t pos = nv;
+    for (uint64_t m = 0; m < parents.size(); ++m) {
+        const auto& k = parents[m];
+        const int cnt = (int)(std::find(k.p.begin(), k.p.end(), NONE) - k.p.begin());
+        const double w = 1.0 / cnt;
+        const uint64_t i = nv + m;
+        t_off[i] = pos;
+        for (int r = 0; r < 3; ++r) {
+            double s = 0.0;
+            for (int q = 0; q < cnt; ++q) s += verts[3 * k.p[q] + r];
+            out_v[3 * i + r] = s * w;
+        }
+        for (int q = 0; q < cnt; ++q) {
+            t_idx[pos] = k.p[q];
+            t_w[pos++] = w;
+        }
+    }
+    t_off[next] = pos;
+}
+
 // ---------------------------------------------------------------------------------------- colouring
 // sequential_greedy_coloring (fenris-paradis/src/coloring.rs:6-70): repeated passes over the still
 // uncoloured elements in ascending order; an element joins the current colour iff none of its nodes
@@ -417,6 +506,15 @@ int fh_hex8_to_hex27(const double* v, uint64_t nv, const uint64_t* hex8, uint64_
     for (uint64_t i = 0; i < 8 * ncells; ++i)
         if (hex8[i] >= nv) return FH_BAD_ARGUMENT;
     hex8_to_hex27(v, hex8, ncells, out_v, out_nv, out_c);
+    return FH_OK;
+}
+int fh_refine_hex8_uniform(const double* v, uint64_t nv, const uint64_t* hex8, uint64_t ncells, double* out_v, uint64_t* out_nv,
+                           uint64_t* out_c, uint64_t* transfer_offsets, uint64_t* transfer_indices, double* transfer_weights, uint64_t* out_nnz) {
+    if (!v || (ncells && !hex8) || !out_nv || !out_nnz) return FH_BAD_ARGUMENT;
+    if (out_c && (!out_v || !transfer_offsets || !transfer_indices || !transfer_weights)) return FH_BAD_ARGUMENT;
+    for (uint64_t i = 0; i < 8 * ncells; ++i)
+        if (hex8[i] >= nv) return FH_BAD_ARGUMENT;
+    refine_hex8_uniform(v, hex8, nv, ncells, out_v, out_nv, out_c, transfer_offsets, transfer_indices, transfer_weights, out_nnz);
     return FH_OK;
 }
 // Tet20Mesh::from(&tet4_mesh), src/mesh_convert.rs:658-775

@@ -107,6 +107,7 @@ enum { FH_ASSEMBLE_OVERWRITE = 0x100 };
 enum { FH_ASSEMBLE_REPRODUCIBLE = 0x200 };
 
 typedef struct fh_ctx fh_ctx;
+typedef struct fh_mg fh_mg;
 
 /* ---- context ------------------------------------------------------------------------------- */
 fh_ctx* fh_create(int device_id);               /* NULL if the device cannot be initialised */
@@ -351,6 +352,16 @@ int fh_refine_to_quadratic(int from_kind, const double* vertices, uint64_t num_v
 int fh_load_msh(const char* bytes, uint64_t len, int elem_kind, double* vertices, uint64_t* num_vertices,
                 uint64_t* connectivity, uint64_t* num_elements);
 const char* fh_msh_last_error(void);
+/* Uniform refinement of a Hex8 mesh: every hexahedron splits into 8 children in the Hex8 node order, with the parent's orientation.
+ * Fine vertices: the coarse vertices first under their own indices, then one per unique edge, face and cell in order of first
+ * appearance (cells in order; within a cell the points of its 3x3x3 reference lattice, x fastest).  The transfer, CSR by fine node:
+ * fine i = sum_k w_k coarse j_k, parents in ascending index, weights 1 (vertex), 1/2 (edge), 1/4 (face), 1/8 (cell) -- the trilinear
+ * interpolation, also the placement of the new vertices.  Two calls: with out_connectivity NULL only *out_num_vertices and *out_nnz
+ * are written; then out_vertices (3 per vertex), out_connectivity (64 per coarse cell), transfer_offsets (num_vertices + 1),
+ * transfer_indices and transfer_weights (nnz each). */
+int fh_refine_hex8_uniform(const double* vertices, uint64_t num_vertices, const uint64_t* hex8, uint64_t num_cells, double* out_vertices,
+                           uint64_t* out_num_vertices, uint64_t* out_connectivity, uint64_t* transfer_offsets, uint64_t* transfer_indices,
+                           double* transfer_weights, uint64_t* out_nnz);
 /* cuthill_mckee on a square sparsity pattern (src/mesh/reorder.rs:171-233): perm_out[target] = source.  The
  * reference orders equal-degree neighbours with an unstable sort (unspecified); ties are broken by ascending index. */
 int fh_cuthill_mckee(uint64_t num_rows, const uint64_t* row_offsets, const uint64_t* col_indices, uint64_t* perm_out);
@@ -376,7 +387,7 @@ int fh_spmv_dev(fh_ctx*, const double* values_dev, const double* x_dev, double* 
  * return (the iterate reached so far on failure); max_iter == 0 means no limit; *num_iterations counts the updates
  * of x.  Errors: FH_CG_MAX_ITERATIONS, FH_CG_INDEFINITE_OPERATOR (p.Ap <= 0), FH_CG_INDEFINITE_PRECONDITIONER
  * (z.r <= 0).  Reductions are ordered (no floating-point atomics): runs are bitwise reproducible. */
-enum { FH_PRECOND_IDENTITY = 0, FH_PRECOND_JACOBI = 1 };
+enum { FH_PRECOND_IDENTITY = 0, FH_PRECOND_JACOBI = 1, FH_PRECOND_MULTIGRID = 2 };
 int fh_cg_solve(fh_ctx*, const double* values, const double* b, double* x, int preconditioner, double rel_tol,
                 uint64_t max_iter, uint64_t* num_iterations);
 int fh_cg_solve_dev(fh_ctx*, const double* values_dev, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
@@ -492,6 +503,38 @@ int fh_newton_solve_dev(fh_ctx*, double alpha, double beta, const double* f_dev,
 /* the same with host arrays */
 int fh_newton_solve(fh_ctx*, double alpha, double beta, const double* f, const double* u_ref, double* u, double tolerance, uint64_t max_iterations,
                     int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter, uint64_t* stats, double* norms);
+/* Geometric multigrid for the matrix-free solvers (FH_PRECOND_MULTIGRID of fh_cg_solve_matrix_free, fh_cg_solve_tangent,
+ * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity or Jacobi only).  Every level is an
+ * ordinary context with its own mesh, operator (Laplace, LinearElastic, NeoHookean or StVK), quadrature, data, density and
+ * fh_set_operator_dirichlet_nodes, on the fine context's device; the hierarchy uses each level's matrix-free map and diagonal as they are.
+ * coarse: num_coarse contexts, coarsest first.  Pair k maps coarse[k] to coarse[k + 1] (the fine context for the last pair):
+ * transfer_offsets[k] (fine nodes + 1), transfer_indices[k], transfer_weights[k] are its CSR by fine node, 1 to 8 parents per row
+ * (fh_refine_hex8_uniform writes it).  A row with one parent of weight 1 injects that coarse node: every coarse node needs exactly one,
+ * and a coarse node is Dirichlet exactly when its injected fine node is; else FH_BAD_ARGUMENT.  A coarsest level of more than 4096 dofs
+ * is FH_UNSUPPORTED.  The Dirichlet sets are read at creation.  The contexts must outlive the hierarchy's use; destroying the fine
+ * context while the hierarchy is attached (or attaching another one) orphans it, and fh_mg_destroy then only frees it.
+ * Each solve (and fh_mg_apply_dev) first injects the fine u into every NeoHookean / StVK level (a coarse LinearElastic context with the
+ * same Lame data is the linearized coarse operator), then forms per level what changed since the last solve: the diagonal of
+ * alpha M + beta T(u), lambda_max of D^-1 A (a fixed number of Jacobi-PCG / Lanczos steps from a fixed start vector), and on the
+ * coarsest level the dense matrix of its map, probed through the map and factored on the host (not SPD: FH_CG_INDEFINITE_PRECONDITIONER).
+ * The V-cycle: Chebyshev-Jacobi smoothing of degree m before and after the coarse correction, restriction P^T of the residual (fine
+ * Dirichlet dofs excluded, coarse Dirichlet rows zero), the correction prolongated by P (fine Dirichlet dofs untouched), the dense
+ * inverse on the coarsest level, and the Dirichlet rows of the result = r / scale.  Smoother, with lambda_hi = 1.1 lambda_max,
+ * lambda_lo = lambda_max / range, theta = (hi + lo)/2, delta = (hi - lo)/2, r = b - A x, d = D^-1 r / theta, rho = delta / theta, for
+ * k = 1..m:  x += d;  if k < m:  r -= A d,  rho' = 1 / (2 theta / delta - rho),  d = rho' rho d + (2 rho' / delta) D^-1 r,  rho = rho'.
+ * Pre-smoothing starts from x = 0.  Every call runs on the fine context's stream (the coarse contexts' streams are pointed at it for the
+ * duration of the call); no host synchronisation inside a V-cycle, no floating-point atomics: every solve repeats bit for bit. */
+int fh_mg_create(fh_ctx* fine, uint64_t num_coarse, fh_ctx* const* coarse, const uint64_t* const* transfer_offsets,
+                 const uint64_t* const* transfer_indices, const double* const* transfer_weights, fh_mg** out);
+void fh_mg_destroy(fh_mg*);
+/* attach (or with NULL detach) the hierarchy the fine context's FH_PRECOND_MULTIGRID solves use */
+int fh_set_multigrid(fh_ctx* fine, fh_mg* mg);
+/* degree m (default 3), range (default 15) and Lanczos steps of the eigenvalue estimate (default 10) */
+int fh_mg_set_smoother(fh_mg*, uint32_t degree, double range, uint32_t eig_steps);
+/* level 0 is the coarsest, num_coarse the fine one: lambda_max of its last setup (0 before one, and on the coarsest) and its dofs */
+int fh_mg_level_info(fh_mg*, uint32_t level, double* lambda_max, uint64_t* num_dofs);
+/* one V-cycle z = B r on alpha M + beta T(u) (the plain map: alpha = 0, beta = 1) after the setup of a solve; r, z on the device */
+int fh_mg_apply_dev(fh_mg*, double alpha, double beta, const double* r_dev, double* z_dev);
 /* estimate_L2_error_squared / estimate_H1_seminorm_error_squared (src/error.rs:287-372):
  *   sum_e sum_q w |det J| |u_h(x_q) - u(x_q)|^2      resp.   |grad u_h(x_q) - grad u(x_q)|_F^2
  * with the quadrature table of the context.  The reference solution is arbitrary code in the reference; here the
