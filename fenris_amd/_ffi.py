@@ -20,7 +20,8 @@ SCATTER_ATOMIC, SCATTER_COLORED, SCATTER_GATHER = 0, 1, 2
 FH_CG_MAX_ITERATIONS, FH_CG_INDEFINITE_OPERATOR, FH_CG_INDEFINITE_PRECONDITIONER = 7, 8, 9
 FH_NEWTON_MAX_ITERATIONS, FH_NEWTON_JACOBIAN_ERROR, FH_NEWTON_LINE_SEARCH_FAILED = 10, 11, 12
 NEWTON_NO_LINE_SEARCH, NEWTON_BACKTRACKING = 0, 1
-PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID = 0, 1, 2
+PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, PRECOND_AMG = 0, 1, 2, 3
+AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER = 0, 1, 2
 ASSEMBLE_OVERWRITE = 0x100
 ASSEMBLE_REPRODUCIBLE = 0x200
 
@@ -142,6 +143,15 @@ _SIGS = {
     "fh_mg_set_smoother": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint32]),
     "fh_mg_level_info": (C.c_int, [C.c_void_p, C.c_uint32, f64p, u64p]),
     "fh_mg_apply_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "fh_amg_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "fh_amg_update_values": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_amg_destroy": (None, [C.c_void_p]),
+    "fh_set_amg": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_amg_set_smoother": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint32]),
+    "fh_amg_apply_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fh_amg_level_info": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u64p, u32p, f64p]),
+    "fh_amg_aggregates": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
+    "fh_amg_level_matrix": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, u64p, u64p, f64p, u64p]),
     "fh_estimate_L2_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),
     "fh_estimate_L2_error_squared_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, f64p]),
     "fh_estimate_H1_seminorm_error_squared": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p, f64p]),

@@ -1314,6 +1314,11 @@ class ConjugateGradient:
         if self._csr is None or self._crit is None:
             raise ValueError("operator and stopping criterion are required")
         pre = 1 if isinstance(self._pre, JacobiPreconditioner) else 0
+        from .amg import SmoothedAggregationAMG
+
+        if isinstance(self._pre, SmoothedAggregationAMG):   # FH_PRECOND_AMG on the assembled matrix
+            self._pre._attach()
+            pre = _ffi.PRECOND_AMG
         if isinstance(self._csr, MatrixFreeOperator):   # Jacobi: the matrix-free diagonal (of the tangent for a MatrixFreeTangent)
             return self._csr.cg_solve(b, x, pre, self._crit.tol, self._max_iter)
         return self._asm.engine.cg_solve(self._csr.values, b, x, pre, self._crit.tol, self._max_iter)

@@ -384,6 +384,7 @@ void fh_destroy(fh_ctx* c) {
     if (!c) return;
     DevGuard dev_guard_(c->device);
     if (c->mg) mg_orphan(c->mg);   // an attached multigrid hierarchy no longer refers to this context (engine_mg.hip)
+    if (c->amg) amg_orphan(c->amg);   // ... nor an attached algebraic one (engine_amg.hip)
     if (c->trace.p) {  // FENRIS_HIP_TRACE: average cycles per wave and phase of the pipelined kernel
         unsigned long long h[32] = {0};
         (void)hipDeviceSynchronize();

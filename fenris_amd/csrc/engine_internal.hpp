@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -462,6 +463,7 @@ struct fh_ctx {
     unsigned long long u_gen = 0;      // counts fh_set_u* calls
     unsigned long long dirichlet_gen = 0;   // counts fh_set_operator_dirichlet_nodes calls
     fh_mg* mg = nullptr;               // the multigrid hierarchy of FH_PRECOND_MULTIGRID (fh_set_multigrid; not owned)
+    fh_amg* amg = nullptr;             // the algebraic hierarchy of FH_PRECOND_AMG (fh_set_amg; not owned)
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -562,6 +564,19 @@ int mg_setup(fh_ctx* fine, double alpha, double beta);
 int mg_precondition(fh_ctx* fine, double alpha, double beta, const double* r, double* z);
 int mg_finish(fh_ctx* fine);
 void mg_orphan(fh_mg* mg);   // its fine context is going away: fh_mg_destroy will not touch it
+// pieces of a V-cycle shared by the geometric (engine_mg.hip) and the algebraic (engine_amg.hip) hierarchies.  A level's operator:
+// y = A x, and with dots given the per-workgroup partials of x . y in *dots (*count of them).
+using LevelApply = std::function<int(const double* x, double* y, DevBuf<double>* dots, int* count)>;
+int mg_estimate_lambda(fh_ctx* f, hipStream_t st, int n, int S, const unsigned char* dmask, const double* diag, uint32_t eig_steps,
+                       const LevelApply& apply, const char* who, double* lambda);
+int mg_chebyshev(hipStream_t st, const LevelApply& apply, int n, const double* diag, double lambda, uint32_t degree, double range, double* r,
+                 double* d, double* t, const double* b, double* x, bool zero_start);
+int mg_dense_inverse(fh_ctx* f, const char* who, std::vector<double>& A, int n, std::vector<double>& Ainv, double drop = 0.0);
+// FH_PRECOND_AMG (engine_amg.hip) on c->amg: one V-cycle z = B r; the context is going away
+int amg_precondition(fh_amg* amg, const double* r, double* z);
+void amg_orphan(fh_amg* amg);
+// y = K x on the context's pattern with the values of an assembled matrix (engine_solver.hip; fh_spmv_dev without the checks)
+int csr_spmv(fh_ctx* c, const double* vals, const double* x, double* y);
 // PCG with the V-cycle (engine_solver.hip): x += alpha p, r -= alpha Ap, partials of r . r into slot 1 of 2 per workgroup; partials of
 // z . r into slot 0 of K, and p = z when p is given.  `blocks` workgroups of 256.
 void mg_cg_update(hipStream_t st, int blocks, int n, double alpha, const double* p, const double* Ap, double* x, double* r, double* partial);

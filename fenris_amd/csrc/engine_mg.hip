@@ -95,11 +95,13 @@ double tridiag_max_eig(const std::vector<double>& a, const std::vector<double>& 
     return hi;
 }
 
-// lambda_max of D^-1 A: eig_steps steps of Jacobi-PCG from the fixed start vector, the Lanczos tridiagonal of their coefficients
-int estimate_lambda(fh_mg* mg, MgLevel& L, double alpha, double beta) {
-    fh_ctx* c = L.c;
-    fh_ctx* f = mg->fine;
-    const int n = L.n;
+}  // namespace
+
+// lambda_max of D^-1 A: eig_steps steps of Jacobi-PCG from the fixed start vector, the Lanczos tridiagonal of their coefficients.  apply
+// writes y = A x and the per-workgroup partials of x . y (*count of them) into *dots; diag: the point diagonal; dmask: S-blocks left at 0
+// in the start vector (or null).  Shared with the algebraic hierarchy (engine_amg.hip).
+extern "C++" int mg_estimate_lambda(fh_ctx* f, hipStream_t st, int n, int S, const unsigned char* dmask, const double* diag, uint32_t eig_steps,
+                                    const LevelApply& apply, const char* who, double* lambda) {
     const int gvb = std::max(1, (n + 255) / 256), gv = std::min(1024, gvb);
     DevBuf<double> v, r, z, p, Ap, x, dinv, partial, wg, dots;
     HIP_TRY(f, v.alloc(n));
@@ -111,10 +113,9 @@ int estimate_lambda(fh_mg* mg, MgLevel& L, double alpha, double beta) {
     HIP_TRY(f, dinv.alloc(n));
     HIP_TRY(f, partial.alloc((size_t)3 * 2048));
     HIP_TRY(f, wg.alloc((size_t)3 * gvb));
-    hipStream_t st = c->stream;
-    HIP_TRY(f, hipMemcpyAsync(dinv.p, L.diag.p, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(f, hipMemcpyAsync(dinv.p, diag, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(k_reciprocal, dim3(gvb), dim3(256), 0, st, n, dinv.p);
-    hipLaunchKernelGGL(k_mg_start_vector, dim3(gvb), dim3(256), 0, st, n, L.S, L.dmask(), v.p);
+    hipLaunchKernelGGL(k_mg_start_vector, dim3(gvb), dim3(256), 0, st, n, S, dmask, v.p);
     HIP_TRY(f, hipMemsetAsync(r.p, 0, sizeof(double) * n, st));   // A x for x = 0
     HIP_TRY(f, hipMemsetAsync(x.p, 0, sizeof(double) * n, st));
     hipLaunchKernelGGL(k_cg_init, dim3(gvb), dim3(256), 0, st, n, v.p, dinv.p, r.p, z.p, p.p, wg.p);
@@ -125,10 +126,10 @@ int estimate_lambda(fh_mg* mg, MgLevel& L, double alpha, double beta) {
     if (rc) return rc;
     double zTr = s3[0];
     std::vector<double> alphas, betas;
-    for (uint32_t k = 0; k < mg->eig_steps; ++k) {
+    for (uint32_t k = 0; k < eig_steps; ++k) {
         if (!(zTr > 0.0)) break;
         int count = 0;
-        rc = mf_shift_apply(c, alpha, beta, p.p, Ap.p, &dots, &count);
+        rc = apply(p.p, Ap.p, &dots, &count);
         if (rc) return rc;
         const int ranges = std::min(2048, count);
         hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(ranges), dim3(256), 0, st, dots.p, (long long)count, partial.p);
@@ -137,7 +138,7 @@ int estimate_lambda(fh_mg* mg, MgLevel& L, double alpha, double beta) {
         rc = sum_partials(f, partial.p, ranges, 1, &pAp);
         if (rc) return rc;
         if (!(pAp > 0.0)) {
-            if (alphas.empty()) return f->fail(FH_CG_INDEFINITE_PRECONDITIONER, "multigrid: a level's operator is not positive definite");
+            if (alphas.empty()) return f->fail(FH_CG_INDEFINITE_PRECONDITIONER, std::string(who) + ": a level's operator is not positive definite");
             break;
         }
         const double a = zTr / pAp;
@@ -150,23 +151,85 @@ int estimate_lambda(fh_mg* mg, MgLevel& L, double alpha, double beta) {
         if (rc) return rc;
         const double bt = s2[0] / zTr;
         zTr = s2[0];
-        if (k + 1 == mg->eig_steps || !(zTr > 0.0)) break;
+        if (k + 1 == eig_steps || !(zTr > 0.0)) break;
         betas.push_back(bt);
         hipLaunchKernelGGL(k_cg_direction, dim3(gvb), dim3(256), 0, st, n, bt, z.p, p.p);
         HIP_TRY(f, hipGetLastError());
     }
-    if (alphas.empty()) return f->fail(FH_CG_INDEFINITE_PRECONDITIONER, "multigrid: no eigenvalue estimate for a level");
+    if (alphas.empty()) return f->fail(FH_CG_INDEFINITE_PRECONDITIONER, std::string(who) + ": no eigenvalue estimate for a level");
     const size_t k = alphas.size();
     std::vector<double> ta(k), tb(k > 1 ? k - 1 : 0);
     for (size_t i = 0; i < k; ++i) {
         ta[i] = 1.0 / alphas[i] + (i ? betas[i - 1] / alphas[i - 1] : 0.0);
         if (i + 1 < k) tb[i] = std::sqrt(betas[i]) / alphas[i];
     }
-    L.lambda = tridiag_max_eig(ta, tb);
+    *lambda = tridiag_max_eig(ta, tb);
     HIP_TRY(f, hipStreamSynchronize(st));   // (the temporaries are released on return)
     return FH_OK;
 }
 
+namespace {
+int estimate_lambda(fh_mg* mg, MgLevel& L, double alpha, double beta) {
+    fh_ctx* c = L.c;
+    return mg_estimate_lambda(mg->fine, c->stream, L.n, L.S, L.dmask(), L.diag.p, mg->eig_steps,
+                              [&](const double* x, double* y, DevBuf<double>* dots, int* count) { return mf_shift_apply(c, alpha, beta, x, y, dots, count); },
+                              "multigrid", &L.lambda);
+}
+
+}  // namespace
+
+// The inverse of the dense symmetric n x n matrix A (row-major; A is overwritten): Cholesky A = L L^T on the host, W = L^-1, Ainv = W^T W,
+// exactly symmetric.  Not SPD: FH_CG_INDEFINITE_PRECONDITIONER.  drop > 0: a pivot at most drop times its diagonal leaves that dof out
+// (its rows of the inverse are zero), for semidefinite matrices.  Shared with the algebraic hierarchy (engine_amg.hip).
+extern "C++" int mg_dense_inverse(fh_ctx* f, const char* who, std::vector<double>& A, int n, std::vector<double>& Ainv, double drop) {
+    std::vector<char> dropped(n, 0);
+    std::vector<double> d0;
+    if (drop > 0.0)
+        for (int j = 0; j < n; ++j) d0.push_back(A[(size_t)j * n + j]);
+    // Cholesky A = L L^T, lower triangle in place
+    for (int j = 0; j < n; ++j) {
+        double* rj = &A[(size_t)j * n];
+        double s = rj[j];
+        for (int k = 0; k < j; ++k) s -= rj[k] * rj[k];
+        if (drop > 0.0 && std::isfinite(s) && s <= drop * d0[j]) {   // (semidefinite: the dof is left out)
+            dropped[j] = 1;
+            for (int i = j; i < n; ++i) A[(size_t)i * n + j] = 0.0;
+            continue;
+        }
+        if (!(s > 0.0) || !std::isfinite(s))
+            return f->fail(FH_CG_INDEFINITE_PRECONDITIONER, std::string(who) + ": the coarsest level's matrix is not positive definite");
+        const double djj = std::sqrt(s);
+        rj[j] = djj;
+        for (int i = j + 1; i < n; ++i) {
+            double* ri = &A[(size_t)i * n];
+            double t = ri[j];
+            for (int k = 0; k < j; ++k) t -= ri[k] * rj[k];
+            ri[j] = t / djj;
+        }
+    }
+    // W = L^-1 (lower), row-major; Ainv = W^T W, exactly symmetric
+    std::vector<double> W((size_t)n * n, 0.0);
+    for (int col = 0; col < n; ++col) {
+        if (dropped[col]) continue;
+        W[(size_t)col * n + col] = 1.0 / A[(size_t)col * n + col];
+        for (int i = col + 1; i < n; ++i) {
+            if (dropped[i]) continue;
+            double t = 0.0;
+            for (int k = col; k < i; ++k) t += A[(size_t)i * n + k] * W[(size_t)k * n + col];
+            W[(size_t)i * n + col] = -t / A[(size_t)i * n + i];
+        }
+    }
+    Ainv.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = i; j < n; ++j) {
+            double t = 0.0;
+            for (int k = j; k < n; ++k) t += W[(size_t)k * n + i] * W[(size_t)k * n + j];
+            Ainv[(size_t)i * n + j] = Ainv[(size_t)j * n + i] = t;
+        }
+    return FH_OK;
+}
+
+namespace {
 // the coarsest level's dense matrix through its map, probed with a distance-2 colouring of its nodes; Cholesky on the host; the inverse
 // W^T W (W = L^-1) uploaded.  Not SPD: FH_CG_INDEFINITE_PRECONDITIONER.
 int factor_coarsest(fh_mg* mg, MgLevel& L, double alpha, double beta) {
@@ -223,73 +286,52 @@ int factor_coarsest(fh_mg* mg, MgLevel& L, double alpha, double beta) {
             const double m = 0.5 * (A[(size_t)i * n + j] + A[(size_t)j * n + i]);
             A[(size_t)i * n + j] = A[(size_t)j * n + i] = m;
         }
-    // Cholesky A = L L^T, lower triangle in place
-    for (int j = 0; j < n; ++j) {
-        double* rj = &A[(size_t)j * n];
-        double s = rj[j];
-        for (int k = 0; k < j; ++k) s -= rj[k] * rj[k];
-        if (!(s > 0.0) || !std::isfinite(s))
-            return f->fail(FH_CG_INDEFINITE_PRECONDITIONER, "multigrid: the coarsest level's matrix is not positive definite");
-        const double djj = std::sqrt(s);
-        rj[j] = djj;
-        for (int i = j + 1; i < n; ++i) {
-            double* ri = &A[(size_t)i * n];
-            double t = ri[j];
-            for (int k = 0; k < j; ++k) t -= ri[k] * rj[k];
-            ri[j] = t / djj;
-        }
-    }
-    // W = L^-1 (lower), row-major; Ainv = W^T W, exactly symmetric
-    std::vector<double> W((size_t)n * n, 0.0);
-    for (int col = 0; col < n; ++col) {
-        W[(size_t)col * n + col] = 1.0 / A[(size_t)col * n + col];
-        for (int i = col + 1; i < n; ++i) {
-            double t = 0.0;
-            for (int k = col; k < i; ++k) t += A[(size_t)i * n + k] * W[(size_t)k * n + col];
-            W[(size_t)i * n + col] = -t / A[(size_t)i * n + i];
-        }
-    }
-    std::vector<double> Ainv((size_t)n * n);
-    for (int i = 0; i < n; ++i)
-        for (int j = i; j < n; ++j) {
-            double t = 0.0;
-            for (int k = j; k < n; ++k) t += W[(size_t)k * n + i] * W[(size_t)k * n + j];
-            Ainv[(size_t)i * n + j] = Ainv[(size_t)j * n + i] = t;
-        }
+    std::vector<double> Ainv;
+    const int rc = mg_dense_inverse(f, "multigrid", A, n, Ainv);
+    if (rc) return rc;
     if (mg->ainv.n < (size_t)n * n) HIP_TRY(f, mg->ainv.alloc((size_t)n * n));
     HIP_TRY(f, hipMemcpyAsync(mg->ainv.p, Ainv.data(), sizeof(double) * Ainv.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(f, hipStreamSynchronize(c->stream));
     return FH_OK;
 }
 
-int chebyshev(fh_mg* mg, MgLevel& L, double alpha, double beta, const double* b, double* x, bool zero_start) {
-    hipStream_t st = mg->fine->stream;
-    const int n = L.n, g = grid_for(n, 256);
-    const double hi = 1.1 * L.lambda, lo = L.lambda / mg->range;
+}  // namespace
+
+// Chebyshev-Jacobi smoothing of degree `degree` on x (the recurrence of fenris_hip.h) with apply = the level's operator (dots null); r, d, t:
+// the level's work vectors.  Shared with the algebraic hierarchy (engine_amg.hip).
+extern "C++" int mg_chebyshev(hipStream_t st, const LevelApply& apply, int n, const double* diag, double lambda, uint32_t degree, double range,
+                              double* r, double* d, double* t, const double* b, double* x, bool zero_start) {
+    const int g = grid_for(n, 256);
+    const double hi = 1.1 * lambda, lo = lambda / range;
     const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo);
     int rc;
     if (zero_start) {
-        hipLaunchKernelGGL(k_mg_cheb_start, dim3(g), dim3(256), 0, st, n, b, (const double*)nullptr, L.diag.p, 1.0 / theta, x, L.r.p, L.d.p);
+        hipLaunchKernelGGL(k_mg_cheb_start, dim3(g), dim3(256), 0, st, n, b, (const double*)nullptr, diag, 1.0 / theta, x, r, d);
     } else {
-        rc = apply_level(L, alpha, beta, x, L.t.p);
+        rc = apply(x, t, nullptr, nullptr);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_mg_cheb_start, dim3(g), dim3(256), 0, st, n, b, (const double*)L.t.p, L.diag.p, 1.0 / theta, (double*)nullptr, L.r.p,
-                           L.d.p);
+        hipLaunchKernelGGL(k_mg_cheb_start, dim3(g), dim3(256), 0, st, n, b, (const double*)t, diag, 1.0 / theta, (double*)nullptr, r, d);
     }
     double rho = delta / theta;
-    for (uint32_t k = 1; k <= mg->degree; ++k) {
-        if (k < mg->degree) {
-            rc = apply_level(L, alpha, beta, L.d.p, L.t.p);
+    for (uint32_t k = 1; k <= degree; ++k) {
+        if (k < degree) {
+            rc = apply(d, t, nullptr, nullptr);
             if (rc) return rc;
             const double rho1 = 1.0 / (2.0 * theta / delta - rho);
-            hipLaunchKernelGGL(k_mg_cheb_step, dim3(g), dim3(256), 0, st, n, (const double*)L.t.p, (const double*)L.diag.p, rho1 * rho,
-                               2.0 * rho1 / delta, x, L.r.p, L.d.p);
+            hipLaunchKernelGGL(k_mg_cheb_step, dim3(g), dim3(256), 0, st, n, (const double*)t, diag, rho1 * rho, 2.0 * rho1 / delta, x, r, d);
             rho = rho1;
         } else {
-            hipLaunchKernelGGL(k_mg_add, dim3(g), dim3(256), 0, st, n, (const double*)L.d.p, x);
+            hipLaunchKernelGGL(k_mg_add, dim3(g), dim3(256), 0, st, n, (const double*)d, x);
         }
     }
     return FH_OK;
+}
+
+namespace {
+int chebyshev(fh_mg* mg, MgLevel& L, double alpha, double beta, const double* b, double* x, bool zero_start) {
+    return mg_chebyshev(mg->fine->stream,
+                        [&](const double* in, double* out, DevBuf<double>*, int*) { return apply_level(L, alpha, beta, in, out); }, L.n,
+                        L.diag.p, L.lambda, mg->degree, mg->range, L.r.p, L.d.p, L.t.p, b, x, zero_start);
 }
 
 int vcycle(fh_mg* mg, int l, double alpha, double beta, const double* b, double* x) {

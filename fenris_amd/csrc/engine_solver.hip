@@ -107,6 +107,7 @@ static int spmv_launch(fh_ctx* c, const double* vals, const double* x, double* y
     }
     return FH_OK;
 }
+extern "C++" int csr_spmv(fh_ctx* c, const double* vals, const double* x, double* y) { return spmv_launch(c, vals, x, y, nullptr, 0, nullptr); }
 static int matrix_ready(fh_ctx* c, const char* who) {
     if (!c->has_pattern) return c->fail(FH_INVALID_STATE, std::string(who) + ": call fh_pattern first");
     if (c->S() < 1 || c->S() > 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": solution dim must be 1..3");
@@ -216,8 +217,10 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
     int rc = matrix_ready(c, "fh_cg_solve");
     if (rc) return rc;
     if (!values_dev || !b_dev || !x_dev) return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve: null argument");
-    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI)
+    if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI && preconditioner != FH_PRECOND_AMG)
         return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve: unknown preconditioner");
+    const bool amg = preconditioner == FH_PRECOND_AMG;
+    if (amg && !c->amg) return c->fail(FH_INVALID_STATE, "fh_cg_solve: FH_PRECOND_AMG needs a hierarchy (fh_set_amg)");
     const int S = c->S();
     const int n = S * (int)c->N;
     if (n == 0) return FH_OK;
@@ -241,7 +244,9 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
                       if (!ranges) return spmv_launch(c, values_dev, in, out, nullptr, 0, nullptr);
                       *ranges = gs;
                       return spmv_launch(c, values_dev, in, out, partial.p, gs, &wg_partial);
-                  });
+                  },
+                  amg ? std::function<int(const double*, double*)>([&](const double* r, double* z) { return amg_precondition(c->amg, r, z); })
+                      : std::function<int(const double*, double*)>());
 }
 
 // The same solver around the matrix-free map (fh_apply_operator_dev, fh_apply_tangent_dev; max_op as mf_ready), or around the shifted map

@@ -108,6 +108,7 @@ enum { FH_ASSEMBLE_REPRODUCIBLE = 0x200 };
 
 typedef struct fh_ctx fh_ctx;
 typedef struct fh_mg fh_mg;
+typedef struct fh_amg fh_amg;
 
 /* ---- context ------------------------------------------------------------------------------- */
 fh_ctx* fh_create(int device_id);               /* NULL if the device cannot be initialised */
@@ -504,7 +505,7 @@ int fh_newton_solve_dev(fh_ctx*, double alpha, double beta, const double* f_dev,
 int fh_newton_solve(fh_ctx*, double alpha, double beta, const double* f, const double* u_ref, double* u, double tolerance, uint64_t max_iterations,
                     int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter, uint64_t* stats, double* norms);
 /* Geometric multigrid for the matrix-free solvers (FH_PRECOND_MULTIGRID of fh_cg_solve_matrix_free, fh_cg_solve_tangent,
- * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity or Jacobi only).  Every level is an
+ * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity, Jacobi or FH_PRECOND_AMG).  Every level is an
  * ordinary context with its own mesh, operator (Laplace, LinearElastic, NeoHookean or StVK), quadrature, data, density and
  * fh_set_operator_dirichlet_nodes, on the fine context's device; the hierarchy uses each level's matrix-free map and diagonal as they are.
  * coarse: num_coarse contexts, coarsest first.  Pair k maps coarse[k] to coarse[k + 1] (the fine context for the last pair):
@@ -535,6 +536,57 @@ int fh_mg_set_smoother(fh_mg*, uint32_t degree, double range, uint32_t eig_steps
 int fh_mg_level_info(fh_mg*, uint32_t level, double* lambda_max, uint64_t* num_dofs);
 /* one V-cycle z = B r on alpha M + beta T(u) (the plain map: alpha = 0, beta = 1) after the setup of a solve; r, z on the device */
 int fh_mg_apply_dev(fh_mg*, double alpha, double beta, const double* r_dev, double* z_dev);
+/* Smoothed-aggregation algebraic multigrid for PCG on the assembled matrix (FH_PRECOND_AMG of fh_cg_solve and fh_cg_solve_dev only; the
+ * matrix-free solves and fh_newton_solve reject it).  AMG-PCG assumes an SPD matrix (no FH_TENSOR operators).  The hierarchy is built from
+ * the context's pattern and values_dev, its node-block CSR values (after fh_apply_dirichlet_csr_dev or not), on the context's stream:
+ *   strength: i != j strong when ||A_ij||_F >= theta sqrt(||A_ii||_F ||A_jj||_F) and A_ij != 0 (theta = 0: the pattern's node graph); a node
+ *     without a nonzero off-diagonal block is isolated: no aggregate, a zero row of P, and z_i = A_ii^-1 r_i in the V-cycle (Cholesky of
+ *     the block; a pivot at most 1e-14 of its diagonal leaves that dof out);
+ *   aggregates: roots form a distance-2 maximal independent set of the strength graph, built in synchronous rounds with the priority
+ *     ((h(i) & 0x7fffffff) << 32) | i, with the 32-bit hash h(x): x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15,
+ *     x *= 0x846ca68b, x ^= x >> 16 (unsigned arithmetic); every node next to a root joins the adjacent root of highest
+ *     priority, then each node still left joins the aggregate of its aggregated strong neighbour of highest priority.  The aggregates
+ *     depend on the matrix alone;
+ *   near-nullspace B (s N x nb, row-major): FH_AMG_CONSTANT (nb = s unit translations), FH_AMG_RIGID_BODY (s = d: translations and rotations
+ *     about the centroid of the context's vertices, nb = 3 in 2D, 6 in 3D) or FH_AMG_USER (B, nb columns, 1 <= nb <= 6);
+ *   T: per aggregate, modified Gram-Schmidt of its rows of B, columns in order; a column whose norm after orthogonalisation is at most
+ *     1e-10 of its norm before is zero in Q and its row of R is zero.  Q's rows form T, R the aggregate's rows of the coarse B;
+ *   P = (I - omega D^-1 A) T, omega = 4 / (3 lambda), D the point diagonal, lambda the Lanczos estimate of lambda_max(D^-1 A) (as fh_mg_*);
+ *   A_c = P^T (A P) with P^T stored explicitly; block (J, I) of A_c is the transpose of block (I, J) bit for bit.  Coarse dofs with a zero
+ *     diagonal have D^-1 = 0 and no correction.
+ * Levels are coarsened until one has at most 4096 dofs or max_levels levels exist (0: 10); a coarsest level above 4096 dofs, or a step that
+ * keeps more than 90 % of the dofs, is FH_UNSUPPORTED.  The coarsest level is inverted densely (Cholesky on the host; a pivot at most 1e-12 of its diagonal leaves that dof out, so a
+ * free-floating body's semidefinite coarsest level is accepted).  The V-cycle is the
+ * one of fh_mg_* (Chebyshev-Jacobi of degree m before and after, restriction by P^T, prolongation by P) with no floating-point atomics and
+ * no host synchronisation; setup sums every entry in a fixed order, so a create, a refresh and a solve repeat bit for bit.
+ * Errors: no pattern: FH_INVALID_STATE; nb of 0 or above 6, a null B for FH_AMG_USER, FH_AMG_RIGID_BODY with s != d, theta < 0:
+ * FH_BAD_ARGUMENT; a row of A P or P^T (A P) with more than 512 blocks: FH_UNSUPPORTED.  values_dev must stay allocated while the hierarchy
+ * is used (level 0 reads it).  The values passed to an FH_PRECOND_AMG solve must be those the hierarchy was built from or last refreshed with.
+ * The hierarchy refers to the context's pattern: destroying the context while it is attached (or attaching another one) orphans it,
+ * and every later call on it but fh_amg_destroy returns FH_BAD_ARGUMENT; fh_amg_destroy then only frees it. */
+enum { FH_PRECOND_AMG = 3 };
+enum { FH_AMG_CONSTANT = 0, FH_AMG_RIGID_BODY = 1, FH_AMG_USER = 2 };
+int fh_amg_create(fh_ctx*, const double* values_dev, int nullspace, const double* B, uint32_t nb, double theta, uint32_t max_levels,
+                  fh_amg** out);
+/* numeric refresh for new values on the same pattern (K(u) of a Newton or time-stepping loop): the aggregates, T and every pattern are
+ * kept; lambda, the values of P and A_c and the coarse factor are formed again, the same bits as a create with the same aggregates */
+int fh_amg_update_values(fh_amg*, const double* values_dev);
+void fh_amg_destroy(fh_amg*);
+/* attach (or with NULL detach) the hierarchy the context's FH_PRECOND_AMG solves use; FH_PRECOND_AMG without one: FH_INVALID_STATE */
+int fh_set_amg(fh_ctx*, fh_amg*);
+/* degree m (default 3), range (default 15) and Lanczos steps of the eigenvalue estimate (default 10); forms lambda, P and A_c again */
+int fh_amg_set_smoother(fh_amg*, uint32_t degree, double range, uint32_t eig_steps);
+/* one V-cycle z = B r; r, z on the device */
+int fh_amg_apply_dev(fh_amg*, const double* r_dev, double* z_dev);
+/* level 0 is the fine one: its dofs, nonzero blocks, block size and lambda_max (0 on the coarsest); level >= number of levels:
+ * FH_BAD_ARGUMENT */
+int fh_amg_level_info(fh_amg*, uint32_t level, uint64_t* num_dofs, uint64_t* nnz_blocks, uint32_t* block_size, double* lambda_max);
+/* the aggregate of every node of a level that has a coarser one (UINT64_MAX: isolated) */
+int fh_amg_aggregates(fh_amg*, uint32_t level, uint64_t* agg_of_node);
+/* A (which = 0), P (1), the tentative prolongator T (2) or the level's near-nullspace B (3; rows: the level's dofs, nb columns) of a level
+ * as scalar CSR, two-phase like fh_pattern: null arrays give *nnz only; row_offsets has rows + 1 entries, cols and vals *nnz.  P and T
+ * exist on every level but the coarsest. */
+int fh_amg_level_matrix(fh_amg*, uint32_t level, int which, uint64_t* row_offsets, uint64_t* cols, double* vals, uint64_t* nnz);
 /* estimate_L2_error_squared / estimate_H1_seminorm_error_squared (src/error.rs:287-372):
  *   sum_e sum_q w |det J| |u_h(x_q) - u(x_q)|^2      resp.   |grad u_h(x_q) - grad u(x_q)|_F^2
  * with the quadrature table of the context.  The reference solution is arbitrary code in the reference; here the
