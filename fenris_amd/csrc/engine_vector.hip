@@ -213,10 +213,14 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
             else hipLaunchKernelGGL(k_vector_from_elements<3>, dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->n2e_off.p, c->n2e.p, c->fe_scratch.p, out_dev);
             HIP_TRY(c, hipGetLastError());
         }
-        if (rs == FH_OK) return read_status(c, failed);
+        if (rs == FH_OK) {
+            c->last_kernel = two_pass ? "k_assemble_vector_stream + k_vector_from_elements" : "k_assemble_vector_stream";
+            return read_status(c, failed);
+        }
         if (rs > 0) return rs;
         a.ke_out = nullptr;
     }
+    c->last_kernel = "k_assemble_vector";
     a.epb = choose_epb(c, WHAT_VECTOR);
     a.ub = a.epb;
     const size_t lds = layout_bytes_dyn(c->elem_kind, c->op, WHAT_VECTOR, c->nq, a.ub, 0, 0, false);
@@ -501,6 +505,7 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
     DevBuf<double> partial;
     HIP_TRY(c, partial.alloc((size_t)grid));
     a.scalar_out = partial.p;
+    c->last_kernel = "k_assemble_scalar";
 #define CALL(EKC, OPC) rc = launch_scalar<EKC, OPC>(c, a, lds, grid)
     FH_FOR_ELEM_OP(c->elem_kind, c->op, CALL)
 #undef CALL

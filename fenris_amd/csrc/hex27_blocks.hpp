@@ -11,6 +11,10 @@
 //     operand of the trace products is  h_d(I) = sum_c (c_m B_cd) a_c(I)  -- nine vector FMAs per fetched row block -- and its column operand
 //     is A again.  G is never stored: a_n = M^T r_n with M = J^-1 F^-1 and r_n the REFERENCE gradient, in one phase.  LDS per workgroup
 //     52.9 -> 29.8 KB, operand fetches per k-step and wavefront 24 -> 12.
+//     Rounding: B is symmetric positive definite, so a_I^T B a_J carries a few eps of |a_I| |B| |a_J| <= cond(F)^2 |g_I| |g_J|; the entries
+//     that set max|K| are the lambda and ln J terms on a = F^-T g, which grow as |F^-1|^2 |g|^2 themselves, so against max|K| the trace
+//     term costs at most ~||F||^2 eps.  Measured against a long-double K (tests/test_large_deformation.py, tests/test_hex27_mfma.py):
+//     4e-15 max|K| at cond F ~ 100 and 1e-15 at cond F ~ 10 (the generic first pass: 1e-14 and 2e-15); the bar 1e-12 holds with a wide margin.
 //   * the gradient of u without G: grad u = (sum_n u_n r_n^T) J^-1 -- the sum over the nodes needs no geometry and is formed next to J.
 //   * the 3 x 3 algebra of a point (J, its inverse, F, its inverse, M, B, the coefficients) runs on nine lanes of ONE wavefront (seven points per
 //     wavefront); the lanes exchange their entries through LDS with no workgroup barrier in between (a wavefront's LDS operations execute

@@ -212,17 +212,35 @@ def test_roles_rotate_and_triangles_are_symmetric(oracle, op, per_point):
 
 
 def test_large_deformation_keeps_the_tolerance(engine, oracle):
-    """the trace term is formed as a_I^T (F F^T) a_J with a = F^-T g instead of g_I . g_J (hex27_blocks.hpp): its rounding error grows with
-    cond(F)^2 -- a stretch of 3 x 1 x 1/3 with shear (cond F ~ 10) stays at 1e-11 of the largest entry"""
+    """a stretch of 3 x 1 x 1/3 with shear (cond F ~ 10): the matrix-core pass holds the bar of every other test, 1e-12 of the largest entry,
+    against the oracle and against the long-double reference (tests/hp_reference.py) -- and so does every element matrix on its own"""
+    _large_deformation(engine, oracle, np.array([[3.0, 0.4, 0.0], [0.0, 1.0, 0.3], [0.2, 0.0, 1.0 / 3.0]]))
+
+
+def test_large_deformation_cond_100_keeps_the_tolerance(engine, oracle):
+    """a stretch of 10 x 1 x 0.1 with shear (cond F ~ 100), the bar unchanged"""
+    _large_deformation(engine, oracle, np.array([[10.0, 1.5, 0.0], [0.0, 1.0, 0.2], [0.3, 0.0, 0.1]]))
+
+
+def _large_deformation(engine, oracle, F):
+    import hp_reference as hp
+
     mesh = _mesh(13, cells=(2, 2, 2))
-    A = np.array([[2.0, 0.4, 0.0], [0.0, 0.0, 0.3], [0.2, 0.0, -2.0 / 3.0]])   # F = I + A
-    u = (mesh.vertices @ A.T).reshape(-1)
+    u = (mesh.vertices @ (F - np.eye(3)).T).reshape(-1)
     asm, ref = _build(engine, oracle, mesh, "NEO_HOOKEAN", u)
     k = fa.CsrAssembler(fa.SCATTER_GATHER).assemble(asm)
     assert engine.last_kernel_name() in HEX27_TWO_PASS
     vals = oracle.assemble(ref)[4]
     assert not np.isnan(vals).any()
-    assert np.abs(k.values - vals).max() <= 1e-11 * np.abs(vals).max()
+    assert np.abs(k.values - vals).max() <= 1e-12 * np.abs(vals).max()
+    w, p = quadrature.tensor.hexahedron_gauss(3)
+    hr = hp.Reference("HEX27", "NEO_HOOKEAN", mesh.vertices, mesh.connectivity, np.asarray(w), np.asarray(p), u, LAME.mu, LAME.lambda_)
+    assert hr.det_F_min > 0.0
+    kh = hr.csr_values(k.row_offsets, k.col_indices)
+    assert np.abs(k.values - kh).max() <= 1e-12 * np.abs(kh).max()
+    ke = engine.element_matrices(0, mesh.num_elements())
+    for e in range(mesh.num_elements()):
+        assert np.abs(ke[e] - hr.ke[e]).max() <= 1e-12 * np.abs(hr.ke[e]).max(), e
 
 
 @pytest.mark.parametrize("k,layers", [(5, 2), (12, 2), (18, 2)])

@@ -165,3 +165,37 @@ def test_oracle_agrees_with_an_independent_numpy_restatement(oracle, kind, op):
     st, eo = res[0], res[-1]
     assert st == 0
     assert abs(eo - energy) <= 1e-13 * max(abs(energy), 1e-300), (kind, op, "energy")
+
+
+def _dense(ro, ci, vals):
+    A = np.zeros((len(ro) - 1, len(ro) - 1))
+    for r in range(len(ro) - 1):
+        A[r, np.asarray(ci[ro[r]: ro[r + 1]]).astype(np.int64)] = vals[ro[r]: ro[r + 1]]
+    return A
+
+
+def test_the_extended_precision_reference_is_this_restatement(oracle):
+    """tests/hp_reference.py restates these formulas once more, vectorised over the elements and in any floating-point type (the long-double
+    reference of test_large_deformation.py): run in float64 it gives this restatement's K, f and energy, and in long double the oracle's"""
+    import hp_reference as hp
+
+    rng = np.random.default_rng(5)
+    for kind in ("HEX8", "TET4", "QUAD4", "HEX27"):
+        verts, conn = small_mesh(kind, oracle, rng)
+        d = verts.shape[1]
+        w, pts = rule(kind, oracle)
+        w, pts = np.asarray(w), np.asarray(pts).reshape(len(w), d)
+        for op in ("NEO_HOOKEAN", "STVK"):
+            u = 0.05 * rng.standard_normal(d * len(verts))
+            K, f, energy = restate(kind, op, verts, conn, w, pts, u)
+            ref = hp.Reference(kind, op, verts, conn, w, pts, u, MU, LAM, dt=np.float64)
+            ro, ci = ref.pattern()
+            assert np.abs(_dense(ro, ci, ref.csr_values(ro, ci)) - K).max() <= 1e-13 * np.abs(K).max()
+            assert np.abs(ref.residual() - f).max() <= 1e-13 * np.abs(f).max()
+            assert abs(ref.energy() - energy) <= 1e-13 * abs(energy)
+            ld = hp.Reference(kind, op, verts, conn, w, pts, u, MU, LAM)
+            asm = oracle.ElementAssembler(getattr(oracle, kind), getattr(oracle, op), verts, conn.astype(np.uint64), w, pts, params=(MU, LAM), u=u)
+            st, _, ro, ci, vals = oracle.assemble(asm)
+            assert st == 0
+            k = ld.csr_values(ro, ci)
+            assert np.abs(vals - k).max() <= 1e-13 * np.abs(k).max()
