@@ -22,9 +22,14 @@ Configurations (BASELINE.json `configs`):
 --dump-outputs DIR writes what the last timed step computed (the CSR values: every entry, or a fixed seeded sample of 2^21 on the large
 meshes) to DIR/*.npy; the inputs of a configuration are the same from run to run, so two builds can be compared entry for entry.
 
-Prints ONE JSON line on rank 0.  The default run (--config ns on one GPU) appends `secondary_vectors` (residual vector and energy of the
-headline mesh) and `secondary`: every other configuration
-(c2, c3, c4, c5 at N = 1, ns-perturbed) timed in the same process after the headline -- {ms, frac of its roofline, kernel}.
+Prints ONE JSON line on rank 0.  A plain run does what the headline figure needs and nothing else: set-up (pattern, first assembly, device
+settle, placement probe), warm-up, the timed steps, --dump-outputs, the line (its roofline fraction comes from the events of the timed steps).
+
+--full adds, after the timed steps and the dump, everything that takes runs of its own (N = 1): the HBM traffic of the dominant kernel (two
+rocprofv3 PMC child passes), the plain fill that gives `measured_write_GBps`, the CPU baseline, and -- on the default --config ns --
+`secondary_vectors` (residual vector and energy of the headline mesh) and `secondary`: every other configuration (c2, c3, c4, c5 at N = 1,
+ns-perturbed) timed in the same process after the headline -- {ms, frac of its roofline, kernel}.  --no-traffic, --no-cpu-baseline and
+--no-secondary leave single parts of --full out.  Without --full the line carries `traffic`, `cpu_baseline` as null and no `secondary*`.
 """
 import argparse
 import json
@@ -489,9 +494,13 @@ def main():
                          "calls behind the C ABI (fh_group_*)")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="N > 1 without a launcher: seconds the torch.distributed.run child may take before its process group is killed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 PMC child passes (roofline.traffic = null)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other configurations timed after the headline (N = 1, --config ns)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also measure what takes runs of its own -- HBM traffic (rocprofv3 PMC child passes), "
+                         "measured_write_GBps, the CPU baseline and, on --config ns, the residual / energy and every other configuration")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (cpu_baseline = null)")
+    ap.add_argument("--no-traffic", action="store_true", help="--full without the two rocprofv3 PMC child passes (roofline.traffic = null)")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full without the other configurations timed after the headline (N = 1, --config ns)")
     ap.add_argument("--placement-tries", type=int, default=6,
                     help="N = 1: allocations of the values array (and of the library's record buffer) tried before the timed region, the "
                          "fastest kept; 0 = take the first (see probe_placement)")
@@ -528,7 +537,8 @@ def main():
     # ---- HBM traffic of the dominant kernel: two PMC passes of this command as child processes of a helper that is started HERE,
     # before this process makes any torch.cuda call, and told to run after the timed region (N = 1, rank 0 only)
     traffic, traffic_detail, helper = None, None, None
-    if world == 1 and not args.no_traffic and os.environ.get("FENRIS_BENCH_CHILD") != "1":
+    full = args.full and os.environ.get("FENRIS_BENCH_CHILD") != "1"   # (the children of the PMC passes are plain runs)
+    if full and world == 1 and not args.no_traffic:
         child = ["--config", cfg, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-traffic", "--no-secondary", "--no-module-warmup",
                  "--scatter", args.scatter]
         if args.cells:
@@ -852,22 +862,23 @@ def main():
             out["roofline"] = hbm
         # what the device sustains on the dominant traffic of this kernel (writing the values once): a plain fill of
         # the same array, timed the same way -- the practical ceiling next to the nominal 8 TB/s
-        try:
-            a0, b0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            scratch = torch.empty_like(values)
-            scratch.fill_(1.0)
-            torch.cuda.synchronize()
-            a0.record()
-            for _ in range(5):
+        if full:
+            try:
+                a0, b0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                scratch = torch.empty_like(values)
                 scratch.fill_(1.0)
-            b0.record()
-            torch.cuda.synchronize()
-            hbm["measured_write_GBps"] = 5 * nnz * 8 / (a0.elapsed_time(b0) * 1e-3) / 1e9
-            del scratch
-        except RuntimeError:
-            pass
+                torch.cuda.synchronize()
+                a0.record()
+                for _ in range(5):
+                    scratch.fill_(1.0)
+                b0.record()
+                torch.cuda.synchronize()
+                hbm["measured_write_GBps"] = 5 * nnz * 8 / (a0.elapsed_time(b0) * 1e-3) / 1e9
+                del scratch
+            except RuntimeError:
+                pass
         # ---- the other configurations, same process, after the headline (driver-verifiable figures for the rows of DESIGN 3.4)
-        if world == 1 and cfg == "ns" and not args.cells and not args.no_secondary and os.environ.get("FENRIS_BENCH_CHILD") != "1":
+        if full and world == 1 and cfg == "ns" and not args.cells and not args.no_secondary:
             # residual vector and energy of the same mesh and operator ("Secondary: ... residual assembly"), the same context
             try:
                 eng.set_u(1e-3 * np.sin(np.arange(s * mesh.num_nodes())))
@@ -923,7 +934,7 @@ def main():
             hbm["traffic_source"] = ("two rocprofv3 --pmc child passes of this command, run after the timed region (FETCH_SIZE x 2 + "
                                      "WRITE_SIZE, KiB -> bytes, averaged over the dispatches of the dominant kernel)")
             hbm["traffic_detail"] = traffic_detail
-        if not args.no_cpu_baseline and world == 1:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(c["cpu_kind"])
         else:
             out["cpu_baseline"] = None

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Regenerate the current-state table of DESIGN.md section 3.4 from the committed measurements -- and from nothing else:
 
-    profiles/r<NN>_bench_default_n1.json           the default `python bench.py` line (headline + `secondary` + `secondary_vectors` + cpu_baseline)
+    profiles/r<NN>_bench_default_n1.json           the `python bench.py --full` line (headline + `secondary` + `secondary_vectors` + cpu_baseline)
     profiles/r<NN>_other_kernels.jsonl             scripts/bench_other_kernels.py (residual / energy / source / SpMV / PCG / pattern)
     profiles/r<NN>_<config>_rocprofv3_summary.txt  scripts/gpu_profile_config.sh <config> (FETCH_SIZE / WRITE_SIZE per kernel: measured bytes)
 
@@ -55,7 +55,7 @@ def main():
     rnd = args.round
     d = json.load(open(os.path.join(ROOT, "profiles", f"r{rnd}_bench_default_n1.json")))
     rows = []
-    head = ("| configuration (`python bench.py`, one MI355X) | kernel(s) | ms per assembly | elements/s | roofline: achieved of peak | fraction | "
+    head = ("| configuration (`python bench.py --full`, one MI355X) | kernel(s) | ms per assembly | elements/s | roofline: achieved of peak | fraction | "
             "measured HBM bytes / algorithmic | first assembly (tables) |")
     rows.append(head)
     rows.append("|---|---|---|---|---|---|---|---|")

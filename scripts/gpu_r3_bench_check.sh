@@ -2,7 +2,7 @@
 # round 3: the default bench line (traffic children, secondary configurations, CPU baseline), the N = 2 self-launch on one device
 # (validation mode) and its refusal without it
 OUT=gpurun_out/r3h; mkdir -p $OUT
-( time python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default rc=$?"; tail -3 $OUT/bench_default.err
+( time python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default rc=$?"; tail -3 $OUT/bench_default.err
 python - <<PY
 import json
 d=json.load(open("$OUT/bench_default.json"))

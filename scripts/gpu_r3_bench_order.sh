@@ -2,7 +2,7 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r3y
 mkdir -p $OUT
 for i in 1 2 3; do
-  python bench.py --no-cpu-baseline > $OUT/bench_$i.json 2> $OUT/bench_$i.err
+  python bench.py --full --no-cpu-baseline > $OUT/bench_$i.json 2> $OUT/bench_$i.err
 done
 python - <<'PY'
 import json,glob,os

@@ -1,8 +1,8 @@
 # what the driver sees: the default line as the FIRST process on a fresh box, then a second one (gpurun_out/r3q)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r3q
 mkdir -p $OUT
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_first.json 2> $OUT/bench_first.err
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_second.json 2> $OUT/bench_second.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_first.json 2> $OUT/bench_first.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_second.json 2> $OUT/bench_second.err
 python - <<'PY'
 import json,glob,os
 for f in sorted(glob.glob(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r3q/bench_*.json')):

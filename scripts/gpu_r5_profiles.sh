@@ -1,7 +1,8 @@
 #!/bin/bash
 # round 5: the default bench line and the rocprofv3 summaries of every configuration (copied to profiles/r05_*)
 mkdir -p gpurun_out/r5p
-python bench.py > gpurun_out/r5p/bench_default.json 2> gpurun_out/r5p/bench_default.err; echo "bench rc=$?"
+OUT=$_   # the folder made above
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
 for cfg in ns ns-perturbed c4 c2 c3 c5; do
   bash scripts/gpu_profile_config.sh $cfg > gpurun_out/r5p/prof_$cfg.log 2>&1
   cp gpurun_out/prof_$cfg/summary.txt gpurun_out/r5p/${cfg}_rocprofv3_summary.txt
