@@ -23,6 +23,7 @@ NEWTON_NO_LINE_SEARCH, NEWTON_BACKTRACKING = 0, 1
 PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, PRECOND_AMG = 0, 1, 2, 3
 AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER = 0, 1, 2
 ASSEMBLE_OVERWRITE = 0x100
+LOAD_TRACTION, LOAD_PRESSURE = 0, 1
 ASSEMBLE_REPRODUCIBLE = 0x200
 
 ELEM_NODES = {QUAD4: 4, HEX8: 8, TET4: 4, HEX27: 27, TRI3: 3, TET10: 10, QUAD9: 9, TRI6: 6, HEX20: 20, TET20: 20}
@@ -114,6 +115,17 @@ _SIGS = {
     "fh_assemble_source_vector_dev": (C.c_int, [C.c_void_p, C.c_uint32, f64p, C.c_void_p, C.c_void_p]),
     "fh_physical_quadrature_points": (C.c_int, [C.c_void_p, f64p]),
     "fh_physical_quadrature_points_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_find_boundary_faces": (C.c_int, [C.c_void_p, u64p, u32p]),
+    "fh_boundary_faces": (C.c_int, [C.c_void_p, u64p, u64p, u32p]),
+    "fh_boundary_faces_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fh_boundary_vertices": (C.c_int, [C.c_void_p, u64p, u64p]),
+    "fh_boundary_cells": (C.c_int, [C.c_void_p, u64p, u64p]),
+    "fh_boundary_search_scratch_bytes": (C.c_int, [C.c_void_p, u64p]),
+    "fh_assemble_surface_load": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, u64p, u32p, C.c_uint64, f64p, f64p, C.c_uint32, f64p, C.c_uint64, f64p]),
+    "fh_assemble_surface_load_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, f64p, f64p, C.c_uint32,
+                                               C.c_void_p, C.c_uint64, C.c_void_p]),
+    "fh_physical_face_quadrature_points": (C.c_int, [C.c_void_p, u64p, u32p, C.c_uint64, f64p, C.c_uint32, f64p]),
+    "fh_physical_face_quadrature_points_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, f64p, C.c_uint32, C.c_void_p]),
     "fh_spmv_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fh_cg_solve": (C.c_int, [C.c_void_p, f64p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_cg_solve_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, u64p]),

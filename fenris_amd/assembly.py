@@ -287,6 +287,63 @@ class Engine:
         self._check(self._lib.fh_physical_quadrature_points(self._h, _ffi.fp(x)))
         return x
 
+    # boundary of the mesh (fh_find_boundary_faces and its queries) and surface loads on face lists
+    def find_boundary_faces(self):
+        """Mesh::find_boundary_faces (mesh.rs:167-203) -> (face_nodes F x nf, cells F, local_faces F)"""
+        nf, npf = C.c_uint64(0), C.c_uint32(0)
+        self._check(self._lib.fh_find_boundary_faces(self._h, C.byref(nf), C.byref(npf)))
+        F, k = int(nf.value), int(npf.value)
+        fn = np.zeros((F, max(k, 1)), dtype=np.uint64)
+        cells, lfs = np.zeros(F, dtype=np.uint64), np.zeros(F, dtype=np.uint32)
+        if F:
+            self._check(self._lib.fh_boundary_faces(self._h, _ffi.up(fn), _ffi.up(cells), lfs.ctypes.data_as(_ffi.u32p)))
+        return fn, cells, lfs
+
+    def _two_phase_u64(self, fn):
+        n = C.c_uint64(0)
+        self._check(fn(self._h, C.byref(n), None))
+        out = np.zeros(int(n.value), dtype=np.uint64)
+        if len(out):
+            self._check(fn(self._h, C.byref(n), _ffi.up(out)))
+        return out
+
+    def boundary_vertices(self):
+        """Mesh::find_boundary_vertices (mesh.rs:208-216): sorted, unique"""
+        return self._two_phase_u64(self._lib.fh_boundary_vertices)
+
+    def boundary_cells(self):
+        """Mesh::find_boundary_cells (mesh.rs:154-163): sorted, unique"""
+        return self._two_phase_u64(self._lib.fh_boundary_cells)
+
+    def assemble_surface_load(self, out, load_kind, solution_dim, cells, local_faces, weights, points, data, data_count):
+        """fh_assemble_surface_load(_dev): out += the traction / pressure load of the faces (cells, local_faces)"""
+        w, p = _ffi.as_f64(weights), _ffi.as_f64(points)
+        if _is_torch(out):
+            import torch
+
+            dev = out.device
+            ct = cells if _is_torch(cells) else torch.from_numpy(np.ascontiguousarray(cells, dtype=np.uint64).view(np.int64)).to(dev)
+            lt = local_faces if _is_torch(local_faces) else torch.from_numpy(np.ascontiguousarray(local_faces, dtype=np.uint32).view(np.int32)).to(dev)
+            dt = data if _is_torch(data) else torch.from_numpy(_ffi.as_f64(data)).to(dev)
+            self._check(self._lib.fh_assemble_surface_load_dev(self._h, load_kind, solution_dim, C.c_void_p(ct.data_ptr()), C.c_void_p(lt.data_ptr()),
+                                                               ct.numel(), _ffi.fp(w), _ffi.fp(p), len(w), C.c_void_p(dt.data_ptr()), int(data_count),
+                                                               C.c_void_p(out.data_ptr())))
+            torch.cuda.synchronize(dev)  # the temporaries above are released on return
+        else:
+            cs, ls, d = _ffi.as_u64(cells), np.ascontiguousarray(local_faces, dtype=np.uint32), _ffi.as_f64(data)
+            self._check(self._lib.fh_assemble_surface_load(self._h, load_kind, solution_dim, _ffi.up(cs), ls.ctypes.data_as(_ffi.u32p), len(cs),
+                                                           _ffi.fp(w), _ffi.fp(p), len(w), _ffi.fp(d), int(data_count), _ffi.fp(out)))
+
+    def physical_face_quadrature_points(self, cells, local_faces, points):
+        """fh_physical_face_quadrature_points -> x (F, nq, d)"""
+        cs, ls, p = _ffi.as_u64(cells), np.ascontiguousarray(local_faces, dtype=np.uint32), _ffi.as_f64(points)
+        d = _ffi.ELEM_DIM[self._mesh.elem_kind]
+        nq = p.size // max(d - 1, 1)
+        x = np.zeros((len(cs), nq, d))
+        self._check(self._lib.fh_physical_face_quadrature_points(self._h, _ffi.up(cs), ls.ctypes.data_as(_ffi.u32p), len(cs), _ffi.fp(p), nq,
+                                                                 _ffi.fp(x)))
+        return x
+
     def spmv(self, values_t, x_t, y_t):
         self._check(self._lib.fh_spmv_dev(self._h, C.c_void_p(values_t.data_ptr()), C.c_void_p(x_t.data_ptr()),
                                           C.c_void_p(y_t.data_ptr())))

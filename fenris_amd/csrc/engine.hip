@@ -429,6 +429,7 @@ void fh_destroy(fh_ctx* c) {
         }
     }
     delete c->rows_stash;
+    boundary_drop(c);
     delete c;
 }
 
@@ -545,6 +546,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     if (E * (uint64_t)ei.n >= (1ull << 32)) return c->fail(FH_UNSUPPORTED, "fh_set_mesh: num_elements * n must be < 2^32");
     HIP_TRY(c, hipSetDevice(c->device));
     invalidate_pattern(c);
+    boundary_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
@@ -643,6 +645,7 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     if (N >= (1ull << 31) || total >= (1ull << 32)) return c->fail(FH_UNSUPPORTED, "connectivity too large");
     HIP_TRY(c, hipSetDevice(c->device));
     invalidate_pattern(c);
+    boundary_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
     c->mass_rho_n = 0;   // (the density belongs to the mesh)

@@ -464,6 +464,7 @@ struct fh_ctx {
     unsigned long long dirichlet_gen = 0;   // counts fh_set_operator_dirichlet_nodes calls
     fh_mg* mg = nullptr;               // the multigrid hierarchy of FH_PRECOND_MULTIGRID (fh_set_multigrid; not owned)
     fh_amg* amg = nullptr;             // the algebraic hierarchy of FH_PRECOND_AMG (fh_set_amg; not owned)
+    struct BoundaryStore* bnd = nullptr;   // boundary faces of the mesh and the adjacency of the last surface-load face list (engine_boundary.hip)
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -575,6 +576,8 @@ int mg_dense_inverse(fh_ctx* f, const char* who, std::vector<double>& A, int n, 
 // FH_PRECOND_AMG (engine_amg.hip) on c->amg: one V-cycle z = B r; the context is going away
 int amg_precondition(fh_amg* amg, const double* r, double* z);
 void amg_orphan(fh_amg* amg);
+// the cached boundary search and surface-load tables (engine_boundary.hip): dropped with the connectivity, kept by fh_update_vertices
+void boundary_drop(fh_ctx* c);
 // y = K x on the context's pattern with the values of an assembled matrix (engine_solver.hip; fh_spmv_dev without the checks)
 int csr_spmv(fh_ctx* c, const double* vals, const double* x, double* y);
 // PCG with the V-cycle (engine_solver.hip): x += alpha p, r -= alpha Ap, partials of r . r into slot 1 of 2 per workgroup; partials of

@@ -31,6 +31,28 @@ class Mesh:
     def num_nodes(self):
         return len(self.vertices)
 
+    # the boundary (src/mesh.rs:154-216, 505-516): searched on the device, see fenris_amd/boundary.py
+    def find_boundary_faces(self, engine=None):
+        """-> BoundaryFaces; unpacks as (face_connectivity, cells, local_faces)"""
+        from . import boundary
+
+        return boundary.find_boundary_faces(self, engine)
+
+    def find_boundary_vertices(self, engine=None):
+        from . import boundary
+
+        return boundary.find_boundary_vertices(self, engine)
+
+    def find_boundary_cells(self, engine=None):
+        from . import boundary
+
+        return boundary.find_boundary_cells(self, engine)
+
+    def extract_surface_mesh(self, engine=None):
+        from . import boundary
+
+        return boundary.extract_surface_mesh(self, engine)
+
 
 def _gen(fn, d, n, kind, *args):
     nv, nc = C.c_uint64(), C.c_uint64()

@@ -301,6 +301,51 @@ int fh_assemble_source_vector_dev(fh_ctx*, uint32_t solution_dim, const double* 
                                   double* out_dev);
 int fh_physical_quadrature_points(fh_ctx*, double* x /* E x nq x d */);
 int fh_physical_quadrature_points_dev(fh_ctx*, double* x_dev);
+/* ---- boundary of the mesh: Mesh::find_boundary_faces / find_boundary_vertices / find_boundary_cells (src/mesh.rs:154-216), on the
+ *      device; bit-identical index arrays ------------------------------------------------------------------------------------------
+ * Every cell emits its faces in local order with the node lists of get_face_connectivity (src/connectivity.rs: Quad4 / Tri3 ->
+ * Segment2, Quad9 / Tri6 -> Segment3, Tet4 -> Tri3, Tet10 -> Tri6, Hex8 -> Quad4, Hex20 -> Quad8, Hex27 -> Quad9, Tet20 -> no faces:
+ * an empty result); faces point outward.  Two faces are the same face iff their sorted full node tuples are equal; a boundary face
+ * is one whose tuple occurs exactly once; the output is in ascending lexicographic order of the sorted tuples (the BTreeMap iteration,
+ * mesh.rs:187-202).  fh_find_boundary_faces runs the search and keeps the result on the context: fh_set_mesh* and
+ * fh_set_connectivity_ragged drop it, fh_update_vertices keeps it; the queries below run it when it is missing.  Before a mesh is
+ * set: FH_INVALID_STATE; on a ragged generic connectivity: FH_UNSUPPORTED.  Scratch, released when the
+ * search returns: 24 bytes per (cell, local face) for keys and face ids plus the radix sort's own temporary, 36 bytes in all
+ * (fh_boundary_search_scratch_bytes: the figure of the search that produced the cached result). */
+int fh_find_boundary_faces(fh_ctx*, uint64_t* num_faces, uint32_t* nodes_per_face);
+/* face_nodes: F x nodes_per_face in the cell's orientation; cells: F; local_faces: F.  Any pointer may be NULL. */
+int fh_boundary_faces(fh_ctx*, uint64_t* face_nodes, uint64_t* cells, uint32_t* local_faces);
+int fh_boundary_faces_dev(fh_ctx*, uint64_t* face_nodes_dev, uint64_t* cells_dev, uint32_t* local_faces_dev);
+/* sorted and unique (mesh.rs:208-216 / 154-163); two-phase like fh_pattern: a NULL array gives *count only.  The vertex list can be
+ * passed to fh_apply_dirichlet_* and fh_set_operator_dirichlet_nodes as it is. */
+int fh_boundary_vertices(fh_ctx*, uint64_t* count, uint64_t* nodes);
+int fh_boundary_cells(fh_ctx*, uint64_t* count, uint64_t* cells);
+int fh_boundary_search_scratch_bytes(const fh_ctx*, uint64_t* bytes);
+/* ---- surface load vector on a list of (cell, local face) pairs -- any subset of the faces in any order, e.g. part of the boundary.
+ * No reference counterpart (the reference has no Neumann assembler); solution_dim s is 1 or the geometry dimension d:
+ *   FH_LOAD_TRACTION: out[s I + c] += sum_faces sum_q  w_q N_I(x_q) t_c(face, q) |a_q|
+ *   FH_LOAD_PRESSURE: out[d I + c] += sum_faces sum_q -w_q N_I(x_q) p(face, q)   a_q[c]          (s == d)
+ * a_q = det(J) J^-T n_ref times the reference face measure is the outward area vector (Nanson), with the CELL's Jacobian at the
+ * face point mapped into the cell (the sub-parametric corner geometry of the high-order kinds, hexahedron.rs:324-330); in 2D the
+ * face is an edge and a_q the tangent turned clockwise.  N_I is the cell's basis; only the face's own nodes are touched.  The face
+ * rule (weights, points: nq x (d - 1), host) lives on the face's reference domain: [-1, 1] for a segment, [-1, 1]^2 for a
+ * quadrilateral, the triangle (-1, -1), (1, -1), (-1, 1).  data holds t (s per item) or p (1 per item); data_count picks the shape:
+ * 1: one item for all faces, num_faces: one per face, num_faces * nq: one per face and point.  out (s N) is ACCUMULATED into, per
+ * node in ascending (position in the list, q) order without atomics: two calls agree bit for bit.  Only |a_q| enters a traction: a
+ * degenerate face is not an error.  The node adjacency of the list is cached on the context, keyed on the list's contents.
+ * Independent of operator and quadrature table.  A cell or local face out of range: FH_BAD_ARGUMENT. */
+enum { FH_LOAD_TRACTION = 0, FH_LOAD_PRESSURE = 1 };
+int fh_assemble_surface_load(fh_ctx*, int load_kind, uint32_t solution_dim, const uint64_t* cells, const uint32_t* local_faces,
+                             uint64_t num_faces, const double* weights, const double* points, uint32_t nq, const double* data,
+                             uint64_t data_count, double* out);
+int fh_assemble_surface_load_dev(fh_ctx*, int load_kind, uint32_t solution_dim, const uint64_t* cells_dev, const uint32_t* local_faces_dev,
+                                 uint64_t num_faces, const double* weights /* host */, const double* points /* host */, uint32_t nq,
+                                 const double* data_dev, uint64_t data_count, double* out_dev);
+/* x_q of every face and point (num_faces x nq x d), where the caller samples t(x) or p(x) -- as fh_physical_quadrature_points for volumes */
+int fh_physical_face_quadrature_points(fh_ctx*, const uint64_t* cells, const uint32_t* local_faces, uint64_t num_faces,
+                                       const double* points, uint32_t nq, double* x);
+int fh_physical_face_quadrature_points_dev(fh_ctx*, const uint64_t* cells_dev, const uint32_t* local_faces_dev, uint64_t num_faces,
+                                           const double* points /* host */, uint32_t nq, double* x_dev);
 /* single element matrix, (s n)^2 column-major: ElementMatrixAssembler::assemble_element_matrix_into
  * (src/assembly/local.rs:78, elliptic.rs:299-340) -- for unit tests of the element kernels */
 int fh_assemble_element_matrices(fh_ctx*, uint64_t first_element, uint64_t count, double* ke_out);
