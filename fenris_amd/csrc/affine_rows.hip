@@ -32,6 +32,7 @@
 // reproducible for the same reason.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "affine_rows.hpp"
@@ -616,14 +617,18 @@ k_affine_rows(const KArgs a, const AffineRowTables T, const int ablate_arg) {
 }
 
 // ------------------------------------------------------------------------------------------------ element records
-// One thread per element, once per assembly, right before k_affine_rows: the record of an affine element from four of its
-// vertices.  The edges from node 0 to nodes 1, 3, 4 are twice the columns of J (hexahedron.rs:49-58: nodes (---), (+--),
+// One thread per element: the record of an affine element from four of its vertices.  The records depend on the context's copies of the
+// vertices, the connectivity and the affine flags only, so launch_affine (engine_matrix.hip) runs this pass when those have changed or the
+// element range is not covered yet, not once per assembly; k_affine_rows reads what an earlier pass left.  The edges from node 0 to nodes 1, 3, 4 are twice the columns of J (hexahedron.rs:49-58: nodes (---), (+--),
 // (-+-), (--+); exact for a parallelepiped; elliptic.rs:398-404 evaluates the same Jacobian at every quadrature point).
 // LinearElastic: R = sqrt(|det J|) J^-1 = sign(det J) rsqrt(|det J|) adj(J), nine doubles + pad; Laplace: M = R R^T, six.
-// det J == 0 exactly is the reference's "Singular element Jacobian" (try_inverse fails only then): reported, record zero.
+// det J == 0 exactly is the reference's "Singular element Jacobian" (try_inverse fails only then): reported, record zero -- and, whatever
+// the mask says, marked in `sing` (word 0: number of marks, then one bit per element) for k_affine_replay_singular, which repeats the report
+// in the assemblies that skip this pass.
 template <int OP>
 __global__ void __launch_bounds__(256) k_affine_records(const double* verts, const int* conn, const unsigned char* elem_aff,
-                                                        const unsigned char* active, long long e_first, long long E, double* rec, DevStatus* status) {
+                                                        const unsigned char* active, long long e_first, long long E, double* rec, DevStatus* status,
+                                                        unsigned* sing) {
     // OP == FH_MASS_SCALAR (the mass matrix of affine elements, mass.rs:131-286: M_ab = |det J| sum_q w rho phi_a phi_b): the Laplace
     // layout with |det J| in the first place -- k_affine_rows<FH_LAPLACE> multiplies it with the reference block (sum_q w rho phi_a phi_b, 0 ...)
     constexpr bool MASS = (OP == FH_MASS_SCALAR);
@@ -659,6 +664,8 @@ __global__ void __launch_bounds__(256) k_affine_records(const double* verts, con
         } else
         if (detJ == 0.0) {
             if (!active || active[e]) report_singular(status, e);
+            atomicOr(&sing[1 + (e >> 5)], 1u << (unsigned)(e & 31));
+            atomicAdd(&sing[0], 1u);
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -694,12 +701,38 @@ __global__ void __launch_bounds__(256) k_affine_records(const double* verts, con
 }
 
 hipError_t affine_records_launch(int op, hipStream_t stream, const double* verts, const int* conn, const unsigned char* elem_aff,
-                                 const unsigned char* active, long long e_first, long long e_end, double* rec, DevStatus* status) {
+                                 const unsigned char* active, long long e_first, long long e_end, double* rec, DevStatus* status, unsigned* sing) {
     if (e_end <= e_first) return hipSuccess;
     const dim3 grid((unsigned)((e_end - e_first + 255) / 256));
-    if (op == FH_LAPLACE) hipLaunchKernelGGL(k_affine_records<FH_LAPLACE>, grid, dim3(256), 0, stream, verts, conn, elem_aff, active, e_first, e_end, rec, status);
-    else if (op == FH_MASS_SCALAR) hipLaunchKernelGGL(k_affine_records<FH_MASS_SCALAR>, grid, dim3(256), 0, stream, verts, conn, elem_aff, active, e_first, e_end, rec, status);
-    else hipLaunchKernelGGL(k_affine_records<FH_LINEAR_ELASTIC>, grid, dim3(256), 0, stream, verts, conn, elem_aff, active, e_first, e_end, rec, status);
+    if (op == FH_LAPLACE) hipLaunchKernelGGL(k_affine_records<FH_LAPLACE>, grid, dim3(256), 0, stream, verts, conn, elem_aff, active, e_first, e_end, rec, status, sing);
+    else if (op == FH_MASS_SCALAR) hipLaunchKernelGGL(k_affine_records<FH_MASS_SCALAR>, grid, dim3(256), 0, stream, verts, conn, elem_aff, active, e_first, e_end, rec, status, sing);
+    else hipLaunchKernelGGL(k_affine_records<FH_LINEAR_ELASTIC>, grid, dim3(256), 0, stream, verts, conn, elem_aff, active, e_first, e_end, rec, status, sing);
+    return hipGetLastError();
+}
+
+// An assembly whose records are still current skips k_affine_records and with it the report of singular elements: this kernel repeats the
+// report for the elements [e_first, e_end) of the active set from the marks the records pass left.  A mesh without a degenerate affine
+// element (word 0 is zero) costs one word read per workgroup.
+__global__ void __launch_bounds__(256) k_affine_replay_singular(const unsigned* sing, const unsigned char* active, long long e_first, long long e_end,
+                                                                DevStatus* status) {
+    if (sing[0] == 0u) return;
+    const long long w_end = (e_end + 31) >> 5;
+    for (long long w = (e_first >> 5) + (long long)blockIdx.x * 256 + threadIdx.x; w < w_end; w += 256LL * gridDim.x) {
+        unsigned bits = sing[1 + w];
+        while (bits) {
+            const long long e = (w << 5) + (__ffs((int)bits) - 1);
+            bits &= bits - 1u;
+            if (e >= e_first && e < e_end && (!active || active[e])) report_singular(status, e);
+        }
+    }
+}
+
+hipError_t affine_replay_singular_launch(hipStream_t stream, const unsigned* sing, const unsigned char* active, long long e_first, long long e_end,
+                                         DevStatus* status) {
+    if (e_end <= e_first) return hipSuccess;
+    const long long words = ((e_end + 31) >> 5) - (e_first >> 5);
+    const dim3 grid((unsigned)std::min<long long>(64, (words + 255) / 256));
+    hipLaunchKernelGGL(k_affine_replay_singular, grid, dim3(256), 0, stream, sing, active, e_first, e_end, status);
     return hipGetLastError();
 }
 

@@ -14,7 +14,7 @@ struct AffineRowTables {
                           //               number of slots}
     const uint2* lanes;   // [ntab][256]  lane records, see affine_rows.hip; positions with identical records share a table
     const int* elem;      // [npos][us]   element id per slot (-1: empty)
-    const double* rec;    // [E][GW]      element records (R or M) written by affine_records_launch before every launch
+    const double* rec;    // [E][GW]      element records (R or M) as affine_records_launch left them
     const double* ghat;   // [64][GW]     reference blocks Ghat_ab (all 64 (a, b); LinearElastic GW = 10, Laplace GW = 6)
     int us, npos, acc_max;  // slots per position, positions of this launch, largest S * S * nrow
     int pos0, npos_all;     // first position of this launch (launches may cover a part of the sweep), positions in the tables
@@ -47,11 +47,17 @@ hipError_t affine_rows_tables(hipStream_t stream, const int* p_rec, int rw_old, 
 // owner only (x bit 29: the lane also stores the transpose to the twin), and y = offset in doubles | node << 13 | twin offset << 16 |
 // twin node << 29 (row strides from the position record)
 
-// element records of the affine elements (elem_aff[e] != 0) among [e_first, e_end) from the current vertex coordinates: once per assembly, on the same
-// stream right before affine_rows_launch.  A singular element (det J == 0 exactly) of the active set (active == NULL: all) is
-// reported through `status`.
+// element records of the affine elements (elem_aff[e] != 0) among [e_first, e_end) from the current vertex coordinates, on the stream of
+// affine_rows_launch in front of it.  They stay valid until the vertices, the connectivity or the flags change: the caller decides when to
+// run this again (launch_affine).  A singular element (det J == 0 exactly) of the active set (active == NULL: all) is reported through
+// `status`, and marked in `sing` whether active or not (affine_sing_words(E) words, zeroed by the caller: the number of marks, one bit per element).
 hipError_t affine_records_launch(int op, hipStream_t stream, const double* verts, const int* conn, const unsigned char* elem_aff,
-                                 const unsigned char* active, long long e_first, long long e_end, double* rec, DevStatus* status);
+                                 const unsigned char* active, long long e_first, long long e_end, double* rec, DevStatus* status, unsigned* sing);
+inline size_t affine_sing_words(unsigned long long E) { return 1 + (size_t)((E + 31) / 32); }
+// what an assembly that does not run the records pass enqueues instead: the marked elements of [e_first, e_end) that are active now are
+// reported through `status` exactly as the pass itself would have
+hipError_t affine_replay_singular_launch(hipStream_t stream, const unsigned* sing, const unsigned char* active, long long e_first, long long e_end,
+                                         DevStatus* status);
 
 // Positions with identical lane records share one table: `lanes_full` [npos][256] as written by affine_rows_build, `ids` the
 // table of every position, `first_pos` [ntab] a position that holds each table.  Writes the compact tables, puts the id into

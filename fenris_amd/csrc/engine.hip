@@ -471,6 +471,7 @@ int fh_set_option(fh_ctx* c, const char* name, const char* value) {
 int fh_set_stream(fh_ctx* c, void* s) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
+    if (c->stream != reinterpret_cast<hipStream_t>(s)) ++c->a_recs_gen;   // kept element records were enqueued on the old stream: formed again on the new one
     c->stream = reinterpret_cast<hipStream_t>(s);
     return FH_OK;
 }
@@ -493,6 +494,7 @@ uint64_t fh_nnz(const fh_ctx* c) { return (c && c->has_pattern) ? (uint64_t)c->S
 static int classify_affine(fh_ctx* c) {
     const bool had = c->has_aff;
     const uint64_t old_count = c->num_aff;
+    ++c->a_recs_gen;   // new vertices, connectivity or tolerance: the element records (launch_affine) are formed again, also where the flags stay
     c->has_aff = false;
     c->num_aff = 0;
     if (c->elem_kind != FH_HEX8 || c->E == 0 || !(c->affine_tol > 0.0)) {
@@ -536,6 +538,7 @@ static int classify_affine(fh_ctx* c) {
     // backed (two modes 8 % apart, profiles/r03_affine_experiments.txt).
     if (h > 0 && c->a_recs.n < (size_t)c->E * AFFINE_ROWS_GW_LE)
         HIP_TRY(c, c->a_recs.alloc((size_t)c->E * AFFINE_ROWS_GW_LE));
+    if (h > 0 && c->a_sing.n < affine_sing_words(c->E)) HIP_TRY(c, c->a_sing.alloc(affine_sing_words(c->E)));
     return FH_OK;
 }
 
@@ -695,6 +698,7 @@ int fh_set_active_elements(fh_ctx* c, const uint8_t* mask) {
 }
 extern "C++" int apply_mask(fh_ctx* c, const uint8_t* mask) {
     c->has_partition = false; ++c->struct_gen; c->has_tp_pos = false;
+    ++c->a_recs_gen;   // (the mask gates only the singular report of the records pass; a mask change is rare enough to pay one pass for it)
     if (!mask) {
         c->has_mask = false;
         if (c->has_colors) return upload_colors(c, c->host_colors_offs, c->host_colors_labels);

@@ -369,7 +369,16 @@ struct fh_ctx {
     DevBuf<int> a_conn, a_elem;     // k_affine_rows (affine_rows.hip): per-slot connectivity (table build only), element ids
     DevBuf<uint2> a_lanes;          // lane records
     DevBuf<int4> a_hdr;             // position headers
-    DevBuf<double> a_recs;          // element records (R or M), rewritten by every assembly
+    DevBuf<double> a_recs;          // element records (R or M) of k_affine_records: kept from assembly to assembly, see a_recs_valid
+    // Which records in a_recs are current: the elements [lo, hi), written in the format of operator `op` (FH_LINEAR_ELASTIC, FH_LAPLACE or
+    // FH_MASS_SCALAR) while a_recs_gen had the value `gen`.  a_recs_gen moves with everything the records pass reads or writes to:
+    // classify_affine (vertices, connectivity, affine flags, tolerance), the element mask (apply_mask), the stream (fh_set_stream), a new
+    // a_recs or a_sing buffer and every exchange of a_recs.p by fh_tune_placement_dev.
+    // launch_affine runs the records pass only for a range this does not cover.  One record set: both sets of partition tables
+    // (rows_stash) share it, and a context that alternates between operators forms the records again at each change.
+    struct { long long lo = 0, hi = 0; int op = -1; unsigned long long gen = ~0ull; } a_recs_valid;
+    unsigned long long a_recs_gen = 0;
+    DevBuf<unsigned> a_sing;        // singular affine elements the records pass met since a_sing was cleared: count, then a bit per element (affine_rows.hpp)
     int a_us = 0, a_npos = 0, a_ntab = 0, a_incomplete = 0;
     // general Hex8 row-owner kernel (hex8_rows.hip): lane tables and position records of the GENERAL positions (p_rec order)
     DevBuf<int4> h_hdr, h_pos;

@@ -171,7 +171,8 @@ int launch_pipelined(fh_ctx* c, KArgs& a, const PipeTables& T, size_t lds, int g
     }
 }
 
-// node blocks all of whose elements are affine: k_affine_records + k_affine_rows (affine_rows.hip) over their position tables
+// node blocks all of whose elements are affine: k_affine_rows (affine_rows.hip) over their position tables, behind k_affine_records where
+// the element records are not current
 int launch_affine(fh_ctx* c, KArgs& a) {
     int dev_cus = 256;
     (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
@@ -182,7 +183,8 @@ int launch_affine(fh_ctx* c, KArgs& a) {
     // headline, profiles/r05_fused_records_experiment.txt; the barrier-free ring form, affine_ring.hip -- 5 % slower; positions dealt in chunks
     // instead of one contiguous range per workgroup, profiles/r04_chunk_experiment.txt; non-temporal row stores for elasticity; two store waves.)
     const int a_depth = c->env_int("FENRIS_HIP_AFFINE_DEPTH", 2);
-    if (c->a_recs.n < (size_t)c->E * gw) HIP_TRY(c, c->a_recs.alloc((size_t)c->E * gw));
+    if (c->a_recs.n < (size_t)c->E * gw) { HIP_TRY(c, c->a_recs.alloc((size_t)c->E * gw)); ++c->a_recs_gen; }
+    if (c->a_sing.n < affine_sing_words(c->E)) { HIP_TRY(c, c->a_sing.alloc(affine_sing_words(c->E))); ++c->a_recs_gen; }
     const unsigned char* act = c->has_mask ? c->active.p : nullptr;
     DevStatus* status = c->status.p + c->status_slot;
     const int nt = (rop == FH_LAPLACE ? AFFINE_ROWS_NT_STORES : 0) | ((c->env_int("FENRIS_HIP_AFFINE_PRIO", 3 | (2 << 2)) & 15) << AFFINE_ROWS_PRIO_SHIFT);
@@ -200,13 +202,35 @@ int launch_affine(fh_ctx* c, KArgs& a) {
         HIP_TRY(c, affine_rows_launch(rop, a_depth, grid, lds, c->stream, a, T, a.ablate | nt, c->has_mask));
         return FH_OK;
     };
-    // element records first (R = sqrt|det J| J^-1 or M = R R^T per affine element): same stream, once per assembly.  (Round 3: making
-    // the records of all but the first eighth of the sweep on a second stream beside the first part's launch was measured 0.3 ms
-    // SLOWER than the 0.41 ms it hides -- the two kernels' workgroups compete for the CUs; two launches of the sweep in one stream cost
+    // Element records (R = sqrt|det J| J^-1 or M = R R^T per affine element) on the same stream in front of the sweep -- but only those that are
+    // not current (fh_ctx::a_recs_valid): they are a function of the context's vertices, connectivity and affine flags, not of the material,
+    // the flags of the call or the values, so a caller that assembles again on an unchanged mesh (time steps, material sweeps, the interface and
+    // main launches of a slab step) gets ONE launch per assembly.  The sweep reads them from memory either way: 20 GB of rows are written
+    // between their production and their use.  FENRIS_HIP_AFFINE_RECORDS_ALWAYS=1 runs the pass in every assembly, as before.
+    // (Round 3: making the records of all but the first eighth of the sweep on a second stream beside the first part's launch was measured
+    // 0.3 ms SLOWER than the 0.41 ms it hides -- the two kernels' workgroups compete for the CUs; two launches of the sweep in one stream cost
     // nothing measurable, and records made chunk by chunk right before their part of the sweep (to be read back from the memory-side
     // cache) change nothing up to 4 chunks and lose from 8 on.  profiles/r03_affine_experiments.txt)
-    HIP_TRY(c, affine_records_launch(c->op, c->stream, c->verts.p, c->conn.p, c->elem_aff.p, act, c->a_emin, std::min<long long>(c->a_emax + 1, (long long)c->E),
-                                     c->a_recs.p, status));
+    const long long e_lo = c->a_emin, e_hi = std::min<long long>(c->a_emax + 1, (long long)c->E);
+    auto& v = c->a_recs_valid;
+    const bool current = v.gen == c->a_recs_gen && v.op == c->op;
+    const bool covered = current && v.lo <= e_lo && e_hi <= v.hi;
+    if (!covered || c->env_int("FENRIS_HIP_AFFINE_RECORDS_ALWAYS", 0)) {
+        // the marks of singular elements belong to one generation and format: cleared when either moves
+        if (!current) HIP_TRY(c, hipMemsetAsync(c->a_sing.p, 0, sizeof(unsigned) * c->a_sing.n, c->stream));
+        if (c->env("FENRIS_HIP_VERBOSE"))
+            std::fprintf(stderr, "[fenris_hip] affine records computed: elements [%lld, %lld)\n", e_lo, e_hi);
+        HIP_TRY(c, affine_records_launch(c->op, c->stream, c->verts.p, c->conn.p, c->elem_aff.p, act, e_lo, e_hi, c->a_recs.p, status, c->a_sing.p));
+        if (current && e_lo <= v.hi && v.lo <= e_hi) {   // touches or overlaps what is valid: the union
+            v.lo = std::min(v.lo, e_lo);
+            v.hi = std::max(v.hi, e_hi);
+        } else {
+            v.lo = e_lo; v.hi = e_hi; v.op = c->op; v.gen = c->a_recs_gen;
+        }
+    } else {
+        // the records pass is also what reports a singular affine element: its marks repeat the report, for this range and this mask
+        HIP_TRY(c, affine_replay_singular_launch(c->stream, c->a_sing.p, act, e_lo, e_hi, status));
+    }
     return rows(0, c->a_npos);
 }
 
@@ -541,6 +565,9 @@ int fh_tune_placement_dev(fh_ctx* c, double* values_dev, int flags, int tries, d
     if (ms_after) *ms_after = best;
     // the one large buffer of its own that the affine kernels stream through: the element records.  (Moving the position tables and
     // the lane tables never changed the level.)  Rejected allocations are held until the end: freed at once they would be handed out again.
+    // A candidate holds no records: every exchange of the pointer, the return to the old buffer included, moves a_recs_gen, so the first of
+    // the reps + 1 assemblies of each timing forms them and the timed ones read them.  The candidates are ranked by the sweep's reads of the
+    // buffer, which is what its placement changes.
     if (!c->a_recs.p || c->a_npos == 0 || tries < 1) return FH_OK;
     std::vector<double*> rejected;
     const size_t bytes = c->a_recs.n * sizeof(double);
@@ -548,14 +575,16 @@ int fh_tune_placement_dev(fh_ctx* c, double* values_dev, int flags, int tries, d
         double* cand = nullptr;
         if (hipMalloc(reinterpret_cast<void**>(&cand), bytes) != hipSuccess) { (void)hipGetLastError(); break; }
         double* old = c->a_recs.p;
-        c->a_recs.p = cand;   // the records are rewritten by every assembly: nothing to copy
+        c->a_recs.p = cand;
+        ++c->a_recs_gen;
         double t = 0.0;
         rc = fh_time_assembly_dev(c, values_dev, flags, 3, &t);
         if (rc == FH_OK && t < 0.98 * best) {
             best = t;
             rejected.push_back(old);
         } else {
-            c->a_recs.p = old;
+            c->a_recs.p = old;   // (its records were current before the exchange, but nothing remembers that: formed again by the next assembly)
+            ++c->a_recs_gen;
             rejected.push_back(cand);
         }
         if (rc) break;

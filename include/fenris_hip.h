@@ -122,12 +122,15 @@ int fh_synchronize(fh_ctx*);
 /* ---- inputs -------------------------------------------------------------------------------- */
 /* Mesh<f64, D, C>: replaces passing &Mesh to ElementEllipticAssemblerBuilder::with_finite_element_space
  * (src/assembly/local/elliptic.rs:86-97).  Data is copied to the device (connectivity narrowed to i32;
- * num_vertices must be < 2^31).  Invalidates pattern, colours and u. */
+ * num_vertices must be < 2^31).  Invalidates pattern, colours and u.  The element records of the affine-element kernel (Hex8) are a
+ * function of the context's copy of this data: fh_set_mesh*, fh_update_vertices and fh_set_affine_tolerance are the calls after which the
+ * next assembly forms them again; assemblies in between reuse them, whatever the material, the operator's parameters or the flags. */
 int fh_set_mesh(fh_ctx*, int elem_kind, const double* vertices, uint64_t num_vertices,
                 const uint64_t* connectivity, uint64_t num_elements);
 int fh_set_mesh_dev(fh_ctx*, int elem_kind, const double* vertices_dev, uint64_t num_vertices,
                     const uint64_t* connectivity_dev, uint64_t num_elements);
-/* only the vertex coordinates change (e.g. moving mesh); pattern stays valid */
+/* only the vertex coordinates change (e.g. moving mesh); pattern stays valid.  The affine flags of the elements and the element records
+ * of the affine-element kernel follow the new coordinates (the records at the next assembly). */
 int fh_update_vertices(fh_ctx*, const double* vertices);
 /* Generic ElementConnectivityAssembler with ragged element node lists (src/assembly/local.rs:18-47),
  * e.g. the mock connectivities of tests/unit_tests/assembly/global.rs:70-142.  Only fh_pattern*,
@@ -197,7 +200,8 @@ int fh_quadrature_rule_groups(const fh_ctx*, uint64_t* num_groups);
  * by O(rel_tol) relative at most (exactly affine elements -- every generated box mesh -- agree to rounding).
  * Default 2^-46 (1.4e-14); 0 switches the path off.  No reference counterpart (the reference has one code path).
  * Only the stiffness fast path follows a loosened tolerance: the residual / energy kernels take the all-affine shortcut of a mesh
- * only at the default tolerance (or tighter) and use the exact geometry otherwise. */
+ * only at the default tolerance (or tighter) and use the exact geometry otherwise.  A changed tolerance classifies the elements again
+ * and, like new vertices, makes the next assembly form the element records again. */
 int fh_set_affine_tolerance(fh_ctx*, double rel_tol);
 /* how the last FH_SCATTER_GATHER assembly was split: elements found affine, node blocks on the affine kernel, node blocks on
  * the general kernels (any pointer may be NULL; zeros before the first assembly) */
@@ -253,7 +257,8 @@ int fh_poll_status(fh_ctx*, uint64_t* failed_element);
  * the life of an allocation, and no HIP call chooses the backing.  fh_time_assembly_dev times `reps` assemblies (after one untimed)
  * with events on the context's stream; a caller uses it to keep the better of several allocations of its `values`.
  * fh_tune_placement_dev does the same for the library's own large buffer (the element records of the affine-element kernel): up to
- * `tries` re-allocations, each timed with three assemblies, the fastest kept.  BOTH need FH_ASSEMBLE_OVERWRITE (the timed / trial
+ * `tries` re-allocations, each timed with three assemblies (behind an untimed one that fills the candidate with the records), the fastest
+ * kept.  BOTH need FH_ASSEMBLE_OVERWRITE (the timed / trial
  * assemblies are real ones and write `values`; FH_BAD_ARGUMENT otherwise).  No reference counterpart. */
 /* A tuning switch of this context (a FENRIS_HIP_* name as fh_create reads them from the environment): set, or removed with value ==
  * NULL.  Launch-variant switches act at the next call.  For comparing variants inside ONE context on the same buffers. */
