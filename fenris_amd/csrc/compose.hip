@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/fenris_hip.h"
+#include "dispatch.hpp"
 #include "group_internal.hpp"
 
 namespace {
@@ -90,10 +91,11 @@ int fh_add_mapped_matrix_dev(fh_ctx* c, const double* src_values_dev, const uint
     const auto* map = reinterpret_cast<const unsigned long long*>(node_map_dev);
     const auto* dro = reinterpret_cast<const unsigned long long*>(dst_row_offsets_dev);
     const auto* dci = reinterpret_cast<const unsigned long long*>(dst_col_indices_dev);
-#define LAUNCH(SV) hipLaunchKernelGGL(k_add_mapped_matrix<SV>, dim3(grid), dim3(256), 0, stream, (int)N, noff, ncols, src_values_dev, map, scale, \
-                                      (unsigned long long)dst_num_nodes, dro, dci, dst_values_dev, flag)
-    if (S == 1) LAUNCH(1); else if (S == 2) LAUNCH(2); else LAUNCH(3);
-#undef LAUNCH
+    fenris_hip::dispatch_or_last(fenris_hip::solution_dims, S, [&](auto s) {
+        hipLaunchKernelGGL(k_add_mapped_matrix<s()>, dim3(grid), dim3(256), 0, stream, (int)N, noff, ncols, src_values_dev, map, scale,
+                           (unsigned long long)dst_num_nodes, dro, dci, dst_values_dev, flag);
+        return 0;
+    });
     if (hipGetLastError() != hipSuccess) { (void)hipFree(flag); return fh_internal_fail(c, FH_HIP_ERROR, "fh_add_mapped_matrix: launch failed"); }
     return check_missing(c, flag, stream, "fh_add_mapped_matrix");
 }
@@ -119,10 +121,11 @@ int fh_add_mapped_vector_sdim_dev(fh_ctx* c, const double* src_dev, const uint64
         return fh_internal_fail(c, FH_HIP_ERROR, "fh_add_mapped_vector: allocation failed");
     const unsigned grid = (unsigned)((N * (uint64_t)S + 255) / 256);
     const auto* map = reinterpret_cast<const unsigned long long*>(node_map_dev);
-#define LAUNCH(SV) hipLaunchKernelGGL(k_add_mapped_vector<SV>, dim3(grid), dim3(256), 0, stream, (int)N, src_dev, map, scale, \
-                                      (unsigned long long)dst_num_nodes, dst_dev, flag)
-    if (S == 1) LAUNCH(1); else if (S == 2) LAUNCH(2); else LAUNCH(3);
-#undef LAUNCH
+    fenris_hip::dispatch_or_last(fenris_hip::solution_dims, S, [&](auto s) {
+        hipLaunchKernelGGL(k_add_mapped_vector<s()>, dim3(grid), dim3(256), 0, stream, (int)N, src_dev, map, scale, (unsigned long long)dst_num_nodes, dst_dev,
+                           flag);
+        return 0;
+    });
     if (hipGetLastError() != hipSuccess) { (void)hipFree(flag); return fh_internal_fail(c, FH_HIP_ERROR, "fh_add_mapped_vector: launch failed"); }
     return check_missing(c, flag, stream, "fh_add_mapped_vector");
 }

@@ -62,14 +62,10 @@ int spmv(fh_amg* h, AmgLevel& L, int which, const double* x, double* y, bool acc
     else { off = L.pt_off.p; cols = L.pt_cols.p; v = L.pt_vals.p; rows = L.nagg * L.C; R = L.C; Cb = L.R; }
     if (rows == 0) return FH_OK;
     const int g = G(rows);
-    switch (Cb) {
-        case 1: hipLaunchKernelGGL(k_amg_spmv<1>, dim3(g), dim3(256), 0, st, rows, R, off, cols, v, x, y, (int)accumulate); break;
-        case 2: hipLaunchKernelGGL(k_amg_spmv<2>, dim3(g), dim3(256), 0, st, rows, R, off, cols, v, x, y, (int)accumulate); break;
-        case 3: hipLaunchKernelGGL(k_amg_spmv<3>, dim3(g), dim3(256), 0, st, rows, R, off, cols, v, x, y, (int)accumulate); break;
-        case 4: hipLaunchKernelGGL(k_amg_spmv<4>, dim3(g), dim3(256), 0, st, rows, R, off, cols, v, x, y, (int)accumulate); break;
-        case 5: hipLaunchKernelGGL(k_amg_spmv<5>, dim3(g), dim3(256), 0, st, rows, R, off, cols, v, x, y, (int)accumulate); break;
-        default: hipLaunchKernelGGL(k_amg_spmv<6>, dim3(g), dim3(256), 0, st, rows, R, off, cols, v, x, y, (int)accumulate); break;
-    }
+    dispatch_or_last(int_list<1, 2, 3, 4, 5, 6>{}, Cb, [&](auto cb) {   // (columns per block: anything else runs as 6)
+        hipLaunchKernelGGL(k_amg_spmv<cb()>, dim3(g), dim3(256), 0, st, rows, R, off, cols, v, x, y, (int)accumulate);
+        return 0;
+    });
     HIP_TRY(c, hipGetLastError());
     return FH_OK;
 }

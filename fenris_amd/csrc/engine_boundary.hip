@@ -86,16 +86,8 @@ static int boundary_ready(fh_ctx* c, const char* who) {
     return FH_OK;
 }
 
-#define FH_FOR_NFN(NFNV, CALL)          \
-    switch (NFNV) {                     \
-        case 2: CALL(2); break;         \
-        case 3: CALL(3); break;         \
-        case 4: CALL(4); break;         \
-        case 6: CALL(6); break;         \
-        case 8: CALL(8); break;         \
-        case 9: CALL(9); break;         \
-        default: break;                 \
-    }
+// nodes per face of the ten element kinds (any other count: nothing is launched)
+constexpr int_list<2, 3, 4, 6, 8, 9> face_node_counts{};
 
 static int find_boundary_faces(fh_ctx* c) {
     BoundaryStore* b = store(c);
@@ -126,16 +118,18 @@ static int find_boundary_faces(fh_ctx* c) {
     b->scratch_bytes = (uint64_t)nf_all * 24 + std::max(sort_bytes, scan_bytes);
     const int grid = (int)((nf_all + 255u) / 256u);
     const int n = c->ei.n;
-#define CALL(NFNC) hipLaunchKernelGGL(k_face_keys<NFNC>, dim3(grid), dim3(256), 0, st, c->conn.p, n, t, nf_all, bits, keys_in.p, vals_in.p)
-    FH_FOR_NFN(t.nfn, CALL)
-#undef CALL
+    dispatch(face_node_counts, t.nfn, 0, [&](auto nfn) {
+        hipLaunchKernelGGL(k_face_keys<nfn()>, dim3(grid), dim3(256), 0, st, c->conn.p, n, t, nf_all, bits, keys_in.p, vals_in.p);
+        return 0;
+    });
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(tmp.p, sort_bytes, keys_in.p, keys.p, vals_in.p, vals.p, (int)nf_all, 0, 2 * bits, st));
     unsigned* flag = reinterpret_cast<unsigned*>(keys_in.p);
     unsigned* scan = flag + nf_all;
-#define CALL(NFNC) hipLaunchKernelGGL(k_face_unique<NFNC>, dim3(grid), dim3(256), 0, st, c->conn.p, n, t, nf_all, keys.p, vals.p, flag)
-    FH_FOR_NFN(t.nfn, CALL)
-#undef CALL
+    dispatch(face_node_counts, t.nfn, 0, [&](auto nfn) {
+        hipLaunchKernelGGL(k_face_unique<nfn()>, dim3(grid), dim3(256), 0, st, c->conn.p, n, t, nf_all, keys.p, vals.p, flag);
+        return 0;
+    });
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(tmp.p, scan_bytes, flag, scan, (int)nf_all, st));
     unsigned tail[2] = {0, 0};
@@ -147,9 +141,11 @@ static int find_boundary_faces(fh_ctx* c) {
     HIP_TRY(c, b->cells.alloc((size_t)F));
     HIP_TRY(c, b->local_faces.alloc((size_t)F));
     if (F) {
-#define CALL(NFNC) hipLaunchKernelGGL(k_face_emit<NFNC>, dim3(grid), dim3(256), 0, st, c->conn.p, n, t, nf_all, keys.p, vals.p, flag, scan, b->face_nodes.p, b->cells.p, b->local_faces.p)
-        FH_FOR_NFN(t.nfn, CALL)
-#undef CALL
+        dispatch(face_node_counts, t.nfn, 0, [&](auto nfn) {
+            hipLaunchKernelGGL(k_face_emit<nfn()>, dim3(grid), dim3(256), 0, st, c->conn.p, n, t, nf_all, keys.p, vals.p, flag, scan, b->face_nodes.p,
+                               b->cells.p, b->local_faces.p);
+            return 0;
+        });
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipStreamSynchronize(st));   // the scratch is released on return
@@ -329,14 +325,6 @@ static void fill_surface_args(fh_ctx* c, SurfaceArgs& a, const uint64_t* cells_d
     a.recs = c->bnd->recs.p;
 }
 
-#define FH_FOR_GEOM(CALL)                                        \
-    switch (c->ei.geom_kind) {                                   \
-        case FH_HEX8: CALL(3, 8); break;                         \
-        case FH_TET4: CALL(3, 4); break;                         \
-        case FH_QUAD4: CALL(2, 4); break;                        \
-        default: CALL(2, 3); break;                              \
-    }
-
 extern "C" {
 
 int fh_find_boundary_faces(fh_ctx* c, uint64_t* num_faces, uint32_t* nodes_per_face) {
@@ -456,9 +444,11 @@ int fh_assemble_surface_load_dev(fh_ctx* c, int load_kind, uint32_t sdim, const 
     a.data_mode = mode;
     a.out = out_dev;
     const unsigned grid = (unsigned)((b->adj_entries + 255) / 256);
-#define CALL(DV, NGV) hipLaunchKernelGGL((k_surface_load<DV, NGV>), dim3(grid), dim3(256), 0, c->stream, a, face_table(c->elem_kind).nfn, b->ent_node.p, b->ent.p, (size_t)b->adj_entries)
-    FH_FOR_GEOM(CALL)
-#undef CALL
+    dispatch_or_last(low_order_kinds, c->ei.geom_kind, [&](auto gk) {
+        hipLaunchKernelGGL((k_surface_load<kind_geom<gk()>::D, kind_geom<gk()>::NG>), dim3(grid), dim3(256), 0, c->stream, a, face_table(c->elem_kind).nfn,
+                           b->ent_node.p, b->ent.p, (size_t)b->adj_entries);
+        return 0;
+    });
     HIP_TRY(c, hipGetLastError());
     c->last_kernel = "k_surface_load";
     return FH_OK;
@@ -516,9 +506,10 @@ int fh_physical_face_quadrature_points_dev(fh_ctx* c, const uint64_t* cells_dev,
     SurfaceArgs a{};
     fill_surface_args(c, a, cells_dev, local_faces_dev, F, nq);
     const unsigned grid = (unsigned)((F * nq + 255) / 256);
-#define CALL(DV, NGV) hipLaunchKernelGGL((k_face_physical_points<DV, NGV>), dim3(grid), dim3(256), 0, c->stream, a, x_dev)
-    FH_FOR_GEOM(CALL)
-#undef CALL
+    dispatch_or_last(low_order_kinds, c->ei.geom_kind, [&](auto gk) {
+        hipLaunchKernelGGL((k_face_physical_points<kind_geom<gk()>::D, kind_geom<gk()>::NG>), dim3(grid), dim3(256), 0, c->stream, a, x_dev);
+        return 0;
+    });
     HIP_TRY(c, hipGetLastError());
     return FH_OK;
 }

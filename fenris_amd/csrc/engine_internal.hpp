@@ -26,6 +26,7 @@
 #include "hex8_rows.hpp"
 #include "vector_tiles.hpp"
 #include "device_common.hpp"
+#include "dispatch.hpp"
 #include "group_internal.hpp"
 #include "host_inputs.hpp"
 #include "host_pool.hpp"
@@ -603,32 +604,16 @@ struct NewtonScratch {
 };
 int newton_residual(fh_ctx* c, double alpha, double beta, const double* f_dev, const double* d_dev, NewtonScratch& ns, double* norm2);
 
-// dispatch over (element kind, operator kind) -> template instantiation
-#define FH_FOR_ELEM_OP(EKV, OPV, CALL)                                             \
-    switch (EKV) {                                                                 \
-        case FH_QUAD4: FH_FOR_OP(FH_QUAD4, OPV, CALL); break;                      \
-        case FH_HEX8: FH_FOR_OP(FH_HEX8, OPV, CALL); break;                        \
-        case FH_TET4: FH_FOR_OP(FH_TET4, OPV, CALL); break;                        \
-        case FH_HEX27: FH_FOR_OP(FH_HEX27, OPV, CALL); break;                      \
-        case FH_TRI3: FH_FOR_OP(FH_TRI3, OPV, CALL); break;                        \
-        case FH_TET10: FH_FOR_OP(FH_TET10, OPV, CALL); break;                      \
-        case FH_QUAD9: FH_FOR_OP(FH_QUAD9, OPV, CALL); break;                      \
-        case FH_TRI6: FH_FOR_OP(FH_TRI6, OPV, CALL); break;                        \
-        case FH_HEX20: FH_FOR_OP(FH_HEX20, OPV, CALL); break;                      \
-        case FH_TET20: FH_FOR_OP(FH_TET20, OPV, CALL); break;                      \
-        default: break;                                                            \
-    }
-#define FH_FOR_OP(EKC, OPV, CALL)                                   \
-    switch (OPV) {                                                  \
-        case FH_LAPLACE: CALL(EKC, FH_LAPLACE); break;              \
-        case FH_LINEAR_ELASTIC: CALL(EKC, FH_LINEAR_ELASTIC); break;\
-        case FH_NEO_HOOKEAN: CALL(EKC, FH_NEO_HOOKEAN); break;      \
-        case FH_STVK: CALL(EKC, FH_STVK); break;                    \
-        case FH_MASS_SCALAR: CALL(EKC, FH_MASS_SCALAR); break;      \
-        case FH_MASS_VECTOR: CALL(EKC, FH_MASS_VECTOR); break;      \
-        case FH_TENSOR: CALL(EKC, FH_TENSOR); break;                \
-        default: break;                                             \
-    }
+// One launch with `lds` bytes of dynamic LDS: more than 48 KB has to be allowed per kernel first.  Which instantiation `kern` is comes from
+// dispatch.hpp.
+template <class... P, class... A>
+int launch_lds(fh_ctx* c, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, A&&... args) {
+    if (lds > 48 * 1024)
+        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, std::forward<A>(args)...);
+    HIP_TRY(c, hipGetLastError());
+    return FH_OK;
+}
 
 // ---- rule-set tables: the groups of rules that share points and weights, one pass each
 int rs_stage(fh_ctx* c, int g);

@@ -4,25 +4,10 @@
 template <int EK, int OP>
 int launch_matrix(fh_ctx* c, KArgs& a, int mode, size_t lds_bytes, int grid) {
     if (grid <= 0) return FH_OK;   // nothing to do (an element mask without an active element): a launch of zero workgroups is an error
-    hipStream_t st = c->stream;
-#define FH_LAUNCH(M)                                                                                              \
-    do {                                                                                                          \
-        auto kern = k_assemble_matrix<EK, OP, M>;                                                                 \
-        if (lds_bytes > 48 * 1024)                                                                                \
-            HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                           (int)lds_bytes));                                                       \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, st, a);                                        \
-    } while (0)
-    switch (mode) {
-        case MODE_ATOMIC: FH_LAUNCH(MODE_ATOMIC); break;
-        case MODE_COLORED: FH_LAUNCH(MODE_COLORED); break;
-        case MODE_GATHER: FH_LAUNCH(MODE_GATHER); break;
-        case MODE_DUMP: FH_LAUNCH(MODE_DUMP); break;
-        default: return c->fail(FH_BAD_ARGUMENT, "bad scatter mode");
-    }
-#undef FH_LAUNCH
-    HIP_TRY(c, hipGetLastError());
-    return FH_OK;
+    const int rc = dispatch(int_list<MODE_ATOMIC, MODE_COLORED, MODE_GATHER, MODE_DUMP>{}, mode, -1, [&](auto m) {
+        return launch_lds(c, k_assemble_matrix<EK, OP, m()>, dim3(grid), dim3(256), lds_bytes, c->stream, a);
+    });
+    return rc < 0 ? c->fail(FH_BAD_ARGUMENT, "bad scatter mode") : rc;
 }
 
 template <int EK, int OP>
@@ -36,11 +21,8 @@ size_t layout_bytes(int what, int nq, int ub, int acc, int nb, bool gather, int 
 
 
 size_t layout_bytes_dyn(int ek, int op, int what, int nq, int ub, int acc, int nb, bool gather, int mb, int fast, int nc_row) {
-    size_t r = 0;
-#define CALL(EKC, OPC) r = layout_bytes<EKC, OPC>(what, nq, ub, acc, nb, gather, mb, fast, nc_row)
-    FH_FOR_ELEM_OP(ek, op, CALL)
-#undef CALL
-    return r;
+    return dispatch(all_kinds, ek, all_ops, op, (size_t)0,
+                    [&](auto ekc, auto opc) { return layout_bytes<ekc(), opc()>(what, nq, ub, acc, nb, gather, mb, fast, nc_row); });
 }
 
 
@@ -51,6 +33,12 @@ int choose_epb(fh_ctx* c, int what, size_t lds_target) {
         if (b <= lds_target) best = epb; else break;
     }
     return best;
+}
+
+// (an element kind or operator outside the lists: nothing is launched)
+static int launch_matrix_dyn(fh_ctx* c, KArgs& a, int mode, size_t lds, int grid) {
+    return dispatch(all_kinds, c->elem_kind, all_ops, c->op, (int)FH_OK,
+                    [&](auto ek, auto op) { return launch_matrix<ek(), op()>(c, a, mode, lds, grid); });
 }
 
 template <int OP, bool ELEMPAR = false>
@@ -68,13 +56,9 @@ int launch_rows_tet4(fh_ctx* c, KArgs& a, const RowTablesS& T) {
     // (FENRIS_HIP_PIPE_GRID: tests force many positions per workgroup on small meshes)
     const int grid = std::max(1, std::min(c->npos_gen, c->env_int("FENRIS_HIP_PIPE_GRID", dev_cus * c->env_int("FENRIS_HIP_PIPE_WGS_PER_CU", per_cu))));
     auto kern = a.trace ? k_gather_rows_tet4<OP, ELEMPAR, true> : k_gather_rows_tet4<OP, ELEMPAR>;   // FENRIS_HIP_TRACE: instrumented twin
-    if (lds > 48 * 1024)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (c->env("FENRIS_HIP_VERBOSE"))
         std::fprintf(stderr, "[fenris_hip] row-owner gather (Tet4): lds=%zu B wgs/cu=%d grid=%d\n", lds, per_cu, grid);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c->stream, a, T);
-    HIP_TRY(c, hipGetLastError());
-    return FH_OK;
+    return launch_lds(c, kern, dim3(grid), dim3(256), lds, c->stream, a, T);
 }
 
 template <int EK, int OP, int QC, int JT>
@@ -117,13 +101,9 @@ int launch_pipelined_j(fh_ctx* c, KArgs& a, const PipeTables& T) {
         } else if (fullq)
             kern = k_gather_pipelined<EK, OP, QC, JT, false, true>;
     }
-    if (lds > 48 * 1024)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (c->env("FENRIS_HIP_VERBOSE"))
         std::fprintf(stderr, "[fenris_hip] pipelined gather: QC=%d JT=%d lds=%zu B wgs/cu=%d grid=%d\n", QC, JT, lds, wgs, grid);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c->stream, a, T);
-    HIP_TRY(c, hipGetLastError());
-    return FH_OK;
+    return launch_lds(c, kern, dim3(grid), dim3(256), lds, c->stream, a, T);
 }
 
 template <int EK, int OP, int QC>
@@ -252,11 +232,7 @@ int element_matrices_enqueue(fh_ctx* c, uint64_t first, uint64_t count, double* 
     const size_t lds = layout_bytes_dyn(c->elem_kind, c->op, WHAT_MATRIX, c->nq, a.ub, 0, 0, false, 0, a.fast);
     if (lds > LDS_LIMIT) return c->fail(FH_UNSUPPORTED, "quadrature rule too large for LDS staging");
     const int grid = (int)((count + a.epb - 1) / a.epb);
-    int rc = FH_OK;
-#define CALL(EKC, OPC) rc = launch_matrix<EKC, OPC>(c, a, MODE_DUMP, lds, grid)
-    FH_FOR_ELEM_OP(c->elem_kind, c->op, CALL)
-#undef CALL
-    return rc;
+    return launch_matrix_dyn(c, a, MODE_DUMP, lds, grid);
 }
 
 // Which kernel the general positions (those not in the affine class) of an FH_SCATTER_GATHER assembly run on: ONE rule, read by the dispatch below
@@ -440,10 +416,7 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
             return launch_pipelined(c, a, T, 0, 0);
         }
         c->last_kernel += "k_assemble_matrix<gather>";
-#define CALL(EKC, OPC) rc = launch_matrix<EKC, OPC>(c, a, MODE_GATHER, lds, c->nblk)
-        FH_FOR_ELEM_OP(c->elem_kind, c->op, CALL)
-#undef CALL
-        return rc;
+        return launch_matrix_dyn(c, a, MODE_GATHER, lds, c->nblk);
     }
     if (c->row_hi >= 0) return c->fail(FH_UNSUPPORTED, "fh_assemble_matrix: a row range needs FH_SCATTER_GATHER");
     if (overwrite) HIP_TRY(c, hipMemsetAsync(values_dev, 0, sizeof(double) * nnz, c->stream));
@@ -465,10 +438,7 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
         if (a.work_end == 0) return FH_OK;
         const int grid = (int)((a.work_end + a.epb - 1) / a.epb);
         c->last_kernel = "k_assemble_matrix<atomic>";
-#define CALL(EKC, OPC) rc = launch_matrix<EKC, OPC>(c, a, MODE_ATOMIC, lds, grid)
-        FH_FOR_ELEM_OP(c->elem_kind, c->op, CALL)
-#undef CALL
-        return rc;
+        return launch_matrix_dyn(c, a, MODE_ATOMIC, lds, grid);
     }
     if (mode == FH_SCATTER_COLORED) {
         if (!c->has_colors) return c->fail(FH_INVALID_STATE, "FH_SCATTER_COLORED: call fh_color or fh_set_colors first");
@@ -480,9 +450,7 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
             const long long cntc = a.work_end - a.work_begin;
             if (cntc <= 0) continue;
             const int grid = (int)((cntc + a.epb - 1) / a.epb);
-#define CALL(EKC, OPC) rc = launch_matrix<EKC, OPC>(c, a, MODE_COLORED, lds, grid)
-            FH_FOR_ELEM_OP(c->elem_kind, c->op, CALL)
-#undef CALL
+            rc = launch_matrix_dyn(c, a, MODE_COLORED, lds, grid);
             if (rc) return rc;
         }
         return FH_OK;

@@ -650,17 +650,11 @@ int build_partition(fh_ctx* c) {
                 HIP_TRY(c, rec.alloc((size_t)npos * c->p_rw));
                 HIP_TRY(c, conn.alloc((size_t)npos * c->p_cs));
                 HIP_TRY(c, elem.alloc((size_t)npos * us));
-#define PT_LAUNCH(NGV)                                                                                                           \
-    hipLaunchKernelGGL(k_build_pipe_tables<NGV>, dim3(nchains), dim3(64), 0, c->stream, order_d.p, chain_d.p, c->gt_hdr.p,        \
-                       c->gt_elems.p, c->gt_ent.p, c->gt_pos.p, noff_d, c->conn.p, n, c->p_cs, ms, nb_target, us, c->p_rw,     \
-                       rec.p, conn.p, elem.p, by_parity)
-                switch (c->ei.ng) {
-                    case 3: PT_LAUNCH(3); break;
-                    case 4: PT_LAUNCH(4); break;
-                    case 8: PT_LAUNCH(8); break;
-                    default: break;
-                }
-#undef PT_LAUNCH
+                dispatch(int_list<3, 4, 8>{}, c->ei.ng, 0, [&](auto ng) {   // (any other count of geometry nodes: nothing is launched)
+                    hipLaunchKernelGGL(k_build_pipe_tables<ng()>, dim3(nchains), dim3(64), 0, c->stream, order_d.p, chain_d.p, c->gt_hdr.p, c->gt_elems.p,
+                                       c->gt_ent.p, c->gt_pos.p, noff_d, c->conn.p, n, c->p_cs, ms, nb_target, us, c->p_rw, rec.p, conn.p, elem.p, by_parity);
+                    return 0;
+                });
                 HIP_TRY(c, hipGetLastError());
                 HIP_TRY(c, hipStreamSynchronize(c->stream));  // the callers' order / chain arrays are released after the return
                 return FH_OK;

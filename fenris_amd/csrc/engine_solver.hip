@@ -85,21 +85,12 @@ static int spmv_launch(fh_ctx* c, const double* vals, const double* x, double* y
         if (scratch->n < (size_t)grid) HIP_TRY(c, scratch->alloc((size_t)grid));
         wg_partial = scratch->p;
     }
-    if (half) {
-        switch (c->S()) {
-            case 1: hipLaunchKernelGGL((k_spmv_blocked_half<1>), dim3(grid), dim3(256), 0, c->stream, N, c->noff.p, c->ncols.p, vals, x, y, wg_partial); break;
-            case 2: hipLaunchKernelGGL((k_spmv_blocked_half<2>), dim3(grid), dim3(256), 0, c->stream, N, c->noff.p, c->ncols.p, vals, x, y, wg_partial); break;
-            default:
-                hipLaunchKernelGGL((k_spmv_blocked_half<3>), dim3(grid), dim3(256), 0, c->stream, N, c->noff.p, c->ncols.p, vals, x, y, wg_partial);
-                break;
-        }
-    } else {
-        switch (c->S()) {
-            case 1: hipLaunchKernelGGL((k_spmv_blocked<1>), dim3(grid), dim3(256), 0, c->stream, N, c->noff.p, c->ncols.p, vals, x, y, wg_partial); break;
-            case 2: hipLaunchKernelGGL((k_spmv_blocked<2>), dim3(grid), dim3(256), 0, c->stream, N, c->noff.p, c->ncols.p, vals, x, y, wg_partial); break;
-            default: hipLaunchKernelGGL((k_spmv_blocked<3>), dim3(grid), dim3(256), 0, c->stream, N, c->noff.p, c->ncols.p, vals, x, y, wg_partial); break;
-        }
-    }
+    c->last_kernel = half ? "k_spmv_blocked_half" : "k_spmv_blocked";
+    dispatch_or_last(solution_dims, c->S(), [&](auto s) {
+        auto kern = half ? k_spmv_blocked_half<s()> : k_spmv_blocked<s()>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, c->stream, N, c->noff.p, c->ncols.p, vals, x, y, wg_partial);
+        return 0;
+    });
     HIP_TRY(c, hipGetLastError());
     if (partial) {
         hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(partials), dim3(256), 0, c->stream, wg_partial, (long long)grid, partial);
@@ -121,7 +112,6 @@ int fh_spmv_dev(fh_ctx* c, const double* values_dev, const double* x_dev, double
     if (rc) return rc;
     if (!values_dev || !x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, "fh_spmv: null argument");
     if (c->N == 0) return FH_OK;
-    c->last_kernel = (c->max_row <= 32 && !c->env("FENRIS_HIP_SPMV_WAVE_PER_NODE")) ? "k_spmv_blocked_half" : "k_spmv_blocked";
     return spmv_launch(c, values_dev, x_dev, y_dev, nullptr, 0, nullptr);
 }
 
@@ -231,14 +221,12 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
     if (preconditioner == FH_PRECOND_JACOBI) {
         HIP_TRY(c, dinv.alloc(n));
         const int g = (n + 255) / 256;
-        switch (S) {
-            case 1: hipLaunchKernelGGL((k_inverse_diagonal<1>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
-            case 2: hipLaunchKernelGGL((k_inverse_diagonal<2>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
-            default: hipLaunchKernelGGL((k_inverse_diagonal<3>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p); break;
-        }
+        dispatch_or_last(solution_dims, S, [&](auto s) {
+            hipLaunchKernelGGL((k_inverse_diagonal<s()>), dim3(g), dim3(256), 0, c->stream, (int)c->N, c->noff.p, c->ncols.p, values_dev, dinv.p);
+            return 0;
+        });
         HIP_TRY(c, hipGetLastError());
     }
-    c->last_kernel = (c->max_row <= 32 && !c->env("FENRIS_HIP_SPMV_WAVE_PER_NODE")) ? "k_spmv_blocked_half" : "k_spmv_blocked";
     return cg_run(c, n, b_dev, x_dev, dinv.p, partial, wg_partial, rel_tol, max_iter, num_iterations,
                   [&](const double* in, double* out, int* ranges) {
                       if (!ranges) return spmv_launch(c, values_dev, in, out, nullptr, 0, nullptr);
@@ -398,12 +386,15 @@ static int error_squared(fh_ctx* c, int which, uint32_t sdim, const double* uh_d
     const int grid = (int)std::min<long long>(2048, (total + 255) / 256);
     DevBuf<double> partial;
     HIP_TRY(c, partial.alloc(grid));
-#define ERRK(DD, SS, WW) hipLaunchKernelGGL((k_error_squared<DD, SS, WW>), dim3(grid), dim3(256), 0, c->stream, a, sa, uh_dev, exact_dev, partial.p)
-    if (D == 2 && sdim == 1) { if (which) ERRK(2, 1, 1); else ERRK(2, 1, 0); }
-    else if (D == 2)         { if (which) ERRK(2, 2, 1); else ERRK(2, 2, 0); }
-    else if (sdim == 1)      { if (which) ERRK(3, 1, 1); else ERRK(3, 1, 0); }
-    else                     { if (which) ERRK(3, 3, 1); else ERRK(3, 3, 0); }
-#undef ERRK
+    dispatch_or_last(int_list<2, 3>{}, D, [&](auto d) {
+        return dispatch_bool(sdim == 1, [&](auto scalar) {
+            return dispatch_bool(which != 0, [&](auto w) {
+                hipLaunchKernelGGL((k_error_squared<d(), scalar() ? 1 : d(), w() ? 1 : 0>), dim3(grid), dim3(256), 0, c->stream, a, sa, uh_dev, exact_dev,
+                                   partial.p);
+                return 0;
+            });
+        });
+    });
     HIP_TRY(c, hipGetLastError());
     rc = sum_partials(c, partial.p, grid, 1, out);
     if (rc) return rc;

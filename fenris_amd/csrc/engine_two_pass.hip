@@ -57,23 +57,17 @@ int launch_rows_t(fh_ctx* c, int layout, hipStream_t st, const PT* pos, const un
         tri_kernel kt = nullptr;
         const int n = (int)c->ei.n;
         if (layout == 2 && n == 27) kt = abl ? k_rows_from_tri<27, false, PT, true> : k_rows_from_tri<27, false, PT, false>;
-        else if (layout == 1 && n == 27) kt = k_rows_from_tri<27, true, PT>;
-        else if (layout == 1 && n == 20) kt = k_rows_from_tri<20, true, PT>;
-        else if (layout == 1 && n == 10) kt = k_rows_from_tri<10, true, PT>;
-        else if (layout == 1 && n == 8) kt = k_rows_from_tri<8, true, PT>;
-        else if (layout == 1 && n == 4) kt = k_rows_from_tri<4, true, PT>;
+        else if (layout == 1)
+            kt = dispatch(int_list<27, 20, 10, 8, 4>{}, n, kt, [](auto nn) -> tri_kernel { return k_rows_from_tri<nn(), true, PT>; });
         if (!kt) return c->fail(FH_HIP_ERROR, "two-pass gather: no triangle kernel for this element");
         overwrite = (overwrite ? 1 : 0) | (abl << 8);
-        if (lds > 48 * 1024) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         // consecutive nodes per wavefront: 4, more when the grid would pass its cap (small grids in the tests: FENRIS_HIP_TWO_PASS_GRID);
         // nodes per wavefront slot of an XCD's chunk: 1 024 (a chunk = 4 096 nodes; 0 = workgroups in launch order)
         int npw = std::max(1, c->env_int("FENRIS_HIP_TWO_PASS_NODES_PER_WAVE", 4));
         while ((long long)grid_cap * wpb * npw < count) npw *= 2;
         const int grid = std::max(1, (count + wpb * npw - 1) / (wpb * npw));
-        hipLaunchKernelGGL(kt, dim3(grid), dim3(threads), lds, st, c->noff.p, adj_off, adj, pos, c->ke_dense.p, values_dev, overwrite, (int)max_row,
-                           node_list, count, npw, std::max(0, c->env_int("FENRIS_HIP_TWO_PASS_XCD_CHUNK", 1024) / npw));
-        HIP_TRY(c, hipGetLastError());
-        return FH_OK;
+        return launch_lds(c, kt, dim3(grid), dim3(threads), lds, st, c->noff.p, adj_off, adj, pos, c->ke_dense.p, values_dev, overwrite, (int)max_row,
+                          node_list, count, npw, std::max(0, c->env_int("FENRIS_HIP_TWO_PASS_XCD_CHUNK", 1024) / npw));
     }
     void (*kern)(int, int, const unsigned*, const unsigned*, const unsigned*, const PT*, const double*, double*, int, int, const int*, int) =
         k_rows_from_dense<SS, PT>;
@@ -83,26 +77,19 @@ int launch_rows_t(fh_ctx* c, int layout, hipStream_t st, const PT* pos, const un
         else if (ld_ <= 16) kern = k_rows_from_dense_small<SS, PT, 16>;
         else if (ld_ <= 32) kern = k_rows_from_dense_small<SS, PT, 32>;
     }
-    if (lds > 48 * 1024)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int grid = std::max(1, std::min((count + wpb - 1) / wpb, grid_cap));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, (int)c->N, c->ei.n, c->noff.p, adj_off, adj, pos, c->ke_dense.p, values_dev,
-                       overwrite, (int)max_row, node_list, count);
-    HIP_TRY(c, hipGetLastError());
-    return FH_OK;
+    return launch_lds(c, kern, dim3(grid), dim3(threads), lds, st, (int)c->N, c->ei.n, c->noff.p, adj_off, adj, pos, c->ke_dense.p, values_dev, overwrite,
+                      (int)max_row, node_list, count);
 }
 
 int launch_rows(fh_ctx* c, int layout, hipStream_t st, const unsigned* adj_off, const unsigned* adj, double* values_dev, int overwrite,
                 unsigned max_row, const int* node_list, int count, int threads, int grid_cap) {
-    const int S = c->S();
-    const bool wide = max_row >= 256;
-#define ROWS(SS)                                                                                                                             \
-    (wide ? launch_rows_t<SS, unsigned short>(c, layout, st, c->tp_pos16.p, adj_off, adj, values_dev, overwrite, max_row, node_list, count, threads, grid_cap) \
-          : launch_rows_t<SS, unsigned char>(c, layout, st, c->tp_pos8.p, adj_off, adj, values_dev, overwrite, max_row, node_list, count, threads, grid_cap))
-    if (S == 1) return ROWS(1);
-    if (S == 2) return ROWS(2);
-    return ROWS(3);
-#undef ROWS
+    return dispatch_or_last(solution_dims, c->S(), [&](auto s) {
+        auto rows = [&](const auto* pos) {
+            return launch_rows_t<s()>(c, layout, st, pos, adj_off, adj, values_dev, overwrite, max_row, node_list, count, threads, grid_cap);
+        };
+        return max_row >= 256 ? rows(c->tp_pos16.p) : rows(c->tp_pos8.p);   // the column slots in 16 or 8 bits
+    });
 }
 
 }  // namespace

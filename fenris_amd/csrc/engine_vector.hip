@@ -3,12 +3,7 @@
 
 template <int EK, int OP>
 static int launch_vector(fh_ctx* c, KArgs& a, size_t lds, int grid) {
-    auto kern = k_assemble_vector<EK, OP>;
-    if (lds > 48 * 1024)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c->stream, a);
-    HIP_TRY(c, hipGetLastError());
-    return FH_OK;
+    return launch_lds(c, k_assemble_vector<EK, OP>, dim3(grid), dim3(256), lds, c->stream, a);
 }
 template <int EK, int OP, int NT>
 static int launch_vector_stream_nt(fh_ctx* c, KArgs& a) {
@@ -20,12 +15,7 @@ static int launch_vector_stream_nt(fh_ctx* c, KArgs& a) {
     const long long nbatch = (a.work_end - a.work_begin + EPB - 1) / EPB;
     const int per_cu = std::max(1, (int)std::min<size_t>(c->env_int("FENRIS_HIP_VEC_WGS_PER_CU", 3), (LDS_LIMIT - 512) / std::max<size_t>(lds, 1)));
     const int grid = std::max(1, (int)std::min<long long>(nbatch, (long long)c->env_int("FENRIS_HIP_PIPE_GRID", dev_cus * per_cu)));   // (tests force many batches per workgroup)
-    auto kern = k_assemble_vector_stream<EK, OP, NT>;
-    if (lds > 48 * 1024)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, a);
-    HIP_TRY(c, hipGetLastError());
-    return FH_OK;
+    return launch_lds(c, k_assemble_vector_stream<EK, OP, NT>, dim3(grid), dim3(NT), lds, c->stream, a);
 }
 template <int EK, int OP>
 static int launch_vector_stream(fh_ctx* c, KArgs& a) {
@@ -39,12 +29,7 @@ static int launch_vector_stream(fh_ctx* c, KArgs& a) {
 }
 template <int EK, int OP>
 static int launch_scalar(fh_ctx* c, KArgs& a, size_t lds, int grid) {
-    auto kern = k_assemble_scalar<EK, OP>;
-    if (lds > 48 * 1024)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c->stream, a);
-    HIP_TRY(c, hipGetLastError());
-    return FH_OK;
+    return launch_lds(c, k_assemble_scalar<EK, OP>, dim3(grid), dim3(256), lds, c->stream, a);
 }
 
 // register-resident element pass (element_pass.hpp): one thread per element of the small iso-parametric kinds, operators with a
@@ -52,42 +37,35 @@ static int launch_scalar(fh_ctx* c, KArgs& a, size_t lds, int grid) {
 template <int WHAT>
 static int launch_element_pass(fh_ctx* c, KArgs& a) {
     const int grid = (int)((a.num_elements + 255) / 256);
-    int rs = -1;
-#define EP_OP(EKC)                                                                                                          \
-    switch (c->op) {                                                                                                        \
-        case FH_LAPLACE: hipLaunchKernelGGL((k_element_pass<EKC, FH_LAPLACE, WHAT>), dim3(grid), dim3(256), 0, c->stream, a); rs = FH_OK; break; \
-        case FH_LINEAR_ELASTIC: hipLaunchKernelGGL((k_element_pass<EKC, FH_LINEAR_ELASTIC, WHAT>), dim3(grid), dim3(256), 0, c->stream, a); rs = FH_OK; break; \
-        case FH_NEO_HOOKEAN: hipLaunchKernelGGL((k_element_pass<EKC, FH_NEO_HOOKEAN, WHAT>), dim3(grid), dim3(256), 0, c->stream, a); rs = FH_OK; break; \
-        case FH_STVK: hipLaunchKernelGGL((k_element_pass<EKC, FH_STVK, WHAT>), dim3(grid), dim3(256), 0, c->stream, a); rs = FH_OK; break; \
-        default: break;                                                                                                     \
-    }
-    switch (c->elem_kind) {
-        case FH_QUAD4: EP_OP(FH_QUAD4) break;
-        case FH_TRI3: EP_OP(FH_TRI3) break;
-        case FH_TET4: EP_OP(FH_TET4) break;
-        case FH_HEX8: EP_OP(FH_HEX8) break;
-        default: break;
-    }
-#undef EP_OP
-    if (rs == FH_OK) HIP_TRY(c, hipGetLastError());
-    return rs;
+    return dispatch(low_order_kinds, c->elem_kind, elliptic_ops, c->op, -1, [&](auto ek, auto op) {
+        hipLaunchKernelGGL((k_element_pass<ek(), op(), WHAT>), dim3(grid), dim3(256), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+        return (int)FH_OK;
+    });
 }
 static int launch_vector_from_elements_soa(fh_ctx* c, int sdim, const double* fe, double* out_dev, const unsigned* adj_off = nullptr,
                                            const unsigned* adj = nullptr, const SourceG* scaled = nullptr) {
     const int grid = (int)(((long long)c->N + 255) / 256);
     if (!adj_off) { adj_off = c->n2e_off.p; adj = c->n2e.p; }
-    if (scaled) {   // scalar entries, sdim components g[c] sum
-        if (sdim == 1) hipLaunchKernelGGL((k_vector_from_elements_soa<1, 1>), dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->ei.n, (long long)c->E, adj_off, adj, fe, out_dev, *scaled);
-        else if (sdim == 2) hipLaunchKernelGGL((k_vector_from_elements_soa<1, 2>), dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->ei.n, (long long)c->E, adj_off, adj, fe, out_dev, *scaled);
-        else hipLaunchKernelGGL((k_vector_from_elements_soa<1, 3>), dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->ei.n, (long long)c->E, adj_off, adj, fe, out_dev, *scaled);
+    return dispatch_or_last(solution_dims, sdim, [&](auto s) {
+        if (scaled)   // scalar entries, sdim components g[c] sum
+            hipLaunchKernelGGL((k_vector_from_elements_soa<1, s()>), dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->ei.n, (long long)c->E, adj_off, adj, fe,
+                               out_dev, *scaled);
+        else
+            hipLaunchKernelGGL((k_vector_from_elements_soa<s(), 0>), dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->ei.n, (long long)c->E, adj_off, adj, fe,
+                               out_dev);
         HIP_TRY(c, hipGetLastError());
-        return FH_OK;
-    }
-    if (sdim == 1) hipLaunchKernelGGL((k_vector_from_elements_soa<1, 0>), dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->ei.n, (long long)c->E, adj_off, adj, fe, out_dev);
-    else if (sdim == 2) hipLaunchKernelGGL((k_vector_from_elements_soa<2, 0>), dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->ei.n, (long long)c->E, adj_off, adj, fe, out_dev);
-    else hipLaunchKernelGGL((k_vector_from_elements_soa<3, 0>), dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->ei.n, (long long)c->E, adj_off, adj, fe, out_dev);
-    HIP_TRY(c, hipGetLastError());
-    return FH_OK;
+        return (int)FH_OK;
+    });
+}
+// ... of the element vectors in c->fe_scratch, one thread per row over the pattern's adjacency
+static int launch_vector_from_elements(fh_ctx* c, int sdim, double* out_dev) {
+    const int grid = (int)(((long long)c->N * sdim + 255) / 256);
+    return dispatch_or_last(solution_dims, sdim, [&](auto s) {
+        hipLaunchKernelGGL(k_vector_from_elements<s()>, dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->n2e_off.p, c->n2e.p, c->fe_scratch.p, out_dev);
+        HIP_TRY(c, hipGetLastError());
+        return (int)FH_OK;
+    });
 }
 static bool element_pass_covers(const fh_ctx* c) {
     return !c->ragged && !c->env("FENRIS_HIP_NO_ELEMENT_PASS") &&
@@ -201,17 +179,10 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
             if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
             a.ke_out = c->fe_scratch.p;
         }
-        int rs = -1;
-#define CALL(EKC, OPC) rs = launch_vector_stream<EKC, OPC>(c, a)
-        FH_FOR_ELEM_OP(c->elem_kind, c->op, CALL)
-#undef CALL
+        const int rs = dispatch(all_kinds, c->elem_kind, all_ops, c->op, -1, [&](auto ek, auto op) { return launch_vector_stream<ek(), op()>(c, a); });
         if (rs == FH_OK && two_pass) {
-            const long long rows = (long long)c->N * c->S();
-            const int grid = (int)((rows + 255) / 256);
-            if (c->S() == 1) hipLaunchKernelGGL(k_vector_from_elements<1>, dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->n2e_off.p, c->n2e.p, c->fe_scratch.p, out_dev);
-            else if (c->S() == 2) hipLaunchKernelGGL(k_vector_from_elements<2>, dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->n2e_off.p, c->n2e.p, c->fe_scratch.p, out_dev);
-            else hipLaunchKernelGGL(k_vector_from_elements<3>, dim3(grid), dim3(256), 0, c->stream, (int)c->N, c->n2e_off.p, c->n2e.p, c->fe_scratch.p, out_dev);
-            HIP_TRY(c, hipGetLastError());
+            rc = launch_vector_from_elements(c, c->S(), out_dev);
+            if (rc) return rc;
         }
         if (rs == FH_OK) {
             c->last_kernel = two_pass ? "k_assemble_vector_stream + k_vector_from_elements" : "k_assemble_vector_stream";
@@ -226,9 +197,7 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
     const size_t lds = layout_bytes_dyn(c->elem_kind, c->op, WHAT_VECTOR, c->nq, a.ub, 0, 0, false);
     if (lds > LDS_LIMIT) return c->fail(FH_UNSUPPORTED, "quadrature rule too large for LDS staging");
     const int grid = (int)((a.work_end + a.epb - 1) / a.epb);
-#define CALL(EKC, OPC) rc = launch_vector<EKC, OPC>(c, a, lds, grid)
-    FH_FOR_ELEM_OP(c->elem_kind, c->op, CALL)
-#undef CALL
+    rc = dispatch(all_kinds, c->elem_kind, all_ops, c->op, (int)FH_OK, [&](auto ek, auto op) { return launch_vector<ek(), op()>(c, a, lds, grid); });
     if (rc) return rc;
     return read_status(c, failed);
 }
@@ -326,17 +295,15 @@ int fh_assemble_source_vector_dev(fh_ctx* c, uint32_t sdim, const double* g, con
         const int ge = (int)((c->E + 255) / 256);
         double* fe = c->fe_scratch.p;
         const bool fact = !values_dev;   // GravitySource: scalar element entries, the node sum multiplies by g (element_pass.hpp)
-#define SRC(DV, SV, NV)                                                                                                                     \
-        do {                                                                                                                                \
-            if (fact) hipLaunchKernelGGL((k_source_elements<DV, SV, NV, true>), dim3(ge), dim3(256), 0, c->stream, a, gval, sa.values, fe); \
-            else hipLaunchKernelGGL((k_source_elements<DV, SV, NV, false>), dim3(ge), dim3(256), 0, c->stream, a, gval, sa.values, fe);     \
-        } while (0)
-        const int n = c->ei.n;
-        if (D == 2 && n == 4) { if (sdim == 1) SRC(2, 1, 4); else SRC(2, 2, 4); }
-        else if (D == 2) { if (sdim == 1) SRC(2, 1, 3); else SRC(2, 2, 3); }
-        else if (n == 8) { if (sdim == 1) SRC(3, 1, 8); else SRC(3, 3, 8); }
-        else { if (sdim == 1) SRC(3, 1, 4); else SRC(3, 3, 4); }
-#undef SRC
+        dispatch(low_order_kinds, c->elem_kind, 0, [&](auto ek) {   // (element_pass_covers: one of these)
+            constexpr int DV = ElemT<ek()>::D, NV = ElemT<ek()>::N;
+            return dispatch_bool(sdim == 1, [&](auto scalar) {
+                return dispatch_bool(fact, [&](auto fc) {
+                    hipLaunchKernelGGL((k_source_elements<DV, scalar() ? 1 : DV, NV, fc()>), dim3(ge), dim3(256), 0, c->stream, a, gval, sa.values, fe);
+                    return 0;
+                });
+            });
+        });
         HIP_TRY(c, hipGetLastError());
         c->last_kernel = "k_source_elements + k_vector_from_elements_soa";
         return launch_vector_from_elements_soa(c, (int)sdim, fe, out_dev, adj_off, adj, fact ? &gval : nullptr);
@@ -351,18 +318,16 @@ int fh_assemble_source_vector_dev(fh_ctx* c, uint32_t sdim, const double* g, con
     const size_t lds = sizeof(double) * (size_t)a.epb * c->nq;
     const int grid = (int)((a.work_end + a.epb - 1) / a.epb);
     c->last_kernel = "k_assemble_source";
-    if (D == 2 && sdim == 1) hipLaunchKernelGGL((k_assemble_source<2, 1>), dim3(grid), dim3(256), lds, c->stream, a, sa);
-    else if (D == 2) hipLaunchKernelGGL((k_assemble_source<2, 2>), dim3(grid), dim3(256), lds, c->stream, a, sa);
-    else if (sdim == 1) hipLaunchKernelGGL((k_assemble_source<3, 1>), dim3(grid), dim3(256), lds, c->stream, a, sa);
-    else hipLaunchKernelGGL((k_assemble_source<3, 3>), dim3(grid), dim3(256), lds, c->stream, a, sa);
+    dispatch_or_last(int_list<2, 3>{}, D, [&](auto d) {
+        return dispatch_bool(sdim == 1, [&](auto scalar) {
+            hipLaunchKernelGGL((k_assemble_source<d(), scalar() ? 1 : d()>), dim3(grid), dim3(256), lds, c->stream, a, sa);
+            return 0;
+        });
+    });
     HIP_TRY(c, hipGetLastError());
     if (two_pass) {
-        const long long rows = (long long)c->N * sdim;
-        const int g2 = (int)((rows + 255) / 256);
-        if (sdim == 1) hipLaunchKernelGGL(k_vector_from_elements<1>, dim3(g2), dim3(256), 0, c->stream, (int)c->N, c->n2e_off.p, c->n2e.p, c->fe_scratch.p, out_dev);
-        else if (sdim == 2) hipLaunchKernelGGL(k_vector_from_elements<2>, dim3(g2), dim3(256), 0, c->stream, (int)c->N, c->n2e_off.p, c->n2e.p, c->fe_scratch.p, out_dev);
-        else hipLaunchKernelGGL(k_vector_from_elements<3>, dim3(g2), dim3(256), 0, c->stream, (int)c->N, c->n2e_off.p, c->n2e.p, c->fe_scratch.p, out_dev);
-        HIP_TRY(c, hipGetLastError());
+        rc = launch_vector_from_elements(c, (int)sdim, out_dev);
+        if (rc) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // gd is released on return
     return FH_OK;
@@ -506,9 +471,7 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
     HIP_TRY(c, partial.alloc((size_t)grid));
     a.scalar_out = partial.p;
     c->last_kernel = "k_assemble_scalar";
-#define CALL(EKC, OPC) rc = launch_scalar<EKC, OPC>(c, a, lds, grid)
-    FH_FOR_ELEM_OP(c->elem_kind, c->op, CALL)
-#undef CALL
+    rc = dispatch(all_kinds, c->elem_kind, all_ops, c->op, (int)FH_OK, [&](auto ek, auto op) { return launch_scalar<ek(), op()>(c, a, lds, grid); });
     if (rc) return rc;
     std::vector<double> h((size_t)grid);
     HIP_TRY(c, hipMemcpyAsync(h.data(), partial.p, sizeof(double) * grid, hipMemcpyDeviceToHost, c->stream));
@@ -600,16 +563,16 @@ static int mf_tiles_pass(fh_ctx* c, KArgs& a, const double* xin, bool* done) {
 
 // the per-element kernels of the map (solver_kernels.hpp) for the context's operator: the element diagonals (x null) or the element vectors
 // of x into fe[a][e][c]
-template <int OP>
 static void mf_elements_launch(fh_ctx* c, const KArgs& a, const unsigned char* active, const double* x, double* fe) {
     const dim3 grid((unsigned)((c->E + 255) / 256));
-    if (c->ei.d == 2) {
-        if (x) hipLaunchKernelGGL((k_mf_apply_elements<2, OpT<OP, 2>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, x, fe);
-        else hipLaunchKernelGGL((k_mf_diagonal_elements<2, OpT<OP, 2>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
-    } else {
-        if (x) hipLaunchKernelGGL((k_mf_apply_elements<3, OpT<OP, 3>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, x, fe);
-        else hipLaunchKernelGGL((k_mf_diagonal_elements<3, OpT<OP, 3>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
-    }
+    dispatch_or_last(elliptic_ops, c->op, [&](auto op) {
+        return dispatch_or_last(int_list<2, 3>{}, c->ei.d, [&](auto d) {
+            constexpr int S = OpT<op(), d()>::S;
+            if (x) hipLaunchKernelGGL((k_mf_apply_elements<d(), S, op()>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, x, fe);
+            else hipLaunchKernelGGL((k_mf_diagonal_elements<d(), S, op()>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+            return 0;
+        });
+    });
 }
 
 // one quadrature table (or one group of a rule-set table): the element diagonals (xin null) or the element vectors of the operand xin ADDED
@@ -636,12 +599,7 @@ static int mf_single(fh_ctx* c, const double* xin, double* out, uint64_t* failed
     const size_t need = (size_t)c->E * c->ei.n * S;
     if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
     const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    switch (c->op) {
-        case FH_LAPLACE: mf_elements_launch<FH_LAPLACE>(c, a, active, xin, c->fe_scratch.p); break;
-        case FH_LINEAR_ELASTIC: mf_elements_launch<FH_LINEAR_ELASTIC>(c, a, active, xin, c->fe_scratch.p); break;
-        case FH_NEO_HOOKEAN: mf_elements_launch<FH_NEO_HOOKEAN>(c, a, active, xin, c->fe_scratch.p); break;
-        default: mf_elements_launch<FH_STVK>(c, a, active, xin, c->fe_scratch.p); break;
-    }
+    mf_elements_launch(c, a, active, xin, c->fe_scratch.p);
     HIP_TRY(c, hipGetLastError());
     if (xin) c->last_kernel = "k_mf_apply_elements + k_vector_from_elements_soa";
     rc = launch_vector_from_elements_soa(c, S, c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
@@ -797,17 +755,6 @@ static int mass_tiles_pass(fh_ctx* c, const double* x, const unsigned char* dmas
     return FH_OK;
 }
 
-template <int D, int S, int N, int NG>
-static void mass_elements_launch(fh_ctx* c, const KArgs& a, const unsigned char* active, const double* x, const unsigned char* dmask) {
-    hipLaunchKernelGGL((k_mass_elements<D, S, N, NG>), dim3((unsigned)((c->E + 255) / 256)), dim3(256), 0, c->stream, a, active, c->mass_rho.p,
-                       c->mass_rho_n > 1 ? 1 : 0, x, dmask, c->fe_scratch.p);
-}
-template <int D, int N, int NG>
-static void mass_elements_launch_s(fh_ctx* c, const KArgs& a, const unsigned char* active, const double* x, const unsigned char* dmask) {
-    if (c->S() == 1) mass_elements_launch<D, 1, N, NG>(c, a, active, x, dmask);
-    else mass_elements_launch<D, D, N, NG>(c, a, active, x, dmask);
-}
-
 // M x (x null: the diagonal of M) of the current table ADDED to out: the tiles where they cover it, else k_mass_elements and the ordered node sums
 static int mass_single(fh_ctx* c, const double* x, const unsigned char* dmask, double* out) {
     if (c->E == 0 || (c->has_mask && c->num_active == 0)) return FH_OK;
@@ -825,19 +772,15 @@ static int mass_single(fh_ctx* c, const double* x, const unsigned char* dmask, d
     KArgs a;
     fill_common(c, a);
     const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    switch (c->elem_kind) {
-        case FH_QUAD4: mass_elements_launch_s<2, 4, 4>(c, a, active, x, dmask); break;
-        case FH_TRI3: mass_elements_launch_s<2, 3, 3>(c, a, active, x, dmask); break;
-        case FH_QUAD9: mass_elements_launch_s<2, 9, 4>(c, a, active, x, dmask); break;
-        case FH_TRI6: mass_elements_launch_s<2, 6, 3>(c, a, active, x, dmask); break;
-        case FH_HEX8: mass_elements_launch_s<3, 8, 8>(c, a, active, x, dmask); break;
-        case FH_TET4: mass_elements_launch_s<3, 4, 4>(c, a, active, x, dmask); break;
-        case FH_HEX27: mass_elements_launch_s<3, 27, 8>(c, a, active, x, dmask); break;
-        case FH_TET10: mass_elements_launch_s<3, 10, 4>(c, a, active, x, dmask); break;
-        case FH_HEX20: mass_elements_launch_s<3, 20, 8>(c, a, active, x, dmask); break;
-        case FH_TET20: mass_elements_launch_s<3, 20, 4>(c, a, active, x, dmask); break;
-        default: return c->fail(FH_UNSUPPORTED, "the shifted map: unknown element kind");
-    }
+    const int covered = dispatch(all_kinds, c->elem_kind, -1, [&](auto ek) {
+        using EL = ElemT<ek()>;
+        return dispatch_bool(c->S() == 1, [&](auto scalar) {
+            hipLaunchKernelGGL((k_mass_elements<EL::D, scalar() ? 1 : EL::D, EL::N, EL::NG>), dim3((unsigned)((c->E + 255) / 256)), dim3(256), 0, c->stream, a,
+                               active, c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, x, dmask, c->fe_scratch.p);
+            return 0;
+        });
+    });
+    if (covered < 0) return c->fail(FH_UNSUPPORTED, "the shifted map: unknown element kind");
     HIP_TRY(c, hipGetLastError());
     return launch_vector_from_elements_soa(c, c->S(), c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
 }
@@ -994,11 +937,14 @@ int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x, double
 
 // r(u) of the current table (or one group of a rule-set table) ADDED to out without atomics, on every element kind: k_residual_elements and
 // the ordered node sums (the Newton residual off the tiles; fh_assemble_vector_dev scatters with fp64 atomics on the quadratic and cubic kinds)
-template <int OP>
 static void residual_elements_launch(fh_ctx* c, const KArgs& a, const unsigned char* active, double* fe) {
     const dim3 grid((unsigned)((c->E + 255) / 256));
-    if (c->ei.d == 2) hipLaunchKernelGGL((k_residual_elements<2, OpT<OP, 2>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
-    else hipLaunchKernelGGL((k_residual_elements<3, OpT<OP, 3>::S, OP>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+    dispatch_or_last(elliptic_ops, c->op, [&](auto op) {
+        return dispatch_or_last(int_list<2, 3>{}, c->ei.d, [&](auto d) {
+            hipLaunchKernelGGL((k_residual_elements<d(), OpT<op(), d()>::S, op()>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+            return 0;
+        });
+    });
 }
 static int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed) {
     int rc = reset_status(c);
@@ -1011,12 +957,7 @@ static int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed) {
     KArgs a;
     fill_common(c, a);
     const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    switch (c->op) {
-        case FH_LAPLACE: residual_elements_launch<FH_LAPLACE>(c, a, active, c->fe_scratch.p); break;
-        case FH_LINEAR_ELASTIC: residual_elements_launch<FH_LINEAR_ELASTIC>(c, a, active, c->fe_scratch.p); break;
-        case FH_NEO_HOOKEAN: residual_elements_launch<FH_NEO_HOOKEAN>(c, a, active, c->fe_scratch.p); break;
-        default: residual_elements_launch<FH_STVK>(c, a, active, c->fe_scratch.p); break;
-    }
+    residual_elements_launch(c, a, active, c->fe_scratch.p);
     HIP_TRY(c, hipGetLastError());
     rc = launch_vector_from_elements_soa(c, c->S(), c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
     if (rc) return rc;

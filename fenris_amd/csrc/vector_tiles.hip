@@ -22,6 +22,7 @@
 
 #include <vector>
 
+#include "dispatch.hpp"
 #include "element_pass.hpp"
 #include "vector_tiles.hpp"
 
@@ -900,235 +901,147 @@ hipError_t vector_tiles_build(hipStream_t stream, const int* conn, int n, long l
     return hipSuccess;
 }
 
+// ---- the launchers.  An element pass returns -1 where the combination has no kernel (the callers keep their other kernels).
+namespace {
+// an element pass: one workgroup per tile, in whole groups of eight (xcd_tile); a node pass: `grid` workgroups of 256
+template <class... P, class... A>
+int tile_launch(void (*kern)(P...), const VecTiles& t, hipStream_t stream, const A&... args) {
+    hipLaunchKernelGGL(kern, dim3(8 * ((t.ntiles + 7) / 8)), dim3(VT_TS), 0, stream, args...);
+    return 0;
+}
+template <class... P, class... A>
+hipError_t node_launch(void (*kern)(P...), int grid, hipStream_t stream, const A&... args) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, args...);
+    return hipGetLastError();
+}
+// The form of the element pass (element_pass.hpp): 0 general; Hex8 with the table of monomials: 1, 2 when every element is affine, 3 when the
+// rule's moments are there too (the linear operators only)
+int mono_mode(int elem_kind, int op, const KArgs& a) {
+    if (elem_kind != FH_HEX8 || !a.qmono) return 0;
+    if (!a.all_affine) return 1;
+    return (a.qmom && op <= FH_LINEAR_ELASTIC) ? 3 : 2;
+}
+constexpr bool mono_has_kernel(int ek, int op, int mode) { return mode == 0 || (ek == FH_HEX8 && (mode < 3 || op <= FH_LINEAR_ELASTIC)); }
+// f(element kind, operator, form) for a low-order kind, an operator of `ops` and the form the arguments ask for
+template <int... OPs, class F>
+int dispatch_tile_pass(int elem_kind, int_list<OPs...> ops, int op, const KArgs& a, F&& f) {
+    return dispatch(low_order_kinds, elem_kind, ops, op, -1, [&](auto ek, auto opc) {
+        return dispatch(int_list<0, 1, 2, 3>{}, mono_mode(elem_kind, op, a), -1, [&](auto m) {
+            if constexpr (mono_has_kernel(ek(), opc(), m())) return f(ek, opc, m);
+            else return -1;
+        });
+    });
+}
+}  // namespace
+
 int vector_tiles_element_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial) {
-    int rs = -1;
-#define VT_OP(EKC)                                                                                                                                   \
-    switch (op) {                                                                                                                                    \
-        case FH_LAPLACE: hipLaunchKernelGGL((k_element_pass_tiled<EKC, FH_LAPLACE, VT_TS>), dim3(8 * ((t.ntiles + 7) / 8)), dim3(VT_TS), 0, stream, a, t, active, partial); rs = 0; break; \
-        case FH_LINEAR_ELASTIC: hipLaunchKernelGGL((k_element_pass_tiled<EKC, FH_LINEAR_ELASTIC, VT_TS>), dim3(8 * ((t.ntiles + 7) / 8)), dim3(VT_TS), 0, stream, a, t, active, partial); rs = 0; break; \
-        case FH_NEO_HOOKEAN: hipLaunchKernelGGL((k_element_pass_tiled<EKC, FH_NEO_HOOKEAN, VT_TS>), dim3(8 * ((t.ntiles + 7) / 8)), dim3(VT_TS), 0, stream, a, t, active, partial); rs = 0; break; \
-        case FH_STVK: hipLaunchKernelGGL((k_element_pass_tiled<EKC, FH_STVK, VT_TS>), dim3(8 * ((t.ntiles + 7) / 8)), dim3(VT_TS), 0, stream, a, t, active, partial); rs = 0; break; \
-        default: break;                                                                                                                              \
-    }
-    if (elem_kind == FH_HEX8 && a.qmono) {   // the monomial form (element_pass.hpp, round 5)
-        const dim3 g(8 * ((t.ntiles + 7) / 8));
-        switch (op) {
-            case FH_LAPLACE: if (a.all_affine && a.qmom) hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_LAPLACE, VT_TS, 3>), g, dim3(VT_TS), 0, stream, a, t, active, partial); else if (a.all_affine) hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_LAPLACE, VT_TS, 2>), g, dim3(VT_TS), 0, stream, a, t, active, partial); else hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_LAPLACE, VT_TS, 1>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0;
-            case FH_LINEAR_ELASTIC: if (a.all_affine && a.qmom) hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_LINEAR_ELASTIC, VT_TS, 3>), g, dim3(VT_TS), 0, stream, a, t, active, partial); else if (a.all_affine) hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_LINEAR_ELASTIC, VT_TS, 2>), g, dim3(VT_TS), 0, stream, a, t, active, partial); else hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_LINEAR_ELASTIC, VT_TS, 1>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0;
-            case FH_NEO_HOOKEAN: if (a.all_affine) hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_NEO_HOOKEAN, VT_TS, 2>), g, dim3(VT_TS), 0, stream, a, t, active, partial); else hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_NEO_HOOKEAN, VT_TS, 1>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0;
-            case FH_STVK: if (a.all_affine) hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_STVK, VT_TS, 2>), g, dim3(VT_TS), 0, stream, a, t, active, partial); else hipLaunchKernelGGL((k_element_pass_tiled<FH_HEX8, FH_STVK, VT_TS, 1>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0;
-            default: return -1;
-        }
-    }
-    switch (elem_kind) {
-        case FH_QUAD4: VT_OP(FH_QUAD4) break;
-        case FH_TRI3: VT_OP(FH_TRI3) break;
-        case FH_TET4: VT_OP(FH_TET4) break;
-        case FH_HEX8: VT_OP(FH_HEX8) break;
-        default: break;
-    }
-#undef VT_OP
-    return rs;
+    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m) {
+        return tile_launch(k_element_pass_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, partial);
+    });
 }
 
 int vector_tiles_energy_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial) {
-    int rs = -1;
-    const int grid = 8 * ((t.ntiles + 7) / 8);
-#define VT_EN(EKC)                                                                                                                                   \
-    switch (op) {                                                                                                                                    \
-        case FH_LAPLACE: hipLaunchKernelGGL((k_element_energy_tiled<EKC, FH_LAPLACE, VT_TS>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); rs = grid; break; \
-        case FH_LINEAR_ELASTIC: hipLaunchKernelGGL((k_element_energy_tiled<EKC, FH_LINEAR_ELASTIC, VT_TS>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); rs = grid; break; \
-        case FH_NEO_HOOKEAN: hipLaunchKernelGGL((k_element_energy_tiled<EKC, FH_NEO_HOOKEAN, VT_TS>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); rs = grid; break; \
-        case FH_STVK: hipLaunchKernelGGL((k_element_energy_tiled<EKC, FH_STVK, VT_TS>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); rs = grid; break; \
-        default: break;                                                                                                                              \
-    }
-    if (elem_kind == FH_HEX8 && a.qmono) {
-        switch (op) {
-            case FH_LAPLACE: if (a.all_affine && a.qmom) hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_LAPLACE, VT_TS, 3>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); else if (a.all_affine) hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_LAPLACE, VT_TS, 2>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); else hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_LAPLACE, VT_TS, 1>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); return grid;
-            case FH_LINEAR_ELASTIC: if (a.all_affine && a.qmom) hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_LINEAR_ELASTIC, VT_TS, 3>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); else if (a.all_affine) hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_LINEAR_ELASTIC, VT_TS, 2>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); else hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_LINEAR_ELASTIC, VT_TS, 1>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); return grid;
-            case FH_NEO_HOOKEAN: if (a.all_affine) hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_NEO_HOOKEAN, VT_TS, 2>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); else hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_NEO_HOOKEAN, VT_TS, 1>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); return grid;
-            case FH_STVK: if (a.all_affine) hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_STVK, VT_TS, 2>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); else hipLaunchKernelGGL((k_element_energy_tiled<FH_HEX8, FH_STVK, VT_TS, 1>), dim3(grid), dim3(VT_TS), 0, stream, a, t, active, partial); return grid;
-            default: return -1;
-        }
-    }
-    switch (elem_kind) {
-        case FH_QUAD4: VT_EN(FH_QUAD4) break;
-        case FH_TRI3: VT_EN(FH_TRI3) break;
-        case FH_TET4: VT_EN(FH_TET4) break;
-        case FH_HEX8: VT_EN(FH_HEX8) break;
-        default: break;
-    }
-#undef VT_EN
-    return rs;
+    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m) {
+        tile_launch(k_element_energy_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, partial);
+        return vector_tiles_energy_partials(t);   // one partial per workgroup
+    });
 }
 
 int vector_tiles_source_pass(int D, int sdim, int n, bool fact, hipStream_t stream, const KArgs& a, const double* g3, const double* values,
                              const VecTiles& t, const unsigned char* active, double* partial) {
     SourceG g{{g3 ? g3[0] : 0.0, g3 ? g3[1] : 0.0, g3 ? g3[2] : 0.0}};
-    int rs = 0;
-#define VT_SRC(DV, SV, NV)                                                                                                                              \
-    do {                                                                                                                                                \
-        if (fact) hipLaunchKernelGGL((k_source_elements_tiled<DV, SV, NV, true, VT_TS>), dim3(8 * ((t.ntiles + 7) / 8)), dim3(VT_TS), 0, stream, a, g, values, t, active, partial); \
-        else hipLaunchKernelGGL((k_source_elements_tiled<DV, SV, NV, false, VT_TS>), dim3(8 * ((t.ntiles + 7) / 8)), dim3(VT_TS), 0, stream, a, g, values, t, active, partial);    \
-    } while (0)
-    if (D == 2 && n == 4) { if (sdim == 1) VT_SRC(2, 1, 4); else VT_SRC(2, 2, 4); }
-    else if (D == 2 && n == 3) { if (sdim == 1) VT_SRC(2, 1, 3); else VT_SRC(2, 2, 3); }
-    else if (D == 3 && n == 8) { if (sdim == 1) VT_SRC(3, 1, 8); else VT_SRC(3, 3, 8); }
-    else if (D == 3 && n == 4) { if (sdim == 1) VT_SRC(3, 1, 4); else VT_SRC(3, 3, 4); }
-    else rs = -1;
-#undef VT_SRC
-    return rs;
+    // the low-order kinds by (D, n): simplex or cube; one component, or (any other sdim) D of them
+    return dispatch(int_list<2, 3>{}, D, int_list<3, 4, 8>{}, n, -1, [&](auto dc, auto nc) {
+        if constexpr (nc() != dc() + 1 && nc() != (1 << dc())) return -1;
+        else return dispatch_bool(sdim == 1, [&](auto scalar) {
+            return dispatch_bool(fact, [&](auto fc) {
+                return tile_launch(k_source_elements_tiled<dc(), scalar() ? 1 : dc(), nc(), fc(), VT_TS>, t, stream, a, g, values, t, active, partial);
+            });
+        });
+    });
 }
 
 hipError_t vector_tiles_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, double* out, const double* scaled_g) {
     const int grid = (num_nodes + 255) / 256;
-    if (scaled_g) {   // scalar partials, S components g[c] sum
-        const SourceG g{{scaled_g[0], scaled_g[1], scaled_g[2]}};
-        if (S == 1) hipLaunchKernelGGL((k_vector_from_partials<1, 1>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out, g);
-        else if (S == 2) hipLaunchKernelGGL((k_vector_from_partials<1, 2>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out, g);
-        else hipLaunchKernelGGL((k_vector_from_partials<1, 3>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out, g);
-        return hipGetLastError();
-    }
-    if (S == 1) hipLaunchKernelGGL((k_vector_from_partials<1, 0>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out);
-    else if (S == 2) hipLaunchKernelGGL((k_vector_from_partials<2, 0>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out);
-    else hipLaunchKernelGGL((k_vector_from_partials<3, 0>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, out);
-    return hipGetLastError();
+    return dispatch_or_last(solution_dims, S, [&](auto s) {
+        if (!scaled_g) return node_launch(k_vector_from_partials<s(), 0>, grid, stream, num_nodes, t.np_off, t.np_idx, partial, out, SourceG{});
+        const SourceG g{{scaled_g[0], scaled_g[1], scaled_g[2]}};   // scalar partials, S components g[c] sum
+        return node_launch(k_vector_from_partials<1, s()>, grid, stream, num_nodes, t.np_off, t.np_idx, partial, out, g);
+    });
 }
 
 int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial) {
-    const dim3 g(8 * ((t.ntiles + 7) / 8));
-#define VT_DG(EKC)                                                                                                                   \
-    switch (op) {                                                                                                                    \
-        case FH_LAPLACE: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_LAPLACE, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
-        case FH_LINEAR_ELASTIC: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_LINEAR_ELASTIC, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
-        case FH_NEO_HOOKEAN: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_NEO_HOOKEAN, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
-        case FH_STVK: hipLaunchKernelGGL((k_diagonal_tiled<EKC, FH_STVK, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, partial); return 0; \
-        default: return -1;                                                                                                          \
-    }
-    switch (elem_kind) {
-        case FH_QUAD4: VT_DG(FH_QUAD4)
-        case FH_TRI3: VT_DG(FH_TRI3)
-        case FH_TET4: VT_DG(FH_TET4)
-        case FH_HEX8: VT_DG(FH_HEX8)
-        default: return -1;
-    }
-#undef VT_DG
+    return dispatch(low_order_kinds, elem_kind, elliptic_ops, op, -1, [&](auto ek, auto opc) {
+        return tile_launch(k_diagonal_tiled<ek(), opc(), VT_TS>, t, stream, a, t, active, partial);
+    });
 }
 
 hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
                                            const unsigned char* dmask, const double* scale, const unsigned long long* xbits, double* y,
                                            double* dot_partial) {
-    const int grid = vector_tiles_operator_partials(num_nodes);
-    if (S == 1) hipLaunchKernelGGL((k_operator_from_partials<1>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, xbits, y, dot_partial);
-    else if (S == 2) hipLaunchKernelGGL((k_operator_from_partials<2>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, xbits, y, dot_partial);
-    else hipLaunchKernelGGL((k_operator_from_partials<3>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, xbits, y, dot_partial);
-    return hipGetLastError();
+    return dispatch_or_last(solution_dims, S, [&](auto s) {
+        return node_launch(k_operator_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask,
+                           scale, xbits, y, dot_partial);
+    });
 }
 
 int vector_tiles_tangent_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* x,
                               double* partial) {
-    const dim3 g(8 * ((t.ntiles + 7) / 8));
-#define VT_TG1(EKC, OPC, M) hipLaunchKernelGGL((k_tangent_tiled<EKC, OPC, VT_TS, M>), g, dim3(VT_TS), 0, stream, a, t, active, x, partial)
-#define VT_TG(EKC, M)                                                              \
-    switch (op) {                                                                  \
-        case FH_NEO_HOOKEAN: VT_TG1(EKC, FH_NEO_HOOKEAN, M); return 0;             \
-        case FH_STVK: VT_TG1(EKC, FH_STVK, M); return 0;                           \
-        default: return -1;                                                        \
-    }
-    if (elem_kind == FH_HEX8 && a.qmono) {   // the monomial form
-        if (a.all_affine) { VT_TG(FH_HEX8, 2) }
-        else { VT_TG(FH_HEX8, 1) }
-    }
-    switch (elem_kind) {
-        case FH_QUAD4: VT_TG(FH_QUAD4, 0)
-        case FH_TRI3: VT_TG(FH_TRI3, 0)
-        case FH_TET4: VT_TG(FH_TET4, 0)
-        case FH_HEX8: VT_TG(FH_HEX8, 0)
-        default: return -1;
-    }
-#undef VT_TG
-#undef VT_TG1
+    return dispatch_tile_pass(elem_kind, hyperelastic_ops, op, a, [&](auto ek, auto opc, auto m) {
+        return tile_launch(k_tangent_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, x, partial);
+    });
 }
 
 int vector_tiles_mass_pass(int elem_kind, int S, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* rho,
                            int rho_per_elem, const double* x, const unsigned char* dmask, double* partial) {
-    const dim3 g(8 * ((t.ntiles + 7) / 8));
-#define VT_MS1(DV, NV, SV)                                                                                                                           \
-    do {                                                                                                                                             \
-        if (x) hipLaunchKernelGGL((k_mass_tiled<DV, NV, SV, false, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, rho, rho_per_elem, x, dmask, partial); \
-        else hipLaunchKernelGGL((k_mass_tiled<DV, NV, SV, true, VT_TS>), g, dim3(VT_TS), 0, stream, a, t, active, rho, rho_per_elem, x, dmask, partial);   \
-    } while (0)
-#define VT_MS(DV, NV)                        \
-    do {                                     \
-        if (S == 1) VT_MS1(DV, NV, 1);       \
-        else if (S == DV) VT_MS1(DV, NV, DV); \
-        else return -1;                      \
-    } while (0)
-    switch (elem_kind) {
-        case FH_QUAD4: VT_MS(2, 4); return 0;
-        case FH_TRI3: VT_MS(2, 3); return 0;
-        case FH_TET4: VT_MS(3, 4); return 0;
-        case FH_HEX8: VT_MS(3, 8); return 0;
-        default: return -1;
-    }
-#undef VT_MS
-#undef VT_MS1
+    return dispatch(low_order_kinds, elem_kind, -1, [&](auto ek) {
+        constexpr int D = kind_geom<ek()>::D, N = kind_geom<ek()>::NG;   // (iso-parametric: N == NG)
+        if (S != 1 && S != D) return -1;
+        return dispatch_bool(S == 1, [&](auto scalar) {
+            return dispatch_bool(x == nullptr, [&](auto diag) {   // no operand: the diagonal
+                return tile_launch(k_mass_tiled<D, N, scalar() ? 1 : D, diag(), VT_TS>, t, stream, a, t, active, rho, rho_per_elem, x, dmask, partial);
+            });
+        });
+    });
 }
 
 hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
                                         const unsigned char* dmask, const double* scale, double alpha, double beta, const double* tv, double* y,
                                         double* dot_partial) {
-    const int grid = vector_tiles_operator_partials(num_nodes);
-    if (S == 1) hipLaunchKernelGGL((k_shift_from_partials<1>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
-    else if (S == 2) hipLaunchKernelGGL((k_shift_from_partials<2>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
-    else hipLaunchKernelGGL((k_shift_from_partials<3>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask, scale, alpha, beta, tv, y, dot_partial);
-    return hipGetLastError();
+    return dispatch_or_last(solution_dims, S, [&](auto s) {
+        return node_launch(k_shift_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask,
+                           scale, alpha, beta, tv, y, dot_partial);
+    });
 }
 
 hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const double* mpart,
                                          const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial) {
-    const int grid = vector_tiles_operator_partials(num_nodes);
-    if (S == 1) hipLaunchKernelGGL((k_newton_from_partials<1>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f, dmask, alpha, beta, F, norm_partial);
-    else if (S == 2) hipLaunchKernelGGL((k_newton_from_partials<2>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f, dmask, alpha, beta, F, norm_partial);
-    else hipLaunchKernelGGL((k_newton_from_partials<3>), dim3(grid), dim3(256), 0, stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f, dmask, alpha, beta, F, norm_partial);
-    return hipGetLastError();
+    return dispatch_or_last(solution_dims, S, [&](auto s) {
+        return node_launch(k_newton_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f,
+                           dmask, alpha, beta, F, norm_partial);
+    });
 }
 
 int vector_tiles_shifted_hex8_pass(int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* x,
                                    const unsigned char* dmask, const MassTerm& mt, double* partial) {
     if (!a.qmono) return -1;
-    const dim3 g(8 * ((t.ntiles + 7) / 8));
     const bool aff = a.all_affine != 0;
-    if (mt.beta == 0.0) {   // the mass alone
-        if (op == FH_LAPLACE) {
-            if (aff) hipLaunchKernelGGL((k_mass_hex8_tiled<1, VT_TS, true>), g, dim3(VT_TS), 0, stream, a, t, active, x, dmask, mt, partial);
-            else hipLaunchKernelGGL((k_mass_hex8_tiled<1, VT_TS, false>), g, dim3(VT_TS), 0, stream, a, t, active, x, dmask, mt, partial);
-        } else {
-            if (aff) hipLaunchKernelGGL((k_mass_hex8_tiled<3, VT_TS, true>), g, dim3(VT_TS), 0, stream, a, t, active, x, dmask, mt, partial);
-            else hipLaunchKernelGGL((k_mass_hex8_tiled<3, VT_TS, false>), g, dim3(VT_TS), 0, stream, a, t, active, x, dmask, mt, partial);
-        }
-        return 0;
-    }
-#define VT_SH(OPC)                                                                                                                                   \
-    do {                                                                                                                                             \
-        if (aff && a.qmom) hipLaunchKernelGGL((k_shifted_pass_tiled<OPC, VT_TS, 2>), g, dim3(VT_TS), 0, stream, a, t, active, mt, partial);          \
-        else if (aff) hipLaunchKernelGGL((k_shifted_pass_tiled<OPC, VT_TS, 1>), g, dim3(VT_TS), 0, stream, a, t, active, mt, partial);               \
-        else hipLaunchKernelGGL((k_shifted_pass_tiled<OPC, VT_TS, 0>), g, dim3(VT_TS), 0, stream, a, t, active, mt, partial);                        \
-    } while (0)
-    switch (op) {
-        case FH_LAPLACE: VT_SH(FH_LAPLACE); return 0;
-        case FH_LINEAR_ELASTIC: VT_SH(FH_LINEAR_ELASTIC); return 0;
-        case FH_NEO_HOOKEAN:
-            if (aff) hipLaunchKernelGGL((k_shifted_tangent_tiled<FH_NEO_HOOKEAN, VT_TS, true>), g, dim3(VT_TS), 0, stream, a, t, active, x, mt, partial);
-            else hipLaunchKernelGGL((k_shifted_tangent_tiled<FH_NEO_HOOKEAN, VT_TS, false>), g, dim3(VT_TS), 0, stream, a, t, active, x, mt, partial);
-            return 0;
-        case FH_STVK:
-            if (aff) hipLaunchKernelGGL((k_shifted_tangent_tiled<FH_STVK, VT_TS, true>), g, dim3(VT_TS), 0, stream, a, t, active, x, mt, partial);
-            else hipLaunchKernelGGL((k_shifted_tangent_tiled<FH_STVK, VT_TS, false>), g, dim3(VT_TS), 0, stream, a, t, active, x, mt, partial);
-            return 0;
-        default: return -1;
-    }
-#undef VT_SH
+    if (mt.beta == 0.0)   // the mass alone: any operator but FH_LAPLACE has three components
+        return dispatch_bool(op == FH_LAPLACE, [&](auto scalar) {
+            return dispatch_bool(aff, [&](auto affc) {
+                return tile_launch(k_mass_hex8_tiled<scalar() ? 1 : 3, VT_TS, affc()>, t, stream, a, t, active, x, dmask, mt, partial);
+            });
+        });
+    return dispatch(elliptic_ops, op, -1, [&](auto opc) {
+        if constexpr (opc() <= FH_LINEAR_ELASTIC)   // form 0 general, 1 affine, 2 affine with the rule's moments
+            return dispatch(int_list<0, 1, 2>{}, !aff ? 0 : a.qmom ? 2 : 1, -1, [&](auto m) {
+                return tile_launch(k_shifted_pass_tiled<opc(), VT_TS, m()>, t, stream, a, t, active, mt, partial);
+            });
+        else
+            return dispatch_bool(aff, [&](auto affc) {
+                return tile_launch(k_shifted_tangent_tiled<opc(), VT_TS, affc()>, t, stream, a, t, active, x, mt, partial);
+            });
+    });
 }
 
 }  // namespace fenris_hip
