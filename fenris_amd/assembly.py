@@ -14,6 +14,7 @@ All numerics run in libfenris_hip.so on the GPU; there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import types
 from dataclasses import dataclass
 from typing import Optional
 
@@ -68,6 +69,7 @@ class Engine:
         self._mesh = mesh  # keep the host arrays alive
         self._mf_bound = None  # fh_set_mesh clears the operator's Dirichlet nodes
         self._mass_bound = None  # ... and the mass density
+        self._refined = None  # ... and drops a held refinement
         self._check(self._lib.fh_set_mesh(self._h, mesh.elem_kind, _ffi.fp(mesh.vertices), mesh.num_nodes(),
                                           _ffi.up(mesh.connectivity), mesh.num_elements()))
 
@@ -298,6 +300,39 @@ class Engine:
         if F:
             self._check(self._lib.fh_boundary_faces(self._h, _ffi.up(fn), _ffi.up(cells), lfs.ctypes.data_as(_ffi.u32p)))
         return fn, cells, lfs
+
+    # uniform refinement on the device (fh_refine_uniform): Tet4, Tri3, Quad4, Hex8
+    def refine_uniformly(self):
+        """refine the engine's mesh; the result stays on the engine until the next refinement or set_mesh.
+        -> (num_vertices, num_cells, transfer nnz)"""
+        nv, nc, nnz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.fh_refine_uniform(self._h, C.byref(nv), C.byref(nc), C.byref(nnz)))
+        self._refined = (int(nv.value), int(nc.value), int(nnz.value), self._mesh.elem_kind, self._mesh.num_nodes())
+        return self._refined[:3]
+
+    def refinement(self):
+        """the held refinement as host arrays -> (Mesh, Transfer)"""
+        from .refinement import Transfer
+
+        if getattr(self, "_refined", None) is None:
+            self._check(self._lib.fh_refinement_mesh(self._h, None, None))   # FH_INVALID_STATE
+        nv, nc, nnz, kind, num_coarse = self._refined
+        v = np.zeros((nv, _ffi.ELEM_DIM[kind]))
+        conn = np.zeros((nc, _ffi.ELEM_NODES[kind]), dtype=np.uint64)
+        off, idx, w = np.zeros(nv + 1, dtype=np.uint64), np.zeros(nnz, dtype=np.uint64), np.zeros(nnz)
+        self._check(self._lib.fh_refinement_mesh(self._h, _ffi.fp(v), _ffi.up(conn)))
+        self._check(self._lib.fh_refinement_transfer(self._h, _ffi.up(off), _ffi.up(idx), _ffi.fp(w)))
+        return Mesh(v, conn, kind), Transfer(off, idx, w, num_coarse)
+
+    def set_mesh_from_refinement(self, coarse_engine: "Engine"):
+        """fh_set_mesh_from_refinement: this engine's mesh becomes the refinement `coarse_engine` holds, device to device"""
+        self._mf_bound = None
+        self._mass_bound = None
+        self._check(self._lib.fh_set_mesh_from_refinement(self._h, coarse_engine._h))
+        nv, nc, _, kind, _ = coarse_engine._refined
+        # no host arrays were given: what the engine's own methods ask of a mesh
+        self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
+        self._refined = None
 
     def _two_phase_u64(self, fn):
         n = C.c_uint64(0)

@@ -475,6 +475,7 @@ struct fh_ctx {
     fh_mg* mg = nullptr;               // the multigrid hierarchy of FH_PRECOND_MULTIGRID (fh_set_multigrid; not owned)
     fh_amg* amg = nullptr;             // the algebraic hierarchy of FH_PRECOND_AMG (fh_set_amg; not owned)
     struct BoundaryStore* bnd = nullptr;   // boundary faces of the mesh and the adjacency of the last surface-load face list (engine_boundary.hip)
+    struct RefineStore* refined = nullptr;   // the uniform refinement of the mesh and its transfer, held since fh_refine_uniform (engine_refine.hip)
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -588,6 +589,8 @@ int amg_precondition(fh_amg* amg, const double* r, double* z);
 void amg_orphan(fh_amg* amg);
 // the cached boundary search and surface-load tables (engine_boundary.hip): dropped with the connectivity, kept by fh_update_vertices
 void boundary_drop(fh_ctx* c);
+// the held uniform refinement (engine_refine.hip): dropped with the mesh
+void refine_drop(fh_ctx* c);
 // y = K x on the context's pattern with the values of an assembled matrix (engine_solver.hip; fh_spmv_dev without the checks)
 int csr_spmv(fh_ctx* c, const double* vals, const double* x, double* y);
 // PCG with the V-cycle (engine_solver.hip): x += alpha p, r -= alpha Ap, partials of r . r into slot 1 of 2 per workgroup; partials of

@@ -1,8 +1,9 @@
-"""Uniform refinement of Hex8 meshes and the transfer between a coarse mesh and its refinement.
+"""Uniform refinement of Tet4, Tri3, Quad4 and Hex8 meshes and the transfer between a coarse mesh and its refinement.
 
-refine_uniformly / refine_uniformly_repeat carry the names of the reference's Tri3 refiners (src/mesh/refinement.rs) for Hex8.  The
-transfer is the trilinear interpolation from the coarse vertices to the fine ones, as CSR by fine node (fh_refine_hex8_uniform); it is
-what GeometricMultigrid prolongates with, and its transpose is the restriction.
+refine_uniformly / refine_uniformly_repeat carry the names of the reference's Tri3 refiners (src/mesh/refinement.rs).  The transfer is
+the linear (bi-, trilinear) interpolation from the coarse vertices to the fine ones, as CSR by fine node; it is what GeometricMultigrid
+prolongates with, and its transpose is the restriction.  Two paths with one numbering convention (include/fenris_hip.h): the device
+refiner of an Engine (fh_refine_uniform, all four kinds) and the host sweep fh_refine_hex8_uniform (Hex8 when no engine is given).
 """
 from __future__ import annotations
 
@@ -40,10 +41,31 @@ class Transfer:
         return self.to_scipy() @ coarse
 
 
-def refine_uniformly_with_transfer(mesh: Mesh):
-    """(fine mesh, Transfer): every hexahedron split into 8, coarse vertices first under their own indices"""
+DEVICE_KINDS = (_ffi.TET4, _ffi.TRI3, _ffi.QUAD4, _ffi.HEX8)
+
+
+def _refine_on_device(mesh: Mesh, engine):
+    engine.set_mesh(mesh)
+    engine.refine_uniformly()
+    return engine.refinement()
+
+
+def refine_uniformly_with_transfer(mesh: Mesh, engine=None):
+    """(fine mesh, Transfer): every cell split uniformly (Tet4, Hex8: 8 children; Tri3, Quad4: 4), coarse vertices first under their own
+    indices.  With an engine: its device refiner (the mesh becomes the engine's mesh).  Without: Hex8 takes the host sweep, the other
+    kinds an Engine(0) of their own for the call."""
+    if engine is not None:
+        return _refine_on_device(mesh, engine)
     if mesh.elem_kind != _ffi.HEX8:
-        raise _ffi.FenrisError(_ffi.FH_UNSUPPORTED, "uniform refinement is implemented for Hex8 meshes only")
+        if mesh.elem_kind not in DEVICE_KINDS:
+            raise _ffi.FenrisError(_ffi.FH_UNSUPPORTED, "uniform refinement is implemented for Tet4, Tri3, Quad4 and Hex8 meshes only")
+        from .assembly import Engine
+
+        own = Engine(0)
+        try:
+            return _refine_on_device(mesh, own)
+        finally:
+            own.close()
     lib = _ffi.lib()
     v, conn = _ffi.as_f64(mesh.vertices), _ffi.as_u64(mesh.connectivity)
     N, E = mesh.num_nodes(), mesh.num_elements()
@@ -65,25 +87,44 @@ def refine_uniformly_with_transfer(mesh: Mesh):
     return fine, Transfer(off, idx[: nnz.value].copy(), w[: nnz.value].copy(), N)
 
 
-def refine_uniformly(mesh: Mesh) -> Mesh:
-    """refine_uniformly (src/mesh/refinement.rs), here for Hex8"""
-    return refine_uniformly_with_transfer(mesh)[0]
+def refine_uniformly(mesh: Mesh, engine=None) -> Mesh:
+    """refine_uniformly (src/mesh/refinement.rs)"""
+    return refine_uniformly_with_transfer(mesh, engine)[0]
 
 
-def refine_uniformly_repeat(mesh: Mesh, n: int) -> Mesh:
+def _with_engine(mesh, engine, n):
+    """(engine to use, whether it is this call's own): one Engine(0) for all n levels of a kind that has no host path"""
+    if engine is None and mesh.elem_kind != _ffi.HEX8 and mesh.elem_kind in DEVICE_KINDS and int(n) > 0:
+        from .assembly import Engine
+
+        return Engine(0), True
+    return engine, False
+
+
+def refine_uniformly_repeat(mesh: Mesh, n: int, engine=None) -> Mesh:
     """refine_uniformly_repeat (src/mesh/refinement.rs): n uniform refinements"""
-    for _ in range(int(n)):
-        mesh = refine_uniformly(mesh)
+    engine, own = _with_engine(mesh, engine, n)
+    try:
+        for _ in range(int(n)):
+            mesh = refine_uniformly(mesh, engine)
+    finally:
+        if own:
+            engine.close()
     return mesh
 
 
-def refine_uniformly_repeat_with_transfers(mesh: Mesh, n: int):
+def refine_uniformly_repeat_with_transfers(mesh: Mesh, n: int, engine=None):
     """(meshes, transfers): meshes[0] is the input, meshes[k + 1] refines meshes[k] through transfers[k] (coarsest first)"""
     meshes, transfers = [mesh], []
-    for _ in range(int(n)):
-        fine, t = refine_uniformly_with_transfer(meshes[-1])
-        meshes.append(fine)
-        transfers.append(t)
+    engine, own = _with_engine(mesh, engine, n)
+    try:
+        for _ in range(int(n)):
+            fine, t = refine_uniformly_with_transfer(meshes[-1], engine)
+            meshes.append(fine)
+            transfers.append(t)
+    finally:
+        if own:
+            engine.close()
     return meshes, transfers
 
 

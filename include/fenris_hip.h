@@ -413,6 +413,32 @@ const char* fh_msh_last_error(void);
 int fh_refine_hex8_uniform(const double* vertices, uint64_t num_vertices, const uint64_t* hex8, uint64_t num_cells, double* out_vertices,
                            uint64_t* out_num_vertices, uint64_t* out_connectivity, uint64_t* transfer_offsets, uint64_t* transfer_indices,
                            double* transfer_weights, uint64_t* out_nnz);
+/* ---- uniform refinement of the context's mesh on the device: Tet4 (8 children), Tri3 (4: refine_uniformly, src/mesh/refinement.rs),
+ *      Quad4 (4) and Hex8 (8); any other kind and a ragged connectivity: FH_UNSUPPORTED ------------------------------------------------
+ * The numbering is fh_refine_hex8_uniform's for every kind: coarse vertices keep their indices; the new vertices follow in order of
+ * first appearance while sweeping the cells in order and, within a cell, the kind's list of new points in order; a new point is
+ * identified by the sorted tuple of its parent coarse vertices, lies at (sum of the parents in ascending index) * (1 / count), and its
+ * transfer row lists the parents in ascending index with weight 1 / count.  The result -- index arrays, vertices and weights -- is
+ * bit-identical to that sequential sweep; for Hex8, to fh_refine_hex8_uniform.  New points (parents as local nodes; local index
+ * n + p names point p) and children:
+ *   Tet4   4=(0,1) 5=(1,2) 6=(0,2) 7=(0,3) 8=(2,3) 9=(1,3)
+ *          [0,4,6,7] [4,1,5,9] [6,5,2,8] [7,9,8,3] [4,6,7,9] [4,9,5,6] [6,7,9,8] [6,8,9,5]      (Bey; every child has the parent's
+ *          orientation and 1/8 of its volume; 3 congruence classes under repeated refinement)
+ *   Tri3   3=(0,1) 4=(1,2) 5=(2,0)                     [0,3,5] [3,1,4] [5,4,2] [3,4,5]
+ *   Quad4  4=(0,1) 5=(1,2) 6=(2,3) 7=(3,0) 8=(0,1,2,3) [0,4,8,7] [4,1,5,8] [8,5,2,6] [7,8,6,3]
+ *   Hex8   the 3x3x3 lattice, x fastest, and child (cx, cy, cz), exactly as fh_refine_hex8_uniform
+ * The children of cell e are cells C e .. C e + C - 1.  fh_refine_uniform keeps the result on the context, on the device, until the next
+ * fh_refine_uniform, fh_set_mesh* or fh_set_connectivity_ragged (fh_update_vertices keeps it, with the positions it was formed from);
+ * without a held result the three functions below return FH_INVALID_STATE.  num_elements * new points per cell (6, 3, 5, 19) must be
+ * < 2^31, else FH_UNSUPPORTED.  Scratch, released on return: 24 bytes per (cell, new point) plus the radix sort's own temporary. */
+int fh_refine_uniform(fh_ctx*, uint64_t* out_num_vertices, uint64_t* out_num_cells, uint64_t* out_nnz);
+/* copies of the held result; any pointer may be NULL.  vertices: d per vertex; connectivity: n per cell; transfer_offsets:
+ * num_vertices + 1; transfer_indices, transfer_weights: nnz each (the layout fh_mg_create reads) */
+int fh_refinement_mesh(fh_ctx*, double* vertices, uint64_t* connectivity);
+int fh_refinement_transfer(fh_ctx*, uint64_t* transfer_offsets, uint64_t* transfer_indices, double* transfer_weights);
+/* fh_set_mesh on `fine` with the refinement that `coarse` holds, device to device (fine == coarse is allowed: the context then holds
+ * no refinement afterwards).  Contexts on different devices: FH_BAD_ARGUMENT. */
+int fh_set_mesh_from_refinement(fh_ctx* fine, fh_ctx* coarse);
 /* cuthill_mckee on a square sparsity pattern (src/mesh/reorder.rs:171-233): perm_out[target] = source.  The
  * reference orders equal-degree neighbours with an unstable sort (unspecified); ties are broken by ascending index. */
 int fh_cuthill_mckee(uint64_t num_rows, const uint64_t* row_offsets, const uint64_t* col_indices, uint64_t* perm_out);
