@@ -27,6 +27,7 @@ LOAD_TRACTION, LOAD_PRESSURE = 0, 1
 ASSEMBLE_REPRODUCIBLE = 0x200
 
 ELEM_NODES = {QUAD4: 4, HEX8: 8, TET4: 4, HEX27: 27, TRI3: 3, TET10: 10, QUAD9: 9, TRI6: 6, HEX20: 20, TET20: 20}
+LINEAR_KIND = {TET10: TET4, TRI6: TRI3, QUAD9: QUAD4, HEX20: HEX8, HEX27: HEX8}   # fh_coarsen_degree
 ELEM_DIM = {QUAD4: 2, HEX8: 3, TET4: 3, HEX27: 3, TRI3: 2, TET10: 3, QUAD9: 2, TRI6: 2, HEX20: 3, TET20: 3}
 
 u64p = C.POINTER(C.c_uint64)
@@ -192,6 +193,10 @@ _SIGS = {
     "fh_refinement_mesh": (C.c_int, [C.c_void_p, f64p, u64p]),
     "fh_refinement_transfer": (C.c_int, [C.c_void_p, u64p, u64p, f64p]),
     "fh_set_mesh_from_refinement": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_coarsen_degree": (C.c_int, [C.c_void_p, u64p, u64p]),
+    "fh_degree_coarsening_mesh": (C.c_int, [C.c_void_p, f64p, u64p, u64p]),
+    "fh_degree_coarsening_transfer": (C.c_int, [C.c_void_p, u64p, u64p, f64p]),
+    "fh_set_mesh_from_degree_coarsening": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_lame_from_young_poisson": (C.c_int, [C.c_double, C.c_double, f64p, f64p]),
     "fh_morton_partition": (C.c_int, [C.c_uint32, f64p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
     "fh_partition_create": (C.c_void_p, [C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),

@@ -70,6 +70,7 @@ class Engine:
         self._mf_bound = None  # fh_set_mesh clears the operator's Dirichlet nodes
         self._mass_bound = None  # ... and the mass density
         self._refined = None  # ... and drops a held refinement
+        self._coarsened = None  # ... and a held degree coarsening
         self._check(self._lib.fh_set_mesh(self._h, mesh.elem_kind, _ffi.fp(mesh.vertices), mesh.num_nodes(),
                                           _ffi.up(mesh.connectivity), mesh.num_elements()))
 
@@ -333,6 +334,43 @@ class Engine:
         # no host arrays were given: what the engine's own methods ask of a mesh
         self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
         self._refined = None
+        self._coarsened = None
+
+    # degree coarsening on the device (fh_coarsen_degree): Tet10, Tri6, Quad9, Hex20, Hex27 -> the linear mesh on their vertex nodes
+    def coarsen_degree(self):
+        """coarsen the engine's mesh to its linear kind; the result stays on the engine until the next coarsening or set_mesh.
+        -> (num_vertices, transfer nnz)"""
+        nv, nnz = C.c_uint64(0), C.c_uint64(0)
+        self._coarsened = None
+        self._check(self._lib.fh_coarsen_degree(self._h, C.byref(nv), C.byref(nnz)))
+        self._coarsened = (int(nv.value), int(nnz.value), _ffi.LINEAR_KIND[self._mesh.elem_kind], self._mesh.num_nodes(), self._mesh.num_elements())
+        return self._coarsened[:2]
+
+    def degree_coarsening(self):
+        """the held degree coarsening as host arrays -> (linear Mesh, Transfer, vertex_nodes)"""
+        from .refinement import Transfer
+
+        if getattr(self, "_coarsened", None) is None:
+            self._check(self._lib.fh_degree_coarsening_mesh(self._h, None, None, None))   # FH_INVALID_STATE
+        nv, nnz, kind, nf, nc = self._coarsened
+        v = np.zeros((nv, _ffi.ELEM_DIM[kind]))
+        conn = np.zeros((nc, _ffi.ELEM_NODES[kind]), dtype=np.uint64)
+        vertex_nodes = np.zeros(nv, dtype=np.uint64)
+        off, idx, w = np.zeros(nf + 1, dtype=np.uint64), np.zeros(nnz, dtype=np.uint64), np.zeros(nnz)
+        self._check(self._lib.fh_degree_coarsening_mesh(self._h, _ffi.fp(v), _ffi.up(conn), _ffi.up(vertex_nodes)))
+        self._check(self._lib.fh_degree_coarsening_transfer(self._h, _ffi.up(off), _ffi.up(idx), _ffi.fp(w)))
+        return Mesh(v, conn, kind), Transfer(off, idx, w, nv), vertex_nodes
+
+    def set_mesh_from_degree_coarsening(self, high_engine: "Engine"):
+        """fh_set_mesh_from_degree_coarsening: this engine's mesh becomes the degree coarsening `high_engine` holds, device to device"""
+        self._mf_bound = None
+        self._mass_bound = None
+        self._check(self._lib.fh_set_mesh_from_degree_coarsening(self._h, high_engine._h))
+        nv, _, kind, _, nc = high_engine._coarsened
+        # no host arrays were given: what the engine's own methods ask of a mesh
+        self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
+        self._refined = None
+        self._coarsened = None
 
     def _two_phase_u64(self, fn):
         n = C.c_uint64(0)

@@ -431,6 +431,7 @@ void fh_destroy(fh_ctx* c) {
     delete c->rows_stash;
     boundary_drop(c);
     refine_drop(c);
+    coarsen_drop(c);
     delete c;
 }
 
@@ -552,6 +553,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     invalidate_pattern(c);
     boundary_drop(c);
     refine_drop(c);
+    coarsen_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
@@ -652,6 +654,7 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     invalidate_pattern(c);
     boundary_drop(c);
     refine_drop(c);
+    coarsen_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
     c->mass_rho_n = 0;   // (the density belongs to the mesh)

@@ -476,6 +476,7 @@ struct fh_ctx {
     fh_amg* amg = nullptr;             // the algebraic hierarchy of FH_PRECOND_AMG (fh_set_amg; not owned)
     struct BoundaryStore* bnd = nullptr;   // boundary faces of the mesh and the adjacency of the last surface-load face list (engine_boundary.hip)
     struct RefineStore* refined = nullptr;   // the uniform refinement of the mesh and its transfer, held since fh_refine_uniform (engine_refine.hip)
+    struct CoarsenStore* coarsened = nullptr;   // the linear mesh under a quadratic one and its transfer, held since fh_coarsen_degree (engine_coarsen.hip)
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -591,6 +592,8 @@ void amg_orphan(fh_amg* amg);
 void boundary_drop(fh_ctx* c);
 // the held uniform refinement (engine_refine.hip): dropped with the mesh
 void refine_drop(fh_ctx* c);
+// the held degree coarsening (engine_coarsen.hip): dropped with the mesh
+void coarsen_drop(fh_ctx* c);
 // y = K x on the context's pattern with the values of an assembled matrix (engine_solver.hip; fh_spmv_dev without the checks)
 int csr_spmv(fh_ctx* c, const double* vals, const double* x, double* y);
 // PCG with the V-cycle (engine_solver.hip): x += alpha p, r -= alpha Ap, partials of r . r into slot 1 of 2 per workgroup; partials of

@@ -1,0 +1,73 @@
+"""Degree coarsening of Tet10, Tri6, Quad9, Hex20 and Hex27 meshes: the linear mesh on their vertex nodes and the transfer from its
+vertices to all nodes (fh_coarsen_degree; the convention is in include/fenris_hip.h).  With it a higher-order problem gets a multigrid
+hierarchy: the p-coarsening step on top of the linear hierarchies of fenris_amd.refinement (degree_hierarchy).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _ffi
+from .mesh import Mesh
+from .refinement import permute_transfer
+
+DEGREE_KINDS = tuple(_ffi.LINEAR_KIND)
+
+
+def coarsen_degree_with_transfer(mesh: Mesh, engine=None):
+    """(linear mesh, Transfer, vertex_nodes): the linear mesh on the vertex nodes of `mesh` in the order of their indices, cells and
+    their nodes in the order of `mesh`; vertex_nodes[j] is the node of `mesh` that became vertex j.  With an engine: its device pass (the
+    mesh becomes the engine's mesh).  Without: an Engine(0) of its own for the call."""
+    if engine is not None:
+        engine.set_mesh(mesh)
+        engine.coarsen_degree()
+        return engine.degree_coarsening()
+    if mesh.elem_kind not in DEGREE_KINDS:
+        raise _ffi.FenrisError(_ffi.FH_UNSUPPORTED, "degree coarsening is implemented for Tet10, Tri6, Quad9, Hex20 and Hex27 meshes only")
+    from .assembly import Engine
+
+    own = Engine(0)
+    try:
+        return coarsen_degree_with_transfer(mesh, own)
+    finally:
+        own.close()
+
+
+def coarsen_degree(mesh: Mesh, engine=None) -> Mesh:
+    """the linear mesh of coarsen_degree_with_transfer"""
+    return coarsen_degree_with_transfer(mesh, engine)[0]
+
+
+def matching_vertex_permutation(new_mesh: Mesh, old_mesh: Mesh, rtol=1e-12):
+    """perm[new] = old for two meshes of one kind with the same cells in the same order and the same node order within each cell, read off
+    the connectivities.  ValueError when the correspondence is not one-to-one or the positions differ (by more than rtol * max |x|)."""
+    if new_mesh.elem_kind != old_mesh.elem_kind:
+        raise ValueError("the meshes differ in element kind")
+    cn = np.asarray(new_mesh.connectivity).astype(np.int64).ravel()
+    co = np.asarray(old_mesh.connectivity).astype(np.int64).ravel()
+    n = new_mesh.num_nodes()
+    if len(cn) != len(co) or n != old_mesh.num_nodes():
+        raise ValueError("the meshes differ in size")
+    perm = np.full(n, -1, dtype=np.int64)
+    perm[cn] = co
+    if (perm < 0).any() or not np.array_equal(perm[cn], co) or len(np.unique(perm)) != n:
+        raise ValueError("the vertices of the two meshes do not correspond one to one")
+    vn, vo = np.asarray(new_mesh.vertices), np.asarray(old_mesh.vertices)[perm]
+    if n and np.abs(vn - vo).max() > rtol * np.abs(vn).max():
+        raise ValueError("corresponding vertices of the two meshes differ in position")
+    return perm.astype(np.uint64)
+
+
+def degree_hierarchy(high_mesh: Mesh, linear_meshes, transfers, engine=None):
+    """(coarse_meshes, transfers) for GeometricMultigrid(fine_assembler, coarse_meshes, transfers) under a fine assembler on high_mesh.
+    linear_meshes (coarsest first) and the transfers between them are what refine_uniformly_repeat_with_transfers returns;
+    linear_meshes[-1] has the cells of high_mesh's linear part in any vertex numbering (the converters relabel).  The finest linear level
+    becomes the degree coarsening of high_mesh: the fine side of transfers[-1] is permuted to its numbering, and the transfer from it to
+    high_mesh is appended.  One linear mesh gives a two-level hierarchy."""
+    linear_meshes, transfers = list(linear_meshes), list(transfers)
+    if not linear_meshes or len(transfers) != len(linear_meshes) - 1:
+        raise ValueError("one transfer between every two consecutive linear meshes")
+    linear, p_transfer, _ = coarsen_degree_with_transfer(high_mesh, engine)
+    perm = matching_vertex_permutation(linear, linear_meshes[-1])
+    if transfers:
+        transfers[-1] = permute_transfer(transfers[-1], fine_perm=perm)
+    return linear_meshes[:-1] + [linear], transfers + [p_transfer]

@@ -439,6 +439,40 @@ int fh_refinement_transfer(fh_ctx*, uint64_t* transfer_offsets, uint64_t* transf
 /* fh_set_mesh on `fine` with the refinement that `coarse` holds, device to device (fine == coarse is allowed: the context then holds
  * no refinement afterwards).  Contexts on different devices: FH_BAD_ARGUMENT. */
 int fh_set_mesh_from_refinement(fh_ctx* fine, fh_ctx* coarse);
+/* ---- degree coarsening of the context's mesh on the device: Tet10 -> Tet4, Tri6 -> Tri3, Quad9 -> Quad4, Hex20 -> Hex8, Hex27 -> Hex8;
+ *      a linear kind, Tet20 and a ragged connectivity: FH_UNSUPPORTED --------------------------------------------------------------------
+ * The linear mesh on the vertex nodes of the mesh, and the transfer that interpolates linear nodal values to all of its nodes: the
+ * p-coarsening step of a multigrid hierarchy (fh_mg_create takes the transfer as it is).
+ *   vertex nodes   the nodes in a vertex slot of a cell: its first 3 (Tri6), 4 (Tet10, Quad9) or 8 (Hex20, Hex27) local nodes.  The
+ *                  coarse index of a vertex node is its rank among the vertex nodes in ascending fine index; vertex_nodes[j] is the
+ *                  fine index of coarse vertex j, and coarse vertex j has that node's position, bit for bit.
+ *   coarse cells   coarse cell e is the vertex slots of fine cell e in their order, renamed to coarse indices: cell order and node order
+ *                  are the fine mesh's.
+ *   transfer       CSR by fine node.  A vertex node's row is (its coarse index, 1.0).  Any other node lists the vertex nodes of its edge,
+ *                  face or cell in ascending coarse index, each with weight 1 / count: 1/2 on an edge, 1/4 on a face, 1/8 in a cell --
+ *                  the linear element's basis functions at the node's reference position.
+ * Parents of the non-vertex local nodes, as local nodes (the node orders of the element kinds):
+ *   Tet10          4=(0,1) 5=(1,2) 6=(0,2) 7=(0,3) 8=(2,3) 9=(1,3)
+ *   Tri6           3=(0,1) 4=(1,2) 5=(0,2)
+ *   Quad9          4=(0,1) 5=(1,2) 6=(2,3) 7=(0,3) 8=(0,1,2,3)
+ *   Hex20, Hex27   8=(0,1) 9=(0,3) 10=(0,4) 11=(1,2) 12=(1,5) 13=(2,3) 14=(2,6) 15=(3,7) 16=(4,5) 17=(4,7) 18=(5,6) 19=(6,7)
+ *   Hex27          20=(0,1,2,3) 21=(0,1,4,5) 22=(0,3,4,7) 23=(1,2,5,6) 24=(2,3,6,7) 25=(4,5,6,7) 26=(0,..,7)
+ * The pass validates the mesh and returns FH_BAD_ARGUMENT, with a message naming the smallest such node, when a node belongs to no
+ * cell, when a node is in a vertex slot of one cell and in another slot of another, or when the sorted parents of a non-vertex node
+ * differ between two cells that share it; the context stays usable.  num_elements * nodes per cell and num_vertices * most parents
+ * of a node (2, 2, 4, 2, 8) must be < 2^31, else FH_UNSUPPORTED.  The output is the same on every call.
+ * fh_coarsen_degree keeps the result on the context, on the device, until the next fh_coarsen_degree, fh_set_mesh* or
+ * fh_set_connectivity_ragged (fh_update_vertices keeps it, with the positions it was formed from); without a held result the three
+ * functions below return FH_INVALID_STATE.  A held refinement (fh_refine_uniform) and a held degree coarsening do not touch each other.
+ * Scratch, released on return: 28 bytes per node plus the scan's own temporary. */
+int fh_coarsen_degree(fh_ctx*, uint64_t* out_num_vertices, uint64_t* out_nnz);
+/* copies of the held result; any pointer may be NULL.  vertices: d per coarse vertex; connectivity: 3, 4 or 8 per cell; vertex_nodes:
+ * one per coarse vertex; transfer_offsets: (nodes of the fine mesh) + 1; transfer_indices, transfer_weights: nnz each */
+int fh_degree_coarsening_mesh(fh_ctx*, double* vertices, uint64_t* connectivity, uint64_t* vertex_nodes);
+int fh_degree_coarsening_transfer(fh_ctx*, uint64_t* transfer_offsets, uint64_t* transfer_indices, double* transfer_weights);
+/* fh_set_mesh on `linear` with the degree coarsening that `high` holds, device to device (linear == high is allowed: the context then
+ * holds no coarsening afterwards).  Contexts on different devices: FH_BAD_ARGUMENT. */
+int fh_set_mesh_from_degree_coarsening(fh_ctx* linear, fh_ctx* high);
 /* cuthill_mckee on a square sparsity pattern (src/mesh/reorder.rs:171-233): perm_out[target] = source.  The
  * reference orders equal-degree neighbours with an unstable sort (unspecified); ties are broken by ascending index. */
 int fh_cuthill_mckee(uint64_t num_rows, const uint64_t* row_offsets, const uint64_t* col_indices, uint64_t* perm_out);
