@@ -19,7 +19,8 @@ from .compose import (AggregateElementAssembler, MapElementNodes, TransformEleme
                       TransformElementVector)
 from .amg import SmoothedAggregationAMG
 from .boundary import BoundaryFaces, SurfaceLoad, SurfaceMesh
-from .degree import coarsen_degree, coarsen_degree_with_transfer, degree_hierarchy, matching_vertex_permutation
+from .degree import (coarsen_degree, coarsen_degree_with_transfer, degree_hierarchy, degree_hierarchy_from_linear, elevate_degree,
+                     elevate_degree_with_transfer, matching_vertex_permutation)
 from .multigrid import GeometricMultigrid
 from .refinement import (Transfer, permute_transfer, refine_uniformly, refine_uniformly_repeat, refine_uniformly_repeat_with_transfers,
                          refine_uniformly_with_transfer)

@@ -197,6 +197,10 @@ _SIGS = {
     "fh_degree_coarsening_mesh": (C.c_int, [C.c_void_p, f64p, u64p, u64p]),
     "fh_degree_coarsening_transfer": (C.c_int, [C.c_void_p, u64p, u64p, f64p]),
     "fh_set_mesh_from_degree_coarsening": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_elevate_degree": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p]),
+    "fh_degree_elevation_mesh": (C.c_int, [C.c_void_p, f64p, u64p]),
+    "fh_degree_elevation_transfer": (C.c_int, [C.c_void_p, u64p, u64p, f64p]),
+    "fh_set_mesh_from_degree_elevation": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_lame_from_young_poisson": (C.c_int, [C.c_double, C.c_double, f64p, f64p]),
     "fh_morton_partition": (C.c_int, [C.c_uint32, f64p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
     "fh_partition_create": (C.c_void_p, [C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),

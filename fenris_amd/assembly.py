@@ -71,6 +71,7 @@ class Engine:
         self._mass_bound = None  # ... and the mass density
         self._refined = None  # ... and drops a held refinement
         self._coarsened = None  # ... and a held degree coarsening
+        self._elevated = None  # ... and a held degree elevation
         self._check(self._lib.fh_set_mesh(self._h, mesh.elem_kind, _ffi.fp(mesh.vertices), mesh.num_nodes(),
                                           _ffi.up(mesh.connectivity), mesh.num_elements()))
 
@@ -335,6 +336,7 @@ class Engine:
         self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
         self._refined = None
         self._coarsened = None
+        self._elevated = None
 
     # degree coarsening on the device (fh_coarsen_degree): Tet10, Tri6, Quad9, Hex20, Hex27 -> the linear mesh on their vertex nodes
     def coarsen_degree(self):
@@ -371,6 +373,43 @@ class Engine:
         self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
         self._refined = None
         self._coarsened = None
+        self._elevated = None
+
+    # degree elevation on the device (fh_elevate_degree): Tet4 -> Tet10, Tri3 -> Tri6, Quad4 -> Quad9, Hex8 -> Hex20 or Hex27
+    def elevate_degree(self, to_kind):
+        """elevate the engine's linear mesh to `to_kind`; the result stays on the engine until the next elevation or set_mesh.
+        -> (num_vertices, transfer nnz)"""
+        nv, nnz = C.c_uint64(0), C.c_uint64(0)
+        self._elevated = None
+        self._check(self._lib.fh_elevate_degree(self._h, int(to_kind), C.byref(nv), C.byref(nnz)))
+        self._elevated = (int(nv.value), int(nnz.value), int(to_kind), self._mesh.num_nodes(), self._mesh.num_elements())
+        return self._elevated[:2]
+
+    def degree_elevation(self):
+        """the held degree elevation as host arrays -> (high Mesh, Transfer from the linear vertices to its nodes)"""
+        from .refinement import Transfer
+
+        if getattr(self, "_elevated", None) is None:
+            self._check(self._lib.fh_degree_elevation_mesh(self._h, None, None))   # FH_INVALID_STATE
+        nv, nnz, kind, nl, nc = self._elevated
+        v = np.zeros((nv, _ffi.ELEM_DIM[kind]))
+        conn = np.zeros((nc, _ffi.ELEM_NODES[kind]), dtype=np.uint64)
+        off, idx, w = np.zeros(nv + 1, dtype=np.uint64), np.zeros(nnz, dtype=np.uint64), np.zeros(nnz)
+        self._check(self._lib.fh_degree_elevation_mesh(self._h, _ffi.fp(v), _ffi.up(conn)))
+        self._check(self._lib.fh_degree_elevation_transfer(self._h, _ffi.up(off), _ffi.up(idx), _ffi.fp(w)))
+        return Mesh(v, conn, kind), Transfer(off, idx, w, nl)
+
+    def set_mesh_from_degree_elevation(self, linear_engine: "Engine"):
+        """fh_set_mesh_from_degree_elevation: this engine's mesh becomes the degree elevation `linear_engine` holds, device to device"""
+        self._mf_bound = None
+        self._mass_bound = None
+        self._check(self._lib.fh_set_mesh_from_degree_elevation(self._h, linear_engine._h))
+        nv, _, kind, _, nc = linear_engine._elevated
+        # no host arrays were given: what the engine's own methods ask of a mesh
+        self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
+        self._refined = None
+        self._coarsened = None
+        self._elevated = None
 
     def _two_phase_u64(self, fn):
         n = C.c_uint64(0)

@@ -9,40 +9,19 @@
 // coarse index is the rank among the vertex nodes.
 #include <hip/hip_runtime.h>
 
+#include "hierarchy_kernels.hpp"
+
 namespace fenris_hip {
 
-constexpr int COARSEN_MAX_NODES = 27;
-
-// The parents of every local node of a cell kind, by value in the kernel arguments.
-struct CoarsenTable {
-    int n, nv;                                   // nodes per cell; vertex slots per cell (the first nv local nodes)
-    signed char cnt[COARSEN_MAX_NODES];          // parents of local node l: 1 (a vertex slot: itself), 2, 4 or 8
-    signed char par[COARSEN_MAX_NODES][8];       // ... as local nodes < nv
-};
-
-constexpr unsigned COARSEN_NONE = 0xFFFFFFFFu;   // padding of a tuple, and "no node" in the status words
 constexpr int COARSEN_SHIFT = 32;                // the scan's packing: vertex rank << 32 | row offset
 // status words: the smallest offending node of each class
 enum { COARSEN_ORPHAN = 0, COARSEN_MIXED = 1, COARSEN_MISMATCH = 2, COARSEN_STATUS_WORDS = 3 };
 
-// the parent tuple of occurrence `id` as fine nodes, ascending, padded with COARSEN_NONE.  Odd-even transposition with compile-time
-// indices: the tuple stays in registers.
+// the parent tuple of occurrence `id` as fine nodes
 template <int MP>
 __device__ __forceinline__ void coarsen_sorted_tuple(const int* __restrict__ conn, const CoarsenTable& t, unsigned id, unsigned (&k)[MP]) {
     const unsigned cell = id / (unsigned)t.n, l = id % (unsigned)t.n;
-    const int* ec = conn + (size_t)cell * t.n;
-    const int cnt = t.cnt[l];
-#pragma unroll
-    for (int a = 0; a < MP; ++a) k[a] = a < cnt ? (unsigned)ec[t.par[l][a]] : COARSEN_NONE;
-#pragma unroll
-    for (int pass = 0; pass < MP; ++pass) {
-#pragma unroll
-        for (int i = pass & 1; i + 1 < MP; i += 2) {
-            const unsigned lo = min(k[i], k[i + 1]), hi = max(k[i], k[i + 1]);
-            k[i] = lo;
-            k[i + 1] = hi;
-        }
-    }
+    sorted_parent_tuple<MP>(conn + (size_t)cell * t.n, t.par[l], t.cnt[l], k);
 }
 
 __global__ void k_coarsen_init(unsigned N, unsigned* __restrict__ owner, unsigned* __restrict__ role, unsigned* __restrict__ status) {

@@ -432,6 +432,7 @@ void fh_destroy(fh_ctx* c) {
     boundary_drop(c);
     refine_drop(c);
     coarsen_drop(c);
+    elevate_drop(c);
     delete c;
 }
 
@@ -554,6 +555,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     boundary_drop(c);
     refine_drop(c);
     coarsen_drop(c);
+    elevate_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
@@ -655,6 +657,7 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     boundary_drop(c);
     refine_drop(c);
     coarsen_drop(c);
+    elevate_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
     c->mass_rho_n = 0;   // (the density belongs to the mesh)

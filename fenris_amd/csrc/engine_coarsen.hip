@@ -38,8 +38,10 @@ CoarsenTable lattice_table(int n, int nv, const Sign& sign) {
     return t;
 }
 
+}  // namespace
+
 // the table and the linear kind; false for a kind without a degree coarsening
-bool coarsen_table(int kind, CoarsenTable& t, int& linear_kind) {
+bool fenris_hip::coarsen_table(int kind, CoarsenTable& t, int& linear_kind) {
     static const int E3[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {2, 3}, {1, 3}};
     static const int E2[3][2] = {{0, 1}, {1, 2}, {0, 2}};
     switch (kind) {
@@ -51,6 +53,8 @@ bool coarsen_table(int kind, CoarsenTable& t, int& linear_kind) {
         default: return false;
     }
 }
+
+namespace {
 
 constexpr int_list<2, 4, 8> coarsen_parents{};
 

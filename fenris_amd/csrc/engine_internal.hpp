@@ -477,6 +477,7 @@ struct fh_ctx {
     struct BoundaryStore* bnd = nullptr;   // boundary faces of the mesh and the adjacency of the last surface-load face list (engine_boundary.hip)
     struct RefineStore* refined = nullptr;   // the uniform refinement of the mesh and its transfer, held since fh_refine_uniform (engine_refine.hip)
     struct CoarsenStore* coarsened = nullptr;   // the linear mesh under a quadratic one and its transfer, held since fh_coarsen_degree (engine_coarsen.hip)
+    struct ElevateStore* elevated = nullptr;   // the quadratic mesh over a linear one and its transfer, held since fh_elevate_degree (engine_elevate.hip)
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -594,6 +595,8 @@ void boundary_drop(fh_ctx* c);
 void refine_drop(fh_ctx* c);
 // the held degree coarsening (engine_coarsen.hip): dropped with the mesh
 void coarsen_drop(fh_ctx* c);
+// the held degree elevation (engine_elevate.hip): dropped with the mesh
+void elevate_drop(fh_ctx* c);
 // y = K x on the context's pattern with the values of an assembled matrix (engine_solver.hip; fh_spmv_dev without the checks)
 int csr_spmv(fh_ctx* c, const double* vals, const double* x, double* y);
 // PCG with the V-cycle (engine_solver.hip): x += alpha p, r -= alpha Ap, partials of r . r into slot 1 of 2 per workgroup; partials of

@@ -11,6 +11,8 @@
 // their indices.
 #include <hip/hip_runtime.h>
 
+#include "hierarchy_kernels.hpp"
+
 namespace fenris_hip {
 
 constexpr int REFINE_MAX_POINTS = 19;   // Hex8: the 3x3x3 lattice without its 8 corners
@@ -111,21 +113,7 @@ __global__ void k_refine_children(const int* __restrict__ conn, RefineTable t, u
     out[i] = l < t.n ? (unsigned long long)conn[cell * t.n + l] : (unsigned long long)fine[cell * t.P + (l - t.n)];
 }
 
-// Stage 5c, coarse part: the coarse vertices keep their indices and positions; their transfer rows are the identity.  Thread N closes
-// the offsets.
-template <int D>
-__global__ void k_refine_coarse_rows(const double* __restrict__ verts, unsigned N, unsigned long long num_fine, unsigned long long nnz,
-                                     double* __restrict__ out_v, unsigned long long* __restrict__ off, unsigned long long* __restrict__ idx,
-                                     double* __restrict__ w) {
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == N) off[num_fine] = nnz;
-    if (i >= N) return;
-#pragma unroll
-    for (int r = 0; r < D; ++r) out_v[(size_t)i * D + r] = verts[(size_t)i * D + r];
-    off[i] = i;
-    idx[i] = i;
-    w[i] = 1.0;
-}
+// Stage 5c, coarse part: k_refine_coarse_rows (hierarchy_kernels.hpp)
 
 // Stage 5c, new part: every first occurrence writes its vertex and its transfer row.  The position is the sum of the parents in
 // ascending index times 1 / count -- the operations and their order of refine_hex8_uniform (host_inputs.cpp), so the bits are the

@@ -473,6 +473,36 @@ int fh_degree_coarsening_transfer(fh_ctx*, uint64_t* transfer_offsets, uint64_t*
 /* fh_set_mesh on `linear` with the degree coarsening that `high` holds, device to device (linear == high is allowed: the context then
  * holds no coarsening afterwards).  Contexts on different devices: FH_BAD_ARGUMENT. */
 int fh_set_mesh_from_degree_coarsening(fh_ctx* linear, fh_ctx* high);
+/* ---- degree elevation of the context's mesh on the device: Tet4 -> Tet10, Tri3 -> Tri6, Quad4 -> Quad9, Hex8 -> Hex20, Hex8 -> Hex27;
+ *      any other to_kind for a linear context: FH_BAD_ARGUMENT; a quadratic or cubic context and a ragged connectivity: FH_UNSUPPORTED ---
+ * The straight-sided quadratic mesh over the linear one, and the transfer that interpolates linear nodal values to all of its nodes (the
+ * p-step of a multigrid hierarchy; fh_mg_create takes the transfer as it is).  Index arrays and vertex coordinates are bit-identical to
+ * fh_refine_to_quadratic and, for Hex27, fh_hex8_to_hex27; the parents of the non-vertex local nodes are those listed above.
+ *   Tet10, Hex20,  sweep the cells in order and, within a cell, its local nodes 0 .. n - 1 in order; a node is identified by the sorted
+ *   Hex27          tuple of its parent linear vertices (1, 2, 4 or 8); its label is its rank in order of first occurrence.  Old vertex
+ *                  indices are not kept, and a vertex of no cell disappears.
+ *   Tri6, Quad9    the old vertices keep their indices (those of no cell too); the midpoints of the edges (m, m + 1 mod n0) follow in
+ *                  order of first occurrence, for Quad9 the cell's centre right after the cell's edges.
+ *   position       computed by the (cell, slot) of the node's first occurrence in that cell's local node order: X[a] for a vertex;
+ *                  0.5 X[b] + 0.5 X[a] on an edge of Tet10, Hex20 and Hex27, (X[a] + X[b]) / 2 of Tri6 and Quad9; on a Hex27 face and in
+ *                  its centre the 8-term trilinear sum over the local nodes in order (weights 1/4 on the face, 1/8 in the centre, 0
+ *                  elsewhere); sum_k 0.25 X[k], k ascending, in a Quad9's centre.
+ *   transfer       CSR by high node over the context's vertices.  A vertex node's row is (its linear index, 1.0).  Any other node lists
+ *                  its parents in ascending linear index, each with weight 1 / count: the convention of fh_coarsen_degree.
+ * num_elements * nodes per high cell must be < 2^31, else FH_UNSUPPORTED.  The output does not depend on the launch geometry and is the
+ * same on every call.  fh_elevate_degree keeps the result on the context, on the device, until the next fh_elevate_degree, fh_set_mesh*
+ * or fh_set_connectivity_ragged (fh_update_vertices keeps it, with the positions it was formed from); without a held result the three
+ * functions below return FH_INVALID_STATE.  A held elevation, a held refinement and a held degree coarsening do not touch each other.
+ * Scratch, released on return: 24 bytes per labelled (cell, slot) -- every slot of Tet10, Hex20 and Hex27, the non-vertex slots of Tri6
+ * and Quad9 -- plus the radix sort's own temporary. */
+int fh_elevate_degree(fh_ctx*, int to_kind, uint64_t* out_num_vertices, uint64_t* out_nnz);
+/* copies of the held result; any pointer may be NULL.  vertices: d per high node; connectivity: n per cell; transfer_offsets:
+ * num_vertices + 1; transfer_indices, transfer_weights: nnz each (the layout fh_mg_create reads) */
+int fh_degree_elevation_mesh(fh_ctx*, double* vertices, uint64_t* connectivity);
+int fh_degree_elevation_transfer(fh_ctx*, uint64_t* transfer_offsets, uint64_t* transfer_indices, double* transfer_weights);
+/* fh_set_mesh on `high` with the degree elevation that `linear` holds, device to device (high == linear is allowed: the context then
+ * holds no elevation afterwards).  Contexts on different devices: FH_BAD_ARGUMENT. */
+int fh_set_mesh_from_degree_elevation(fh_ctx* high, fh_ctx* linear);
 /* cuthill_mckee on a square sparsity pattern (src/mesh/reorder.rs:171-233): perm_out[target] = source.  The
  * reference orders equal-degree neighbours with an unstable sort (unspecified); ties are broken by ascending index. */
 int fh_cuthill_mckee(uint64_t num_rows, const uint64_t* row_offsets, const uint64_t* col_indices, uint64_t* perm_out);
