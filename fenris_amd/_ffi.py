@@ -201,7 +201,22 @@ _SIGS = {
     "fh_degree_elevation_mesh": (C.c_int, [C.c_void_p, f64p, u64p]),
     "fh_degree_elevation_transfer": (C.c_int, [C.c_void_p, u64p, u64p, f64p]),
     "fh_set_mesh_from_degree_elevation": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "fh_lame_from_young_poisson": (C.c_int, [C.c_double, C.c_double, f64p, f64p]),
+    "fh_point_index_build": (C.c_int, [C.c_void_p]),
+    "fh_locate_points": (C.c_int, [C.c_void_p, f64p, C.c_uint64, u64p, f64p, C.POINTER(C.c_uint8)]),
+    "fh_locate_points_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fh_interpolator_create": (C.c_int, [C.c_void_p, f64p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
+    "fh_interpolator_create_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
+    "fh_interpolator_from_compressed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, u64p, u64p, C.c_uint64, f64p, C.c_uint64, f64p, C.c_uint64,
+                                                  C.POINTER(C.c_void_p)]),
+    "fh_interpolator_destroy": (None, [C.c_void_p]),
+    "fh_interpolator_last_error": (C.c_char_p, [C.c_void_p]),
+    "fh_interpolator_sizes": (C.c_int, [C.c_void_p, u64p, u64p, u32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fh_interpolator_data": (C.c_int, [C.c_void_p, u64p, u64p, f64p, f64p]),
+    "fh_interpolator_apply": (C.c_int, [C.c_void_p, C.c_uint32, f64p, C.c_uint64, f64p]),
+    "fh_interpolator_apply_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "fh_interpolator_apply_gradients": (C.c_int, [C.c_void_p, C.c_uint32, f64p, C.c_uint64, f64p]),
+    "fh_interpolator_apply_gradients_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "fh_lame_from_young_poisson":(C.c_int, [C.c_double, C.c_double, f64p, f64p]),
     "fh_morton_partition": (C.c_int, [C.c_uint32, f64p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
     "fh_partition_create": (C.c_void_p, [C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),
     "fh_partition_destroy": (None, [C.c_void_p]),

@@ -433,6 +433,7 @@ void fh_destroy(fh_ctx* c) {
     refine_drop(c);
     coarsen_drop(c);
     elevate_drop(c);
+    point_index_drop(c);
     delete c;
 }
 
@@ -556,6 +557,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     refine_drop(c);
     coarsen_drop(c);
     elevate_drop(c);
+    point_index_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
@@ -642,6 +644,7 @@ int fh_update_vertices(fh_ctx* c, const double* vertices) {
     HIP_TRY(c, hipMemcpyAsync(c->verts.p, vertices, sizeof(double) * c->N * c->ei.d, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     ++c->geom_gen;
+    point_index_drop(c);   // the boxes follow the vertices
     return classify_affine(c);
 }
 
@@ -658,6 +661,7 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     refine_drop(c);
     coarsen_drop(c);
     elevate_drop(c);
+    point_index_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
     c->mass_rho_n = 0;   // (the density belongs to the mesh)

@@ -478,6 +478,7 @@ struct fh_ctx {
     struct RefineStore* refined = nullptr;   // the uniform refinement of the mesh and its transfer, held since fh_refine_uniform (engine_refine.hip)
     struct CoarsenStore* coarsened = nullptr;   // the linear mesh under a quadratic one and its transfer, held since fh_coarsen_degree (engine_coarsen.hip)
     struct ElevateStore* elevated = nullptr;   // the quadratic mesh over a linear one and its transfer, held since fh_elevate_degree (engine_elevate.hip)
+    struct PointIndex* point_index = nullptr;   // element boxes and cell lists for point location, of the vertices as they are (engine_points.hip)
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -597,6 +598,8 @@ void refine_drop(fh_ctx* c);
 void coarsen_drop(fh_ctx* c);
 // the held degree elevation (engine_elevate.hip): dropped with the mesh
 void elevate_drop(fh_ctx* c);
+// the point-location index (engine_points.hip): dropped with the mesh and with its vertices (fh_update_vertices)
+void point_index_drop(fh_ctx* c);
 // y = K x on the context's pattern with the values of an assembled matrix (engine_solver.hip; fh_spmv_dev without the checks)
 int csr_spmv(fh_ctx* c, const double* vals, const double* x, double* y);
 // PCG with the V-cycle (engine_solver.hip): x += alpha p, r -= alpha Ap, partials of r . r into slot 1 of 2 per workgroup; partials of

@@ -503,6 +503,55 @@ int fh_degree_elevation_transfer(fh_ctx*, uint64_t* transfer_offsets, uint64_t* 
 /* fh_set_mesh on `high` with the degree elevation that `linear` holds, device to device (high == linear is allowed: the context then
  * holds no elevation afterwards).  Contexts on different devices: FH_BAD_ARGUMENT. */
 int fh_set_mesh_from_degree_elevation(fh_ctx* high, fh_ctx* linear);
+/* ---- point location and interpolation at arbitrary points on the device (SpatiallyIndexed, FixedInterpolator of src/space) ---
+ * Tri3, Tri6, Tet4, Tet10 and Tet20 meshes; quadrilateral and hexahedral kinds and a ragged connectivity: FH_UNSUPPORTED (the
+ * reference has no closest_point for them).  The kinds are sub-parametric: location uses the vertex nodes (the Tri3 / Tet4
+ * geometry), basis values and gradients the element's own kind.
+ * Every element e reports closest_point(e, p) as the reference's element code does (triangle.rs:440-527, tetrahedron.rs:616-672):
+ * InElement or ClosestPoint, reference coordinates xi_e, and d2_e = |x_e(xi_e) - p|^2.  The answer for p is the InElement report
+ * with the LOWEST element index when there is one, else the report with the smallest d2_e, the lower index on a tie: one of the
+ * answers the reference may give (it takes the first InElement in R-tree order), made independent of any traversal order.  The
+ * index prunes only what cannot change that answer.  No floating-point atomics: every call repeats bit for bit.
+ * The index (element boxes scaled by 1.01 about their centres, a uniform cell grid, per-cell element lists in ascending order) is
+ * held on the context; fh_set_mesh*, fh_set_mesh_from_*, fh_set_connectivity_ragged and fh_update_vertices drop it, and the calls
+ * below build it when it is missing. */
+int fh_point_index_build(fh_ctx*);
+/* points: m x d.  element: m (UINT64_MAX: no element, a mesh without elements or, _dev only, a non-finite coordinate); xi: m x d
+ * reference coordinates; in_element (may be NULL): m flags, 1 for InElement.  The host entry point returns FH_BAD_ARGUMENT for a
+ * non-finite coordinate; the _dev one (all pointers on the device, enqueued on the context's stream) gives such a point
+ * UINT64_MAX and xi = 0. */
+int fh_locate_points(fh_ctx*, const double* points, uint64_t m, uint64_t* element, double* xi, uint8_t* in_element);
+int fh_locate_points_dev(fh_ctx*, const double* points_dev, uint64_t m, uint64_t* element_dev, double* xi_dev, uint8_t* in_element_dev);
+/* A fixed interpolator: for each of m points the n nodes of its element in element order, their basis values and / or their
+ * physical gradients J^-T grad phi (d per node) -- a CSR by point with offsets n i.  It owns its device arrays and outlives changes
+ * of the context's mesh; it works on the device and stream the context had when it was created.  A point without an element
+ * (see above) has index 0 and zero weights; gradients on an element without volume are NaN. */
+typedef struct fh_interpolator fh_interpolator;
+#define FH_INTERP_BOTH 0
+#define FH_INTERP_VALUES 1
+#define FH_INTERP_GRADIENTS 2
+int fh_interpolator_create(fh_ctx*, const double* points, uint64_t m, int what, fh_interpolator** out);
+int fh_interpolator_create_dev(fh_ctx*, const double* points_dev, uint64_t m, int what, fh_interpolator** out);
+/* FixedInterpolator::from_compressed_values with its assertions as FH_BAD_ARGUMENT (the message: fh_last_error of the context):
+ * offsets (m + 1) within num_indices and not decreasing -- rows may differ in length or be empty --, num_values == num_indices
+ * when values are given, num_gradients == d * num_indices when gradients are given (d = 1, 2 or 3).  Either may be NULL. */
+int fh_interpolator_from_compressed(fh_ctx*, uint32_t d, uint64_t m, const uint64_t* offsets, const uint64_t* indices, uint64_t num_indices,
+                                    const double* values, uint64_t num_values, const double* gradients, uint64_t num_gradients,
+                                    fh_interpolator** out);
+void fh_interpolator_destroy(fh_interpolator*);
+const char* fh_interpolator_last_error(const fh_interpolator*);
+/* any pointer may be NULL.  offsets: num_points + 1; indices, values: num_indices; gradients: d * num_indices, d per index */
+int fh_interpolator_sizes(const fh_interpolator*, uint64_t* num_points, uint64_t* num_indices, uint32_t* geometry_dim, int* has_values,
+                          int* has_gradients);
+int fh_interpolator_data(fh_interpolator*, uint64_t* offsets, uint64_t* indices, double* values, double* gradients);
+/* out[p sdim + j] = sum over the entries k of point p, in stored order, of value_k u[sdim node_k + j]  (m x sdim);
+ * gradients: out[p d sdim + j d + i] = sum of gradient_k[i] u[sdim node_k + j]  (per point d x sdim, column-major).
+ * u_len: the doubles u holds; sdim * (largest node index + 1) > u_len: FH_BAD_ARGUMENT (an interpolator created from a mesh counts
+ * the mesh's last node).  Applying what was not computed: FH_INVALID_STATE.  m == 0 is valid.  sdim: 1 .. 64. */
+int fh_interpolator_apply(fh_interpolator*, uint32_t sdim, const double* u, uint64_t u_len, double* out);
+int fh_interpolator_apply_dev(fh_interpolator*, uint32_t sdim, const double* u_dev, uint64_t u_len, double* out_dev);
+int fh_interpolator_apply_gradients(fh_interpolator*, uint32_t sdim, const double* u, uint64_t u_len, double* out);
+int fh_interpolator_apply_gradients_dev(fh_interpolator*, uint32_t sdim, const double* u_dev, uint64_t u_len, double* out_dev);
 /* cuthill_mckee on a square sparsity pattern (src/mesh/reorder.rs:171-233): perm_out[target] = source.  The
  * reference orders equal-degree neighbours with an unstable sort (unspecified); ties are broken by ascending index. */
 int fh_cuthill_mckee(uint64_t num_rows, const uint64_t* row_offsets, const uint64_t* col_indices, uint64_t* perm_out);
