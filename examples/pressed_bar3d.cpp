@@ -122,9 +122,16 @@ int main(int argc, char** argv) {
                 (unsigned long long)(4 * cpu), (unsigned long long)cpu, (unsigned long long)cpu, L, (unsigned long long)num_faces,
                 end_cells.size(), (unsigned long long)num_bv, clamped.size(), (unsigned long long)iterations, tip, uniaxial, total_load, pull,
                 clamped_motion);
+    // the stress of the solution: von Mises per element (fh_recover), its maximum beside the applied traction
+    CHECK(ctx, fh_set_u_dev(ctx, u));
+    std::vector<double> von_mises(nc);
+    CHECK(ctx, fh_recover(ctx, FH_RECOVER_VON_MISES, FH_AT_ELEMENTS, von_mises.data()));
+    double vm_max = 0.0;
+    for (double s : von_mises) vm_max = std::fmax(vm_max, s);
+    std::printf("von Mises stress, maximum over the elements: %.6e (applied traction %g)\n", vm_max, pull);
     (void)hipFree(values); (void)hipFree(rhs); (void)hipFree(u); (void)hipFree(p_dev); (void)hipFree(ec_dev); (void)hipFree(ef_dev);
     fh_destroy(ctx);
-    const bool ok = iterations > 0 && clamped_motion == 0.0 && end_cells.size() == cpu * cpu && clamped.size() == (cpu + 1) * (cpu + 1) &&
+    const bool ok = vm_max > 0.5 * pull && iterations > 0 && clamped_motion == 0.0 && end_cells.size() == cpu * cpu && clamped.size() == (cpu + 1) * (cpu + 1) &&
                     std::fabs(total_load - pull) < 1e-9 * pull && tip > 0.9 * uniaxial && tip < 1.001 * uniaxial;
     return ok ? 0 : 3;
 }

@@ -25,6 +25,8 @@ AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER = 0, 1, 2
 ASSEMBLE_OVERWRITE = 0x100
 LOAD_TRACTION, LOAD_PRESSURE = 0, 1
 ASSEMBLE_REPRODUCIBLE = 0x200
+RECOVER_GRAD_U, RECOVER_STRAIN, RECOVER_STRESS_PK1, RECOVER_STRESS_CAUCHY, RECOVER_VON_MISES, RECOVER_ENERGY_DENSITY, RECOVER_VOLUME = range(7)
+AT_POINTS, AT_ELEMENTS, AT_NODES = 0, 1, 2
 
 ELEM_NODES = {QUAD4: 4, HEX8: 8, TET4: 4, HEX27: 27, TRI3: 3, TET10: 10, QUAD9: 9, TRI6: 6, HEX20: 20, TET20: 20}
 LINEAR_KIND = {TET10: TET4, TRI6: TRI3, QUAD9: QUAD4, HEX20: HEX8, HEX27: HEX8}   # fh_coarsen_degree
@@ -216,6 +218,10 @@ _SIGS = {
     "fh_interpolator_apply_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "fh_interpolator_apply_gradients": (C.c_int, [C.c_void_p, C.c_uint32, f64p, C.c_uint64, f64p]),
     "fh_interpolator_apply_gradients_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "fh_recover_components": (C.c_int, [C.c_void_p, C.c_int, u32p]),
+    "fh_recover_rows": (C.c_int, [C.c_void_p, C.c_int, u64p]),
+    "fh_recover_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "fh_recover": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p]),
     "fh_lame_from_young_poisson":(C.c_int, [C.c_double, C.c_double, f64p, f64p]),
     "fh_morton_partition": (C.c_int, [C.c_uint32, f64p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
     "fh_partition_create": (C.c_void_p, [C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),

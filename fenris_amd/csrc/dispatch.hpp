@@ -49,6 +49,9 @@ constexpr int_list<FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK, FH_MA
 constexpr int_list<FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK> elliptic_ops{};
 constexpr int_list<FH_NEO_HOOKEAN, FH_STVK> hyperelastic_ops{};
 constexpr int_list<1, 2, 3> solution_dims{};
+constexpr int_list<FH_RECOVER_GRAD_U, FH_RECOVER_STRAIN, FH_RECOVER_STRESS_PK1, FH_RECOVER_STRESS_CAUCHY, FH_RECOVER_VON_MISES,
+                   FH_RECOVER_ENERGY_DENSITY, FH_RECOVER_VOLUME> recover_quantities{};
+constexpr int_list<1, 2, 3, 4, 9> recover_components{};   // 1, d, d x s in two and three dimensions
 
 // (D, NG) of an element kind: the dimension and the node count of its geometry
 template <int EK>

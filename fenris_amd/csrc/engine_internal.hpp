@@ -479,6 +479,7 @@ struct fh_ctx {
     struct CoarsenStore* coarsened = nullptr;   // the linear mesh under a quadratic one and its transfer, held since fh_coarsen_degree (engine_coarsen.hip)
     struct ElevateStore* elevated = nullptr;   // the quadratic mesh over a linear one and its transfer, held since fh_elevate_degree (engine_elevate.hip)
     struct PointIndex* point_index = nullptr;   // element boxes and cell lists for point location, of the vertices as they are (engine_points.hip)
+    DevBuf<double> recover_scratch;    // fh_recover*: element means and volumes of a nodal request, point rows and measures of the quadratic kinds
 
     int S() const {
         if (ragged) return (int)sdim_ragged;

@@ -787,6 +787,41 @@ int fh_estimate_H1_seminorm_error_squared(fh_ctx*, uint32_t solution_dim, const 
 int fh_estimate_H1_seminorm_error_squared_dev(fh_ctx*, uint32_t solution_dim, const double* u_h_dev, const double* grad_exact_dev,
                                               double* out);
 
+/* ---- recovery: what a user reads off a solved field.  For the context's mesh, operator, quadrature table and u (fh_set_u*; zeros when
+ * none is set), with s the operator's solution dimension and d the geometry dimension; every array is row-major doubles.
+ *   FH_RECOVER_GRAD_U          d x s   g[i][k] = d u_k / d x_i (the convention of fh_estimate_H1_seminorm_error_squared)
+ *   FH_RECOVER_STRAIN          d x d   FH_LINEAR_ELASTIC: sym(grad u); FH_NEO_HOOKEAN, FH_STVK: Green-Lagrange (F^T F - I) / 2 with
+ *                                      F = I + (grad u)^T (fenris-solid/src/lib.rs:20-29); the full symmetric matrix
+ *   FH_RECOVER_STRESS_PK1      s x d   the operator's stress P (fenris-solid/src/materials.rs), the flux grad u for FH_LAPLACE;
+ *                                      NeoHookean with det F <= 0: NaN, as in the residual
+ *   FH_RECOVER_STRESS_CAUCHY   d x d   P F^T / det F for NeoHookean and StVK (NaN when det F <= 0), P for LinearElastic
+ *   FH_RECOVER_VON_MISES       1       of the Cauchy stress: sqrt(3/2 dev : dev) in 3-D; in 2-D the IN-PLANE form
+ *                                      sqrt(sxx^2 - sxx syy + syy^2 + 3 sxy^2) (no out-of-plane stress is assumed or added)
+ *   FH_RECOVER_ENERGY_DENSITY  1       psi; NeoHookean: +inf when det F <= 0
+ *   FH_RECOVER_VOLUME          1       sum_q w_q |det J_q|; FH_AT_ELEMENTS only
+ * FH_LAPLACE has no strain, Cauchy or von Mises stress: FH_UNSUPPORTED, as are the mass operators and FH_TENSOR.
+ * Locations:
+ *   FH_AT_POINTS    (E nq) x ncomp, one row per (element, quadrature point) in the order of fh_physical_quadrature_points; Lame
+ *                   parameters from wherever the residual takes them (uniform, per-point or compact table)
+ *   FH_AT_ELEMENTS  E x ncomp, the measure-weighted mean  sum_q w |det J| v_q / sum_q w |det J|  in point order (a von Mises mean is the
+ *                   mean of the pointwise values); FH_RECOVER_VOLUME is the denominator
+ *   FH_AT_NODES     N x ncomp, the volume-weighted patch average  sum_e V_e mean_e / sum_e V_e  over the active elements of the node in
+ *                   ascending element order (no atomics: two calls agree bit for bit); a node without an active element gets zeros.
+ *                   Deliberately not an L2 projection: vertex basis functions of Tet10 and Hex20 have non-positive integrals.
+ * Elements masked by fh_set_active_elements give zeros at points and elements and take no part at the nodes.  Rule-set tables
+ * (fh_set_quadrature_rules): FH_UNSUPPORTED, like fh_physical_quadrature_points.  det J == 0 in an active element:
+ * FH_SINGULAR_JACOBIAN, read once at the end of the call like the residual reads it.  An unknown quantity or location, or
+ * FH_RECOVER_VOLUME anywhere but FH_AT_ELEMENTS: FH_BAD_ARGUMENT.  The launches go to the context's stream; `out` is OVERWRITTEN. */
+enum { FH_RECOVER_GRAD_U = 0, FH_RECOVER_STRAIN = 1, FH_RECOVER_STRESS_PK1 = 2, FH_RECOVER_STRESS_CAUCHY = 3, FH_RECOVER_VON_MISES = 4,
+       FH_RECOVER_ENERGY_DENSITY = 5, FH_RECOVER_VOLUME = 6 };
+enum { FH_AT_POINTS = 0, FH_AT_ELEMENTS = 1, FH_AT_NODES = 2 };
+/* components per row of a quantity for the context's operator and mesh; also validates quantity x operator */
+int fh_recover_components(fh_ctx*, int quantity, uint32_t* ncomp);
+/* rows of a location: E nq, E or N */
+int fh_recover_rows(fh_ctx*, int where, uint64_t* rows);
+int fh_recover_dev(fh_ctx*, int quantity, int where, double* out_dev);
+int fh_recover(fh_ctx*, int quantity, int where, double* out);
+
 /* ---- composition of element assemblers: AggregateElementAssembler, MapElementNodes and TransformElementMatrix / Vector with
  * a scale factor (src/assembly/local.rs:152-340; tests/unit_tests/assembly/local.rs:189-336).  Every body keeps its own
  * context -- mesh, operator, table, element kind, fastest kernels -- and what it assembled in ITS node numbering is added,
