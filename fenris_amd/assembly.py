@@ -29,6 +29,18 @@ from .mesh import Mesh
 
 
 # ------------------------------------------------------------------------------------------ engine
+@dataclass(frozen=True)
+class _Held:
+    """what an Engine remembers of a derived mesh and its transfer that the library holds on the device"""
+
+    kind: int
+    num_nodes: int
+    num_cells: int
+    nnz: int
+    num_rows: int  # of the transfer
+    num_coarse: int  # its columns
+
+
 class Engine:
     """Owns one fh_ctx (one device, one stream)."""
 
@@ -69,9 +81,7 @@ class Engine:
         self._mesh = mesh  # keep the host arrays alive
         self._mf_bound = None  # fh_set_mesh clears the operator's Dirichlet nodes
         self._mass_bound = None  # ... and the mass density
-        self._refined = None  # ... and drops a held refinement
-        self._coarsened = None  # ... and a held degree coarsening
-        self._elevated = None  # ... and a held degree elevation
+        self._drop_held()  # ... and drops a held refinement, degree coarsening and degree elevation
         self._check(self._lib.fh_set_mesh(self._h, mesh.elem_kind, _ffi.fp(mesh.vertices), mesh.num_nodes(),
                                           _ffi.up(mesh.connectivity), mesh.num_elements()))
 
@@ -80,6 +90,7 @@ class Engine:
         en_p = en if len(en) else np.zeros(1, dtype=np.uint64)
         self._mf_bound = None
         self._mass_bound = None
+        self._drop_held()
         self._check(self._lib.fh_set_connectivity_ragged(self._h, sdim, num_nodes, _ffi.up(eo), _ffi.up(en_p), len(eo) - 1))
 
     def set_active_elements(self, mask):
@@ -303,40 +314,50 @@ class Engine:
             self._check(self._lib.fh_boundary_faces(self._h, _ffi.up(fn), _ffi.up(cells), lfs.ctypes.data_as(_ffi.u32p)))
         return fn, cells, lfs
 
+    # meshes derived on the device and held on the engine, side by side, until the next call of the same kind or set_mesh
+    def _drop_held(self):
+        """the library drops what the engine holds with the mesh"""
+        self._refined = self._coarsened = self._elevated = None
+
+    def _fetch_held(self, held, mesh_fn, transfer_fn, with_vertex_nodes=False):
+        """a held mesh and its transfer as host arrays -> (Mesh, Transfer[, vertex_nodes])"""
+        from .refinement import Transfer
+
+        if held is None:
+            self._check(mesh_fn(self._h, *([None] * (3 if with_vertex_nodes else 2))))   # FH_INVALID_STATE
+        v = np.zeros((held.num_nodes, _ffi.ELEM_DIM[held.kind]))
+        conn = np.zeros((held.num_cells, _ffi.ELEM_NODES[held.kind]), dtype=np.uint64)
+        extra = (np.zeros(held.num_nodes, dtype=np.uint64),) if with_vertex_nodes else ()
+        off, idx, w = np.zeros(held.num_rows + 1, dtype=np.uint64), np.zeros(held.nnz, dtype=np.uint64), np.zeros(held.nnz)
+        self._check(mesh_fn(self._h, _ffi.fp(v), _ffi.up(conn), *[_ffi.up(x) for x in extra]))
+        self._check(transfer_fn(self._h, _ffi.up(off), _ffi.up(idx), _ffi.fp(w)))
+        return (Mesh(v, conn, held.kind), Transfer(off, idx, w, held.num_coarse)) + extra
+
+    def _adopt_held(self, fn, other: "Engine", held):
+        """this engine's mesh becomes the mesh `other` holds, device to device"""
+        self._mf_bound = None
+        self._mass_bound = None
+        self._check(fn(self._h, other._h))
+        # no host arrays were given: what the engine's own methods ask of a mesh
+        self._mesh = types.SimpleNamespace(elem_kind=held.kind, num_nodes=lambda: held.num_nodes, num_elements=lambda: held.num_cells)
+        self._drop_held()
+
     # uniform refinement on the device (fh_refine_uniform): Tet4, Tri3, Quad4, Hex8
     def refine_uniformly(self):
         """refine the engine's mesh; the result stays on the engine until the next refinement or set_mesh.
         -> (num_vertices, num_cells, transfer nnz)"""
         nv, nc, nnz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.fh_refine_uniform(self._h, C.byref(nv), C.byref(nc), C.byref(nnz)))
-        self._refined = (int(nv.value), int(nc.value), int(nnz.value), self._mesh.elem_kind, self._mesh.num_nodes())
-        return self._refined[:3]
+        self._refined = _Held(self._mesh.elem_kind, int(nv.value), int(nc.value), int(nnz.value), int(nv.value), self._mesh.num_nodes())
+        return int(nv.value), int(nc.value), int(nnz.value)
 
     def refinement(self):
         """the held refinement as host arrays -> (Mesh, Transfer)"""
-        from .refinement import Transfer
-
-        if getattr(self, "_refined", None) is None:
-            self._check(self._lib.fh_refinement_mesh(self._h, None, None))   # FH_INVALID_STATE
-        nv, nc, nnz, kind, num_coarse = self._refined
-        v = np.zeros((nv, _ffi.ELEM_DIM[kind]))
-        conn = np.zeros((nc, _ffi.ELEM_NODES[kind]), dtype=np.uint64)
-        off, idx, w = np.zeros(nv + 1, dtype=np.uint64), np.zeros(nnz, dtype=np.uint64), np.zeros(nnz)
-        self._check(self._lib.fh_refinement_mesh(self._h, _ffi.fp(v), _ffi.up(conn)))
-        self._check(self._lib.fh_refinement_transfer(self._h, _ffi.up(off), _ffi.up(idx), _ffi.fp(w)))
-        return Mesh(v, conn, kind), Transfer(off, idx, w, num_coarse)
+        return self._fetch_held(getattr(self, "_refined", None), self._lib.fh_refinement_mesh, self._lib.fh_refinement_transfer)
 
     def set_mesh_from_refinement(self, coarse_engine: "Engine"):
         """fh_set_mesh_from_refinement: this engine's mesh becomes the refinement `coarse_engine` holds, device to device"""
-        self._mf_bound = None
-        self._mass_bound = None
-        self._check(self._lib.fh_set_mesh_from_refinement(self._h, coarse_engine._h))
-        nv, nc, _, kind, _ = coarse_engine._refined
-        # no host arrays were given: what the engine's own methods ask of a mesh
-        self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
-        self._refined = None
-        self._coarsened = None
-        self._elevated = None
+        self._adopt_held(self._lib.fh_set_mesh_from_refinement, coarse_engine, getattr(coarse_engine, "_refined", None))
 
     # degree coarsening on the device (fh_coarsen_degree): Tet10, Tri6, Quad9, Hex20, Hex27 -> the linear mesh on their vertex nodes
     def coarsen_degree(self):
@@ -345,35 +366,18 @@ class Engine:
         nv, nnz = C.c_uint64(0), C.c_uint64(0)
         self._coarsened = None
         self._check(self._lib.fh_coarsen_degree(self._h, C.byref(nv), C.byref(nnz)))
-        self._coarsened = (int(nv.value), int(nnz.value), _ffi.LINEAR_KIND[self._mesh.elem_kind], self._mesh.num_nodes(), self._mesh.num_elements())
-        return self._coarsened[:2]
+        self._coarsened = _Held(_ffi.LINEAR_KIND[self._mesh.elem_kind], int(nv.value), self._mesh.num_elements(), int(nnz.value),
+                                self._mesh.num_nodes(), int(nv.value))
+        return int(nv.value), int(nnz.value)
 
     def degree_coarsening(self):
         """the held degree coarsening as host arrays -> (linear Mesh, Transfer, vertex_nodes)"""
-        from .refinement import Transfer
-
-        if getattr(self, "_coarsened", None) is None:
-            self._check(self._lib.fh_degree_coarsening_mesh(self._h, None, None, None))   # FH_INVALID_STATE
-        nv, nnz, kind, nf, nc = self._coarsened
-        v = np.zeros((nv, _ffi.ELEM_DIM[kind]))
-        conn = np.zeros((nc, _ffi.ELEM_NODES[kind]), dtype=np.uint64)
-        vertex_nodes = np.zeros(nv, dtype=np.uint64)
-        off, idx, w = np.zeros(nf + 1, dtype=np.uint64), np.zeros(nnz, dtype=np.uint64), np.zeros(nnz)
-        self._check(self._lib.fh_degree_coarsening_mesh(self._h, _ffi.fp(v), _ffi.up(conn), _ffi.up(vertex_nodes)))
-        self._check(self._lib.fh_degree_coarsening_transfer(self._h, _ffi.up(off), _ffi.up(idx), _ffi.fp(w)))
-        return Mesh(v, conn, kind), Transfer(off, idx, w, nv), vertex_nodes
+        return self._fetch_held(getattr(self, "_coarsened", None), self._lib.fh_degree_coarsening_mesh, self._lib.fh_degree_coarsening_transfer,
+                                with_vertex_nodes=True)
 
     def set_mesh_from_degree_coarsening(self, high_engine: "Engine"):
         """fh_set_mesh_from_degree_coarsening: this engine's mesh becomes the degree coarsening `high_engine` holds, device to device"""
-        self._mf_bound = None
-        self._mass_bound = None
-        self._check(self._lib.fh_set_mesh_from_degree_coarsening(self._h, high_engine._h))
-        nv, _, kind, _, nc = high_engine._coarsened
-        # no host arrays were given: what the engine's own methods ask of a mesh
-        self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
-        self._refined = None
-        self._coarsened = None
-        self._elevated = None
+        self._adopt_held(self._lib.fh_set_mesh_from_degree_coarsening, high_engine, getattr(high_engine, "_coarsened", None))
 
     # degree elevation on the device (fh_elevate_degree): Tet4 -> Tet10, Tri3 -> Tri6, Quad4 -> Quad9, Hex8 -> Hex20 or Hex27
     def elevate_degree(self, to_kind):
@@ -382,34 +386,16 @@ class Engine:
         nv, nnz = C.c_uint64(0), C.c_uint64(0)
         self._elevated = None
         self._check(self._lib.fh_elevate_degree(self._h, int(to_kind), C.byref(nv), C.byref(nnz)))
-        self._elevated = (int(nv.value), int(nnz.value), int(to_kind), self._mesh.num_nodes(), self._mesh.num_elements())
-        return self._elevated[:2]
+        self._elevated = _Held(int(to_kind), int(nv.value), self._mesh.num_elements(), int(nnz.value), int(nv.value), self._mesh.num_nodes())
+        return int(nv.value), int(nnz.value)
 
     def degree_elevation(self):
         """the held degree elevation as host arrays -> (high Mesh, Transfer from the linear vertices to its nodes)"""
-        from .refinement import Transfer
-
-        if getattr(self, "_elevated", None) is None:
-            self._check(self._lib.fh_degree_elevation_mesh(self._h, None, None))   # FH_INVALID_STATE
-        nv, nnz, kind, nl, nc = self._elevated
-        v = np.zeros((nv, _ffi.ELEM_DIM[kind]))
-        conn = np.zeros((nc, _ffi.ELEM_NODES[kind]), dtype=np.uint64)
-        off, idx, w = np.zeros(nv + 1, dtype=np.uint64), np.zeros(nnz, dtype=np.uint64), np.zeros(nnz)
-        self._check(self._lib.fh_degree_elevation_mesh(self._h, _ffi.fp(v), _ffi.up(conn)))
-        self._check(self._lib.fh_degree_elevation_transfer(self._h, _ffi.up(off), _ffi.up(idx), _ffi.fp(w)))
-        return Mesh(v, conn, kind), Transfer(off, idx, w, nl)
+        return self._fetch_held(getattr(self, "_elevated", None), self._lib.fh_degree_elevation_mesh, self._lib.fh_degree_elevation_transfer)
 
     def set_mesh_from_degree_elevation(self, linear_engine: "Engine"):
         """fh_set_mesh_from_degree_elevation: this engine's mesh becomes the degree elevation `linear_engine` holds, device to device"""
-        self._mf_bound = None
-        self._mass_bound = None
-        self._check(self._lib.fh_set_mesh_from_degree_elevation(self._h, linear_engine._h))
-        nv, _, kind, _, nc = linear_engine._elevated
-        # no host arrays were given: what the engine's own methods ask of a mesh
-        self._mesh = types.SimpleNamespace(elem_kind=kind, num_nodes=lambda: nv, num_elements=lambda: nc)
-        self._refined = None
-        self._coarsened = None
-        self._elevated = None
+        self._adopt_held(self._lib.fh_set_mesh_from_degree_elevation, linear_engine, getattr(linear_engine, "_elevated", None))
 
     def _two_phase_u64(self, fn):
         n = C.c_uint64(0)

@@ -1,5 +1,5 @@
 #pragma once
-// Degree coarsening kernels (engine_coarsen.hip): the linear mesh on the vertex nodes of a quadratic mesh and
+// Degree coarsening kernels (engine_hierarchy.hip): the linear mesh on the vertex nodes of a quadratic mesh and
 // the transfer from its vertices to all nodes.  Integer work only, apart from copying positions and writing the weights 1, 1/2, 1/4, 1/8.
 // The only atomics are integer atomicMin / atomicOr, whose results do not depend on the order of arrival.
 //

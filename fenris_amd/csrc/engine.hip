@@ -430,9 +430,7 @@ void fh_destroy(fh_ctx* c) {
     }
     delete c->rows_stash;
     boundary_drop(c);
-    refine_drop(c);
-    coarsen_drop(c);
-    elevate_drop(c);
+    held_drop_all(c);
     point_index_drop(c);
     delete c;
 }
@@ -554,9 +552,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     HIP_TRY(c, hipSetDevice(c->device));
     invalidate_pattern(c);
     boundary_drop(c);
-    refine_drop(c);
-    coarsen_drop(c);
-    elevate_drop(c);
+    held_drop_all(c);
     point_index_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
@@ -658,9 +654,7 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     HIP_TRY(c, hipSetDevice(c->device));
     invalidate_pattern(c);
     boundary_drop(c);
-    refine_drop(c);
-    coarsen_drop(c);
-    elevate_drop(c);
+    held_drop_all(c);
     point_index_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;

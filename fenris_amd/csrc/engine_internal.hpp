@@ -281,6 +281,9 @@ using namespace fenris_hip_detail;
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
+// the slots of fh_ctx::held
+enum HeldSlot { HELD_REFINEMENT = 0, HELD_COARSENING = 1, HELD_ELEVATION = 2, HELD_SLOTS = 3 };
+
 struct fh_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -475,9 +478,9 @@ struct fh_ctx {
     fh_mg* mg = nullptr;               // the multigrid hierarchy of FH_PRECOND_MULTIGRID (fh_set_multigrid; not owned)
     fh_amg* amg = nullptr;             // the algebraic hierarchy of FH_PRECOND_AMG (fh_set_amg; not owned)
     struct BoundaryStore* bnd = nullptr;   // boundary faces of the mesh and the adjacency of the last surface-load face list (engine_boundary.hip)
-    struct RefineStore* refined = nullptr;   // the uniform refinement of the mesh and its transfer, held since fh_refine_uniform (engine_refine.hip)
-    struct CoarsenStore* coarsened = nullptr;   // the linear mesh under a quadratic one and its transfer, held since fh_coarsen_degree (engine_coarsen.hip)
-    struct ElevateStore* elevated = nullptr;   // the quadratic mesh over a linear one and its transfer, held since fh_elevate_degree (engine_elevate.hip)
+    // the meshes derived from this one and their transfers (engine_hierarchy.hip), side by side: the uniform refinement held since
+    // fh_refine_uniform, the linear mesh under a quadratic one since fh_coarsen_degree, the quadratic mesh over a linear one since fh_elevate_degree
+    struct HeldMesh* held[HELD_SLOTS] = {};
     struct PointIndex* point_index = nullptr;   // element boxes and cell lists for point location, of the vertices as they are (engine_points.hip)
     DevBuf<double> recover_scratch;    // fh_recover*: element means and volumes of a nodal request, point rows and measures of the quadratic kinds
 
@@ -593,12 +596,8 @@ int amg_precondition(fh_amg* amg, const double* r, double* z);
 void amg_orphan(fh_amg* amg);
 // the cached boundary search and surface-load tables (engine_boundary.hip): dropped with the connectivity, kept by fh_update_vertices
 void boundary_drop(fh_ctx* c);
-// the held uniform refinement (engine_refine.hip): dropped with the mesh
-void refine_drop(fh_ctx* c);
-// the held degree coarsening (engine_coarsen.hip): dropped with the mesh
-void coarsen_drop(fh_ctx* c);
-// the held degree elevation (engine_elevate.hip): dropped with the mesh
-void elevate_drop(fh_ctx* c);
+// the held refinement, degree coarsening and degree elevation (engine_hierarchy.hip): dropped with the mesh
+void held_drop_all(fh_ctx* c);
 // the point-location index (engine_points.hip): dropped with the mesh and with its vertices (fh_update_vertices)
 void point_index_drop(fh_ctx* c);
 // y = K x on the context's pattern with the values of an assembled matrix (engine_solver.hip; fh_spmv_dev without the checks)

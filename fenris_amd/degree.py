@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _ffi
 from .mesh import Mesh
-from .refinement import permute_transfer
+from .refinement import _engine_for_call, permute_transfer
 
 DEGREE_KINDS = tuple(_ffi.LINEAR_KIND)
 
@@ -21,19 +21,12 @@ def coarsen_degree_with_transfer(mesh: Mesh, engine=None):
     """(linear mesh, Transfer, vertex_nodes): the linear mesh on the vertex nodes of `mesh` in the order of their indices, cells and
     their nodes in the order of `mesh`; vertex_nodes[j] is the node of `mesh` that became vertex j.  With an engine: its device pass (the
     mesh becomes the engine's mesh).  Without: an Engine(0) of its own for the call."""
-    if engine is not None:
-        engine.set_mesh(mesh)
-        engine.coarsen_degree()
-        return engine.degree_coarsening()
-    if mesh.elem_kind not in DEGREE_KINDS:
+    if engine is None and mesh.elem_kind not in DEGREE_KINDS:
         raise _ffi.FenrisError(_ffi.FH_UNSUPPORTED, "degree coarsening is implemented for Tet10, Tri6, Quad9, Hex20 and Hex27 meshes only")
-    from .assembly import Engine
-
-    own = Engine(0)
-    try:
-        return coarsen_degree_with_transfer(mesh, own)
-    finally:
-        own.close()
+    with _engine_for_call(engine) as eng:
+        eng.set_mesh(mesh)
+        eng.coarsen_degree()
+        return eng.degree_coarsening()
 
 
 def coarsen_degree(mesh: Mesh, engine=None) -> Mesh:
@@ -46,20 +39,13 @@ def elevate_degree_with_transfer(mesh: Mesh, to_kind, engine=None):
     tet10_mesh_from_tet4 and its siblings, and the transfer from the vertices of `mesh` to its nodes.  With an engine: its device pass
     (the linear mesh becomes the engine's mesh and the engine holds the elevation: Engine.set_mesh_from_degree_elevation).  Without: an
     Engine(0) of its own for the call."""
-    if engine is not None:
-        engine.set_mesh(mesh)
-        engine.elevate_degree(to_kind)
-        return engine.degree_elevation()
-    if _ffi.LINEAR_KIND.get(to_kind) != mesh.elem_kind:
+    if engine is None and _ffi.LINEAR_KIND.get(to_kind) != mesh.elem_kind:
         code = _ffi.FH_BAD_ARGUMENT if mesh.elem_kind in _ffi.LINEAR_KIND.values() else _ffi.FH_UNSUPPORTED
         raise _ffi.FenrisError(code, "degree elevation goes from Tet4 to Tet10, Tri3 to Tri6, Quad4 to Quad9 and Hex8 to Hex20 or Hex27")
-    from .assembly import Engine
-
-    own = Engine(0)
-    try:
-        return elevate_degree_with_transfer(mesh, to_kind, own)
-    finally:
-        own.close()
+    with _engine_for_call(engine) as eng:
+        eng.set_mesh(mesh)
+        eng.elevate_degree(to_kind)
+        return eng.degree_elevation()
 
 
 def elevate_degree(mesh: Mesh, to_kind, engine=None) -> Mesh:

@@ -7,6 +7,7 @@ refiner of an Engine (fh_refine_uniform, all four kinds) and the host sweep fh_r
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 
@@ -44,28 +45,32 @@ class Transfer:
 DEVICE_KINDS = (_ffi.TET4, _ffi.TRI3, _ffi.QUAD4, _ffi.HEX8)
 
 
-def _refine_on_device(mesh: Mesh, engine):
-    engine.set_mesh(mesh)
-    engine.refine_uniformly()
-    return engine.refinement()
+@contextlib.contextmanager
+def _engine_for_call(engine, needed=True):
+    """`engine`, or where there is none and one is needed an Engine(0) of the call's own, closed afterwards"""
+    if engine is not None or not needed:
+        yield engine
+        return
+    from .assembly import Engine
+
+    own = Engine(0)
+    try:
+        yield own
+    finally:
+        own.close()
 
 
 def refine_uniformly_with_transfer(mesh: Mesh, engine=None):
     """(fine mesh, Transfer): every cell split uniformly (Tet4, Hex8: 8 children; Tri3, Quad4: 4), coarse vertices first under their own
     indices.  With an engine: its device refiner (the mesh becomes the engine's mesh).  Without: Hex8 takes the host sweep, the other
     kinds an Engine(0) of their own for the call."""
-    if engine is not None:
-        return _refine_on_device(mesh, engine)
-    if mesh.elem_kind != _ffi.HEX8:
-        if mesh.elem_kind not in DEVICE_KINDS:
+    if engine is not None or mesh.elem_kind != _ffi.HEX8:
+        if engine is None and mesh.elem_kind not in DEVICE_KINDS:
             raise _ffi.FenrisError(_ffi.FH_UNSUPPORTED, "uniform refinement is implemented for Tet4, Tri3, Quad4 and Hex8 meshes only")
-        from .assembly import Engine
-
-        own = Engine(0)
-        try:
-            return _refine_on_device(mesh, own)
-        finally:
-            own.close()
+        with _engine_for_call(engine) as eng:
+            eng.set_mesh(mesh)
+            eng.refine_uniformly()
+            return eng.refinement()
     lib = _ffi.lib()
     v, conn = _ffi.as_f64(mesh.vertices), _ffi.as_u64(mesh.connectivity)
     N, E = mesh.num_nodes(), mesh.num_elements()
@@ -92,39 +97,27 @@ def refine_uniformly(mesh: Mesh, engine=None) -> Mesh:
     return refine_uniformly_with_transfer(mesh, engine)[0]
 
 
-def _with_engine(mesh, engine, n):
-    """(engine to use, whether it is this call's own): one Engine(0) for all n levels of a kind that has no host path"""
-    if engine is None and mesh.elem_kind != _ffi.HEX8 and mesh.elem_kind in DEVICE_KINDS and int(n) > 0:
-        from .assembly import Engine
-
-        return Engine(0), True
-    return engine, False
+def _needs_engine(mesh, n):
+    """whether n refinements of `mesh` need an engine: one Engine(0) then serves all n levels of a kind that has no host path"""
+    return mesh.elem_kind != _ffi.HEX8 and mesh.elem_kind in DEVICE_KINDS and int(n) > 0
 
 
 def refine_uniformly_repeat(mesh: Mesh, n: int, engine=None) -> Mesh:
     """refine_uniformly_repeat (src/mesh/refinement.rs): n uniform refinements"""
-    engine, own = _with_engine(mesh, engine, n)
-    try:
+    with _engine_for_call(engine, _needs_engine(mesh, n)) as eng:
         for _ in range(int(n)):
-            mesh = refine_uniformly(mesh, engine)
-    finally:
-        if own:
-            engine.close()
+            mesh = refine_uniformly(mesh, eng)
     return mesh
 
 
 def refine_uniformly_repeat_with_transfers(mesh: Mesh, n: int, engine=None):
     """(meshes, transfers): meshes[0] is the input, meshes[k + 1] refines meshes[k] through transfers[k] (coarsest first)"""
     meshes, transfers = [mesh], []
-    engine, own = _with_engine(mesh, engine, n)
-    try:
+    with _engine_for_call(engine, _needs_engine(mesh, n)) as eng:
         for _ in range(int(n)):
-            fine, t = refine_uniformly_with_transfer(meshes[-1], engine)
+            fine, t = refine_uniformly_with_transfer(meshes[-1], eng)
             meshes.append(fine)
             transfers.append(t)
-    finally:
-        if own:
-            engine.close()
     return meshes, transfers
 
 

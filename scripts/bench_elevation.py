@@ -24,7 +24,7 @@ import fenris_amd as fa  # noqa: E402
 from fenris_amd import _ffi  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "degree_elevation.jsonl")
-# (labelled slots per cell, of which sorted) of the high kinds: elevate_kernels.hpp
+# (labelled slots per cell, of which sorted) of the high kinds: label_table, engine_hierarchy.hip
 SLOTS = {fa.HEX27: (27, 26), fa.HEX20: (20, 20), fa.TET10: (10, 10), fa.QUAD9: (5, 4), fa.TRI6: (3, 3)}
 
 
