@@ -20,6 +20,8 @@ SCATTER_ATOMIC, SCATTER_COLORED, SCATTER_GATHER = 0, 1, 2
 FH_CG_MAX_ITERATIONS, FH_CG_INDEFINITE_OPERATOR, FH_CG_INDEFINITE_PRECONDITIONER = 7, 8, 9
 FH_NEWTON_MAX_ITERATIONS, FH_NEWTON_JACOBIAN_ERROR, FH_NEWTON_LINE_SEARCH_FAILED = 10, 11, 12
 NEWTON_NO_LINE_SEARCH, NEWTON_BACKTRACKING = 0, 1
+FH_EIG_MAX_ITERATIONS, FH_EIG_BREAKDOWN = 13, 14
+EIG_MAX_BLOCK = 32
 PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, PRECOND_AMG = 0, 1, 2, 3
 AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER = 0, 1, 2
 ASSEMBLE_OVERWRITE = 0x100
@@ -222,6 +224,12 @@ _SIGS = {
     "fh_recover_rows": (C.c_int, [C.c_void_p, C.c_int, u64p]),
     "fh_recover_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fh_recover": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p]),
+    "fh_block_gram_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, f64p]),
+    "fh_block_combine_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, f64p, C.c_void_p, C.c_uint64, C.c_int]),
+    "fh_dense_generalized_eigh": (C.c_int, [C.c_uint32, f64p, f64p, f64p, f64p]),
+    "fh_eigs_lowest_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_int, C.c_double, C.c_uint64, C.c_int, C.c_void_p, f64p, f64p, u64p]),
+    "fh_eigs_lowest": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_int, C.c_double, C.c_uint64, C.c_int, f64p, f64p, f64p, u64p]),
+    "fh_eigs_profile": (C.c_int, [C.c_void_p, f64p]),
     "fh_lame_from_young_poisson":(C.c_int, [C.c_double, C.c_double, f64p, f64p]),
     "fh_morton_partition": (C.c_int, [C.c_uint32, f64p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
     "fh_partition_create": (C.c_void_p, [C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),
@@ -261,6 +269,17 @@ def lib():
 
 def exported_symbols():
     return sorted(_SIGS)
+
+
+def dense_generalized_eigh(A, B):
+    """fh_dense_generalized_eigh on the host (no GPU): A c = w B c for symmetric A and SPD B; returns (status, w ascending, C with C^T B C = I)"""
+    A, B = as_f64(A), as_f64(B)
+    p = A.shape[0]
+    if A.shape != (p, p) or B.shape != (p, p):
+        raise ValueError("A and B must be square and of one size")
+    w, Cm = np.zeros(p), np.zeros((p, p))
+    rc = lib().fh_dense_generalized_eigh(p, fp(A), fp(B), fp(w), fp(Cm))
+    return rc, w, Cm
 
 
 def fp(a):

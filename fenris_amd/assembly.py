@@ -570,6 +570,26 @@ class Engine:
             self._check(rc)
         return rc, stats, norms
 
+    # the block-vector layer of the eigensolver (fenris_amd.eigen): column-major blocks, column j of a block at data_ptr + j ld doubles
+    def block_gram(self, n, p, s_t, lds, q, t_t, ldt):
+        """fh_block_gram_dev: G = S^T T (p x q numpy array) for the device blocks S (n x p, ld lds) and T (n x q, ld ldt)"""
+        g = np.zeros((max(int(p), 1), max(int(q), 1)))
+        self._check(self._lib.fh_block_gram_dev(self._h, int(n), int(p), _ptr(s_t), int(lds), int(q), _ptr(t_t), int(ldt), _ffi.fp(g)))
+        return g
+
+    def block_combine(self, n, p, s_t, lds, c, y_t, ldy, accumulate=False):
+        """fh_block_combine_dev: Y = S C (accumulate: Y += S C) with the host matrix c (p x q); Y may not overlap S"""
+        c = _ffi.as_f64(c)
+        self._check(self._lib.fh_block_combine_dev(self._h, int(n), int(p), _ptr(s_t), int(lds), int(c.shape[1]), _ffi.fp(c), _ptr(y_t), int(ldy),
+                                                   int(bool(accumulate))))
+
+    def dense_generalized_eigh(self, A, B):
+        """fh_dense_generalized_eigh (host): (w ascending, C with C^T B C = I) of A c = w B c"""
+        rc, w, cm = _ffi.dense_generalized_eigh(A, B)
+        if rc != _ffi.FH_OK:
+            raise FenrisError(rc, "fh_dense_generalized_eigh: B is not positive definite" if rc == _ffi.FH_EIG_BREAKDOWN else "bad argument")
+        return w, cm
+
     def apply_dirichlet_csr_dev(self, values_t, nodes):
         nodes = _ffi.as_u64(nodes)
         self._check(self._lib.fh_apply_dirichlet_csr_dev(self._h, C.c_void_p(values_t.data_ptr()), _ffi.up(nodes), len(nodes)))

@@ -483,6 +483,7 @@ struct fh_ctx {
     struct HeldMesh* held[HELD_SLOTS] = {};
     struct PointIndex* point_index = nullptr;   // element boxes and cell lists for point location, of the vertices as they are (engine_points.hip)
     DevBuf<double> recover_scratch;    // fh_recover*: element means and volumes of a nodal request, point rows and measures of the quadratic kinds
+    double eig_profile[8] = {};        // fh_eigs_lowest*: seconds per phase of the last solve (fh_eigs_profile; engine_eigs.hip)
 
     int S() const {
         if (ragged) return (int)sdim_ragged;
@@ -539,7 +540,8 @@ struct DevGuard {
 
 // ---- functions shared by the translation units of the engine (engine.hip: context, mesh, pattern, options; engine_partition.hip: owner
 // blocks and position tables; engine_matrix.hip: stiffness / mass launchers; engine_two_pass.hip: dense element matrices + row gather;
-// engine_vector.hip: residual, source, energy; engine_solver.hip: Dirichlet rows, SpMV, PCG, error integrals)
+// engine_vector.hip: residual, source, energy; engine_solver.hip: Dirichlet rows, SpMV, PCG, error integrals; engine_eigs.hip: block vectors
+// and the LOBPCG eigensolver)
 constexpr size_t LDS_TARGET = 64 * 1024;   // two workgroups per CU
 constexpr size_t LDS_LIMIT = 160 * 1024;   // hardware limit per workgroup
 inline bool generic_fast(const fh_ctx* c) { return c->fast_ok && (!c->has_rules || c->op == FH_LAPLACE); }

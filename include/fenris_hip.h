@@ -57,7 +57,11 @@ enum {
      * PCG: fh_newton_solve's stats[3] holds its code), LineSearchError */
     FH_NEWTON_MAX_ITERATIONS = 10,
     FH_NEWTON_JACOBIAN_ERROR = 11,
-    FH_NEWTON_LINE_SEARCH_FAILED = 12
+    FH_NEWTON_LINE_SEARCH_FAILED = 12,
+    /* the eigensolver (fh_eigs_lowest): max_iter exhausted before every pair met the criterion; a Cholesky factor or the dense
+     * Rayleigh-Ritz problem met a pivot that is not positive (also fh_dense_generalized_eigh on its own) */
+    FH_EIG_MAX_ITERATIONS = 13,
+    FH_EIG_BREAKDOWN = 14
 };
 
 /* element kinds: Quad4d2Element (src/element/quadrilateral.rs:70-142), Hex8Element
@@ -693,6 +697,64 @@ int fh_newton_solve_dev(fh_ctx*, double alpha, double beta, const double* f_dev,
 /* the same with host arrays */
 int fh_newton_solve(fh_ctx*, double alpha, double beta, const double* f, const double* u_ref, double* u, double tolerance, uint64_t max_iterations,
                     int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter, uint64_t* stats, double* norms);
+/* ---- the lowest eigenpairs of  T(u) phi = lambda M phi  (natural frequencies and mode shapes; the stiffness of a prestressed state; the
+ * smallest eigenvalue of a Newton iterate's tangent), matrix-free: T(u) is fh_apply_tangent_dev's map at the context's u (Laplace,
+ * LinearElastic: K), M the mass of fh_set_mass_density.  The problem is restricted to the dofs that are not Dirichlet
+ * (fh_set_operator_dirichlet_nodes): iterates, residuals and results are zero on the constrained dofs, so the pair scale_K / scale_M of
+ * the modified matrices does not appear.
+ *
+ * Block vectors are column-major: column j is a contiguous n-vector at base + j ld, ld >= n, n = s N < 2^31.  Two kernels of the block
+ * layer are reachable on their own:
+ *   fh_block_gram_dev     G = S^T T, S n x p and T n x q on the device, 1 <= p, q <= 96, G p x q row-major on the host.  At most 1024
+ *                         workgroups own one contiguous row range each and leave a partial tile; the partials are summed in workgroup order
+ *                         (no floating-point atomics): the result repeats bit for bit and does not depend on the rows between n and ld.
+ *   fh_block_combine_dev  Y = S C (accumulate != 0: Y += S C), C p x q row-major on the host, Y n x q on the device; Y may not overlap S;
+ *                         rows >= n of Y are not touched.
+ * Both: FH_BAD_ARGUMENT for a null pointer, p or q of 0 or above 96, ld < n, n >= 2^31; n == 0 is FH_OK (G zero).
+ *
+ * fh_dense_generalized_eigh: A c = w B c for symmetric A and symmetric positive definite B (p x p row-major, 1 <= p <= 96) on the host, by
+ * Cholesky of B and cyclic Jacobi on L^-1 A L^-T: w ascending, the columns of C the vectors with C^T B C = I.  Needs no context and no
+ * GPU.  FH_BAD_ARGUMENT: null pointer, p of 0 or above 96; FH_EIG_BREAKDOWN: a pivot of B is not positive, or an entry is not finite.
+ *
+ * fh_eigs_lowest(_dev): Knyazev's LOBPCG on the basis [X W P] for the lowest m pairs, 1 <= m <= FH_EIG_MAX_BLOCK.
+ *   - W = B R on the columns that have not converged, R = K X - theta M X, B the preconditioner of shift M + T(u): FH_PRECOND_IDENTITY,
+ *     FH_PRECOND_JACOBI (the inverse of fh_shifted_tangent_diagonal_dev(shift, 1)) or FH_PRECOND_MULTIGRID (one V-cycle of the attached
+ *     hierarchy per column).  W is M-orthogonalised against X, then W and P are M-orthonormalised by Cholesky of their Gram matrices.
+ *   - K X, M X, K P, M P follow by recombination; only W goes through the maps (two applications per active column and iteration).
+ *   - Rayleigh-Ritz on [X W P] with both Gram matrices formed in full (fh_dense_generalized_eigh); the new X and the new P come from one
+ *     read of the basis.
+ *   - criterion per column: ||r_i||_2 <= tol (|theta_i| + shift) ||M x_i||_2.  A column that meets it leaves the active set (soft locking:
+ *     no W or P for it, but it stays in X for the Rayleigh-Ritz step).  On a free body pass shift > 0 of the order of the first elastic
+ *     eigenvalue: the rigid modes (theta ~ 0) are then a reachable target and the preconditioner's matrix is definite.
+ *   - a Cholesky or Rayleigh-Ritz breakdown restarts the iteration once without P; a second one returns FH_EIG_BREAKDOWN.
+ *   - once every column meets the criterion, K X and M X are applied afresh and one Rayleigh-Ritz step on X alone makes X M-orthonormal and
+ *     theta ascending; the criterion is tested again on these residuals (and the iteration goes on if a column misses it).  The same step
+ *     opens the solve, so a guess that already meets the criterion returns after 0 iterations.
+ * use_guess == 0: X is filled by the library, X(dof, j) = (splitmix64((j << 32) | dof) >> 11) 2^-52 - 1 in [-1, 1) with
+ *   splitmix64(z): z += 0x9e3779b97f4a7c15; z = (z ^ z >> 30) 0xbf58476d1ce4e5b9; z = (z ^ z >> 27) 0x94d049bb133111eb; z ^ z >> 31,
+ * so a solve needs no input and repeats.  use_guess != 0: the m columns in X are the start block (their Dirichlet entries are zeroed).
+ * X: n x m, ld = n (device for _dev); theta: m on the host; residual_norms (host, m, may be null): ||r_i||_2 of the returned pairs;
+ * stats (may be null): [0] iterations, [1] map applications, [2] preconditioner applications, [3] restarts.
+ * Errors: FH_EIG_MAX_ITERATIONS when max_iter (0: no limit) is exhausted and FH_EIG_BREAKDOWN -- in both cases the pairs reached so far are
+ * handed back (X M-orthonormal, theta its Rayleigh quotients); FH_INVALID_STATE without a density or for FH_PRECOND_MULTIGRID without a
+ * hierarchy; FH_UNSUPPORTED for the mass operators and FH_TENSOR; FH_BAD_ARGUMENT for a null X or theta, m of 0, above FH_EIG_MAX_BLOCK or
+ * above a third of the free dofs, shift < 0 or not finite, tol not finite, an unknown preconditioner; FH_SINGULAR_JACOBIAN from the maps.
+ * No floating-point atomics anywhere: a solve repeats bit for bit, and the host and device entry points return the same bits.  The host
+ * waits for the device once per Gram matrix (the small dense problem lives on the host).  Device memory: 17 n m doubles.
+ * With FENRIS_HIP_EIGS_PROFILE set when the context was created, the solver waits for the device after every phase and fh_eigs_profile
+ * returns the seconds of the last solve: [0] map applications, [1] preconditioning, [2] Gram matrices, [3] recombinations, [4] residuals,
+ * [5] dense host work, [6] other, [7] the whole solve (without the variable only [7] is filled). */
+enum { FH_EIG_MAX_BLOCK = 32 };
+int fh_block_gram_dev(fh_ctx*, uint64_t n, uint32_t p, const double* S_dev, uint64_t lds, uint32_t q, const double* T_dev, uint64_t ldt,
+                      double* G);
+int fh_block_combine_dev(fh_ctx*, uint64_t n, uint32_t p, const double* S_dev, uint64_t lds, uint32_t q, const double* C, double* Y_dev,
+                         uint64_t ldy, int accumulate);
+int fh_dense_generalized_eigh(uint32_t p, const double* A, const double* B, double* w, double* C);
+int fh_eigs_lowest_dev(fh_ctx*, uint32_t m, double shift, int preconditioner, double tol, uint64_t max_iter, int use_guess, double* X_dev,
+                       double* theta, double* residual_norms, uint64_t* stats);
+int fh_eigs_lowest(fh_ctx*, uint32_t m, double shift, int preconditioner, double tol, uint64_t max_iter, int use_guess, double* X, double* theta,
+                   double* residual_norms, uint64_t* stats);
+int fh_eigs_profile(fh_ctx*, double* seconds);
 /* Geometric multigrid for the matrix-free solvers (FH_PRECOND_MULTIGRID of fh_cg_solve_matrix_free, fh_cg_solve_tangent,
  * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity, Jacobi or FH_PRECOND_AMG).  Every level is an
  * ordinary context with its own mesh, operator (Laplace, LinearElastic, NeoHookean or StVK), quadrature, data, density and
