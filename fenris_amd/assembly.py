@@ -187,6 +187,21 @@ class Engine:
         self._check(self._lib.fh_affine_stats(self._h, C.byref(a), C.byref(b), C.byref(g)))
         return int(a.value), int(b.value), int(g.value)
 
+    def affine_shared_stats(self):
+        """fh_affine_shared_stats: {"shared", "records", "lists", "reason"} of the last affine sweep"""
+        on, nrec, nvec, why = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_char_p()
+        self._check(self._lib.fh_affine_shared_stats(self._h, C.byref(on), C.byref(nrec), C.byref(nvec), C.byref(why)))
+        return {"shared": bool(on.value), "records": int(nrec.value), "lists": int(nvec.value), "reason": (why.value or b"").decode()}
+
+    def affine_slot_elements(self):
+        """fh_affine_slot_elements (internal, for tests): int32 array [node blocks of the affine kernel, slots] of element ids, -1 for an empty slot"""
+        us, npos = C.c_int(0), C.c_uint64(0)
+        self._check(self._lib.fh_affine_slot_elements(self._h, C.byref(us), C.byref(npos), None))
+        out = np.empty((int(npos.value), int(us.value)), dtype=np.int32)
+        if out.size:
+            self._check(self._lib.fh_affine_slot_elements(self._h, C.byref(us), C.byref(npos), C.c_void_p(out.ctypes.data)))
+        return out
+
     # pattern
     def pattern(self, want_cols=True):
         R = self.num_rows()

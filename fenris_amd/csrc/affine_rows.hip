@@ -51,7 +51,7 @@ size_t affine_rows_lds_bytes(int op, int us, int acc_max) {
     return sizeof(double) * ((size_t)65 * gw + (size_t)2 * us * gw + 2 * accp) + 4 * sizeof(int4) + 2 * 256 * sizeof(uint2) + 64;   // (+ 64: where the lanes without a block write)
 }
 
-template <int OP, bool OVERWRITE, bool DBG, int DEPTH, int NSTORE, bool MASKED>
+template <int OP, bool OVERWRITE, bool DBG, int DEPTH, int NSTORE, bool MASKED, bool SHARED = false>
 __global__ void __launch_bounds__(320 + 64 * NSTORE, 5)
 k_affine_rows(const KArgs a, const AffineRowTables T, const int ablate_arg) {
     constexpr int NT = 320 + 64 * NSTORE;
@@ -256,6 +256,8 @@ k_affine_rows(const KArgs a, const AffineRowTables T, const int ablate_arg) {
 
 
     // ring entry .w: head | extent of the position's rows in doubles << 4 (what an incomplete position clears, below)
+    // (unmasked: head | header word << 8, of which only the head, `& 15`, is ever read -- bits 8 and up of the header word belong to the shared
+    // tables, k_affine_shared_verify_lists, so whoever wants the slot count from it masks with 0xff)
     auto with_head = [&](int4 h) { h.w = MASKED ? (head_of(h.x) | ((SS * h.y) << 4)) : (head_of(h.x) | (h.w << 8)); return h; };
     if (wave == 4) {
         // ------------------------------------------------------------------------------------------ loader wave
@@ -294,6 +296,98 @@ k_affine_rows(const KArgs a, const AffineRowTables T, const int ablate_arg) {
             o.z = (hq.z & 9) | (slot << 1) | (changed ? 4 : 0) | (beyond ? 16 : 0) | (hq.z & ~0xff);
             return o;
         };
+        if constexpr (SHARED) {
+            // Shared form (unmasked sweeps of a mesh whose affine elements have few distinct records -- structured, graded, extruded boxes;
+            // launch_affine builds and verifies the tables): a slot's record comes from rec_tab[class], the classes of a position's slots from
+            // slot_tab[list], the list's id from the fourth word of the position header.  Both tables are a few hundred KB that every workgroup
+            // touches all the time, so these reads are answered by the caches and only the headers still come from memory, beside the row
+            // stores.  Everything lands in the same places of LDS at the same depth as in the per-element form below: the row waves and the
+            // store wave cannot tell the two apart.  One level of indirection more (header -> list -> records), so the list ids run
+            // 1 + 3 DEPTH positions ahead, fetched as single words of headers that the ring asks for in full a little later.
+            static_assert(!MASKED && !DBG, "the shared loader serves the unmasked production instantiations");
+            auto list_of = [&](int q) { return __builtin_amdgcn_readfirstlane(T.hdr[min(q, npos - 1)].w) >> 8; };   // (prologue)
+            auto load_cls = [&](int id, int r) { return (int)T.slot_tab[(size_t)((unsigned)id * (unsigned)T.us + (unsigned)slot_of(r))]; };
+            // (an empty slot, 0xffff, reads class 0 as an empty slot of the per-element form reads element 0: no lane with a term uses it)
+            auto load_rec = [&](int cl, int r) { return reinterpret_cast<const f64x2*>(T.rec_tab)[(size_t)(unsigned)(cl == 0xffff ? 0 : cl) * NPC + piece_of(r)]; };
+            int4 hq0 = T.hdr[p_begin], hq1 = T.hdr[min(p_begin + 1, npos - 1)];
+            int slot_cur = 0;
+            int id_prev = hq0.z >> 8;
+            {
+                const uint4 t0 = load_tab(id_prev, 0), t1 = load_tab(id_prev, 1);
+                park_tab(0, 0, t0); park_tab(0, 1, t1);
+                const bool ch1 = (hq1.z >> 8) != id_prev;
+                if (ch1) { const uint4 u0 = load_tab(hq1.z >> 8, 0), u1 = load_tab(hq1.z >> 8, 1); park_tab(1, 0, u0); park_tab(1, 1, u1); slot_cur = 1; }
+                if (lane == 0) { HDR[p_begin & 3] = ring_entry(hq0, 0, true, false); HDR[(p_begin + 1) & 3] = ring_entry(hq1, slot_cur, ch1, p_begin + 1 >= p_end); }
+                id_prev = hq1.z >> 8;
+            }
+            // Stage k belongs to the positions p with (p - p_begin) mod DEPTH = k.  While p is current it holds the records of p + 1 (parked
+            // now), the classes of p + 1 + DEPTH (their records are requested now), the list id of p + 1 + 2 DEPTH (its classes are requested
+            // now -- unless it is the list the stage already holds: those registers have arrived, the list of the position right before is
+            // still on its way) and the header of p + 2.
+            f64x2 piece[DEPTH][ROUNDS];
+            int c_nxt[DEPTH][ROUNDS];
+            int w_nxt[DEPTH], list_cur[DEPTH];
+            int4 h_nxt[DEPTH];
+            uint4 tab0 = {0, 0, 0, 0}, tab1 = {0, 0, 0, 0};
+            bool tab_pending = false;
+            int slot_pending = 0;
+            {
+                const int l0 = hq0.w >> 8;
+#pragma unroll
+                for (int r = 0; r < ROUNDS; ++r) park_piece(0, r, load_rec(load_cls(l0, r), r));
+            }
+#pragma unroll
+            for (int k = 0; k < DEPTH; ++k) {
+                h_nxt[k] = T.hdr[min(p_begin + k + 2, npos - 1)];
+                const int l1 = list_of(p_begin + k + 1);
+                list_cur[k] = list_of(p_begin + k + 1 + DEPTH);
+                w_nxt[k] = T.hdr[min(p_begin + k + 1 + 2 * DEPTH, npos - 1)].w;
+#pragma unroll
+                for (int r = 0; r < ROUNDS; ++r) {
+                    const int c1 = load_cls(l1, r);
+                    c_nxt[k][r] = load_cls(list_cur[k], r);
+                    piece[k][r] = load_rec(c1, r);
+                }
+            }
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see the row waves
+            lds_barrier();  // B0
+            tr_start();
+            int par = 0;
+#define AFFINE_SHARED_LOADER_STEP(k, p)                                                                                       \
+            {                                                                                                                 \
+                _Pragma("unroll") for (int r = 0; r < ROUNDS; ++r) {                                                          \
+                    park_piece(par ^ 1, r, piece[k][r]);              /* records of p + 1 */                                  \
+                    piece[k][r] = load_rec(c_nxt[k][r], r);           /* records of p + 1 + DEPTH */                          \
+                }                                                                                                             \
+                const int l2 = __builtin_amdgcn_readfirstlane(w_nxt[k]) >> 8;   /* list of p + 1 + 2 DEPTH */                \
+                if (l2 != list_cur[k]) {                                                                                      \
+                    _Pragma("unroll") for (int r = 0; r < ROUNDS; ++r) c_nxt[k][r] = load_cls(l2, r);                         \
+                    list_cur[k] = l2;                                                                                         \
+                }                                                                                                             \
+                w_nxt[k] = T.hdr[min((p) + 1 + 3 * DEPTH, npos - 1)].w;                                                       \
+                if (tab_pending) { park_tab(slot_pending, 0, tab0); park_tab(slot_pending, 1, tab1); tab_pending = false; }   \
+                const int id2 = __builtin_amdgcn_readfirstlane(h_nxt[k].z) >> 8;                                              \
+                const bool ch2 = id2 != id_prev;                                                                              \
+                const int slot2 = ch2 ? (slot_cur ^ 1) : slot_cur;                                                            \
+                if (lane == 0) HDR[((p) + 2) & 3] = ring_entry(h_nxt[k], slot2, ch2, (p) + 2 >= p_end);                       \
+                if (ch2) { tab0 = load_tab(id2, 0); tab1 = load_tab(id2, 1); tab_pending = true; slot_pending = slot2; }      \
+                slot_cur = slot2;                                                                                             \
+                id_prev = id2;                                                                                                \
+                h_nxt[k] = T.hdr[min((p) + 2 + DEPTH, npos - 1)];                                                             \
+                tr_barrier();                                                                                                 \
+                par ^= 1;                                                                                                     \
+            }
+            int p0 = p_begin;
+            for (; p0 + DEPTH <= p_end; p0 += DEPTH) {
+#pragma unroll
+                for (int k = 0; k < DEPTH; ++k) AFFINE_SHARED_LOADER_STEP(k, p0 + k)
+            }
+#pragma unroll
+            for (int k = 0; k < DEPTH - 1; ++k)
+                if (p0 + k < p_end) AFFINE_SHARED_LOADER_STEP(k, p0 + k)
+#undef AFFINE_SHARED_LOADER_STEP
+            return;
+        }
         // prologue: ring entries, lane tables and records of p_begin (and what p_begin + 1 needs), fetches for the next ones
         int4 hq0 = T.hdr[p_begin], hq1 = T.hdr[min(p_begin + 1, npos - 1)];
         int slot_cur = 0;                                              // table slot of position p + 1 while p is current
@@ -996,22 +1090,149 @@ hipError_t affine_rows_compact(hipStream_t stream, const uint2* lanes_full, cons
     return hipGetLastError();
 }
 
-template <int OP, int DEPTH, int NSTORE, bool MASKED>
+// ------------------------------------------------------------------------------------------------ shared records and slot lists
+// the two mixers of the lane-table hashes (k_build_affine_rows), over a sequence of 64-bit words
+__device__ inline void shared_hash_step(unsigned long long w, unsigned i, unsigned long long& h1, unsigned long long& h2) {
+    unsigned long long z = w + 0x9E3779B97F4A7C15ull * (unsigned long long)(i + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    h1 += z ^ (z >> 31);
+    unsigned long long y = (w ^ 0xD6E8FEB86659FD93ull) * (2ull * (unsigned long long)i + 0xC2B2AE3D27D4EB4Full);
+    y = (y ^ (y >> 32)) * 0xFF51AFD7ED558CCDull;
+    y = (y ^ (y >> 29)) * 0xC4CEB9FE1A85EC53ull;
+    h2 += y ^ (y >> 32);
+}
+
+template <int GW>
+__global__ void __launch_bounds__(256) k_affine_shared_hash_records(const double* rec, const unsigned char* elem_aff, long long e_first, long long e_end,
+                                                                    unsigned long long* hash) {
+    const long long n = e_end - e_first, i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long e = e_first + i;
+    unsigned long long h1 = 0ull, h2 = 0ull;
+    if (elem_aff[e]) {
+        const unsigned long long* w = reinterpret_cast<const unsigned long long*>(rec) + (size_t)e * GW;
+#pragma unroll
+        for (int k = 0; k < GW; ++k) shared_hash_step(w[k], (unsigned)k, h1, h2);
+        h2 |= 1ull;   // (0, 0) is "not affine"
+    }
+    hash[i] = h1;
+    hash[n + i] = h2;
+}
+
+template <int GW>
+__global__ void __launch_bounds__(256) k_affine_shared_gather_records(const double* rec, const long long* first, int nrec, double* rec_tab) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < nrec * GW) rec_tab[i] = rec[(size_t)first[i / GW] * GW + (i % GW)];
+}
+
+template <int GW>
+__global__ void __launch_bounds__(256) k_affine_shared_verify_records(const double* rec, const unsigned char* elem_aff, const unsigned short* cls,
+                                                                      const double* rec_tab, int nrec, long long e_first, long long e_end, int* mismatch) {
+    const long long e = e_first + (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= e_end || !elem_aff[e]) return;
+    const int cl = cls[e];
+    if (cl >= nrec) { *mismatch = 1; return; }
+    const unsigned long long* w = reinterpret_cast<const unsigned long long*>(rec) + (size_t)e * GW;
+    const unsigned long long* t = reinterpret_cast<const unsigned long long*>(rec_tab) + (size_t)cl * GW;
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < GW; ++k) same = same && w[k] == t[k];
+    if (!same) *mismatch = 1;
+}
+
+hipError_t affine_shared_hash_records(int gw, hipStream_t stream, const double* rec, const unsigned char* elem_aff, long long e_first, long long e_end,
+                                      unsigned long long* hash) {
+    if (e_end <= e_first) return hipSuccess;
+    const dim3 grid((unsigned)((e_end - e_first + 255) / 256));
+    if (gw == AFFINE_ROWS_GW_LAP) hipLaunchKernelGGL(k_affine_shared_hash_records<AFFINE_ROWS_GW_LAP>, grid, dim3(256), 0, stream, rec, elem_aff, e_first, e_end, hash);
+    else hipLaunchKernelGGL(k_affine_shared_hash_records<AFFINE_ROWS_GW_LE>, grid, dim3(256), 0, stream, rec, elem_aff, e_first, e_end, hash);
+    return hipGetLastError();
+}
+
+hipError_t affine_shared_record_table(int gw, hipStream_t stream, const double* rec, const unsigned char* elem_aff, const unsigned short* cls,
+                                      const long long* first, int nrec, long long e_first, long long e_end, double* rec_tab, int* mismatch) {
+    if (e_end <= e_first || nrec <= 0) return hipSuccess;
+    const dim3 gt((unsigned)((nrec * gw + 255) / 256)), gv((unsigned)((e_end - e_first + 255) / 256));
+    if (gw == AFFINE_ROWS_GW_LAP) {
+        hipLaunchKernelGGL(k_affine_shared_gather_records<AFFINE_ROWS_GW_LAP>, gt, dim3(256), 0, stream, rec, first, nrec, rec_tab);
+        hipLaunchKernelGGL(k_affine_shared_verify_records<AFFINE_ROWS_GW_LAP>, gv, dim3(256), 0, stream, rec, elem_aff, cls, rec_tab, nrec, e_first, e_end, mismatch);
+    } else {
+        hipLaunchKernelGGL(k_affine_shared_gather_records<AFFINE_ROWS_GW_LE>, gt, dim3(256), 0, stream, rec, first, nrec, rec_tab);
+        hipLaunchKernelGGL(k_affine_shared_verify_records<AFFINE_ROWS_GW_LE>, gv, dim3(256), 0, stream, rec, elem_aff, cls, rec_tab, nrec, e_first, e_end, mismatch);
+    }
+    return hipGetLastError();
+}
+
+// the list of position p: the class of every slot's element, 0xffff for an empty slot
+__device__ inline unsigned shared_slot_class(const int* elem, const unsigned short* cls, int p, int us, int s) {
+    const int e = elem[(size_t)p * us + s];
+    return e < 0 ? 0xffffu : (unsigned)cls[e];
+}
+
+__global__ void __launch_bounds__(256) k_affine_shared_hash_lists(const int* elem, const unsigned short* cls, int npos, int us, unsigned long long* hash) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npos) return;
+    unsigned long long h1 = 0ull, h2 = 0ull;
+    for (int s = 0; s < us; ++s) shared_hash_step(shared_slot_class(elem, cls, p, us, s), (unsigned)s, h1, h2);
+    hash[p] = h1;
+    hash[(size_t)npos + p] = h2;
+}
+
+__global__ void __launch_bounds__(256) k_affine_shared_gather_lists(const int* elem, const unsigned short* cls, const int* first_pos, int nvec, int us,
+                                                                    unsigned short* slot_tab) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < nvec * us) slot_tab[i] = (unsigned short)shared_slot_class(elem, cls, first_pos[i / us], us, i % us);
+}
+
+__global__ void __launch_bounds__(256) k_affine_shared_verify_lists(const int* elem, const unsigned short* cls, const int* ids, const unsigned short* slot_tab,
+                                                                    int npos, int nvec, int us, int4* hdr, int* mismatch) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npos) return;
+    const int id = ids[p];
+    bool same = id >= 0 && id < nvec;
+    for (int s = 0; same && s < us; ++s) {
+        const unsigned cl = shared_slot_class(elem, cls, p, us, s);
+        // (an element without a class -- not affine -- in a slot of an affine position cannot happen; it would read as an empty slot)
+        same = cl == (unsigned)slot_tab[(size_t)id * us + s] && (cl != 0xffffu || elem[(size_t)p * us + s] < 0);
+    }
+    if (!same) { *mismatch = 1; return; }
+    hdr[p].w = (hdr[p].w & 0xff) | (id << 8);
+}
+
+hipError_t affine_shared_hash_lists(hipStream_t stream, const int* elem, const unsigned short* cls, int npos, int us, unsigned long long* hash) {
+    if (npos <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_affine_shared_hash_lists, dim3((npos + 255) / 256), dim3(256), 0, stream, elem, cls, npos, us, hash);
+    return hipGetLastError();
+}
+
+hipError_t affine_shared_list_table(hipStream_t stream, const int* elem, const unsigned short* cls, const int* ids, const int* first_pos, int npos,
+                                    int nvec, int us, unsigned short* slot_tab, int4* hdr, int* mismatch) {
+    if (npos <= 0 || nvec <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_affine_shared_gather_lists, dim3((nvec * us + 255) / 256), dim3(256), 0, stream, elem, cls, first_pos, nvec, us, slot_tab);
+    hipLaunchKernelGGL(k_affine_shared_verify_lists, dim3((npos + 255) / 256), dim3(256), 0, stream, elem, cls, ids, slot_tab, npos, nvec, us, hdr, mismatch);
+    return hipGetLastError();
+}
+
+template <int OP, int DEPTH, int NSTORE, bool MASKED, bool SHARED>
 static auto affine_rows_pick(bool ow, bool dbg) -> void (*)(const KArgs, const AffineRowTables, int) {
+    if constexpr (SHARED) return ow ? k_affine_rows<OP, true, false, DEPTH, NSTORE, false, true> : k_affine_rows<OP, false, false, DEPTH, NSTORE, false, true>;
     if (dbg) return k_affine_rows<OP, true, true, DEPTH, NSTORE, MASKED>;
     return ow ? k_affine_rows<OP, true, false, DEPTH, NSTORE, MASKED> : k_affine_rows<OP, false, false, DEPTH, NSTORE, MASKED>;
 }
-template <int OP, bool MASKED>
+template <int OP, bool MASKED, bool SHARED = false>
 static auto affine_rows_pick_variant(int depth, bool ow, bool dbg) -> void (*)(const KArgs, const AffineRowTables, int) {
     // depth 3 and beyond: the loader's stages no longer fit the register budget of five waves per SIMD (measured slower); a second store wave
     // (NSTORE = 2) was measured and is no longer instantiated
-    return depth <= 1 ? affine_rows_pick<OP, 1, 1, MASKED>(ow, dbg) : affine_rows_pick<OP, 2, 1, MASKED>(ow, dbg);
+    return depth <= 1 ? affine_rows_pick<OP, 1, 1, MASKED, SHARED>(ow, dbg) : affine_rows_pick<OP, 2, 1, MASKED, SHARED>(ow, dbg);
 }
 
 hipError_t affine_rows_launch(int op, int depth, int grid, size_t lds_bytes, hipStream_t stream, const KArgs& a, const AffineRowTables& T, int ablate,
-                              bool masked) {
+                              bool masked, bool shared) {
     const bool ow = a.overwrite != 0, dbg = (ablate & 0xffff) != 0;
+    if (shared && (masked || dbg)) return hipErrorInvalidValue;   // (no such instantiation: the caller keeps the per-element tables there)
     void (*kern)(const KArgs, const AffineRowTables, int) =
+        shared ? (op == FH_LAPLACE ? affine_rows_pick_variant<FH_LAPLACE, false, true>(depth, ow, false) : affine_rows_pick_variant<FH_LINEAR_ELASTIC, false, true>(depth, ow, false)) :
         masked ? (op == FH_LAPLACE ? affine_rows_pick_variant<FH_LAPLACE, true>(depth, ow, dbg) : affine_rows_pick_variant<FH_LINEAR_ELASTIC, true>(depth, ow, dbg))
                : (op == FH_LAPLACE ? affine_rows_pick_variant<FH_LAPLACE, false>(depth, ow, dbg) : affine_rows_pick_variant<FH_LINEAR_ELASTIC, false>(depth, ow, dbg));
     if (lds_bytes > 48 * 1024) {

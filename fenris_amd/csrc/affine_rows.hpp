@@ -11,10 +11,19 @@ namespace fenris_hip {
 struct AffineRowTables {
     const int4* hdr;      // [npos]       {r0: first node-level CSR entry, nrow: node-level entries of the block's rows,
                           //               flags (bit 0: every (node, column) block of the rows has an owner lane) | lane table << 8,
-                          //               number of slots}
+                          //               number of slots (bits 0-7) | id of the position's slot list << 8 once the shared tables were
+                          //               built -- also after a build that ended in a mismatch: readers of the count mask with 0xff}
     const uint2* lanes;   // [ntab][256]  lane records, see affine_rows.hip; positions with identical records share a table
-    const int* elem;      // [npos][us]   element id per slot (-1: empty)
-    const double* rec;    // [E][GW]      element records (R or M) as affine_records_launch left them
+    // The shared form of the loader (affine_rows_launch: shared) reads slot_tab and rec_tab INSTEAD of elem and rec: they share the two places,
+    // so that the argument block of the other instantiations -- and with it their instruction streams -- stays exactly what it was.
+    union {
+        const int* elem;                  // [npos][us]   element id per slot (-1: empty)
+        const unsigned short* slot_tab;   // [nvec][us]   record class per slot (0xffff: empty); the list of a position: fourth word of its header >> 8
+    };
+    union {
+        const double* rec;                // [E][GW]      element records (R or M) as affine_records_launch left them
+        const double* rec_tab;            // [nrec][GW]   the distinct records among them (affine_shared_* below)
+    };
     const double* ghat;   // [64][GW]     reference blocks Ghat_ab (all 64 (a, b); LinearElastic GW = 10, Laplace GW = 6)
     int us, npos, acc_max;  // slots per position, positions of this launch, largest S * S * nrow
     int pos0, npos_all;     // first position of this launch (launches may cover a part of the sweep), positions in the tables
@@ -68,7 +77,25 @@ hipError_t affine_rows_compact(hipStream_t stream, const uint2* lanes_full, cons
 // op: FH_LAPLACE or FH_LINEAR_ELASTIC; depth (1 or 2): positions the loader wave's requests run ahead; ablate != 0 selects the instrumented
 // instantiation (profiling only).  (Retired to scripts/attic/: the fused form whose seventh wavefront formed the element records, the chunked
 // dealing of positions, a second store wave, and the ring form affine_ring.hip.)
+// shared: T holds slot_tab / rec_tab (unmasked, not instrumented: anything else is an error)
 hipError_t affine_rows_launch(int op, int depth, int grid, size_t lds_bytes, hipStream_t stream, const KArgs& a, const AffineRowTables& T, int ablate,
-                              bool masked);
+                              bool masked, bool shared = false);
+
+// ---- shared records and slot lists (structured, graded, extruded meshes: most affine elements have bit-identical records).  The engine
+// (launch_affine) merges on the host what these hash on the device, and uses the tables only after the two verify passes found every
+// element's record and every position's list equal, bit for bit, to the table entry it was given.
+// two 64-bit hashes of the record of every affine element of [e_first, e_end): hash[e - e_first] and hash[n + e - e_first], n = e_end - e_first;
+// the second hash of an affine element is odd, an element that is not affine gets (0, 0)
+hipError_t affine_shared_hash_records(int gw, hipStream_t stream, const double* rec, const unsigned char* elem_aff, long long e_first, long long e_end,
+                                      unsigned long long* hash);
+// rec_tab[c] = rec[first[c]]; then every affine element of [e_first, e_end) compares its record with rec_tab[cls[e]]: *mismatch = 1 on any difference
+hipError_t affine_shared_record_table(int gw, hipStream_t stream, const double* rec, const unsigned char* elem_aff, const unsigned short* cls,
+                                      const long long* first, int nrec, long long e_first, long long e_end, double* rec_tab, int* mismatch);
+// two 64-bit hashes of every position's list {cls[elem[p][s]] or 0xffff}: hash[p] and hash[npos + p]
+hipError_t affine_shared_hash_lists(hipStream_t stream, const int* elem, const unsigned short* cls, int npos, int us, unsigned long long* hash);
+// slot_tab[v] = the list of position first_pos[v]; then every position compares its list with slot_tab[ids[p]] (*mismatch = 1 on any
+// difference) and takes the id into the fourth word of its header: slot count | id << 8
+hipError_t affine_shared_list_table(hipStream_t stream, const int* elem, const unsigned short* cls, const int* ids, const int* first_pos, int npos,
+                                    int nvec, int us, unsigned short* slot_tab, int4* hdr, int* mismatch);
 
 }  // namespace fenris_hip

@@ -497,6 +497,7 @@ static int classify_affine(fh_ctx* c) {
     const bool had = c->has_aff;
     const uint64_t old_count = c->num_aff;
     ++c->a_recs_gen;   // new vertices, connectivity or tolerance: the element records (launch_affine) are formed again, also where the flags stay
+    ++c->a_geom_gen;   // ... and with them the tables of distinct records (fh_ctx::a_shared)
     c->has_aff = false;
     c->num_aff = 0;
     if (c->elem_kind != FH_HEX8 || c->E == 0 || !(c->affine_tol > 0.0)) {
@@ -758,6 +759,29 @@ int fh_affine_stats(const fh_ctx* c, uint64_t* affine_elements, uint64_t* affine
     if (affine_elements) *affine_elements = c->has_aff ? c->num_aff : 0;
     if (affine_blocks) *affine_blocks = c->has_partition ? (uint64_t)c->a_npos : 0;
     if (general_blocks) *general_blocks = c->has_partition ? (uint64_t)c->npos_gen : 0;
+    return FH_OK;
+}
+
+int fh_affine_shared_stats(const fh_ctx* c, int* shared, uint64_t* num_records, uint64_t* num_lists, const char** reason) {
+    if (!c) return FH_BAD_ARGUMENT;
+    const auto& sh = c->a_shared;
+    if (shared) *shared = sh.used ? 1 : 0;
+    if (num_records) *num_records = sh.used ? (uint64_t)sh.nrec : 0;
+    if (num_lists) *num_lists = sh.used ? (uint64_t)sh.nvec : 0;
+    if (reason) *reason = sh.used ? "" : sh.reason;
+    return FH_OK;
+}
+
+int fh_affine_slot_elements(fh_ctx* c, int* slots_per_block, uint64_t* blocks, int32_t* elements_out) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const bool have = c->has_partition && c->a_npos > 0;
+    if (slots_per_block) *slots_per_block = have ? c->a_us : 0;
+    if (blocks) *blocks = have ? (uint64_t)c->a_npos : 0;
+    if (have && elements_out) {
+        HIP_TRY(c, hipMemcpyAsync(elements_out, c->a_elem.p, sizeof(int) * (size_t)c->a_npos * c->a_us, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
     return FH_OK;
 }
 

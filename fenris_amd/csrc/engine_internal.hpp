@@ -383,6 +383,30 @@ struct fh_ctx {
     struct { long long lo = 0, hi = 0; int op = -1; unsigned long long gen = ~0ull; } a_recs_valid;
     unsigned long long a_recs_gen = 0;
     DevBuf<unsigned> a_sing;        // singular affine elements the records pass met since a_sing was cleared: count, then a bit per element (affine_rows.hpp)
+    // Shared form of the sweep's loader (affine_rows.hip): the distinct records among those of a_recs, the class of every element, the distinct
+    // per-position lists of slot classes (their ids live in bits 8 and up of the fourth word of a_hdr).  Built by launch_affine behind the
+    // records pass for one (a_geom_gen, operator, element interval, partition, pair of limits) and built again when any of them moves; `on`:
+    // the two verify passes agreed and the limits hold -- otherwise `reason` says why the sweep keeps the per-element loader.
+    // a_geom_gen moves in classify_affine only (vertices, connectivity, tolerance): the tables hold copies of record VALUES, so an exchange of
+    // the record buffer (fh_tune_placement_dev), a new stream or a mask, after which the records pass writes the same bits again, leaves them.
+    // The build costs three round trips, 16 bytes per element to the host and a host loop over elements and positions -- tens of sweeps
+    // (profiles/affine_shared_records.txt) -- so it is not run for a generation that may be gone after one assembly: `seen` counts the sweeps of
+    // the current key, the build runs once FENRIS_HIP_AFFINE_SHARED_AFTER (default 2) of them have used the per-element loader, doubled for
+    // every build in a row that ended over a limit (`fails`: a mesh that moves every step and never fits stops paying), or at once inside the
+    // untimed set-up assembly of fh_time_assembly_dev (a_shared_now), which is where a caller that settles and probes already pays set-up.
+    unsigned long long a_geom_gen = 0;
+    bool a_shared_now = false;
+    DevBuf<double> a_rec_tab;
+    DevBuf<unsigned short> a_cls, a_slot_tab;
+    struct {
+        long long lo = 0, hi = 0; int op = -1; unsigned long long gen = ~0ull, struct_gen = ~0ull; const void* hdr = nullptr; int npos = 0;
+        int max_rec = 0, max_vec = 0;
+        bool on = false; int nrec = 0, nvec = 0; const char* reason = "no affine sweep yet";   // of the last sweep
+        const char* build_reason = "";   // why the build of this key left `on` false
+        bool used = false;   // the last sweep ran the shared loader
+        bool built = false;  // the build for this key has run (whatever it found)
+        long long seen = 0; int fails = 0; double build_ms = 0.0;
+    } a_shared;
     int a_us = 0, a_npos = 0, a_ntab = 0, a_incomplete = 0;
     // general Hex8 row-owner kernel (hex8_rows.hip): lane tables and position records of the GENERAL positions (p_rec order)
     DevBuf<int4> h_hdr, h_pos;

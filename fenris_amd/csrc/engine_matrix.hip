@@ -151,6 +151,153 @@ int launch_pipelined(fh_ctx* c, KArgs& a, const PipeTables& T, size_t lds, int g
     }
 }
 
+// Shared records and slot lists of the affine sweep (fh_ctx::a_shared): on a structured, graded or extruded mesh most affine elements have
+// bit-identical records, and most positions the same list of them.  Two 64-bit hashes per record (per list) from the device, merged here on
+// equality of the 128 bits like the lane tables (build_lane_tables), then a pass in which every element (position) compares itself bit for
+// bit with the table entry it was given: the sweep then reads a few hundred KB that stay in the caches instead of E records and npos lists
+// beside its own row stores.  Equality is of BITS: congruent elements whose coordinates round differently keep records of their own.
+// Runs behind the records pass when its key moved; costs three round trips and one pass over the records, once per mesh generation.
+static int affine_shared_prepare(fh_ctx* c, int gw, long long e_lo, long long e_hi, bool dbg, bool& use) {
+    auto& sh = c->a_shared;
+    use = false;
+    auto off = [&](const char* why) { sh.on = false; sh.nrec = sh.nvec = 0; sh.reason = sh.build_reason = why; return (int)FH_OK; };
+    // states that need no tables (and leave the ones there are alone)
+    // Elasticity by default.  The Laplace / mass sweep is bound by the scalar unit and LDS, not by memory (profiles/r06_c2_lds_bound.txt), and its
+    // loader's extra level of indirection costs more than the reads it saves: 0.296 against 0.205 ms on 128^3 Poisson in one context
+    // (profiles/affine_shared_records.txt item 8).  The form is there and exact; FENRIS_HIP_AFFINE_SHARED=1 selects it.
+    if (!c->env_int("FENRIS_HIP_AFFINE_SHARED", gw == AFFINE_ROWS_GW_LE ? 1 : 0)) {
+        sh.reason = c->env("FENRIS_HIP_AFFINE_SHARED") ? "switched off (FENRIS_HIP_AFFINE_SHARED=0)"
+                                                       : "Laplace / mass: per-element loader unless FENRIS_HIP_AFFINE_SHARED=1";
+        return FH_OK;
+    }
+    if (c->has_mask) { sh.reason = "element mask: per-element loader"; return FH_OK; }
+    if (c->row_hi >= 0 || c->status_slot != 0) { sh.reason = "row range: per-element loader"; return FH_OK; }
+    if (dbg) { sh.reason = "instrumented launch: per-element loader"; return FH_OK; }
+    const int max_rec = std::min(c->env_int("FENRIS_HIP_AFFINE_SHARED_MAX_RECORDS", 4096), 0xfffe);
+    const int max_vec = std::min(c->env_int("FENRIS_HIP_AFFINE_SHARED_MAX_LISTS", 8192), 1 << 22);
+    const bool current = sh.built && sh.gen == c->a_geom_gen && sh.op == c->op && sh.lo == e_lo && e_hi == sh.hi && sh.struct_gen == c->struct_gen &&
+                         sh.hdr == (const void*)c->a_hdr.p && sh.npos == c->a_npos && sh.max_rec == max_rec && sh.max_vec == max_vec;
+    if (current) {
+        sh.reason = sh.on ? "" : sh.build_reason;
+        use = sh.on;
+        return FH_OK;
+    }
+    const bool same_key = sh.gen == c->a_geom_gen && sh.op == c->op && sh.lo == e_lo && sh.hi == e_hi && sh.struct_gen == c->struct_gen &&
+                          sh.hdr == (const void*)c->a_hdr.p && sh.npos == c->a_npos && sh.max_rec == max_rec && sh.max_vec == max_vec;
+    if (!same_key) {
+        sh.gen = c->a_geom_gen; sh.op = c->op; sh.lo = e_lo; sh.hi = e_hi; sh.struct_gen = c->struct_gen; sh.hdr = c->a_hdr.p; sh.npos = c->a_npos;
+        sh.max_rec = max_rec; sh.max_vec = max_vec;
+        sh.built = false; sh.seen = 0;
+        off("");
+    }
+    {   // not for a generation that may be gone after one assembly (fh_ctx::a_shared)
+        const long long need = (long long)std::max(0, c->env_int("FENRIS_HIP_AFFINE_SHARED_AFTER", 2)) << std::min(sh.fails, 20);
+        if (!c->a_shared_now && sh.seen < need) {
+            ++sh.seen;
+            sh.reason = "tables not built yet: the first sweeps of a mesh generation keep the per-element loader";
+            return FH_OK;
+        }
+    }
+    sh.built = true;
+    const auto t_build = std::chrono::steady_clock::now();
+    struct BuildTime {   // every way out of the build
+        decltype(c->a_shared)& s; std::chrono::steady_clock::time_point t0; bool verbose;
+        ~BuildTime() {
+            s.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            const bool over = !s.on && std::strstr(s.build_reason, "limit") != nullptr;
+            s.fails = over ? std::min(s.fails + 1, 20) : 0;
+            if (verbose) std::fprintf(stderr, "[fenris_hip] affine rows, shared form: table build took %.1f ms (%s)\n", s.build_ms, s.on ? "shared" : s.build_reason);
+        }
+    } build_time{sh, t_build, c->env("FENRIS_HIP_VERBOSE") != nullptr};
+    const long long n = e_hi - e_lo;
+    const int npos = c->a_npos, us = c->a_us;
+    if (n <= 0 || npos <= 0) return off("no affine positions");
+    // 1. distinct records
+    DevBuf<unsigned long long> hash_d;
+    HIP_TRY(c, hash_d.alloc((size_t)2 * std::max<long long>(n, npos)));
+    HostBuf<unsigned long long> hash_h((size_t)2 * std::max<long long>(n, npos));
+    HIP_TRY(c, affine_shared_hash_records(gw, c->stream, c->a_recs.p, c->elem_aff.p, e_lo, e_hi, hash_d.p));
+    HIP_TRY(c, hipMemcpyAsync(hash_h.data(), hash_d.p, sizeof(unsigned long long) * (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HostBuf<unsigned short> cls_h((size_t)n);
+    hvec<long long> first;
+    {
+        std::unordered_map<unsigned long long, int> seen;
+        seen.reserve(1024);
+        unsigned long long p1 = 0ull, p2 = 0ull;   // the element before: neighbours mostly agree
+        int pc = 0xffff;
+        for (long long i = 0; i < n; ++i) {
+            const unsigned long long h1 = hash_h[(size_t)i], h2 = hash_h[(size_t)(n + i)];
+            if (h1 == p1 && h2 == p2) { cls_h[(size_t)i] = (unsigned short)pc; continue; }
+            p1 = h1; p2 = h2;
+            if (!h1 && !h2) { pc = 0xffff; cls_h[(size_t)i] = 0xffff; continue; }   // not affine
+            auto it = seen.find(h1);
+            if (it == seen.end()) {
+                if ((int)first.size() >= max_rec) return off("more distinct records than the limit");
+                it = seen.emplace(h1, (int)first.size()).first;
+                first.push_back(e_lo + i);
+            } else if (hash_h[(size_t)(n + first[(size_t)it->second] - e_lo)] != h2) {
+                return off("hash collision among the records");
+            }
+            pc = it->second;
+            cls_h[(size_t)i] = (unsigned short)pc;
+        }
+    }
+    const int nrec = (int)first.size();
+    if (nrec == 0) return off("no affine elements");
+    DevBuf<long long> first_d;
+    DevBuf<int> st;
+    HIP_TRY(c, first_d.alloc((size_t)nrec));
+    HIP_TRY(c, st.alloc(2));
+    HIP_TRY(c, hipMemsetAsync(st.p, 0, 2 * sizeof(int), c->stream));
+    if (c->a_cls.n < (size_t)c->E) HIP_TRY(c, c->a_cls.alloc((size_t)c->E));
+    HIP_TRY(c, c->a_rec_tab.alloc((size_t)nrec * gw));
+    HIP_TRY(c, hipMemcpyAsync(c->a_cls.p + e_lo, cls_h.data(), sizeof(unsigned short) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(first_d.p, first.data(), sizeof(long long) * (size_t)nrec, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, affine_shared_record_table(gw, c->stream, c->a_recs.p, c->elem_aff.p, c->a_cls.p, first_d.p, nrec, e_lo, e_hi, c->a_rec_tab.p, st.p));
+    // 2. distinct lists of slot classes
+    HIP_TRY(c, affine_shared_hash_lists(c->stream, c->a_elem.p, c->a_cls.p, npos, us, hash_d.p));
+    int mismatch[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(mismatch, st.p, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hash_h.data(), hash_d.p, sizeof(unsigned long long) * (size_t)npos * 2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (mismatch[0]) return off("an element's record differs from its table entry");
+    HostBuf<int> ids((size_t)npos);
+    hvec<int> first_pos;
+    {
+        std::unordered_map<unsigned long long, int> seen;
+        seen.reserve(1024);
+        for (int p = 0; p < npos; ++p) {
+            const unsigned long long h1 = hash_h[(size_t)p], h2 = hash_h[(size_t)npos + p];
+            auto it = seen.find(h1);
+            if (it == seen.end()) {
+                if ((int)first_pos.size() >= max_vec) return off("more distinct slot lists than the limit");
+                it = seen.emplace(h1, (int)first_pos.size()).first;
+                first_pos.push_back(p);
+            } else if (hash_h[(size_t)npos + first_pos[(size_t)it->second]] != h2) {
+                return off("hash collision among the slot lists");
+            }
+            ids[(size_t)p] = it->second;
+        }
+    }
+    const int nvec = (int)first_pos.size();
+    DevBuf<int> ids_d, first_pos_d;
+    HIP_TRY(c, ids_d.alloc((size_t)npos));
+    HIP_TRY(c, first_pos_d.alloc((size_t)nvec));
+    HIP_TRY(c, c->a_slot_tab.alloc((size_t)nvec * us));
+    HIP_TRY(c, hipMemcpyAsync(ids_d.p, ids.data(), sizeof(int) * (size_t)npos, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(first_pos_d.p, first_pos.data(), sizeof(int) * (size_t)nvec, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, affine_shared_list_table(c->stream, c->a_elem.p, c->a_cls.p, ids_d.p, first_pos_d.p, npos, nvec, us, c->a_slot_tab.p, c->a_hdr.p, st.p + 1));
+    HIP_TRY(c, hipMemcpyAsync(mismatch, st.p, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (mismatch[1]) return off("a position's slot list differs from its table entry");
+    sh.on = true; sh.nrec = nrec; sh.nvec = nvec; sh.reason = sh.build_reason = "";
+    use = true;
+    if (c->env("FENRIS_HIP_VERBOSE"))
+        std::fprintf(stderr, "[fenris_hip] affine rows, shared form: %lld elements share %d records, %d positions share %d slot lists\n", n, nrec, npos, nvec);
+    return FH_OK;
+}
+
 // node blocks all of whose elements are affine: k_affine_rows (affine_rows.hip) over their position tables, behind k_affine_records where
 // the element records are not current
 int launch_affine(fh_ctx* c, KArgs& a) {
@@ -168,8 +315,9 @@ int launch_affine(fh_ctx* c, KArgs& a) {
     const unsigned char* act = c->has_mask ? c->active.p : nullptr;
     DevStatus* status = c->status.p + c->status_slot;
     const int nt = (rop == FH_LAPLACE ? AFFINE_ROWS_NT_STORES : 0) | ((c->env_int("FENRIS_HIP_AFFINE_PRIO", 3 | (2 << 2)) & 15) << AFFINE_ROWS_PRIO_SHIFT);
+    bool shared = false;
     auto rows = [&](int pos0, int count) -> int {
-        AffineRowTables T{c->a_hdr.p, c->a_lanes.p, c->a_elem.p, c->a_recs.p,
+        AffineRowTables T{c->a_hdr.p, c->a_lanes.p, {c->a_elem.p}, {c->a_recs.p},
                           c->ghat.p + (c->op == FH_MASS_SCALAR ? 64 * (AFFINE_GW_LE + AFFINE_GW_LAP) : c->op == FH_LAPLACE ? 64 * AFFINE_GW_LE : 0), c->a_us, count,
                           c->g_acc, pos0, c->a_npos, c->a_incomplete};
         const size_t lds = affine_rows_lds_bytes(rop, c->a_us, c->g_acc);
@@ -179,7 +327,8 @@ int launch_affine(fh_ctx* c, KArgs& a) {
         const int grid = std::max(1, std::min(count, c->env_int("FENRIS_HIP_AFFINE_GRID", dev_cus * c->env_int("FENRIS_HIP_AFFINE_WGS_PER_CU", per_cu))));
         if (c->env("FENRIS_HIP_VERBOSE"))
             std::fprintf(stderr, "[fenris_hip] affine rows: positions %d + %d lds=%zu B wgs/cu=%d grid=%d\n", pos0, count, lds, per_cu, grid);
-        HIP_TRY(c, affine_rows_launch(rop, a_depth, grid, lds, c->stream, a, T, a.ablate | nt, c->has_mask));
+        if (shared) { T.slot_tab = c->a_slot_tab.p; T.rec_tab = c->a_rec_tab.p; }
+        HIP_TRY(c, affine_rows_launch(rop, a_depth, grid, lds, c->stream, a, T, a.ablate | nt, c->has_mask, shared));
         return FH_OK;
     };
     // Element records (R = sqrt|det J| J^-1 or M = R R^T per affine element) on the same stream in front of the sweep -- but only those that are
@@ -211,6 +360,9 @@ int launch_affine(fh_ctx* c, KArgs& a) {
         // the records pass is also what reports a singular affine element: its marks repeat the report, for this range and this mask
         HIP_TRY(c, affine_replay_singular_launch(c->stream, c->a_sing.p, act, e_lo, e_hi, status));
     }
+    const int rc_shared = affine_shared_prepare(c, gw, e_lo, e_hi, (a.ablate & 0xffff) != 0, shared);
+    if (rc_shared) return rc_shared;
+    c->a_shared.used = shared;
     return rows(0, c->a_npos);
 }
 
@@ -494,7 +646,9 @@ int fh_time_assembly_dev(fh_ctx* c, double* values_dev, int flags, int reps, dou
     if (!ms_per_assembly || reps < 1) return c->fail(FH_BAD_ARGUMENT, "fh_time_assembly_dev: bad argument");
     // reps + 1 REAL assemblies run into the caller's array: without FH_ASSEMBLE_OVERWRITE they would pile up reps + 1 copies of K
     if (!(flags & FH_ASSEMBLE_OVERWRITE)) return c->fail(FH_BAD_ARGUMENT, "fh_time_assembly_dev: needs FH_ASSEMBLE_OVERWRITE (the timed assemblies write the values)");
+    c->a_shared_now = true;   // the tables of the shared affine loader belong to this set-up assembly, not into the timed ones
     int rc = fh_assemble_matrix_async_dev(c, values_dev, flags);   // tables, code objects, first touch
+    c->a_shared_now = false;
     if (rc) return rc;
     // the deferred lane tuner of k_hex8_rows (host work in front of a later launch) belongs to the set-up, not into the timed assemblies --
     // nor into the baseline fh_tune_placement_dev compares its candidates with
@@ -547,7 +701,9 @@ int fh_tune_placement_dev(fh_ctx* c, double* values_dev, int flags, int tries, d
         ++c->a_recs_gen;
         double t = 0.0;
         rc = fh_time_assembly_dev(c, values_dev, flags, 3, &t);
-        if (rc == FH_OK && t < 0.98 * best) {
+        // (FENRIS_HIP_PLACEMENT_KEEP=1, TESTS ONLY -- listed as such in scripts/README.md: every candidate is kept whatever its time, so
+        // that a test can hold an assembly behind an exchange against the one before it; it makes the placement worse)
+        if (rc == FH_OK && (t < 0.98 * best || c->env_int("FENRIS_HIP_PLACEMENT_KEEP", 0))) {
             best = t;
             rejected.push_back(old);
         } else {

@@ -210,6 +210,25 @@ int fh_set_affine_tolerance(fh_ctx*, double rel_tol);
 /* how the last FH_SCATTER_GATHER assembly was split: elements found affine, node blocks on the affine kernel, node blocks on
  * the general kernels (any pointer may be NULL; zeros before the first assembly) */
 int fh_affine_stats(const fh_ctx*, uint64_t* affine_elements, uint64_t* affine_blocks, uint64_t* general_blocks);
+/* The affine kernel of the last FH_SCATTER_GATHER assembly: whether its loader took the element records from the table of DISTINCT records
+ * (elements whose records agree bit for bit share one entry; structured, graded and extruded meshes have a few hundred) and the slots of a
+ * node block from the table of distinct slot lists, how many entries the two tables have (0 when it did not), and -- when it did not -- why (a string owned by
+ * the library, "" when shared).  Contexts with an element mask or a row range, more than 4096 distinct records or 8192 distinct lists
+ * (FENRIS_HIP_AFFINE_SHARED_MAX_RECORDS / _MAX_LISTS), FENRIS_HIP_AFFINE_SHARED=0 and -- unless FENRIS_HIP_AFFINE_SHARED=1 asks for it, it is
+ * slower there -- the Laplace and scalar mass operators keep the per-element loader; the values are the same
+ * bits either way.  The tables follow the vertices, the connectivity and the tolerance; building them costs tens of assemblies, so the
+ * first FENRIS_HIP_AFFINE_SHARED_AFTER (default 2) assemblies of a mesh generation keep the per-element loader, twice as many after every
+ * build in a row that ended over a limit, and fh_time_assembly_dev builds them in its untimed first assembly.  THE ASSEMBLY THAT BUILDS
+ * THEM BLOCKS: fh_assemble_matrix_async_dev, otherwise an enqueue, waits for the stream three times in that one call (record hashes to the host;
+ * the result of the record check with the list hashes; the result of the list check) and returns only after 28 - 39 ms on the 216^3 headline mesh (a few ms where
+ * the build ends over a limit); work the caller meant to overlap with that call waits with it.  A caller that cannot afford the stall at
+ * that place sets FENRIS_HIP_AFFINE_SHARED_AFTER=0 to have it in the first assembly of the generation, or FENRIS_HIP_AFFINE_SHARED=0. */
+int fh_affine_shared_stats(const fh_ctx*, int* shared, uint64_t* num_records, uint64_t* num_lists, const char** reason);
+/* INTERNAL, not a supported part of the interface: a view of the partition for the project's own tests and tools, which restate the shared
+ * tables from it; the layout it exposes may change with any release.  The node blocks of the affine kernel as the last FH_SCATTER_GATHER
+ * assembly's partition holds them: slots per block, number of blocks, and (elements_out, blocks x slots_per_block int32 on the host, may
+ * be NULL) the element of every slot, -1 for an empty one. */
+int fh_affine_slot_elements(fh_ctx*, int* slots_per_block, uint64_t* blocks, int32_t* elements_out);
 /* .with_u(&u) (elliptic.rs:123-137); u has s*N entries; NULL = zeros */
 int fh_set_u(fh_ctx*, const double* u);
 int fh_set_u_dev(fh_ctx*, const double* u_dev);
