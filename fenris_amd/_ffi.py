@@ -77,6 +77,7 @@ _SIGS = {
     "fh_add_mapped_vector_sdim_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_uint64, C.c_void_p]),
     "fh_group_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "fh_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
+    "fh_option_name": (C.c_char_p, [C.c_int]),
     "fh_time_assembly_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "fh_tune_placement_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fh_vmm_alloc": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),

@@ -272,10 +272,10 @@ void fill_common(fh_ctx* c, KArgs& a) {
     // operator: only under the default tolerance, where that is below rounding -- a caller who loosened fh_set_affine_tolerance gets the
     // stiffness fast path its documentation promises and exact geometry everywhere else, consistent with the two-pass tangent)
     a.all_affine = (c->elem_kind == FH_HEX8 && c->has_aff && c->num_aff == c->E && c->E > 0 && c->affine_tol <= 0x1p-46 &&
-                    !c->env("FENRIS_HIP_NO_AFFINE_PASS")) ? 1 : 0;
-    a.qmono = (c->elem_kind == FH_HEX8 && c->qmono.p && !c->env("FENRIS_HIP_NO_MONOMIAL")) ? c->qmono.p : nullptr;
+                    !c->opt.NO_AFFINE_PASS) ? 1 : 0;
+    a.qmono = (c->elem_kind == FH_HEX8 && c->qmono.p && !c->opt.NO_MONOMIAL) ? c->qmono.p : nullptr;
     a.qmom = (a.qmono && a.all_affine && c->qmom_ok && c->qmom.p && !c->has_rules && (c->op == FH_LAPLACE || (c->op == FH_LINEAR_ELASTIC && c->has_params)) &&
-              c->env_int("FENRIS_HIP_NO_MOMENT_RESIDUAL", 0) == 0) ? c->qmom.p : nullptr;
+              c->opt.NO_MOMENT_RESIDUAL.value_or(0) == 0) ? c->qmom.p : nullptr;
     a.qparams = c->has_params ? c->qparams.p : nullptr;
     a.tensor = c->op == FH_TENSOR ? c->tensor.p : nullptr;
     a.nonsym = (c->op == FH_TENSOR && !c->tensor_sym) ? 1 : 0;
@@ -290,9 +290,9 @@ void fill_common(fh_ctx* c, KArgs& a) {
     a.n2e_off = c->n2e_off.p;
     a.n2e = c->n2e.p;
     a.status = c->status.p + c->status_slot;
-    a.ablate = c->env_int("FENRIS_HIP_ABLATE", 0);
+    a.ablate = c->opt.ABLATE.value_or(0);
     a.trace = nullptr;
-    if (c->env("FENRIS_HIP_TRACE")) {
+    if (c->opt.TRACE) {
         if (!c->trace.p && c->trace.alloc(32) == hipSuccess) (void)hipMemset(c->trace.p, 0, 256);
         a.trace = c->trace.p;
     }
@@ -367,11 +367,13 @@ fh_ctx* fh_create(int device_id) {
     fh_ctx* c = new fh_ctx();
     c->device = device_id;
     // the tuning / diagnostic switches, once (include/fenris_hip.h): nothing in the dispatch reads the environment later
-    for (char** ev = environ; ev && *ev; ++ev) {
-        if (std::strncmp(*ev, "FENRIS_HIP_", 11) != 0) continue;
-        const char* eq = std::strchr(*ev, '=');
-        if (eq) c->env_vars.emplace(std::string(*ev, (size_t)(eq - *ev)), std::string(eq + 1));
-    }
+    std::vector<std::string> unknown;
+    options_from_env(c->opt, unknown);
+    if (c->opt.VERBOSE)
+        for (const std::string& name : unknown)
+            if (name != "FENRIS_HIP_LIB")   // (the Python loader's: which build of the library)
+                std::fprintf(stderr, "[fenris_hip] %s: not a switch of this library (options.def), ignored\n", name.c_str());
+    if (hipDeviceGetAttribute(&c->num_cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess) c->num_cus = 256;
     const DevStatus z[2] = {{0, 0, ~0ull}, {0, 0, ~0ull}};
     if (c->status.alloc(2) != hipSuccess || hipMemcpy(c->status.p, z, sizeof z, hipMemcpyHostToDevice) != hipSuccess) {
         delete c;
@@ -460,15 +462,21 @@ bool fh_internal_sizes(const fh_ctx* c, uint64_t* num_nodes, int* solution_dim) 
 extern "C" {
 const char* fh_last_kernel_name(const fh_ctx* c) { return c ? c->last_kernel.c_str() : ""; }
 
-// A tuning switch of THIS context (the FENRIS_HIP_* names, read by fh_create from the environment): set or, with value == NULL,
-// removed.  Switches that select a launch variant take effect at the next call; those that shape tables need the tables rebuilt
+// A tuning switch of THIS context (the FENRIS_HIP_* names of options.def, read by fh_create from the environment): set or, with value ==
+// NULL, removed.  Switches that select a launch variant take effect at the next call; those that shape tables need the tables rebuilt
 // (fh_set_operator / fh_set_mesh).  For experiments that compare variants inside one context, on the same buffers -- the only
-// comparison that resolves less than ~4 %.
+// comparison that resolves less than ~4 %.  A name the table does not declare is refused (FH_BAD_ARGUMENT), and so is
+// one that is read from the process's environment only.
 int fh_set_option(fh_ctx* c, const char* name, const char* value) {
     if (!c || !name) return FH_BAD_ARGUMENT;
-    if (value) c->env_vars[name] = value; else c->env_vars.erase(name);
-    return FH_OK;
+    switch (option_set(c->opt, name, value)) {
+        case OptResult::OK: return FH_OK;
+        case OptResult::ENV_ONLY:
+            return c->fail(FH_BAD_ARGUMENT, std::string("fh_set_option: ") + name + " is read from the environment of the process, not per context");
+        default: return c->fail(FH_BAD_ARGUMENT, std::string("fh_set_option: unknown switch ") + name);
+    }
 }
+const char* fh_option_name(int index) { return option_name(index); }
 
 int fh_set_stream(fh_ctx* c, void* s) {
     if (!c) return FH_BAD_ARGUMENT;
@@ -973,7 +981,7 @@ int fh_set_quadrature_uniform(fh_ctx* c, const double* w, const double* pts, uin
         c->uni_lambda = params[1];
         for (uint32_t q = 1; q < nq; ++q) c->fast_ok = c->fast_ok && params[2 * q] == params[0] && params[2 * q + 1] == params[1];
     }
-    if (c->env("FENRIS_HIP_NO_FAST")) c->fast_ok = false;
+    if (c->opt.NO_FAST) c->fast_ok = false;
     c->has_rules = false;
     c->elem_par = false;
     c->has_partition = false; ++c->struct_gen; c->has_tp_pos = false;
@@ -1024,7 +1032,7 @@ int fh_set_quadrature_compact(fh_ctx* c, const double* w, const double* pts, uin
         for (uint32_t q = 1; q < nq; ++q)
             rules_const = rules_const && rule_params[(r * nq + q) * 2] == rule_params[r * nq * 2] &&
                           rule_params[(r * nq + q) * 2 + 1] == rule_params[r * nq * 2 + 1];
-    c->elem_par = weights_ok && rules_const && !c->env("FENRIS_HIP_NO_FAST") && !c->env("FENRIS_HIP_NO_ELEM_PAR");
+    c->elem_par = weights_ok && rules_const && !c->opt.NO_FAST && !c->opt.NO_ELEM_PAR;
     c->fast_ok = c->elem_par;
     c->has_slotpar = false;
     c->has_partition = false; ++c->struct_gen; c->has_tp_pos = false;
@@ -1286,7 +1294,7 @@ int fh_color_parallel(fh_ctx* c, uint64_t* num_colors, uint64_t* color_offsets, 
             if (i > 0 && hk[i] != hk[i - 1]) offs.push_back((uint64_t)i);
         }
         offs.push_back((uint64_t)E);
-        if (c->env("FENRIS_HIP_VERBOSE"))
+        if (c->opt.VERBOSE)
             std::fprintf(stderr, "[fenris_hip] parallel colouring: %zu colours in %d rounds\n", offs.size() - 1, rounds);
     }
     if (num_colors) *num_colors = offs.size() - 1;

@@ -392,7 +392,7 @@ int eigs_lowest_dev(fh_ctx* c, uint32_t m32, double shift, int preconditioner, d
     }
     rc = reset_status(c);
     if (rc) return rc;
-    e.prof = c->env("FENRIS_HIP_EIGS_PROFILE") != nullptr;
+    e.prof = c->opt.EIGS_PROFILE;
     std::fill(c->eig_profile, c->eig_profile + 8, 0.0);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();

@@ -30,9 +30,8 @@
 #include "group_internal.hpp"
 #include "host_inputs.hpp"
 #include "host_pool.hpp"
+#include "options.hpp"
 #include "pattern_kernels.hpp"
-
-extern char** environ;
 
 using namespace fenris_hip;
 
@@ -439,17 +438,10 @@ struct fh_ctx {
         std::vector<std::vector<uint32_t>> groups;  // rules of each group
         int staged = -1;
     } rs;
-    // Tuning / diagnostic switches: the FENRIS_HIP_* environment variables as they were when fh_create ran (read once; a
-    // host that wants different settings sets them before creating the context -- see include/fenris_hip.h)
-    std::unordered_map<std::string, std::string> env_vars;
-    const char* env(const char* name) const {
-        auto it = env_vars.find(name);
-        return it == env_vars.end() ? nullptr : it->second.c_str();
-    }
-    int env_int(const char* name, int dflt) const {
-        const char* v = env(name);
-        return (v && *v) ? std::atoi(v) : dflt;
-    }
+    // Tuning / diagnostic switches (options.def): the FENRIS_HIP_* environment variables as they were when fh_create ran (read once; a
+    // host that wants different settings sets them before creating the context -- see include/fenris_hip.h) and what fh_set_option changed
+    Options opt;
+    int num_cus = 256;   // compute units of the device (fh_create): the default grids are multiples of it
     bool rs_staging = false;                 // the setters are being called by the group walk, not by the user
     std::vector<uint8_t> user_mask;          // fh_set_active_elements as the caller gave it
     bool user_has_mask = false;

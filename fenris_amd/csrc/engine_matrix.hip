@@ -47,16 +47,14 @@ int launch_rows_tet4(fh_ctx* c, KArgs& a, const RowTablesS& T) {
     const size_t lds = make_layout<FH_TET4, OP, WHAT_MATRIX>(a.nq, a.ub, 0, a.nb_max, true, 0, 1, 1, 0, 2).bytes() +
                        sizeof(int) * (size_t)(2 * T.rw + T.us + 4);
     if (lds > LDS_LIMIT) return c->fail(FH_UNSUPPORTED, "row-owner gather: LDS footprint too large");
-    int dev_cus = 256;
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
     // workgroups per CU, measured inside one context on the same buffers (scripts/ab_in_context.py, C3): elasticity 2 (0.562 ms; 3: 0.594,
     // 4: 0.603, 5: 0.585), Laplace 4
     const size_t cap = (c->op == FH_LAPLACE) ? 4 : 2;
     const int per_cu = std::max(1, (int)std::min<size_t>(cap, (LDS_LIMIT - 512) / std::max<size_t>(lds, 1)));
     // (FENRIS_HIP_PIPE_GRID: tests force many positions per workgroup on small meshes)
-    const int grid = std::max(1, std::min(c->npos_gen, c->env_int("FENRIS_HIP_PIPE_GRID", dev_cus * c->env_int("FENRIS_HIP_PIPE_WGS_PER_CU", per_cu))));
+    const int grid = std::max(1, std::min(c->npos_gen, c->opt.PIPE_GRID.value_or(c->num_cus * c->opt.PIPE_WGS_PER_CU.value_or(per_cu))));
     auto kern = a.trace ? k_gather_rows_tet4<OP, ELEMPAR, true> : k_gather_rows_tet4<OP, ELEMPAR>;   // FENRIS_HIP_TRACE: instrumented twin
-    if (c->env("FENRIS_HIP_VERBOSE"))
+    if (c->opt.VERBOSE)
         std::fprintf(stderr, "[fenris_hip] row-owner gather (Tet4): lds=%zu B wgs/cu=%d grid=%d\n", lds, per_cu, grid);
     return launch_lds(c, kern, dim3(grid), dim3(256), lds, c->stream, a, T);
 }
@@ -74,13 +72,11 @@ int launch_pipelined_j(fh_ctx* c, KArgs& a, const PipeTables& T) {
                 (2 * lds_planar + 1024 <= LDS_LIMIT || 2 * lds + 1024 > LDS_LIMIT);
         if (fullq) lds = lds_planar;
     }
-    int dev_cus = 256;
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
     const int per_cu = std::max(1, (int)std::min<size_t>(8, (LDS_LIMIT - 512) / std::max<size_t>(lds, 1)));
-    const int wgs = std::max(1, c->env_int("FENRIS_HIP_PIPE_WGS_PER_CU", per_cu));
-    const int grid = std::max(1, std::min(c->npos_gen, c->env_int("FENRIS_HIP_PIPE_GRID", dev_cus * wgs)));
+    const int wgs = std::max(1, c->opt.PIPE_WGS_PER_CU.value_or(per_cu));
+    const int grid = std::max(1, std::min(c->npos_gen, c->opt.PIPE_GRID.value_or(c->num_cus * wgs)));
     // the instrumented instantiation only where it is used for profiling (Hex8, the default tiling)
-    const bool dbg = (c->env("FENRIS_HIP_TRACE") || c->env("FENRIS_HIP_ABLATE"));
+    const bool dbg = (c->opt.TRACE || c->opt.ABLATE.set);
     void (*kern)(const KArgs, const PipeTables) = k_gather_pipelined<EK, OP, QC, JT>;
     constexpr int N_ = ElemT<EK>::N;
     constexpr bool DEFAULT_JT = JT == ((N_ % 2 == 0) ? 2 : N_);  // per-element data: the default tiling only
@@ -101,7 +97,7 @@ int launch_pipelined_j(fh_ctx* c, KArgs& a, const PipeTables& T) {
         } else if (fullq)
             kern = k_gather_pipelined<EK, OP, QC, JT, false, true>;
     }
-    if (c->env("FENRIS_HIP_VERBOSE"))
+    if (c->opt.VERBOSE)
         std::fprintf(stderr, "[fenris_hip] pipelined gather: QC=%d JT=%d lds=%zu B wgs/cu=%d grid=%d\n", QC, JT, lds, wgs, grid);
     return launch_lds(c, kern, dim3(grid), dim3(256), lds, c->stream, a, T);
 }
@@ -120,7 +116,7 @@ template <int EK, int OP>
 int launch_pipelined_t(fh_ctx* c, KArgs& a, const PipeTables& T, size_t, int) {
     // staged quadrature points per chunk: the largest chunk (not larger than the rule) that still lets >= 2
     // workgroups share a CU (measured on Hex8: profiles/r01_sweep_128_pipelined_nb_qc_jt.txt)
-    int qc = c->env_int("FENRIS_HIP_PIPE_QC", 0);
+    int qc = c->opt.PIPE_QC.value_or(0);
     if (qc <= 0) {
         qc = 1;
         for (int cand : {8, 4, 2}) {
@@ -165,25 +161,23 @@ static int affine_shared_prepare(fh_ctx* c, int gw, long long e_lo, long long e_
     // Elasticity by default.  The Laplace / mass sweep is bound by the scalar unit and LDS, not by memory (profiles/r06_c2_lds_bound.txt), and its
     // loader's extra level of indirection costs more than the reads it saves: 0.296 against 0.205 ms on 128^3 Poisson in one context
     // (profiles/affine_shared_records.txt item 8).  The form is there and exact; FENRIS_HIP_AFFINE_SHARED=1 selects it.
-    if (!c->env_int("FENRIS_HIP_AFFINE_SHARED", gw == AFFINE_ROWS_GW_LE ? 1 : 0)) {
-        sh.reason = c->env("FENRIS_HIP_AFFINE_SHARED") ? "switched off (FENRIS_HIP_AFFINE_SHARED=0)"
-                                                       : "Laplace / mass: per-element loader unless FENRIS_HIP_AFFINE_SHARED=1";
+    if (!c->opt.AFFINE_SHARED.value_or(gw == AFFINE_ROWS_GW_LE ? 1 : 0)) {
+        sh.reason = c->opt.AFFINE_SHARED.set ? "switched off (FENRIS_HIP_AFFINE_SHARED=0)"
+                                             : "Laplace / mass: per-element loader unless FENRIS_HIP_AFFINE_SHARED=1";
         return FH_OK;
     }
     if (c->has_mask) { sh.reason = "element mask: per-element loader"; return FH_OK; }
     if (c->row_hi >= 0 || c->status_slot != 0) { sh.reason = "row range: per-element loader"; return FH_OK; }
     if (dbg) { sh.reason = "instrumented launch: per-element loader"; return FH_OK; }
-    const int max_rec = std::min(c->env_int("FENRIS_HIP_AFFINE_SHARED_MAX_RECORDS", 4096), 0xfffe);
-    const int max_vec = std::min(c->env_int("FENRIS_HIP_AFFINE_SHARED_MAX_LISTS", 8192), 1 << 22);
-    const bool current = sh.built && sh.gen == c->a_geom_gen && sh.op == c->op && sh.lo == e_lo && e_hi == sh.hi && sh.struct_gen == c->struct_gen &&
-                         sh.hdr == (const void*)c->a_hdr.p && sh.npos == c->a_npos && sh.max_rec == max_rec && sh.max_vec == max_vec;
-    if (current) {
+    const int max_rec = std::min(c->opt.AFFINE_SHARED_MAX_RECORDS.value_or(4096), 0xfffe);
+    const int max_vec = std::min(c->opt.AFFINE_SHARED_MAX_LISTS.value_or(8192), 1 << 22);
+    const bool same_key = sh.gen == c->a_geom_gen && sh.op == c->op && sh.lo == e_lo && sh.hi == e_hi && sh.struct_gen == c->struct_gen &&
+                          sh.hdr == (const void*)c->a_hdr.p && sh.npos == c->a_npos && sh.max_rec == max_rec && sh.max_vec == max_vec;
+    if (sh.built && same_key) {   // current
         sh.reason = sh.on ? "" : sh.build_reason;
         use = sh.on;
         return FH_OK;
     }
-    const bool same_key = sh.gen == c->a_geom_gen && sh.op == c->op && sh.lo == e_lo && sh.hi == e_hi && sh.struct_gen == c->struct_gen &&
-                          sh.hdr == (const void*)c->a_hdr.p && sh.npos == c->a_npos && sh.max_rec == max_rec && sh.max_vec == max_vec;
     if (!same_key) {
         sh.gen = c->a_geom_gen; sh.op = c->op; sh.lo = e_lo; sh.hi = e_hi; sh.struct_gen = c->struct_gen; sh.hdr = c->a_hdr.p; sh.npos = c->a_npos;
         sh.max_rec = max_rec; sh.max_vec = max_vec;
@@ -191,7 +185,7 @@ static int affine_shared_prepare(fh_ctx* c, int gw, long long e_lo, long long e_
         off("");
     }
     {   // not for a generation that may be gone after one assembly (fh_ctx::a_shared)
-        const long long need = (long long)std::max(0, c->env_int("FENRIS_HIP_AFFINE_SHARED_AFTER", 2)) << std::min(sh.fails, 20);
+        const long long need = (long long)std::max(0, c->opt.AFFINE_SHARED_AFTER.value_or(2)) << std::min(sh.fails, 20);
         if (!c->a_shared_now && sh.seen < need) {
             ++sh.seen;
             sh.reason = "tables not built yet: the first sweeps of a mesh generation keep the per-element loader";
@@ -208,7 +202,7 @@ static int affine_shared_prepare(fh_ctx* c, int gw, long long e_lo, long long e_
             s.fails = over ? std::min(s.fails + 1, 20) : 0;
             if (verbose) std::fprintf(stderr, "[fenris_hip] affine rows, shared form: table build took %.1f ms (%s)\n", s.build_ms, s.on ? "shared" : s.build_reason);
         }
-    } build_time{sh, t_build, c->env("FENRIS_HIP_VERBOSE") != nullptr};
+    } build_time{sh, t_build, c->opt.VERBOSE};
     const long long n = e_hi - e_lo;
     const int npos = c->a_npos, us = c->a_us;
     if (n <= 0 || npos <= 0) return off("no affine positions");
@@ -293,7 +287,7 @@ static int affine_shared_prepare(fh_ctx* c, int gw, long long e_lo, long long e_
     if (mismatch[1]) return off("a position's slot list differs from its table entry");
     sh.on = true; sh.nrec = nrec; sh.nvec = nvec; sh.reason = sh.build_reason = "";
     use = true;
-    if (c->env("FENRIS_HIP_VERBOSE"))
+    if (c->opt.VERBOSE)
         std::fprintf(stderr, "[fenris_hip] affine rows, shared form: %lld elements share %d records, %d positions share %d slot lists\n", n, nrec, npos, nvec);
     return FH_OK;
 }
@@ -301,20 +295,18 @@ static int affine_shared_prepare(fh_ctx* c, int gw, long long e_lo, long long e_
 // node blocks all of whose elements are affine: k_affine_rows (affine_rows.hip) over their position tables, behind k_affine_records where
 // the element records are not current
 int launch_affine(fh_ctx* c, KArgs& a) {
-    int dev_cus = 256;
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
     // the scalar mass matrix rides the Laplace kernel: records (|det J|, 0 ...), reference blocks (sum_q w rho phi_a phi_b, 0 ...)
     const int rop = (c->op == FH_MASS_SCALAR) ? (int)FH_LAPLACE : c->op;
     const int gw = (rop == FH_LAPLACE) ? AFFINE_ROWS_GW_LAP : AFFINE_ROWS_GW_LE;
     // (Measured and retired to scripts/attic/: the element records formed inside k_affine_rows by a seventh wavefront -- 4.82 against 4.73 ms on the
     // headline, profiles/r05_fused_records_experiment.txt; the barrier-free ring form, affine_ring.hip -- 5 % slower; positions dealt in chunks
     // instead of one contiguous range per workgroup, profiles/r04_chunk_experiment.txt; non-temporal row stores for elasticity; two store waves.)
-    const int a_depth = c->env_int("FENRIS_HIP_AFFINE_DEPTH", 2);
+    const int a_depth = c->opt.AFFINE_DEPTH.value_or(2);
     if (c->a_recs.n < (size_t)c->E * gw) { HIP_TRY(c, c->a_recs.alloc((size_t)c->E * gw)); ++c->a_recs_gen; }
     if (c->a_sing.n < affine_sing_words(c->E)) { HIP_TRY(c, c->a_sing.alloc(affine_sing_words(c->E))); ++c->a_recs_gen; }
     const unsigned char* act = c->has_mask ? c->active.p : nullptr;
     DevStatus* status = c->status.p + c->status_slot;
-    const int nt = (rop == FH_LAPLACE ? AFFINE_ROWS_NT_STORES : 0) | ((c->env_int("FENRIS_HIP_AFFINE_PRIO", 3 | (2 << 2)) & 15) << AFFINE_ROWS_PRIO_SHIFT);
+    const int nt = (rop == FH_LAPLACE ? AFFINE_ROWS_NT_STORES : 0) | ((c->opt.AFFINE_PRIO.value_or(3 | (2 << 2)) & 15) << AFFINE_ROWS_PRIO_SHIFT);
     bool shared = false;
     auto rows = [&](int pos0, int count) -> int {
         AffineRowTables T{c->a_hdr.p, c->a_lanes.p, {c->a_elem.p}, {c->a_recs.p},
@@ -324,8 +316,8 @@ int launch_affine(fh_ctx* c, KArgs& a) {
         if (lds > LDS_LIMIT) return c->fail(FH_UNSUPPORTED, "affine gather: LDS footprint too large");
         // workgroups per CU, measured best: 3 (elasticity), 4 (Laplace: fewer registers, less LDS)
         const int per_cu = std::max(1, (int)std::min<size_t>(rop == FH_LAPLACE ? 4 : 3, (LDS_LIMIT - 512) / std::max<size_t>(lds, 1)));
-        const int grid = std::max(1, std::min(count, c->env_int("FENRIS_HIP_AFFINE_GRID", dev_cus * c->env_int("FENRIS_HIP_AFFINE_WGS_PER_CU", per_cu))));
-        if (c->env("FENRIS_HIP_VERBOSE"))
+        const int grid = std::max(1, std::min(count, c->opt.AFFINE_GRID.value_or(c->num_cus * c->opt.AFFINE_WGS_PER_CU.value_or(per_cu))));
+        if (c->opt.VERBOSE)
             std::fprintf(stderr, "[fenris_hip] affine rows: positions %d + %d lds=%zu B wgs/cu=%d grid=%d\n", pos0, count, lds, per_cu, grid);
         if (shared) { T.slot_tab = c->a_slot_tab.p; T.rec_tab = c->a_rec_tab.p; }
         HIP_TRY(c, affine_rows_launch(rop, a_depth, grid, lds, c->stream, a, T, a.ablate | nt, c->has_mask, shared));
@@ -344,10 +336,10 @@ int launch_affine(fh_ctx* c, KArgs& a) {
     auto& v = c->a_recs_valid;
     const bool current = v.gen == c->a_recs_gen && v.op == c->op;
     const bool covered = current && v.lo <= e_lo && e_hi <= v.hi;
-    if (!covered || c->env_int("FENRIS_HIP_AFFINE_RECORDS_ALWAYS", 0)) {
+    if (!covered || c->opt.AFFINE_RECORDS_ALWAYS.value_or(0)) {
         // the marks of singular elements belong to one generation and format: cleared when either moves
         if (!current) HIP_TRY(c, hipMemsetAsync(c->a_sing.p, 0, sizeof(unsigned) * c->a_sing.n, c->stream));
-        if (c->env("FENRIS_HIP_VERBOSE"))
+        if (c->opt.VERBOSE)
             std::fprintf(stderr, "[fenris_hip] affine records computed: elements [%lld, %lld)\n", e_lo, e_hi);
         HIP_TRY(c, affine_records_launch(c->op, c->stream, c->verts.p, c->conn.p, c->elem_aff.p, act, e_lo, e_hi, c->a_recs.p, status, c->a_sing.p));
         if (current && e_lo <= v.hi && v.lo <= e_hi) {   // touches or overlaps what is valid: the union
@@ -396,16 +388,18 @@ static GatherKernel select_gather_kernel(fh_ctx* c, bool fast, bool* pipe_rules_
     if (pipe_rules_out) *pipe_rules_out = pipe_rules;
     // Tet4 is affine: with uniform parameters any rule equals the one-point rule that carries the sum of its weights
     if (c->has_pipe && c->has_rows && c->elem_kind == FH_TET4 && (fast || pipe_rules) && lin) return GK_ROWS_TET4;
-    if (c->has_pipe && c->has_hrows && fast && !pipe_rules && c->nq == 8 && c->elem_kind == FH_HEX8 && lin && !c->env("FENRIS_HIP_NO_HEX8_ROWS") &&
+    if (c->has_pipe && c->has_hrows && fast && !pipe_rules && c->nq == 8 && c->elem_kind == FH_HEX8 && lin && !c->opt.NO_HEX8_ROWS &&
         hex8_rows_lds_bytes(c->g_acc) <= LDS_LIMIT)
         return GK_HEX8_ROWS;
     if (c->has_pipe && (fast || pipe_rules) && lin) return GK_PIPELINED;
     return GK_GENERIC;
 }
+// largest buffer of dense element matrices the two-pass form may allocate, in GB
+static int two_pass_max_gb(const fh_ctx* c) { return c->opt.TWO_PASS_MAX_GB.value_or(96); }
 
 int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset) {
     const auto t_entry = std::chrono::steady_clock::now();
-    const bool vt_entry = !c->has_partition && c->env("FENRIS_HIP_VERBOSE") != nullptr;
+    const bool vt_entry = !c->has_partition && c->opt.VERBOSE;
     struct ExitPrint {   // FENRIS_HIP_VERBOSE: the first assembly of a context from entry to the end of its enqueueing
         bool on; std::chrono::steady_clock::time_point t0; hipStream_t st;
         ~ExitPrint() {
@@ -429,15 +423,15 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
     a.vals = values_dev;
     a.overwrite = overwrite;
     const uint64_t nnz = (uint64_t)c->S() * c->S() * c->nnz_nodes;
-    if (mode == FH_SCATTER_GATHER && c->row_hi < 0 && !c->env("FENRIS_HIP_NO_TWO_PASS")) {
+    if (mode == FH_SCATTER_GATHER && c->row_hi < 0 && !c->opt.NO_TWO_PASS) {
         // two-pass owner-computes (dense element matrices, then a row gather) where recomputing the element prologue per
         // owning node block is the expensive part: high-order elements, and the nonlinear materials on any element
         // (measured, Hex8 128^3: NeoHookean 11.1 -> 9.2 ms, StVK 19.2 -> 10.0 ms; LinearElastic with per-point
         // parameters is faster one-pass: 5.7 vs 8.2 ms).  The dense buffer costs E (s n)^2 doubles: capped.
         const size_t dense_doubles = two_pass_dense_doubles(c);
         const double dense_gb = (double)dense_doubles * 8.0 / 1e9;
-        const bool want = c->ei.n > 8 || c->op == FH_NEO_HOOKEAN || c->op == FH_STVK || c->env("FENRIS_HIP_TWO_PASS");
-        if (want && dense_gb <= (double)c->env_int("FENRIS_HIP_TWO_PASS_MAX_GB", 96)) {
+        const bool want = c->ei.n > 8 || c->op == FH_NEO_HOOKEAN || c->op == FH_STVK || c->opt.TWO_PASS;
+        if (want && dense_gb <= (double)two_pass_max_gb(c)) {
             // the dense buffer is allocated here: when the device cannot hold it the one-pass gather below takes over
             if (c->ke_dense.n >= dense_doubles || c->ke_dense.alloc(dense_doubles) == hipSuccess)
                 return assemble_two_pass(c, values_dev, overwrite);
@@ -445,7 +439,7 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
         }
     }
     if (mode == FH_SCATTER_GATHER) {
-        const bool vt_first = !c->has_partition && c->env("FENRIS_HIP_VERBOSE") != nullptr;
+        const bool vt_first = !c->has_partition && c->opt.VERBOSE;
         const auto t_bp0 = std::chrono::steady_clock::now();
         if (vt_first) std::fprintf(stderr, "[fenris_hip] set-up: before build_partition               %7.1f ms\n",
                                    std::chrono::duration<double, std::milli>(t_bp0 - t_entry).count());
@@ -457,7 +451,7 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_bp0).count());
         }
         if (c->part_rows_only && !(c->has_pipe && c->has_rows && a.fast && (c->op == FH_LAPLACE || c->op == FH_LINEAR_ELASTIC) &&
-                              !c->env("FENRIS_HIP_TRACE"))) {
+                              !c->opt.TRACE)) {
             // these tables are for the row-owner kernel only (see build_partition); another kernel is about to run
             c->perm_failed = true;
             c->has_partition = false; ++c->struct_gen;
@@ -473,7 +467,7 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
             if (!stable) {
                 if (c->row_hi >= 0) return c->fail(FH_UNSUPPORTED, "FH_ASSEMBLE_REPRODUCIBLE: this configuration needs the two-pass form, which has no row range");
                 const size_t dense_doubles = two_pass_dense_doubles(c);
-                if ((double)dense_doubles * 8.0 / 1e9 > (double)c->env_int("FENRIS_HIP_TWO_PASS_MAX_GB", 96))
+                if ((double)dense_doubles * 8.0 / 1e9 > (double)two_pass_max_gb(c))
                     return c->fail(FH_OUT_OF_MEMORY, "FH_ASSEMBLE_REPRODUCIBLE: the dense element matrices of the two-pass form exceed FENRIS_HIP_TWO_PASS_MAX_GB");
                 if (c->ke_dense.n < dense_doubles && c->ke_dense.alloc(dense_doubles) != hipSuccess) {
                     (void)hipGetLastError();
@@ -521,7 +515,7 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
                 a.nq = 1;
             }
             RowTablesS T{c->r_rec.p, c->r_lanes4.p, c->r_vconn.p, c->p_elem.p, pipe_rules ? c->p_slotpar.p : nullptr,
-                         c->r_rw, c->p_us, c->p_nbs, c->npos_gen, c->r_ls, c->r_vn, c->env_int("FENRIS_HIP_TET4_PRIO", 0) & 15};
+                         c->r_rw, c->p_us, c->p_nbs, c->npos_gen, c->r_ls, c->r_vn, c->opt.TET4_PRIO.value_or(0) & 15};
             a.ub = std::max(c->p_us, 76);   // the X region of the layout (14 doubles per slot) holds the vertex table: 256 x 4 doubles
             a.nb_max = c->p_nbs;
             if (c->has_mask && a.overwrite) {   // blocks without an active element have no lane: clear the range first (rows_kernel.hpp)
@@ -539,10 +533,8 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
         if (gk == GK_HEX8_ROWS) {
             const size_t lds_h = hex8_rows_lds_bytes(c->g_acc);
             {
-                int dev_cus = 256;
-                (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
                 const int per_cu = std::max(1, (int)std::min<size_t>(2, (LDS_LIMIT - 512) / std::max<size_t>(lds_h, 1)));
-                const int grid = std::max(1, std::min(c->npos_gen, c->env_int("FENRIS_HIP_PIPE_GRID", dev_cus * c->env_int("FENRIS_HIP_PIPE_WGS_PER_CU", per_cu))));
+                const int grid = std::max(1, std::min(c->npos_gen, c->opt.PIPE_GRID.value_or(c->num_cus * c->opt.PIPE_WGS_PER_CU.value_or(per_cu))));
                 // the deferred lane tuner: in front of the launch that follows the first FENRIS_HIP_TUNE_AFTER ones
                 if (c->h_tune_pending > 0 && --c->h_tune_pending == 0) {
                     c->h_tune_pending = 1;
@@ -550,10 +542,10 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
                     if (rt) return rt;
                 }
                 Hex8RowTables T{c->h_pos.p, c->h_lanes.p, c->p_conn.p, c->p_elem.p, c->p_us, c->p_cs, c->npos_gen, c->g_acc};
-                if (c->env("FENRIS_HIP_VERBOSE"))
+                if (c->opt.VERBOSE)
                     std::fprintf(stderr, "[fenris_hip] hex8 rows: positions %d lds=%zu B wgs/cu=%d grid=%d\n", c->npos_gen, lds_h, per_cu, grid);
                 c->last_kernel += "k_hex8_rows";
-                HIP_TRY(c, hex8_rows_launch(c->op, grid, lds_h, c->stream, a, T, a.ablate | (a.trace ? 0x10000 : 0) | ((c->env_int("FENRIS_HIP_HEX8_PRIO", 40) & 63) << HEX8_ROWS_PRIO_SHIFT)));
+                HIP_TRY(c, hex8_rows_launch(c->op, grid, lds_h, c->stream, a, T, a.ablate | (a.trace ? 0x10000 : 0) | ((c->opt.HEX8_PRIO.value_or(40) & 63) << HEX8_ROWS_PRIO_SHIFT)));
                 return FH_OK;
             }
         }
@@ -701,9 +693,9 @@ int fh_tune_placement_dev(fh_ctx* c, double* values_dev, int flags, int tries, d
         ++c->a_recs_gen;
         double t = 0.0;
         rc = fh_time_assembly_dev(c, values_dev, flags, 3, &t);
-        // (FENRIS_HIP_PLACEMENT_KEEP=1, TESTS ONLY -- listed as such in scripts/README.md: every candidate is kept whatever its time, so
+        // (FENRIS_HIP_PLACEMENT_KEEP=1, TESTS ONLY -- declared as such in options.def: every candidate is kept whatever its time, so
         // that a test can hold an assembly behind an exchange against the one before it; it makes the placement worse)
-        if (rc == FH_OK && (t < 0.98 * best || c->env_int("FENRIS_HIP_PLACEMENT_KEEP", 0))) {
+        if (rc == FH_OK && (t < 0.98 * best || c->opt.PLACEMENT_KEEP.value_or(0))) {
             best = t;
             rejected.push_back(old);
         } else {

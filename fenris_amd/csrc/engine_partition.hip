@@ -16,7 +16,7 @@ static int build_lane_tables(fh_ctx* c, const int* rec, int us, int ms, int nb_t
     // first position of every distinct table are formed once more into the compact tables.  Writing all of them (2 KB x 1.46 M positions
     // = 3 GB on the 216^3 mesh) cost an allocation of 40 - 120 ms.  FENRIS_HIP_NO_LANE_DEDUPE keeps the full form (its compaction
     // compares every position with its table); two positions whose first hashes agree and whose second ones differ send the build there too.
-    bool full = c->env("FENRIS_HIP_NO_LANE_DEDUPE") != nullptr || npos >= (1 << 23);
+    bool full = c->opt.NO_LANE_DEDUPE || npos >= (1 << 23);
     DevBuf<uint2> lanes_full;
     DevBuf<unsigned long long> hash_d;
     HIP_TRY(c, hash_d.alloc((size_t)npos * 2));
@@ -61,7 +61,7 @@ static int build_lane_tables(fh_ctx* c, const int* rec, int us, int ms, int nb_t
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             ntab_out = ntab;
             incomplete_out = mismatch[1];
-            if (c->env("FENRIS_HIP_VERBOSE")) {
+            if (c->opt.VERBOSE) {
                 long long changes = 0;
                 for (int p = 1; p < npos; ++p) changes += ids[p] != ids[p - 1];
                 std::fprintf(stderr, "[fenris_hip] %s: %d positions share %d lane tables, %lld changes of table along the sweep%s\n", what,
@@ -102,7 +102,7 @@ static int build_lane_tables(fh_ctx* c, const int* rec, int us, int ms, int nb_t
             ids[p] = it->second;
         }
     };
-    dedupe(c->env("FENRIS_HIP_NO_LANE_DEDUPE") != nullptr || npos >= (1 << 23));  // the id has 23 bits
+    dedupe(c->opt.NO_LANE_DEDUPE || npos >= (1 << 23));  // the id has 23 bits
     for (int attempt = 0; attempt < 2; ++attempt) {
         const int ntab = (int)first.size();
         DevBuf<int> ids_d, first_d;
@@ -121,7 +121,7 @@ static int build_lane_tables(fh_ctx* c, const int* rec, int us, int ms, int nb_t
         if (!mismatch[0]) break;
         dedupe(true);  // a hash collision: every position keeps its own table
     }
-    if (c->env("FENRIS_HIP_VERBOSE")) {
+    if (c->opt.VERBOSE) {
         long long changes = 0;   // positions whose table differs from their predecessor's in the sweep: each is a 2 KB fetch
         for (int p = 1; p < npos; ++p) changes += ids[p] != ids[p - 1];
         std::fprintf(stderr, "[fenris_hip] %s: %d positions share %d lane tables, %lld changes of table along the sweep%s\n", what,
@@ -187,7 +187,7 @@ int hex8_tune_lanes_now(fh_ctx* c) {
     hex8_rows_tune_lanes(tabs.data(), c->h_ntab, 12345u, &cb, &ca, 1000000ll);   // (proposals: a third of round 4's, +1.7 % kernel time for half the tuner's)
     HIP_TRY(c, hipMemcpyAsync(c->h_lanes.p, tabs.data(), sizeof(uint2) * tabs.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->env("FENRIS_HIP_VERBOSE"))
+    if (c->opt.VERBOSE)
         std::fprintf(stderr, "[fenris_hip] hex8 rows: %d lane tables tuned in %.1f ms, modelled LDS cycles per position and operand sweep %.1f -> %.1f (64 = conflict-free)\n",
                      c->h_ntab, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), cb, ca);
     return FH_OK;
@@ -199,7 +199,7 @@ int build_partition(fh_ctx* c) {
     if (c->has_partition) return FH_OK;
     // FENRIS_HIP_VERBOSE: wall time of the stages of this set-up (stream drained at every mark)
     auto t_last = std::chrono::steady_clock::now();
-    const bool vt = c->env("FENRIS_HIP_VERBOSE") != nullptr;
+    const bool vt = c->opt.VERBOSE;
     // (The stream is drained at every stage boundary ALSO without the print: measured on the 216^3 mesh, the first assembly takes 90 ms
     // with these synchronisations and 118 ms without them -- the stages' temporaries are released with work still queued behind them
     // otherwise, and a release then waits out the whole queue inside the runtime.)
@@ -236,8 +236,8 @@ int build_partition(fh_ctx* c) {
     std::vector<unsigned> h_noff_v, adj_off_hv;
     c->part_perm = false;
     const bool perm_cand = c->elem_kind == FH_TET4 && (c->op == FH_LAPLACE || c->op == FH_LINEAR_ELASTIC) && c->row_hi < 0 &&
-                           !c->perm_failed && !c->has_rules && c->fast_ok && N > 64 && !c->env("FENRIS_HIP_NO_ROWS") &&
-                           !c->env("FENRIS_HIP_NO_NODE_ORDER") && !c->env("FENRIS_HIP_TRACE");
+                           !c->perm_failed && !c->has_rules && c->fast_ok && N > 64 && !c->opt.NO_ROWS &&
+                           !c->opt.NO_NODE_ORDER && !c->opt.TRACE;
     if (perm_cand) {
         // how local is the numbering?  fraction of nodes that share an element with their successor
         DevBuf<unsigned char> link_d;
@@ -248,7 +248,7 @@ int build_partition(fh_ctx* c) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         long long linked = 0;
         for (int i = 0; i < N; ++i) linked += lk[i];
-        const bool force = c->env_int("FENRIS_HIP_NODE_ORDER", 0) != 0;
+        const bool force = c->opt.NODE_ORDER.value_or(0) != 0;
         if (force || linked * 2 < (long long)N) {
             { const int rc_h = host_offsets(c); if (rc_h) return rc_h; }
             const int D = c->ei.d;
@@ -306,7 +306,7 @@ int build_partition(fh_ctx* c) {
             h_noff_p = &h_noff_v;
             adj_off_hp = &adj_off_hv;
             c->part_perm = true;
-            if (c->env("FENRIS_HIP_VERBOSE"))
+            if (c->opt.VERBOSE)
                 std::fprintf(stderr, "[fenris_hip] node numbering without locality (%.1f %% of the nodes share an element with their successor): "
                                      "owner blocks formed in Morton order\n", 100.0 * (double)linked / (double)N);
         }
@@ -320,18 +320,18 @@ int build_partition(fh_ctx* c) {
     const bool rows_special = perm_cand;   // tables for the row-owner Tet4 kernel alone: larger blocks (below)
     // Hex8 Laplace / LinearElastic without a mask: the general positions run on k_hex8_rows (36 row lanes per node as well)
     const bool hrows_cand = c->elem_kind == FH_HEX8 && (c->op == FH_LAPLACE || c->op == FH_LINEAR_ELASTIC) && !c->has_rules &&
-                            !c->env("FENRIS_HIP_NO_HEX8_ROWS");
+                            !c->opt.NO_HEX8_ROWS;
     // (row-owner Tet4 tables, by attempt: 13 nodes / 352 entries, 11 / 288, 9 / 256, 7 / 224 -- whatever the lane format takes: 256 lanes, 252 slots,
     // 256 distinct vertices per position; round 6: a position's cost is mostly cost per POSITION, C3 0.456 ms at 9 nodes, 0.394 at 12 - 13)
     static const int rows_nb[4] = {13, 11, 9, 7}, rows_mb[4] = {352, 288, 256, 224};
-    const int nb_target = std::max(1, std::min(64, c->env_int("FENRIS_HIP_GATHER_NB", rows_special ? rows_nb[std::min(c->rows_try, 3)]
+    const int nb_target = std::max(1, std::min(64, c->opt.GATHER_NB.value_or(rows_special ? rows_nb[std::min(c->rows_try, 3)]
                                                                                                      : (S == 1 && !aff_cand && !hrows_cand) ? 8 : 7)));  // < 256: packed in 8 bits
     // Tables for the row-owner Tet4 kernel alone may hold more entries per block than the pipelined kernel's lane mapping takes
     // and more nodes (the lane word has four bits for the node): nine nodes / 256 entries first (C3: 98 k positions of ~170 lanes
     // instead of 171 k of ~90, 0.80 -> 0.64 ms), seven / 224 when that cannot be expressed (0.67 ms), then the standard form
     c->part_rows_only = rows_special;
-    const int mb = std::max(16, std::min(1024, c->env_int("FENRIS_HIP_GATHER_MB", rows_special ? rows_mb[std::min(c->rows_try, 3)] : 128)));
-    const size_t lds_target = (size_t)c->env_int("FENRIS_HIP_GATHER_LDS_KB", 52) * 1024;
+    const int mb = std::max(16, std::min(1024, c->opt.GATHER_MB.value_or(rows_special ? rows_mb[std::min(c->rows_try, 3)] : 128)));
+    const size_t lds_target = (size_t)c->opt.GATHER_LDS_KB.value_or(52) * 1024;
     // accumulators: nb_target typical rows, but at least the largest single row block
     unsigned noff_ends[2] = {0, 0};   // (telescoping sum of the row lengths; two values of the device array: the host copy may not exist)
     if (N) {
@@ -362,7 +362,7 @@ int build_partition(fh_ctx* c) {
     // Numberings made of grid lines: the cut on the device (k_cut_runs), the block offsets never on the host
     bool cut_done = false;
     unsigned max_m = 0;
-    if (aligned && n_hi > n_lo && c->env_int("FENRIS_HIP_HOST_CUT", 0) == 0) {
+    if (aligned && n_hi > n_lo && c->opt.HOST_CUT.value_or(0) == 0) {
         DevBuf<unsigned char> start_d;
         DevBuf<int> info_d;
         HIP_TRY(c, start_d.alloc((size_t)N + 2));
@@ -551,7 +551,7 @@ int build_partition(fh_ctx* c) {
         if (layout_bytes_dyn(c->elem_kind, c->op, WHAT_MATRIX, c->nq, 1, acc, 64, true, mb, c->fast_ok) > LDS_LIMIT)
             return c->fail(FH_UNSUPPORTED, "gather mode: a row block does not fit in LDS; use FH_SCATTER_ATOMIC");
     }
-    if (c->env("FENRIS_HIP_VERBOSE"))
+    if (c->opt.VERBOSE)
         std::fprintf(stderr, "[fenris_hip] gather partition: nblk=%d nb=%d umax=%d mmax=%d acc=%d ub=%d lds=%zu B\n", c->nblk,
                      nb_target, umax, mmax, acc, ub,
                      layout_bytes_dyn(c->elem_kind, c->op, WHAT_MATRIX, c->nq, ub, acc, 64, true, mb, c->fast_ok));
@@ -560,12 +560,12 @@ int build_partition(fh_ctx* c) {
     c->has_rows = false;
     c->a_npos = 0;
     c->npos_gen = c->nblk;
-    if (c->has_pos && !c->env("FENRIS_HIP_NO_PIPE") && c->ei.n == c->ei.ng && c->ei.n <= 8 && c->nblk > 0) {
+    if (c->has_pos && !c->opt.NO_PIPE && c->ei.n == c->ei.ng && c->ei.n <= 8 && c->nblk > 0) {
         const int n = c->ei.n;
         const int ms = (mmax + 3) / 4 * 4;
         const int us = (umax + 3) / 4 * 4;
         // local nodes per lane in the pipelined kernel's phase C
-        int jt = c->env_int("FENRIS_HIP_PIPE_JT", (n % 2 == 0) ? 2 : n);
+        int jt = c->opt.PIPE_JT.value_or((n % 2 == 0) ? 2 : n);
         if (jt != 1 && jt != 2 && jt != 4 && jt != n) jt = 1;
         if (n % jt != 0) jt = 1;
         c->p_jt = jt;
@@ -581,7 +581,7 @@ int build_partition(fh_ctx* c) {
             const bool want_aff = c->elem_kind == FH_HEX8 && c->has_aff && c->has_ghat && c->num_aff > 0 && !c->has_rules &&
                                   !c->aff_failed && c->affine_tol > 0.0 &&
                                   (c->op == FH_LAPLACE || c->op == FH_LINEAR_ELASTIC || (c->op == FH_MASS_SCALAR && c->has_params)) &&
-                                  us <= 32 && nb_target <= 8 && !c->env("FENRIS_HIP_NO_AFFINE");
+                                  us <= 32 && nb_target <= 8 && !c->opt.NO_AFFINE;
             if (want_aff) {
                 HIP_TRY(c, cls_d.alloc((size_t)nblk));
                 hipLaunchKernelGGL(k_block_class, dim3((nblk + 255) / 256), dim3(256), 0, c->stream, c->gt_hdr.p, c->gt_elems.p,
@@ -607,7 +607,7 @@ int build_partition(fh_ctx* c) {
             // host loops with their uploads were 18 ms of the 216^3 mesh's first assembly)
             const bool ident_aff = all_affine;
             if (ident_aff) {
-            } else if (!c->env("FENRIS_HIP_NO_SWEEP") && !all_affine) {
+            } else if (!c->opt.NO_SWEEP && !all_affine) {
                 DevBuf<int> node2blk, succ_d;
                 HIP_TRY(c, node2blk.alloc((size_t)N + 1));
                 HIP_TRY(c, hipMemsetAsync(node2blk.p, 0xff, sizeof(int) * ((size_t)N + 1), c->stream));  // -1: not in a block
@@ -727,7 +727,7 @@ int build_partition(fh_ctx* c) {
                 mark("position tables of the general class");
             }
             c->has_pipe = true;
-            if (c->env("FENRIS_HIP_VERBOSE"))
+            if (c->opt.VERBOSE)
                 std::fprintf(stderr, "[fenris_hip] sweep order: %d general blocks in %d chains, %d affine blocks in %d chains (us=%d ms=%d)\n",
                              c->npos_gen, (int)chain_off[0].size() - 1, c->a_npos, ident_aff ? c->a_npos : (int)chain_off[1].size() - 1, us, ms);
             c->has_rows = false;
@@ -738,7 +738,7 @@ int build_partition(fh_ctx* c) {
             // tables are kept: they serve every other rule and per-element parameters.
             c->has_hrows = false;
             if (c->elem_kind == FH_HEX8 && (c->op == FH_LAPLACE || c->op == FH_LINEAR_ELASTIC) && us <= HEX8_ROWS_US && nb_target <= 8 && npg > 0 &&
-                !c->has_rules && !c->env("FENRIS_HIP_NO_HEX8_ROWS")) {
+                !c->has_rules && !c->opt.NO_HEX8_ROWS) {
                 bool bad = false;
                 int rs = build_lane_tables(c, c->p_rec.p, us, ms, nb_target, npg, S, c->p_conn.p, c->p_elem.p, c->h_hdr, c->h_lanes, c->h_ntab,
                                            c->h_incomplete, bad, "hex8 rows", 1);
@@ -749,8 +749,8 @@ int build_partition(fh_ctx* c) {
                     // the tuner takes 18 ms on the 216^3 mesh and buys 0.16 ms per assembly (the matrix is the same bit for bit either way): a
                     // caller who assembles once never needs it, a Newton loop pays it on its second assembly.
                     c->h_tune_pending = 0;
-                    if (c->h_ntab <= 4096 && !c->env("FENRIS_HIP_NO_LANE_TUNING")) {
-                        c->h_tune_pending = 1 + std::max(0, c->env_int("FENRIS_HIP_TUNE_AFTER", 1));
+                    if (c->h_ntab <= 4096 && !c->opt.NO_LANE_TUNING) {
+                        c->h_tune_pending = 1 + std::max(0, c->opt.TUNE_AFTER.value_or(1));
                         if (c->h_tune_pending == 1) { const int rt = hex8_tune_lanes_now(c); if (rt) return rt; }
                     }
                     HIP_TRY(c, c->h_pos.alloc((size_t)npg * 4));
@@ -760,12 +760,12 @@ int build_partition(fh_ctx* c) {
                 }
                 c->h_hdr.release();   // folded into the position records
                 mark("lane tables of the general class (hex8 rows)");
-                if (c->env("FENRIS_HIP_VERBOSE"))
+                if (c->opt.VERBOSE)
                     std::fprintf(stderr, "[fenris_hip] row-owner lanes (Hex8, general positions): %s\n", c->has_hrows ? "built" : "mesh not expressible, pipelined kernel kept");
             }
             // Tet4 with a one-point rule: the row-owner kernel is the default (C3: 1.31 -> 0.85 ms), FENRIS_HIP_NO_ROWS keeps
             // the pipelined kernel
-            if (c->elem_kind == FH_TET4 && us * 4 <= 1024 && nb_target <= 16 && npg > 0 && !c->env("FENRIS_HIP_NO_ROWS")) {
+            if (c->elem_kind == FH_TET4 && us * 4 <= 1024 && nb_target <= 16 && npg > 0 && !c->opt.NO_ROWS) {
                 c->r_rw = 8 + us / 4 + nb_target + 1 + nb_target;
                 DevBuf<unsigned> row_real;   // first entry of every node's real row, in the order of the blocks
                 HIP_TRY(c, row_real.alloc((size_t)N + 1));
@@ -828,7 +828,7 @@ int build_partition(fh_ctx* c) {
                 c->has_rows = bad == 0;
                 HIP_TRY(c, hipStreamSynchronize(c->stream));  // row_real is released at the end of this scope
                 mark("row vertices (Tet4)");
-                if (c->env("FENRIS_HIP_VERBOSE"))
+                if (c->opt.VERBOSE)
                     std::fprintf(stderr, "[fenris_hip] row-owner lanes (Tet4, %d lanes and %d vertices per position): %s\n", c->r_ls, c->r_vn,
                                  c->has_rows ? "built" : "mesh not expressible, pipelined kernel kept");
             }

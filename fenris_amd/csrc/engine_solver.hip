@@ -78,7 +78,7 @@ extern "C++" int sum_partials(fh_ctx* c, const double* dev, int blocks, int K, d
 // ones: 6.7).  The per-workgroup partials of x . y go to `scratch` and are summed over `partials` contiguous ranges in a fixed order.
 static int spmv_launch(fh_ctx* c, const double* vals, const double* x, double* y, double* partial, int partials, DevBuf<double>* scratch) {
     const int N = (int)c->N;
-    const bool half = c->max_row <= 32 && !c->env("FENRIS_HIP_SPMV_WAVE_PER_NODE");   // half a wavefront per node, one lane per column block
+    const bool half = c->max_row <= 32 && !c->opt.SPMV_WAVE_PER_NODE;   // half a wavefront per node, one lane per column block
     const int grid = std::max(1, half ? (N + 15) / 16 : (N + 3) / 4);
     double* wg_partial = nullptr;
     if (partial) {

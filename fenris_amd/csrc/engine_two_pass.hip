@@ -14,7 +14,7 @@ int launch_hex27_blocks(fh_ctx* c, long long w0, long long w1, hipStream_t st) {
     a.labels = c->has_mask ? c->active_list.p : nullptr;
     a.work_begin = w0;
     a.work_end = w1;
-    if (!c->env("FENRIS_HIP_HEX27_NO_LEX")) {
+    if (!c->opt.HEX27_NO_LEX) {
         a.conn = c->tp_conn.p;   // nodes in lexicographic order (assemble_two_pass built the tables)
         a.gref = c->gref_lex.p;
         a.gref_t = c->gref_t_lex.p;
@@ -29,12 +29,10 @@ int launch_hex27_blocks(fh_ctx* c, long long w0, long long w1, hipStream_t st) {
     // (scripts/attic/hex27_mfma_tiles_r05.hpp) took 7.1 - 7.4 ms for C4 where this form takes 6.6 - 6.9 (profiles/r06_c4_triangle.txt).
     const size_t lds1 = sizeof(double) * (size_t)Hex27BlkLds::total;
     const int wgs_default = (int)std::min<size_t>(4, LDS_LIMIT / lds1);
-    int dev_cus = 256;
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
     // (FENRIS_HIP_TWO_PASS_GRID: tests force many elements / nodes per workgroup on small meshes)
     // eight times the resident workgroups, dispatched in order (each strides over ~24 elements on C4): 1 / 2 / 4 / 16 x the resident ones 6.15 / 6.08 /
     // 6.04 / 6.03 ms, one element per workgroup 6.54 (the tables a workgroup stages once)
-    const int grid1 = std::max(1, (int)std::min<long long>(w1 - w0, c->env_int("FENRIS_HIP_TWO_PASS_GRID", 8 * dev_cus * std::max(1, c->env_int("FENRIS_HIP_HEX27_WGS_PER_CU", wgs_default)))));
+    const int grid1 = std::max(1, (int)std::min<long long>(w1 - w0, c->opt.TWO_PASS_GRID.value_or(8 * c->num_cus * std::max(1, c->opt.HEX27_WGS_PER_CU.value_or(wgs_default)))));
     void (*kern)(const KArgs, double, double);
     if (a.trace) kern = c->op == FH_NEO_HOOKEAN ? k_hex27_dense_blocks<FH_NEO_HOOKEAN, true> : k_hex27_dense_blocks<FH_LINEAR_ELASTIC, true>;   // FENRIS_HIP_TRACE: per-phase cycles
     else kern = c->op == FH_NEO_HOOKEAN ? k_hex27_dense_blocks<FH_NEO_HOOKEAN> : k_hex27_dense_blocks<FH_LINEAR_ELASTIC>;
@@ -52,7 +50,7 @@ int launch_rows_t(fh_ctx* c, int layout, hipStream_t st, const PT* pos, const un
     const size_t lds = (size_t)wpb * sizeof(double) * SS * SS * max_row;
     if (layout != 0) {   // node-block triangles: 2 = upper (Hex27 from hex27_blocks.hpp), 1 = lower (the generic first pass with ke_tri)
         if (SS != 3) return c->fail(FH_HIP_ERROR, "two-pass gather: the triangle layouts are for s = 3");
-        const int abl = c->env_int("FENRIS_HIP_ABLATE", 0) >> 8;   // (profiling, timing only: bits 8.. = no stores / no value loads / no LDS adds / no clearing in the second pass)
+        const int abl = c->opt.ABLATE.value_or(0) >> 8;   // (profiling, timing only: bits 8.. = no stores / no value loads / no LDS adds / no clearing in the second pass)
         typedef void (*tri_kernel)(const unsigned*, const unsigned*, const unsigned*, const PT*, const double*, double*, int, int, const int*, int, int, int);
         tri_kernel kt = nullptr;
         const int n = (int)c->ei.n;
@@ -63,11 +61,11 @@ int launch_rows_t(fh_ctx* c, int layout, hipStream_t st, const PT* pos, const un
         overwrite = (overwrite ? 1 : 0) | (abl << 8);
         // consecutive nodes per wavefront: 4, more when the grid would pass its cap (small grids in the tests: FENRIS_HIP_TWO_PASS_GRID);
         // nodes per wavefront slot of an XCD's chunk: 1 024 (a chunk = 4 096 nodes; 0 = workgroups in launch order)
-        int npw = std::max(1, c->env_int("FENRIS_HIP_TWO_PASS_NODES_PER_WAVE", 4));
+        int npw = std::max(1, c->opt.TWO_PASS_NODES_PER_WAVE.value_or(4));
         while ((long long)grid_cap * wpb * npw < count) npw *= 2;
         const int grid = std::max(1, (count + wpb * npw - 1) / (wpb * npw));
         return launch_lds(c, kt, dim3(grid), dim3(threads), lds, st, c->noff.p, adj_off, adj, pos, c->ke_dense.p, values_dev, overwrite, (int)max_row,
-                          node_list, count, npw, std::max(0, c->env_int("FENRIS_HIP_TWO_PASS_XCD_CHUNK", 1024) / npw));
+                          node_list, count, npw, std::max(0, c->opt.TWO_PASS_XCD_CHUNK.value_or(1024) / npw));
     }
     void (*kern)(int, int, const unsigned*, const unsigned*, const unsigned*, const PT*, const double*, double*, int, int, const int*, int) =
         k_rows_from_dense<SS, PT>;
@@ -99,11 +97,11 @@ int launch_rows(fh_ctx* c, int layout, hipStream_t st, const unsigned* adj_off, 
 // (generic first pass, s = 3 on the 3D elements, symmetric operators: half the bytes between the passes, written as runs of 72 bytes)
 static int two_pass_layout(fh_ctx* c) {
     const bool mfma = c->elem_kind == FH_HEX27 && (c->op == FH_LINEAR_ELASTIC || c->op == FH_NEO_HOOKEAN) && !c->has_rules &&
-                      c->nq == 27 && c->has_params && c->gref_t.p != nullptr && c->has_hex27_perm && !c->env("FENRIS_HIP_NO_MFMA");
+                      c->nq == 27 && c->has_params && c->gref_t.p != nullptr && c->has_hex27_perm && !c->opt.NO_MFMA;
     if (mfma) return 2;
     const int n = (int)c->ei.n;
     const bool tri = c->S() == 3 && c->ei.d == 3 && !c->ragged && (n == 4 || n == 8 || n == 10 || n == 20 || n == 27) &&
-                     !(c->op == FH_TENSOR && !c->tensor_sym) && !c->env("FENRIS_HIP_TWO_PASS_FULL");
+                     !(c->op == FH_TENSOR && !c->tensor_sym) && !c->opt.TWO_PASS_FULL;
     return tri ? 1 : 0;
 }
 size_t two_pass_dense_doubles(fh_ctx* c) {
@@ -126,7 +124,7 @@ int assemble_two_pass(fh_ctx* c, double* values_dev, int overwrite) {
     const unsigned* adj_off = c->has_mask ? c->n2e_off_c.p : c->n2e_off.p;
     const unsigned* adj = c->has_mask ? c->n2e_c.p : c->n2e.p;
     const bool wide = max_row >= 256;
-    const bool lex = layout == 2 && !c->env("FENRIS_HIP_HEX27_NO_LEX");
+    const bool lex = layout == 2 && !c->opt.HEX27_NO_LEX;
     if (!c->has_tp_pos || c->tp_pos_layout != layout + (lex ? 16 : 0)) {  // once per pattern / element mask / layout
         // number of (node, element) adjacencies: the last offset, read from the device (round 5: this used to pull both offset arrays to the host)
         unsigned last_off = 0;
@@ -176,7 +174,7 @@ int assemble_two_pass(fh_ctx* c, double* values_dev, int overwrite) {
     // L2s (17.7 -> 10.1 GB) and make the pass SLOWER, 3.4 -> 3.6 - 4.1 ms; the pass follows its occupancy instead (4 / 8 / 16 / 20 wavefronts per
     // CU: 7.4 / 4.5 / 3.4 / ~3.25 ms), which registers and the LDS rows of the longest node row hold at 16.)
     const int* node_list = nullptr;
-    const int rows_grid_cap = c->env_int("FENRIS_HIP_TWO_PASS_ROWS_GRID", c->env_int("FENRIS_HIP_TWO_PASS_GRID", 1 << 17));   // (C4: 2^17 workgroups 8.33 ms, one per four nodes (410 k) 8.42, 2^13 8.45, 2^11 8.68)
+    const int rows_grid_cap = c->opt.TWO_PASS_ROWS_GRID.value_or(c->opt.TWO_PASS_GRID.value_or(1 << 17));   // (C4: 2^17 workgroups 8.33 ms, one per four nodes (410 k) 8.42, 2^13 8.45, 2^11 8.68)
     c->last_kernel = mfma ? "k_hex27_dense_blocks + k_rows_from_tri" : layout == 1 ? "k_assemble_matrix<dump> + k_rows_from_tri" : "k_assemble_matrix<dump> + k_rows_from_dense";
 
     // ---- serial form: all element matrices, then all rows

@@ -10,11 +10,9 @@ static int launch_vector_stream_nt(fh_ctx* c, KArgs& a) {
     constexpr int EPB = NT / ElemT<EK>::N;
     const size_t lds = make_layout<EK, OP, WHAT_VECTOR>(a.nq, EPB, 0, 0, false, 0, 1).bytes();
     if (lds > LDS_TARGET + 8 * 1024) return -1;
-    int dev_cus = 256;
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
     const long long nbatch = (a.work_end - a.work_begin + EPB - 1) / EPB;
-    const int per_cu = std::max(1, (int)std::min<size_t>(c->env_int("FENRIS_HIP_VEC_WGS_PER_CU", 3), (LDS_LIMIT - 512) / std::max<size_t>(lds, 1)));
-    const int grid = std::max(1, (int)std::min<long long>(nbatch, (long long)c->env_int("FENRIS_HIP_PIPE_GRID", dev_cus * per_cu)));   // (tests force many batches per workgroup)
+    const int per_cu = std::max(1, (int)std::min<size_t>(c->opt.VEC_WGS_PER_CU.value_or(3), (LDS_LIMIT - 512) / std::max<size_t>(lds, 1)));
+    const int grid = std::max(1, (int)std::min<long long>(nbatch, (long long)c->opt.PIPE_GRID.value_or(c->num_cus * per_cu)));   // (tests force many batches per workgroup)
     return launch_lds(c, k_assemble_vector_stream<EK, OP, NT>, dim3(grid), dim3(NT), lds, c->stream, a);
 }
 template <int EK, int OP>
@@ -68,9 +66,11 @@ static int launch_vector_from_elements(fh_ctx* c, int sdim, double* out_dev) {
     });
 }
 static bool element_pass_covers(const fh_ctx* c) {
-    return !c->ragged && !c->env("FENRIS_HIP_NO_ELEMENT_PASS") &&
+    return !c->ragged && !c->opt.NO_ELEMENT_PASS &&
            (c->elem_kind == FH_HEX8 || c->elem_kind == FH_TET4 || c->elem_kind == FH_QUAD4 || c->elem_kind == FH_TRI3);
 }
+// the element tiles (vector_tiles.hip) serve this context
+static bool tiles_enabled(const fh_ctx* c) { return element_pass_covers(c) && !c->opt.VECTOR_ATOMICS && !c->opt.NO_VECTOR_TILES; }
 
 extern "C" {
 
@@ -131,7 +131,7 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
     // small iso-parametric elements: tiles of 256 elements, one thread per element, the tile's distinct nodes summed in LDS, only
     // those partial sums through HBM, then one thread per node (vector_tiles.hip); no atomics, bitwise reproducible; an element mask
     // zeroes the contributions of the inactive elements
-    if (element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->env("FENRIS_HIP_NO_VECTOR_TILES") && c->op <= FH_STVK) {
+    if (tiles_enabled(c) && c->op <= FH_STVK) {
         rc = ensure_vector_tiles(c);
         if (rc) return rc;
         if (!c->vt_bad) {
@@ -150,7 +150,7 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
     }
     // small iso-parametric elements without an element list: one thread per element, element vectors laid out by local node, then
     // one thread per node (element_pass.hpp); no atomics, bitwise reproducible
-    if (!a.labels && element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS")) {
+    if (!a.labels && element_pass_covers(c) && !c->opt.VECTOR_ATOMICS) {
         rc = build_pattern(c);  // the node -> (element, local node) adjacency comes with the pattern
         if (rc) return rc;
         const size_t need = (size_t)c->E * c->ei.n * c->S();
@@ -170,7 +170,7 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
     // Two passes by default: element vectors to a scratch buffer, then one thread per row sums its node's entries in
     // ascending element order -- no atomics, bitwise reproducible (FENRIS_HIP_VECTOR_ATOMICS keeps the one-pass scatter)
     if (!a.labels) {
-        const bool two_pass = !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->ragged &&
+        const bool two_pass = !c->opt.VECTOR_ATOMICS && !c->ragged &&
                               (c->elem_kind == FH_HEX8 || c->elem_kind == FH_TET4 || c->elem_kind == FH_QUAD4);
         if (two_pass) {
             rc = build_pattern(c);  // the node -> (element, local node) adjacency comes with the pattern
@@ -257,7 +257,7 @@ int fh_assemble_source_vector_dev(fh_ctx* c, uint32_t sdim, const double* g, con
     if (a.work_end == 0) return FH_OK;
     // small iso-parametric elements: the tiles of the residual (vector_tiles.hip) -- element vectors summed per distinct node of a tile
     // in LDS, partial sums through HBM, one thread per node; an element mask zeroes the inactive elements
-    if (element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && !c->env("FENRIS_HIP_NO_VECTOR_TILES")) {
+    if (tiles_enabled(c)) {
         rc = ensure_vector_tiles(c);
         if (rc) return rc;
         if (!c->vt_bad) {
@@ -277,11 +277,11 @@ int fh_assemble_source_vector_dev(fh_ctx* c, uint32_t sdim, const double* g, con
     }
     // two passes without atomics where the node adjacency is available (it comes with the pattern, which needs an operator
     // for the solution dimension): element vectors to scratch, then a per-row sum in element order
-    bool two_pass = !a.labels && !c->ragged && c->op >= 0 && !c->env("FENRIS_HIP_VECTOR_ATOMICS");
+    bool two_pass = !a.labels && !c->ragged && c->op >= 0 && !c->opt.VECTOR_ATOMICS;
     if (two_pass && build_pattern(c) != FH_OK) two_pass = false;
     // a context without an operator (the usual case of a source assembler): the adjacency alone, for the element pass
     const unsigned *adj_off = nullptr, *adj = nullptr;
-    if (!two_pass && !a.labels && c->op < 0 && element_pass_covers(c) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") && build_source_adjacency(c) == FH_OK) {
+    if (!two_pass && !a.labels && c->op < 0 && element_pass_covers(c) && !c->opt.VECTOR_ATOMICS && build_source_adjacency(c) == FH_OK) {
         two_pass = true;
         adj_off = c->src_n2e_off.p;
         adj = c->src_n2e.p;
@@ -426,7 +426,8 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
     if (a.work_end == 0) return FH_OK;
     // element tiles (vector_tiles.hip): the elements in the tiles' (space-compact) order -- what makes the gathers local on a numbering
     // without locality (C3's permuted tetrahedra: 0.76 -> 0.20 ms per call); an element mask zeroes the inactive elements' energies
-    if (element_pass_covers(c) && !c->env("FENRIS_HIP_NO_VECTOR_TILES")) {
+    // (deliberately not tiles_enabled: the energy is a sum of partials whatever VECTOR_ATOMICS says, so that switch leaves it on the tiles)
+    if (element_pass_covers(c) && !c->opt.NO_VECTOR_TILES) {
         rc = ensure_vector_tiles(c);
         if (rc) return rc;
         if (!c->vt_bad) {
@@ -540,7 +541,7 @@ static int mf_scale_from(fh_ctx* c, const double* diag_dev, double alpha = 0.0, 
 // residual's element pass fed xin (linear operators), or k_tangent_tiled at the context's u.  *done = false: the tiles do not cover it.
 static int mf_tiles_pass(fh_ctx* c, KArgs& a, const double* xin, bool* done) {
     *done = false;
-    if (!element_pass_covers(c) || c->env("FENRIS_HIP_VECTOR_ATOMICS") || c->env("FENRIS_HIP_NO_VECTOR_TILES")) return FH_OK;
+    if (!tiles_enabled(c)) return FH_OK;
     const int rc = ensure_vector_tiles(c);
     if (rc || c->vt_bad) return rc;
     const size_t need = (size_t)c->vt.v.npartials * c->S();
@@ -739,7 +740,7 @@ int mf_shift_ready(fh_ctx* c, const char* who, double alpha, double beta) {
 // the mass partials of the current table over the tiles into c->fe_scratch (x null: the diagonal); *done = false: the tiles do not cover it
 static int mass_tiles_pass(fh_ctx* c, const double* x, const unsigned char* dmask, bool* done) {
     *done = false;
-    if (!element_pass_covers(c) || c->ei.ng != c->ei.n || c->env("FENRIS_HIP_VECTOR_ATOMICS") || c->env("FENRIS_HIP_NO_VECTOR_TILES")) return FH_OK;
+    if (!tiles_enabled(c) || c->ei.ng != c->ei.n) return FH_OK;
     const int rc = ensure_vector_tiles(c);
     if (rc || c->vt_bad) return rc;
     const size_t need = (size_t)c->vt.v.npartials * c->S();
@@ -828,9 +829,7 @@ int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bo
 // *done = false: not covered, nothing was run.
 static int shift_hex8_fused(fh_ctx* c, double alpha, double beta, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials, bool* done) {
     *done = false;
-    if (c->elem_kind != FH_HEX8 || !element_pass_covers(c) || c->env("FENRIS_HIP_VECTOR_ATOMICS") ||
-        c->env("FENRIS_HIP_NO_VECTOR_TILES"))
-        return FH_OK;
+    if (c->elem_kind != FH_HEX8 || !tiles_enabled(c)) return FH_OK;
     KArgs a;
     fill_common(c, a);
     if (!a.qmono) return FH_OK;
@@ -976,8 +975,7 @@ int newton_residual(fh_ctx* c, double alpha, double beta, const double* f, const
     int count = 0;   // per-workgroup partials of |F|^2 in ns.wg
     int rc;
     if (ns.F.n < (size_t)n) HIP_TRY(c, ns.F.alloc((size_t)n));
-    if (c->E > 0 && !c->rs.active && element_pass_covers(c) && (alpha == 0.0 || c->ei.ng == c->ei.n) && !c->env("FENRIS_HIP_VECTOR_ATOMICS") &&
-        !c->env("FENRIS_HIP_NO_VECTOR_TILES")) {
+    if (c->E > 0 && !c->rs.active && tiles_enabled(c) && (alpha == 0.0 || c->ei.ng == c->ei.n)) {
         rc = ensure_vector_tiles(c);
         if (rc) return rc;
         if (!c->vt_bad) {

@@ -34,7 +34,8 @@ extern "C" {
 
 #define FH_ABI_VERSION 1
 
-/* Tuning and diagnostics: environment variables named FENRIS_HIP_* (scripts/README.md) are read ONCE, by fh_create, into the
+/* Tuning and diagnostics: environment variables named FENRIS_HIP_* (the table fenris_amd/csrc/options.def declares every one, with its
+ * reading, default and meaning; fh_option_name lists the names) are read ONCE, by fh_create, into the
  * context; no later call reads the environment.  They change which kernel variant runs or print diagnostics, never results
  * beyond rounding -- except FENRIS_HIP_ABLATE / FENRIS_HIP_TRACE, which select instrumented instantiations for profiling
  * (FENRIS_HIP_ABLATE switches work off and produces wrong values by design). */
@@ -284,8 +285,12 @@ int fh_poll_status(fh_ctx*, uint64_t* failed_element);
  * kept.  BOTH need FH_ASSEMBLE_OVERWRITE (the timed / trial
  * assemblies are real ones and write `values`; FH_BAD_ARGUMENT otherwise).  No reference counterpart. */
 /* A tuning switch of this context (a FENRIS_HIP_* name as fh_create reads them from the environment): set, or removed with value ==
- * NULL.  Launch-variant switches act at the next call.  For comparing variants inside ONE context on the same buffers. */
+ * NULL.  Launch-variant switches act at the next call.  For comparing variants inside ONE context on the same buffers.  A name that
+ * fenris_amd/csrc/options.def does not declare is FH_BAD_ARGUMENT (fh_last_error names it), and so is FENRIS_HIP_RCCL_LIB, which is read
+ * from the environment of the process and not per context. */
 int fh_set_option(fh_ctx*, const char* name, const char* value);
+/* The full name ("FENRIS_HIP_...") of the index-th declared switch, NULL past the end of the table.  Needs neither a context nor a GPU. */
+const char* fh_option_name(int index);
 /* Device memory through the virtual-memory API with an explicit physical chunk size (hipMemAddressReserve / hipMemCreate / hipMemMap): `bytes`
  * on `device` from chunks of `chunk_bytes` (rounded up to the allocation granularity, reported in *granularity_out; 0 = one chunk).  For
  * experiments on how a large `values` array is backed (profiles/r05_vmm_experiment.txt); free with fh_vmm_free.  No reference counterpart. */
