@@ -17,6 +17,7 @@
 #pragma once
 #include <type_traits>
 #include "device_common.hpp"
+#include "material.hpp"
 #include "small_ops.hpp"
 
 namespace fenris_hip {
@@ -369,17 +370,7 @@ __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double
                 for (int k = 0; k < S; ++k) gu[i][k] = fma(g[i], Ue[n * S + k], gu[i][k]);
         }
     }
-    if constexpr (VCOMPACT) {  // grad u = J^-T R
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                double t = 0.0;
-#pragma unroll
-                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], Rm[m % (VCOMPACT ? D : 1)][k % (VCOMPACT ? S : 1)], t);
-                gu[i][k] = t;
-            }
-    }
+    if constexpr (VCOMPACT) pull_back<D, S>(Ji, Rm, gu);
     double mu = 0.0, lambda = 0.0;
     if (OP != FH_LAPLACE) {
         if (a.rule_map) {  // per-element data (compact table): the slow path, never with L.fast
@@ -399,7 +390,9 @@ __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double
         }
     }
 
-    // deformation gradient F = I + (grad u)^T  (fenris-solid/src/lib.rs:20-29)
+    // deformation gradient F = I + (grad u)^T  (fenris-solid/src/lib.rs:20-29) for the matrix coefficients below; the vector and scalar forms
+    // take material_point's.  (Written out, not deformation_gradient(): through it sixteen k_assemble_matrix<*, FH_NEO_HOOKEAN, *> kernels come
+    // out with other registers, and the assembled path keeps its device code: profiles/material_refactor_device_code.txt)
     double F[D][D];
     if (S == D && want_u) {
 #pragma unroll
@@ -444,17 +437,9 @@ __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double
                     at[n * D + i] = t;
                 }
         } else {  // StVK, materials.rs:417-438
-            double Eg[D][D];  // Green strain (F^T F - I)/2
+            double Eg[D][D];
             double trE = 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(F[k][i], F[k][j], t);
-                    Eg[i][j] = (t - (i == j ? 1.0 : 0.0)) * 0.5;
-                }
+            green_strain<D>(F, Eg);
 #pragma unroll
             for (int i = 0; i < D; ++i) trE += Eg[i][i];
             coef[0] = s * 2.0 * mu;
@@ -485,116 +470,18 @@ __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double
                     eg[n * D + i] = t2;
                 }
         }
-    } else {
+    } else if constexpr (OP <= FH_STVK) {   // (the operators with a stress: the mass operators and FH_TENSOR have no vector / scalar form)
         // stress P (s x d), scaled by s, for the residual; energy density for the scalar path
         double P[S][D];
-        double psi = 0.0;
-        if (OP == FH_LAPLACE) {
-            // g^T = (grad u)^T (laplace.rs:52-56); psi = 1/2 |grad u|^2 (laplace.rs:35-37)
-#pragma unroll
-            for (int k = 0; k < D; ++k) { P[0][k] = gu[k][0]; psi = fma(gu[k][0], gu[k][0], psi); }
-            psi *= 0.5;
-        } else if (OP == FH_LINEAR_ELASTIC) {
-            // eps = sym(F) - I formed from F like the reference does (materials.rs:71-79)
-            double eps[D][D];
-            double tr = 0.0, ee = 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    eps[i][j] = (F[j][i] + F[i][j]) * 0.5 - (i == j ? 1.0 : 0.0);
-                    ee = fma(eps[i][j], eps[i][j], ee);
-                }
-#pragma unroll
-            for (int i = 0; i < D; ++i) tr += eps[i][i];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) P[i % S][j] = eps[i][j] * 2.0 * mu + (i == j ? lambda * tr : 0.0);
-            psi = mu * ee + 0.5 * lambda * (tr * tr);
-        } else if (OP == FH_NEO_HOOKEAN) {
-            const double Jd = det_small<D>(F);
-            if (Jd <= 0.0) {  // materials.rs:271-274
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) P[i % S][j] = __builtin_nan("");
-            } else {
-                double Fi[D][D];
-                inv_small(F, Jd, Fi);
-                const double c = -mu + lambda * log(Jd);
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) P[i % S][j] = Fi[j][i] * c + F[i][j] * mu;
-            }
-            if (WHAT == WHAT_SCALAR) {
-                // materials.rs:249-262 with log_det_F of du_dX = (grad u)^T (logdet.rs:17-86)
-                double U[D][D];
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) U[i][j] = gu[j][i % S];
-                double gamma;
-                if (D == 2) {
-                    gamma = U[0][0] * U[1][1] + U[0][0] + U[1][1] - U[0][1] * U[1][0];
-                } else {
-                    const double u11 = U[0][0], u22 = U[1][1], u33 = U[2 % D][2 % D];
-                    const double aa = 1.0 + u11, e2 = 1.0 + u22, i2 = 1.0 + u33;
-                    const double b = U[0][1], c = U[0][2 % D], d2 = U[1][0], f = U[1][2 % D], g = U[2 % D][0], h = U[2 % D][1];
-                    gamma = u11 * u22 * u33 + u11 * u22 + u11 * u33 + u22 * u33 + u11 + u22 + u33 + b * f * g + c * d2 * h -
-                            c * e2 * g - b * d2 * i2 - aa * f * h;
-                }
-                if (gamma > -1.0) {
-                    const double logJ = log1p(gamma);
-                    double trU = 0.0, nn = 0.0;
-#pragma unroll
-                    for (int i = 0; i < D; ++i) {
-                        trU += U[i][i];
-#pragma unroll
-                        for (int j = 0; j < D; ++j) nn = fma(U[i][j], U[i][j], nn);
-                    }
-                    psi = mu * (trU + 0.5 * nn) - mu * logJ + (0.5 * lambda) * (logJ * logJ);
-                } else {
-                    psi = __builtin_inf();
-                }
-            }
-        } else {  // StVK: P = F E 2 mu + F lambda tr E ; psi = mu E:E + lambda/2 tr^2
-            double Eg[D][D];
-            double trE = 0.0, ee = 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(F[k][i], F[k][j], t);
-                    Eg[i][j] = (t - (i == j ? 1.0 : 0.0)) * 0.5;
-                    ee = fma(Eg[i][j], Eg[i][j], ee);
-                }
-#pragma unroll
-            for (int i = 0; i < D; ++i) trE += Eg[i][i];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(F[i][k], Eg[k][j], t);
-                    P[i % S][j] = t * 2.0 * mu + F[i][j] * lambda * trE;
-                }
-            psi = mu * ee + 0.5 * lambda * (trE * trE);
-        }
+        double psi;
+        material_point<OP, D, S, WHAT == WHAT_SCALAR ? EP_SCALAR : EP_VECTOR>(gu, mu, lambda, P, psi);
         if (WHAT == WHAT_VECTOR && VCOMPACT) {
+            double M[S][D];
+            push_forward<D, S>(s, P, Ji, M);
 #pragma unroll
             for (int i = 0; i < S; ++i)
 #pragma unroll
-                for (int m = 0; m < D; ++m) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(P[i][k], Ji[m][k], t);
-                    qp[i * D + m] = s * t;
-                }
+                for (int m = 0; m < D; ++m) qp[i * D + m] = M[i][m];
         } else if (WHAT == WHAT_VECTOR) {
             double* sp = qp + N * D;
 #pragma unroll

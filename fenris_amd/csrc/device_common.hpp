@@ -150,6 +150,12 @@ struct KArgs {
     int nb_max;              // max nodes per block
 };
 
+// The quadrature tables (weights, reference gradients, basis values, uniform parameters) are read at wavefront-uniform addresses and
+// never written while a kernel runs: through the constant address space they come by scalar loads (s_load) and enter the
+// multiplications as scalar operands -- as plain global loads every table entry was a 64-lane vector load of one address.
+typedef const __attribute__((address_space(4))) double* ep_table;
+__device__ __forceinline__ ep_table ep_const(const double* p) { return (ep_table)p; }
+
 __device__ __forceinline__ void report_singular(DevStatus* st, long long e) {
     st->singular = 1;
     atomicMin(&st->failed_elem, static_cast<unsigned long long>(e));

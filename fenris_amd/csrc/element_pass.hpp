@@ -5,7 +5,8 @@
 //
 //  * a thread fetches its element's node indices, vertex coordinates and u once (8-byte gathers whose lanes walk consecutive
 //    nodes of consecutive elements), keeps them in registers and walks the quadrature points: J = X G^T, its inverse,
-//    grad u = J^-T (sum_n ghat_n u_n^T), the operator's stress / energy density, and f_n += (s P J^-T) ghat_n -- what
+//    grad u = J^-T (sum_n ghat_n u_n^T), the operator's stress / energy density (material.hpp), and f_n += (s P J^-T) ghat_n
+//    (the point geometry: small_ops.hpp) -- what
 //    assemble_element_elliptic_vector / compute_element_elliptic_energy do per point (src/assembly/local/elliptic.rs:457-605),
 //    with the physical gradients never formed.  The reference-gradient table is uniform over the wavefront: it comes through
 //    scalar loads and enters the multiplications as a scalar operand.
@@ -23,126 +24,10 @@
 #include <type_traits>
 
 #include "device_common.hpp"
+#include "material.hpp"
 #include "small_ops.hpp"
 
 namespace fenris_hip {
-
-enum { EP_VECTOR = 0, EP_SCALAR = 1 };
-
-// The quadrature tables (weights, reference gradients, basis values, uniform parameters) are read at wavefront-uniform addresses and
-// never written while a kernel runs: through the constant address space they come by scalar loads (s_load) and enter the
-// multiplications as scalar operands -- as plain global loads every table entry was a 64-lane vector load of one address.
-typedef const __attribute__((address_space(4))) double* ep_table;
-__device__ __forceinline__ ep_table ep_const(const double* p) { return (ep_table)p; }
-
-// stress P (s x d) and energy density psi of one quadrature point from grad u (d x s):
-// laplace.rs:26-73; fenris-solid/src/materials.rs:71-123 (LinearElastic), 236-353 (NeoHookean, J <= 0 => NaN block / inf),
-// 392-469 (StVK).  Same formulas as phase B of assemble_kernels.hpp.
-template <int OP, int D, int S, int WHAT>
-__device__ __forceinline__ void material_point(const double (&gu)[D][S], double mu, double lambda, double (&P)[S][D], double& psi) {
-    psi = 0.0;
-    if constexpr (OP == FH_LAPLACE) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) { P[0][k] = gu[k][0]; psi = fma(gu[k][0], gu[k][0], psi); }
-        psi *= 0.5;
-    } else {
-        double F[D][D];  // F = I + (grad u)^T  (fenris-solid/src/lib.rs:20-29)
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + gu[j][i];
-        if constexpr (OP == FH_LINEAR_ELASTIC) {
-            double eps[D][D];
-            double tr = 0.0, ee = 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    eps[i][j] = (F[j][i] + F[i][j]) * 0.5 - (i == j ? 1.0 : 0.0);
-                    ee = fma(eps[i][j], eps[i][j], ee);
-                }
-#pragma unroll
-            for (int i = 0; i < D; ++i) tr += eps[i][i];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) P[i][j] = eps[i][j] * 2.0 * mu + (i == j ? lambda * tr : 0.0);
-            psi = mu * ee + 0.5 * lambda * (tr * tr);
-        } else if constexpr (OP == FH_NEO_HOOKEAN) {
-            const double Jd = det_small<D>(F);
-            if (Jd <= 0.0) {
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) P[i][j] = __builtin_nan("");
-            } else {
-                double Fi[D][D];
-                inv_small(F, Jd, Fi);
-                const double c = -mu + lambda * log(Jd);
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) P[i][j] = Fi[j][i] * c + F[i][j] * mu;
-            }
-            if constexpr (WHAT == EP_SCALAR) {
-                // materials.rs:249-262 with log_det_F of du_dX = (grad u)^T (logdet.rs:17-86)
-                double U[D][D];
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) U[i][j] = gu[j][i];
-                double gamma;
-                if constexpr (D == 2) {
-                    gamma = U[0][0] * U[1][1] + U[0][0] + U[1][1] - U[0][1] * U[1][0];
-                } else {
-                    const double u11 = U[0][0], u22 = U[1][1], u33 = U[2][2];
-                    const double aa = 1.0 + u11, e2 = 1.0 + u22, i2 = 1.0 + u33;
-                    const double b = U[0][1], c = U[0][2], d2 = U[1][0], f = U[1][2], g = U[2][0], h = U[2][1];
-                    gamma = u11 * u22 * u33 + u11 * u22 + u11 * u33 + u22 * u33 + u11 + u22 + u33 + b * f * g + c * d2 * h -
-                            c * e2 * g - b * d2 * i2 - aa * f * h;
-                }
-                if (gamma > -1.0) {
-                    const double logJ = log1p(gamma);
-                    double trU = 0.0, nn = 0.0;
-#pragma unroll
-                    for (int i = 0; i < D; ++i) {
-                        trU += U[i][i];
-#pragma unroll
-                        for (int j = 0; j < D; ++j) nn = fma(U[i][j], U[i][j], nn);
-                    }
-                    psi = mu * (trU + 0.5 * nn) - mu * logJ + (0.5 * lambda) * (logJ * logJ);
-                } else {
-                    psi = __builtin_inf();
-                }
-            }
-        } else {  // StVK: P = F E 2 mu + F lambda tr E ; psi = mu E:E + lambda/2 tr^2
-            double Eg[D][D];
-            double trE = 0.0, ee = 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(F[k][i], F[k][j], t);
-                    Eg[i][j] = (t - (i == j ? 1.0 : 0.0)) * 0.5;
-                    ee = fma(Eg[i][j], Eg[i][j], ee);
-                }
-#pragma unroll
-            for (int i = 0; i < D; ++i) trE += Eg[i][i];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(F[i][k], Eg[k][j], t);
-                    P[i][j] = t * 2.0 * mu + F[i][j] * lambda * trE;
-                }
-            psi = mu * ee + 0.5 * lambda * (trE * trE);
-        }
-    }
-}
 
 // sum of v over the workgroup (256 threads) in a fixed tree: lanes by xor-shuffles, wavefronts in index order
 __device__ __forceinline__ double block_sum_256(double v, double* lds4) {
@@ -344,16 +229,7 @@ __device__ __forceinline__ void element_pass_body_hex8(const KArgs& a, const lon
         if constexpr (need_j) {
 #pragma unroll
             for (int i = 0; i < D; ++i) grad(cx[i], xi, eta, zeta, ez, xz, xe, J[i]);   // J[i][j] = d x_i / d xi_j (hexahedron.rs:101-107)
-            const double detJ = det_small<D>(J);
-            if (detJ == 0.0) {  // try_inverse fails only for det == 0 exactly (elliptic.rs:401-404)
-                if (live) report_singular(a.status, e);
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) Ji[i][j] = 0.0;
-            } else {
-                inv_small(J, detJ, Ji);
-            }
+            const double detJ = inverse_or_zeros(J, Ji, [&] { if (live) report_singular(a.status, e); });
             adet = fabs(detJ);
         }
         double R[D][S];   // R[j][k] = d u_k / d xi_j = sum_n ghat_n u_n^T
@@ -370,25 +246,16 @@ __device__ __forceinline__ void element_pass_body_hex8(const KArgs& a, const lon
             s *= mt.beta;
         }
         double gu[D][S];                             // grad u = J^-T R
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                double t = 0.0;
-#pragma unroll
-                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], R[m][k], t);
-                gu[i][k] = t;
-            }
-        double mu = 0.0, lambda = 0.0;
-        if (OP != FH_LAPLACE) {
-            if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
-            else { mu = ep_const(a.qparams)[2 * q]; lambda = ep_const(a.qparams)[2 * q + 1]; }
-        }
+        pull_back<D, S>(Ji, R, gu);
+        double mu, lambda;
+        point_params<OP>(a, par_e, q, mu, lambda);
         double P[S][D], psi;
         material_point<OP, D, S, WHAT>(gu, mu, lambda, P, psi);
         if constexpr (WHAT == EP_SCALAR) {
             energy = fma(s, psi, energy);
         } else {
+            // (one row at a time, not push_forward(): with all of M formed ahead of the moment sums k_shifted_pass_tiled<LinearElastic> takes
+            // 172 instead of 168 VGPRs and loses a wave per SIMD, profiles/material_refactor_device_code.txt)
 #pragma unroll
             for (int i = 0; i < S; ++i) {
                 double Mi[D];   // (s P J^-T)[i][m]
@@ -413,16 +280,7 @@ __device__ __forceinline__ void element_pass_body_hex8(const KArgs& a, const lon
         // J = (c1, c2, c4) of the map, once (what point(0) forms: the mixed coefficients are zero here)
 #pragma unroll
         for (int i = 0; i < D; ++i) { J[i][0] = cx[i][1]; J[i][1] = cx[i][2]; J[i][2] = cx[i][4]; }
-        const double detJ = det_small<D>(J);
-        if (detJ == 0.0) {  // try_inverse fails only for det == 0 exactly (elliptic.rs:401-404)
-            if (live) report_singular(a.status, e);
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) Ji[i][j] = 0.0;
-        } else {
-            inv_small(J, detJ, Ji);
-        }
+        const double detJ = inverse_or_zeros(J, Ji, [&] { if (live) report_singular(a.status, e); });
         adet = fabs(detJ);
         const double mu = (OP != FH_LAPLACE) ? ep_const(a.qparams)[0] : 0.0, lambda = (OP != FH_LAPLACE) ? ep_const(a.qparams)[1] : 0.0;
         // L restricted: ROWS = which rows (reference directions) of the coefficient matrix are present (bit j: row j = r_j), COLS = which
@@ -601,49 +459,21 @@ __device__ __forceinline__ void element_pass_body(const KArgs& a, const long lon
                 for (int k = 0; k < S; ++k) R[j][k] = fma(g, U(n, k), R[j][k]);       // sum_n ghat_n u_n^T
             }
         if constexpr (need_j) {
-            const double detJ = det_small<D>(J);
-            if (detJ == 0.0) {  // try_inverse fails only for det == 0 exactly (elliptic.rs:401-404)
-                if (live) report_singular(a.status, e);
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) Ji[i][j] = 0.0;
-            } else {
-                inv_small(J, detJ, Ji);
-            }
+            const double detJ = inverse_or_zeros(J, Ji, [&] { if (live) report_singular(a.status, e); });
             adet = fabs(detJ);
         }
         const double s = ep_const(a.qw)[q] * adet;   // w |det J| (elliptic.rs:422)
         double gu[D][S];                          // grad u = J^-T R
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                double t = 0.0;
-#pragma unroll
-                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], R[m][k], t);
-                gu[i][k] = t;
-            }
-        double mu = 0.0, lambda = 0.0;
-        if (OP != FH_LAPLACE) {
-            if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
-            else { mu = ep_const(a.qparams)[2 * q]; lambda = ep_const(a.qparams)[2 * q + 1]; }
-        }
+        pull_back<D, S>(Ji, R, gu);
+        double mu, lambda;
+        point_params<OP>(a, par_e, q, mu, lambda);
         double P[S][D], psi;
         material_point<OP, D, S, WHAT>(gu, mu, lambda, P, psi);
         if constexpr (WHAT == EP_SCALAR) {
             energy = fma(s, psi, energy);
         } else {
             double M[S][D];   // s P J^-T
-#pragma unroll
-            for (int i = 0; i < S; ++i)
-#pragma unroll
-                for (int m = 0; m < D; ++m) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(P[i][k], Ji[m][k], t);
-                    M[i][m] = s * t;
-                }
+            push_forward<D, S>(s, P, Ji, M);
 #pragma unroll
             for (int n = 0; n < N; ++n)
 #pragma unroll
@@ -840,29 +670,21 @@ __device__ __forceinline__ void diagonal_element_body(const KArgs& a, const long
 #pragma unroll
                 for (int i = 0; i < D; ++i) J[i][j] = fma(X[n][i], g, J[i][j]);
             }
-        const double detJ = det_small<D>(J);
-        if (detJ == 0.0) {
+        const double detJ = det_small<D>(J);   // (not inverse_or_zeros(): a skipped point needs no zero inverse, and through it
+        if (detJ == 0.0) {                      // k_diagonal_tiled<Tet4, Laplace> loses a wave per SIMD, profiles/material_refactor_device_code.txt)
             if (live) report_singular(a.status, e);
             continue;
         }
         inv_small(J, detJ, Ji);
         const double s = ep_const(a.qw)[q] * fabs(detJ);
-        double mu = 0.0, lambda = 0.0;
-        if (OP != FH_LAPLACE) {
-            if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
-            else { mu = ep_const(a.qparams)[2 * q]; lambda = ep_const(a.qparams)[2 * q + 1]; }
-        }
+        double mu, lambda;
+        point_params<OP>(a, par_e, q, mu, lambda);
 #pragma unroll
         for (int n = 0; n < N; ++n) {
             double g[D], gg = 0.0;
+            physical_gradient<D>(Ji, G + n * D, g);
 #pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double t = 0.0;
-#pragma unroll
-                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], G[n * D + m], t);
-                g[i] = t;
-                gg = fma(t, t, gg);
-            }
+            for (int i = 0; i < D; ++i) gg = fma(g[i], g[i], gg);
             if constexpr (OP == FH_LAPLACE) {
                 f[n][0] = fma(s, gg, f[n][0]);
             } else {
@@ -873,140 +695,8 @@ __device__ __forceinline__ void diagonal_element_body(const KArgs& a, const long
     }
 }
 
-// ---- tangent of the residual, T(u) = dr/du at the context's u, applied without the matrix (engine_vector.hip).  Per point the element vector
-// of the operand x is  y_a += w |det J| dP(F)[H] g_a  with F = I + grad u^T, H = grad x^T (x enters linearly: I + grad x is never formed):
-//   Laplace        h
-//   LinearElastic  mu (H + H^T) + lambda tr(H) I
-//   NeoHookean     mu H + lambda tr(F^-1 H) F^-T + (mu - lambda ln J) F^-T H^T F^-T        (J <= 0: NaN, materials.rs:297-300)
-//   StVK           H S + F (lambda tr(dE) I + 2 mu dE),  S = lambda tr(E) I + 2 mu E,  dE = sym(F^T H)
-// which is  sum_b C(F; g_a, g_b) x_b  with C the stress contraction the assembled K(u) is made of (materials.rs:287-315 and 417-439).
-// TangentLin holds what depends on u alone (formed once per point); tangent_apply is linear in grad x.
-template <int OP, int D>
-struct TangentLin {
-    double mu, lambda, beta;   // NeoHookean: beta = mu - lambda ln J
-    double F[D][D];            // NeoHookean: F^-1; StVK: F
-    double Sg[D][D];           // StVK: the second Piola-Kirchhoff stress S
-};
-template <int OP, int D, int S>
-__device__ __forceinline__ void tangent_lin(const double (&gu)[D][S], double mu, double lambda, TangentLin<OP, D>& L) {
-    L.mu = mu;
-    L.lambda = lambda;
-    if constexpr (OP == FH_NEO_HOOKEAN || OP == FH_STVK) {
-        double F[D][D];   // F = I + (grad u)^T  (fenris-solid/src/lib.rs:20-29)
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + gu[j][i];
-        if constexpr (OP == FH_NEO_HOOKEAN) {
-            const double Jd = det_small<D>(F);
-            if (Jd <= 0.0) {
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) L.F[i][j] = __builtin_nan("");
-                L.beta = __builtin_nan("");
-            } else {
-                inv_small(F, Jd, L.F);
-                L.beta = mu - lambda * log(Jd);
-            }
-        } else {
-            double trE = 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(F[k][i], F[k][j], t);
-                    L.Sg[i][j] = (t - (i == j ? 1.0 : 0.0)) * 0.5;   // E (green_strain_tensor)
-                    L.F[i][j] = F[i][j];
-                }
-#pragma unroll
-            for (int i = 0; i < D; ++i) trE += L.Sg[i][i];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) L.Sg[i][j] = L.Sg[i][j] * 2.0 * mu + (i == j ? lambda * trE : 0.0);
-        }
-    }
-}
-// dP (s x d) from gx = grad x (d x s, gx[i][k] = d x_k / d X_i)
-template <int OP, int D, int S>
-__device__ __forceinline__ void tangent_apply(const TangentLin<OP, D>& L, const double (&gx)[D][S], double (&dP)[S][D]) {
-    if constexpr (OP == FH_LAPLACE) {
-#pragma unroll
-        for (int r = 0; r < D; ++r) dP[0][r] = gx[r][0];
-    } else if constexpr (OP == FH_LINEAR_ELASTIC) {
-        double tr = 0.0;
-#pragma unroll
-        for (int i = 0; i < D; ++i) tr += gx[i][i];
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) dP[i][j] = L.mu * (gx[j][i] + gx[i][j]) + (i == j ? L.lambda * tr : 0.0);
-    } else if constexpr (OP == FH_NEO_HOOKEAN) {
-        double A[D][D], tr = 0.0;   // A = F^-1 H
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                double t = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) t = fma(L.F[i][k], gx[j][k], t);
-                A[i][j] = t;
-            }
-#pragma unroll
-        for (int i = 0; i < D; ++i) tr += A[i][i];
-        const double lt = L.lambda * tr;
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                double b = 0.0;   // (F^-1 H F^-1)[j][i]
-#pragma unroll
-                for (int k = 0; k < D; ++k) b = fma(A[j][k], L.F[k][i], b);
-                dP[i][j] = fma(L.beta, b, fma(lt, L.F[j][i], L.mu * gx[j][i]));
-            }
-    } else {   // StVK
-        double C[D][D];   // F^T H
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                double t = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) t = fma(L.F[k][i], gx[j][k], t);
-                C[i][j] = t;
-            }
-        double tr = 0.0;
-#pragma unroll
-        for (int i = 0; i < D; ++i) tr += C[i][i];
-        double T[D][D];   // lambda tr(dE) I + 2 mu dE
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) T[i][j] = L.mu * (C[i][j] + C[j][i]) + (i == j ? L.lambda * tr : 0.0);
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                double t = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) t = fma(gx[k][i], L.Sg[k][j], fma(L.F[i][k], T[k][j], t));
-                dP[i][j] = t;
-            }
-    }
-}
-template <int OP, int D, int S>
-__device__ __forceinline__ void tangent_params(const KArgs& a, const double* par_e, int q, double& mu, double& lambda) {
-    mu = 0.0;
-    lambda = 0.0;
-    if (OP != FH_LAPLACE) {
-        if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
-        else { mu = ep_const(a.qparams)[2 * q]; lambda = ep_const(a.qparams)[2 * q + 1]; }
-    }
-}
-
+// ---- tangent of the residual, T(u) = dr/du at the context's u, applied without the matrix (engine_vector.hip): tangent_lin / tangent_apply
+// of material.hpp per point.
 // the tangent's element vector of one small iso-parametric element in the registers of one thread: vertex coordinates X, u (U) and the
 // operand (V) of its nodes; J per point from the reference-gradient table (the generic body's sums, elliptic.rs:398-422).  det J == 0 is
 // reported like the residual reports it and adds nothing.
@@ -1042,39 +732,23 @@ __device__ __forceinline__ void tangent_element_body(const KArgs& a, const long 
                     Rv[j][k] = fma(g, V[n][k], Rv[j][k]);
                 }
             }
-        const double detJ = det_small<D>(J);
-        if (detJ == 0.0) {
+        const double detJ = det_small<D>(J);   // (not inverse_or_zeros(): a skipped point needs no zero inverse, and through it
+        if (detJ == 0.0) {                      // k_diagonal_tiled<Tet4, Laplace> loses a wave per SIMD, profiles/material_refactor_device_code.txt)
             if (live) report_singular(a.status, e);
             continue;
         }
         inv_small(J, detJ, Ji);
         const double s = ep_const(a.qw)[q] * fabs(detJ);
         double gu[D][S], gx[D][S];
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                double t = 0.0, t2 = 0.0;
-#pragma unroll
-                for (int m = 0; m < D; ++m) { t = fma(Ji[m][i], Ru[m][k], t); t2 = fma(Ji[m][i], Rv[m][k], t2); }
-                gu[i][k] = t;
-                gx[i][k] = t2;
-            }
+        pull_back<D, S>(Ji, Ru, gu);
+        pull_back<D, S>(Ji, Rv, gx);
         double mu, lambda;
-        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        point_params<OP>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
         tangent_lin<OP, D, S>(gu, mu, lambda, L);
         double dP[S][D], M[S][D];   // M = s dP J^-T
         tangent_apply<OP, D, S>(L, gx, dP);
-#pragma unroll
-        for (int i = 0; i < S; ++i)
-#pragma unroll
-            for (int m = 0; m < D; ++m) {
-                double t = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) t = fma(dP[i][k], Ji[m][k], t);
-                M[i][m] = s * t;
-            }
+        push_forward<D, S>(s, dP, Ji, M);
 #pragma unroll
         for (int n = 0; n < N; ++n)
 #pragma unroll
@@ -1151,6 +825,8 @@ __device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long lon
         if constexpr (need_j) {
 #pragma unroll
             for (int i = 0; i < D; ++i) grad(cx[i], xi, eta, zeta, ez, xz, xe, J[i]);
+            // (this body keeps its point geometry written out: through inverse_or_zeros / pull_back / push_forward the PCG iteration of
+            // the Hex8 StVK tangent measured 1 % above the parent's, more than the spread of the runs: profiles/material_refactor.txt)
             const double detJ = det_small<D>(J);
             if (detJ == 0.0) {
                 if (live) report_singular(a.status, e);
@@ -1191,7 +867,7 @@ __device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long lon
             s *= mt.beta;
         }
         double mu, lambda;
-        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        point_params<OP>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
         tangent_lin<OP, D, S>(gu, mu, lambda, L);
         double dP[S][D];
@@ -1274,37 +950,23 @@ __device__ __forceinline__ void tangent_diagonal_body(const KArgs& a, const long
 #pragma unroll
                 for (int k = 0; k < S; ++k) Ru[j][k] = fma(g, U[n][k], Ru[j][k]);
             }
-        const double detJ = det_small<D>(J);
-        if (detJ == 0.0) {
+        const double detJ = det_small<D>(J);   // (not inverse_or_zeros(): a skipped point needs no zero inverse, and through it
+        if (detJ == 0.0) {                      // k_diagonal_tiled<Tet4, Laplace> loses a wave per SIMD, profiles/material_refactor_device_code.txt)
             if (live) report_singular(a.status, e);
             continue;
         }
         inv_small(J, detJ, Ji);
         const double s = ep_const(a.qw)[q] * fabs(detJ);
         double gu[D][S];
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                double t = 0.0;
-#pragma unroll
-                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], Ru[m][k], t);
-                gu[i][k] = t;
-            }
+        pull_back<D, S>(Ji, Ru, gu);
         double mu, lambda;
-        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        point_params<OP>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
         tangent_lin<OP, D, S>(gu, mu, lambda, L);
 #pragma unroll
         for (int n = 0; n < N; ++n) {
             double g[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) {
-                double t = 0.0;
-#pragma unroll
-                for (int m = 0; m < D; ++m) t = fma(Ji[m][i], G[n * D + m], t);
-                g[i] = t;
-            }
+            physical_gradient<D>(Ji, G + n * D, g);
 #pragma unroll
             for (int c = 0; c < S; ++c) {
                 double gx[D][S], dP[S][D];

@@ -179,7 +179,7 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
             if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
             a.ke_out = c->fe_scratch.p;
         }
-        const int rs = dispatch(all_kinds, c->elem_kind, all_ops, c->op, -1, [&](auto ek, auto op) { return launch_vector_stream<ek(), op()>(c, a); });
+        const int rs = dispatch(all_kinds, c->elem_kind, elliptic_ops, c->op, -1, [&](auto ek, auto op) { return launch_vector_stream<ek(), op()>(c, a); });
         if (rs == FH_OK && two_pass) {
             rc = launch_vector_from_elements(c, c->S(), out_dev);
             if (rc) return rc;
@@ -197,7 +197,7 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
     const size_t lds = layout_bytes_dyn(c->elem_kind, c->op, WHAT_VECTOR, c->nq, a.ub, 0, 0, false);
     if (lds > LDS_LIMIT) return c->fail(FH_UNSUPPORTED, "quadrature rule too large for LDS staging");
     const int grid = (int)((a.work_end + a.epb - 1) / a.epb);
-    rc = dispatch(all_kinds, c->elem_kind, all_ops, c->op, (int)FH_OK, [&](auto ek, auto op) { return launch_vector<ek(), op()>(c, a, lds, grid); });
+    rc = dispatch(all_kinds, c->elem_kind, elliptic_ops, c->op, (int)FH_OK, [&](auto ek, auto op) { return launch_vector<ek(), op()>(c, a, lds, grid); });
     if (rc) return rc;
     return read_status(c, failed);
 }
@@ -472,7 +472,7 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
     HIP_TRY(c, partial.alloc((size_t)grid));
     a.scalar_out = partial.p;
     c->last_kernel = "k_assemble_scalar";
-    rc = dispatch(all_kinds, c->elem_kind, all_ops, c->op, (int)FH_OK, [&](auto ek, auto op) { return launch_scalar<ek(), op()>(c, a, lds, grid); });
+    rc = dispatch(all_kinds, c->elem_kind, elliptic_ops, c->op, (int)FH_OK, [&](auto ek, auto op) { return launch_scalar<ek(), op()>(c, a, lds, grid); });
     if (rc) return rc;
     std::vector<double> h((size_t)grid);
     HIP_TRY(c, hipMemcpyAsync(h.data(), partial.p, sizeof(double) * grid, hipMemcpyDeviceToHost, c->stream));
@@ -491,7 +491,7 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
 // its diagonal, without a pattern or values.  For FH_LAPLACE and FH_LINEAR_ELASTIC the element vector is linear in u, so T(u) is the
 // operator A of LinearOperator::apply (fenris-sparse/src/cg.rs:16-18) for every u, and the residual of the operand IS  A x:  the element pass
 // of the residual, fed x in place of the context's u.  For FH_NEO_HOOKEAN and FH_STVK the element pass gathers u and the operand per
-// element and forms dP(F)[grad x^T] per point (tangent_lin / tangent_apply, element_pass.hpp).  On the tiles (Hex8, Tet4, Quad4, Tri3
+// element and forms dP(F)[grad x^T] per point (tangent_lin / tangent_apply, material.hpp).  On the tiles (Hex8, Tet4, Quad4, Tri3
 // without a rule-set table) the node pass overwrites y, applies the Dirichlet rows on store and leaves the partials of x . y for CG;
 // otherwise every group of a rule-set table takes the tiles where they cover it, else the per-element kernels, all accumulating into a
 // zeroed y, and one more pass over y does the same.  Homogeneous Dirichlet nodes make the map the one fh_apply_dirichlet_csr_dev leaves

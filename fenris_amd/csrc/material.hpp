@@ -1,0 +1,268 @@
+// The material laws of the elliptic operators, written once: stress and energy density of a quadrature point (material_point), the
+// tangent of the stress (tangent_lin / tangent_apply) and the point's Lame parameters (point_params).  Every element kernel that needs a
+// stress calls these: the register-resident element pass and the tiles (element_pass.hpp, vector_tiles.hip), the LDS-staged vector and
+// scalar kernels (prologue() of assemble_kernels.hpp), the matrix-free kernels of solver_kernels.hpp and recovery (recover_kernels.hpp).
+// (The coefficients of the assembled matrices -- the matrix branch of prologue(), hex27_blocks.hpp -- are not stresses and stay there.)
+// Only __device__ __forceinline__ functions: safe to include from several translation units.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "device_common.hpp"
+#include "small_ops.hpp"
+
+namespace fenris_hip {
+
+enum { EP_VECTOR = 0, EP_SCALAR = 1 };
+
+// F = I + (grad u)^T from gu[i][k] = d u_k / d X_i  (fenris-solid/src/lib.rs:20-29)
+template <int D, int S>
+__device__ __forceinline__ void deformation_gradient(const double (&gu)[D][S], double (&F)[D][D]) {
+    static_assert(S == D, "a deformation gradient needs a vector field");
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + gu[j][i];
+}
+// Green strain E = (F^T F - I) / 2  (green_strain_tensor)
+template <int D>
+__device__ __forceinline__ void green_strain(const double (&F)[D][D], double (&E)[D][D]) {
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) t = fma(F[k][i], F[k][j], t);
+            E[i][j] = (t - (i == j ? 1.0 : 0.0)) * 0.5;
+        }
+}
+
+// stress P (s x d) and energy density psi of one quadrature point from grad u (d x s):
+// laplace.rs:26-73; fenris-solid/src/materials.rs:71-123 (LinearElastic), 236-353 (NeoHookean, J <= 0 => NaN block / inf),
+// 392-469 (StVK).
+template <int OP, int D, int S, int WHAT>
+__device__ __forceinline__ void material_point(const double (&gu)[D][S], double mu, double lambda, double (&P)[S][D], double& psi) {
+    psi = 0.0;
+    if constexpr (OP == FH_LAPLACE) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) { P[0][k] = gu[k][0]; psi = fma(gu[k][0], gu[k][0], psi); }
+        psi *= 0.5;
+    } else {
+        double F[D][D];
+        deformation_gradient<D, S>(gu, F);
+        if constexpr (OP == FH_LINEAR_ELASTIC) {
+            double eps[D][D];
+            double tr = 0.0, ee = 0.0;
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) {
+                    eps[i][j] = (F[j][i] + F[i][j]) * 0.5 - (i == j ? 1.0 : 0.0);
+                    ee = fma(eps[i][j], eps[i][j], ee);
+                }
+#pragma unroll
+            for (int i = 0; i < D; ++i) tr += eps[i][i];
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) P[i][j] = eps[i][j] * 2.0 * mu + (i == j ? lambda * tr : 0.0);
+            psi = mu * ee + 0.5 * lambda * (tr * tr);
+        } else if constexpr (OP == FH_NEO_HOOKEAN) {
+            const double Jd = det_small<D>(F);
+            if (Jd <= 0.0) {
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j < D; ++j) P[i][j] = __builtin_nan("");
+            } else {
+                double Fi[D][D];
+                inv_small(F, Jd, Fi);
+                const double c = -mu + lambda * log(Jd);
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j < D; ++j) P[i][j] = Fi[j][i] * c + F[i][j] * mu;
+            }
+            if constexpr (WHAT == EP_SCALAR) {
+                // materials.rs:249-262 with log_det_F of du_dX = (grad u)^T (logdet.rs:17-86)
+                double U[D][D];
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j < D; ++j) U[i][j] = gu[j][i];
+                double gamma;
+                if constexpr (D == 2) {
+                    gamma = U[0][0] * U[1][1] + U[0][0] + U[1][1] - U[0][1] * U[1][0];
+                } else {
+                    const double u11 = U[0][0], u22 = U[1][1], u33 = U[2][2];
+                    const double aa = 1.0 + u11, e2 = 1.0 + u22, i2 = 1.0 + u33;
+                    const double b = U[0][1], c = U[0][2], d2 = U[1][0], f = U[1][2], g = U[2][0], h = U[2][1];
+                    gamma = u11 * u22 * u33 + u11 * u22 + u11 * u33 + u22 * u33 + u11 + u22 + u33 + b * f * g + c * d2 * h -
+                            c * e2 * g - b * d2 * i2 - aa * f * h;
+                }
+                if (gamma > -1.0) {
+                    const double logJ = log1p(gamma);
+                    double trU = 0.0, nn = 0.0;
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        trU += U[i][i];
+#pragma unroll
+                        for (int j = 0; j < D; ++j) nn = fma(U[i][j], U[i][j], nn);
+                    }
+                    psi = mu * (trU + 0.5 * nn) - mu * logJ + (0.5 * lambda) * (logJ * logJ);
+                } else {
+                    psi = __builtin_inf();
+                }
+            }
+        } else {  // StVK: P = F E 2 mu + F lambda tr E ; psi = mu E:E + lambda/2 tr^2
+            double Eg[D][D];
+            double trE = 0.0, ee = 0.0;
+            green_strain<D>(F, Eg);
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) ee = fma(Eg[i][j], Eg[i][j], ee);
+#pragma unroll
+            for (int i = 0; i < D; ++i) trE += Eg[i][i];
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) t = fma(F[i][k], Eg[k][j], t);
+                    P[i][j] = t * 2.0 * mu + F[i][j] * lambda * trE;
+                }
+            psi = mu * ee + 0.5 * lambda * (trE * trE);
+        }
+    }
+}
+
+// ---- tangent of the stress: T(u) = dr/du at the context's u is applied without the matrix (engine_vector.hip).  Per point the element vector
+// of the operand x is  y_a += w |det J| dP(F)[H] g_a  with F = I + grad u^T, H = grad x^T (x enters linearly: I + grad x is never formed):
+//   Laplace        h
+//   LinearElastic  mu (H + H^T) + lambda tr(H) I
+//   NeoHookean     mu H + lambda tr(F^-1 H) F^-T + (mu - lambda ln J) F^-T H^T F^-T        (J <= 0: NaN, materials.rs:297-300)
+//   StVK           H S + F (lambda tr(dE) I + 2 mu dE),  S = lambda tr(E) I + 2 mu E,  dE = sym(F^T H)
+// which is  sum_b C(F; g_a, g_b) x_b  with C the stress contraction the assembled K(u) is made of (materials.rs:287-315 and 417-439).
+// TangentLin holds what depends on u alone (formed once per point); tangent_apply is linear in grad x.
+template <int OP, int D>
+struct TangentLin {
+    double mu, lambda, beta;   // NeoHookean: beta = mu - lambda ln J
+    double F[D][D];            // NeoHookean: F^-1; StVK: F
+    double Sg[D][D];           // StVK: the second Piola-Kirchhoff stress S
+};
+template <int OP, int D, int S>
+__device__ __forceinline__ void tangent_lin(const double (&gu)[D][S], double mu, double lambda, TangentLin<OP, D>& L) {
+    L.mu = mu;
+    L.lambda = lambda;
+    if constexpr (OP == FH_NEO_HOOKEAN || OP == FH_STVK) {
+        double F[D][D];
+        deformation_gradient<D, S>(gu, F);
+        if constexpr (OP == FH_NEO_HOOKEAN) {
+            const double Jd = det_small<D>(F);
+            if (Jd <= 0.0) {
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j < D; ++j) L.F[i][j] = __builtin_nan("");
+                L.beta = __builtin_nan("");
+            } else {
+                inv_small(F, Jd, L.F);
+                L.beta = mu - lambda * log(Jd);
+            }
+        } else {
+            double trE = 0.0;
+            green_strain<D>(F, L.Sg);   // E, overwritten by S below
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) L.F[i][j] = F[i][j];
+#pragma unroll
+            for (int i = 0; i < D; ++i) trE += L.Sg[i][i];
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int j = 0; j < D; ++j) L.Sg[i][j] = L.Sg[i][j] * 2.0 * mu + (i == j ? lambda * trE : 0.0);
+        }
+    }
+}
+// dP (s x d) from gx = grad x (d x s, gx[i][k] = d x_k / d X_i)
+template <int OP, int D, int S>
+__device__ __forceinline__ void tangent_apply(const TangentLin<OP, D>& L, const double (&gx)[D][S], double (&dP)[S][D]) {
+    if constexpr (OP == FH_LAPLACE) {
+#pragma unroll
+        for (int r = 0; r < D; ++r) dP[0][r] = gx[r][0];
+    } else if constexpr (OP == FH_LINEAR_ELASTIC) {
+        double tr = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) tr += gx[i][i];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) dP[i][j] = L.mu * (gx[j][i] + gx[i][j]) + (i == j ? L.lambda * tr : 0.0);
+    } else if constexpr (OP == FH_NEO_HOOKEAN) {
+        double A[D][D], tr = 0.0;   // A = F^-1 H
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) t = fma(L.F[i][k], gx[j][k], t);
+                A[i][j] = t;
+            }
+#pragma unroll
+        for (int i = 0; i < D; ++i) tr += A[i][i];
+        const double lt = L.lambda * tr;
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double b = 0.0;   // (F^-1 H F^-1)[j][i]
+#pragma unroll
+                for (int k = 0; k < D; ++k) b = fma(A[j][k], L.F[k][i], b);
+                dP[i][j] = fma(L.beta, b, fma(lt, L.F[j][i], L.mu * gx[j][i]));
+            }
+    } else {   // StVK
+        double C[D][D];   // F^T H
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) t = fma(L.F[k][i], gx[j][k], t);
+                C[i][j] = t;
+            }
+        double tr = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) tr += C[i][i];
+        double T[D][D];   // lambda tr(dE) I + 2 mu dE
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) T[i][j] = L.mu * (C[i][j] + C[j][i]) + (i == j ? L.lambda * tr : 0.0);
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) t = fma(gx[k][i], L.Sg[k][j], fma(L.F[i][k], T[k][j], t));
+                dP[i][j] = t;
+            }
+    }
+}
+// the Lame parameters of point q: the element's own (par_e: its row of a compact table, KArgs::rparams) or the uniform table's, by scalar loads
+template <int OP>
+__device__ __forceinline__ void point_params(const KArgs& a, const double* par_e, int q, double& mu, double& lambda) {
+    mu = 0.0;
+    lambda = 0.0;
+    if (OP != FH_LAPLACE) {
+        if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
+        else { mu = ep_const(a.qparams)[2 * q]; lambda = ep_const(a.qparams)[2 * q + 1]; }
+    }
+}
+
+}  // namespace fenris_hip

@@ -1,7 +1,8 @@
 // Recovery of the quantities a user reads off a solved field (engine_recover.hip): displacement gradient, strain, operator (first
 // Piola-Kirchhoff) stress, Cauchy stress, von Mises stress, energy density and element measure -- per (element, quadrature point), as the
 // measure-weighted element mean, and as the volume-weighted patch average at the nodes.  A pure per-point map on what the residual's
-// element pass already forms (grad u = J^-T sum_n ghat_n u_n^T, element_pass.hpp) followed by material_point, so nothing leaves the device.
+// element pass already forms (grad u = J^-T sum_n ghat_n u_n^T, element_pass.hpp) followed by material_point (material.hpp), so nothing leaves
+// the device.
 //
 //  * k_recover_elements<EK, OP, QUANTITY, FH_AT_ELEMENTS>, the four iso-parametric kinds: ONE THREAD PER ELEMENT in the register-resident
 //    form of element_pass.hpp -- vertex coordinates and u of the element in registers, the tables through scalar loads (ep_const), J, its
@@ -18,6 +19,7 @@
 
 #include "device_common.hpp"
 #include "element_pass.hpp"
+#include "material.hpp"
 #include "small_ops.hpp"
 
 namespace fenris_hip {
@@ -63,20 +65,13 @@ __device__ __forceinline__ void recover_values(const double (&gu)[D][S], double 
 #pragma unroll
                 for (int j = 0; j < D; ++j) v[i * D + j] = 0.5 * (gu[i][j] + gu[j][i]);
         } else {   // Green-Lagrange (F^T F - I) / 2 with F = I + (grad u)^T  (fenris-solid/src/lib.rs:20-29)
-            double F[D][D];
+            double F[D][D], E[D][D];
+            deformation_gradient<D, S>(gu, F);
+            green_strain<D>(F, E);
 #pragma unroll
             for (int i = 0; i < D; ++i)
 #pragma unroll
-                for (int j = 0; j < D; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + gu[j][i];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) t = fma(F[k][i], F[k][j], t);
-                    v[i * D + j] = (t - (i == j ? 1.0 : 0.0)) * 0.5;
-                }
+                for (int j = 0; j < D; ++j) v[i * D + j] = E[i][j];
         }
     } else if constexpr (Q == FH_RECOVER_ENERGY_DENSITY) {
         double P[S][D], psi;
@@ -99,10 +94,7 @@ __device__ __forceinline__ void recover_values(const double (&gu)[D][S], double 
                     for (int j = 0; j < D; ++j) sg[i][j] = P[i][j];
             } else {
                 double F[D][D];
-#pragma unroll
-                for (int i = 0; i < D; ++i)
-#pragma unroll
-                    for (int j = 0; j < D; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + gu[j][i];
+                deformation_gradient<D, S>(gu, F);
                 const double Jd = det_small<D>(F);
                 const double rj = Jd <= 0.0 ? __builtin_nan("") : 1.0 / Jd;
 #pragma unroll
@@ -143,25 +135,8 @@ template <int D, int S>
 __device__ __forceinline__ double recover_grad_u(const KArgs& a, const long long e, const double (&J)[D][D], const double (&R)[D][S],
                                                  double (&gu)[D][S]) {
     double Ji[D][D];
-    const double detJ = det_small<D>(J);
-    if (detJ == 0.0) {
-        report_singular(a.status, e);
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) Ji[i][j] = 0.0;
-    } else {
-        inv_small(J, detJ, Ji);
-    }
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-            double t = 0.0;
-#pragma unroll
-            for (int m = 0; m < D; ++m) t = fma(Ji[m][i], R[m][k], t);
-            gu[i][k] = t;
-        }
+    const double detJ = inverse_or_zeros(J, Ji, [&] { report_singular(a.status, e); });
+    pull_back<D, S>(Ji, R, gu);
     return fabs(detJ);
 }
 
@@ -226,11 +201,8 @@ __global__ void __launch_bounds__(256) k_recover_elements(const KArgs a, const R
             const double s = ep_const(a.qw)[q] * recover_grad_u<D, S>(a, e, J, R, gu);   // w |det J|
             vol += s;
             if constexpr (FIELD) {
-                double mu = 0.0, lambda = 0.0;
-                if (OP != FH_LAPLACE) {
-                    if (par_e) { mu = par_e[2 * q]; lambda = par_e[2 * q + 1]; }
-                    else { mu = ep_const(a.qparams)[2 * q]; lambda = ep_const(a.qparams)[2 * q + 1]; }
-                }
+                double mu, lambda;
+                point_params<OP>(a, par_e, q, mu, lambda);
                 double v[NC];
                 recover_values<OP, D, S, Q>(gu, mu, lambda, v);
 #pragma unroll

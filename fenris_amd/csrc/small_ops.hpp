@@ -47,6 +47,62 @@ __device__ __forceinline__ void adj_scaled(const double (&m)[3][3], double r, do
     o[2][2] = (m[0][0] * m[1][1] - m[1][0] * m[0][1]) * r;
 }
 
+// ------------------------------------------------------------------------------------------ point geometry
+// What the one-thread-per-element bodies do at a quadrature point with the Jacobian J of the map, its inverse Ji and s = w |det J|.
+// Ji = J^-1 by cofactors, or zeros when det J == 0 exactly (try_inverse fails only then, elliptic.rs:401-404), after on_singular() has
+// reported the element; returns det J
+template <int D, class OnSingular>
+__device__ __forceinline__ double inverse_or_zeros(const double (&J)[D][D], double (&Ji)[D][D], OnSingular&& on_singular) {
+    const double det = det_small<D>(J);
+    if (det == 0.0) {
+        on_singular();
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) Ji[i][j] = 0.0;
+    } else {
+        inv_small(J, det, Ji);
+    }
+    return det;
+}
+// grad u = J^-T R from the reference gradient R[j][k] = d u_k / d xi_j = sum_n ghat_n u_n^T
+template <int D, int S>
+__device__ __forceinline__ void pull_back(const double (&Ji)[D][D], const double (&R)[D][S], double (&gu)[D][S]) {
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+            double t = 0.0;
+#pragma unroll
+            for (int m = 0; m < D; ++m) t = fma(Ji[m][i], R[m][k], t);
+            gu[i][k] = t;
+        }
+}
+// M = s P J^-T, the matrix the element vector is made of: f_n += M ghat_n (P: a stress or its tangent dP, s x d)
+template <int D, int S>
+__device__ __forceinline__ void push_forward(double s, const double (&P)[S][D], const double (&Ji)[D][D], double (&M)[S][D]) {
+#pragma unroll
+    for (int i = 0; i < S; ++i)
+#pragma unroll
+        for (int m = 0; m < D; ++m) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) t = fma(P[i][k], Ji[m][k], t);
+            M[i][m] = s * t;
+        }
+}
+// g = J^-T ghat, the physical gradient of a basis function from its reference gradient (ghat: any pointer to D doubles)
+template <int D, class Ptr>
+__device__ __forceinline__ void physical_gradient(const double (&Ji)[D][D], Ptr ghat, double (&g)[D]) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double t = 0.0;
+#pragma unroll
+        for (int m = 0; m < D; ++m) t = fma(Ji[m][i], ghat[m], t);
+        g[i] = t;
+    }
+}
+
 // explicit LDS fetch of one double (ds_read_b64).  The generic address of an LDS object carries the LDS byte
 // offset in its low 32 bits.  Callers must call lds_wait_all() before using the values.
 template <int OFF_BYTES>

@@ -9,6 +9,7 @@
 #include "assemble_kernels.hpp"
 #include "device_common.hpp"
 #include "element_pass.hpp"
+#include "material.hpp"
 
 namespace fenris_hip {
 
@@ -384,18 +385,11 @@ __device__ __forceinline__ bool mf_point(const KArgs& a, const int* nodes, int N
 // ... and g_n = J^-T ghat_n, the physical gradient of basis function n there
 template <int D>
 __device__ __forceinline__ void mf_grad(const KArgs& a, int N, int q, int n, const double (&Ji)[D][D], double (&g)[D]) {
-    const double* gr = a.gref + ((size_t)q * N + n) * D;
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-        double t = 0.0;
-#pragma unroll
-        for (int c = 0; c < D; ++c) t = fma(Ji[c][r], gr[c], t);
-        g[r] = t;
-    }
+    physical_gradient<D>(Ji, a.gref + ((size_t)q * N + n) * D, g);
 }
 
 // y = T(u) x (= A x for FH_LAPLACE and FH_LINEAR_ELASTIC) for any element kind, deterministic: grad x = J^-T sum_n ghat_n x_n^T per point (and
-// grad u from a.u, may be null: zero, for the nonlinear operators only), dP(F)[grad x^T] by tangent_lin / tangent_apply (element_pass.hpp;
+// grad u from a.u, may be null: zero, for the nonlinear operators only), dP(F)[grad x^T] by tangent_lin / tangent_apply (material.hpp;
 // for the linear operators the stress of material_point without F), element vectors f_n = w |det J| dP g_n by local node.  Inactive elements
 // write zeros.
 template <int D, int S, int OP>
@@ -437,7 +431,7 @@ __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N,
             }
         }
         double mu, lambda;
-        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        point_params<OP>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
         tangent_lin<OP, D, S>(gu, mu, lambda, L);
         double dP[S][D];
@@ -458,7 +452,7 @@ __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N,
 }
 
 // the residual r(u) of any element kind without atomics (the Newton residual off the tiles, engine_vector.hip): per point grad u = J^-T
-// sum_n ghat_n u_n^T (a.u, may be null: zero), the stress P of material_point, element vectors f_n = w |det J| P g_n by local node into
+// sum_n ghat_n u_n^T (a.u, may be null: zero), the stress P of material_point (material.hpp), element vectors f_n = w |det J| P g_n by local node into
 // fe[a][e][c] for the ordered node sums of k_vector_from_elements_soa.  Inactive elements write zeros; det J == 0 is reported like the residual.
 template <int D, int S, int OP>
 __global__ void __launch_bounds__(256) k_residual_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
@@ -495,7 +489,7 @@ __global__ void __launch_bounds__(256) k_residual_elements(const KArgs a, int N,
                 }
             }
         double mu, lambda;
-        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        point_params<OP>(a, par_e, q, mu, lambda);
         double P[S][D], psi;
         material_point<OP, D, S, EP_VECTOR>(gu, mu, lambda, P, psi);
         for (int n = 0; n < N; ++n) {
@@ -552,7 +546,7 @@ __global__ void __launch_bounds__(256) k_mf_diagonal_elements(const KArgs a, int
             }
         }
         double mu, lambda;
-        tangent_params<OP, D, S>(a, par_e, q, mu, lambda);
+        point_params<OP>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
         tangent_lin<OP, D, S>(gu, mu, lambda, L);
         for (int n = 0; n < N; ++n) {

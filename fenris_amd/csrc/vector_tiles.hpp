@@ -53,7 +53,7 @@ hipError_t vector_tiles_node_pass(hipStream_t stream, int S, int num_nodes, cons
                                   const double* scaled_g = nullptr);
 
 // diagonal of the matrix-free map (FH_LAPLACE, FH_LINEAR_ELASTIC: diagonal_element_body; FH_NEO_HOOKEAN, FH_STVK: tangent_diagonal_body at
-// a.u) over the tiles into partial[P][S]; the caller sums them with vector_tiles_node_pass.  Returns -1 when (elem_kind, op) is not covered.
+// a.u; both element_pass.hpp, the material law material.hpp) over the tiles into partial[P][S]; the caller sums them with vector_tiles_node_pass.  Returns -1 when (elem_kind, op) is not covered.
 int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial);
 
 // tangent of the residual of FH_NEO_HOOKEAN and FH_STVK at a.u applied to x (k_tangent_tiled) over the tiles into partial[P][S] (the linear

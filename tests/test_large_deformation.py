@@ -319,9 +319,12 @@ def _shifted_route(engine, asm, kind, ref, x, tag):
 
 
 def _vector_routes(engine, asm, kind, ref, case, tag):
-    """the residual and the energy on every route of the kind: the tiles, and for Hex8 / Tet4 also the element pass without them"""
+    """the residual and the energy on every route of the kind: the LDS-staged kernels, the tiles, and for Hex8 / Tet4 also the element pass
+    without them"""
     if kind in TILED_KINDS:
-        routes = [(None, "k_element_pass_tiled + k_vector_from_partials", "k_element_energy_tiled")]
+        staged = "k_assemble_vector" if kind == "TRI3" else "k_assemble_vector_stream + k_vector_from_elements"
+        routes = [("FENRIS_HIP_NO_ELEMENT_PASS", staged, "k_assemble_scalar"),
+                  (None, "k_element_pass_tiled + k_vector_from_partials", "k_element_energy_tiled")]
         if kind in ("HEX8", "TET4"):
             routes.append(("FENRIS_HIP_NO_VECTOR_TILES", "k_element_pass + k_vector_from_elements_soa", "k_element_pass<scalar>"))
     else:

@@ -1,4 +1,4 @@
-"""Residual and energy (element pass, element_pass.hpp) against the oracle on awkward inputs: long rules, inverted elements (negative
+"""Residual and energy (element pass, element_pass.hpp, and the LDS-staged kernels of assemble_kernels.hpp) against the oracle on awkward inputs: long rules, inverted elements (negative
 det J), affine and distorted elements mixed inside one wavefront, large displacements (NeoHookean with det F <= 0 somewhere: the NaN
 entries must be the oracle's)."""
 import numpy as np
@@ -64,16 +64,26 @@ def test_vector_and_energy_on_awkward_inputs(engine, oracle):
                     st, _, of = oracle.assemble_vector(ref)
                     st2, _, oe = oracle.assemble_scalar(ref)
                     assert st == 0 and st2 == 0
-                    f = fa.VectorAssembler().assemble_vector(asm)
-                    e = fa.assemble_scalar(asm)
-                    where = (name, len(w), opname, scale, engine.last_kernel_name())
-                    assert np.array_equal(np.isnan(f), np.isnan(of)), where
-                    ok = ~np.isnan(of)
-                    if ok.any():
-                        assert np.abs(f[ok] - of[ok]).max() <= 1e-11 * max(np.abs(of[ok]).max(), 1e-300), where
-                    if np.isfinite(oe):
-                        assert abs(e - oe) <= 1e-11 * max(abs(oe), 1e-300), where
-                    else:
-                        assert np.isnan(e) == np.isnan(oe), where
+                    for option in (None, "FENRIS_HIP_NO_ELEMENT_PASS"):   # the default route, then the LDS-staged kernels on the same u
+                        if option:
+                            engine.set_option(option, 1)
+                        try:
+                            f = fa.VectorAssembler().assemble_vector(asm)
+                            vname = engine.last_kernel_name()
+                            e = fa.assemble_scalar(asm)
+                            where = (name, len(w), opname, scale, vname, engine.last_kernel_name())
+                        finally:
+                            if option:
+                                engine.set_option(option, None)
+                        assert vname.startswith("k_assemble_vector") == bool(option), where
+                        assert (where[-1] == "k_assemble_scalar") == bool(option), where
+                        assert np.array_equal(np.isnan(f), np.isnan(of)), where
+                        ok = ~np.isnan(of)
+                        if ok.any():
+                            assert np.abs(f[ok] - of[ok]).max() <= 1e-11 * max(np.abs(of[ok]).max(), 1e-300), where
+                        if np.isfinite(oe):
+                            assert abs(e - oe) <= 1e-11 * max(abs(oe), 1e-300), where
+                        else:
+                            assert np.isnan(e) == np.isnan(oe), where
                     cases += 1
     assert cases > 60
