@@ -21,6 +21,8 @@ FH_CG_MAX_ITERATIONS, FH_CG_INDEFINITE_OPERATOR, FH_CG_INDEFINITE_PRECONDITIONER
 FH_NEWTON_MAX_ITERATIONS, FH_NEWTON_JACOBIAN_ERROR, FH_NEWTON_LINE_SEARCH_FAILED = 10, 11, 12
 NEWTON_NO_LINE_SEARCH, NEWTON_BACKTRACKING = 0, 1
 FH_EIG_MAX_ITERATIONS, FH_EIG_BREAKDOWN = 13, 14
+FH_DYNAMICS_NONFINITE = 15
+DYN_CENTRAL_DIFFERENCE, DYN_BACKWARD_EULER, DYN_NEWMARK = 0, 1, 2
 EIG_MAX_BLOCK = 32
 PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, PRECOND_AMG = 0, 1, 2, 3
 AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER = 0, 1, 2
@@ -37,6 +39,14 @@ ELEM_DIM = {QUAD4: 2, HEX8: 3, TET4: 3, HEX27: 3, TRI3: 2, TET10: 3, QUAD9: 2, T
 u64p = C.POINTER(C.c_uint64)
 f64p = C.POINTER(C.c_double)
 u32p = C.POINTER(C.c_uint32)
+
+
+class DynamicsSettings(C.Structure):
+    """fh_dynamics_settings"""
+
+    _fields_ = [("scheme", C.c_int), ("dt", C.c_double), ("newmark_beta", C.c_double), ("newmark_gamma", C.c_double),
+                ("newton_tolerance", C.c_double), ("newton_max_iterations", C.c_uint64), ("line_search", C.c_int), ("preconditioner", C.c_int),
+                ("linear_rel_tol", C.c_double), ("linear_max_iter", C.c_uint64)]
 
 
 class FenrisError(RuntimeError):
@@ -156,6 +166,16 @@ _SIGS = {
                                   C.c_uint64, u64p, f64p]),
     "fh_newton_solve_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_int,
                                       C.c_int, C.c_double, C.c_uint64, u64p, f64p]),
+    "fh_dynamics_create": (C.c_int, [C.c_void_p, C.POINTER(DynamicsSettings), C.POINTER(C.c_void_p)]),
+    "fh_dynamics_destroy": (None, [C.c_void_p]),
+    "fh_dynamics_set_state": (C.c_int, [C.c_void_p, f64p, f64p]),
+    "fh_dynamics_set_state_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fh_dynamics_set_load": (C.c_int, [C.c_void_p, f64p, f64p, C.c_uint64]),
+    "fh_dynamics_set_load_dev": (C.c_int, [C.c_void_p, C.c_void_p, f64p, C.c_uint64]),
+    "fh_dynamics_step": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, f64p, u64p, u64p]),
+    "fh_dynamics_state": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p, u64p]),
+    "fh_dynamics_state_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f64p, u64p]),
+    "fh_dynamics_stable_dt": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p]),
     "fh_mg_create": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(u64p), C.POINTER(u64p), C.POINTER(f64p),
                                C.POINTER(C.c_void_p)]),
     "fh_mg_destroy": (None, [C.c_void_p]),

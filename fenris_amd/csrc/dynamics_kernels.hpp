@@ -1,0 +1,108 @@
+// Time integration (engine_dynamics.hip): the central-difference update on a summed residual (the arithmetic of dynamics_step.hpp, which
+// the fused node pass k_dynamics_from_partials of vector_tiles.hip shares), the Newmark predictor and corrector, the kinetic-energy
+// partials and the vector kernels of the power iteration.  No atomics: every sum is a fixed tree per workgroup, the partials summed in index order.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "dynamics_step.hpp"
+#include "element_pass.hpp"
+
+namespace fenris_hip {
+
+// the central-difference update on a residual that is already summed (r: S N, read with DYN_ACCEL): the routes off the tiles -- Hex27,
+// Quad9, the quadratic simplices, rule-set tables, tiles that could not be built -- and the first kick and drift of a call on every route
+static __global__ void __launch_bounds__(256) k_dynamics_update(int n, int S, const double* r, const DynStep p) {
+    __shared__ double red[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    double ke = 0.0;
+    if (i < n) ke = dyn_dof(p, (size_t)i, p.dmask && p.dmask[i / S], dyn_load_factor(p), (p.flags & DYN_ACCEL) ? r[i] : 0.0);
+    if (p.flags & DYN_STORE) {
+        const double tot = block_sum_256(ke, red);
+        if (threadIdx.x == 0) p.ke_partial[blockIdx.x] = tot;
+    }
+}
+
+// Newmark predictor: u_ref = u + dt v + dt^2 (1/2 - beta) a (backward Euler: c2 = 0), and the Newton guess: the context's u takes u_ref on
+// the free dofs and keeps its Dirichlet entries; u_prev keeps u_n
+static __global__ void __launch_bounds__(256) k_newmark_predict(int n, int S, double dt, double c2, const unsigned char* dmask, double* u,
+                                                                const double* v, const double* a, double* u_ref, double* u_prev) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double un = u[i];
+    u_prev[i] = un;
+    const bool fixed = dmask && dmask[i / S];
+    const double ur = fixed ? un : fma(c2, a[i], fma(dt, v[i], un));
+    u_ref[i] = ur;
+    u[i] = ur;
+}
+
+// Newmark corrector on the solved u: a_new = (u - u_ref) inv_bdt2, v += dt ((1 - gamma) a + gamma a_new); backward Euler (euler != 0):
+// v = (u - u_prev) / dt, a = (v - v_old) / dt.  Dirichlet dofs: v = a = 0.
+static __global__ void __launch_bounds__(256) k_newmark_correct(int n, int S, int euler, double dt, double inv_bdt2, double gamma,
+                                                                const unsigned char* dmask, const double* u, const double* u_ref,
+                                                                const double* u_prev, double* v, double* a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (dmask && dmask[i / S]) {
+        v[i] = 0.0;
+        a[i] = 0.0;
+        return;
+    }
+    if (euler) {
+        const double vn = (u[i] - u_prev[i]) / dt;
+        a[i] = (vn - v[i]) / dt;
+        v[i] = vn;
+    } else {
+        const double an = (u[i] - u_ref[i]) * inv_bdt2, ao = a[i];
+        v[i] = fma(dt, fma(gamma, an, (1.0 - gamma) * ao), v[i]);
+        a[i] = an;
+    }
+}
+
+// per-workgroup partials of x . y: the consistent kinetic energy from y = M v, the load potential f . u
+static __global__ void __launch_bounds__(256) k_kinetic_partials(int n, const double* x, const double* y, double* partial) {
+    __shared__ double red[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const double t = i < n ? x[i] * y[i] : 0.0;
+    const double tot = block_sum_256(t, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+// b = lf f - r with the rows of the Dirichlet nodes zero: the right-hand side of M a_0 = lf_0 f - r(u_0)
+static __global__ void __launch_bounds__(256) k_dynamics_rhs(int n, int S, const double* f, const double* lf, unsigned long long lf_count,
+                                                             unsigned long long step, const unsigned char* dmask, const double* r, double* b) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double l = lf ? lf[step < lf_count ? step : lf_count - 1] : 1.0;
+    b[i] = (dmask && dmask[i / S]) ? 0.0 : fma(l, f ? f[i] : 0.0, -r[i]);
+}
+
+// x[i] *= s, or x[i] = 0 on the Dirichlet dofs (power iteration on the free dofs); x = y / m on the free dofs
+static __global__ void __launch_bounds__(256) k_dynamics_scale(int n, int S, double s, const unsigned char* dmask, double* x) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) x[i] = (dmask && dmask[i / S]) ? 0.0 : x[i] * s;
+}
+static __global__ void __launch_bounds__(256) k_dynamics_divide(int n, int S, const unsigned char* dmask, const double* y, const double* m, double* x) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) x[i] = (dmask && dmask[i / S]) ? 0.0 : y[i] / m[i];
+}
+// the start vector of the power iteration: column 0 of fh_eigs_lowest's fill
+static __global__ void __launch_bounds__(256) k_dynamics_fill(int n, double* x) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    unsigned long long z = (unsigned long long)i + 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    x[i] = (double)(z >> 11) * 0x1p-52 - 1.0;
+}
+// three partials per workgroup: x . (m x), x . y, and nothing else
+static __global__ void __launch_bounds__(256) k_dynamics_mdot(int n, const double* x, const double* m, double* partial) {
+    __shared__ double red[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const double t = i < n ? m[i] * (x[i] * x[i]) : 0.0;
+    const double tot = block_sum_256(t, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+}  // namespace fenris_hip

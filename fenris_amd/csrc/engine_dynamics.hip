@@ -1,0 +1,547 @@
+// Time integration on the device: M a + r(u) = lf f with the context's residual r and the mass of fh_set_mass_density, by central
+// differences (velocity-Verlet form, row-sum lumped mass), Newmark(beta, gamma) or backward Euler (one Newton solve per step: newton_run
+// of engine_newton.hip on alpha = 1, beta = newmark_beta dt^2); the handle, the step loops, the records and the C ABI
+#include "engine_internal.hpp"
+
+#include "dynamics_kernels.hpp"
+
+#include <cmath>
+
+struct fh_dynamics {
+    fh_ctx* c = nullptr;
+    fh_dynamics_settings s{};
+    unsigned long long topo_gen = 0;   // the context's mesh at creation: fh_set_mesh* invalidates the handle
+    int n = 0;                         // S N at creation
+    DevBuf<double> v, a, m, f, lf, r, rpart, kep, u_ref, u_prev, work, load;
+    std::vector<double> h_lf;
+    bool has_f = false;
+    uint64_t step = 0;                 // steps taken since fh_dynamics_set_state
+    // what m (the first five) and a_n (all six) were formed for: struct_gen (operator, table, mask), topo_gen, geom_gen, density_gen,
+    // dirichlet_gen, and the u_gen this handle left behind
+    unsigned long long m_key[5] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
+    unsigned long long a_key[6] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
+    bool load_changed = true;
+};
+
+namespace {
+
+const char* WHO = "fh_dynamics_step";
+
+bool explicit_scheme(const fh_dynamics* d) { return d->s.scheme == FH_DYN_CENTRAL_DIFFERENCE; }
+const unsigned char* dmask_of(const fh_ctx* c) { return c->mf_num_dirichlet ? c->mf_dmask.p : nullptr; }
+int blocks_of(int n) { return std::max(1, (n + 255) / 256); }
+
+void key_now(const fh_ctx* c, unsigned long long (&k)[6]) {
+    k[0] = c->struct_gen;
+    k[1] = c->topo_gen;
+    k[2] = c->geom_gen;
+    k[3] = c->density_gen;
+    k[4] = c->dirichlet_gen;
+    k[5] = c->u_gen;
+}
+
+// the handle still belongs to the context's mesh and the context can form M and r
+int dyn_ready(fh_dynamics* d, const char* who) {
+    fh_ctx* c = d->c;
+    if (c->topo_gen != d->topo_gen || c->S() * (int)c->N != d->n)
+        return c->fail(FH_INVALID_STATE, std::string(who) + ": the context's mesh or operator has changed since fh_dynamics_create");
+    return mf_shift_ready(c, who, 1.0, 1.0);
+}
+
+// the residual's partials over the tiles into d->rpart (*tiles = true), where newton_residual takes the tiles; nothing is waited for
+int residual_tiles(fh_dynamics* d, bool* tiles) {
+    fh_ctx* c = d->c;
+    *tiles = false;
+    if (!(c->E > 0 && !c->rs.active && tiles_enabled(c))) return FH_OK;
+    int rc = ensure_vector_tiles(c);
+    if (rc || c->vt_bad) return rc;
+    const size_t need = (size_t)c->vt.v.npartials * c->S();
+    if (d->rpart.n < need) HIP_TRY(c, d->rpart.alloc(need));
+    KArgs a;
+    fill_common(c, a);
+    a.work_begin = 0;
+    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
+    a.labels = nullptr;
+    if (vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, c->has_mask ? c->active.p : nullptr, d->rpart.p) != FH_OK) return FH_OK;
+    HIP_TRY(c, hipGetLastError());
+    *tiles = true;
+    return FH_OK;
+}
+
+// r(u) summed into d->r on every other route (newton_residual's second branch): waits for the device and reports the kernels' status
+int residual_summed(fh_dynamics* d) {
+    fh_ctx* c = d->c;
+    HIP_TRY(c, hipMemsetAsync(d->r.p, 0, sizeof(double) * (size_t)d->n, c->stream));
+    return c->rs.active ? rs_walk_accumulating(c, nullptr, [&](uint64_t* fl) { return residual_ordered_single(c, d->r.p, fl); })
+                        : residual_ordered_single(c, d->r.p, nullptr);
+}
+
+int sum_blocks(fh_ctx* c, const double* partial, int count, double* out) { return sum_partials(c, partial, count, 1, out); }
+
+// x . y in a fixed order
+int dot(fh_dynamics* d, const double* x, const double* y, double* out) {
+    fh_ctx* c = d->c;
+    const int g = blocks_of(d->n);
+    hipLaunchKernelGGL(k_kinetic_partials, dim3(g), dim3(256), 0, c->stream, d->n, x, y, d->kep.p);
+    HIP_TRY(c, hipGetLastError());
+    return sum_blocks(c, d->kep.p, g, out);
+}
+
+// the row-sum lumped mass m = M 1 (no Dirichlet rows take part) for the current mesh, table, mask and density; every free dof must have m > 0
+int ensure_lumped(fh_dynamics* d, const char* who) {
+    fh_ctx* c = d->c;
+    unsigned long long k[6];
+    key_now(c, k);
+    if (std::equal(k, k + 5, d->m_key)) return FH_OK;
+    const int n = d->n;
+    const std::vector<double> ones((size_t)n, 1.0);
+    std::vector<double> h((size_t)n);
+    HIP_TRY(c, hipMemcpyAsync(d->work.p, ones.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    int rc = mass_full(c, d->work.p, nullptr, d->m.p);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(h.data(), d->m.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    std::vector<unsigned char> hm(c->N, 0);
+    if (c->mf_num_dirichlet) HIP_TRY(c, hipMemcpyAsync(hm.data(), c->mf_dmask.p, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int S = c->S();
+    for (int i = 0; i < n; ++i)
+        if (!hm[(size_t)(i / S)] && !(h[(size_t)i] > 0.0))
+            return c->fail(FH_UNSUPPORTED, std::string(who) + ": the row-sum lumped mass of dof " + std::to_string(i) + " (node " + std::to_string(i / S) +
+                                               ") is " + std::to_string(h[(size_t)i]) + ", not positive: central differences need another lumping on this element kind");
+    std::copy(k, k + 5, d->m_key);
+    return FH_OK;
+}
+
+DynStep step_args(fh_dynamics* d, int flags, uint64_t step) {
+    fh_ctx* c = d->c;
+    DynStep p;
+    p.dt = d->s.dt;
+    p.half_dt = 0.5 * d->s.dt;
+    p.f = d->has_f ? d->f.p : nullptr;
+    p.lf = d->h_lf.empty() ? nullptr : d->lf.p;
+    p.lf_count = d->h_lf.size();
+    p.step = step;
+    p.m = d->m.p;
+    p.dmask = dmask_of(c);
+    p.u = c->u.p;
+    p.v = d->v.p;
+    p.a = d->a.p;
+    p.ke_partial = d->kep.p;
+    p.flags = flags;
+    return p;
+}
+
+// one launch of the central-difference update on the residual at the context's u (flags with DYN_ACCEL), or the first kick and drift alone.
+// *ke_count: the partials a DYN_STORE launch leaves.  On the tiles nothing is waited for.
+int explicit_launch(fh_dynamics* d, int flags, uint64_t step, uint64_t* stats, int* ke_count) {
+    fh_ctx* c = d->c;
+    const int S = c->S(), n = d->n;
+    const DynStep p = step_args(d, flags, step);
+    if (flags & DYN_ACCEL) {
+        bool tiles;
+        int rc = residual_tiles(d, &tiles);
+        if (rc) return rc;
+        ++stats[1];
+        if (tiles) {
+            HIP_TRY(c, vector_tiles_dynamics_node_pass(c->stream, S, (int)c->N, c->vt.v, d->rpart.p, p));
+            c->last_kernel = "k_element_pass_tiled + k_dynamics_from_partials";
+            if (ke_count) *ke_count = vector_tiles_operator_partials((int)c->N);
+            if (flags & DYN_ADVANCE) ++c->u_gen;
+            return FH_OK;
+        }
+        rc = residual_summed(d);
+        if (rc) return rc;
+        c->last_kernel = "k_residual_elements + k_vector_from_elements_soa + k_dynamics_update";
+    }
+    hipLaunchKernelGGL(k_dynamics_update, dim3(blocks_of(n)), dim3(256), 0, c->stream, n, S, d->r.p, p);
+    HIP_TRY(c, hipGetLastError());
+    if (ke_count) *ke_count = blocks_of(n);
+    if (flags & DYN_ADVANCE) ++c->u_gen;
+    return FH_OK;
+}
+
+double load_factor(const fh_dynamics* d, uint64_t step) {
+    return d->h_lf.empty() ? 1.0 : d->h_lf[(size_t)std::min<uint64_t>(step, d->h_lf.size() - 1)];
+}
+
+// stored energy and load potential of the state after `step` steps, into row[1..3]
+int record_rest(fh_dynamics* d, uint64_t step, double* row) {
+    fh_ctx* c = d->c;
+    int rc = fh_assemble_scalar(c, &row[1], nullptr);
+    if (rc) return rc;
+    row[2] = 0.0;
+    if (d->has_f) {
+        rc = dot(d, d->f.p, c->u.p, &row[2]);
+        if (rc) return rc;
+        row[2] *= load_factor(d, step);
+    }
+    row[3] = (double)step * d->s.dt;
+    return FH_OK;
+}
+
+// a_n for the state as it stands, when anything it depends on has changed since it was formed
+int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
+    fh_ctx* c = d->c;
+    unsigned long long k[6];
+    key_now(c, k);
+    if (std::equal(k, k + 6, d->a_key) && !d->load_changed) return FH_OK;
+    const int n = d->n, S = c->S(), g = blocks_of(n);
+    int rc;
+    // (v and a of a Dirichlet dof are zero whatever fh_dynamics_set_state was given)
+    hipLaunchKernelGGL(k_dynamics_scale, dim3(g), dim3(256), 0, c->stream, n, S, 1.0, dmask_of(c), d->v.p);
+    HIP_TRY(c, hipGetLastError());
+    if (explicit_scheme(d)) {
+        rc = reset_status(c);
+        if (rc) return rc;
+        rc = explicit_launch(d, DYN_ACCEL, d->step, stats, nullptr);
+        if (rc) return rc;
+    } else {   // Newmark: M a_0 = lf_0 f - r(u_0) on the free dofs; backward Euler keeps no a_0 but refuses the same states
+        rc = residual_summed(d);
+        if (rc) return rc;
+        ++stats[1];
+        hipLaunchKernelGGL(k_dynamics_rhs, dim3(g), dim3(256), 0, c->stream, n, S, d->has_f ? d->f.p : nullptr, d->h_lf.empty() ? nullptr : d->lf.p,
+                           (unsigned long long)d->h_lf.size(), (unsigned long long)d->step, dmask_of(c), d->r.p, d->work.p);
+        HIP_TRY(c, hipGetLastError());
+        double b2 = 0.0;   // (an inverted NeoHookean state makes r NaN: reported as such, not as a breakdown of the PCG or of Newton)
+        rc = dot(d, d->work.p, d->work.p, &b2);
+        if (rc) return rc;
+        if (!std::isfinite(b2)) return c->fail(FH_DYNAMICS_NONFINITE, std::string(WHO) + ": the residual of the initial state is not finite");
+        HIP_TRY(c, hipMemsetAsync(d->a.p, 0, sizeof(double) * (size_t)n, c->stream));
+        if (d->s.scheme == FH_DYN_NEWMARK) {
+            uint64_t it = 0;
+            const int pre = d->s.preconditioner == FH_PRECOND_MULTIGRID ? (int)FH_PRECOND_JACOBI : d->s.preconditioner;   // (M alone needs no hierarchy)
+            rc = cg_solve_free_dev(c, WHO, FH_STVK, d->work.p, d->a.p, pre, d->s.linear_rel_tol, d->s.linear_max_iter, &it, 1.0, 0.0);
+            stats[3] += it;
+            if (rc) return rc;
+        }
+    }
+    key_now(c, k);
+    std::copy(k, k + 6, d->a_key);
+    d->load_changed = false;
+    return FH_OK;
+}
+
+void remember_u(fh_dynamics* d) { d->a_key[5] = d->c->u_gen; }
+
+int explicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, double* records, uint64_t* done, uint64_t* stats) {
+    fh_ctx* c = d->c;
+    const uint64_t s0 = d->step;
+    int rc = reset_status(c);
+    if (rc) return rc;
+    rc = explicit_launch(d, DYN_ADVANCE, s0, stats, nullptr);   // the first kick and drift of the call
+    if (rc) return rc;
+    for (uint64_t j = 0; j < num_steps; ++j) {
+        const bool last = j + 1 == num_steps;
+        const bool rec = last || (record_every && (j + 1) % record_every == 0);
+        int ke_count = 0;
+        // (a record needs u_{n+1} for the stored energy and the load potential, so the launch of a record stores and stops; every other
+        // launch goes straight on to the next kick and drift)
+        rc = explicit_launch(d, DYN_ACCEL | DYN_COMPLETE | (rec ? DYN_STORE : DYN_ADVANCE), s0 + j + 1, stats, rec ? &ke_count : nullptr);
+        if (rc) return rc;
+        if (!rec) continue;
+        double row[4] = {0.0, 0.0, 0.0, 0.0};
+        rc = sum_blocks(c, d->kep.p, ke_count, &row[0]);   // the host waits here: once per record
+        if (rc) return rc;
+        row[0] *= 0.5;
+        rc = read_status(c, nullptr);
+        if (rc) return rc;
+        rc = record_rest(d, s0 + j + 1, row);
+        if (rc) return rc;
+        if (!std::isfinite(row[0]) || !std::isfinite(row[1]))
+            return c->fail(FH_DYNAMICS_NONFINITE, std::string(WHO) + ": the kinetic or stored energy after step " + std::to_string(s0 + j + 1) + " is not finite");
+        if (records) std::copy(row, row + 4, records + 4 * stats[4]);
+        ++stats[4];
+        *done = j + 1;
+        d->step = s0 + j + 1;
+        remember_u(d);
+        if (!last) {
+            rc = reset_status(c);
+            if (rc) return rc;
+            rc = explicit_launch(d, DYN_ADVANCE, d->step, stats, nullptr);
+            if (rc) return rc;
+        }
+    }
+    return FH_OK;
+}
+
+int implicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, double* records, uint64_t* done, uint64_t* stats) {
+    fh_ctx* c = d->c;
+    const int n = d->n, S = c->S(), g = blocks_of(n);
+    const bool euler = d->s.scheme == FH_DYN_BACKWARD_EULER;
+    const double dt = d->s.dt, nb = euler ? 1.0 : d->s.newmark_beta, bdt2 = nb * dt * dt;
+    for (uint64_t j = 0; j < num_steps; ++j) {
+        const uint64_t g_step = d->step + 1;
+        hipLaunchKernelGGL(k_newmark_predict, dim3(g), dim3(256), 0, c->stream, n, S, dt, euler ? 0.0 : dt * dt * (0.5 - nb), dmask_of(c), c->u.p,
+                           d->v.p, d->a.p, d->u_ref.p, d->u_prev.p);
+        HIP_TRY(c, hipGetLastError());
+        ++c->u_gen;
+        const double* load = nullptr;
+        if (d->has_f) {   // the load of the step: lf_{n+1} f
+            HIP_TRY(c, hipMemcpyAsync(d->load.p, d->f.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+            hipLaunchKernelGGL(k_dynamics_scale, dim3(g), dim3(256), 0, c->stream, n, S, load_factor(d, g_step), (const unsigned char*)nullptr, d->load.p);
+            HIP_TRY(c, hipGetLastError());
+            load = d->load.p;
+        }
+        uint64_t st[4] = {0, 0, 0, 0};
+        double nm[3] = {0.0, 0.0, 0.0};
+        int rc = newton_run(c, 1.0, bdt2, load, d->u_ref.p, d->s.newton_tolerance, d->s.newton_max_iterations, d->s.line_search, d->s.preconditioner,
+                            d->s.linear_rel_tol, d->s.linear_max_iter, st, nm);
+        stats[1] += st[1];
+        stats[2] += st[0];
+        stats[3] += st[2];
+        if (rc) {   // the state stays that of the last completed step
+            const std::string msg = c->err;
+            HIP_TRY(c, hipMemcpyAsync(c->u.p, d->u_prev.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            ++c->u_gen;
+            remember_u(d);
+            return c->fail(rc, msg);
+        }
+        hipLaunchKernelGGL(k_newmark_correct, dim3(g), dim3(256), 0, c->stream, n, S, euler ? 1 : 0, dt, 1.0 / bdt2, d->s.newmark_gamma, dmask_of(c),
+                           c->u.p, d->u_ref.p, d->u_prev.p, d->v.p, d->a.p);
+        HIP_TRY(c, hipGetLastError());
+        d->step = g_step;
+        remember_u(d);
+        *done = j + 1;
+        const bool last = j + 1 == num_steps;
+        if (!(last || (record_every && (j + 1) % record_every == 0))) continue;
+        double row[4] = {0.0, 0.0, 0.0, 0.0};
+        rc = mass_full(c, d->v.p, nullptr, d->work.p);   // the consistent kinetic energy 1/2 v . M v
+        if (rc) return rc;
+        rc = dot(d, d->v.p, d->work.p, &row[0]);
+        if (rc) return rc;
+        row[0] *= 0.5;
+        rc = record_rest(d, g_step, row);
+        if (rc) return rc;
+        if (records) std::copy(row, row + 4, records + 4 * stats[4]);
+        ++stats[4];
+        if (!std::isfinite(row[0]) || !std::isfinite(row[1]))
+            return c->fail(FH_DYNAMICS_NONFINITE, std::string(WHO) + ": the kinetic or stored energy after step " + std::to_string(g_step) + " is not finite");
+    }
+    return FH_OK;
+}
+
+int set_state_common(fh_dynamics* d, const double* u, const double* v, hipMemcpyKind kind) {
+    fh_ctx* c = d->c;
+    int rc = dyn_ready(d, "fh_dynamics_set_state");
+    if (rc) return rc;
+    const size_t bytes = sizeof(double) * (size_t)d->n;
+    if (u) {
+        rc = kind == hipMemcpyHostToDevice ? fh_set_u(c, u) : fh_set_u_dev(c, u);
+    } else {
+        std::vector<double> z((size_t)d->n, 0.0);
+        rc = fh_set_u(c, z.data());
+    }
+    if (rc) return rc;
+    if (v) HIP_TRY(c, hipMemcpyAsync(d->v.p, v, bytes, kind, c->stream));
+    else HIP_TRY(c, hipMemsetAsync(d->v.p, 0, bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d->a.p, 0, bytes, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    d->step = 0;
+    d->a_key[5] = ~0ull;
+    return FH_OK;
+}
+
+int set_load_common(fh_dynamics* d, const double* f, const double* load_factor, uint64_t count, hipMemcpyKind kind) {
+    fh_ctx* c = d->c;
+    if (load_factor && count == 0) return c->fail(FH_BAD_ARGUMENT, "fh_dynamics_set_load: load_factor needs count >= 1");
+    d->has_f = f != nullptr;
+    if (f) HIP_TRY(c, hipMemcpyAsync(d->f.p, f, sizeof(double) * (size_t)d->n, kind, c->stream));
+    d->h_lf.clear();
+    if (load_factor) {
+        d->h_lf.assign(load_factor, load_factor + count);
+        if (d->lf.n < count) HIP_TRY(c, d->lf.alloc((size_t)count));
+        HIP_TRY(c, hipMemcpyAsync(d->lf.p, d->h_lf.data(), sizeof(double) * (size_t)count, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    d->load_changed = true;
+    return FH_OK;
+}
+
+int state_common(fh_dynamics* d, double* u, double* v, double* a, double* time, uint64_t* step, hipMemcpyKind kind) {
+    fh_ctx* c = d->c;
+    int rc = dyn_ready(d, "fh_dynamics_state");
+    if (rc) return rc;
+    const size_t bytes = sizeof(double) * (size_t)d->n;
+    if (a && c->has_u && c->N) {   // a_n of the state as it stands (a_0 before the first step)
+        uint64_t st[5] = {0, 0, 0, 0, 0};
+        if (explicit_scheme(d)) rc = ensure_lumped(d, "fh_dynamics_state");
+        if (!rc) rc = ensure_acceleration(d, st);
+        if (rc) return rc;
+    }
+    if (u) {
+        if (!c->has_u) return c->fail(FH_INVALID_STATE, "fh_dynamics_state: no state set");
+        HIP_TRY(c, hipMemcpyAsync(u, c->u.p, bytes, kind, c->stream));
+    }
+    if (v) HIP_TRY(c, hipMemcpyAsync(v, d->v.p, bytes, kind, c->stream));
+    if (a) HIP_TRY(c, hipMemcpyAsync(a, d->a.p, bytes, kind, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (time) *time = (double)d->step * d->s.dt;
+    if (step) *step = d->step;
+    return FH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fh_dynamics_create(fh_ctx* c, const fh_dynamics_settings* s, fh_dynamics** out) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_dynamics_create";
+    if (!s || !out) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    *out = nullptr;
+    if (s->scheme != FH_DYN_CENTRAL_DIFFERENCE && s->scheme != FH_DYN_BACKWARD_EULER && s->scheme != FH_DYN_NEWMARK)
+        return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown scheme");
+    if (!std::isfinite(s->dt) || !(s->dt > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": dt must be positive and finite");
+    if (s->scheme == FH_DYN_NEWMARK && (!std::isfinite(s->newmark_beta) || !(s->newmark_beta > 0.0) || !std::isfinite(s->newmark_gamma)))
+        return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": newmark_beta must be positive and newmark_gamma finite");
+    if (s->scheme != FH_DYN_CENTRAL_DIFFERENCE) {
+        if (!std::isfinite(s->newton_tolerance) || !std::isfinite(s->linear_rel_tol))
+            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the tolerances must be finite");
+        if (s->line_search != FH_NEWTON_NO_LINE_SEARCH && s->line_search != FH_NEWTON_BACKTRACKING)
+            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown line search");
+        if (s->preconditioner != FH_PRECOND_IDENTITY && s->preconditioner != FH_PRECOND_JACOBI && s->preconditioner != FH_PRECOND_MULTIGRID)
+            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown preconditioner");
+    }
+    int rc = mf_shift_ready(c, who, 1.0, 1.0);   // FH_UNSUPPORTED: mass operators, FH_TENSOR; FH_INVALID_STATE: no mesh, table or density
+    if (rc) return rc;
+    fh_dynamics* d = new fh_dynamics;
+    d->c = c;
+    d->s = *s;
+    d->topo_gen = c->topo_gen;
+    d->n = c->S() * (int)c->N;
+    const size_t n = (size_t)d->n;
+    const bool ex = s->scheme == FH_DYN_CENTRAL_DIFFERENCE;
+    hipError_t e = hipSuccess;
+    auto get = [&](DevBuf<double>& b, size_t count) { if (e == hipSuccess) e = b.alloc(count); };
+    get(d->v, n); get(d->a, n); get(d->m, n); get(d->f, n); get(d->r, n); get(d->work, n);
+    get(d->kep, (size_t)blocks_of(d->n));
+    if (!ex) { get(d->u_ref, n); get(d->u_prev, n); get(d->load, n); }
+    if (e == hipSuccess) e = hipMemsetAsync(d->v.p, 0, sizeof(double) * std::max<size_t>(n, 1), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d->a.p, 0, sizeof(double) * std::max<size_t>(n, 1), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        delete d;
+        return e == hipErrorOutOfMemory ? c->fail(FH_OUT_OF_MEMORY, std::string(who) + ": no room for the state vectors") : c->hip_fail(e, who);
+    }
+    *out = d;
+    return FH_OK;
+}
+
+void fh_dynamics_destroy(fh_dynamics* d) {
+    if (!d) return;
+    DevGuard dev_guard_(d->c->device);
+    delete d;
+}
+
+int fh_dynamics_set_state(fh_dynamics* d, const double* u, const double* v) {
+    if (!d) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(d->c->device);
+    return set_state_common(d, u, v, hipMemcpyHostToDevice);
+}
+int fh_dynamics_set_state_dev(fh_dynamics* d, const double* u_dev, const double* v_dev) {
+    if (!d) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(d->c->device);
+    return set_state_common(d, u_dev, v_dev, hipMemcpyDeviceToDevice);
+}
+
+int fh_dynamics_set_load(fh_dynamics* d, const double* f, const double* load_factor, uint64_t count) {
+    if (!d) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(d->c->device);
+    return set_load_common(d, f, load_factor, count, hipMemcpyHostToDevice);
+}
+int fh_dynamics_set_load_dev(fh_dynamics* d, const double* f_dev, const double* load_factor, uint64_t count) {
+    if (!d) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(d->c->device);
+    return set_load_common(d, f_dev, load_factor, count, hipMemcpyDeviceToDevice);
+}
+
+int fh_dynamics_step(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, double* records, uint64_t* steps_done, uint64_t* stats) {
+    if (!d) return FH_BAD_ARGUMENT;
+    fh_ctx* c = d->c;
+    DevGuard dev_guard_(c->device);
+    uint64_t st[5] = {0, 0, 0, 0, 0}, done = 0;
+    if (steps_done) *steps_done = 0;
+    if (stats) std::fill(stats, stats + 5, 0);
+    int rc = dyn_ready(d, WHO);
+    if (rc) return rc;
+    if (c->N == 0 || num_steps == 0) return FH_OK;
+    if (!c->has_u) {
+        rc = set_state_common(d, nullptr, nullptr, hipMemcpyHostToDevice);
+        if (rc) return rc;
+    }
+    if (explicit_scheme(d)) rc = ensure_lumped(d, WHO);
+    if (!rc) rc = ensure_acceleration(d, st);
+    if (!rc)
+        rc = explicit_scheme(d) ? explicit_steps(d, num_steps, record_every, records, &done, st)
+                                : implicit_steps(d, num_steps, record_every, records, &done, st);
+    st[0] = done;
+    if (steps_done) *steps_done = done;
+    if (stats) std::copy(st, st + 5, stats);
+    return rc;
+}
+
+int fh_dynamics_state(fh_dynamics* d, double* u, double* v, double* a, double* time, uint64_t* step) {
+    if (!d) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(d->c->device);
+    return state_common(d, u, v, a, time, step, hipMemcpyDeviceToHost);
+}
+int fh_dynamics_state_dev(fh_dynamics* d, double* u_dev, double* v_dev, double* a_dev, double* time, uint64_t* step) {
+    if (!d) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(d->c->device);
+    return state_common(d, u_dev, v_dev, a_dev, time, step, hipMemcpyDeviceToDevice);
+}
+
+int fh_dynamics_stable_dt(fh_dynamics* d, uint32_t iterations, double* omega_max, double* dt_crit) {
+    if (!d) return FH_BAD_ARGUMENT;
+    fh_ctx* c = d->c;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_dynamics_stable_dt";
+    if (!omega_max || !dt_crit || iterations == 0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null result or no iterations");
+    int rc = dyn_ready(d, who);
+    if (rc) return rc;
+    if (!c->has_u) {
+        rc = set_state_common(d, nullptr, nullptr, hipMemcpyHostToDevice);
+        if (rc) return rc;
+    }
+    rc = ensure_lumped(d, who);
+    if (rc) return rc;
+    const int n = d->n, S = c->S(), g = blocks_of(n);
+    DevBuf<double> x, y;
+    HIP_TRY(c, x.alloc((size_t)n));
+    HIP_TRY(c, y.alloc((size_t)n));
+    auto normalise = [&]() -> int {   // x <- x / sqrt(x . m x), zero on the Dirichlet dofs
+        double mm = 0.0;
+        hipLaunchKernelGGL(k_dynamics_mdot, dim3(g), dim3(256), 0, c->stream, n, x.p, d->m.p, d->kep.p);
+        HIP_TRY(c, hipGetLastError());
+        const int r = sum_blocks(c, d->kep.p, g, &mm);
+        if (r) return r;
+        hipLaunchKernelGGL(k_dynamics_scale, dim3(g), dim3(256), 0, c->stream, n, S, 1.0 / std::sqrt(mm), dmask_of(c), x.p);
+        HIP_TRY(c, hipGetLastError());
+        return (int)FH_OK;
+    };
+    hipLaunchKernelGGL(k_dynamics_fill, dim3(g), dim3(256), 0, c->stream, n, x.p);
+    hipLaunchKernelGGL(k_dynamics_scale, dim3(g), dim3(256), 0, c->stream, n, S, 1.0, dmask_of(c), x.p);
+    HIP_TRY(c, hipGetLastError());
+    rc = normalise();
+    if (rc) return rc;
+    double rq = 0.0;
+    for (uint32_t it = 0; it < iterations; ++it) {
+        rc = fh_apply_tangent_dev(c, x.p, y.p);
+        if (rc) return rc;
+        rc = dot(d, x.p, y.p, &rq);   // x is m-normalised: the Rayleigh quotient of (T, m)
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_dynamics_divide, dim3(g), dim3(256), 0, c->stream, n, S, dmask_of(c), y.p, d->m.p, x.p);
+        HIP_TRY(c, hipGetLastError());
+        rc = normalise();
+        if (rc) return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!(rq > 0.0) || !std::isfinite(rq)) return c->fail(FH_DYNAMICS_NONFINITE, std::string(who) + ": the Rayleigh quotient is not positive and finite");
+    *omega_max = std::sqrt(rq);
+    *dt_crit = 2.0 / *omega_max;
+    return FH_OK;
+}
+
+}  // extern "C"

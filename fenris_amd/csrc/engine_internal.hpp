@@ -557,7 +557,7 @@ struct DevGuard {
 // ---- functions shared by the translation units of the engine (engine.hip: context, mesh, pattern, options; engine_partition.hip: owner
 // blocks and position tables; engine_matrix.hip: stiffness / mass launchers; engine_two_pass.hip: dense element matrices + row gather;
 // engine_vector.hip: residual, source, energy; engine_solver.hip: Dirichlet rows, SpMV, PCG, error integrals; engine_eigs.hip: block vectors
-// and the LOBPCG eigensolver)
+// and the LOBPCG eigensolver; engine_dynamics.hip: the time integrators)
 constexpr size_t LDS_TARGET = 64 * 1024;   // two workgroups per CU
 constexpr size_t LDS_LIMIT = 160 * 1024;   // hardware limit per workgroup
 inline bool generic_fast(const fh_ctx* c) { return c->fast_ok && (!c->has_rules || c->op == FH_LAPLACE); }
@@ -633,6 +633,16 @@ struct NewtonScratch {
     DevBuf<double> wg, sums;          // per-workgroup partials of |F|^2, and their ordered range sums
 };
 int newton_residual(fh_ctx* c, double alpha, double beta, const double* f_dev, const double* d_dev, NewtonScratch& ns, double* norm2);
+// pieces of that residual and of the Newton loop that the time integrators (engine_dynamics.hip) compose again: the element tiles serve this
+// context / are built for its topology (vt_bad: they could not be); r(u) of the current table ADDED to out through element vectors and the
+// ordered node sums (engine_vector.hip); M x (x null: the diagonal) over every group of the table into out; the loop of fh_newton_solve on
+// the context's u (engine_newton.hip; st: 4 counters, nm: 3 norms, as fh_newton_solve's stats and norms)
+bool tiles_enabled(const fh_ctx* c);
+int ensure_vector_tiles(fh_ctx* c);
+int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed);
+int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* out);
+int newton_run(fh_ctx* c, double alpha, double beta, const double* f, const double* u_ref, double tolerance, uint64_t max_iterations,
+               int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter, uint64_t* st, double* nm);
 
 // One launch with `lds` bytes of dynamic LDS: more than 48 KB has to be allowed per kernel first.  Which instantiation `kern` is comes from
 // dispatch.hpp.

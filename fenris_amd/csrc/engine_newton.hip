@@ -19,7 +19,7 @@ double next_step_length(double a) {
 // newton_line_search (newton.rs:77-130) for F(u) = alpha M (u - u_ref) + beta (r(u) - f).  The iterate is the context's u, moved in place
 // (k_newton_move, which also forms d = u - u_ref for the mass term), so that every residual evaluation reads it where it lies; u_gen moves with
 // every move.  Each Newton step solves J q = F (q = -dx of newton.rs:109-117) by the matrix-free shifted PCG from a zero guess; the step is p = -q.
-static int newton_run(fh_ctx* c, double alpha, double beta, const double* f, const double* u_ref, double tolerance, uint64_t max_iterations,
+int newton_run(fh_ctx* c, double alpha, double beta, const double* f, const double* u_ref, double tolerance, uint64_t max_iterations,
                       int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter, uint64_t* st, double* nm) {
     const char* who = "fh_newton_solve";
     const int n = c->S() * (int)c->N;

@@ -70,7 +70,7 @@ static bool element_pass_covers(const fh_ctx* c) {
            (c->elem_kind == FH_HEX8 || c->elem_kind == FH_TET4 || c->elem_kind == FH_QUAD4 || c->elem_kind == FH_TRI3);
 }
 // the element tiles (vector_tiles.hip) serve this context
-static bool tiles_enabled(const fh_ctx* c) { return element_pass_covers(c) && !c->opt.VECTOR_ATOMICS && !c->opt.NO_VECTOR_TILES; }
+bool tiles_enabled(const fh_ctx* c) { return element_pass_covers(c) && !c->opt.VECTOR_ATOMICS && !c->opt.NO_VECTOR_TILES; }
 
 extern "C" {
 
@@ -98,7 +98,7 @@ int fh_assemble_vector_async_dev(fh_ctx* c, double* out_dev) {
     return rc;
 }
 // element tiles of the residual / source vector passes (vector_tiles.hip): once per mesh topology
-static int ensure_vector_tiles(fh_ctx* c) {
+extern "C++" int ensure_vector_tiles(fh_ctx* c) {
     if (c->vt_gen == c->topo_gen) return FH_OK;
     int bad = 0;
     const hipError_t e = vector_tiles_build(c->stream, c->conn.p, c->ei.n, (long long)c->E, c->verts.p, c->ei.d, (int)c->N, &c->vt, &bad);
@@ -787,7 +787,7 @@ static int mass_single(fh_ctx* c, const double* x, const unsigned char* dmask, d
 }
 
 // M x (x null: its diagonal) over every group of the table into out (S N doubles)
-static int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* out) {
+int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* out) {
     const size_t n = (size_t)c->S() * c->N;
     HIP_TRY(c, hipMemsetAsync(out, 0, sizeof(double) * n, c->stream));
     if (c->rs.active) return rs_walk_accumulating(c, nullptr, [&](uint64_t*) { return mass_single(c, x, dmask, out); });
@@ -945,7 +945,7 @@ static void residual_elements_launch(fh_ctx* c, const KArgs& a, const unsigned c
         });
     });
 }
-static int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed) {
+int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed) {
     int rc = reset_status(c);
     if (rc) return rc;
     if (c->E == 0 || (c->has_mask && c->num_active == 0)) return FH_OK;

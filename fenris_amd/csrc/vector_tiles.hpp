@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.hpp"
+#include "dynamics_step.hpp"
 
 namespace fenris_hip {
 
@@ -87,6 +88,11 @@ hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes
 // them), to be summed in index order.
 hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const double* mpart,
                                          const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial);
+
+// node pass of a central-difference step: the node sums of the residual's partials (vector_tiles_element_pass) and the integrator's state
+// update of p.flags (DynStep, dynamics_kernels.hpp) in one visit; with DYN_STORE one partial of sum m v^2 per workgroup
+// (vector_tiles_operator_partials of them) into p.ke_partial, to be summed in index order.
+hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const DynStep& p);
 
 // the shifted map fused on Hex8 with the monomial table (a.qmono; -1 otherwise): partial[P][S] of beta T(u) x + alpha M x in ONE element pass
 // (k_shifted_pass_tiled for the linear operators, which read the operand from a.u; k_shifted_tangent_tiled for NeoHookean / StVK, operand x),

@@ -1,0 +1,260 @@
+"""Time integration on the device (fh_dynamics_*, include/fenris_hip.h):  M a + r(u) = lf_n f  with an element assembler's residual and
+the mass of MatrixFreeShiftedTangent, by central differences, Newmark(beta, gamma) or backward Euler.
+
+    ti = (CentralDifference(asm, density, dt).with_dirichlet_nodes(clamp).with_load(f, load_factor=np.linspace(0, 1, 8)))
+    ti.set_state(u0, v0)
+    rec = ti.step(1000, record_every=100)        # rec.kinetic, rec.stored, rec.load_potential, rec.time: one entry per record
+    u, v, a, time, step = ti.state()
+
+The whole loop runs in the library: on Hex8, Tet4, Quad4 and Tri3 an explicit step is the residual's element pass and one node pass, and
+the host waits only at records."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _ffi
+from ._ffi import FenrisError, SingularJacobianError
+from .assembly import (BacktrackingLineSearch, JacobianError, LineSearchError, MaximumIterationsReached, NewtonResult, NewtonSettings, _is_torch,
+                       _ptr)
+
+
+class DynamicsError(FenrisError):
+    """fh_dynamics_step ended early (FH_DYNAMICS_NONFINITE, or any code that is not a Newton failure); steps_done: the steps of the call
+    that stand (for central differences: up to the last clean record)"""
+
+    def __init__(self, code, message, steps_done):
+        super().__init__(code, message)
+        self.steps_done = steps_done
+
+
+@dataclass
+class DynamicsRecord:
+    """the records of one step() call, one entry per record: time, kinetic energy, stored energy, lf f . u; steps_done; stats = (steps,
+    residual evaluations, Newton iterations, PCG iterations, records)"""
+
+    time: np.ndarray
+    kinetic: np.ndarray
+    stored: np.ndarray
+    load_potential: np.ndarray
+    steps_done: int
+    stats: tuple
+
+
+class TimeIntegrator:
+    """The interface the three schemes share.  Density, Dirichlet nodes and load belong to this object and are handed to the engine before
+    every use (the discipline of MatrixFreeNewton._bind), so several objects may share one assembler.  The assembler's u is the state's u."""
+
+    scheme = None
+
+    def __init__(self, element_assembler, density, dt):
+        self.element_assembler = element_assembler
+        self.engine = element_assembler.engine
+        self.dt = float(dt)
+        self._rho = np.ascontiguousarray(np.atleast_1d(np.asarray(density, dtype=np.float64)).ravel()).copy()
+        self._nodes = None
+        self._mg = None
+        self._settings = NewtonSettings()
+        self._line_search = BacktrackingLineSearch()
+        self._linear_rel_tol, self._linear_max_iter = 1e-8, 0
+        self._beta, self._gamma = 0.25, 0.5
+        self._h = None
+        self._load = (None, None)
+        self.engine.set_mass_density(self._rho)   # (checks the count now)
+        self.engine._mass_bound = self
+
+    # ---- configuration
+    def with_dirichlet_nodes(self, nodes):
+        """the nodes held at the u of set_state, with v = a = 0 (None: none); returns self"""
+        self._nodes = None if nodes is None else _ffi.as_u64(nodes).copy()
+        self._bind(force=True)
+        return self
+
+    def with_load(self, f, load_factor=None):
+        """the load f (numpy array or device tensor; None: zero) and the factor per step, lf_n = load_factor[min(n, len - 1)] (None: 1)"""
+        self._load = (f, None if load_factor is None else _ffi.as_f64(load_factor).reshape(-1).copy())
+        if self._h is not None:
+            self._send_load()
+        return self
+
+    def _bind(self, force=False):
+        if force or getattr(self.engine, "_mf_bound", None) is not self:
+            self.engine.set_operator_dirichlet_nodes(self._nodes)
+            self.engine._mf_bound = self
+        if force or getattr(self.engine, "_mass_bound", None) is not self:
+            self.engine.set_mass_density(self._rho)
+            self.engine._mass_bound = self
+
+    def _n(self):
+        return self.element_assembler.solution_dim() * self.engine.num_nodes()
+
+    def _fh_settings(self):
+        s = _ffi.DynamicsSettings()
+        s.scheme, s.dt = self.scheme, self.dt
+        s.newmark_beta, s.newmark_gamma = self._beta, self._gamma
+        s.newton_tolerance, s.newton_max_iterations = self._settings.tolerance, self._settings.max_iterations or 0
+        s.line_search = self._line_search.kind
+        s.preconditioner = _ffi.PRECOND_MULTIGRID if self._mg is not None else _ffi.PRECOND_JACOBI
+        s.linear_rel_tol, s.linear_max_iter = self._linear_rel_tol, self._linear_max_iter
+        return s
+
+    def _handle(self):
+        self._bind()
+        if self._h is None:
+            h = C.c_void_p()
+            s = self._fh_settings()
+            self.engine._check(self.engine._lib.fh_dynamics_create(self.engine._h, C.byref(s), C.byref(h)))
+            self._h = h
+            self._send_load()
+        return self._h
+
+    def _drop(self):
+        if self._h is not None:
+            self.engine._lib.fh_dynamics_destroy(self._h)
+            self._h = None
+
+    def close(self):
+        self._drop()
+
+    def __del__(self):
+        try:
+            if getattr(self.engine, "_h", None):
+                self._drop()
+        except Exception:
+            pass
+
+    def _send_load(self):
+        f, lf = self._load
+        n = self._n()
+        lib = self.engine._lib
+        if f is not None and (f.numel() if _is_torch(f) else np.size(f)) != n:
+            raise ValueError(f"f must hold {n} entries")
+        cnt = 0 if lf is None else len(lf)
+        if _is_torch(f):
+            import torch
+
+            ft = f.to(dtype=torch.float64, device=f"cuda:{self.engine.device}").reshape(-1).contiguous()
+            rc = lib.fh_dynamics_set_load_dev(self._h, _ptr(ft), _ffi.fp(lf), cnt)
+        else:
+            fa = None if f is None else _ffi.as_f64(f).reshape(-1)
+            rc = lib.fh_dynamics_set_load(self._h, _ffi.fp(fa), _ffi.fp(lf), cnt)
+        self.engine._check(rc)
+
+    # ---- state
+    def set_state(self, u, v=None):
+        """u_0 (with the Dirichlet values) and v_0 (None: zero): numpy arrays or device tensors; time and step count return to 0"""
+        h = self._handle()
+        n = self._n()
+        lib = self.engine._lib
+        for name, x in (("u", u), ("v", v)):
+            if x is not None and (x.numel() if _is_torch(x) else np.size(x)) != n:
+                raise ValueError(f"{name} must hold {n} entries")
+        if _is_torch(u) or _is_torch(v):
+            import torch
+
+            dev = f"cuda:{self.engine.device}"
+            ut = None if u is None else torch.as_tensor(u, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+            vt = None if v is None else torch.as_tensor(v, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+            rc = lib.fh_dynamics_set_state_dev(h, _ptr(ut), _ptr(vt))
+        else:
+            ua = None if u is None else _ffi.as_f64(u).reshape(-1)
+            va = None if v is None else _ffi.as_f64(v).reshape(-1)
+            rc = lib.fh_dynamics_set_state(h, _ffi.fp(ua), _ffi.fp(va))
+        self.engine._check(rc)
+        return self
+
+    def step(self, num_steps, record_every=0):
+        """num_steps steps; a record after every record_every steps and after the last (0: the last only).  Raises the Newton errors of
+        MatrixFreeNewton for a failed implicit step, SingularJacobianError, and DynamicsError for everything else; each carries steps_done."""
+        h = self._handle()
+        if self._mg is not None:
+            self._mg._bind(self._nodes, self._rho)
+        num_steps, record_every = int(num_steps), int(record_every)
+        rows = 1 + (num_steps // record_every if record_every else 0)
+        rec = np.zeros((rows, 4))
+        done = C.c_uint64(0)
+        stats = np.zeros(5, dtype=np.uint64)
+        rc = self.engine._lib.fh_dynamics_step(h, num_steps, record_every, _ffi.fp(rec), C.byref(done), _ffi.up(stats))
+        k = int(stats[4])
+        out = DynamicsRecord(rec[:k, 3].copy(), rec[:k, 0].copy(), rec[:k, 1].copy(), rec[:k, 2].copy(), int(done.value), tuple(int(x) for x in stats))
+        if rc == _ffi.FH_OK:
+            return out
+        msg = self.engine.last_error()
+        newton = {_ffi.FH_NEWTON_MAX_ITERATIONS: MaximumIterationsReached, _ffi.FH_NEWTON_JACOBIAN_ERROR: JacobianError,
+                  _ffi.FH_NEWTON_LINE_SEARCH_FAILED: LineSearchError}
+        if rc in newton:
+            err = newton[rc](rc, msg, NewtonResult(int(stats[2]), int(stats[1]), int(stats[3]), 0, float("nan"), float("nan"), 0.0))
+            err.steps_done, err.record = int(done.value), out
+            raise err
+        if rc == _ffi.FH_SINGULAR_JACOBIAN:
+            err = SingularJacobianError(msg, -1)
+            err.steps_done, err.record = int(done.value), out
+            raise err
+        err = DynamicsError(rc, msg, int(done.value))
+        err.record = out
+        raise err
+
+    def state(self, device=False):
+        """(u, v, a, time, step): numpy arrays, or device tensors with device=True"""
+        h = self._handle()
+        n = self._n()
+        t, k = C.c_double(0.0), C.c_uint64(0)
+        if device:
+            import torch
+
+            u, v, a = (torch.empty(n, dtype=torch.float64, device=f"cuda:{self.engine.device}") for _ in range(3))
+            rc = self.engine._lib.fh_dynamics_state_dev(h, _ptr(u), _ptr(v), _ptr(a), C.byref(t), C.byref(k))
+        else:
+            u, v, a = np.zeros(n), np.zeros(n), np.zeros(n)
+            rc = self.engine._lib.fh_dynamics_state(h, _ffi.fp(u), _ffi.fp(v), _ffi.fp(a), C.byref(t), C.byref(k))
+        self.engine._check(rc)
+        return u, v, a, t.value, int(k.value)
+
+    def stable_dt(self, iterations=30):
+        """(omega_max, dt_crit = 2 / omega_max) from `iterations` steps of the power iteration on m^-1 T(u); the estimate of omega_max is a
+        Rayleigh quotient and never too large, so dt_crit errs on the large side: apply a safety factor"""
+        h = self._handle()
+        om, dtc = C.c_double(0.0), C.c_double(0.0)
+        self.engine._check(self.engine._lib.fh_dynamics_stable_dt(h, int(iterations), C.byref(om), C.byref(dtc)))
+        return om.value, dtc.value
+
+
+class CentralDifference(TimeIntegrator):
+    """velocity-Verlet central differences with the row-sum lumped mass; the element kinds whose lumped mass has an entry that is not
+    positive (Tet10, Tri6) are refused by step (FH_UNSUPPORTED)"""
+
+    scheme = _ffi.DYN_CENTRAL_DIFFERENCE
+
+
+class _Implicit(TimeIntegrator):
+    def with_newton(self, settings=None, line_search=None, linear_rel_tol=1e-8, linear_max_iter=0):
+        """the Newton solve of every step: NewtonSettings, NoLineSearch / BacktrackingLineSearch and the inner PCG's criterion; returns self"""
+        self._settings = settings or NewtonSettings()
+        self._line_search = line_search or BacktrackingLineSearch()
+        self._linear_rel_tol, self._linear_max_iter = float(linear_rel_tol), int(linear_max_iter)
+        self._drop()   # (the settings live in the handle: the state is set again afterwards)
+        return self
+
+    def with_multigrid(self, mg):
+        """a GeometricMultigrid over this assembler: the steps' PCG then takes PRECOND_MULTIGRID; returns self"""
+        self._mg = mg
+        self._drop()
+        return self
+
+
+class Newmark(_Implicit):
+    """Newmark(beta, gamma); the default (1/4, 1/2) is the average-acceleration (trapezoidal) rule"""
+
+    scheme = _ffi.DYN_NEWMARK
+
+    def __init__(self, element_assembler, density, dt, beta=0.25, gamma=0.5):
+        super().__init__(element_assembler, density, dt)
+        self._beta, self._gamma = float(beta), float(gamma)
+
+
+class BackwardEuler(_Implicit):
+    """backward Euler on positions: alpha = 1, beta = dt^2, u_ref = u_n + dt v_n"""
+
+    scheme = _ffi.DYN_BACKWARD_EULER

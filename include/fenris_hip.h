@@ -62,7 +62,9 @@ enum {
     /* the eigensolver (fh_eigs_lowest): max_iter exhausted before every pair met the criterion; a Cholesky factor or the dense
      * Rayleigh-Ritz problem met a pivot that is not positive (also fh_dense_generalized_eigh on its own) */
     FH_EIG_MAX_ITERATIONS = 13,
-    FH_EIG_BREAKDOWN = 14
+    FH_EIG_BREAKDOWN = 14,
+    /* time integration (fh_dynamics_step): the kinetic or the stored energy of a recorded state is not finite */
+    FH_DYNAMICS_NONFINITE = 15
 };
 
 /* element kinds: Quad4d2Element (src/element/quadrilateral.rs:70-142), Hex8Element
@@ -779,6 +781,78 @@ int fh_eigs_lowest_dev(fh_ctx*, uint32_t m, double shift, int preconditioner, do
 int fh_eigs_lowest(fh_ctx*, uint32_t m, double shift, int preconditioner, double tol, uint64_t max_iter, int use_guess, double* X, double* theta,
                    double* residual_norms, uint64_t* stats);
 int fh_eigs_profile(fh_ctx*, double* seconds);
+/* ---- time integration on the device:  M a + r(u) = lf_n f  with r the context's residual (FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN,
+ * FH_STVK; mass operators and FH_TENSOR: FH_UNSUPPORTED), M the mass of fh_set_mass_density (none: FH_INVALID_STATE) and
+ * lf_n = load_factor[min(n, count - 1)] (null: 1), n the global index of the step being computed (the state of fh_dynamics_set_state is
+ * step 0).  The Dirichlet nodes of fh_set_operator_dirichlet_nodes are held at the u of fh_dynamics_set_state with v = a = 0; those entries
+ * of u come back bit for bit.  The handle uses the context's u as u_n: fh_set_u* holds the last state afterwards, as after fh_newton_solve.
+ *
+ * FH_DYN_CENTRAL_DIFFERENCE, in velocity-Verlet form with the row-sum lumped mass m = M 1 (no Dirichlet rows take part in forming it):
+ *     a_0 = (lf_0 f - r(u_0)) / m;   v_h = v_n + dt/2 a_n;   u_{n+1} = u_n + dt v_h;   a_{n+1} = (lf_{n+1} f - r(u_{n+1})) / m;
+ *     v_{n+1} = v_h + dt/2 a_{n+1}.
+ *   An entry of m on a free dof that is not positive (decided from its value: the vertex rows of Tet10 and Tri6, for example) gives
+ *   FH_UNSUPPORTED from fh_dynamics_step and fh_dynamics_stable_dt; the message names the dof.  On Hex8, Tet4, Quad4 and Tri3 without a
+ *   rule-set table a step is the residual's element pass over the tiles and ONE node pass that sums the node's partials and does the whole
+ *   state update -- acceleration, second kick, and either the stores of a record or the next step's first kick and drift into the context's
+ *   u; lf is read from a device array indexed by the step.  Between records the loop only enqueues kernels: the kernels' status word and
+ *   the kinetic energy are read at records and at the end of the call, where FH_SINGULAR_JACOBIAN is reported.  A step that is recorded
+ *   stores v, a and the energy partials and the following step opens with a kick-and-drift launch of its own (the record reads u_{n+1});
+ *   kick, drift and acceleration are one device function each with explicit fma, so a run gives the same bits however it is cut into calls
+ *   and records.  On every other route (Hex27, Quad9, the quadratic simplices, rule-set tables) the residual is summed first (element
+ *   vectors, ordered node sums; the host waits once per step there) and k_dynamics_update does the same arithmetic.
+ * FH_DYN_NEWMARK(newmark_beta, newmark_gamma) and FH_DYN_BACKWARD_EULER: each step is one Newton solve as fh_newton_solve_dev runs it, with
+ *     alpha = 1, beta = newmark_beta dt^2 (backward Euler: dt^2), the load lf_{n+1} f,
+ *     u_ref = u_n + dt v_n + dt^2 (1/2 - newmark_beta) a_n (backward Euler: u_n + dt v_n), the guess u_ref with the Dirichlet entries of u_n;
+ *     Newmark: a_{n+1} = (u_{n+1} - u_ref) / (newmark_beta dt^2), v_{n+1} = v_n + dt ((1 - gamma) a_n + gamma a_{n+1});
+ *     backward Euler: v_{n+1} = (u_{n+1} - u_n) / dt (a_{n+1} = (v_{n+1} - v_n) / dt is kept for fh_dynamics_state only).
+ *   Newmark's a_0 solves M a_0 = lf_0 f - r(u_0) on the free dofs by fh_cg_solve_shifted_tangent_dev(1, 0, ...) at linear_rel_tol (Jacobi
+ *   where the settings ask for the hierarchy).  A Newton failure ends the call with that Newton code (FH_NEWTON_*); *steps_done counts the
+ *   steps completed before it and the state is that of the last completed step.
+ * fh_dynamics_create: FH_BAD_ARGUMENT for an unknown scheme, dt <= 0, newmark_beta <= 0, settings that are not finite, an unknown line
+ *   search or preconditioner; the context must have its mesh, operator, table and density.  fh_set_mesh* on the context invalidates the
+ *   handle (every later call: FH_INVALID_STATE); destroy the handle before the context.  Vertices, operator data, table, element mask,
+ *   density and Dirichlet nodes may change between calls: m, a_n and the caches are formed again, keyed on the context's generation counters
+ *   (so is a_n after fh_set_u* or fh_dynamics_set_load).
+ * fh_dynamics_set_state: u and v (S N doubles each, null: zero); the step counter and the time return to 0.
+ * fh_dynamics_set_load: f (S N doubles, null: no load) and load_factor (host, count >= 1 entries, null: 1).
+ * fh_dynamics_step: num_steps steps.  A record is taken after every record_every steps of the call and after its last step (record_every
+ *   == 0: the last step only); records (host, may be null) receives one row of 4 per record: [0] the kinetic energy 1/2 v^T M v (lumped m
+ *   for central differences, the consistent M for the implicit schemes), [1] the stored energy (fh_assemble_scalar at u), [2] lf f . u,
+ *   [3] the time.  Every sum is ordered: no floating-point atomics, a run repeats bit for bit.  A kinetic or stored energy that is not
+ *   finite (a NeoHookean point with det F <= 0 makes it so) returns FH_DYNAMICS_NONFINITE; for central differences *steps_done is then the
+ *   last clean record of the call (as for FH_SINGULAR_JACOBIAN) and the state is not to be used.  A state whose residual is not finite when
+ *   a_n has to be formed (the first call after fh_dynamics_set_state) returns the same code with *steps_done == 0, under every scheme.
+ *   stats (may be null): [0] steps done in this call, [1] residual evaluations, [2] Newton iterations summed, [3] PCG iterations summed,
+ *   [4] records written.
+ * fh_dynamics_state: u, v, a (S N each, any may be null), the time and the step count; a is a_n of the state as it stands (a_0 before the
+ *   first step: it is formed here when asked for, with the errors of fh_dynamics_step).  The _dev forms take device arrays for u, v, a, f.
+ * fh_dynamics_stable_dt: `iterations` steps of the power iteration x <- m^-1 T(u) x on the free dofs from column 0 of fh_eigs_lowest's
+ *   fill (X(dof, 0)), the iterates normalised in the m-norm; omega_max^2 is the last Rayleigh quotient, dt_crit = 2 / omega_max.  A Rayleigh
+ *   quotient never exceeds the largest eigenvalue, so dt_crit errs on the LARGE side: apply a safety factor (0.9 or less) before stepping. */
+typedef struct fh_dynamics fh_dynamics;
+enum { FH_DYN_CENTRAL_DIFFERENCE = 0, FH_DYN_BACKWARD_EULER = 1, FH_DYN_NEWMARK = 2 };
+typedef struct {
+    int scheme;
+    double dt;
+    double newmark_beta, newmark_gamma;   /* FH_DYN_NEWMARK only */
+    /* the implicit schemes: fh_newton_solve's arguments */
+    double newton_tolerance;
+    uint64_t newton_max_iterations;
+    int line_search;
+    int preconditioner;
+    double linear_rel_tol;
+    uint64_t linear_max_iter;
+} fh_dynamics_settings;
+int fh_dynamics_create(fh_ctx*, const fh_dynamics_settings* settings, fh_dynamics** out);
+void fh_dynamics_destroy(fh_dynamics*);
+int fh_dynamics_set_state(fh_dynamics*, const double* u, const double* v);
+int fh_dynamics_set_state_dev(fh_dynamics*, const double* u_dev, const double* v_dev);
+int fh_dynamics_set_load(fh_dynamics*, const double* f, const double* load_factor, uint64_t count);
+int fh_dynamics_set_load_dev(fh_dynamics*, const double* f_dev, const double* load_factor, uint64_t count);
+int fh_dynamics_step(fh_dynamics*, uint64_t num_steps, uint64_t record_every, double* records, uint64_t* steps_done, uint64_t* stats);
+int fh_dynamics_state(fh_dynamics*, double* u, double* v, double* a, double* time, uint64_t* step);
+int fh_dynamics_state_dev(fh_dynamics*, double* u_dev, double* v_dev, double* a_dev, double* time, uint64_t* step);
+int fh_dynamics_stable_dt(fh_dynamics*, uint32_t iterations, double* omega_max, double* dt_crit);
 /* Geometric multigrid for the matrix-free solvers (FH_PRECOND_MULTIGRID of fh_cg_solve_matrix_free, fh_cg_solve_tangent,
  * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity, Jacobi or FH_PRECOND_AMG).  Every level is an
  * ordinary context with its own mesh, operator (Laplace, LinearElastic, NeoHookean or StVK), quadrature, data, density and
