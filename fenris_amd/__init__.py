@@ -23,7 +23,8 @@ from .degree import (coarsen_degree, coarsen_degree_with_transfer, degree_hierar
                      elevate_degree_with_transfer, matching_vertex_permutation)
 from .interpolate import FixedInterpolator, SpatiallyIndexed, ValuesOrGradients
 from .multigrid import GeometricMultigrid
-from .dynamics import BackwardEuler, CentralDifference, DynamicsError, DynamicsRecord, Newmark, TimeIntegrator
+from .dynamics import (BackwardEuler, CentralDifference, DynamicsError, DynamicsRecord, FirstOrderIntegrator, FirstOrderRecord, ForwardEuler, Newmark,
+                       RungeKuttaLegendre, ThetaMethod, TimeIntegrator)
 from .eigen import EigenResult, EigenSolveError, MatrixFreeEigensolver
 from .recovery import Recovery
 from .refinement import (Transfer, permute_transfer, refine_uniformly, refine_uniformly_repeat, refine_uniformly_repeat_with_transfers,

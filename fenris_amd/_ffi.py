@@ -23,6 +23,7 @@ NEWTON_NO_LINE_SEARCH, NEWTON_BACKTRACKING = 0, 1
 FH_EIG_MAX_ITERATIONS, FH_EIG_BREAKDOWN = 13, 14
 FH_DYNAMICS_NONFINITE = 15
 DYN_CENTRAL_DIFFERENCE, DYN_BACKWARD_EULER, DYN_NEWMARK = 0, 1, 2
+FO_RKL, FO_THETA = 0, 1
 EIG_MAX_BLOCK = 32
 PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, PRECOND_AMG = 0, 1, 2, 3
 AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER = 0, 1, 2
@@ -45,6 +46,14 @@ class DynamicsSettings(C.Structure):
     """fh_dynamics_settings"""
 
     _fields_ = [("scheme", C.c_int), ("dt", C.c_double), ("newmark_beta", C.c_double), ("newmark_gamma", C.c_double),
+                ("newton_tolerance", C.c_double), ("newton_max_iterations", C.c_uint64), ("line_search", C.c_int), ("preconditioner", C.c_int),
+                ("linear_rel_tol", C.c_double), ("linear_max_iter", C.c_uint64)]
+
+
+class FirstOrderSettings(C.Structure):
+    """fh_first_order_settings"""
+
+    _fields_ = [("scheme", C.c_int), ("dt", C.c_double), ("stages", C.c_uint32), ("theta", C.c_double),
                 ("newton_tolerance", C.c_double), ("newton_max_iterations", C.c_uint64), ("line_search", C.c_int), ("preconditioner", C.c_int),
                 ("linear_rel_tol", C.c_double), ("linear_max_iter", C.c_uint64)]
 
@@ -167,6 +176,7 @@ _SIGS = {
     "fh_newton_solve_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_int,
                                       C.c_int, C.c_double, C.c_uint64, u64p, f64p]),
     "fh_dynamics_create": (C.c_int, [C.c_void_p, C.POINTER(DynamicsSettings), C.POINTER(C.c_void_p)]),
+    "fh_first_order_create": (C.c_int, [C.c_void_p, C.POINTER(FirstOrderSettings), C.POINTER(C.c_void_p)]),
     "fh_dynamics_destroy": (None, [C.c_void_p]),
     "fh_dynamics_set_state": (C.c_int, [C.c_void_p, f64p, f64p]),
     "fh_dynamics_set_state_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -22,6 +22,30 @@ static __global__ void __launch_bounds__(256) k_dynamics_update(int n, int S, co
     }
 }
 
+// one stage of a Runge-Kutta-Legendre step, or the rate alone (fo_dof, dynamics_step.hpp), on a residual that is already summed: the routes
+// off the tiles, as k_dynamics_update serves them
+static __global__ void __launch_bounds__(256) k_first_order_update(int n, int S, const double* r, const FoStage p) {
+    __shared__ double red[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    double q = 0.0;
+    if (i < n) q = fo_dof(p, (size_t)i, p.dmask && p.dmask[i / S], dyn_load_factor(p), r[i]);
+    if (p.flags & FO_STORE) {
+        const double tot = block_sum_256(q, red);
+        if (threadIdx.x == 0) p.partial[blockIdx.x] = tot;
+    }
+}
+
+// the load of a theta step: g = (lf_{n+1} + c lf_n) f - c r(u_n), c = (1 - theta) / theta (c == 0: r is not read and may be null)
+static __global__ void __launch_bounds__(256) k_theta_load(int n, const double* f, const double* lf, unsigned long long lf_count,
+                                                           unsigned long long step, double c, const double* r, double* g) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double l0 = lf ? lf[step < lf_count ? step : lf_count - 1] : 1.0;
+    const double l1 = lf ? lf[step + 1 < lf_count ? step + 1 : lf_count - 1] : 1.0;
+    const double lfv = fma(c, l0, l1) * (f ? f[i] : 0.0);
+    g[i] = c != 0.0 ? fma(-c, r[i], lfv) : lfv;
+}
+
 // Newmark predictor: u_ref = u + dt v + dt^2 (1/2 - beta) a (backward Euler: c2 = 0), and the Newton guess: the context's u takes u_ref on
 // the free dofs and keeps its Dirichlet entries; u_prev keeps u_n
 static __global__ void __launch_bounds__(256) k_newmark_predict(int n, int S, double dt, double c2, const unsigned char* dmask, double* u,

@@ -1,6 +1,7 @@
 // Time integration (engine_dynamics.hip): the arithmetic of one central-difference launch per dof -- the acceleration, the kick and the
 // drift -- as the fused node pass over the tile partials (k_dynamics_from_partials, vector_tiles.hip) and the stand-alone kernel
-// (k_dynamics_update, dynamics_kernels.hpp) share it.
+// (k_dynamics_update, dynamics_kernels.hpp) share it; and the same for one stage of a first-order Runge-Kutta-Legendre step (fo_dof:
+// k_first_order_from_partials, k_first_order_update).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,7 +27,8 @@ struct DynStep {
     int flags;
 };
 
-__device__ __forceinline__ double dyn_load_factor(const DynStep& p) {
+template <class P>   // (DynStep, or FoStage below)
+__device__ __forceinline__ double dyn_load_factor(const P& p) {
     return p.lf ? p.lf[p.step < p.lf_count ? p.step : p.lf_count - 1] : 1.0;
 }
 // the three pieces every route shares: the same bits however a run is cut into calls and records
@@ -62,6 +64,45 @@ __device__ __forceinline__ double dyn_dof(const DynStep& p, size_t i, bool fixed
         p.u[i] = dyn_drift(p.u[i], vh, p.dt);
     }
     return ke;
+}
+
+// ---- first order: M du/dt + r(u) = lf f.  One launch is one stage of a Runge-Kutta-Legendre step of s stages (s = 1: forward Euler), or
+// the rate L(u) = (lf f - r(u)) / m alone
+enum {
+    FO_FIRST = 1,  // stage 1: Y_1 = fma(mut_dt, L(Y_0), Y_0) -- prev is not read
+    FO_KEEP = 2,   // a later stage of the step reads Y_{j-1}: prev takes the u this stage read
+    FO_STORE = 4,  // the workgroup leaves its partial of sum m y^2 over all its dofs (the last stage of a recorded step)
+    FO_RATE = 8    // no stage: rate takes L(u) (Dirichlet dofs: 0) and u stays
+};
+
+struct FoStage {
+    double mut_dt, mu, nu;      // mu_j w1 dt, mu_j, nu_j (stage 1: w1 dt; mu and nu are not read)
+    const double* f;            // load, S N (null: zero)
+    const double* lf;           // load factors on the device (null: 1) ...
+    unsigned long long lf_count, step;   // ... lf[min(step, lf_count - 1)], step the index of the state the step starts from
+    const double* m;            // row-sum lumped mass, S N
+    const unsigned char* dmask; // N membership flags of the Dirichlet nodes (null: none)
+    double *u, *prev;           // S N each: the context's u holds Y_{j-1} and takes Y_j; prev holds Y_{j-2}
+    double* rate;               // FO_RATE
+    double* partial;            // FO_STORE: one partial per workgroup
+    int flags;
+};
+
+// one dof of a stage: returns the dof's m y^2 (FO_STORE, else 0); a Dirichlet dof keeps its u
+__device__ __forceinline__ double fo_dof(const FoStage& p, size_t i, bool fixed, double lf, double r) {
+    if (p.flags & FO_RATE) {
+        p.rate[i] = fixed ? 0.0 : dyn_accel(lf, p.f ? p.f[i] : 0.0, r, p.m[i]);
+        return 0.0;
+    }
+    const double m = p.m[i], u = p.u[i];
+    double y = u;
+    if (!fixed) {
+        const double w = dyn_accel(lf, p.f ? p.f[i] : 0.0, r, m);
+        y = (p.flags & FO_FIRST) ? fma(p.mut_dt, w, u) : fma(p.mut_dt, w, fma(p.mu, u, p.nu * p.prev[i]));
+        if (p.flags & FO_KEEP) p.prev[i] = u;
+        p.u[i] = y;
+    }
+    return (p.flags & FO_STORE) ? m * (y * y) : 0.0;
 }
 
 }  // namespace fenris_hip

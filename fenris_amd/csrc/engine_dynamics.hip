@@ -1,6 +1,8 @@
 // Time integration on the device: M a + r(u) = lf f with the context's residual r and the mass of fh_set_mass_density, by central
 // differences (velocity-Verlet form, row-sum lumped mass), Newmark(beta, gamma) or backward Euler (one Newton solve per step: newton_run
-// of engine_newton.hip on alpha = 1, beta = newmark_beta dt^2); the handle, the step loops, the records and the C ABI
+// of engine_newton.hip on alpha = 1, beta = newmark_beta dt^2); and the first-order problem M du/dt + r(u) = lf f on the same handle, by
+// Runge-Kutta-Legendre super-steps (one stage: forward Euler; lumped mass) or the theta method (newton_run on alpha = 1, beta = theta dt);
+// the handle, the step loops, the records and the C ABI
 #include "engine_internal.hpp"
 
 #include "dynamics_kernels.hpp"
@@ -9,15 +11,19 @@
 
 struct fh_dynamics {
     fh_ctx* c = nullptr;
-    fh_dynamics_settings s{};
+    fh_dynamics_settings s{};          // (a first-order handle keeps its dt and Newton arguments here; s.scheme is not read then)
+    int fo_scheme = -1;                // FH_FO_RKL or FH_FO_THETA; -1: the second-order problem of s.scheme
+    double theta = 1.0;
+    uint32_t stages = 1;
+    bool fresh = true;                 // first order: no step call has checked the state since fh_dynamics_set_state
     unsigned long long topo_gen = 0;   // the context's mesh at creation: fh_set_mesh* invalidates the handle
     int n = 0;                         // S N at creation
     DevBuf<double> v, a, m, f, lf, r, rpart, kep, u_ref, u_prev, work, load;
     std::vector<double> h_lf;
     bool has_f = false;
     uint64_t step = 0;                 // steps taken since fh_dynamics_set_state
-    // what m (the first five) and a_n (all six) were formed for: struct_gen (operator, table, mask), topo_gen, geom_gen, density_gen,
-    // dirichlet_gen, and the u_gen this handle left behind
+    // what m (the first five) and a_n (all six; first order: the rate, kept in v) were formed for: struct_gen (operator, table, mask),
+    // topo_gen, geom_gen, density_gen, dirichlet_gen, and the u_gen this handle left behind
     unsigned long long m_key[5] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
     unsigned long long a_key[6] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
     bool load_changed = true;
@@ -27,7 +33,9 @@ namespace {
 
 const char* WHO = "fh_dynamics_step";
 
-bool explicit_scheme(const fh_dynamics* d) { return d->s.scheme == FH_DYN_CENTRAL_DIFFERENCE; }
+bool first_order(const fh_dynamics* d) { return d->fo_scheme >= 0; }
+// the schemes on the row-sum lumped mass
+bool explicit_scheme(const fh_dynamics* d) { return first_order(d) ? d->fo_scheme == FH_FO_RKL : d->s.scheme == FH_DYN_CENTRAL_DIFFERENCE; }
 const unsigned char* dmask_of(const fh_ctx* c) { return c->mf_num_dirichlet ? c->mf_dmask.p : nullptr; }
 int blocks_of(int n) { return std::max(1, (n + 255) / 256); }
 
@@ -107,7 +115,7 @@ int ensure_lumped(fh_dynamics* d, const char* who) {
     for (int i = 0; i < n; ++i)
         if (!hm[(size_t)(i / S)] && !(h[(size_t)i] > 0.0))
             return c->fail(FH_UNSUPPORTED, std::string(who) + ": the row-sum lumped mass of dof " + std::to_string(i) + " (node " + std::to_string(i / S) +
-                                               ") is " + std::to_string(h[(size_t)i]) + ", not positive: central differences need another lumping on this element kind");
+                                               ") is " + std::to_string(h[(size_t)i]) + ", not positive: the explicit schemes need another lumping on this element kind");
     std::copy(k, k + 5, d->m_key);
     return FH_OK;
 }
@@ -321,8 +329,202 @@ int implicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, do
     return FH_OK;
 }
 
+// ---- first order
+FoStage stage_args(fh_dynamics* d, int flags, uint64_t step, double mut_dt, double mu, double nu) {
+    fh_ctx* c = d->c;
+    FoStage p;
+    p.mut_dt = mut_dt;
+    p.mu = mu;
+    p.nu = nu;
+    p.f = d->has_f ? d->f.p : nullptr;
+    p.lf = d->h_lf.empty() ? nullptr : d->lf.p;
+    p.lf_count = d->h_lf.size();
+    p.step = step;
+    p.m = d->m.p;
+    p.dmask = dmask_of(c);
+    p.u = c->u.p;
+    p.prev = d->u_prev.p;
+    p.rate = d->v.p;
+    p.partial = d->kep.p;
+    p.flags = flags;
+    return p;
+}
+
+// one stage (or the rate, FO_RATE) on the residual at the context's u.  *count: the partials a FO_STORE launch leaves.  On the tiles
+// nothing is waited for.
+int first_order_launch(fh_dynamics* d, const FoStage& p, uint64_t* stats, int* count) {
+    fh_ctx* c = d->c;
+    const int S = c->S(), n = d->n;
+    bool tiles;
+    int rc = residual_tiles(d, &tiles);
+    if (rc) return rc;
+    ++stats[1];
+    if (tiles) {
+        HIP_TRY(c, vector_tiles_first_order_node_pass(c->stream, S, (int)c->N, c->vt.v, d->rpart.p, p));
+        c->last_kernel = "k_element_pass_tiled + k_first_order_from_partials";
+        if (count) *count = vector_tiles_operator_partials((int)c->N);
+    } else {
+        rc = residual_summed(d);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_first_order_update, dim3(blocks_of(n)), dim3(256), 0, c->stream, n, S, d->r.p, p);
+        HIP_TRY(c, hipGetLastError());
+        c->last_kernel = "k_residual_elements + k_vector_from_elements_soa + k_first_order_update";
+        if (count) *count = blocks_of(n);
+    }
+    if (!(p.flags & FO_RATE)) ++c->u_gen;
+    return FH_OK;
+}
+
+// the right-hand side lf_n f - r(u_n) of the state as it stands, refused when it is not finite, and with `solve` the rate du/dt into v
+// (RKL: L(u_n), which is that right-hand side over m; theta: M w = lf_n f - r(u_n) on the free dofs by the CG of Newmark's a_0), when
+// anything it depends on has changed since it was formed
+int ensure_rate(fh_dynamics* d, bool solve, uint64_t* stats) {
+    fh_ctx* c = d->c;
+    unsigned long long k[6];
+    key_now(c, k);
+    if (std::equal(k, k + 6, d->a_key) && !d->load_changed) return FH_OK;
+    const int n = d->n, S = c->S(), g = blocks_of(n);
+    const double* rhs = d->v.p;
+    int rc;
+    if (d->fo_scheme == FH_FO_RKL) {
+        rc = reset_status(c);
+        if (rc) return rc;
+        rc = first_order_launch(d, stage_args(d, FO_RATE, d->step, 0.0, 0.0, 0.0), stats, nullptr);
+        if (rc) return rc;
+    } else {
+        rc = residual_summed(d);
+        if (rc) return rc;
+        ++stats[1];
+        hipLaunchKernelGGL(k_dynamics_rhs, dim3(g), dim3(256), 0, c->stream, n, S, d->has_f ? d->f.p : nullptr, d->h_lf.empty() ? nullptr : d->lf.p,
+                           (unsigned long long)d->h_lf.size(), (unsigned long long)d->step, dmask_of(c), d->r.p, d->work.p);
+        HIP_TRY(c, hipGetLastError());
+        rhs = d->work.p;
+    }
+    double b2 = 0.0;   // (an inverted NeoHookean state makes r NaN: reported as such, not as a breakdown of the PCG or of Newton)
+    rc = dot(d, rhs, rhs, &b2);
+    if (rc) return rc;
+    if (!std::isfinite(b2)) return c->fail(FH_DYNAMICS_NONFINITE, std::string(WHO) + ": the residual of the initial state is not finite");
+    if (d->fo_scheme == FH_FO_RKL) {
+        rc = read_status(c, nullptr);
+        if (rc) return rc;
+    }
+    if (d->fo_scheme == FH_FO_THETA) {
+        if (!solve) return FH_OK;   // (a step needs the check alone)
+        HIP_TRY(c, hipMemsetAsync(d->v.p, 0, sizeof(double) * (size_t)n, c->stream));
+        uint64_t it = 0;
+        const int pre = d->s.preconditioner == FH_PRECOND_MULTIGRID ? (int)FH_PRECOND_JACOBI : d->s.preconditioner;   // (M alone needs no hierarchy)
+        rc = cg_solve_free_dev(c, WHO, FH_STVK, d->work.p, d->v.p, pre, d->s.linear_rel_tol, d->s.linear_max_iter, &it, 1.0, 0.0);
+        stats[3] += it;
+        if (rc) return rc;
+    }
+    key_now(c, k);
+    std::copy(k, k + 6, d->a_key);
+    d->load_changed = false;
+    return FH_OK;
+}
+
+// the end of a recorded first-order step: row[0] holds u^T B u; *done and the step counter move only when the record is clean
+int first_order_record(fh_dynamics* d, uint64_t g_step, double* row, double* records, uint64_t* stats) {
+    fh_ctx* c = d->c;
+    row[0] *= 0.5;
+    int rc = record_rest(d, g_step, row);
+    if (rc) return rc;
+    if (!std::isfinite(row[0]) || !std::isfinite(row[1]))
+        return c->fail(FH_DYNAMICS_NONFINITE, std::string(WHO) + ": 1/2 u^T B u or the stored energy after step " + std::to_string(g_step) + " is not finite");
+    if (records) std::copy(row, row + 4, records + 4 * stats[4]);
+    ++stats[4];
+    return FH_OK;
+}
+
+// Runge-Kutta-Legendre: s stages per step, each the residual's element pass and one node pass; the loop only enqueues between records
+int first_order_explicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, double* records, uint64_t* done, uint64_t* stats) {
+    fh_ctx* c = d->c;
+    const uint64_t s0 = d->step;
+    const uint32_t s = d->stages;
+    const double w1dt = 2.0 / ((double)s * (double)s + (double)s) * d->s.dt;
+    int rc = reset_status(c);
+    if (rc) return rc;
+    for (uint64_t j = 0; j < num_steps; ++j) {
+        const bool last = j + 1 == num_steps;
+        const bool rec = last || (record_every && (j + 1) % record_every == 0);
+        int count = 0;
+        for (uint32_t k = 1; k <= s; ++k) {
+            const double mu = (2.0 * k - 1.0) / k, nu = (1.0 - k) / k;
+            const int flags = (k == 1 ? FO_FIRST : 0) | (k < s ? FO_KEEP : 0) | (k == s && rec ? FO_STORE : 0);
+            rc = first_order_launch(d, stage_args(d, flags, s0 + j, k == 1 ? w1dt : mu * w1dt, mu, nu), stats, &count);
+            if (rc) return rc;
+        }
+        if (!rec) continue;
+        double row[4] = {0.0, 0.0, 0.0, 0.0};
+        rc = sum_blocks(c, d->kep.p, count, &row[0]);   // the host waits here: once per record
+        if (rc) return rc;
+        rc = read_status(c, nullptr);
+        if (rc) return rc;
+        rc = first_order_record(d, s0 + j + 1, row, records, stats);
+        if (rc) return rc;
+        *done = j + 1;
+        d->step = s0 + j + 1;
+        if (!last) {
+            rc = reset_status(c);
+            if (rc) return rc;
+        }
+    }
+    return FH_OK;
+}
+
+// theta method: one newton_run per step on alpha = 1, beta = theta dt, u_ref = u_n, from the guess u_n
+int first_order_theta_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, double* records, uint64_t* done, uint64_t* stats) {
+    fh_ctx* c = d->c;
+    const int n = d->n, g = blocks_of(n);
+    const double dt = d->s.dt, cw = (1.0 - d->theta) / d->theta;
+    for (uint64_t j = 0; j < num_steps; ++j) {
+        const uint64_t g_step = d->step + 1;
+        HIP_TRY(c, hipMemcpyAsync(d->u_prev.p, c->u.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+        int rc;
+        if (cw != 0.0) {
+            rc = residual_summed(d);
+            if (rc) return rc;
+            ++stats[1];
+        }
+        const double* load = nullptr;
+        if (d->has_f || cw != 0.0) {
+            hipLaunchKernelGGL(k_theta_load, dim3(g), dim3(256), 0, c->stream, n, d->has_f ? d->f.p : nullptr, d->h_lf.empty() ? nullptr : d->lf.p,
+                               (unsigned long long)d->h_lf.size(), (unsigned long long)d->step, cw, d->r.p, d->load.p);
+            HIP_TRY(c, hipGetLastError());
+            load = d->load.p;
+        }
+        uint64_t st[4] = {0, 0, 0, 0};
+        double nm[3] = {0.0, 0.0, 0.0};
+        rc = newton_run(c, 1.0, d->theta * dt, load, d->u_prev.p, d->s.newton_tolerance, d->s.newton_max_iterations, d->s.line_search,
+                        d->s.preconditioner, d->s.linear_rel_tol, d->s.linear_max_iter, st, nm);
+        stats[1] += st[1];
+        stats[2] += st[0];
+        stats[3] += st[2];
+        if (rc) {   // the state stays that of the last completed step
+            const std::string msg = c->err;
+            HIP_TRY(c, hipMemcpyAsync(c->u.p, d->u_prev.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            ++c->u_gen;
+            return c->fail(rc, msg);
+        }
+        d->step = g_step;
+        *done = j + 1;
+        const bool last = j + 1 == num_steps;
+        if (!(last || (record_every && (j + 1) % record_every == 0))) continue;
+        double row[4] = {0.0, 0.0, 0.0, 0.0};
+        rc = mass_full(c, c->u.p, nullptr, d->work.p);   // u^T M u with the consistent mass
+        if (rc) return rc;
+        rc = dot(d, c->u.p, d->work.p, &row[0]);
+        if (rc) return rc;
+        rc = first_order_record(d, g_step, row, records, stats);
+        if (rc) return rc;
+    }
+    return FH_OK;
+}
+
 int set_state_common(fh_dynamics* d, const double* u, const double* v, hipMemcpyKind kind) {
     fh_ctx* c = d->c;
+    if (first_order(d) && v) return c->fail(FH_BAD_ARGUMENT, "fh_dynamics_set_state: the state of a first-order handle is u alone: v must be null");
     int rc = dyn_ready(d, "fh_dynamics_set_state");
     if (rc) return rc;
     const size_t bytes = sizeof(double) * (size_t)d->n;
@@ -339,6 +541,7 @@ int set_state_common(fh_dynamics* d, const double* u, const double* v, hipMemcpy
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     d->step = 0;
     d->a_key[5] = ~0ull;
+    d->fresh = true;
     return FH_OK;
 }
 
@@ -363,10 +566,10 @@ int state_common(fh_dynamics* d, double* u, double* v, double* a, double* time, 
     int rc = dyn_ready(d, "fh_dynamics_state");
     if (rc) return rc;
     const size_t bytes = sizeof(double) * (size_t)d->n;
-    if (a && c->has_u && c->N) {   // a_n of the state as it stands (a_0 before the first step)
+    if ((first_order(d) ? v : a) && c->has_u && c->N) {   // a_n of the state as it stands (a_0 before the first step); first order: the rate
         uint64_t st[5] = {0, 0, 0, 0, 0};
         if (explicit_scheme(d)) rc = ensure_lumped(d, "fh_dynamics_state");
-        if (!rc) rc = ensure_acceleration(d, st);
+        if (!rc) rc = first_order(d) ? ensure_rate(d, true, st) : ensure_acceleration(d, st);
         if (rc) return rc;
     }
     if (u) {
@@ -378,6 +581,46 @@ int state_common(fh_dynamics* d, double* u, double* v, double* a, double* time, 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (time) *time = (double)d->step * d->s.dt;
     if (step) *step = d->step;
+    return FH_OK;
+}
+
+// the handle of either problem: `implicit` checks the Newton arguments of s and takes the vectors of the Newton steps
+int create_handle(fh_ctx* c, const char* who, const fh_dynamics_settings& s, bool implicit, int fo_scheme, double theta, uint32_t stages,
+                  fh_dynamics** out) {
+    if (implicit) {
+        if (!std::isfinite(s.newton_tolerance) || !std::isfinite(s.linear_rel_tol))
+            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the tolerances must be finite");
+        if (s.line_search != FH_NEWTON_NO_LINE_SEARCH && s.line_search != FH_NEWTON_BACKTRACKING)
+            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown line search");
+        if (s.preconditioner != FH_PRECOND_IDENTITY && s.preconditioner != FH_PRECOND_JACOBI && s.preconditioner != FH_PRECOND_MULTIGRID)
+            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown preconditioner");
+    }
+    int rc = mf_shift_ready(c, who, 1.0, 1.0);   // FH_UNSUPPORTED: mass operators, FH_TENSOR; FH_INVALID_STATE: no mesh, table or density
+    if (rc) return rc;
+    fh_dynamics* d = new fh_dynamics;
+    d->c = c;
+    d->s = s;
+    d->fo_scheme = fo_scheme;
+    d->theta = theta;
+    d->stages = stages;
+    d->topo_gen = c->topo_gen;
+    d->n = c->S() * (int)c->N;
+    const size_t n = (size_t)d->n;
+    hipError_t e = hipSuccess;
+    auto get = [&](DevBuf<double>& b, size_t count) { if (e == hipSuccess) e = b.alloc(count); };
+    get(d->v, n); get(d->a, n); get(d->m, n); get(d->f, n); get(d->r, n); get(d->work, n);
+    get(d->kep, (size_t)blocks_of(d->n));
+    if (implicit) { get(d->u_prev, n); get(d->load, n); }
+    if (implicit && fo_scheme < 0) get(d->u_ref, n);
+    if (fo_scheme == FH_FO_RKL && stages > 1) get(d->u_prev, n);   // (Y_{j-2} of the stages)
+    if (e == hipSuccess) e = hipMemsetAsync(d->v.p, 0, sizeof(double) * std::max<size_t>(n, 1), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d->a.p, 0, sizeof(double) * std::max<size_t>(n, 1), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        delete d;
+        return e == hipErrorOutOfMemory ? c->fail(FH_OUT_OF_MEMORY, std::string(who) + ": no room for the state vectors") : c->hip_fail(e, who);
+    }
+    *out = d;
     return FH_OK;
 }
 
@@ -396,39 +639,31 @@ int fh_dynamics_create(fh_ctx* c, const fh_dynamics_settings* s, fh_dynamics** o
     if (!std::isfinite(s->dt) || !(s->dt > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": dt must be positive and finite");
     if (s->scheme == FH_DYN_NEWMARK && (!std::isfinite(s->newmark_beta) || !(s->newmark_beta > 0.0) || !std::isfinite(s->newmark_gamma)))
         return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": newmark_beta must be positive and newmark_gamma finite");
-    if (s->scheme != FH_DYN_CENTRAL_DIFFERENCE) {
-        if (!std::isfinite(s->newton_tolerance) || !std::isfinite(s->linear_rel_tol))
-            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the tolerances must be finite");
-        if (s->line_search != FH_NEWTON_NO_LINE_SEARCH && s->line_search != FH_NEWTON_BACKTRACKING)
-            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown line search");
-        if (s->preconditioner != FH_PRECOND_IDENTITY && s->preconditioner != FH_PRECOND_JACOBI && s->preconditioner != FH_PRECOND_MULTIGRID)
-            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown preconditioner");
-    }
-    int rc = mf_shift_ready(c, who, 1.0, 1.0);   // FH_UNSUPPORTED: mass operators, FH_TENSOR; FH_INVALID_STATE: no mesh, table or density
-    if (rc) return rc;
-    fh_dynamics* d = new fh_dynamics;
-    d->c = c;
-    d->s = *s;
-    d->topo_gen = c->topo_gen;
-    d->n = c->S() * (int)c->N;
-    const size_t n = (size_t)d->n;
-    const bool ex = s->scheme == FH_DYN_CENTRAL_DIFFERENCE;
-    hipError_t e = hipSuccess;
-    auto get = [&](DevBuf<double>& b, size_t count) { if (e == hipSuccess) e = b.alloc(count); };
-    get(d->v, n); get(d->a, n); get(d->m, n); get(d->f, n); get(d->r, n); get(d->work, n);
-    get(d->kep, (size_t)blocks_of(d->n));
-    if (!ex) { get(d->u_ref, n); get(d->u_prev, n); get(d->load, n); }
-    if (e == hipSuccess) e = hipMemsetAsync(d->v.p, 0, sizeof(double) * std::max<size_t>(n, 1), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d->a.p, 0, sizeof(double) * std::max<size_t>(n, 1), c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        delete d;
-        return e == hipErrorOutOfMemory ? c->fail(FH_OUT_OF_MEMORY, std::string(who) + ": no room for the state vectors") : c->hip_fail(e, who);
-    }
-    *out = d;
-    return FH_OK;
+    return create_handle(c, who, *s, s->scheme != FH_DYN_CENTRAL_DIFFERENCE, -1, 1.0, 1, out);
 }
 
+int fh_first_order_create(fh_ctx* c, const fh_first_order_settings* s, fh_dynamics** out) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_first_order_create";
+    if (!s || !out) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    *out = nullptr;
+    if (s->scheme != FH_FO_RKL && s->scheme != FH_FO_THETA) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown scheme");
+    if (!std::isfinite(s->dt) || !(s->dt > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": dt must be positive and finite");
+    if (s->scheme == FH_FO_RKL && s->stages == 0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": stages must be at least 1");
+    if (s->scheme == FH_FO_THETA && !(s->theta >= 0.5 && s->theta <= 1.0))
+        return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": theta must lie in [0.5, 1]");
+    fh_dynamics_settings ds{};
+    ds.dt = s->dt;
+    ds.newton_tolerance = s->newton_tolerance;
+    ds.newton_max_iterations = s->newton_max_iterations;
+    ds.line_search = s->line_search;
+    ds.preconditioner = s->preconditioner;
+    ds.linear_rel_tol = s->linear_rel_tol;
+    ds.linear_max_iter = s->linear_max_iter;
+    return create_handle(c, who, ds, s->scheme == FH_FO_THETA, s->scheme, s->scheme == FH_FO_THETA ? s->theta : 1.0,
+                         s->scheme == FH_FO_RKL ? s->stages : 1, out);
+}
 void fh_dynamics_destroy(fh_dynamics* d) {
     if (!d) return;
     DevGuard dev_guard_(d->c->device);
@@ -472,10 +707,19 @@ int fh_dynamics_step(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, 
         if (rc) return rc;
     }
     if (explicit_scheme(d)) rc = ensure_lumped(d, WHO);
-    if (!rc) rc = ensure_acceleration(d, st);
-    if (!rc)
-        rc = explicit_scheme(d) ? explicit_steps(d, num_steps, record_every, records, &done, st)
-                                : implicit_steps(d, num_steps, record_every, records, &done, st);
+    if (first_order(d)) {   // (the steps do not read the rate: the state is checked once)
+        if (!rc && d->fresh) rc = ensure_rate(d, false, st);
+        if (!rc) {
+            d->fresh = false;
+            rc = explicit_scheme(d) ? first_order_explicit_steps(d, num_steps, record_every, records, &done, st)
+                                    : first_order_theta_steps(d, num_steps, record_every, records, &done, st);
+        }
+    } else {
+        if (!rc) rc = ensure_acceleration(d, st);
+        if (!rc)
+            rc = explicit_scheme(d) ? explicit_steps(d, num_steps, record_every, records, &done, st)
+                                    : implicit_steps(d, num_steps, record_every, records, &done, st);
+    }
     st[0] = done;
     if (steps_done) *steps_done = done;
     if (stats) std::copy(st, st + 5, stats);
@@ -540,7 +784,8 @@ int fh_dynamics_stable_dt(fh_dynamics* d, uint32_t iterations, double* omega_max
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!(rq > 0.0) || !std::isfinite(rq)) return c->fail(FH_DYNAMICS_NONFINITE, std::string(who) + ": the Rayleigh quotient is not positive and finite");
     *omega_max = std::sqrt(rq);
-    *dt_crit = 2.0 / *omega_max;
+    if (!first_order(d)) *dt_crit = 2.0 / *omega_max;
+    else *dt_crit = d->fo_scheme == FH_FO_RKL ? ((double)d->stages * (double)d->stages + (double)d->stages) / (*omega_max * *omega_max) : HUGE_VAL;
     return FH_OK;
 }
 

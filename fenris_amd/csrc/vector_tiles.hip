@@ -771,6 +771,31 @@ __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, con
     if (threadIdx.x == 0) norm_partial[blockIdx.x] = tot;
 }
 
+// the residual partials of one node summed in ascending order (k_vector_from_partials' loads: four partials in flight, the additions in
+// order), for the node passes of the time integrators
+template <int S>
+__device__ __forceinline__ void node_partials_sum(const unsigned* np_off, const unsigned* np_idx, const double* rpart, int node, double (&racc)[S]) {
+#pragma unroll
+    for (int c = 0; c < S; ++c) racc[c] = 0.0;
+    const unsigned k0 = np_off[node], k1 = np_off[node + 1];
+    for (unsigned kb = k0; kb < k1; kb += 4) {
+        unsigned v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
+        double rp[4][S];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int c = 0; c < S; ++c) rp[j][c] = rpart[(size_t)v[j] * S + c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (kb + j < k1) {
+#pragma unroll
+                for (int c = 0; c < S; ++c) racc[c] += rp[j][c];
+            }
+    }
+}
+
 // node pass of a central-difference step (engine_dynamics.hip): the node's residual partials summed in ascending order as
 // k_vector_from_partials forms them, and in the same visit the integrator's whole state update (dyn_dof, dynamics_kernels.hpp): a_{n+1} =
 // (lf f - r) / m, the second kick that completes v_{n+1}, then either the stores and the kinetic-energy partial of a record (DYN_STORE) or
@@ -783,25 +808,7 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
     double ke = 0.0;
     if (node < num_nodes) {
         double racc[S];
-#pragma unroll
-        for (int c = 0; c < S; ++c) racc[c] = 0.0;
-        const unsigned k0 = np_off[node], k1 = np_off[node + 1];
-        for (unsigned kb = k0; kb < k1; kb += 4) {     // (k_vector_from_partials' loads: four partials in flight, the additions in order)
-            unsigned v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
-            double rp[4][S];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int c = 0; c < S; ++c) rp[j][c] = rpart[(size_t)v[j] * S + c];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (kb + j < k1) {
-#pragma unroll
-                    for (int c = 0; c < S; ++c) racc[c] += rp[j][c];
-                }
-        }
+        node_partials_sum<S>(np_off, np_idx, rpart, node, racc);
         const bool fixed = p.dmask && p.dmask[node];
         const double lf = dyn_load_factor(p);
 #pragma unroll
@@ -810,6 +817,29 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
     if (p.flags & DYN_STORE) {
         const double tot = block_sum_256(ke, red);
         if (threadIdx.x == 0) p.ke_partial[blockIdx.x] = tot;
+    }
+}
+
+// node pass of one stage of a first-order Runge-Kutta-Legendre step, or of the rate alone (engine_dynamics.hip): the same ordered sum, then
+// fo_dof (dynamics_step.hpp): Y_j from Y_{j-1} (the context's u) and Y_{j-2} (prev), both updated in this visit; with FO_STORE the partial
+// of sum m y^2 of the u just written, so a recorded step needs no launch of its own.  The element pass that follows reads the u this leaves.
+template <int S>
+__global__ void __launch_bounds__(256) k_first_order_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
+                                                                   const FoStage p) {
+    __shared__ double red[4];
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    double q = 0.0;
+    if (node < num_nodes) {
+        double racc[S];
+        node_partials_sum<S>(np_off, np_idx, rpart, node, racc);
+        const bool fixed = p.dmask && p.dmask[node];
+        const double lf = dyn_load_factor(p);
+#pragma unroll
+        for (int c = 0; c < S; ++c) q += fo_dof(p, (size_t)node * S + c, fixed, lf, racc[c]);
+    }
+    if (p.flags & FO_STORE) {
+        const double tot = block_sum_256(q, red);
+        if (threadIdx.x == 0) p.partial[blockIdx.x] = tot;
     }
 }
 
@@ -1067,6 +1097,12 @@ hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_node
 hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const DynStep& p) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
         return node_launch(k_dynamics_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p);
+    });
+}
+
+hipError_t vector_tiles_first_order_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const FoStage& p) {
+    return dispatch_or_last(solution_dims, S, [&](auto s) {
+        return node_launch(k_first_order_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p);
     });
 }
 

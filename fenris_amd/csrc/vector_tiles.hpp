@@ -94,6 +94,11 @@ hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_node
 // (vector_tiles_operator_partials of them) into p.ke_partial, to be summed in index order.
 hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const DynStep& p);
 
+// node pass of one stage of a first-order Runge-Kutta-Legendre step, or of the rate alone (FoStage, dynamics_step.hpp): the node sums of the
+// residual's partials and fo_dof in one visit; with FO_STORE one partial of sum m u^2 per workgroup (vector_tiles_operator_partials of them)
+// into p.partial, to be summed in index order.
+hipError_t vector_tiles_first_order_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const FoStage& p);
+
 // the shifted map fused on Hex8 with the monomial table (a.qmono; -1 otherwise): partial[P][S] of beta T(u) x + alpha M x in ONE element pass
 // (k_shifted_pass_tiled for the linear operators, which read the operand from a.u; k_shifted_tangent_tiled for NeoHookean / StVK, operand x),
 // or with mt.beta == 0 of alpha M x alone (k_mass_hex8_tiled, x read with the Dirichlet entries of dmask as zero; u not read).  The caller sums

@@ -7,7 +7,16 @@ the mass of MatrixFreeShiftedTangent, by central differences, Newmark(beta, gamm
     u, v, a, time, step = ti.state()
 
 The whole loop runs in the library: on Hex8, Tet4, Quad4 and Tri3 an explicit step is the residual's element pass and one node pass, and
-the host waits only at records."""
+the host waits only at records.
+
+The first-order problem  M du/dt + r(u) = lf_n f  (heat conduction for the Laplace operator, the gradient flow of the stored energy for the
+elastic ones) runs on the same handle (fh_first_order_create): RungeKuttaLegendre (super-stepped explicit; ForwardEuler is its one-stage
+case) and ThetaMethod (Crank-Nicolson, implicit Euler).
+
+    ti = RungeKuttaLegendre(asm, capacity, dt, stages=8).with_dirichlet_nodes(cold).with_load(q)
+    ti.set_state(u0)
+    rec = ti.step(200, record_every=50)          # rec.mass_norm, rec.stored, rec.load_potential, rec.time
+    u, rate, time, step = ti.state()"""
 from __future__ import annotations
 
 import ctypes as C
@@ -48,6 +57,7 @@ class TimeIntegrator:
     every use (the discipline of MatrixFreeNewton._bind), so several objects may share one assembler.  The assembler's u is the state's u."""
 
     scheme = None
+    _create = "fh_dynamics_create"
 
     def __init__(self, element_assembler, density, dt):
         self.element_assembler = element_assembler
@@ -105,7 +115,7 @@ class TimeIntegrator:
         if self._h is None:
             h = C.c_void_p()
             s = self._fh_settings()
-            self.engine._check(self.engine._lib.fh_dynamics_create(self.engine._h, C.byref(s), C.byref(h)))
+            self.engine._check(getattr(self.engine._lib, self._create)(self.engine._h, C.byref(s), C.byref(h)))
             self._h = h
             self._send_load()
         return self._h
@@ -258,3 +268,81 @@ class BackwardEuler(_Implicit):
     """backward Euler on positions: alpha = 1, beta = dt^2, u_ref = u_n + dt v_n"""
 
     scheme = _ffi.DYN_BACKWARD_EULER
+
+
+@dataclass
+class FirstOrderRecord(DynamicsRecord):
+    """the records of a first-order step() call: column 0 (`kinetic`) holds 1/2 u^T B u, B the scheme's mass -- readable as mass_norm"""
+
+    @property
+    def mass_norm(self):
+        return self.kinetic
+
+
+class FirstOrderIntegrator(TimeIntegrator):
+    """M du/dt + r(u) = lf_n f on the handle of fh_first_order_create.  The state is u alone: set_state takes no v, state() returns
+    (u, rate, time, step) with rate = du/dt of the state as it stands, and step() returns a FirstOrderRecord."""
+
+    _create = "fh_first_order_create"
+    _stages, _theta = 1, 1.0
+
+    def _fh_settings(self):
+        s = _ffi.FirstOrderSettings()
+        s.scheme, s.dt, s.stages, s.theta = self.scheme, self.dt, self._stages, self._theta
+        s.newton_tolerance, s.newton_max_iterations = self._settings.tolerance, self._settings.max_iterations or 0
+        s.line_search = self._line_search.kind
+        s.preconditioner = _ffi.PRECOND_MULTIGRID if self._mg is not None else _ffi.PRECOND_JACOBI
+        s.linear_rel_tol, s.linear_max_iter = self._linear_rel_tol, self._linear_max_iter
+        return s
+
+    def step(self, num_steps, record_every=0):
+        """as TimeIntegrator.step; the errors carry a FirstOrderRecord too"""
+        def first_order(rec):
+            return FirstOrderRecord(rec.time, rec.kinetic, rec.stored, rec.load_potential, rec.steps_done, rec.stats)
+
+        try:
+            return first_order(super().step(num_steps, record_every))
+        except FenrisError as err:
+            if hasattr(err, "record"):
+                err.record = first_order(err.record)
+            raise
+
+    def state(self, device=False):
+        """(u, rate, time, step): numpy arrays, or device tensors with device=True"""
+        u, rate, _, time, step = super().state(device)
+        return u, rate, time, step
+
+
+class RungeKuttaLegendre(FirstOrderIntegrator):
+    """Runge-Kutta-Legendre super-steps of `stages` stages with the row-sum lumped mass: stable for dt <= (stages^2 + stages) / lambda_max
+    at the cost of `stages` residual passes (stable_dt returns that bound from a power iteration); the element kinds whose lumped mass has
+    an entry that is not positive (Tet10, Tri6) are refused by step (FH_UNSUPPORTED)"""
+
+    scheme = _ffi.FO_RKL
+
+    def __init__(self, element_assembler, density, dt, stages=1):
+        super().__init__(element_assembler, density, dt)
+        self._stages = int(stages)
+
+    def stable_dt(self, iterations=30):
+        """(omega_max, dt_crit = (stages^2 + stages) / omega_max^2): omega_max^2 is a Rayleigh quotient of m^-1 T(u) and never too large, so
+        dt_crit errs on the large side: apply a safety factor"""
+        return super().stable_dt(iterations)
+
+
+class ForwardEuler(RungeKuttaLegendre):
+    """forward Euler: the one-stage Runge-Kutta-Legendre step, u_{n+1} = u_n + dt (lf_n f - r(u_n)) / m"""
+
+    def __init__(self, element_assembler, density, dt):
+        super().__init__(element_assembler, density, dt, stages=1)
+
+
+class ThetaMethod(FirstOrderIntegrator, _Implicit):
+    """the theta method with the consistent mass, 0.5 <= theta <= 1: Crank-Nicolson (the default 1/2) to implicit Euler (1); one Newton
+    solve per step (with_newton, with_multigrid); stable_dt returns dt_crit = inf"""
+
+    scheme = _ffi.FO_THETA
+
+    def __init__(self, element_assembler, density, dt, theta=0.5):
+        super().__init__(element_assembler, density, dt)
+        self._theta = float(theta)

@@ -853,6 +853,55 @@ int fh_dynamics_step(fh_dynamics*, uint64_t num_steps, uint64_t record_every, do
 int fh_dynamics_state(fh_dynamics*, double* u, double* v, double* a, double* time, uint64_t* step);
 int fh_dynamics_state_dev(fh_dynamics*, double* u_dev, double* v_dev, double* a_dev, double* time, uint64_t* step);
 int fh_dynamics_stable_dt(fh_dynamics*, uint32_t iterations, double* omega_max, double* dt_crit);
+/* ---- the first-order problem on the same handle:  M du/dt + r(u) = lf_n f  (the heat equation for FH_LAPLACE; the gradient flow of the
+ * stored energy for the elastic operators), Dirichlet nodes held.  fh_first_order_create makes an fh_dynamics handle on which every
+ * fh_dynamics_* call works as described above, with these differences.  The state is u alone (the context's u) and the step counter:
+ * fh_dynamics_set_state with a non-null v is FH_BAD_ARGUMENT.
+ *
+ * FH_FO_RKL(stages = s): a Runge-Kutta-Legendre super-step of s stages with the row-sum lumped mass m = M 1, formed and checked as for
+ * central differences (FH_UNSUPPORTED names the dof).  With L(y) = (lf_n f - r(y)) / m, w1 = 2 / (s^2 + s), mu_j = (2j - 1) / j and
+ * nu_j = (1 - j) / j (formed on the host in double; every stage of step n uses lf_n, the factor at the step's start):
+ *     Y_0 = u_n;   Y_1 = fma(w1 dt, L(Y_0), Y_0);   Y_j = mu_j Y_{j-1} + nu_j Y_{j-2} + mu_j w1 dt L(Y_{j-1}), j = 2..s;   u_{n+1} = Y_s.
+ *   Per free dof one device function does a stage (Dirichlet dofs are not touched):
+ *     w = fma(lf, f, -r) / m;   y = fma(mu_j w1 dt, w, fma(mu_j, u, nu_j * prev))   (stage 1: y = fma(w1 dt, w, u));   prev = u;   u = y
+ *   so s = 1 is forward Euler to the bit.  On an eigenmode of (K, diag m) with eigenvalue lambda a step multiplies by the Legendre
+ *   polynomial P_s(1 - 2 lambda dt / (s^2 + s)): stable for dt <= (s^2 + s) / lambda_max, at the cost of s residual passes.  On Hex8, Tet4,
+ *   Quad4 and Tri3 without a rule-set table a stage is the residual's element pass over the tiles and ONE node pass
+ *   (k_first_order_from_partials); the last stage of a recorded step leaves the partials of the record in the same launch.  The loop only
+ *   enqueues between records; the kernels' status word is read at records and at the end of the call.  Every other route sums the residual
+ *   first and k_first_order_update does the same arithmetic.
+ * FH_FO_THETA(theta), 0.5 <= theta <= 1 (1/2: Crank-Nicolson; 1: implicit Euler), with the consistent mass: each step is one Newton solve as
+ *   fh_newton_solve_dev runs it, with alpha = 1, beta = theta dt, u_ref = u_n, the guess u_n and the load
+ *     g = (lf_{n+1} + c lf_n) f - c r(u_n),  c = (1 - theta) / theta   (theta = 1 evaluates no r(u_n)),
+ *   which is M (u_{n+1} - u_n) + dt [theta (r(u_{n+1}) - lf_{n+1} f) + (1 - theta) (r(u_n) - lf_n f)] = 0.  A Newton failure restores u_n and
+ *   returns the Newton code, as backward Euler does.
+ * fh_first_order_create: FH_BAD_ARGUMENT for an unknown scheme, dt <= 0, stages == 0 (FH_FO_RKL), theta outside [0.5, 1] (FH_FO_THETA),
+ *   settings that are not finite, and for FH_FO_THETA an unknown line search or preconditioner; everything else as fh_dynamics_create.
+ * fh_dynamics_step: records keep their layout and cadence; [0] is 1/2 u^T B u over all dofs, B = diag m for FH_FO_RKL and the consistent M
+ *   for FH_FO_THETA, [1] the stored energy, [2] lf f . u, [3] the time.  [0] or [1] not finite: FH_DYNAMICS_NONFINITE (FH_FO_RKL:
+ *   *steps_done is the last clean record).  The first call after fh_dynamics_set_state forms lf_0 f - r(u_0) once; if that is not finite
+ *   the call returns FH_DYNAMICS_NONFINITE with *steps_done == 0.  stats: residual evaluations are s per FH_FO_RKL step plus that one per
+ *   state; for FH_FO_THETA Newton's, plus one per step when theta < 1, plus that one per state.
+ * fh_dynamics_state: v receives the rate du/dt of the state as it stands -- FH_FO_RKL: L(u_n); FH_FO_THETA: M w = lf_n f - r(u_n) on the
+ *   free dofs, by the CG that forms Newmark's a_0 -- formed when asked for and kept until the state, the load or the context changes; zero
+ *   on the Dirichlet dofs.  a receives zeros.
+ * fh_dynamics_stable_dt: the same power iteration and omega_max; dt_crit = (s^2 + s) / omega_max^2 for FH_FO_RKL, which errs on the LARGE
+ *   side as above (apply a safety factor), and HUGE_VAL for FH_FO_THETA (unconditionally stable for theta >= 1/2). */
+enum { FH_FO_RKL = 0, FH_FO_THETA = 1 };
+typedef struct {
+    int scheme;
+    double dt;
+    uint32_t stages;        /* FH_FO_RKL: s >= 1 (1 is forward Euler) */
+    double theta;           /* FH_FO_THETA: 0.5 <= theta <= 1 */
+    /* FH_FO_THETA: fh_newton_solve's arguments, as in fh_dynamics_settings */
+    double newton_tolerance;
+    uint64_t newton_max_iterations;
+    int line_search;
+    int preconditioner;
+    double linear_rel_tol;
+    uint64_t linear_max_iter;
+} fh_first_order_settings;
+int fh_first_order_create(fh_ctx*, const fh_first_order_settings* settings, fh_dynamics** out);
 /* Geometric multigrid for the matrix-free solvers (FH_PRECOND_MULTIGRID of fh_cg_solve_matrix_free, fh_cg_solve_tangent,
  * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity, Jacobi or FH_PRECOND_AMG).  Every level is an
  * ordinary context with its own mesh, operator (Laplace, LinearElastic, NeoHookean or StVK), quadrature, data, density and
