@@ -4,13 +4,16 @@
 //   homogeneous Dirichlet conditions -> Jacobi-preconditioned CG.  No node or face list comes from anywhere but the search.
 // Mirrors a fenris application that calls Mesh::find_boundary_vertices / find_boundary_faces (src/mesh.rs:167-216) for its
 // boundary conditions.  cantilever3d.cpp is the body-force counterpart.
-// Build:  make -C examples    Run: ./examples/pressed_bar3d [cells_per_unit]
+// With `stable-neo-hookean` as the second argument the material is FH_STABLE_NEO_HOOKEAN with converted parameters: its tangent at u = 0 is
+// the same linear elasticity, so this first Newton step gives the same displacement.
+// Build:  make -C examples    Run: ./examples/pressed_bar3d [cells_per_unit [stable-neo-hookean]]
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../include/fenris_hip.h"
@@ -45,13 +48,15 @@ int main(int argc, char** argv) {
     fh_quadrilateral_gauss(2, wf.data(), xf.data());   // the face rule on [-1, 1]^2
     double mu, lambda;
     fh_lame_from_young_poisson(E, nu, &mu, &lambda);
+    const bool snh = argc > 2 && std::strcmp(argv[2], "stable-neo-hookean") == 0;
+    if (snh) fh_stable_neo_hookean_parameters(3, mu, lambda, &mu, &lambda);
     std::vector<double> lame(16);
     for (int q = 0; q < 8; ++q) { lame[2 * q] = mu; lame[2 * q + 1] = lambda; }
 
     fh_ctx* ctx = fh_create(0);
     if (!ctx) { std::fprintf(stderr, "no HIP device\n"); return 2; }
     CHECK(ctx, fh_set_mesh(ctx, FH_HEX8, vertices.data(), nv, connectivity.data(), nc));
-    CHECK(ctx, fh_set_operator(ctx, FH_LINEAR_ELASTIC));
+    CHECK(ctx, fh_set_operator(ctx, snh ? FH_STABLE_NEO_HOOKEAN : FH_LINEAR_ELASTIC));
     CHECK(ctx, fh_set_quadrature_uniform(ctx, w.data(), xi.data(), 8, lame.data()));
     CHECK(ctx, fh_set_u(ctx, nullptr));
 

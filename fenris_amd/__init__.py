@@ -5,7 +5,7 @@ fenris -- global stiffness / residual assembly -- lives here; see DESIGN.md.
 """
 from . import _ffi, amg, assembly, boundary, degree, dynamics, eigen, interpolate, io, mesh, multigrid, operators, quadrature, recovery, refinement, reorder
 from ._ffi import (ASSEMBLE_OVERWRITE, ASSEMBLE_REPRODUCIBLE, HEX8, HEX27, LAPLACE, LINEAR_ELASTIC, NEO_HOOKEAN, QUAD4, SCATTER_ATOMIC,
-                   SCATTER_COLORED, SCATTER_GATHER, STVK, PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, PRECOND_AMG, AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER, TET4, TRI3, TET10, QUAD9, TRI6, HEX20, TET20, MASS_SCALAR, MASS_VECTOR, FenrisError, SingularJacobianError)
+                   SCATTER_COLORED, SCATTER_GATHER, STVK, STABLE_NEO_HOOKEAN, PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, PRECOND_AMG, AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER, TET4, TRI3, TET10, QUAD9, TRI6, HEX20, TET20, MASS_SCALAR, MASS_VECTOR, FenrisError, SingularJacobianError)
 from .assembly import (CsrAssembler, CsrMatrix, CsrParAssembler, DisjointSubsetsColors, ElementEllipticAssembler, ElementMassAssembler,
                        ElementEllipticAssemblerBuilder, ElementSourceAssembler, ElementSourceAssemblerBuilder, Engine,
                        MockElementAssembler, UniformQuadratureTable, CompactQuadratureTable, GeneralQuadratureTable,
@@ -31,6 +31,6 @@ from .refinement import (Transfer, permute_transfer, refine_uniformly, refine_un
                          refine_uniformly_with_transfer)
 from .mesh import Mesh, hex20_mesh_from_hex8, hex27_mesh_from_hex8, procedural, quad9_mesh_from_quad4, tet10_mesh_from_tet4, tet20_mesh_from_tet4, tri6_mesh_from_tri3
 from .operators import (Density, GravitySource, SourceFunction, LameParameters, LaplaceOperator, LinearElasticMaterial, MaterialEllipticOperator,
-                        NeoHookeanMaterial, StVKMaterial, TensorEllipticOperator, YoungPoisson)
+                        NeoHookeanMaterial, StableNeoHookeanMaterial, StVKMaterial, TensorEllipticOperator, YoungPoisson)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("FENRIS_HIP_LIB") or os.path.join(_HERE, "lib", "libfe
 
 FH_OK, FH_SINGULAR_JACOBIAN, FH_BAD_ARGUMENT, FH_HIP_ERROR, FH_OUT_OF_MEMORY, FH_INVALID_STATE, FH_UNSUPPORTED = 0, 1, 2, 3, 4, 5, 6
 QUAD4, HEX8, TET4, HEX27, TRI3, TET10, QUAD9, TRI6, HEX20, TET20 = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
-LAPLACE, LINEAR_ELASTIC, NEO_HOOKEAN, STVK, MASS_SCALAR, MASS_VECTOR, TENSOR = 0, 1, 2, 3, 4, 5, 6
+LAPLACE, LINEAR_ELASTIC, NEO_HOOKEAN, STVK, MASS_SCALAR, MASS_VECTOR, TENSOR, STABLE_NEO_HOOKEAN = 0, 1, 2, 3, 4, 5, 6, 7
 SCATTER_ATOMIC, SCATTER_COLORED, SCATTER_GATHER = 0, 1, 2
 FH_CG_MAX_ITERATIONS, FH_CG_INDEFINITE_OPERATOR, FH_CG_INDEFINITE_PRECONDITIONER = 7, 8, 9
 FH_NEWTON_MAX_ITERATIONS, FH_NEWTON_JACOBIAN_ERROR, FH_NEWTON_LINE_SEARCH_FAILED = 10, 11, 12
@@ -264,6 +264,7 @@ _SIGS = {
     "fh_eigs_lowest": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_int, C.c_double, C.c_uint64, C.c_int, f64p, f64p, f64p, u64p]),
     "fh_eigs_profile": (C.c_int, [C.c_void_p, f64p]),
     "fh_lame_from_young_poisson":(C.c_int, [C.c_double, C.c_double, f64p, f64p]),
+    "fh_stable_neo_hookean_parameters": (C.c_int, [C.c_uint32, C.c_double, C.c_double, f64p, f64p]),
     "fh_morton_partition": (C.c_int, [C.c_uint32, f64p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
     "fh_partition_create": (C.c_void_p, [C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),
     "fh_partition_destroy": (None, [C.c_void_p]),

@@ -1232,7 +1232,7 @@ class MatrixFreeOperator:
 
 class MatrixFreeTangent(MatrixFreeOperator):
     """The tangent T(u) = dr/du of an element assembler's residual at its current u (any material: Laplace, LinearElastic, NeoHookean,
-    StVK), applied without pattern or values: the matrix assemble_matrix forms for the same u, without forming it.  The interface of
+    StVK, StableNeoHookean), applied without pattern or values: the matrix assemble_matrix forms for the same u, without forming it.  The interface of
     MatrixFreeOperator (Dirichlet nodes owned by the object, apply on numpy arrays or device tensors, diagonal, cg_solve); its Jacobi
     preconditioner takes the tangent's diagonal.  Changing the assembler's u (with_u) changes the operator."""
 
@@ -1247,7 +1247,7 @@ class MatrixFreeTangent(MatrixFreeOperator):
 
 
 class MatrixFreeShiftedTangent(MatrixFreeOperator):
-    """alpha M + beta T(u) of an element assembler (Laplace, LinearElastic, NeoHookean, StVK), the system of an implicit time step (backward
+    """alpha M + beta T(u) of an element assembler (Laplace, LinearElastic, NeoHookean, StVK, StableNeoHookean), the system of an implicit time step (backward
     Euler: alpha = 1, beta = dt^2), applied without pattern or values.  M is the mass matrix the assembled mass operator forms on the same
     mesh and quadrature table with this object's density (a scalar for the whole mesh, or one value per element), the scalar mass for
     Laplace and the vector mass for the materials; T(u) is MatrixFreeTangent's map at the assembler's current u.  Density, coefficients and

@@ -436,6 +436,37 @@ __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double
                     for (int k = 0; k < D; ++k) t = fma(Fi[k][i], gout[n * D + k], t);
                     at[n * D + i] = t;
                 }
+        } else if (OP == FH_STABLE_NEO_HOOKEAN) {
+            // fenris_hip.h, FH_STABLE_NEO_HOOKEAN: the four scaled scalars and F (for G); F g_n and cof F g_n.  No branch on det F.
+            if constexpr (S == D) {
+                double Fs[D][D], Cf[D][D];
+                double c, gamma;
+                snh_kinematics<D, S>(gu, Fs, Cf, c, gamma);
+                double a0, a1, b;
+                snh_coefficients<D>(mu, lambda, c, gamma, a0, a1, b);
+                coef[0] = s * a0;
+                coef[1] = s * a1;
+                coef[2] = s * lambda;
+                coef[3] = s * b;
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j < D; ++j) coef[4 + i * D + j] = Fs[i][j];
+                double* fg = qp + N * D;       // F g_n
+                double* cg = qp + 2 * N * D;   // cof F g_n
+                for (int n = 0; n < N; ++n)
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        double t = 0.0, t2 = 0.0;
+#pragma unroll
+                        for (int k = 0; k < D; ++k) {
+                            t = fma(Fs[i][k], gout[n * D + k], t);
+                            t2 = fma(Cf[i][k], gout[n * D + k], t2);
+                        }
+                        fg[n * D + i] = t;
+                        cg[n * D + i] = t2;
+                    }
+            }
         } else {  // StVK, materials.rs:417-438
             double Eg[D][D];
             double trE = 0.0;
@@ -470,7 +501,7 @@ __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double
                     eg[n * D + i] = t2;
                 }
         }
-    } else if constexpr (OP <= FH_STVK) {   // (the operators with a stress: the mass operators and FH_TENSOR have no vector / scalar form)
+    } else if constexpr (op_has_stress(OP)) {   // (the mass operators and FH_TENSOR have no vector / scalar form)
         // stress P (s x d), scaled by s, for the residual; energy density for the scalar path
         double P[S][D];
         double psi;
@@ -633,6 +664,59 @@ __device__ __forceinline__ void pair_block(const KArgs& ka, const Layout& L, con
                 const double tl = c[0] * ta[i], tal = c[1] * tb[i];
 #pragma unroll
                 for (int j = 0; j < D; ++j) B[i][j] += tl * tb[j] - tal * ta[j] + (i == j ? diag : 0.0 * diag);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) blk[i % S][j % S] = B[i][j];
+    } else if (OP == FH_STABLE_NEO_HOOKEAN) {
+        // c0 (a.b) I + c1 (F a)(F b)^T + c2 (cof F a)(cof F b)^T + c3 G(a, b)   (fenris_hip.h, FH_STABLE_NEO_HOOKEAN)
+        double B[D][D];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) B[i][j] = 0.0;
+        for (int q = 0; q < nq; ++q, qp += L.qpd) {
+            const double* a = qp + I * D;
+            const double* b = qp + J * D;
+            const double* fa = qp + N * D + I * D;
+            const double* fb = qp + N * D + J * D;
+            const double* ca = qp + 2 * N * D + I * D;
+            const double* cb = qp + 2 * N * D + J * D;
+            const double* c = qp + 3 * N * D;
+            double ab = 0.0;
+#pragma unroll
+            for (int i = 0; i < D; ++i) ab = fma(a[i], b[i], ab);
+            const double diag = c[0] * ab;
+            double G[D][D];   // G[i][k] = sum_jl a[j] (d cof F[i][j] / d F[k][l]) b[l], antisymmetric
+#pragma unroll
+            for (int i = 0; i < D; ++i) G[i][i] = 0.0;
+            if constexpr (D == 2) {
+                G[0][1] = a[0] * b[1] - a[1] * b[0];
+                G[1][0] = -G[0][1];
+            } else {
+                double x[D], w[D];   // w = F (a x b)
+#pragma unroll
+                for (int i = 0; i < D; ++i) x[i] = a[(i + 1) % D] * b[(i + 2) % D] - a[(i + 2) % D] * b[(i + 1) % D];
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) t = fma(c[4 + i * D + k], x[k], t);
+                    w[i] = t;
+                }
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    G[i][(i + 1) % D] = w[(i + 2) % D];
+                    G[(i + 1) % D][i] = -w[(i + 2) % D];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                const double f1 = c[1] * fa[i], c2 = c[2] * ca[i];
+#pragma unroll
+                for (int j = 0; j < D; ++j) B[i][j] += (i == j ? diag : 0.0) + f1 * fb[j] + c2 * cb[j] + c[3] * G[i][j];
             }
         }
 #pragma unroll

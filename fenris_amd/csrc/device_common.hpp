@@ -24,7 +24,8 @@ template <> struct ElemT<FH_TET20> { static constexpr int D = 3, N = 20, NG = 4;
 
 // ------------------------------------------------------------------------------------ operator traits
 // Per (element, quadrature point) the prologue leaves in LDS:  NVEC vectors per node (physical
-// gradient g_n; for NeoHookean also F^{-T} g_n; for StVK also F g_n and E g_n) and NCOEF scalars.
+// gradient g_n; for NeoHookean also F^{-T} g_n; for StVK also F g_n and E g_n; for Stable Neo-Hookean also F g_n and cof F g_n) and
+// NCOEF scalars.
 template <int OP, int D> struct OpT;
 template <int D> struct OpT<FH_LAPLACE, D> {
     static constexpr int S = 1, NVEC = 1, NCOEF = 1;  // [s]
@@ -59,6 +60,22 @@ template <int D> struct OpT<FH_TENSOR, D> {
     static constexpr int S = D, NVEC = 1, NCOEF = 1;  // [s]
     static constexpr bool NEEDS_U = false;
 };
+
+// Stable Neo-Hookean (fenris_hip.h, FH_STABLE_NEO_HOOKEAN): g_n, F g_n, cof F g_n and StVK's scalar count, so its LDS footprint
+template <int D> struct OpT<FH_STABLE_NEO_HOOKEAN, D> {
+    static constexpr int S = D, NVEC = 3, NCOEF = 4 + D * D;  // [s mu (1 - 1/m), s 2 mu/m^2, s lambda, s (lambda gamma - k), F]
+    static constexpr bool NEEDS_U = true;
+};
+
+// What an operator is, asked by property and not by the rank of its number (the numbers are ABI and grow at the end).
+constexpr bool op_is_mass(int op) { return op == FH_MASS_SCALAR || op == FH_MASS_VECTOR; }
+constexpr bool op_is_data(int op) { return op == FH_TENSOR; }   // its coefficients come from KArgs::tensor
+// has a stress and an energy density (material_point): residual, energy, matrix-free map, recovery
+constexpr bool op_has_stress(int op) {
+    return op == FH_LAPLACE || op == FH_LINEAR_ELASTIC || op == FH_NEO_HOOKEAN || op == FH_STVK || op == FH_STABLE_NEO_HOOKEAN;
+}
+// its stress is nonlinear in u: K depends on u, the tangent is not the operator
+constexpr bool op_depends_on_u(int op) { return op == FH_NEO_HOOKEAN || op == FH_STVK || op == FH_STABLE_NEO_HOOKEAN; }
 
 enum { MODE_ATOMIC = 0, MODE_COLORED = 1, MODE_GATHER = 2, MODE_DUMP = 3 };
 

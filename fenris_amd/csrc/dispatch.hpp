@@ -45,9 +45,9 @@ auto dispatch_bool(bool b, F&& f) {
 // The recurring sets.  A new element kind or operator is added to the lists it has kernels for, here and nowhere else.
 constexpr int_list<FH_QUAD4, FH_HEX8, FH_TET4, FH_HEX27, FH_TRI3, FH_TET10, FH_QUAD9, FH_TRI6, FH_HEX20, FH_TET20> all_kinds{};
 constexpr int_list<FH_QUAD4, FH_HEX8, FH_TET4, FH_TRI3> low_order_kinds{};   // iso-parametric; the geometry kinds of all ten (Tri3 last: dispatch_or_last)
-constexpr int_list<FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK, FH_MASS_SCALAR, FH_MASS_VECTOR, FH_TENSOR> all_ops{};
-constexpr int_list<FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK> elliptic_ops{};
-constexpr int_list<FH_NEO_HOOKEAN, FH_STVK> hyperelastic_ops{};
+constexpr int_list<FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK, FH_MASS_SCALAR, FH_MASS_VECTOR, FH_TENSOR, FH_STABLE_NEO_HOOKEAN> all_ops{};
+constexpr int_list<FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK, FH_STABLE_NEO_HOOKEAN> elliptic_ops{};   // op_has_stress
+constexpr int_list<FH_NEO_HOOKEAN, FH_STVK, FH_STABLE_NEO_HOOKEAN> hyperelastic_ops{};                              // op_depends_on_u
 constexpr int_list<1, 2, 3> solution_dims{};
 constexpr int_list<FH_RECOVER_GRAD_U, FH_RECOVER_STRAIN, FH_RECOVER_STRESS_PK1, FH_RECOVER_STRESS_CAUCHY, FH_RECOVER_VON_MISES,
                    FH_RECOVER_ENERGY_DENSITY, FH_RECOVER_VOLUME> recover_quantities{};

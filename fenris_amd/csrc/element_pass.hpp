@@ -703,7 +703,7 @@ __device__ __forceinline__ void diagonal_element_body(const KArgs& a, const long
 template <int D, int S, int N, int OP>
 __device__ __forceinline__ void tangent_element_body(const KArgs& a, const long long e, bool live, const double (&X)[N][D], const double (&U)[N][S],
                                                      const double (&V)[N][S], double (&f)[N][S]) {
-    static_assert(OP == FH_NEO_HOOKEAN || OP == FH_STVK, "nonlinear operators only: the linear ones take the residual's element pass");
+    static_assert(op_depends_on_u(OP), "nonlinear operators only: the linear ones take the residual's element pass");
 #pragma unroll
     for (int n = 0; n < N; ++n)
 #pragma unroll
@@ -768,7 +768,7 @@ template <int OP, bool AFF, bool MASS = false>
 __device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long long e, const bool live, const double (&X)[8][3], const double (&U)[8][OpT<OP, 3>::S],
                                                   const double (&V)[8][OpT<OP, 3>::S], double (&f)[8][OpT<OP, 3>::S],
                                                   const MassTerm& mt = MassTerm{}) {
-    static_assert(OP == FH_NEO_HOOKEAN || OP == FH_STVK, "nonlinear operators only: the linear ones take the residual's element pass");
+    static_assert(op_depends_on_u(OP), "nonlinear operators only: the linear ones take the residual's element pass");
     constexpr int D = 3, N = 8, S = OpT<OP, 3>::S;
     const double* par_e = a.rule_map ? a.rparams + (size_t)a.rule_map[e] * a.nq * 2 : nullptr;
     double cx[D][8], cu[S][8], cv[S][8];
@@ -924,7 +924,7 @@ __device__ __forceinline__ void tangent_body_hex8(const KArgs& a, const long lon
 template <int D, int S, int N, int OP>
 __device__ __forceinline__ void tangent_diagonal_body(const KArgs& a, const long long e, bool live, const double (&X)[N][D], const double (&U)[N][S],
                                                       double (&f)[N][S]) {
-    static_assert(OP == FH_NEO_HOOKEAN || OP == FH_STVK, "nonlinear operators only: the linear ones take diagonal_element_body");
+    static_assert(op_depends_on_u(OP), "nonlinear operators only: the linear ones take diagonal_element_body");
 #pragma unroll
     for (int n = 0; n < N; ++n)
 #pragma unroll

@@ -796,7 +796,7 @@ int fh_affine_slot_elements(fh_ctx* c, int* slots_per_block, uint64_t* blocks, i
 int fh_set_operator(fh_ctx* c, int op_kind) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
-    if (op_kind < FH_LAPLACE || op_kind > FH_TENSOR) return c->fail(FH_BAD_ARGUMENT, "fh_set_operator: unknown operator");
+    if (op_kind < FH_LAPLACE || op_kind > FH_STABLE_NEO_HOOKEAN) return c->fail(FH_BAD_ARGUMENT, "fh_set_operator: unknown operator");
     if (c->ragged) return c->fail(FH_INVALID_STATE, "fh_set_operator: context holds a ragged connectivity");
     const int old_s = c->S(), old_op = c->op;
     c->op = op_kind;

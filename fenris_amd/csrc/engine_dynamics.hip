@@ -218,7 +218,7 @@ int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
         if (d->s.scheme == FH_DYN_NEWMARK) {
             uint64_t it = 0;
             const int pre = d->s.preconditioner == FH_PRECOND_MULTIGRID ? (int)FH_PRECOND_JACOBI : d->s.preconditioner;   // (M alone needs no hierarchy)
-            rc = cg_solve_free_dev(c, WHO, FH_STVK, d->work.p, d->a.p, pre, d->s.linear_rel_tol, d->s.linear_max_iter, &it, 1.0, 0.0);
+            rc = cg_solve_free_dev(c, WHO, MF_TANGENT, d->work.p, d->a.p, pre, d->s.linear_rel_tol, d->s.linear_max_iter, &it, 1.0, 0.0);
             stats[3] += it;
             if (rc) return rc;
         }
@@ -413,7 +413,7 @@ int ensure_rate(fh_dynamics* d, bool solve, uint64_t* stats) {
         HIP_TRY(c, hipMemsetAsync(d->v.p, 0, sizeof(double) * (size_t)n, c->stream));
         uint64_t it = 0;
         const int pre = d->s.preconditioner == FH_PRECOND_MULTIGRID ? (int)FH_PRECOND_JACOBI : d->s.preconditioner;   // (M alone needs no hierarchy)
-        rc = cg_solve_free_dev(c, WHO, FH_STVK, d->work.p, d->v.p, pre, d->s.linear_rel_tol, d->s.linear_max_iter, &it, 1.0, 0.0);
+        rc = cg_solve_free_dev(c, WHO, MF_TANGENT, d->work.p, d->v.p, pre, d->s.linear_rel_tol, d->s.linear_max_iter, &it, 1.0, 0.0);
         stats[3] += it;
         if (rc) return rc;
     }

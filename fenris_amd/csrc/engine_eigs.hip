@@ -345,7 +345,7 @@ int eigs_lowest_dev(fh_ctx* c, uint32_t m32, double shift, int preconditioner, d
                     double* theta, double* residual_norms, uint64_t* stats) {
     const char* who = "fh_eigs_lowest";
     if (stats) std::fill(stats, stats + 4, (uint64_t)0);
-    int rc = mf_ready(c, who, FH_STVK);
+    int rc = mf_ready(c, who, MF_TANGENT);
     if (rc) return rc;
     if (!X_dev || !theta) return c->fail(FH_BAD_ARGUMENT, "fh_eigs_lowest: null argument");
     if (m32 == 0 || m32 > FH_EIG_MAX_BLOCK) return c->fail(FH_BAD_ARGUMENT, "fh_eigs_lowest: m must be 1..FH_EIG_MAX_BLOCK");

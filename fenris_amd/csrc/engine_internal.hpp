@@ -580,9 +580,10 @@ int assemble_two_pass(fh_ctx* c, double* values_dev, int overwrite);
 size_t two_pass_dense_doubles(fh_ctx* c);   // doubles of the element-matrix buffer between the two passes (depends on the first pass's layout)
 int hex8_tune_lanes_now(fh_ctx* c);
 int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset = true);
-// matrix-free map (engine_vector.hip): checks (max_op: FH_LINEAR_ELASTIC for the operator, FH_STVK for the tangent), y = T(u) x (+ per-workgroup
+// matrix-free map (engine_vector.hip): checks (scope: MF_OPERATOR for the operator, MF_TANGENT for the tangent), y = T(u) x (+ per-workgroup
 // partials of x . y; *partials: their number), the diagonal
-int mf_ready(fh_ctx* c, const char* who, int max_op);
+enum { MF_OPERATOR = 0, MF_TANGENT = 1 };
+int mf_ready(fh_ctx* c, const char* who, int scope);
 int mf_apply(fh_ctx* c, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
 int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
 // the shifted map alpha M + beta T(u) (fh_apply_shifted_tangent_dev): checks (alpha != 0 needs the density), y and its partials of x . y as
@@ -590,9 +591,9 @@ int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
 int mf_shift_ready(fh_ctx* c, const char* who, double alpha, double beta);
 int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
 int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bool with_scale);
-// Jacobi-PCG on the matrix-free map (engine_solver.hip; alpha == 0, beta == 1: the plain map of max_op), and the ordered host sum of
+// Jacobi-PCG on the matrix-free map (engine_solver.hip; alpha == 0, beta == 1: the plain map of scope), and the ordered host sum of
 // per-workgroup partials (stride K)
-int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
+int cg_solve_free_dev(fh_ctx* c, const char* who, int scope, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
                       uint64_t max_iter, uint64_t* num_iterations, double alpha = 0.0, double beta = 1.0);
 int sum_partials(fh_ctx* c, const double* dev, int blocks, int K, double* out);
 // FH_PRECOND_MULTIGRID (engine_mg.hip) on c->mg: per solve the injection of u into the nonlinear coarse levels and the per-level diagonal,

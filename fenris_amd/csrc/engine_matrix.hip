@@ -430,7 +430,7 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
         // parameters is faster one-pass: 5.7 vs 8.2 ms).  The dense buffer costs E (s n)^2 doubles: capped.
         const size_t dense_doubles = two_pass_dense_doubles(c);
         const double dense_gb = (double)dense_doubles * 8.0 / 1e9;
-        const bool want = c->ei.n > 8 || c->op == FH_NEO_HOOKEAN || c->op == FH_STVK || c->opt.TWO_PASS;
+        const bool want = c->ei.n > 8 || op_depends_on_u(c->op) || c->opt.TWO_PASS;
         if (want && dense_gb <= (double)two_pass_max_gb(c)) {
             // the dense buffer is allocated here: when the device cannot hold it the one-pass gather below takes over
             if (c->ke_dense.n >= dense_doubles || c->ke_dense.alloc(dense_doubles) == hipSuccess)

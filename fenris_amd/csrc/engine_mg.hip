@@ -388,7 +388,7 @@ extern "C++" int mg_setup(fh_ctx* fine, double alpha, double beta) {
     for (int l = L - 1; l >= 0; --l) {
         MgLevel& C = mg->lv[l];
         const fh_ctx* src = mg->lv[l + 1].c;
-        if (C.c->op != FH_NEO_HOOKEAN && C.c->op != FH_STVK) continue;
+        if (!op_depends_on_u(C.c->op)) continue;
         if (!src->has_u) return fine->fail(FH_INVALID_STATE, "multigrid: a nonlinear coarse level needs u on the level above it");
         hipLaunchKernelGGL(k_mg_inject, dim3(grid_for(C.n, 256)), dim3(256), 0, fine->stream, C.N, C.S, (const unsigned*)mg->lv[l + 1].inj.p,
                            (const double*)src->u.p, C.t.p);
@@ -399,7 +399,7 @@ extern "C++" int mg_setup(fh_ctx* fine, double alpha, double beta) {
     for (int l = 0; l <= L; ++l) {
         MgLevel& V = mg->lv[l];
         fh_ctx* c = V.c;
-        rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, "multigrid", FH_STVK) : mf_shift_ready(c, "multigrid", alpha, beta);
+        rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, "multigrid", MF_TANGENT) : mf_shift_ready(c, "multigrid", alpha, beta);
         if (rc) return c == fine ? rc : fine->fail(rc, "multigrid level " + std::to_string(l) + ": " + c->err);
         unsigned long long key[8];
         mg_key(c, alpha, beta, key);
@@ -464,7 +464,7 @@ int fh_mg_create(fh_ctx* fine, uint64_t num_coarse, fh_ctx* const* coarse, const
         if (!c) return fine->fail(FH_BAD_ARGUMENT, "fh_mg_create: null coarse context");
         if (c->device != fine->device) return fine->fail(FH_BAD_ARGUMENT, "fh_mg_create: every level must be on the fine context's device");
         if (!c->has_mesh || c->ragged || c->op < 0) return fine->fail(FH_INVALID_STATE, "fh_mg_create: every level needs a mesh and an operator");
-        if (c->op > FH_STVK) return fine->fail(FH_UNSUPPORTED, "fh_mg_create: the levels' operators must have a matrix-free map (Laplace, LinearElastic, NeoHookean, StVK)");
+        if (!op_has_stress(c->op)) return fine->fail(FH_UNSUPPORTED, "fh_mg_create: the levels' operators must have a matrix-free map (Laplace, LinearElastic, NeoHookean, StVK, StableNeoHookean)");
         if (c->S() != fine->S()) return fine->fail(FH_BAD_ARGUMENT, "fh_mg_create: the levels differ in solution dim");
         for (size_t k = 0; k < l; ++k)
             if (ctx[k] == c) return fine->fail(FH_BAD_ARGUMENT, "fh_mg_create: a context appears twice");

@@ -56,7 +56,7 @@ int newton_run(fh_ctx* c, double alpha, double beta, const double* f, const doub
             return c->fail(FH_NEWTON_MAX_ITERATIONS, std::string(who) + ": failed to converge within the maximum number of iterations");
         HIP_TRY(c, hipMemsetAsync(q.p, 0, sizeof(double) * (size_t)n, c->stream));
         uint64_t cg_it = 0;
-        const int rcg = cg_solve_free_dev(c, who, FH_STVK, ns.F.p, q.p, preconditioner, linear_rel_tol, linear_max_iter, &cg_it, alpha, beta);
+        const int rcg = cg_solve_free_dev(c, who, MF_TANGENT, ns.F.p, q.p, preconditioner, linear_rel_tol, linear_max_iter, &cg_it, alpha, beta);
         st[2] += cg_it;
         st[3] = (uint64_t)rcg;
         // (any error of solve_jacobian_system is a JacobianError, newton.rs:112-115: the PCG's own codes and what its map reports, e.g.

@@ -9,7 +9,7 @@ static int recover_check(fh_ctx* c, const char* who, int quantity, uint32_t* nco
     if (quantity < FH_RECOVER_GRAD_U || quantity > FH_RECOVER_VOLUME) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown quantity");
     if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, std::string(who) + ": no finite element mesh set");
     if (c->op < 0) return c->fail(FH_INVALID_STATE, std::string(who) + ": no operator set");
-    if (c->op > FH_STVK) return c->fail(FH_UNSUPPORTED, std::string(who) + ": the mass operators and FH_TENSOR have no recovered quantities");
+    if (!op_has_stress(c->op)) return c->fail(FH_UNSUPPORTED, std::string(who) + ": the mass operators and FH_TENSOR have no recovered quantities");
     const int d = c->ei.d, s = c->S();
     const bool solid = quantity == FH_RECOVER_STRAIN || quantity == FH_RECOVER_STRESS_CAUCHY || quantity == FH_RECOVER_VON_MISES;
     if (c->op == FH_LAPLACE && solid) return c->fail(FH_UNSUPPORTED, std::string(who) + ": FH_LAPLACE has no strain, Cauchy or von Mises stress");

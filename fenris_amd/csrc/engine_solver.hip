@@ -237,16 +237,16 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
                       : std::function<int(const double*, double*)>());
 }
 
-// The same solver around the matrix-free map (fh_apply_operator_dev, fh_apply_tangent_dev; max_op as mf_ready), or around the shifted map
+// The same solver around the matrix-free map (fh_apply_operator_dev, fh_apply_tangent_dev; scope as mf_ready), or around the shifted map
 // alpha M + beta T(u) (fh_apply_shifted_tangent_dev; the plain map is alpha = 0, beta = 1): no pattern, no values.  The partials of p . Ap
 // come from the map's node pass (or its last pass off the tiles), summed over at most 2048 ranges in a fixed order; Jacobi takes the
 // matrix-free diagonal.  The diagonal (and with it the scale of the Dirichlet rows) is formed once per solve.
-extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
+extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int scope, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
                                    uint64_t max_iter, uint64_t* num_iterations, double alpha, double beta) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     if (num_iterations) *num_iterations = 0;
-    int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, max_op) : mf_shift_ready(c, who, alpha, beta);
+    int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, scope) : mf_shift_ready(c, who, alpha, beta);
     if (rc) return rc;
     if (!b_dev || !x_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (preconditioner != FH_PRECOND_IDENTITY && preconditioner != FH_PRECOND_JACOBI && preconditioner != FH_PRECOND_MULTIGRID)
@@ -299,15 +299,15 @@ extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int max_op, const
 
 int fh_cg_solve_matrix_free_dev(fh_ctx* c, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
                                 uint64_t* num_iterations) {
-    return cg_solve_free_dev(c, "fh_cg_solve_matrix_free", FH_LINEAR_ELASTIC, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations);
+    return cg_solve_free_dev(c, "fh_cg_solve_matrix_free", MF_OPERATOR, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations);
 }
 int fh_cg_solve_tangent_dev(fh_ctx* c, const double* b_dev, double* x_dev, int preconditioner, double rel_tol, uint64_t max_iter,
                             uint64_t* num_iterations) {
-    return cg_solve_free_dev(c, "fh_cg_solve_tangent", FH_STVK, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations);
+    return cg_solve_free_dev(c, "fh_cg_solve_tangent", MF_TANGENT, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations);
 }
 int fh_cg_solve_shifted_tangent_dev(fh_ctx* c, double alpha, double beta, const double* b_dev, double* x_dev, int preconditioner, double rel_tol,
                                     uint64_t max_iter, uint64_t* num_iterations) {
-    return cg_solve_free_dev(c, "fh_cg_solve_shifted_tangent", FH_STVK, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
+    return cg_solve_free_dev(c, "fh_cg_solve_shifted_tangent", MF_TANGENT, b_dev, x_dev, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
 }
 
 int fh_cg_solve(fh_ctx* c, const double* values, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter,
@@ -332,12 +332,12 @@ int fh_cg_solve(fh_ctx* c, const double* values, const double* b, double* x, int
     return rc;
 }
 
-static int cg_solve_free_host(fh_ctx* c, const char* who, int max_op, const double* b, double* x, int preconditioner, double rel_tol,
+static int cg_solve_free_host(fh_ctx* c, const char* who, int scope, const double* b, double* x, int preconditioner, double rel_tol,
                               uint64_t max_iter, uint64_t* num_iterations, double alpha = 0.0, double beta = 1.0) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     if (num_iterations) *num_iterations = 0;
-    int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, max_op) : mf_shift_ready(c, who, alpha, beta);
+    int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, scope) : mf_shift_ready(c, who, alpha, beta);
     if (rc) return rc;
     if (!b || !x) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     const size_t n = (size_t)c->S() * c->N;
@@ -346,7 +346,7 @@ static int cg_solve_free_host(fh_ctx* c, const char* who, int max_op, const doub
     HIP_TRY(c, dx.alloc(n + 1));
     HIP_TRY(c, hipMemcpyAsync(db.p, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    rc = cg_solve_free_dev(c, who, max_op, db.p, dx.p, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
+    rc = cg_solve_free_dev(c, who, scope, db.p, dx.p, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
     // like the reference's SolveError, the iterate reached so far is handed back on failure
     HIP_TRY(c, hipMemcpyAsync(x, dx.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -354,14 +354,14 @@ static int cg_solve_free_host(fh_ctx* c, const char* who, int max_op, const doub
 }
 
 int fh_cg_solve_matrix_free(fh_ctx* c, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations) {
-    return cg_solve_free_host(c, "fh_cg_solve_matrix_free", FH_LINEAR_ELASTIC, b, x, preconditioner, rel_tol, max_iter, num_iterations);
+    return cg_solve_free_host(c, "fh_cg_solve_matrix_free", MF_OPERATOR, b, x, preconditioner, rel_tol, max_iter, num_iterations);
 }
 int fh_cg_solve_tangent(fh_ctx* c, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter, uint64_t* num_iterations) {
-    return cg_solve_free_host(c, "fh_cg_solve_tangent", FH_STVK, b, x, preconditioner, rel_tol, max_iter, num_iterations);
+    return cg_solve_free_host(c, "fh_cg_solve_tangent", MF_TANGENT, b, x, preconditioner, rel_tol, max_iter, num_iterations);
 }
 int fh_cg_solve_shifted_tangent(fh_ctx* c, double alpha, double beta, const double* b, double* x, int preconditioner, double rel_tol, uint64_t max_iter,
                                 uint64_t* num_iterations) {
-    return cg_solve_free_host(c, "fh_cg_solve_shifted_tangent", FH_STVK, b, x, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
+    return cg_solve_free_host(c, "fh_cg_solve_shifted_tangent", MF_TANGENT, b, x, preconditioner, rel_tol, max_iter, num_iterations, alpha, beta);
 }
 
 static int error_squared(fh_ctx* c, int which, uint32_t sdim, const double* uh_dev, const double* exact_dev, double* out) {

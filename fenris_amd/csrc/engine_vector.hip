@@ -116,7 +116,7 @@ extern "C++" int ensure_vector_tiles(fh_ctx* c) {
 static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) {
     int rc = check_ready(c, "fh_assemble_vector", false);
     if (rc) return rc;
-    if (c->op > FH_STVK) return c->fail(FH_UNSUPPORTED, "fh_assemble_vector: the mass assembler has no vector form");
+    if (!op_has_stress(c->op)) return c->fail(FH_UNSUPPORTED, "fh_assemble_vector: the mass assembler has no vector form");
     if (!out_dev) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_vector: out is null");
     rc = c->keep_status ? FH_OK : reset_status(c);
     if (rc) return rc;
@@ -131,7 +131,7 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
     // small iso-parametric elements: tiles of 256 elements, one thread per element, the tile's distinct nodes summed in LDS, only
     // those partial sums through HBM, then one thread per node (vector_tiles.hip); no atomics, bitwise reproducible; an element mask
     // zeroes the contributions of the inactive elements
-    if (tiles_enabled(c) && c->op <= FH_STVK) {
+    if (tiles_enabled(c) && op_has_stress(c->op)) {
         rc = ensure_vector_tiles(c);
         if (rc) return rc;
         if (!c->vt_bad) {
@@ -412,7 +412,7 @@ int fh_assemble_scalar(fh_ctx* c, double* out, uint64_t* failed) {
 static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
     int rc = check_ready(c, "fh_assemble_scalar", false);
     if (rc) return rc;
-    if (c->op > FH_STVK) return c->fail(FH_UNSUPPORTED, "fh_assemble_scalar: the mass assembler has no scalar form");
+    if (!op_has_stress(c->op)) return c->fail(FH_UNSUPPORTED, "fh_assemble_scalar: the mass assembler has no scalar form");
     if (!out) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_scalar: out is null");
     rc = reset_status(c);
     if (rc) return rc;
@@ -490,19 +490,19 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
 // ---- the matrix-free map: y = T(u) x with T(u) = dr/du at the context's u (the matrix fh_assemble_matrix forms for the same context), and
 // its diagonal, without a pattern or values.  For FH_LAPLACE and FH_LINEAR_ELASTIC the element vector is linear in u, so T(u) is the
 // operator A of LinearOperator::apply (fenris-sparse/src/cg.rs:16-18) for every u, and the residual of the operand IS  A x:  the element pass
-// of the residual, fed x in place of the context's u.  For FH_NEO_HOOKEAN and FH_STVK the element pass gathers u and the operand per
+// of the residual, fed x in place of the context's u.  For FH_NEO_HOOKEAN, FH_STVK and FH_STABLE_NEO_HOOKEAN the element pass gathers u and the operand per
 // element and forms dP(F)[grad x^T] per point (tangent_lin / tangent_apply, material.hpp).  On the tiles (Hex8, Tet4, Quad4, Tri3
 // without a rule-set table) the node pass overwrites y, applies the Dirichlet rows on store and leaves the partials of x . y for CG;
 // otherwise every group of a rule-set table takes the tiles where they cover it, else the per-element kernels, all accumulating into a
 // zeroed y, and one more pass over y does the same.  Homogeneous Dirichlet nodes make the map the one fh_apply_dirichlet_csr_dev leaves
 // (global.rs:379-451): the element pass reads x with their entries zeroed (their columns vanish), their rows are  scale x.
 // LinearElastic: the element pass reads x 2^-e with |x 2^-e|_inf in [1/2, 1) (mf_exponent, device_common.hpp).
-// max_op: FH_LINEAR_ELASTIC for the operator's entry points, FH_STVK for the tangent's.
-int mf_ready(fh_ctx* c, const char* who, int max_op) {
-    if (c->op > max_op)
-        return c->fail(FH_UNSUPPORTED, std::string(who) + (max_op == FH_LINEAR_ELASTIC
+// scope: MF_OPERATOR for the operator's entry points (the operators linear in u), MF_TANGENT for the tangent's (every operator with a stress).
+int mf_ready(fh_ctx* c, const char* who, int scope) {
+    if (c->op >= 0 && (!op_has_stress(c->op) || (scope == MF_OPERATOR && op_depends_on_u(c->op))))   // (no operator yet: check_ready says so)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + (scope == MF_OPERATOR
                                                                ? ": the matrix-free operator covers FH_LAPLACE and FH_LINEAR_ELASTIC only"
-                                                               : ": the matrix-free tangent covers FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN and FH_STVK"));
+                                                               : ": the matrix-free tangent covers FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK and FH_STABLE_NEO_HOOKEAN"));
     const int rc = check_ready(c, who, false);
     if (rc) return rc;
     if (c->S() < 1 || c->S() > 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": solution dim must be 1..3");
@@ -687,10 +687,10 @@ int mf_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch,
 }
 
 // the entry points: y = T(u) x (the scale of the Dirichlet rows formed again only when what it depends on has changed), and the diagonal
-static int mf_apply_entry(fh_ctx* c, const char* who, int max_op, const double* x_dev, double* y_dev) {
+static int mf_apply_entry(fh_ctx* c, const char* who, int scope, const double* x_dev, double* y_dev) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
-    int rc = mf_ready(c, who, max_op);
+    int rc = mf_ready(c, who, scope);
     if (rc) return rc;
     if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (c->N == 0) return FH_OK;
@@ -710,10 +710,10 @@ static int mf_apply_entry(fh_ctx* c, const char* who, int max_op, const double* 
     return read_status(c, nullptr);
 }
 
-static int mf_diagonal_entry(fh_ctx* c, const char* who, int max_op, double* diag_dev) {
+static int mf_diagonal_entry(fh_ctx* c, const char* who, int scope, double* diag_dev) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
-    int rc = mf_ready(c, who, max_op);
+    int rc = mf_ready(c, who, scope);
     if (rc) return rc;
     if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (c->N == 0) return FH_OK;
@@ -730,7 +730,7 @@ static int mf_diagonal_entry(fh_ctx* c, const char* who, int max_op, double* dia
 // of x . y.  beta == 0 runs no stiffness work and does not read u; alpha == 0 runs the tangent alone.  Dirichlet nodes: the matrix
 // fh_apply_dirichlet_csr_dev leaves of the assembled alpha M + beta K(u) (its scale from the shifted diagonal).
 int mf_shift_ready(fh_ctx* c, const char* who, double alpha, double beta) {
-    const int rc = mf_ready(c, who, FH_STVK);
+    const int rc = mf_ready(c, who, MF_TANGENT);
     if (rc) return rc;
     if (!std::isfinite(alpha) || !std::isfinite(beta)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": alpha and beta must be finite");
     if (alpha != 0.0 && c->mass_rho_n == 0) return c->fail(FH_INVALID_STATE, std::string(who) + ": alpha != 0 needs fh_set_mass_density");
@@ -1057,13 +1057,13 @@ int fh_set_operator_dirichlet_nodes(fh_ctx* c, const uint64_t* nodes, uint64_t n
 }
 
 int fh_apply_operator_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
-    return mf_apply_entry(c, "fh_apply_operator_dev", FH_LINEAR_ELASTIC, x_dev, y_dev);
+    return mf_apply_entry(c, "fh_apply_operator_dev", MF_OPERATOR, x_dev, y_dev);
 }
-int fh_operator_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_operator_diagonal_dev", FH_LINEAR_ELASTIC, diag_dev); }
+int fh_operator_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_operator_diagonal_dev", MF_OPERATOR, diag_dev); }
 int fh_apply_tangent_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
-    return mf_apply_entry(c, "fh_apply_tangent_dev", FH_STVK, x_dev, y_dev);
+    return mf_apply_entry(c, "fh_apply_tangent_dev", MF_TANGENT, x_dev, y_dev);
 }
-int fh_tangent_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_tangent_diagonal_dev", FH_STVK, diag_dev); }
+int fh_tangent_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_tangent_diagonal_dev", MF_TANGENT, diag_dev); }
 
 int fh_set_mass_density(fh_ctx* c, const double* rho, uint64_t count) {
     if (!c) return FH_BAD_ARGUMENT;
@@ -1083,7 +1083,7 @@ int fh_set_mass_density(fh_ctx* c, const double* rho, uint64_t count) {
 int fh_apply_shifted_tangent_dev(fh_ctx* c, double alpha, double beta, const double* x_dev, double* y_dev) {
     if (!c) return FH_BAD_ARGUMENT;
     const char* who = "fh_apply_shifted_tangent_dev";
-    if (alpha == 0.0 && beta == 1.0) return mf_apply_entry(c, who, FH_STVK, x_dev, y_dev);
+    if (alpha == 0.0 && beta == 1.0) return mf_apply_entry(c, who, MF_TANGENT, x_dev, y_dev);
     DevGuard dev_guard_(c->device);
     int rc = mf_shift_ready(c, who, alpha, beta);
     if (rc) return rc;
@@ -1108,7 +1108,7 @@ int fh_apply_shifted_tangent_dev(fh_ctx* c, double alpha, double beta, const dou
 int fh_shifted_tangent_diagonal_dev(fh_ctx* c, double alpha, double beta, double* diag_dev) {
     if (!c) return FH_BAD_ARGUMENT;
     const char* who = "fh_shifted_tangent_diagonal_dev";
-    if (alpha == 0.0 && beta == 1.0) return mf_diagonal_entry(c, who, FH_STVK, diag_dev);
+    if (alpha == 0.0 && beta == 1.0) return mf_diagonal_entry(c, who, MF_TANGENT, diag_dev);
     DevGuard dev_guard_(c->device);
     int rc = mf_shift_ready(c, who, alpha, beta);
     if (rc) return rc;

@@ -1,5 +1,7 @@
 // Dense element matrices of tri-quadratic hexahedra (Hex27, s = 3) on the fp64 matrix cores -- round 6 form of the first pass of the two-pass
 // owner-computes assembly (LinearElastic / NeoHookean, uniform quadrature table of 27 points).
+// These two laws only: StVK and Stable Neo-Hookean have other contractions (FH_STABLE_NEO_HOOKEAN: four terms, one of them antisymmetric) and take
+// the generic first pass k_assemble_matrix<dump>.
 //
 // Per quadrature point the stress contraction of both materials has the form (fenris-solid/src/materials.rs:108-118, 302-313)
 //     C(I, J)[i][j] = c_l a_I[i] a_J[j]  -  c_a a_J[i] a_I[j]  +  delta_ij c_m g_I . g_J

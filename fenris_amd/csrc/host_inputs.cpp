@@ -897,4 +897,12 @@ int fh_lame_from_young_poisson(double young, double poisson, double* mu, double*
     return FH_OK;
 }
 
+int fh_stable_neo_hookean_parameters(uint32_t dim, double mu_lame, double lambda_lame, double* mu, double* lambda) {
+    if ((dim != 2 && dim != 3) || !mu || !lambda) return FH_BAD_ARGUMENT;
+    const double d = (double)dim;
+    *mu = (d + 1.0) / d * mu_lame;
+    *lambda = lambda_lame + mu_lame - 2.0 * mu_lame / (d * (d + 1.0));
+    return FH_OK;
+}
+
 }  // extern "C"

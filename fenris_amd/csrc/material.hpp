@@ -37,9 +37,84 @@ __device__ __forceinline__ void green_strain(const double (&F)[D][D], double (&E
         }
 }
 
+// gamma = det(I + U) - 1 expanded in U, so that it keeps its relative precision where det F is close to 1 (logdet.rs:17-86)
+template <int D>
+__device__ __forceinline__ double det_minus_one(const double (&U)[D][D]) {
+    if constexpr (D == 2) {
+        return U[0][0] * U[1][1] + U[0][0] + U[1][1] - U[0][1] * U[1][0];
+    } else {
+        const double u11 = U[0][0], u22 = U[1][1], u33 = U[2][2];
+        const double aa = 1.0 + u11, e2 = 1.0 + u22, i2 = 1.0 + u33;
+        const double b = U[0][1], c = U[0][2], d2 = U[1][0], f = U[1][2], g = U[2][0], h = U[2][1];
+        return u11 * u22 * u33 + u11 * u22 + u11 * u33 + u22 * u33 + u11 + u22 + u33 + b * f * g + c * d2 * h -
+               c * e2 * g - b * d2 * i2 - aa * f * h;
+    }
+}
+// cof F = dJ/dF, and its derivative along H written out from the entries (linear in H): the H x F cross terms in 3-D, the 2 x 2 swap in 2-D
+template <int D>
+__device__ __forceinline__ void cofactor(const double (&F)[D][D], double (&C)[D][D]) {
+    if constexpr (D == 2) {
+        C[0][0] = F[1][1]; C[0][1] = -F[1][0];
+        C[1][0] = -F[0][1]; C[1][1] = F[0][0];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+                C[i][j] = F[i1][j1] * F[i2][j2] - F[i1][j2] * F[i2][j1];
+            }
+    }
+}
+template <int D>
+__device__ __forceinline__ void cofactor_lin(const double (&F)[D][D], const double (&H)[D][D], double (&dC)[D][D]) {
+    if constexpr (D == 2) {
+        dC[0][0] = H[1][1]; dC[0][1] = -H[1][0];
+        dC[1][0] = -H[0][1]; dC[1][1] = H[0][0];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+                dC[i][j] = fma(H[i1][j1], F[i2][j2], F[i1][j1] * H[i2][j2]) - fma(H[i1][j2], F[i2][j1], F[i1][j2] * H[i2][j1]);
+            }
+    }
+}
+// What Stable Neo-Hookean takes from grad u at a point (fenris_hip.h, FH_STABLE_NEO_HOOKEAN): F, cof F, c = F:F - d and gamma = det F - 1.
+// Polynomial in U; nothing here or in what follows branches on det F.
+template <int D, int S>
+__device__ __forceinline__ void snh_kinematics(const double (&gu)[D][S], double (&F)[D][D], double (&C)[D][D], double& c, double& gamma) {
+    static_assert(S == D, "a deformation gradient needs a vector field");
+    double U[D][D];
+    double trU = 0.0, nn = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            U[i][j] = gu[j][i];
+            F[i][j] = (i == j ? 1.0 : 0.0) + U[i][j];
+            nn = fma(U[i][j], U[i][j], nn);
+        }
+#pragma unroll
+    for (int i = 0; i < D; ++i) trU += U[i][i];
+    c = fma(2.0, trU, nn);
+    gamma = det_minus_one<D>(U);
+    cofactor<D>(F, C);
+}
+// its three coefficients: a0 = mu (1 - 1/m) written as mu (d + c)/m, a1 = 2 mu/m^2 and b = lambda gamma - k with m = d + 1 + c >= 1 and
+// k = mu d/(d + 1).  At F = I (c = 0, gamma = 0) a0 and k are the same product, so P(I) = a0 I - k I = 0 exactly.
+template <int D>
+__device__ __forceinline__ void snh_coefficients(double mu, double lambda, double c, double gamma, double& a0, double& a1, double& b) {
+    const double m = (double)(D + 1) + c;
+    a0 = mu * (((double)D + c) / m);
+    a1 = 2.0 * mu / (m * m);
+    b = fma(lambda, gamma, -(mu * ((double)D / (double)(D + 1))));
+}
+
 // stress P (s x d) and energy density psi of one quadrature point from grad u (d x s):
 // laplace.rs:26-73; fenris-solid/src/materials.rs:71-123 (LinearElastic), 236-353 (NeoHookean, J <= 0 => NaN block / inf),
-// 392-469 (StVK).
+// 392-469 (StVK); Stable Neo-Hookean: fenris_hip.h, FH_STABLE_NEO_HOOKEAN (finite for every F).
 template <int OP, int D, int S, int WHAT>
 __device__ __forceinline__ void material_point(const double (&gu)[D][S], double mu, double lambda, double (&P)[S][D], double& psi) {
     psi = 0.0;
@@ -47,6 +122,18 @@ __device__ __forceinline__ void material_point(const double (&gu)[D][S], double 
 #pragma unroll
         for (int k = 0; k < D; ++k) { P[0][k] = gu[k][0]; psi = fma(gu[k][0], gu[k][0], psi); }
         psi *= 0.5;
+    } else if constexpr (OP == FH_STABLE_NEO_HOOKEAN) {
+        double F[D][D], C[D][D];
+        double c, gamma;
+        snh_kinematics<D, S>(gu, F, C, c, gamma);
+        double a0, a1, b;
+        snh_coefficients<D>(mu, lambda, c, gamma, a0, a1, b);
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) P[i][j] = fma(a0, F[i][j], b * C[i][j]);
+        if constexpr (WHAT == EP_SCALAR)
+            psi = (0.5 * mu) * (c - log1p(c / (double)(D + 1))) + (0.5 * lambda) * (gamma * gamma) - mu * ((double)D / (double)(D + 1)) * gamma;
     } else {
         double F[D][D];
         deformation_gradient<D, S>(gu, F);
@@ -90,16 +177,7 @@ __device__ __forceinline__ void material_point(const double (&gu)[D][S], double 
                 for (int i = 0; i < D; ++i)
 #pragma unroll
                     for (int j = 0; j < D; ++j) U[i][j] = gu[j][i];
-                double gamma;
-                if constexpr (D == 2) {
-                    gamma = U[0][0] * U[1][1] + U[0][0] + U[1][1] - U[0][1] * U[1][0];
-                } else {
-                    const double u11 = U[0][0], u22 = U[1][1], u33 = U[2][2];
-                    const double aa = 1.0 + u11, e2 = 1.0 + u22, i2 = 1.0 + u33;
-                    const double b = U[0][1], c = U[0][2], d2 = U[1][0], f = U[1][2], g = U[2][0], h = U[2][1];
-                    gamma = u11 * u22 * u33 + u11 * u22 + u11 * u33 + u22 * u33 + u11 + u22 + u33 + b * f * g + c * d2 * h -
-                            c * e2 * g - b * d2 * i2 - aa * f * h;
-                }
+                const double gamma = det_minus_one<D>(U);
                 if (gamma > -1.0) {
                     const double logJ = log1p(gamma);
                     double trU = 0.0, nn = 0.0;
@@ -144,6 +222,7 @@ __device__ __forceinline__ void material_point(const double (&gu)[D][S], double 
 //   LinearElastic  mu (H + H^T) + lambda tr(H) I
 //   NeoHookean     mu H + lambda tr(F^-1 H) F^-T + (mu - lambda ln J) F^-T H^T F^-T        (J <= 0: NaN, materials.rs:297-300)
 //   StVK           H S + F (lambda tr(dE) I + 2 mu dE),  S = lambda tr(E) I + 2 mu E,  dE = sym(F^T H)
+//   Stable NH      mu (1 - 1/m) H + 2 mu/m^2 (F:H) F + lambda (cof F:H) cof F + (lambda gamma - k) dcof(F)[H],  m = d + 1 + F:F - d
 // which is  sum_b C(F; g_a, g_b) x_b  with C the stress contraction the assembled K(u) is made of (materials.rs:287-315 and 417-439).
 // TangentLin holds what depends on u alone (formed once per point); tangent_apply is linear in grad x.
 template <int OP, int D>
@@ -152,10 +231,23 @@ struct TangentLin {
     double F[D][D];            // NeoHookean: F^-1; StVK: F
     double Sg[D][D];           // StVK: the second Piola-Kirchhoff stress S
 };
+template <int D>
+struct TangentLin<FH_STABLE_NEO_HOOKEAN, D> {
+    double a0, a1, lambda, b;   // mu (1 - 1/m), 2 mu/m^2, lambda, lambda gamma - k
+    double F[D][D], C[D][D];    // F and cof F
+};
 template <int OP, int D, int S>
 __device__ __forceinline__ void tangent_lin(const double (&gu)[D][S], double mu, double lambda, TangentLin<OP, D>& L) {
-    L.mu = mu;
-    L.lambda = lambda;
+    if constexpr (OP == FH_STABLE_NEO_HOOKEAN) {
+        double c, gamma;
+        snh_kinematics<D, S>(gu, L.F, L.C, c, gamma);
+        snh_coefficients<D>(mu, lambda, c, gamma, L.a0, L.a1, L.b);
+        L.lambda = lambda;
+        return;
+    } else {
+        L.mu = mu;
+        L.lambda = lambda;
+    }
     if constexpr (OP == FH_NEO_HOOKEAN || OP == FH_STVK) {
         double F[D][D];
         deformation_gradient<D, S>(gu, F);
@@ -224,6 +316,23 @@ __device__ __forceinline__ void tangent_apply(const TangentLin<OP, D>& L, const 
                 for (int k = 0; k < D; ++k) b = fma(A[j][k], L.F[k][i], b);
                 dP[i][j] = fma(L.beta, b, fma(lt, L.F[j][i], L.mu * gx[j][i]));
             }
+    } else if constexpr (OP == FH_STABLE_NEO_HOOKEAN) {
+        double H[D][D], dC[D][D];
+        double fh = 0.0, ch = 0.0;   // F:H, cof F:H
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                H[i][j] = gx[j][i];
+                fh = fma(L.F[i][j], H[i][j], fh);
+                ch = fma(L.C[i][j], H[i][j], ch);
+            }
+        cofactor_lin<D>(L.F, H, dC);
+        const double f1 = L.a1 * fh, c1 = L.lambda * ch;
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) dP[i][j] = fma(L.a0, H[i][j], fma(f1, L.F[i][j], fma(c1, L.C[i][j], L.b * dC[i][j])));
     } else {   // StVK
         double C[D][D];   // F^T H
 #pragma unroll

@@ -422,10 +422,10 @@ __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N,
             for (int k = 0; k < S; ++k) {
                 const double xv = x[(size_t)nodes[n] * S + k];
                 double uv = 0.0;
-                if constexpr (OP >= FH_NEO_HOOKEAN) uv = a.u ? a.u[(size_t)nodes[n] * S + k] : 0.0;
+                if constexpr (op_depends_on_u(OP)) uv = a.u ? a.u[(size_t)nodes[n] * S + k] : 0.0;
 #pragma unroll
                 for (int r = 0; r < D; ++r) {
-                    if constexpr (OP >= FH_NEO_HOOKEAN) gu[r][k] = fma(g[r], uv, gu[r][k]);
+                    if constexpr (op_depends_on_u(OP)) gu[r][k] = fma(g[r], uv, gu[r][k]);
                     gx[r][k] = fma(g[r], xv, gx[r][k]);
                 }
             }
@@ -533,7 +533,7 @@ __global__ void __launch_bounds__(256) k_mf_diagonal_elements(const KArgs a, int
         for (int r = 0; r < D; ++r)
 #pragma unroll
             for (int k = 0; k < S; ++k) gu[r][k] = 0.0;
-        if constexpr (OP >= FH_NEO_HOOKEAN) {
+        if constexpr (op_depends_on_u(OP)) {
             for (int n = 0; n < N; ++n) {
                 double g[D];
                 mf_grad<D>(a, N, q, n, Ji, g);

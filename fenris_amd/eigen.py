@@ -38,7 +38,7 @@ class EigenSolveError(FenrisError):
 
 
 class MatrixFreeEigensolver:
-    """LOBPCG for the lowest modes of T(u) phi = lambda M phi on an element assembler (Laplace, LinearElastic, NeoHookean, StVK): T(u) is
+    """LOBPCG for the lowest modes of T(u) phi = lambda M phi on an element assembler (Laplace, LinearElastic, NeoHookean, StVK, StableNeoHookean): T(u) is
     MatrixFreeTangent's map at the assembler's u, M the mass of MatrixFreeShiftedTangent with this object's density.  Dirichlet nodes,
     density and shift belong to this object and are handed to the engine before every solve, so it may share an assembler with other
     matrix-free objects.  On a free body give with_shift(sigma), sigma > 0 of the order of the first elastic eigenvalue."""

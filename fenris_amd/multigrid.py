@@ -27,10 +27,13 @@ def _injection(transfer):
     return inj
 
 
+_NONLINEAR = (_ffi.NEO_HOOKEAN, _ffi.STVK, _ffi.STABLE_NEO_HOOKEAN)   # their levels need a u
+
+
 class GeometricMultigrid:
     """V-cycle preconditioner over coarse_meshes (coarsest first) and transfers (transfers[k]: coarse_meshes[k] -> the next finer mesh, the
     last one -> the fine assembler's mesh; Transfer objects of fenris_amd.refinement).  coarse_operator "tangent": the fine operator on
-    every level (NeoHookean and StVK levels receive the fine u by injection at each solve); "linearized": LinearElastic with the same Lame
+    every level (NeoHookean, StVK and StableNeoHookean levels receive the fine u by injection at each solve); "linearized": LinearElastic with the same Lame
     data on the coarse levels (the tangent at u = 0).  degree, smoothing_range: the Chebyshev-Jacobi smoother (fh_mg_set_smoother)."""
 
     def __init__(self, fine_assembler, coarse_meshes, transfers, coarse_operator="tangent", degree=3, smoothing_range=15.0, eig_steps=10):
@@ -47,13 +50,13 @@ class GeometricMultigrid:
         self.engine = fine_assembler.engine
         self.degree, self.smoothing_range, self.eig_steps = int(degree), float(smoothing_range), int(eig_steps)
         op = fine_assembler.op
-        nonlinear = op.op_kind in (_ffi.NEO_HOOKEAN, _ffi.STVK)
+        nonlinear = op.op_kind in _NONLINEAR
         cop = MaterialEllipticOperator(LinearElasticMaterial()) if (coarse_operator == "linearized" and nonlinear) else op
         s = self.engine.solution_dim()
         self.levels = []
         for m in coarse_meshes:
             eng = Engine(self.engine.device)
-            u = np.zeros(s * m.num_nodes()) if cop.op_kind in (_ffi.NEO_HOOKEAN, _ffi.STVK) else None
+            u = np.zeros(s * m.num_nodes()) if cop.op_kind in _NONLINEAR else None
             self.levels.append(ElementEllipticAssembler(eng, m, cop, qt, u))
         self.transfers = [self._check_transfer(t, k) for k, t in enumerate(transfers)]
         self._inj = [_injection(t) for t in self.transfers]

@@ -25,6 +25,15 @@ class LameParameters:
         _ffi.lib().fh_lame_from_young_poisson(yp.young, yp.poisson, C.byref(mu), C.byref(lam))
         return cls(mu.value, lam.value)
 
+    def for_stable_neo_hookean(self, dim):
+        """the (mu, lambda) of StableNeoHookeanMaterial that linearise at F = I to these Lame parameters in ``dim`` dimensions
+        (fh_stable_neo_hookean_parameters); pass the result as the quadrature data of that material"""
+        mu, lam = C.c_double(), C.c_double()
+        rc = _ffi.lib().fh_stable_neo_hookean_parameters(int(dim), self.mu, self.lambda_, C.byref(mu), C.byref(lam))
+        if rc != 0:
+            raise _ffi.FenrisError(rc, "LameParameters.for_stable_neo_hookean: dim must be 2 or 3")
+        return type(self)(mu.value, lam.value)
+
     def as_pair(self):
         return (self.mu, self.lambda_)
 
@@ -49,6 +58,14 @@ class NeoHookeanMaterial:
 class StVKMaterial:
     """materials.rs:370-469"""
     op_kind = _ffi.STVK
+
+
+class StableNeoHookeanMaterial:
+    """Stable Neo-Hookean (Smith, de Goes, Kim 2018; FH_STABLE_NEO_HOOKEAN in include/fenris_hip.h): energy, stress and tangent finite for
+    every F, inverted (det F < 0) and flattened (det F = 0) elements included.  Its (mu, lambda) per point are its own:
+    ``LameParameters(..).for_stable_neo_hookean(dim)`` converts a Lame pair so that the linearisation at rest is that LinearElasticMaterial.
+    At inverted states the tangent is indefinite (no per-element projection)."""
+    op_kind = _ffi.STABLE_NEO_HOOKEAN
 
 
 class TensorEllipticOperator:

@@ -93,7 +93,20 @@ enum { FH_LAPLACE = 0, FH_LINEAR_ELASTIC = 1, FH_NEO_HOOKEAN = 2, FH_STVK = 3,
         * with one tensor A per quadrature point (fh_set_operator_tensor).  Covers every LINEAR elliptic operator -- anisotropic elasticity,
         * a linearisation frozen at some state, operators that are not symmetric -- without a closure crossing the boundary; a caller
         * with a nonlinear operator evaluates its tangent at the quadrature data it owns.  Stiffness matrix only (all scatter modes). */
-       FH_TENSOR = 6 };
+       FH_TENSOR = 6,
+       /* Stable Neo-Hookean (Smith, de Goes, Kim 2018), rest value subtracted and its alpha eliminated: finite for EVERY F, det F <= 0 included,
+        * with no branch on det F.  With U = (grad u)^T, F = I + U, c = 2 tr U + U:U (= F:F - d), gamma = det F - 1 (expanded in U, never
+        * det(F) - 1), k = mu d / (d + 1), cof F = dJ/dF and m = d + 1 + c (>= 1):
+        *     psi     = mu/2 [c - log1p(c / (d + 1))] + lambda/2 gamma^2 - k gamma
+        *     P       = mu (1 - 1/m) F + (lambda gamma - k) cof F
+        *     C(a, b) = mu (1 - 1/m) (a.b) I + 2 mu/m^2 (F a)(F b)^T + lambda (cof F a)(cof F b)^T + (lambda gamma - k) G(a, b)
+        *     G(a, b)[i][k] = sum_jl a[j] (d cof F[i][j] / d F[k][l]) b[l]:   d = 3: G v = v x w with w = F (a x b);
+        *                                                                     d = 2: (a0 b1 - a1 b0) [[0, 1], [-1, 0]]
+        * mu, lambda are the law's own pair per point; they linearise at F = I to the Lame pair mu_L = mu d/(d+1),
+        * lambda_L = lambda + 2 mu/(d+1)^2 - mu d/(d+1) (fh_stable_neo_hookean_parameters converts).  lambda = 0 is allowed.  Everything the
+        * other two nonlinear laws have: matrix, residual, energy, matrix-free tangent, solvers, recovery.  At inverted states K(u) is
+        * indefinite (no per-element projection). */
+       FH_STABLE_NEO_HOOKEAN = 7 };
 
 /* how K_e contributions reach the CSR values (flags argument of fh_assemble_matrix*):
  *   FH_SCATTER_ATOMIC  : element-parallel, fp64 atomic adds (replaces the rayon colour loop)
@@ -107,7 +120,7 @@ enum { FH_SCATTER_ATOMIC = 0, FH_SCATTER_COLORED = 1, FH_SCATTER_GATHER = 2, FH_
 enum { FH_ASSEMBLE_OVERWRITE = 0x100 };
 /* OR-in FH_ASSEMBLE_REPRODUCIBLE (with FH_SCATTER_GATHER) to get the same bits from run to run and from launch geometry to launch geometry, like the
  * reference's coloured loop (global.rs:322-373: every entry is a sum in a fixed order).  The row-owner kernels (affine and general Hex8 with the
- * eight-point rule, Tet4) and the two-pass form (Hex27, NeoHookean, StVK) already are; the configurations whose one-pass kernel accumulates with
+ * eight-point rule, Tet4) and the two-pass form (Hex27, NeoHookean, StVK, Stable Neo-Hookean) already are; the configurations whose one-pass kernel accumulates with
  * LDS atomics in hardware order (Quad4 / Tri3, Hex8 with other rules or per-point parameters) take the two-pass form instead -- slower, and the
  * dense element matrices need E (s n)^2 doubles (9 E n (n + 1) / 2 for 3 x 3 blocks on the 3D elements: node-block triangles); FH_UNSUPPORTED under a row range.  FH_SCATTER_COLORED is reproducible as it is;
  * FH_SCATTER_ATOMIC never is (FH_BAD_ARGUMENT with this flag). */
@@ -592,6 +605,10 @@ int fh_reorder_mesh(uint64_t num_vertices, uint64_t nodes_per_element, const uin
                     uint64_t* vertex_perm, uint64_t* connectivity_perm);
 /* LameParameters::from(YoungPoisson) (fenris-solid/src/materials.rs:31-43) */
 int fh_lame_from_young_poisson(double young, double poisson, double* mu, double* lambda);
+/* The (mu, lambda) of FH_STABLE_NEO_HOOKEAN whose linearisation at F = I has the Lame parameters (mu_lame, lambda_lame) in dimension dim:
+ * mu = (d + 1)/d mu_lame, lambda = lambda_lame + mu_lame - 2 mu_lame / (d (d + 1))  (d = 3: 4/3 mu_lame and lambda_lame + 5/6 mu_lame).
+ * FH_BAD_ARGUMENT for a dim other than 2 or 3 or a null pointer. */
+int fh_stable_neo_hookean_parameters(uint32_t dim, double mu_lame, double lambda_lame, double* mu, double* lambda);
 
 /* ---- introspection for benchmarks --------------------------------------------------------------- */
 /* name of the device kernel the last fh_assemble_matrix* call launched (for rocprof matching) */
@@ -650,8 +667,8 @@ int fh_cg_solve_matrix_free_dev(fh_ctx*, const double* b_dev, double* x_dev, int
  * FH_UNSUPPORTED for the mass operators and FH_TENSOR; FH_INVALID_STATE for a missing mesh, operator or table; FH_SINGULAR_JACOBIAN as the
  * residual reports it.  Dirichlet nodes: those of fh_set_operator_dirichlet_nodes, with the same meaning as for fh_apply_operator_dev (the
  * matrix fh_apply_dirichlet_csr_dev leaves of the assembled K(u); scale = |first nonzero diagonal entry| of K(u) in row order, or 1).  The scale
- * is the operator's cache, formed again after the mesh, vertices, operator, table or element mask have changed, and for FH_NEO_HOOKEAN and
- * FH_STVK also after u has changed.
+ * is the operator's cache, formed again after the mesh, vertices, operator, table or element mask have changed, and for FH_NEO_HOOKEAN,
+ * FH_STVK and FH_STABLE_NEO_HOOKEAN also after u has changed.
  *
  * y = T(u) x, both s N doubles on the device; y is OVERWRITTEN, u is read and not changed.  Deterministic on every element kind (no
  * floating-point atomics). */
@@ -668,7 +685,7 @@ int fh_cg_solve_tangent_dev(fh_ctx*, const double* b_dev, double* x_dev, int pre
 /* ---- matrix-free shifted tangent for implicit time stepping: (alpha M + beta T(u)) Delta = b, e.g. backward Euler alpha = 1, beta = dt^2.
  * M is the mass matrix the assembled FH_MASS_SCALAR / FH_MASS_VECTOR form on the same mesh and quadrature table, M_IJ = I_s sum_q w |det J|
  * rho phi_I phi_J with s the context operator's solution dim (Laplace: the scalar mass, the materials: the vector mass), rho the density of
- * fh_set_mass_density; T(u) is fh_apply_tangent_dev's map.  Operators: FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK (mass operators
+ * fh_set_mass_density; T(u) is fh_apply_tangent_dev's map.  Operators: FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK, FH_STABLE_NEO_HOOKEAN (mass operators
  * and FH_TENSOR: FH_UNSUPPORTED).  alpha != 0 without a density: FH_INVALID_STATE; alpha and beta not finite: FH_BAD_ARGUMENT.  alpha == 0
  * runs the tangent's kernels alone (alpha == 0, beta == 1: exactly fh_apply_tangent_dev); beta == 0 runs no stiffness work and does not read
  * u.  It honours every element kind, every table form, the element mask and the Dirichlet nodes of fh_set_operator_dirichlet_nodes, with the
@@ -709,7 +726,7 @@ int fh_cg_solve_shifted_tangent_dev(fh_ctx*, double alpha, double beta, const do
  * their rows and so is the step, so those entries of u come back bit for bit.  f_dev (the load) and u_ref_dev: S N doubles, or null for zero.
  * u_dev: the guess on entry (with the Dirichlet values); on return the iterate the reference leaves in x -- the solution, or on failure the
  * last iterate (for FH_NEWTON_LINE_SEARCH_FAILED from the search: the last trial).  The context's u (fh_set_u*) holds the same on return and
- * u_gen has moved.  Operators: FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK (mass operators, FH_TENSOR: FH_UNSUPPORTED); alpha != 0
+ * u_gen has moved.  Operators: FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN, FH_STVK, FH_STABLE_NEO_HOOKEAN (mass operators, FH_TENSOR: FH_UNSUPPORTED); alpha != 0
  * without fh_set_mass_density: FH_INVALID_STATE; alpha, beta or tolerance not finite, a null u, an unknown line search or preconditioner:
  * FH_BAD_ARGUMENT.  It honours the element kinds, table forms and element masks of the residual.  The residual and its norm come from one node
  * pass over the tile partials on Hex8, Tet4, Quad4 and Tri3 (no rule-set table); elsewhere from element vectors summed per node in a fixed
@@ -782,7 +799,7 @@ int fh_eigs_lowest(fh_ctx*, uint32_t m, double shift, int preconditioner, double
                    double* residual_norms, uint64_t* stats);
 int fh_eigs_profile(fh_ctx*, double* seconds);
 /* ---- time integration on the device:  M a + r(u) = lf_n f  with r the context's residual (FH_LAPLACE, FH_LINEAR_ELASTIC, FH_NEO_HOOKEAN,
- * FH_STVK; mass operators and FH_TENSOR: FH_UNSUPPORTED), M the mass of fh_set_mass_density (none: FH_INVALID_STATE) and
+ * FH_STVK, FH_STABLE_NEO_HOOKEAN; mass operators and FH_TENSOR: FH_UNSUPPORTED), M the mass of fh_set_mass_density (none: FH_INVALID_STATE) and
  * lf_n = load_factor[min(n, count - 1)] (null: 1), n the global index of the step being computed (the state of fh_dynamics_set_state is
  * step 0).  The Dirichlet nodes of fh_set_operator_dirichlet_nodes are held at the u of fh_dynamics_set_state with v = a = 0; those entries
  * of u come back bit for bit.  The handle uses the context's u as u_n: fh_set_u* holds the last state afterwards, as after fh_newton_solve.
@@ -999,14 +1016,15 @@ int fh_estimate_H1_seminorm_error_squared_dev(fh_ctx*, uint32_t solution_dim, co
 /* ---- recovery: what a user reads off a solved field.  For the context's mesh, operator, quadrature table and u (fh_set_u*; zeros when
  * none is set), with s the operator's solution dimension and d the geometry dimension; every array is row-major doubles.
  *   FH_RECOVER_GRAD_U          d x s   g[i][k] = d u_k / d x_i (the convention of fh_estimate_H1_seminorm_error_squared)
- *   FH_RECOVER_STRAIN          d x d   FH_LINEAR_ELASTIC: sym(grad u); FH_NEO_HOOKEAN, FH_STVK: Green-Lagrange (F^T F - I) / 2 with
+ *   FH_RECOVER_STRAIN          d x d   FH_LINEAR_ELASTIC: sym(grad u); FH_NEO_HOOKEAN, FH_STVK, FH_STABLE_NEO_HOOKEAN: Green-Lagrange (F^T F - I) / 2 with
  *                                      F = I + (grad u)^T (fenris-solid/src/lib.rs:20-29); the full symmetric matrix
  *   FH_RECOVER_STRESS_PK1      s x d   the operator's stress P (fenris-solid/src/materials.rs), the flux grad u for FH_LAPLACE;
- *                                      NeoHookean with det F <= 0: NaN, as in the residual
- *   FH_RECOVER_STRESS_CAUCHY   d x d   P F^T / det F for NeoHookean and StVK (NaN when det F <= 0), P for LinearElastic
+ *                                      NeoHookean with det F <= 0: NaN, as in the residual; Stable Neo-Hookean: finite for every F
+ *   FH_RECOVER_STRESS_CAUCHY   d x d   P F^T / det F for NeoHookean, StVK and Stable Neo-Hookean (NaN when det F <= 0, for Stable
+ *                                      Neo-Hookean too: its P is finite there, the push-forward is not defined), P for LinearElastic
  *   FH_RECOVER_VON_MISES       1       of the Cauchy stress: sqrt(3/2 dev : dev) in 3-D; in 2-D the IN-PLANE form
  *                                      sqrt(sxx^2 - sxx syy + syy^2 + 3 sxy^2) (no out-of-plane stress is assumed or added)
- *   FH_RECOVER_ENERGY_DENSITY  1       psi; NeoHookean: +inf when det F <= 0
+ *   FH_RECOVER_ENERGY_DENSITY  1       psi; NeoHookean: +inf when det F <= 0; Stable Neo-Hookean: finite for every F
  *   FH_RECOVER_VOLUME          1       sum_q w_q |det J_q|; FH_AT_ELEMENTS only
  * FH_LAPLACE has no strain, Cauchy or von Mises stress: FH_UNSUPPORTED, as are the mass operators and FH_TENSOR.
  * Locations:
