@@ -3,7 +3,7 @@
 Python host layer over the C ABI of libfenris_hip.so (include/fenris_hip.h).  Only the hot path of
 fenris -- global stiffness / residual assembly -- lives here; see DESIGN.md.
 """
-from . import _ffi, amg, assembly, boundary, degree, dynamics, eigen, interpolate, io, mesh, multigrid, operators, quadrature, recovery, refinement, reorder
+from . import _ffi, amg, assembly, boundary, contact, degree, dynamics, eigen, interpolate, io, mesh, multigrid, operators, quadrature, recovery, refinement, reorder
 from ._ffi import (ASSEMBLE_OVERWRITE, ASSEMBLE_REPRODUCIBLE, HEX8, HEX27, LAPLACE, LINEAR_ELASTIC, NEO_HOOKEAN, QUAD4, SCATTER_ATOMIC,
                    SCATTER_COLORED, SCATTER_GATHER, STVK, STABLE_NEO_HOOKEAN, PRECOND_IDENTITY, PRECOND_JACOBI, PRECOND_MULTIGRID, PRECOND_AMG, AMG_CONSTANT, AMG_RIGID_BODY, AMG_USER, TET4, TRI3, TET10, QUAD9, TRI6, HEX20, TET20, MASS_SCALAR, MASS_VECTOR, FenrisError, SingularJacobianError)
 from .assembly import (CsrAssembler, CsrMatrix, CsrParAssembler, DisjointSubsetsColors, ElementEllipticAssembler, ElementMassAssembler,
@@ -25,6 +25,7 @@ from .interpolate import FixedInterpolator, SpatiallyIndexed, ValuesOrGradients
 from .multigrid import GeometricMultigrid
 from .dynamics import (BackwardEuler, CentralDifference, DynamicsError, DynamicsRecord, FirstOrderIntegrator, FirstOrderRecord, ForwardEuler, Newmark,
                        RungeKuttaLegendre, ThetaMethod, TimeIntegrator)
+from .contact import Ball, Cavity, Contact, HalfSpace, Obstacles
 from .eigen import EigenResult, EigenSolveError, MatrixFreeEigensolver
 from .recovery import Recovery
 from .refinement import (Transfer, permute_transfer, refine_uniformly, refine_uniformly_repeat, refine_uniformly_repeat_with_transfers,

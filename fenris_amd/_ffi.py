@@ -58,6 +58,12 @@ class FirstOrderSettings(C.Structure):
                 ("linear_rel_tol", C.c_double), ("linear_max_iter", C.c_uint64)]
 
 
+class Obstacle(C.Structure):
+    """fh_obstacle"""
+
+    _fields_ = [("kind", C.c_int), ("stiffness", C.c_double), ("point", C.c_double * 3), ("normal", C.c_double * 3), ("radius", C.c_double)]
+
+
 class FenrisError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"fenris_hip error {code}: {message}")
@@ -186,6 +192,11 @@ _SIGS = {
     "fh_dynamics_state": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p, u64p]),
     "fh_dynamics_state_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f64p, u64p]),
     "fh_dynamics_stable_dt": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p]),
+    "fh_set_obstacles": (C.c_int, [C.c_void_p, C.POINTER(Obstacle), C.c_uint64, f64p]),
+    "fh_contact_energy": (C.c_int, [C.c_void_p, f64p]),
+    "fh_contact_force_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_contact_gap_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_add_contact_tangent_csr_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_mg_create": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(u64p), C.POINTER(u64p), C.POINTER(f64p),
                                C.POINTER(C.c_void_p)]),
     "fh_mg_destroy": (None, [C.c_void_p]),

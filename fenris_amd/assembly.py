@@ -21,6 +21,7 @@ from typing import Optional
 import numpy as np
 
 from . import _ffi
+from . import contact as _contact
 from .compose import _Composable, is_composed
 from . import compose as _compose
 from ._ffi import (ASSEMBLE_OVERWRITE, SCATTER_ATOMIC, SCATTER_COLORED, SCATTER_GATHER, FenrisError,
@@ -81,6 +82,7 @@ class Engine:
         self._mesh = mesh  # keep the host arrays alive
         self._mf_bound = None  # fh_set_mesh clears the operator's Dirichlet nodes
         self._mass_bound = None  # ... and the mass density
+        self._contact_bound = None  # ... and the obstacles of the penalty contact term
         self._drop_held()  # ... and drops a held refinement, degree coarsening and degree elevation
         self._check(self._lib.fh_set_mesh(self._h, mesh.elem_kind, _ffi.fp(mesh.vertices), mesh.num_nodes(),
                                           _ffi.up(mesh.connectivity), mesh.num_elements()))
@@ -90,6 +92,7 @@ class Engine:
         en_p = en if len(en) else np.zeros(1, dtype=np.uint64)
         self._mf_bound = None
         self._mass_bound = None
+        self._contact_bound = None
         self._drop_held()
         self._check(self._lib.fh_set_connectivity_ragged(self._h, sdim, num_nodes, _ffi.up(eo), _ffi.up(en_p), len(eo) - 1))
 
@@ -352,6 +355,7 @@ class Engine:
         """this engine's mesh becomes the mesh `other` holds, device to device"""
         self._mf_bound = None
         self._mass_bound = None
+        self._contact_bound = None
         self._check(fn(self._h, other._h))
         # no host arrays were given: what the engine's own methods ask of a mesh
         self._mesh = types.SimpleNamespace(elem_kind=held.kind, num_nodes=lambda: held.num_nodes, num_elements=lambda: held.num_cells)
@@ -501,6 +505,12 @@ class Engine:
         out = np.zeros((count, ld, ld))
         self._check(self._lib.fh_assemble_element_matrices(self._h, first, count, _ffi.fp(out)))
         return out.transpose(0, 2, 1).copy()  # column-major blocks -> [e][row][col]
+
+    def set_obstacles(self, obstacles):
+        """the rigid obstacles of the penalty contact term (fenris_amd.contact: an Obstacles, a list of obstacles, or None to clear them)"""
+        from .contact import set_obstacles
+
+        set_obstacles(self, obstacles)
 
     # matrix-free operator (FH_LAPLACE, FH_LINEAR_ELASTIC): no pattern, no values
     def set_operator_dirichlet_nodes(self, nodes):
@@ -1185,6 +1195,7 @@ class MatrixFreeOperator:
         if force or getattr(self.engine, "_mf_bound", None) is not self:
             self.engine.set_operator_dirichlet_nodes(self._nodes)
             self.engine._mf_bound = self
+        _contact.bind_obstacles(self, force)
 
     def apply(self, y, x):
         """y = A x (y overwritten, like LinearOperator::apply)"""
@@ -1236,6 +1247,10 @@ class MatrixFreeTangent(MatrixFreeOperator):
     MatrixFreeOperator (Dirichlet nodes owned by the object, apply on numpy arrays or device tensors, diagonal, cg_solve); its Jacobi
     preconditioner takes the tangent's diagonal.  Changing the assembler's u (with_u) changes the operator."""
 
+    def with_obstacles(self, obstacles):
+        """the rigid obstacles whose penalty term B(u) joins T(u) (fenris_amd.contact.Obstacles; None: none); they belong to this object"""
+        return _contact.with_obstacles(self, obstacles)
+
     def _apply_dev(self, x_t, y_t):
         self.engine.apply_tangent_dev(x_t, y_t)
 
@@ -1265,6 +1280,10 @@ class MatrixFreeShiftedTangent(MatrixFreeOperator):
         """new alpha, beta (e.g. another dt between steps); returns self"""
         self.alpha, self.beta = float(alpha), float(beta)
         return self
+
+    def with_obstacles(self, obstacles):
+        """the rigid obstacles whose penalty term joins the map: alpha M + beta (T(u) + B(u)) (None: none); they belong to this object"""
+        return _contact.with_obstacles(self, obstacles)
 
     def _mg_density(self):
         return self._rho if self.alpha != 0.0 else None
@@ -1424,6 +1443,11 @@ class MatrixFreeNewton:
         if self._rho is not None and (force or getattr(self.engine, "_mass_bound", None) is not self):
             self.engine.set_mass_density(self._rho)
             self.engine._mass_bound = self
+        _contact.bind_obstacles(self, force)
+
+    def with_obstacles(self, obstacles):
+        """the rigid obstacles of the penalty contact term: F = alpha M (u - u_ref) + beta (r(u) + g(u) - f) (None: none); returns self"""
+        return _contact.with_obstacles(self, obstacles)
 
     def solve(self, u, settings: NewtonSettings = NewtonSettings(), line_search=None, preconditioner=None, linear_rel_tol=1e-8, linear_max_iter=0):
         """u: the guess with the Dirichlet values (numpy array or device tensor), overwritten by the solution.  Returns a NewtonResult;

@@ -1,0 +1,249 @@
+// Penalty contact with rigid, fixed obstacles: the arithmetic of the term, in one place, and the stand-alone node kernels.
+//   E_c = sum_o sum_i (k_o w_i / 2) p^2,  p = min(0, phi_o(x_i)),  x_i = X_i + u_i
+//   g_i = sum_o k_o w_i p n                                  n = grad phi_o(x_i)
+//   B_i = sum_o k_o w_i ([phi_o < 0] n n^T + c (I - n n^T))    c = -p / |y| for the cavity, 0 otherwise (max-PSD of p Hess phi)
+// Every kernel that forms r(u), K(u) x, the diagonal or the stored energy with the term calls contact_force / contact_apply /
+// contact_diagonal / contact_energy below: the node passes of the tiles (vector_tiles.hip) in the same visit that sums the node's
+// partials, the routes off the tiles through the stand-alone kernels at the end of this file (engine_contact.hip launches them).
+// The table travels BY VALUE in the kernel arguments: it is the same for every lane, so it stays in scalar registers; count == 0 is "off"
+// and the only thing such a kernel reads of it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/fenris_hip.h"
+#include "device_common.hpp"
+
+namespace fenris_hip {
+
+struct ContactObstacle {
+    double p[3];      // a point of the plane / the centre
+    double n[3];      // half-space: the unit normal
+    double radius;
+    double k;
+    int kind, pad_;
+};
+
+struct ContactTable {
+    int count, dim;          // count == 0: no obstacles; dim: the geometric (= solution) dimension
+    const double* X;         // [N][dim] vertices
+    const double* u;         // [N][dim] displacement (null: zero)
+    const double* w;         // [N] node weights (null: 1)
+    ContactObstacle o[FH_MAX_OBSTACLES];
+};
+inline ContactTable contact_off() {
+    ContactTable t{};
+    return t;
+}
+
+// phi, n = grad phi (has_n false: the centre of a ball or cavity, where the gradient does not exist) and 1 / |y| (0 for the half-space)
+template <int D>
+__host__ __device__ __forceinline__ void contact_eval(const ContactObstacle& ob, const double (&x)[D], double& phi, double (&n)[D], bool& has_n,
+                                                      double& inv_r) {
+    if (ob.kind == FH_OBSTACLE_HALF_SPACE) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            n[c] = ob.n[c];
+            s += (x[c] - ob.p[c]) * ob.n[c];
+        }
+        phi = s;
+        has_n = true;
+        inv_r = 0.0;
+        return;
+    }
+    double y[D], r2 = 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        y[c] = x[c] - ob.p[c];
+        r2 += y[c] * y[c];
+    }
+    const double r = sqrt(r2);
+    const double sign = ob.kind == FH_OBSTACLE_BALL ? 1.0 : -1.0;
+    phi = sign * (r - ob.radius);
+    has_n = r > 0.0;
+    inv_r = has_n ? 1.0 / r : 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) n[c] = has_n ? sign * y[c] * inv_r : 0.0;
+}
+
+// f(k w, phi, n, has_n, c) for every obstacle at node `node`, in the table's order (c: the coefficient of I - n n^T in B)
+template <int D, class F>
+__host__ __device__ __forceinline__ void contact_visit(const ContactTable& ct, int node, F&& f) {
+    double x[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) x[c] = ct.X[(size_t)node * D + c] + (ct.u ? ct.u[(size_t)node * D + c] : 0.0);
+    const double w = ct.w ? ct.w[node] : 1.0;
+    for (int o = 0; o < ct.count; ++o) {
+        const ContactObstacle& ob = ct.o[o];
+        double phi, n[D], inv_r;
+        bool has_n;
+        contact_eval<D>(ob, x, phi, n, has_n, inv_r);
+        const double p = phi < 0.0 ? phi : 0.0;
+        f(ob.k * w, phi, n, has_n, ob.kind == FH_OBSTACLE_CAVITY ? -p * inv_r : 0.0);
+    }
+}
+
+// g[] += g_i
+template <int D>
+__host__ __device__ __forceinline__ void contact_force(const ContactTable& ct, int node, double (&g)[D]) {
+    double s[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) s[c] = 0.0;
+    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double) {
+        if (!(phi < 0.0) || !has_n) return;
+        const double kp = kw * phi;
+#pragma unroll
+        for (int c = 0; c < D; ++c) s[c] += kp * n[c];
+    });
+#pragma unroll
+    for (int c = 0; c < D; ++c) g[c] += s[c];
+}
+
+// y[] += scale B_i v
+template <int D>
+__host__ __device__ __forceinline__ void contact_apply(const ContactTable& ct, int node, const double (&v)[D], double scale, double (&y)[D]) {
+    double s[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) s[c] = 0.0;
+    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+        if (!(phi < 0.0) || !has_n) return;
+        double nv = 0.0;
+#pragma unroll
+        for (int c = 0; c < D; ++c) nv += n[c] * v[c];
+#pragma unroll
+        for (int c = 0; c < D; ++c) s[c] += kw * (n[c] * nv + cc * (v[c] - n[c] * nv));
+    });
+#pragma unroll
+    for (int c = 0; c < D; ++c) y[c] += scale * s[c];
+}
+
+// B[][] += B_i
+template <int D>
+__host__ __device__ __forceinline__ void contact_block(const ContactTable& ct, int node, double (&B)[D][D]) {
+    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+        if (!(phi < 0.0) || !has_n) return;
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b < D; ++b) B[a][b] += kw * (n[a] * n[b] + cc * ((a == b ? 1.0 : 0.0) - n[a] * n[b]));
+    });
+}
+
+// d[] += diag B_i
+template <int D>
+__host__ __device__ __forceinline__ void contact_diagonal(const ContactTable& ct, int node, double (&d)[D]) {
+    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+        if (!(phi < 0.0) || !has_n) return;
+#pragma unroll
+        for (int c = 0; c < D; ++c) d[c] += kw * (n[c] * n[c] + cc * (1.0 - n[c] * n[c]));
+    });
+}
+
+// the node's share of E_c, and min_o phi_o
+template <int D>
+__host__ __device__ __forceinline__ double contact_energy(const ContactTable& ct, int node) {
+    double e = 0.0;
+    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&)[D], bool, double) {
+        if (phi < 0.0) e += 0.5 * kw * phi * phi;
+    });
+    return e;
+}
+template <int D>
+__host__ __device__ __forceinline__ double contact_gap(const ContactTable& ct, int node) {
+    double g = HUGE_VAL;
+    contact_visit<D>(ct, node, [&](double, double phi, const double (&)[D], bool, double) { g = phi < g ? phi : g; });
+    return g;
+}
+
+#ifdef __HIPCC__
+// ---- the stand-alone node kernels: one thread per node
+
+// per-workgroup partials of E_c in a fixed tree; the caller sums them in index order (k_sum_partial_ranges / sum_partials)
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_energy(const ContactTable ct, int num_nodes, double* partial) {
+    __shared__ double red[4];
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    const double e = node < num_nodes ? contact_energy<D>(ct, node) : 0.0;
+    const double tot = block_sum_256(e, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+// out += g
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_force(const ContactTable ct, int num_nodes, double* out) {
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    if (node >= num_nodes) return;
+    double g[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) g[c] = out[(size_t)node * D + c];
+    contact_force<D>(ct, node, g);
+#pragma unroll
+    for (int c = 0; c < D; ++c) out[(size_t)node * D + c] = g[c];
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_gap(const ContactTable ct, int num_nodes, double* gap) {
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    if (node < num_nodes) gap[node] = contact_gap<D>(ct, node);
+}
+
+// y += B x 2^-e (xbits: mf_exponent of the operand the element pass of the map saw, may be null: the pass that finishes y multiplies by 2^e)
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_apply(const ContactTable ct, int num_nodes, const double* x, const unsigned long long* xbits,
+                                                       double* y) {
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    if (node >= num_nodes) return;
+    const int ex = mf_exponent(xbits);
+    double v[D], s[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        v[c] = x[(size_t)node * D + c];
+        s[c] = 0.0;
+    }
+    contact_apply<D>(ct, node, v, 1.0, s);
+#pragma unroll
+    for (int c = 0; c < D; ++c) y[(size_t)node * D + c] += ldexp(s[c], -ex);
+}
+
+// diag += diag B
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_diagonal(const ContactTable ct, int num_nodes, double* diag) {
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    if (node >= num_nodes) return;
+    double d[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) d[c] = diag[(size_t)node * D + c];
+    contact_diagonal<D>(ct, node, d);
+#pragma unroll
+    for (int c = 0; c < D; ++c) diag[(size_t)node * D + c] = d[c];
+}
+
+// B_i added to the diagonal node block of block row `node` of the pattern's CSR values (row S i + a holds cnt blocks of S entries; the
+// columns of a row are sorted: a binary search finds the node's own)
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_csr(const ContactTable ct, int num_nodes, const unsigned* noff, const unsigned* ncols,
+                                                     double* vals) {
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    if (node >= num_nodes) return;
+    const unsigned r0 = noff[node], cnt = noff[node + 1] - r0;
+    unsigned lo = 0, hi = cnt;
+    while (lo < hi) {
+        const unsigned mid = (lo + hi) / 2;
+        if (ncols[r0 + mid] < (unsigned)node) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= cnt || ncols[r0 + lo] != (unsigned)node) return;   // (a pattern always holds the diagonal block)
+    double B[D][D];
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) B[a][b] = 0.0;
+    contact_block<D>(ct, node, B);
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) vals[(size_t)D * D * r0 + (size_t)a * D * cnt + (size_t)D * lo + b] += B[a][b];
+}
+#endif
+
+}  // namespace fenris_hip

@@ -565,6 +565,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     point_index_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
+    contact_clear(c);   // (the node weights of the obstacles belong to the mesh)
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
     ++c->density_gen;
     c->ragged = false;
@@ -667,6 +668,7 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     point_index_drop(c);
     c->has_mesh = false;
     c->mf_num_dirichlet = 0;
+    contact_clear(c);   // (the node weights of the obstacles belong to the mesh)
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
     ++c->density_gen;
     c->ragged = true;

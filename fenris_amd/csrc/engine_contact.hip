@@ -1,0 +1,242 @@
+// Penalty contact with rigid, fixed obstacles (contact_kernels.hpp holds the arithmetic and the node kernels): the obstacle table of the
+// context, the stand-alone launches the routes off the tiles compose, and the C ABI.
+//
+// Where the term enters ("Penalty contact"): on the element tiles it is FUSED into the node pass that finishes the node sums
+// (k_operator_from_partials, k_newton_from_partials, k_dynamics_from_partials, k_first_order_from_partials take the table by value and call
+// contact_apply / contact_force for the node they already visit: no launch, no pass over memory of its own).  Off the tiles (the quadratic
+// and cubic kinds, rule-set tables) the residual and the map are accumulated into a vector anyway, and ONE stand-alone launch adds the term
+// to it before the pass that finishes it (k_contact_force behind the node sums of r(u); k_contact_apply before k_mf_finish /
+// k_mf_shift_combine; k_contact_diagonal behind the diagonal's sums, once per solve).  Nothing here waits for the device except the energy,
+// which hands one double back; nothing uses atomics; the energy partials are summed in a fixed order.
+#include "engine_internal.hpp"
+
+#include <cmath>
+
+namespace {
+
+// (fh_set_mesh* refuses 2^31 vertices or more, so a node index and the number of workgroups fit an int; the kernels index with size_t)
+int blocks_of(long long n) { return (int)std::max<long long>(1, (n + 255) / 256); }
+
+// the table of the stand-alone terms: the obstacles as they are set, whatever the scope
+ContactTable table_at_u(const fh_ctx* c) {
+    ContactTable t = c->contact;
+    t.dim = c->ei.d;
+    t.X = c->verts.p;
+    t.u = c->has_u ? c->u.p : nullptr;
+    t.w = c->contact_has_w ? c->contact_w.p : nullptr;
+    return t;
+}
+
+template <class F>
+int by_dim(fh_ctx* c, F&& f) {
+    return dispatch_or_last(int_list<2, 3>{}, c->ei.d, [&](auto d) {
+        f(d);
+        return 0;
+    });
+}
+
+int standalone_ready(fh_ctx* c, const char* who) {
+    if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, std::string(who) + ": no finite element mesh set");
+    if (c->ei.d != 2 && c->ei.d != 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": the geometric dim must be 2 or 3");
+    if (c->has_u && c->S() != c->ei.d)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": the contact term needs the operator's solution dim to equal the geometric dim");
+    return FH_OK;
+}
+
+}  // namespace
+
+ContactTable contact_table(const fh_ctx* c) {
+    if (c->contact.count == 0 || c->mf_scope != MF_TANGENT) return contact_off();
+    return table_at_u(c);
+}
+
+int contact_blocked(fh_ctx* c, const char* who) {
+    if (c->contact.count && c->op >= 0 && c->S() != c->ei.d)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": obstacles are set (fh_set_obstacles) and the operator's solution dim is not the geometric dim");
+    return FH_OK;
+}
+
+void contact_clear(fh_ctx* c) {
+    if (c->contact.count || c->contact_has_w) ++c->contact_gen;
+    c->contact = contact_off();
+    c->contact_has_w = false;
+}
+
+int contact_add_force(fh_ctx* c, double* out_dev) {
+    const ContactTable t = contact_table(c);
+    if (!t.count || c->N == 0) return FH_OK;
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_force<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, out_dev); });
+    HIP_TRY(c, hipGetLastError());
+    return FH_OK;
+}
+
+int contact_add_apply(fh_ctx* c, const double* x_dev, const unsigned long long* xbits, double* y_dev) {
+    const ContactTable t = contact_table(c);
+    if (!t.count || c->N == 0) return FH_OK;
+    by_dim(c, [&](auto d) {
+        hipLaunchKernelGGL((k_contact_apply<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, x_dev, xbits, y_dev);
+    });
+    HIP_TRY(c, hipGetLastError());
+    // (behind mf_single, which names the element kernels it ran; with no element to run it names nothing)
+    if (c->E == 0 || (c->has_mask && c->num_active == 0)) c->last_kernel = "k_contact_apply";
+    else c->last_kernel += " + k_contact_apply";
+    return FH_OK;
+}
+
+int contact_add_diagonal(fh_ctx* c, double* diag_dev) {
+    const ContactTable t = contact_table(c);
+    if (!t.count || c->N == 0) return FH_OK;
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_diagonal<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, diag_dev); });
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_contact_diagonal";   // (the diagonal's own passes leave no name: this is the last kernel of the diagonal with B)
+    return FH_OK;
+}
+
+// E_c of `t` added to *energy: per-workgroup partials in a fixed tree, at most 2048 ordered range sums, the ordered host sum
+static int energy_of(fh_ctx* c, const ContactTable& t, double* energy) {
+    if (!t.count || c->N == 0) return FH_OK;
+    const int count = blocks_of((long long)c->N), ranges = std::min(2048, count);
+    DevBuf<double>& part = c->contact_part;
+    if (part.n < (size_t)count + (size_t)ranges) HIP_TRY(c, part.alloc((size_t)count + (size_t)ranges));
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_energy<d()>), dim3(count), dim3(256), 0, c->stream, t, (int)c->N, part.p); });
+    hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(ranges), dim3(256), 0, c->stream, part.p, (long long)count, part.p + count);
+    HIP_TRY(c, hipGetLastError());
+    double e = 0.0;
+    const int rc = sum_partials(c, part.p + count, ranges, 1, &e);   // (waits for the device: one double comes back)
+    if (rc) return rc;
+    *energy += e;
+    return FH_OK;
+}
+int contact_add_energy(fh_ctx* c, double* energy) { return energy_of(c, contact_table(c), energy); }
+
+extern "C" {
+
+int fh_set_obstacles(fh_ctx* c, const fh_obstacle* obstacles, uint64_t count, const double* node_weights) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_set_obstacles";
+    if (count > FH_MAX_OBSTACLES) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": more than FH_MAX_OBSTACLES obstacles");
+    if (count && !obstacles) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null obstacle list");
+    ContactTable t = contact_off();
+    for (uint64_t i = 0; i < count; ++i) {
+        const fh_obstacle& o = obstacles[i];
+        ContactObstacle& k = t.o[i];
+        if (o.kind != FH_OBSTACLE_HALF_SPACE && o.kind != FH_OBSTACLE_BALL && o.kind != FH_OBSTACLE_CAVITY)
+            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown obstacle kind");
+        if (!std::isfinite(o.stiffness) || !(o.stiffness > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the stiffness must be positive and finite");
+        double nn = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(o.point[a])) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a point is not finite");
+            if (o.kind == FH_OBSTACLE_HALF_SPACE && !std::isfinite(o.normal[a])) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a normal is not finite");
+            k.p[a] = o.point[a];
+            nn += o.kind == FH_OBSTACLE_HALF_SPACE ? o.normal[a] * o.normal[a] : 0.0;
+        }
+        k.kind = o.kind;
+        k.k = o.stiffness;
+        k.radius = 0.0;
+        if (o.kind == FH_OBSTACLE_HALF_SPACE) {
+            if (!(nn > 0.0) || !std::isfinite(nn)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a half-space needs a normal that is not zero");
+            const double len = std::sqrt(nn);
+            for (int a = 0; a < 3; ++a) k.n[a] = o.normal[a] / len;
+        } else {
+            if (!std::isfinite(o.radius) || !(o.radius > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the radius must be positive and finite");
+            k.radius = o.radius;
+        }
+    }
+    if (count && node_weights) {
+        if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, std::string(who) + ": no finite element mesh set");
+        for (uint64_t i = 0; i < c->N; ++i)
+            if (!std::isfinite(node_weights[i]) || node_weights[i] < 0.0)
+                return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a node weight is negative or not finite");
+    }
+    if (count == 0) {
+        contact_clear(c);
+        return FH_OK;
+    }
+    if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, std::string(who) + ": no finite element mesh set");
+    if (c->ei.d != 2 && c->ei.d != 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": the geometric dim must be 2 or 3");
+    if (c->ei.d == 2)   // the third components take no part in a plane problem: a normal is normalised over the first two
+        for (uint64_t i = 0; i < count; ++i) {
+            ContactObstacle& k = t.o[i];
+            if (k.kind != FH_OBSTACLE_HALF_SPACE) continue;
+            const double len = std::sqrt(obstacles[i].normal[0] * obstacles[i].normal[0] + obstacles[i].normal[1] * obstacles[i].normal[1]);
+            if (!(len > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a half-space needs a normal that is not zero");
+            k.n[0] = obstacles[i].normal[0] / len;
+            k.n[1] = obstacles[i].normal[1] / len;
+            k.n[2] = 0.0;
+        }
+    if (node_weights) {
+        HIP_TRY(c, c->contact_w.alloc((size_t)c->N + 1));
+        HIP_TRY(c, hipMemcpyAsync(c->contact_w.p, node_weights, sizeof(double) * (size_t)c->N, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    t.count = (int)count;
+    c->contact = t;
+    c->contact_has_w = node_weights != nullptr;
+    ++c->contact_gen;
+    return FH_OK;
+}
+
+int fh_contact_energy(fh_ctx* c, double* energy) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_contact_energy";
+    if (!energy) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    *energy = 0.0;
+    const int rc = standalone_ready(c, who);
+    if (rc) return rc;
+    c->last_kernel = "k_contact_energy";
+    return energy_of(c, table_at_u(c), energy);
+}
+
+int fh_contact_force_dev(fh_ctx* c, double* out_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_contact_force_dev";
+    if (!out_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    const int rc = standalone_ready(c, who);
+    if (rc) return rc;
+    const ContactTable t = table_at_u(c);
+    if (!t.count || c->N == 0) return FH_OK;
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_force<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, out_dev); });
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_contact_force";
+    return FH_OK;
+}
+
+int fh_contact_gap_dev(fh_ctx* c, double* gap_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_contact_gap_dev";
+    if (!gap_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    const int rc = standalone_ready(c, who);
+    if (rc) return rc;
+    if (c->N == 0) return FH_OK;
+    const ContactTable t = table_at_u(c);
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_gap<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, gap_dev); });
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_contact_gap";
+    return FH_OK;
+}
+
+int fh_add_contact_tangent_csr_dev(fh_ctx* c, double* values_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_add_contact_tangent_csr_dev";
+    if (!values_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    int rc = standalone_ready(c, who);
+    if (rc) return rc;
+    if (!c->has_pattern) return c->fail(FH_INVALID_STATE, std::string(who) + ": call fh_pattern first");
+    if (c->S() != c->ei.d)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": the contact term needs the operator's solution dim to equal the geometric dim");
+    const ContactTable t = table_at_u(c);
+    if (!t.count || c->N == 0) return FH_OK;
+    by_dim(c, [&](auto d) {
+        hipLaunchKernelGGL((k_contact_csr<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, c->noff.p, c->ncols.p, values_dev);
+    });
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_contact_csr";
+    return FH_OK;
+}
+
+}  // extern "C"

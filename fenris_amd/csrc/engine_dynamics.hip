@@ -23,9 +23,9 @@ struct fh_dynamics {
     bool has_f = false;
     uint64_t step = 0;                 // steps taken since fh_dynamics_set_state
     // what m (the first five) and a_n (all six; first order: the rate, kept in v) were formed for: struct_gen (operator, table, mask),
-    // topo_gen, geom_gen, density_gen, dirichlet_gen, and the u_gen this handle left behind
+    // topo_gen, geom_gen, density_gen, dirichlet_gen, the u_gen this handle left behind, and the contact_gen of fh_set_obstacles
     unsigned long long m_key[5] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
-    unsigned long long a_key[6] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
+    unsigned long long a_key[7] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
     bool load_changed = true;
 };
 
@@ -39,13 +39,14 @@ bool explicit_scheme(const fh_dynamics* d) { return first_order(d) ? d->fo_schem
 const unsigned char* dmask_of(const fh_ctx* c) { return c->mf_num_dirichlet ? c->mf_dmask.p : nullptr; }
 int blocks_of(int n) { return std::max(1, (n + 255) / 256); }
 
-void key_now(const fh_ctx* c, unsigned long long (&k)[6]) {
+void key_now(const fh_ctx* c, unsigned long long (&k)[7]) {
     k[0] = c->struct_gen;
     k[1] = c->topo_gen;
     k[2] = c->geom_gen;
     k[3] = c->density_gen;
     k[4] = c->dirichlet_gen;
     k[5] = c->u_gen;
+    k[6] = c->contact_gen;
 }
 
 // the handle still belongs to the context's mesh and the context can form M and r
@@ -76,12 +77,14 @@ int residual_tiles(fh_dynamics* d, bool* tiles) {
     return FH_OK;
 }
 
-// r(u) summed into d->r on every other route (newton_residual's second branch): waits for the device and reports the kernels' status
+// r(u) summed into d->r on every other route (newton_residual's second branch): waits for the device and reports the kernels' status;
+// with obstacles set, r + g (one launch of k_contact_force behind the node sums)
 int residual_summed(fh_dynamics* d) {
     fh_ctx* c = d->c;
     HIP_TRY(c, hipMemsetAsync(d->r.p, 0, sizeof(double) * (size_t)d->n, c->stream));
-    return c->rs.active ? rs_walk_accumulating(c, nullptr, [&](uint64_t* fl) { return residual_ordered_single(c, d->r.p, fl); })
-                        : residual_ordered_single(c, d->r.p, nullptr);
+    const int rc = c->rs.active ? rs_walk_accumulating(c, nullptr, [&](uint64_t* fl) { return residual_ordered_single(c, d->r.p, fl); })
+                                : residual_ordered_single(c, d->r.p, nullptr);
+    return rc ? rc : contact_add_force(c, d->r.p);
 }
 
 int sum_blocks(fh_ctx* c, const double* partial, int count, double* out) { return sum_partials(c, partial, count, 1, out); }
@@ -98,7 +101,7 @@ int dot(fh_dynamics* d, const double* x, const double* y, double* out) {
 // the row-sum lumped mass m = M 1 (no Dirichlet rows take part) for the current mesh, table, mask and density; every free dof must have m > 0
 int ensure_lumped(fh_dynamics* d, const char* who) {
     fh_ctx* c = d->c;
-    unsigned long long k[6];
+    unsigned long long k[7];
     key_now(c, k);
     if (std::equal(k, k + 5, d->m_key)) return FH_OK;
     const int n = d->n;
@@ -151,7 +154,7 @@ int explicit_launch(fh_dynamics* d, int flags, uint64_t step, uint64_t* stats, i
         if (rc) return rc;
         ++stats[1];
         if (tiles) {
-            HIP_TRY(c, vector_tiles_dynamics_node_pass(c->stream, S, (int)c->N, c->vt.v, d->rpart.p, p));
+            HIP_TRY(c, vector_tiles_dynamics_node_pass(c->stream, S, (int)c->N, c->vt.v, d->rpart.p, p, contact_table(c)));
             c->last_kernel = "k_element_pass_tiled + k_dynamics_from_partials";
             if (ke_count) *ke_count = vector_tiles_operator_partials((int)c->N);
             if (flags & DYN_ADVANCE) ++c->u_gen;
@@ -159,7 +162,8 @@ int explicit_launch(fh_dynamics* d, int flags, uint64_t step, uint64_t* stats, i
         }
         rc = residual_summed(d);
         if (rc) return rc;
-        c->last_kernel = "k_residual_elements + k_vector_from_elements_soa + k_dynamics_update";
+        c->last_kernel = contact_table(c).count ? "k_residual_elements + k_vector_from_elements_soa + k_contact_force + k_dynamics_update"
+                                                : "k_residual_elements + k_vector_from_elements_soa + k_dynamics_update";
     }
     hipLaunchKernelGGL(k_dynamics_update, dim3(blocks_of(n)), dim3(256), 0, c->stream, n, S, d->r.p, p);
     HIP_TRY(c, hipGetLastError());
@@ -172,10 +176,12 @@ double load_factor(const fh_dynamics* d, uint64_t step) {
     return d->h_lf.empty() ? 1.0 : d->h_lf[(size_t)std::min<uint64_t>(step, d->h_lf.size() - 1)];
 }
 
-// stored energy and load potential of the state after `step` steps, into row[1..3]
+// stored energy (with obstacles set: plus the contact energy E_c) and load potential of the state after `step` steps, into row[1..3]
 int record_rest(fh_dynamics* d, uint64_t step, double* row) {
     fh_ctx* c = d->c;
     int rc = fh_assemble_scalar(c, &row[1], nullptr);
+    if (rc) return rc;
+    rc = contact_add_energy(c, &row[1]);
     if (rc) return rc;
     row[2] = 0.0;
     if (d->has_f) {
@@ -190,9 +196,9 @@ int record_rest(fh_dynamics* d, uint64_t step, double* row) {
 // a_n for the state as it stands, when anything it depends on has changed since it was formed
 int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
     fh_ctx* c = d->c;
-    unsigned long long k[6];
+    unsigned long long k[7];
     key_now(c, k);
-    if (std::equal(k, k + 6, d->a_key) && !d->load_changed) return FH_OK;
+    if (std::equal(k, k + 7, d->a_key) && !d->load_changed) return FH_OK;
     const int n = d->n, S = c->S(), g = blocks_of(n);
     int rc;
     // (v and a of a Dirichlet dof are zero whatever fh_dynamics_set_state was given)
@@ -224,7 +230,7 @@ int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
         }
     }
     key_now(c, k);
-    std::copy(k, k + 6, d->a_key);
+    std::copy(k, k + 7, d->a_key);
     d->load_changed = false;
     return FH_OK;
 }
@@ -360,7 +366,7 @@ int first_order_launch(fh_dynamics* d, const FoStage& p, uint64_t* stats, int* c
     if (rc) return rc;
     ++stats[1];
     if (tiles) {
-        HIP_TRY(c, vector_tiles_first_order_node_pass(c->stream, S, (int)c->N, c->vt.v, d->rpart.p, p));
+        HIP_TRY(c, vector_tiles_first_order_node_pass(c->stream, S, (int)c->N, c->vt.v, d->rpart.p, p, contact_table(c)));
         c->last_kernel = "k_element_pass_tiled + k_first_order_from_partials";
         if (count) *count = vector_tiles_operator_partials((int)c->N);
     } else {
@@ -368,7 +374,8 @@ int first_order_launch(fh_dynamics* d, const FoStage& p, uint64_t* stats, int* c
         if (rc) return rc;
         hipLaunchKernelGGL(k_first_order_update, dim3(blocks_of(n)), dim3(256), 0, c->stream, n, S, d->r.p, p);
         HIP_TRY(c, hipGetLastError());
-        c->last_kernel = "k_residual_elements + k_vector_from_elements_soa + k_first_order_update";
+        c->last_kernel = contact_table(c).count ? "k_residual_elements + k_vector_from_elements_soa + k_contact_force + k_first_order_update"
+                                                : "k_residual_elements + k_vector_from_elements_soa + k_first_order_update";
         if (count) *count = blocks_of(n);
     }
     if (!(p.flags & FO_RATE)) ++c->u_gen;
@@ -380,9 +387,9 @@ int first_order_launch(fh_dynamics* d, const FoStage& p, uint64_t* stats, int* c
 // anything it depends on has changed since it was formed
 int ensure_rate(fh_dynamics* d, bool solve, uint64_t* stats) {
     fh_ctx* c = d->c;
-    unsigned long long k[6];
+    unsigned long long k[7];
     key_now(c, k);
-    if (std::equal(k, k + 6, d->a_key) && !d->load_changed) return FH_OK;
+    if (std::equal(k, k + 7, d->a_key) && !d->load_changed) return FH_OK;
     const int n = d->n, S = c->S(), g = blocks_of(n);
     const double* rhs = d->v.p;
     int rc;
@@ -418,7 +425,7 @@ int ensure_rate(fh_dynamics* d, bool solve, uint64_t* stats) {
         if (rc) return rc;
     }
     key_now(c, k);
-    std::copy(k, k + 6, d->a_key);
+    std::copy(k, k + 7, d->a_key);
     d->load_changed = false;
     return FH_OK;
 }

@@ -356,6 +356,8 @@ int eigs_lowest_dev(fh_ctx* c, uint32_t m32, double shift, int preconditioner, d
     if (c->mass_rho_n == 0) return c->fail(FH_INVALID_STATE, "fh_eigs_lowest: the mass needs fh_set_mass_density");
     const bool multigrid = preconditioner == FH_PRECOND_MULTIGRID;
     if (multigrid && !c->mg) return c->fail(FH_INVALID_STATE, "fh_eigs_lowest: FH_PRECOND_MULTIGRID needs a hierarchy (fh_set_multigrid)");
+    if (multigrid && contact_table(c).count)
+        return c->fail(FH_UNSUPPORTED, "fh_eigs_lowest: FH_PRECOND_MULTIGRID with obstacles set (fh_set_obstacles): the coarse levels would not see the contact term");
     if ((uint64_t)c->S() * c->N >= (1ull << 31)) return c->fail(FH_UNSUPPORTED, "fh_eigs_lowest: more than 2^31 - 1 dofs");
     EigState e;
     e.c = c;

@@ -481,7 +481,7 @@ struct fh_ctx {
     // (struct_gen, topo_gen, geom_gen, u_gen, alpha, beta, density_gen) mf_scale was formed for: u_gen is 0 for the linear operators (their
     // scale does not depend on u) and when beta == 0; alpha and beta as bits (the plain map: 0 and 1); density_gen 0 unless alpha != 0.  One
     // slot: calls that alternate between the shifted and the plain map form the scale again.
-    unsigned long long mf_scale_key[7] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
+    unsigned long long mf_scale_key[8] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};   // ([7]: contact_gen in the tangent's scope)
     // the density of the shifted map's mass term (fh_set_mass_density): 1 (the whole mesh) or E (per element) doubles, none when 0;
     // density_gen counts the calls; mf_mass: S N, M x or the mass diagonal off the tiles
     DevBuf<double> mass_rho;
@@ -491,6 +491,15 @@ struct fh_ctx {
     unsigned long long geom_gen = 0;   // counts fh_update_vertices calls
     unsigned long long u_gen = 0;      // counts fh_set_u* calls
     unsigned long long dirichlet_gen = 0;   // counts fh_set_operator_dirichlet_nodes calls
+    // penalty contact (engine_contact.hip): the obstacles of fh_set_obstacles as the kernels take them (count == 0: none), the node weights,
+    // contact_gen counts the calls.  mf_scope: the scope of the matrix-free map being formed -- the operator's entry points (MF_OPERATOR)
+    // leave the term out, everything else is the tangent and includes it.
+    ContactTable contact = contact_off();
+    DevBuf<double> contact_w;
+    DevBuf<double> contact_part;       // workgroup partials of E_c and their range sums (kept: no allocation per record)
+    bool contact_has_w = false;
+    unsigned long long contact_gen = 0;
+    int mf_scope = 1;   // MF_TANGENT
     fh_mg* mg = nullptr;               // the multigrid hierarchy of FH_PRECOND_MULTIGRID (fh_set_multigrid; not owned)
     fh_amg* amg = nullptr;             // the algebraic hierarchy of FH_PRECOND_AMG (fh_set_amg; not owned)
     struct BoundaryStore* bnd = nullptr;   // boundary faces of the mesh and the adjacency of the last surface-load face list (engine_boundary.hip)
@@ -642,6 +651,23 @@ bool tiles_enabled(const fh_ctx* c);
 int ensure_vector_tiles(fh_ctx* c);
 int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed);
 int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* out);
+// penalty contact (engine_contact.hip).  contact_table: the table for a kernel of the tangent / residual routes at the context's u, "off"
+// (count 0) without obstacles or in the operator's scope; contact_blocked: FH_UNSUPPORTED when obstacles are set and the operator's solution
+// dim is not the geometric dim.  The stand-alone launches (routes off the tiles; nothing is waited for): out += g; y += B x 2^-e;
+// diag += diag B; *energy += E_c (waits for the device).  Each is a no-op for an "off" table.
+ContactTable contact_table(const fh_ctx* c);
+int contact_blocked(fh_ctx* c, const char* who);
+int contact_add_force(fh_ctx* c, double* out_dev);
+int contact_add_apply(fh_ctx* c, const double* x_dev, const unsigned long long* xbits, double* y_dev);
+int contact_add_diagonal(fh_ctx* c, double* diag_dev);
+int contact_add_energy(fh_ctx* c, double* energy);
+void contact_clear(fh_ctx* c);
+struct MfScope {   // the scope of the map for the duration of an entry point
+    fh_ctx* c;
+    int prev;
+    MfScope(fh_ctx* ctx, int scope) : c(ctx), prev(ctx->mf_scope) { c->mf_scope = scope; }
+    ~MfScope() { c->mf_scope = prev; }
+};
 int newton_run(fh_ctx* c, double alpha, double beta, const double* f, const double* u_ref, double tolerance, uint64_t max_iterations,
                int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter, uint64_t* st, double* nm);
 

@@ -591,6 +591,8 @@ int fh_mg_apply_dev(fh_mg* mg, double alpha, double beta, const double* r_dev, d
     DevGuard dev_guard_(f->device);
     if (!r_dev || !z_dev || r_dev == z_dev) return f->fail(FH_BAD_ARGUMENT, "fh_mg_apply_dev: null or aliased vectors");
     if (f->mg != mg) return f->fail(FH_INVALID_STATE, "fh_mg_apply_dev: attach the hierarchy with fh_set_multigrid first");
+    if (contact_table(f).count)
+        return f->fail(FH_UNSUPPORTED, "fh_mg_apply_dev: obstacles are set (fh_set_obstacles): the coarse levels would not see the contact term");
     int rc = mg_setup(f, alpha, beta);
     if (rc) return rc;
     rc = reset_status(f);

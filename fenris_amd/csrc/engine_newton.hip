@@ -22,6 +22,8 @@ double next_step_length(double a) {
 int newton_run(fh_ctx* c, double alpha, double beta, const double* f, const double* u_ref, double tolerance, uint64_t max_iterations,
                       int line_search, int preconditioner, double linear_rel_tol, uint64_t linear_max_iter, uint64_t* st, double* nm) {
     const char* who = "fh_newton_solve";
+    if (preconditioner == FH_PRECOND_MULTIGRID && contact_table(c).count)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": FH_PRECOND_MULTIGRID with obstacles set (fh_set_obstacles): the coarse levels would not see the contact term");
     const int n = c->S() * (int)c->N;
     const int g = (n + 255) / 256;
     NewtonScratch ns;

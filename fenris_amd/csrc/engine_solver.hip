@@ -253,6 +253,9 @@ extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int scope, const 
         return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown preconditioner");
     const bool multigrid = preconditioner == FH_PRECOND_MULTIGRID;
     if (multigrid && !c->mg) return c->fail(FH_INVALID_STATE, std::string(who) + ": FH_PRECOND_MULTIGRID needs a hierarchy (fh_set_multigrid)");
+    MfScope scope_guard_(c, scope);
+    if (multigrid && contact_table(c).count)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": FH_PRECOND_MULTIGRID with obstacles set (fh_set_obstacles): the coarse levels would not see the contact term");
     const int S = c->S();
     const int n = S * (int)c->N;
     if (n == 0) return FH_OK;

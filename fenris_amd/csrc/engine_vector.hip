@@ -506,20 +506,24 @@ int mf_ready(fh_ctx* c, const char* who, int scope) {
     const int rc = check_ready(c, who, false);
     if (rc) return rc;
     if (c->S() < 1 || c->S() > 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": solution dim must be 1..3");
+    if (scope == MF_TANGENT) return contact_blocked(c, who);   // (the operator's entry points leave the contact term out)
     return FH_OK;
 }
 
 // what the scale of the Dirichlet rows depends on: mesh, vertices, operator, quadrature table and parameters, element mask (the setters of
 // the last three move struct_gen), u for the nonlinear operators, and for the shifted map alpha M + beta T(u) its coefficients and (alpha != 0)
-// the density -- not on which nodes are constrained.  The plain map is alpha = 0, beta = 1.
-static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[7], double alpha = 0.0, double beta = 1.0) {
+// the density, and the obstacles of fh_set_obstacles where the map includes them (their B(u) depends on u for every operator) -- not on
+// which nodes are constrained.  The plain map is alpha = 0, beta = 1.
+static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[8], double alpha = 0.0, double beta = 1.0) {
+    const bool contact = contact_table(c).count != 0 && beta != 0.0;
     k[0] = c->struct_gen;
     k[1] = c->topo_gen;
     k[2] = c->geom_gen;
-    k[3] = (c->op <= FH_LINEAR_ELASTIC || beta == 0.0) ? 0 : c->u_gen;
+    k[3] = ((c->op <= FH_LINEAR_ELASTIC && !contact) || beta == 0.0) ? 0 : c->u_gen;
     std::memcpy(&k[4], &alpha, sizeof(double));
     std::memcpy(&k[5], &beta, sizeof(double));
     k[6] = alpha != 0.0 ? c->density_gen : 0;
+    k[7] = contact ? c->contact_gen : 0;
 }
 
 // the scale of the Dirichlet rows into c->mf_scale, from the unmodified diagonal (diag_dev) of alpha M + beta T(u)
@@ -616,6 +620,8 @@ int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale) {
     int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_single(c, nullptr, diag_dev, f); })
                           : mf_single(c, nullptr, diag_dev, &failed);
     if (rc) return rc;
+    rc = contact_add_diagonal(c, diag_dev);   // diag B(u) of the penalty contact term (k_contact_diagonal), before the scale is taken
+    if (rc) return rc;
     if (c->mf_num_dirichlet && with_scale) {
         rc = mf_scale_from(c, diag_dev);
         if (rc) return rc;
@@ -661,7 +667,8 @@ int mf_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch,
                 *partials = g;
             }
             c->last_kernel = c->op <= FH_LINEAR_ELASTIC ? "k_element_pass_tiled + k_operator_from_partials" : "k_tangent_tiled + k_operator_from_partials";
-            HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp));
+            HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp,
+                                                       contact_table(c)));
             return FH_OK;
         }
     }
@@ -672,6 +679,8 @@ int mf_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch,
     const int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_single(c, xin, y, f); })
                                 : mf_single(c, xin, y, &failed);
     if (rc) return rc;
+    const int rcc = contact_add_apply(c, x, xbits, y);   // B(u) x of the penalty contact term (k_contact_apply), one launch, before the finish
+    if (rcc) return rcc;
     const int g = (n + 255) / 256;
     double* dp = nullptr;
     if (dot_scratch) {
@@ -694,9 +703,10 @@ static int mf_apply_entry(fh_ctx* c, const char* who, int scope, const double* x
     if (rc) return rc;
     if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (c->N == 0) return FH_OK;
-    unsigned long long key[7];
+    MfScope scope_guard_(c, scope);
+    unsigned long long key[8];
     mf_scale_key_now(c, key);
-    if (c->mf_num_dirichlet && !std::equal(key, key + 7, c->mf_scale_key)) {
+    if (c->mf_num_dirichlet && !std::equal(key, key + 8, c->mf_scale_key)) {
         DevBuf<double> diag;
         HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
         rc = mf_diagonal(c, diag.p, true);
@@ -717,6 +727,7 @@ static int mf_diagonal_entry(fh_ctx* c, const char* who, int scope, double* diag
     if (rc) return rc;
     if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (c->N == 0) return FH_OK;
+    MfScope scope_guard_(c, scope);
     rc = mf_diagonal(c, diag_dev, true);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -876,7 +887,8 @@ static int shift_hex8_fused(fh_ctx* c, double alpha, double beta, const double* 
     }
     c->last_kernel = beta == 0.0 ? "k_mass_hex8_tiled + k_operator_from_partials"
                      : c->op <= FH_LINEAR_ELASTIC ? "k_shifted_pass_tiled + k_operator_from_partials" : "k_shifted_tangent_tiled + k_operator_from_partials";
-    HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp));
+    HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp,
+                                               beta != 0.0 ? contact_table(c) : contact_off(), beta));   // (+ beta B(u) x)
     *done = true;
     return FH_OK;
 }
@@ -999,7 +1011,7 @@ int newton_residual(fh_ctx* c, double alpha, double beta, const double* f, const
                 count = vector_tiles_operator_partials(N);
                 if (ns.wg.n < (size_t)count) HIP_TRY(c, ns.wg.alloc((size_t)count));
                 HIP_TRY(c, vector_tiles_newton_node_pass(c->stream, S, N, c->vt.v, ns.rpart.p, alpha != 0.0 ? ns.mpart.p : nullptr, f, dmask, alpha,
-                                                         beta, ns.F.p, ns.wg.p));
+                                                         beta, ns.F.p, ns.wg.p, contact_table(c)));
                 c->last_kernel = alpha != 0.0 ? "k_element_pass_tiled + k_mass_tiled + k_newton_from_partials"
                                               : "k_element_pass_tiled + k_newton_from_partials";
                 rc = read_status(c, nullptr);
@@ -1013,6 +1025,8 @@ int newton_residual(fh_ctx* c, double alpha, double beta, const double* f, const
         rc = c->rs.active ? rs_walk_accumulating(c, nullptr, [&](uint64_t* fl) { return residual_ordered_single(c, ns.r.p, fl); })
                           : residual_ordered_single(c, ns.r.p, nullptr);
         if (rc) return rc;
+        rc = contact_add_force(c, ns.r.p);   // r + g (k_contact_force), one launch
+        if (rc) return rc;
         if (alpha != 0.0) {
             if (ns.m.n < (size_t)n) HIP_TRY(c, ns.m.alloc((size_t)n));
             rc = mass_full(c, d, nullptr, ns.m.p);
@@ -1023,7 +1037,8 @@ int newton_residual(fh_ctx* c, double alpha, double beta, const double* f, const
         hipLaunchKernelGGL(k_newton_combine, dim3(count), dim3(256), 0, c->stream, n, S, alpha, alpha != 0.0 ? ns.m.p : nullptr, beta, ns.r.p, f,
                            dmask, ns.F.p, ns.wg.p);
         HIP_TRY(c, hipGetLastError());
-        c->last_kernel = "k_residual_elements + k_vector_from_elements_soa + k_newton_combine";
+        c->last_kernel = contact_table(c).count ? "k_residual_elements + k_vector_from_elements_soa + k_contact_force + k_newton_combine"
+                                                : "k_residual_elements + k_vector_from_elements_soa + k_newton_combine";
     }
     const int ranges = std::min(2048, count);
     if (ns.sums.n < (size_t)ranges) HIP_TRY(c, ns.sums.alloc(2048));
@@ -1089,9 +1104,9 @@ int fh_apply_shifted_tangent_dev(fh_ctx* c, double alpha, double beta, const dou
     if (rc) return rc;
     if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
     if (c->N == 0) return FH_OK;
-    unsigned long long key[7];
+    unsigned long long key[8];
     mf_scale_key_now(c, key, alpha, beta);
-    if (c->mf_num_dirichlet && !std::equal(key, key + 7, c->mf_scale_key)) {
+    if (c->mf_num_dirichlet && !std::equal(key, key + 8, c->mf_scale_key)) {
         DevBuf<double> diag;
         HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
         rc = mf_shift_diagonal(c, alpha, beta, diag.p, true);

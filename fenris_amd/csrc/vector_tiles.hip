@@ -493,10 +493,13 @@ __global__ void __launch_bounds__(TS) k_tangent_tiled(const KArgs a, const VecTi
 // node pass of the matrix-free operator y = A x: y[S node + c] = sum of the node's partials in ascending order, OVERWRITTEN (not added).
 // dmask (may be null): homogeneous Dirichlet nodes, whose rows hold  scale x  (the element pass saw x with those entries zeroed, so
 // their columns are zero already); the element pass saw x 2^-e (xbits: mf_exponent), the sums are scaled back.  dot_partial (may be null): per workgroup  x . y  over its nodes, in a fixed tree.
+// ct (count 0: off): the penalty contact term of the node, contact_scale B x with the UNSCALED x (contact_kernels.hpp), joins the scaled-back
+// sum before the Dirichlet rows and the dot product are formed; S == 1 has no such term.
 template <int S>
 __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* partial,
                                                                 const double* x, const unsigned char* dmask, const double* scale,
-                                                                const unsigned long long* xbits, double* y, double* dot_partial) {
+                                                                const unsigned long long* xbits, double* y, double* dot_partial,
+                                                                const ContactTable ct, double contact_scale) {
     __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     const int ex = mf_exponent(xbits);
@@ -523,12 +526,20 @@ __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, c
                 }
         }
         const bool fixed = dmask && dmask[node];
+        double xv[S];
 #pragma unroll
         for (int c = 0; c < S; ++c) {
-            const double xv = x[(size_t)node * S + c];
-            const double yv = fixed ? *scale * xv : ldexp(acc[c], ex);
+            xv[c] = x[(size_t)node * S + c];
+            acc[c] = ldexp(acc[c], ex);
+        }
+        if constexpr (S > 1) {
+            if (ct.count) contact_apply<S>(ct, node, xv, contact_scale, acc);   // (the unscaled operand)
+        }
+#pragma unroll
+        for (int c = 0; c < S; ++c) {
+            const double yv = fixed ? *scale * xv[c] : acc[c];
             y[(size_t)node * S + c] = yv;
-            dot = fma(xv, yv, dot);
+            dot = fma(xv[c], yv, dot);
         }
     }
     if (dot_partial) {
@@ -722,11 +733,12 @@ __global__ void __launch_bounds__(256) k_shift_from_partials(int num_nodes, cons
 // node pass of the Newton residual (engine_newton.hip): F = alpha (node sums of the mass partials of d = u - u_ref) + beta (node sums of the
 // residual partials - f), OVERWRITTEN, both sums in ascending order as k_vector_from_partials forms them (mpart null: alpha = 0; f null: zero);
 // rows of the Dirichlet nodes (dmask, may be null) are zero.  norm_partial: per workgroup |F|^2 over its nodes, in a fixed tree
-// (k_operator_from_partials' layout), summed in index order by the caller.
+// (k_operator_from_partials' layout), summed in index order by the caller.  ct (count 0: off): the contact force g of the node
+// (contact_kernels.hpp) joins the residual sum first, so F and |F|^2 are those of r + g.
 template <int S>
 __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
                                                               const double* mpart, const double* f, const unsigned char* dmask, double alpha,
-                                                              double beta, double* F, double* norm_partial) {
+                                                              double beta, double* F, double* norm_partial, const ContactTable ct) {
     __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     double sq = 0.0;
@@ -758,6 +770,9 @@ __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, con
                 }
         }
         const bool fixed = dmask && dmask[node];
+        if constexpr (S > 1) {
+            if (ct.count) contact_force<S>(ct, node, racc);
+        }
 #pragma unroll
         for (int c = 0; c < S; ++c) {
             const size_t i = (size_t)node * S + c;
@@ -800,15 +815,19 @@ __device__ __forceinline__ void node_partials_sum(const unsigned* np_off, const 
 // k_vector_from_partials forms them, and in the same visit the integrator's whole state update (dyn_dof, dynamics_kernels.hpp): a_{n+1} =
 // (lf f - r) / m, the second kick that completes v_{n+1}, then either the stores and the kinetic-energy partial of a record (DYN_STORE) or
 // the next step's first kick and drift into the context's u (DYN_ADVANCE).  The element pass that follows reads the u this leaves.
+// ct (count 0: off): the contact force g at the u the element pass read joins r before dyn_dof, which stays as it is.
 template <int S>
 __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
-                                                                const DynStep p) {
+                                                                const DynStep p, const ContactTable ct) {
     __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     double ke = 0.0;
     if (node < num_nodes) {
         double racc[S];
         node_partials_sum<S>(np_off, np_idx, rpart, node, racc);
+        if constexpr (S > 1) {
+            if (ct.count) contact_force<S>(ct, node, racc);
+        }
         const bool fixed = p.dmask && p.dmask[node];
         const double lf = dyn_load_factor(p);
 #pragma unroll
@@ -823,15 +842,19 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
 // node pass of one stage of a first-order Runge-Kutta-Legendre step, or of the rate alone (engine_dynamics.hip): the same ordered sum, then
 // fo_dof (dynamics_step.hpp): Y_j from Y_{j-1} (the context's u) and Y_{j-2} (prev), both updated in this visit; with FO_STORE the partial
 // of sum m y^2 of the u just written, so a recorded step needs no launch of its own.  The element pass that follows reads the u this leaves.
+// ct (count 0: off): the contact force g at Y_{j-1} joins r before fo_dof, which stays as it is.
 template <int S>
 __global__ void __launch_bounds__(256) k_first_order_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
-                                                                   const FoStage p) {
+                                                                   const FoStage p, const ContactTable ct) {
     __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     double q = 0.0;
     if (node < num_nodes) {
         double racc[S];
         node_partials_sum<S>(np_off, np_idx, rpart, node, racc);
+        if constexpr (S > 1) {
+            if (ct.count) contact_force<S>(ct, node, racc);
+        }
         const bool fixed = p.dmask && p.dmask[node];
         const double lf = dyn_load_factor(p);
 #pragma unroll
@@ -1050,10 +1073,10 @@ int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const 
 
 hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
                                            const unsigned char* dmask, const double* scale, const unsigned long long* xbits, double* y,
-                                           double* dot_partial) {
+                                           double* dot_partial, const ContactTable& ct, double contact_scale) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
         return node_launch(k_operator_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask,
-                           scale, xbits, y, dot_partial);
+                           scale, xbits, y, dot_partial, ct, contact_scale);
     });
 }
 
@@ -1087,22 +1110,25 @@ hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes
 }
 
 hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const double* mpart,
-                                         const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial) {
+                                         const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial,
+                                         const ContactTable& ct) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
         return node_launch(k_newton_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f,
-                           dmask, alpha, beta, F, norm_partial);
+                           dmask, alpha, beta, F, norm_partial, ct);
     });
 }
 
-hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const DynStep& p) {
+hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const DynStep& p,
+                                           const ContactTable& ct) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
-        return node_launch(k_dynamics_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p);
+        return node_launch(k_dynamics_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p, ct);
     });
 }
 
-hipError_t vector_tiles_first_order_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const FoStage& p) {
+hipError_t vector_tiles_first_order_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const FoStage& p,
+                                              const ContactTable& ct) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
-        return node_launch(k_first_order_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p);
+        return node_launch(k_first_order_from_partials<s()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p, ct);
     });
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "contact_kernels.hpp"
 #include "device_common.hpp"
 #include "dynamics_step.hpp"
 
@@ -65,11 +66,12 @@ int vector_tiles_tangent_pass(int elem_kind, int op, hipStream_t stream, const K
 
 // node pass of the matrix-free operator: y = the node sums of the partials, OVERWRITTEN; rows of the nodes with dmask[node] != 0
 // (dmask, scale: device, may be null / unused) are  *scale x; the other rows are multiplied by 2^e (xbits: mf_exponent, may be null).  dot_partial (may be null): one partial of x . y per workgroup
-// (vector_tiles_operator_partials of them), to be summed in index order.
+// (vector_tiles_operator_partials of them), to be summed in index order.  ct (count 0: off): contact_scale B x of the penalty contact term
+// (contact_kernels.hpp; the unscaled x) joins the node's sum before the Dirichlet rows and the dot product.
 inline int vector_tiles_operator_partials(int num_nodes) { return (num_nodes + 255) / 256; }
 hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
                                            const unsigned char* dmask, const double* scale, const unsigned long long* xbits, double* y,
-                                           double* dot_partial);
+                                           double* dot_partial, const ContactTable& ct, double contact_scale = 1.0);
 
 // the mass term of the shifted map (engine_vector.hip) over the tiles into partial[P][S]: M x (x null: the diagonal of M), rho[rho_per_elem ? e : 0]
 // the density, the entries of the nodes with dmask[node] != 0 read as zero (dmask may be null).  Returns -1 when (elem_kind, S) is not covered.
@@ -85,19 +87,23 @@ hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes
 // node pass of the Newton residual: F = alpha (node sums of mpart) + beta (node sums of rpart - f), OVERWRITTEN, with rpart the residual's
 // partials (vector_tiles_element_pass) and mpart the mass partials of d = u - u_ref (vector_tiles_mass_pass; null when alpha == 0), f null: zero;
 // the rows of the nodes with dmask[node] != 0 are zero.  norm_partial: one partial of |F|^2 per workgroup (vector_tiles_operator_partials of
-// them), to be summed in index order.
+// them), to be summed in index order.  ct (count 0: off; here and in the two node passes below): the contact force g of the node
+// (contact_kernels.hpp) joins its residual sum before anything else is formed from it.
 hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const double* mpart,
-                                         const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial);
+                                         const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial,
+                                         const ContactTable& ct);
 
 // node pass of a central-difference step: the node sums of the residual's partials (vector_tiles_element_pass) and the integrator's state
 // update of p.flags (DynStep, dynamics_kernels.hpp) in one visit; with DYN_STORE one partial of sum m v^2 per workgroup
 // (vector_tiles_operator_partials of them) into p.ke_partial, to be summed in index order.
-hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const DynStep& p);
+hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const DynStep& p,
+                                           const ContactTable& ct);
 
 // node pass of one stage of a first-order Runge-Kutta-Legendre step, or of the rate alone (FoStage, dynamics_step.hpp): the node sums of the
 // residual's partials and fo_dof in one visit; with FO_STORE one partial of sum m u^2 per workgroup (vector_tiles_operator_partials of them)
 // into p.partial, to be summed in index order.
-hipError_t vector_tiles_first_order_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const FoStage& p);
+hipError_t vector_tiles_first_order_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const FoStage& p,
+                                              const ContactTable& ct);
 
 // the shifted map fused on Hex8 with the monomial table (a.qmono; -1 otherwise): partial[P][S] of beta T(u) x + alpha M x in ONE element pass
 // (k_shifted_pass_tiled for the linear operators, which read the operand from a.u; k_shifted_tangent_tiled for NeoHookean / StVK, operand x),

@@ -25,6 +25,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi
+from . import contact as _contact
 from ._ffi import FenrisError, SingularJacobianError
 from .assembly import (BacktrackingLineSearch, JacobianError, LineSearchError, MaximumIterationsReached, NewtonResult, NewtonSettings, _is_torch,
                        _ptr)
@@ -96,6 +97,12 @@ class TimeIntegrator:
         if force or getattr(self.engine, "_mass_bound", None) is not self:
             self.engine.set_mass_density(self._rho)
             self.engine._mass_bound = self
+        _contact.bind_obstacles(self, force)
+
+    def with_obstacles(self, obstacles):
+        """the rigid obstacles of the penalty contact term (fenris_amd.contact.Obstacles; None: none): their force joins r(u) in every
+        scheme and their energy the stored-energy column of the records; returns self"""
+        return _contact.with_obstacles(self, obstacles)
 
     def _n(self):
         return self.element_assembler.solution_dim() * self.engine.num_nodes()

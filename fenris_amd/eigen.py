@@ -11,6 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi
+from . import contact as _contact
 from ._ffi import FenrisError
 from .assembly import _is_torch
 
@@ -76,6 +77,11 @@ class MatrixFreeEigensolver:
         if force or getattr(self.engine, "_mass_bound", None) is not self:
             self.engine.set_mass_density(self._rho)
             self.engine._mass_bound = self
+        _contact.bind_obstacles(self, force)
+
+    def with_obstacles(self, obstacles):
+        """the rigid obstacles whose penalty term joins the stiffness: (T(u) + B(u)) phi = lambda M phi (None: none); returns self"""
+        return _contact.with_obstacles(self, obstacles)
 
     def solve(self, num_modes, tol=1e-8, max_iter=0, preconditioner=None, guess=None, device=False):
         """The lowest num_modes pairs.  preconditioner None: PRECOND_MULTIGRID with a hierarchy (with_multigrid), else Jacobi.  guess: n x

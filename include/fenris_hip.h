@@ -919,6 +919,47 @@ typedef struct {
     uint64_t linear_max_iter;
 } fh_first_order_settings;
 int fh_first_order_create(fh_ctx*, const fh_first_order_settings* settings, fh_dynamics** out);
+
+/* ---- penalty contact with rigid, fixed obstacles (engine_contact.hip; the arithmetic: contact_kernels.hpp) ----------------------------
+ * Obstacle o has a signed distance phi_o(x), positive where the body may be, and a stiffness k_o > 0.  With x_i = X_i + u_i the current
+ * position of node i, w_i >= 0 a node weight (default 1) and p = min(0, phi_o(x_i)):
+ *   energy   E_c(u) = sum_o sum_i (k_o w_i / 2) p^2
+ *   force    g_i    = sum_o k_o w_i p grad phi_o(x_i)                                        (added to the residual r(u))
+ *   tangent  B_i    = sum_o k_o w_i ([phi_o < 0] n n^T + c (I - n n^T)),  n = grad phi_o     (a block on the diagonal, per node)
+ * FH_OBSTACLE_HALF_SPACE: phi = (x - point) . normal (normalised here), c = 0.  FH_OBSTACLE_BALL (the body stays outside): phi = |y| - radius,
+ * y = x - point, n = y / |y|, c = 0: the curvature term p Hess phi is negative semi-definite and is dropped, so B_i is a Gauss-Newton
+ * tangent there.  FH_OBSTACLE_CAVITY (the body stays inside): phi = radius - |y|, n = -y / |y|, c = -p / |y| >= 0: B_i is the exact
+ * derivative of g_i.  B_i is symmetric positive semi-definite for every kind.  A node with phi == 0 is inactive (the test is phi < 0); a
+ * node at y == 0 of a ball or a cavity gets no force and no block from it but counts in E_c.
+ * fh_set_obstacles: count == 0 (or a null list) clears them; node_weights: num_nodes doubles or NULL.  FH_BAD_ARGUMENT: count above
+ *   FH_MAX_OBSTACLES, an unknown kind, a value that is not finite, a zero normal, stiffness <= 0, radius <= 0 (ball, cavity), a negative
+ *   weight; FH_INVALID_STATE: no mesh.  fh_set_mesh* clears the obstacles.
+ * While obstacles are set, the term is part of: fh_apply_tangent_dev, fh_tangent_diagonal_dev, fh_cg_solve_tangent(_dev) and the shifted
+ *   family (alpha M + beta (T(u) + B(u)), the scale of the Dirichlet rows from the diagonal with B), fh_newton_solve(_dev)
+ *   (F = alpha M (u - u_ref) + beta (r + g - f)), every scheme of fh_dynamics_* and fh_first_order_* (E_c is added to the stored-energy
+ *   column of the records), fh_dynamics_stable_dt and fh_eigs_lowest(_dev).  These need the solution dim to equal the geometric dim:
+ *   FH_LAPLACE answers FH_UNSUPPORTED.  FH_PRECOND_MULTIGRID and fh_mg_apply_dev with obstacles set: FH_UNSUPPORTED (the coarse levels
+ *   would not see the term).
+ *   Not part of: fh_apply_operator_dev, fh_operator_diagonal_dev, fh_cg_solve_matrix_free, every fh_assemble_*, fh_recover*.
+ *   Without obstacles all of them compute what they computed before, bit for bit.
+ * The stand-alone terms at the context's u (none set: u = 0), over every node (Dirichlet nodes included), for users of the assembled path:
+ *   fh_contact_energy; fh_contact_force_dev ADDS g into out_dev (S N doubles); fh_contact_gap_dev writes min_o phi_o(x_i) per node (N
+ *   doubles; without obstacles +infinity); fh_add_contact_tangent_csr_dev ADDS B_i into the diagonal node blocks of the fh_pattern CSR
+ *   values (FH_INVALID_STATE without a pattern). */
+enum { FH_OBSTACLE_HALF_SPACE = 0, FH_OBSTACLE_BALL = 1, FH_OBSTACLE_CAVITY = 2 };
+#define FH_MAX_OBSTACLES 16
+typedef struct {
+    int kind;
+    double stiffness;
+    double point[3];        /* a point of the plane, or the centre; 2-D: the first two entries */
+    double normal[3];       /* FH_OBSTACLE_HALF_SPACE: points into the admissible side, any length > 0 */
+    double radius;          /* FH_OBSTACLE_BALL, FH_OBSTACLE_CAVITY */
+} fh_obstacle;
+int fh_set_obstacles(fh_ctx*, const fh_obstacle* obstacles, uint64_t count, const double* node_weights);
+int fh_contact_energy(fh_ctx*, double* energy);
+int fh_contact_force_dev(fh_ctx*, double* out_dev);
+int fh_contact_gap_dev(fh_ctx*, double* gap_dev);
+int fh_add_contact_tangent_csr_dev(fh_ctx*, double* values_dev);
 /* Geometric multigrid for the matrix-free solvers (FH_PRECOND_MULTIGRID of fh_cg_solve_matrix_free, fh_cg_solve_tangent,
  * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity, Jacobi or FH_PRECOND_AMG).  Every level is an
  * ordinary context with its own mesh, operator (Laplace, LinearElastic, NeoHookean or StVK), quadrature, data, density and
