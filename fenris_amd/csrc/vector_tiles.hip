@@ -18,6 +18,12 @@
 // coordinates merely decide how compact the tiles are) and are built on the device: Morton keys, hipcub radix sort, one workgroup
 // per tile that sorts its 2048 (node, entry) keys in LDS, two scans.  Element masks (fh_set_active_elements: the multi-GPU partitions)
 // zero the inactive elements' contributions.
+//
+// Every route over the tiles repeats bit for bit and agrees with the others because there is ONE copy of the load pattern and of the
+// order of the additions: TilePass is the frame of every element pass (the tile, the element, the gathers, the staging store, the
+// tile's node sums) and node_partials_sum the ordered sum of every node pass (block_partial_store: the per-workgroup partial some of
+// them leave).  A new tile kernel is a body between TilePass's begin, its gathers and finish; a new node pass is a per-node statement
+// after node_partials_sum.  Neither reads the tables itself.
 #include <hipcub/hipcub.hpp>
 
 #include <vector>
@@ -269,51 +275,104 @@ struct TileSums {
     }
 };
 
+// The frame of every element pass over tiles.  A kernel declares the LDS (stage[N SV TS], ents[(N % 4 == 0) ? TS N : 4]) and is
+// begin, one walk over the nodes with the gathers it needs, its own body, finish; what differs between kernels stands between these
+// calls.  SUMS = false: a pass without node sums (the energy), which shares begin and the gathers only.
+template <int N, int TS, bool SUMS = true>
+struct TilePass {
+    int tile, tid, el, ec;   // ec: el, or 0 for a thread without an element (it computes like the others and its result is dropped)
+    bool live;               // the thread has an element and the mask (may be null) keeps it
+    int nd[N];
+    TileSums<N, TS> ts;
+    // false: the workgroup has no tile.  Workgroup b runs on XCD b mod 8 (round-robin dispatch): every XCD takes one contiguous eighth of
+    // the tiles, so that tiles that are neighbours in space (consecutive in the Morton order) share their boundary nodes' coordinates and u
+    // through one L2.  The tables of the node sums are requested here, before the gathers and the arithmetic, and land behind them.  The
+    // tile's connectivity comes from a table laid out by tile thread (tconn[tile][a][thread]: coalesced, and not behind the load of the
+    // element id), all N nodes before the first gather.
+    __device__ __forceinline__ bool begin(const VecTiles& t, const unsigned char* active) {
+        tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
+        if (tile >= t.ntiles) return false;
+        el = t.elem[(size_t)tile * TS + tid];
+        live = el >= 0 && (!active || active[el] != 0);
+        ec = el >= 0 ? el : 0;
+        if constexpr (SUMS) ts.request(t, tile, tid);
+#pragma unroll
+        for (int n = 0; n < N; ++n) nd[n] = t.tconn[((size_t)tile * N + n) * TS + tid];
+        return true;
+    }
+    // the gathers of local node n (the kernel walks the nodes, what it needs of a node side by side): the vertex coordinates; a nodal
+    // field (a null pointer reads as zero); a field whose entries at the nodes of dmask (may be null) read as zero
+    template <int D>
+    __device__ __forceinline__ void coords(int n, const double* verts, double (&x)[D]) const {
+#pragma unroll
+        for (int i = 0; i < D; ++i) x[i] = verts[(size_t)nd[n] * D + i];
+    }
+    template <int S>
+    __device__ __forceinline__ void field(int n, const double* u, double (&v)[S]) const {
+#pragma unroll
+        for (int k = 0; k < S; ++k) v[k] = u ? u[(size_t)nd[n] * S + k] : 0.0;
+    }
+    template <int S>
+    __device__ __forceinline__ void field_masked(int n, const double* x, const unsigned char* dmask, double (&v)[S]) const {
+        const bool fixed = dmask && dmask[nd[n]];
+#pragma unroll
+        for (int k = 0; k < S; ++k) v[k] = fixed ? 0.0 : x[(size_t)nd[n] * S + k];
+    }
+    // finish = store + sum: the element vector into LDS, stage[a][c][thread], entry by entry through put (i = a SV + c; the select: a
+    // skipped element may hold NaN), and the tile's node sums into the partials
+    __device__ __forceinline__ void put(double* stage, int i, double v) const { stage[i * TS + tid] = live ? v : 0.0; }
+    template <int SV>
+    __device__ __forceinline__ void store(const double (&f)[N][SV], double* stage) const {
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int c = 0; c < SV; ++c) put(stage, n * SV + c, f[n][c]);
+    }
+    template <int SV>
+    __device__ __forceinline__ void sum(const VecTiles& t, const double* stage, unsigned short* ents, double* partial) {
+        ts.template sum<SV>(t, tile, tid, stage, ents, partial);
+    }
+    template <int SV>
+    __device__ __forceinline__ void finish(const VecTiles& t, const double (&f)[N][SV], double* stage, unsigned short* ents, double* partial) {
+        store(f, stage);
+        sum<SV>(t, stage, ents, partial);
+    }
+};
+
+// v summed over the workgroup in the fixed tree of block_sum_256 (xor-shuffles over the lanes, then (w0 + w1) + (w2 + w3)), stored by
+// thread 0 as the workgroup's partial.  Whether a kernel leaves a partial at all is its own condition, uniform over the workgroup.
+__device__ __forceinline__ void block_partial_store(double v, double* partial) {
+    __shared__ double red[4];
+    const double tot = block_sum_256(v, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
 template <int EK, int OP, int TS, int MONO = 0>
 __global__ void __launch_bounds__(TS) k_element_pass_tiled(const KArgs a, const VecTiles t, const unsigned char* active, double* partial) {
     constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
     __shared__ double stage[N * S * TS];
     __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
-    // workgroup b runs on XCD b mod 8 (round-robin dispatch): every XCD takes one contiguous eighth of the tiles, so that tiles that are
-    // neighbours in space (consecutive in the Morton order) share their boundary nodes' coordinates and u through one L2
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    const long long ec = el >= 0 ? el : 0;
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    // the tile's connectivity comes from a table laid out by tile thread (tconn[tile][a][thread]: coalesced, and not behind the load
-    // of the element id)
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    if (a.ablate & 128) {   // (profiling: what the scattered gathers cost -- every thread reads the nodes of its wavefront's first element: wrong results)
+#pragma unroll
+        for (int n = 0; n < N; ++n) tp.nd[n] = __builtin_amdgcn_readfirstlane(tp.nd[n]);
+    }
     double X[N][D], Uv[N][S];
-    {
-        int nd[N];
 #pragma unroll
-        for (int n = 0; n < N; ++n) nd[n] = t.tconn[((size_t)tile * N + n) * TS + tid];
-        if (a.ablate & 128) {   // (profiling: what the scattered gathers cost -- every thread reads the nodes of its wavefront's first element: wrong results)
-#pragma unroll
-            for (int n = 0; n < N; ++n) nd[n] = __builtin_amdgcn_readfirstlane(nd[n]);
-        }
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd[n] * D + i];
-#pragma unroll
-            for (int k = 0; k < S; ++k) Uv[n][k] = a.u ? a.u[(size_t)nd[n] * S + k] : 0.0;
-        }
+    for (int n = 0; n < N; ++n) {
+        tp.coords(n, a.verts, X[n]);
+        tp.field(n, a.u, Uv[n]);
     }
     // (measured and dropped, Hex8 elasticity 216^3, element pass 1.03 ms: the distinct nodes' coordinates and u through LDS instead of
     // the gathers -- two more barriers, nothing in flight across them: 1.35 ms; u parked in LDS and 168 registers for a third
     // wavefront per SIMD -- 62 registers spill: 1.66 ms)
     double f[N][S];
     double energy;
-    element_pass_body<EK, OP, EP_VECTOR, MONO>(a, el, live, ec, X, EPRegU<N, S>{Uv}, f, energy);
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;   // (select: a skipped element may hold NaN)
+    element_pass_body<EK, OP, EP_VECTOR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+    tp.store(f, stage);
     if (a.ablate & 64) return;   // (profiling: the element phase alone)
-    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+    tp.template sum<S>(t, stage, ents, partial);
 }
 
 // energy (compute_element_elliptic_energy, local/elliptic.rs:551-605) over the same tiles: on a numbering without locality the tile order
@@ -322,33 +381,22 @@ __global__ void __launch_bounds__(TS) k_element_pass_tiled(const KArgs a, const 
 template <int EK, int OP, int TS, int MONO = 0>
 __global__ void __launch_bounds__(TS) k_element_energy_tiled(const KArgs a, const VecTiles t, const unsigned char* active, double* partial) {
     constexpr int N = EPDims<EK, OP, EP_SCALAR>::N, S = EPDims<EK, OP, EP_SCALAR>::S, D = EPDims<EK, OP, EP_SCALAR>::D;
-    static_assert(TS == 256, "block_sum_256");
-    __shared__ double red[4];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) {
-        if (tid == 0) partial[blockIdx.x] = 0.0;
+    static_assert(TS == 256, "the workgroup's sum is a tree over 256 threads");
+    TilePass<N, TS, false> tp;
+    if (!tp.begin(t, active)) {
+        if (threadIdx.x == 0) partial[blockIdx.x] = 0.0;
         return;
     }
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
     double X[N][D], Uv[N][S];
-    {
-        int nd[N];
 #pragma unroll
-        for (int n = 0; n < N; ++n) nd[n] = t.tconn[((size_t)tile * N + n) * TS + tid];
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd[n] * D + i];
-#pragma unroll
-            for (int k = 0; k < S; ++k) Uv[n][k] = a.u ? a.u[(size_t)nd[n] * S + k] : 0.0;
-        }
+    for (int n = 0; n < N; ++n) {
+        tp.coords(n, a.verts, X[n]);
+        tp.field(n, a.u, Uv[n]);
     }
     double f[1][S];
     double energy;
-    element_pass_body<EK, OP, EP_SCALAR, MONO>(a, el, live, el >= 0 ? el : 0, X, EPRegU<N, S>{Uv}, f, energy);
-    const double tot = block_sum_256(live ? energy : 0.0, red);
-    if (tid == 0) partial[blockIdx.x] = tot;
+    element_pass_body<EK, OP, EP_SCALAR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+    block_partial_store(tp.live ? energy : 0.0, partial);
 }
 
 // source vector (local/source.rs:159-278) over the same tiles: source_element_body per thread, the tile's node sums, partials
@@ -358,26 +406,51 @@ __global__ void __launch_bounds__(TS) k_source_elements_tiled(const KArgs a, con
     constexpr int SF = FACT ? 1 : S;
     __shared__ double stage[N * SF * TS];
     __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    double X[N][D];
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    double X[N][D], f[N][SF];
 #pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
+    for (int n = 0; n < N; ++n) tp.coords(n, a.verts, X[n]);
+    source_element_body<D, S, N, FACT>(a, g, values, tp.ec, X, f);
+    tp.finish(t, f, stage, ents, partial);
+}
+
+// The partials of one node summed in ascending order, the only walk over np_off and np_idx: four partials requested before the first sum,
+// the additions stay in order (a last group of fewer than four reads the list's last index again and does not add it).  NA arrays of
+// partials over the same list, their loads in flight together; an array after the first may be null and sums to zero.
+template <int NA, int S>
+__device__ __forceinline__ void node_partials_sum(const unsigned* np_off, const unsigned* np_idx, const double* const (&part)[NA], int node,
+                                                  double (&acc)[NA][S]) {
 #pragma unroll
-        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int c = 0; c < S; ++c) acc[a][c] = 0.0;
+    const unsigned k0 = np_off[node], k1 = np_off[node + 1];
+    for (unsigned kb = k0; kb < k1; kb += 4) {
+        unsigned v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
+        double x[4][S][NA];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int c = 0; c < S; ++c)
+#pragma unroll
+                for (int a = 0; a < NA; ++a) x[j][c][a] = (a == 0 || part[a]) ? part[a][(size_t)v[j] * S + c] : 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (kb + j < k1) {
+#pragma unroll
+                for (int c = 0; c < S; ++c)
+#pragma unroll
+                    for (int a = 0; a < NA; ++a) acc[a][c] += x[j][c][a];
+            }
     }
-    double f[N][SF];
-    source_element_body<D, S, N, FACT>(a, g, values, el >= 0 ? el : 0, X, f);
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int c = 0; c < SF; ++c) stage[(n * SF + c) * TS + tid] = live ? f[n][c] : 0.0;
-    ts.template sum<SF>(t, tile, tid, stage, ents, partial);
+}
+// ... of one array
+template <int S>
+__device__ __forceinline__ void node_partials_sum(const unsigned* np_off, const unsigned* np_idx, const double* part, int node, double (&acc)[S]) {
+    node_partials_sum(np_off, np_idx, {part}, node, reinterpret_cast<double(&)[1][S]>(acc));
 }
 
 // SO > 0: the partials are scalars (S = 1) and the node's SO components are  g[c] sum  (k_source_elements_tiled<FACT>)
@@ -390,26 +463,8 @@ __global__ void __launch_bounds__(256) k_vector_from_partials(int num_nodes, con
     constexpr int SP = SO > 0 ? SO : S;
     double acc[S], prev[SP];
 #pragma unroll
-    for (int c = 0; c < S; ++c) acc[c] = 0.0;
-#pragma unroll
-    for (int c = 0; c < SP; ++c) prev[c] = out[(size_t)node * SP + c];
-    const unsigned k0 = np_off[node], k1 = np_off[node + 1];
-    for (unsigned kb = k0; kb < k1; kb += 4) {     // four partials requested before the first sum; the additions stay in order
-        unsigned v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
-        double x[4][S];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int c = 0; c < S; ++c) x[j][c] = partial[(size_t)v[j] * S + c];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (kb + j < k1) {
-#pragma unroll
-                for (int c = 0; c < S; ++c) acc[c] += x[j][c];
-            }
-    }
+    for (int c = 0; c < SP; ++c) prev[c] = out[(size_t)node * SP + c];   // (requested before the sum: the load overlaps it)
+    node_partials_sum<S>(np_off, np_idx, partial, node, acc);
     if constexpr (SO > 0) {
 #pragma unroll
         for (int c = 0; c < SO; ++c) out[(size_t)node * SO + c] = fma(g.v[c], acc[0], prev[c]);
@@ -427,31 +482,23 @@ __global__ void __launch_bounds__(TS) k_diagonal_tiled(const KArgs a, const VecT
     constexpr bool lin = OP <= FH_LINEAR_ELASTIC;
     __shared__ double stage[N * S * TS];
     __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    double X[N][D], Uv[lin ? 1 : N][S];
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    double X[N][D], Uv[lin ? 1 : N][S], f[N][S];
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
-#pragma unroll
-        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
-        if constexpr (!lin) {
-#pragma unroll
-            for (int k = 0; k < S; ++k) Uv[n][k] = a.u ? a.u[(size_t)nd * S + k] : 0.0;
-        }
+        tp.coords(n, a.verts, X[n]);
+        if constexpr (!lin) tp.field(n, a.u, Uv[n]);
     }
-    double f[N][S];
-    if constexpr (lin) diagonal_element_body<D, S, N, OP>(a, el >= 0 ? el : 0, live, X, f);
-    else tangent_diagonal_body<D, S, N, OP>(a, el >= 0 ? el : 0, live, X, Uv, f);
+    if constexpr (lin) diagonal_element_body<D, S, N, OP>(a, tp.ec, tp.live, X, f);
+    else tangent_diagonal_body<D, S, N, OP>(a, tp.ec, tp.live, X, Uv, f);
+    // (finish, with the loops of store written out here: through store, whose loops are unrolled before they meet the body's, f is kept as
+    // one vector across the point loop and Tri3 StVK takes 98 registers for 92, four waves per SIMD for five)
 #pragma unroll
     for (int n = 0; n < N; ++n)
 #pragma unroll
-        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
-    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+        for (int c = 0; c < S; ++c) tp.put(stage, n * S + c, f[n][c]);
+    tp.template sum<S>(t, stage, ents, partial);
 }
 
 // tangent of the residual T(u) x of the nonlinear operators over the tiles (matrix-free, engine_vector.hip): the element pass with both u
@@ -462,32 +509,18 @@ __global__ void __launch_bounds__(TS) k_tangent_tiled(const KArgs a, const VecTi
     constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
     __shared__ double stage[N * S * TS];
     __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    double X[N][D], Uv[N][S], Vv[N][S];
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    double X[N][D], Uv[N][S], Vv[N][S], f[N][S];
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
-#pragma unroll
-        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-            Uv[n][k] = a.u ? a.u[(size_t)nd * S + k] : 0.0;
-            Vv[n][k] = x[(size_t)nd * S + k];
-        }
+        tp.coords(n, a.verts, X[n]);
+        tp.field(n, a.u, Uv[n]);
+        tp.field_masked(n, x, nullptr, Vv[n]);   // (the operand: always there)
     }
-    double f[N][S];
-    if constexpr (MONO != 0 && EK == FH_HEX8) tangent_body_hex8<OP, MONO == 2>(a, el >= 0 ? el : 0, live, X, Uv, Vv, f);
-    else tangent_element_body<D, S, N, OP>(a, el >= 0 ? el : 0, live, X, Uv, Vv, f);
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;   // (select: a skipped element may hold NaN)
-    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+    if constexpr (MONO != 0 && EK == FH_HEX8) tangent_body_hex8<OP, MONO == 2>(a, tp.ec, tp.live, X, Uv, Vv, f);
+    else tangent_element_body<D, S, N, OP>(a, tp.ec, tp.live, X, Uv, Vv, f);
+    tp.finish(t, f, stage, ents, partial);
 }
 
 // node pass of the matrix-free operator y = A x: y[S node + c] = sum of the node's partials in ascending order, OVERWRITTEN (not added).
@@ -500,31 +533,12 @@ __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, c
                                                                 const double* x, const unsigned char* dmask, const double* scale,
                                                                 const unsigned long long* xbits, double* y, double* dot_partial,
                                                                 const ContactTable ct, double contact_scale) {
-    __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     const int ex = mf_exponent(xbits);
     double dot = 0.0;
     if (node < num_nodes) {
         double acc[S];
-#pragma unroll
-        for (int c = 0; c < S; ++c) acc[c] = 0.0;
-        const unsigned k0 = np_off[node], k1 = np_off[node + 1];
-        for (unsigned kb = k0; kb < k1; kb += 4) {     // (k_vector_from_partials' loads: four partials in flight, the additions in order)
-            unsigned v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
-            double xp[4][S];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int c = 0; c < S; ++c) xp[j][c] = partial[(size_t)v[j] * S + c];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (kb + j < k1) {
-#pragma unroll
-                    for (int c = 0; c < S; ++c) acc[c] += xp[j][c];
-                }
-        }
+        node_partials_sum<S>(np_off, np_idx, partial, node, acc);
         const bool fixed = dmask && dmask[node];
         double xv[S];
 #pragma unroll
@@ -542,10 +556,7 @@ __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, c
             dot = fma(xv[c], yv, dot);
         }
     }
-    if (dot_partial) {
-        const double tot = block_sum_256(dot, red);
-        if (threadIdx.x == 0) dot_partial[blockIdx.x] = tot;
-    }
+    if (dot_partial) block_partial_store(dot, dot_partial);
 }
 
 // the mass term of the shifted map alpha M + beta T(u) (engine_vector.hip) over the tiles: the element pass of mass_element_body (x null: the
@@ -556,32 +567,17 @@ __global__ void __launch_bounds__(TS) k_mass_tiled(const KArgs a, const VecTiles
                                                    const double* x, const unsigned char* dmask, double* partial) {
     __shared__ double stage[N * S * TS];
     __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    double X[N][D], Vv[DIAG ? 1 : N][S];
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    double X[N][D], Vv[DIAG ? 1 : N][S], f[N][S];
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
-#pragma unroll
-        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
-        if constexpr (!DIAG) {
-            const bool fixed = dmask && dmask[nd];
-#pragma unroll
-            for (int k = 0; k < S; ++k) Vv[n][k] = fixed ? 0.0 : x[(size_t)nd * S + k];
-        }
+        tp.coords(n, a.verts, X[n]);
+        if constexpr (!DIAG) tp.field_masked(n, x, dmask, Vv[n]);
     }
-    double f[N][S];
-    const double r = rho[rho_per_elem ? (el >= 0 ? el : 0) : 0];
+    const double r = rho[rho_per_elem ? tp.ec : 0];
     mass_element_body<D, S, N, N, DIAG>(a, r, X, [&](int n, int k) { return Vv[DIAG ? 0 : n][k]; }, f);
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
-    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+    tp.finish(t, f, stage, ents, partial);
 }
 
 // the shifted map fused on Hex8 (the monomial form of element_pass.hpp, MASS instantiations): one element pass forms
@@ -592,29 +588,16 @@ __global__ void __launch_bounds__(TS) k_shifted_pass_tiled(const KArgs a, const 
     constexpr int N = 8, S = OpT<OP, 3>::S, D = 3;
     __shared__ double stage[N * S * TS];
     __shared__ unsigned short ents[TS * N];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    const long long ec = el >= 0 ? el : 0;
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    double X[N][D], Uv[N][S];
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    double X[N][D], Uv[N][S], f[N][S], energy;
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
-#pragma unroll
-        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
-#pragma unroll
-        for (int k = 0; k < S; ++k) Uv[n][k] = a.u[(size_t)nd * S + k];
+        tp.coords(n, a.verts, X[n]);
+        tp.field_masked(n, a.u, nullptr, Uv[n]);   // (the operand: always there)
     }
-    double f[N][S], energy;
-    element_pass_body_hex8<OP, EP_VECTOR, AFFM, EPRegU<N, S>, true>(a, el, live, ec, X, EPRegU<N, S>{Uv}, f, energy, mt);
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
-    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+    element_pass_body_hex8<OP, EP_VECTOR, AFFM, EPRegU<N, S>, true>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy, mt);
+    tp.finish(t, f, stage, ents, partial);
 }
 
 // ... the nonlinear operators: tangent_body_hex8 with the mass term (x: the tangent's operand)
@@ -624,31 +607,17 @@ __global__ void __launch_bounds__(TS) k_shifted_tangent_tiled(const KArgs a, con
     constexpr int N = 8, S = 3, D = 3;
     __shared__ double stage[N * S * TS];
     __shared__ unsigned short ents[TS * N];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    double X[N][D], Uv[N][S], Vv[N][S];
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    double X[N][D], Uv[N][S], Vv[N][S], f[N][S];
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
-#pragma unroll
-        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-            Uv[n][k] = a.u ? a.u[(size_t)nd * S + k] : 0.0;
-            Vv[n][k] = x[(size_t)nd * S + k];
-        }
+        tp.coords(n, a.verts, X[n]);
+        tp.field(n, a.u, Uv[n]);
+        tp.field_masked(n, x, nullptr, Vv[n]);   // (the operand: always there)
     }
-    double f[N][S];
-    tangent_body_hex8<OP, AFF, true>(a, el >= 0 ? el : 0, live, X, Uv, Vv, f, mt);
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
-    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+    tangent_body_hex8<OP, AFF, true>(a, tp.ec, tp.live, X, Uv, Vv, f, mt);
+    tp.finish(t, f, stage, ents, partial);
 }
 
 // ... and the mass alone (beta == 0: u is not read): x with the Dirichlet entries (dmask, may be null) read as zero
@@ -658,29 +627,16 @@ __global__ void __launch_bounds__(TS) k_mass_hex8_tiled(const KArgs a, const Vec
     constexpr int N = 8, D = 3;
     __shared__ double stage[N * S * TS];
     __shared__ unsigned short ents[TS * N];
-    const int tile = xcd_tile((int)blockIdx.x, t.ntiles), tid = threadIdx.x;
-    if (tile >= t.ntiles) return;
-    const int el = t.elem[(size_t)tile * TS + tid];
-    const bool live = el >= 0 && (!active || active[el] != 0);
-    TileSums<N, TS> ts;
-    ts.request(t, tile, tid);
-    double X[N][D], Vv[N][S];
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    double X[N][D], Vv[N][S], f[N][S];
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-        const int nd = t.tconn[((size_t)tile * N + n) * TS + tid];
-#pragma unroll
-        for (int i = 0; i < D; ++i) X[n][i] = a.verts[(size_t)nd * D + i];
-        const bool fixed = dmask && dmask[nd];
-#pragma unroll
-        for (int k = 0; k < S; ++k) Vv[n][k] = fixed ? 0.0 : x[(size_t)nd * S + k];
+        tp.coords(n, a.verts, X[n]);
+        tp.field_masked(n, x, dmask, Vv[n]);
     }
-    double f[N][S];
-    mass_body_hex8<S, AFF>(a, el >= 0 ? el : 0, X, Vv, mt, f);
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-#pragma unroll
-        for (int c = 0; c < S; ++c) stage[(n * S + c) * TS + tid] = live ? f[n][c] : 0.0;
-    ts.template sum<S>(t, tile, tid, stage, ents, partial);
+    mass_body_hex8<S, AFF>(a, tp.ec, X, Vv, mt, f);
+    tp.finish(t, f, stage, ents, partial);
 }
 
 // node pass of the shifted map: y = alpha (node sums of the mass partials, in ascending order) + beta t, OVERWRITTEN (t: the tangent's y,
@@ -690,30 +646,11 @@ template <int S>
 __global__ void __launch_bounds__(256) k_shift_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* partial,
                                                              const double* x, const unsigned char* dmask, const double* scale, double alpha,
                                                              double beta, const double* tv, double* y, double* dot_partial) {
-    __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     double dot = 0.0;
     if (node < num_nodes) {
         double acc[S];
-#pragma unroll
-        for (int c = 0; c < S; ++c) acc[c] = 0.0;
-        const unsigned k0 = np_off[node], k1 = np_off[node + 1];
-        for (unsigned kb = k0; kb < k1; kb += 4) {
-            unsigned v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
-            double xp[4][S];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int c = 0; c < S; ++c) xp[j][c] = partial[(size_t)v[j] * S + c];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (kb + j < k1) {
-#pragma unroll
-                    for (int c = 0; c < S; ++c) acc[c] += xp[j][c];
-                }
-        }
+        node_partials_sum<S>(np_off, np_idx, partial, node, acc);
         const bool fixed = dmask && dmask[node];
 #pragma unroll
         for (int c = 0; c < S; ++c) {
@@ -724,14 +661,12 @@ __global__ void __launch_bounds__(256) k_shift_from_partials(int num_nodes, cons
             dot = fma(xv, yv, dot);
         }
     }
-    if (dot_partial) {
-        const double tot = block_sum_256(dot, red);
-        if (threadIdx.x == 0) dot_partial[blockIdx.x] = tot;
-    }
+    if (dot_partial) block_partial_store(dot, dot_partial);
 }
 
 // node pass of the Newton residual (engine_newton.hip): F = alpha (node sums of the mass partials of d = u - u_ref) + beta (node sums of the
-// residual partials - f), OVERWRITTEN, both sums in ascending order as k_vector_from_partials forms them (mpart null: alpha = 0; f null: zero);
+// residual partials - f), OVERWRITTEN, both sums in ascending order and over one walk of the node's list, so that their loads are in flight
+// together (mpart null: alpha = 0; f null: zero);
 // rows of the Dirichlet nodes (dmask, may be null) are zero.  norm_partial: per workgroup |F|^2 over its nodes, in a fixed tree
 // (k_operator_from_partials' layout), summed in index order by the caller.  ct (count 0: off): the contact force g of the node
 // (contact_kernels.hpp) joins the residual sum first, so F and |F|^2 are those of r + g.
@@ -739,36 +674,12 @@ template <int S>
 __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
                                                               const double* mpart, const double* f, const unsigned char* dmask, double alpha,
                                                               double beta, double* F, double* norm_partial, const ContactTable ct) {
-    __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     double sq = 0.0;
     if (node < num_nodes) {
-        double racc[S], macc[S];
-#pragma unroll
-        for (int c = 0; c < S; ++c) racc[c] = macc[c] = 0.0;
-        const unsigned k0 = np_off[node], k1 = np_off[node + 1];
-        for (unsigned kb = k0; kb < k1; kb += 4) {     // (k_vector_from_partials' loads: four partials in flight, the additions in order)
-            unsigned v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
-            double rp[4][S], mp[4][S];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int c = 0; c < S; ++c) {
-                    rp[j][c] = rpart[(size_t)v[j] * S + c];
-                    mp[j][c] = mpart ? mpart[(size_t)v[j] * S + c] : 0.0;
-                }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (kb + j < k1) {
-#pragma unroll
-                    for (int c = 0; c < S; ++c) {
-                        racc[c] += rp[j][c];
-                        macc[c] += mp[j][c];
-                    }
-                }
-        }
+        double acc[2][S];
+        node_partials_sum(np_off, np_idx, {rpart, mpart}, node, acc);
+        double(&racc)[S] = acc[0], (&macc)[S] = acc[1];
         const bool fixed = dmask && dmask[node];
         if constexpr (S > 1) {
             if (ct.count) contact_force<S>(ct, node, racc);
@@ -782,33 +693,7 @@ __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, con
             sq = fma(v, v, sq);
         }
     }
-    const double tot = block_sum_256(sq, red);
-    if (threadIdx.x == 0) norm_partial[blockIdx.x] = tot;
-}
-
-// the residual partials of one node summed in ascending order (k_vector_from_partials' loads: four partials in flight, the additions in
-// order), for the node passes of the time integrators
-template <int S>
-__device__ __forceinline__ void node_partials_sum(const unsigned* np_off, const unsigned* np_idx, const double* rpart, int node, double (&racc)[S]) {
-#pragma unroll
-    for (int c = 0; c < S; ++c) racc[c] = 0.0;
-    const unsigned k0 = np_off[node], k1 = np_off[node + 1];
-    for (unsigned kb = k0; kb < k1; kb += 4) {
-        unsigned v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = np_idx[min(kb + j, k1 - 1)];
-        double rp[4][S];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int c = 0; c < S; ++c) rp[j][c] = rpart[(size_t)v[j] * S + c];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (kb + j < k1) {
-#pragma unroll
-                for (int c = 0; c < S; ++c) racc[c] += rp[j][c];
-            }
-    }
+    block_partial_store(sq, norm_partial);
 }
 
 // node pass of a central-difference step (engine_dynamics.hip): the node's residual partials summed in ascending order as
@@ -819,7 +704,6 @@ __device__ __forceinline__ void node_partials_sum(const unsigned* np_off, const 
 template <int S>
 __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
                                                                 const DynStep p, const ContactTable ct) {
-    __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     double ke = 0.0;
     if (node < num_nodes) {
@@ -833,10 +717,7 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
 #pragma unroll
         for (int c = 0; c < S; ++c) ke += dyn_dof(p, (size_t)node * S + c, fixed, lf, racc[c]);
     }
-    if (p.flags & DYN_STORE) {
-        const double tot = block_sum_256(ke, red);
-        if (threadIdx.x == 0) p.ke_partial[blockIdx.x] = tot;
-    }
+    if (p.flags & DYN_STORE) block_partial_store(ke, p.ke_partial);
 }
 
 // node pass of one stage of a first-order Runge-Kutta-Legendre step, or of the rate alone (engine_dynamics.hip): the same ordered sum, then
@@ -846,7 +727,6 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
 template <int S>
 __global__ void __launch_bounds__(256) k_first_order_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
                                                                    const FoStage p, const ContactTable ct) {
-    __shared__ double red[4];
     const int node = blockIdx.x * 256 + threadIdx.x;
     double q = 0.0;
     if (node < num_nodes) {
@@ -860,10 +740,7 @@ __global__ void __launch_bounds__(256) k_first_order_from_partials(int num_nodes
 #pragma unroll
         for (int c = 0; c < S; ++c) q += fo_dof(p, (size_t)node * S + c, fixed, lf, racc[c]);
     }
-    if (p.flags & FO_STORE) {
-        const double tot = block_sum_256(q, red);
-        if (threadIdx.x == 0) p.partial[blockIdx.x] = tot;
-    }
+    if (p.flags & FO_STORE) block_partial_store(q, p.partial);
 }
 
 template <typename T>
