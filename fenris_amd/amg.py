@@ -30,7 +30,11 @@ class SmoothedAggregationAMG:
 
     The constructor attaches the hierarchy to the engine (fh_set_amg).  An engine holds one hierarchy: attaching another one (a second
     SmoothedAggregationAMG on the same Engine) or closing the engine orphans this one, and every later call on it (apply, update,
-    level_info, use as a preconditioner) raises FH_BAD_ARGUMENT.  Build a new one instead."""
+    level_info, use as a preconditioner) raises FH_BAD_ARGUMENT.  Build a new one instead.
+
+    The hierarchy holds the engine's pattern: a new mesh on the engine (Engine.set_mesh, a new assembler on it) followed by a pattern
+    build, or an operator of another solution dim, invalidates it, and apply, update and the AMG solves then raise FH_INVALID_STATE (the
+    lifetime rule in fenris_hip.h, above fh_mg_create).  Build a new one for the new mesh."""
 
     def __init__(self, element_assembler, csr, near_nullspace="rigid_body", theta=0.0, max_levels=10, degree=3, smoothing_range=15.0,
                  eig_steps=10):

@@ -553,6 +553,13 @@ static int classify_affine(fh_ctx* c) {
     return FH_OK;
 }
 
+// the FH_TENSOR coefficients are nq x d^4 doubles for the mesh they were sent for: a new mesh may have another d under the same nq, so
+// they go with the mesh, and check_ready answers FH_INVALID_STATE until fh_set_operator_tensor sends them again
+static void drop_tensor(fh_ctx* c) {
+    c->tensor_nq = 0;
+    c->tensor.release();
+}
+
 static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     ElemInfo ei;
     if (!elem_info(elem_kind, ei)) return c->fail(FH_BAD_ARGUMENT, "fh_set_mesh: unknown element kind");
@@ -587,6 +594,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     c->row_lo = 0;   // the row range is per-mesh state
     c->row_hi = -1;
     c->nq = 0;  // reference gradient tables depend on the element kind
+    drop_tensor(c);
     HIP_TRY(c, c->verts.alloc((size_t)N * ei.d));
     HIP_TRY(c, c->conn.alloc((size_t)c->flat_len));
     ++c->topo_gen;   // a new connectivity: tables that depend on the topology alone (the element tiles) are rebuilt
@@ -672,7 +680,21 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
     ++c->density_gen;
     c->ragged = true;
+    // the per-mesh state set_mesh_common drops.  A mask left from a flat mesh reached build_compute_adjacency through fh_pattern: ei.n is 0
+    // here (an element index k / 0) and `active` holds the old element count.
+    c->has_u = false;
+    c->has_mask = false;
     c->has_aff = false;
+    c->aff_failed = false;
+    c->perm_failed = false;
+    c->rows_try = 0;
+    c->has_ghat = false;
+    c->rs.active = false;
+    c->user_has_mask = false;
+    c->user_mask.clear();
+    c->nq = 0;
+    drop_tensor(c);
+    ++c->topo_gen;
     c->row_lo = 0;
     c->row_hi = -1;
     c->elem_kind = -1;

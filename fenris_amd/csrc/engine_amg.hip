@@ -44,6 +44,9 @@ struct fh_amg {
     uint32_t degree = 3, eig_steps = 10;
     double range = 15.0;
     DevBuf<double> ainv;   // coarsest level: the dense inverse, row-major
+    // level 0 holds the context's noff / ncols pointers, N and nnz: the pattern build and the solution dim they were read at
+    unsigned long long pattern_gen = 0;
+    int S = 0;
 };
 
 namespace {
@@ -453,6 +456,13 @@ int near_nullspace(fh_ctx* c, AmgLevel& L, int kind, const double* B) {
 }  // namespace
 
 extern "C++" int amg_precondition(fh_amg* h, const double* r, double* z) { return vcycle(h, 0, r, z); }
+// a pattern rebuilt since (fh_set_mesh*, fh_set_connectivity_ragged, then fh_pattern) frees or resizes what level 0 points into; another
+// solution dim (fh_set_operator) changes the block size under the same node-level arrays
+extern "C++" int amg_current(fh_amg* h, const char* who) {
+    fh_ctx* c = h->c;
+    if (c->has_pattern && c->pattern_gen == h->pattern_gen && c->S() == h->S) return FH_OK;
+    return c->fail(FH_INVALID_STATE, std::string(who) + ": the context's pattern changed since fh_amg_create (fh_set_mesh*, fh_pattern or fh_set_operator) -- make a new hierarchy");
+}
 extern "C++" void amg_orphan(fh_amg* h) { h->c = nullptr; }
 
 extern "C" {
@@ -483,6 +493,8 @@ int fh_amg_create(fh_ctx* c, const double* values_dev, int nullspace, const doub
     auto h = std::make_unique<fh_amg>();
     h->c = c;
     h->device = c->device;
+    h->pattern_gen = c->pattern_gen;
+    h->S = S;
     auto l0 = std::make_unique<AmgLevel>();
     l0->N = (int)c->N;
     l0->R = S;
@@ -515,6 +527,7 @@ int fh_amg_update_values(fh_amg* h, const double* values_dev) {
     if (!h || !h->c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(h->device);
     if (!values_dev) return h->c->fail(FH_BAD_ARGUMENT, "fh_amg_update_values: null values");
+    if (const int rc = amg_current(h, "fh_amg_update_values")) return rc;
     h->lv[0]->vals = values_dev;
     return numeric_all(h);
 }
@@ -543,6 +556,7 @@ int fh_amg_set_smoother(fh_amg* h, uint32_t degree, double range, uint32_t eig_s
     DevGuard dev_guard_(h->device);
     if (degree < 1 || degree > 64 || !(range > 1.0) || eig_steps < 1 || eig_steps > 200)
         return h->c->fail(FH_BAD_ARGUMENT, "fh_amg_set_smoother: degree 1..64, range > 1, eig_steps 1..200");
+    if (const int rc = amg_current(h, "fh_amg_set_smoother")) return rc;
     h->degree = degree;
     h->range = range;
     h->eig_steps = eig_steps;
@@ -554,7 +568,9 @@ int fh_amg_apply_dev(fh_amg* h, const double* r_dev, double* z_dev) {
     fh_ctx* c = h->c;
     DevGuard dev_guard_(c->device);
     if (!r_dev || !z_dev || r_dev == z_dev) return c->fail(FH_BAD_ARGUMENT, "fh_amg_apply_dev: null or aliased vectors");
-    const int rc = vcycle(h, 0, r_dev, z_dev);
+    int rc = amg_current(h, "fh_amg_apply_dev");
+    if (rc) return rc;
+    rc = vcycle(h, 0, r_dev, z_dev);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FH_OK;
@@ -592,6 +608,8 @@ int fh_amg_level_matrix(fh_amg* h, uint32_t level, int which, uint64_t* row_offs
     if (!nnz || which < 0 || which > 3) return c->fail(FH_BAD_ARGUMENT, "fh_amg_level_matrix: which is 0 (A), 1 (P), 2 (T) or 3 (B); nnz is required");
     const bool transfer = which == 1 || which == 2;
     if (level >= h->lv.size() || (transfer && level + 1 >= h->lv.size())) return c->fail(FH_BAD_ARGUMENT, "fh_amg_level_matrix: no such matrix");
+    if (level == 0 && which == 0)
+        if (const int rc = amg_current(h, "fh_amg_level_matrix")) return rc;
     const AmgLevel& L = *h->lv[level];
     const int R = L.R, N = L.N;
     if (which >= 2) {   // dense rows of C entries: T (block column agg(i), none on isolated nodes) or B

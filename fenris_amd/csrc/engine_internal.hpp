@@ -621,6 +621,8 @@ int mg_chebyshev(hipStream_t st, const LevelApply& apply, int n, const double* d
 int mg_dense_inverse(fh_ctx* f, const char* who, std::vector<double>& A, int n, std::vector<double>& Ainv, double drop = 0.0);
 // FH_PRECOND_AMG (engine_amg.hip) on c->amg: one V-cycle z = B r; the context is going away
 int amg_precondition(fh_amg* amg, const double* r, double* z);
+// FH_OK while the context's pattern and solution dim are the ones the hierarchy's level 0 points into, FH_INVALID_STATE after
+int amg_current(fh_amg* amg, const char* who);
 void amg_orphan(fh_amg* amg);
 // the cached boundary search and surface-load tables (engine_boundary.hip): dropped with the connectivity, kept by fh_update_vertices
 void boundary_drop(fh_ctx* c);

@@ -18,6 +18,7 @@ constexpr int MG_MAX_COARSE_DOFS = 4096;
 struct MgLevel {
     fh_ctx* c = nullptr;
     int S = 0, N = 0, n = 0;
+    unsigned long long topo_gen = 0;   // the level's mesh at creation: the vectors and transfers below have its sizes
     DevBuf<double> diag, b, x, r, d, t;
     double lambda = 0.0;
     unsigned long long key[8] = {};
@@ -385,6 +386,13 @@ extern "C++" int mg_setup(fh_ctx* fine, double alpha, double beta) {
     StreamBorrow borrow(mg);
     const int L = (int)mg->lv.size() - 1;
     int rc;
+    // the work vectors, the diagonal and the transfers were sized for each level's mesh at fh_mg_create: a level whose mesh or solution dim has
+    // changed since would have S * N entries written into arrays of the old length
+    for (int l = 0; l <= L; ++l) {
+        const MgLevel& V = mg->lv[l];
+        if (V.c->topo_gen != V.topo_gen || (int)V.c->N != V.N || V.c->S() != V.S || !V.c->has_mesh || V.c->ragged)
+            return fine->fail(FH_INVALID_STATE, "multigrid level " + std::to_string(l) + ": the level's mesh or operator changed since fh_mg_create (fh_set_mesh*) -- make a new hierarchy");
+    }
     for (int l = L - 1; l >= 0; --l) {
         MgLevel& C = mg->lv[l];
         const fh_ctx* src = mg->lv[l + 1].c;
@@ -485,6 +493,7 @@ int fh_mg_create(fh_ctx* fine, uint64_t num_coarse, fh_ctx* const* coarse, const
         V.S = S;
         V.N = (int)ctx[l]->N;
         V.n = S * V.N;
+        V.topo_gen = ctx[l]->topo_gen;
         HIP_TRY(fine, V.diag.alloc(V.n));
         HIP_TRY(fine, V.r.alloc(V.n));
         HIP_TRY(fine, V.d.alloc(V.n));

@@ -211,6 +211,7 @@ int fh_cg_solve_dev(fh_ctx* c, const double* values_dev, const double* b_dev, do
         return c->fail(FH_BAD_ARGUMENT, "fh_cg_solve: unknown preconditioner");
     const bool amg = preconditioner == FH_PRECOND_AMG;
     if (amg && !c->amg) return c->fail(FH_INVALID_STATE, "fh_cg_solve: FH_PRECOND_AMG needs a hierarchy (fh_set_amg)");
+    if (amg && (rc = amg_current(c->amg, "fh_cg_solve"))) return rc;
     const int S = c->S();
     const int n = S * (int)c->N;
     if (n == 0) return FH_OK;

@@ -34,7 +34,11 @@ class GeometricMultigrid:
     """V-cycle preconditioner over coarse_meshes (coarsest first) and transfers (transfers[k]: coarse_meshes[k] -> the next finer mesh, the
     last one -> the fine assembler's mesh; Transfer objects of fenris_amd.refinement).  coarse_operator "tangent": the fine operator on
     every level (NeoHookean, StVK and StableNeoHookean levels receive the fine u by injection at each solve); "linearized": LinearElastic with the same Lame
-    data on the coarse levels (the tangent at u = 0).  degree, smoothing_range: the Chebyshev-Jacobi smoother (fh_mg_set_smoother)."""
+    data on the coarse levels (the tangent at u = 0).  degree, smoothing_range: the Chebyshev-Jacobi smoother (fh_mg_set_smoother).
+
+    The hierarchy is sized for the meshes its engines hold when it is made: Engine.set_mesh on the fine engine or on a level's engine
+    invalidates it, and the multigrid solves and apply then raise FH_INVALID_STATE naming the level (the lifetime rule in fenris_hip.h,
+    above fh_mg_create).  Build a new GeometricMultigrid for the new meshes."""
 
     def __init__(self, fine_assembler, coarse_meshes, transfers, coarse_operator="tangent", degree=3, smoothing_range=15.0, eig_steps=10):
         if coarse_operator not in ("tangent", "linearized"):

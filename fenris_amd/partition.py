@@ -443,12 +443,15 @@ class PartAssembly:
         scratch = self._vec_scratch
         self.main.assemble_vector(scratch)
         self.exchange.run_vector(scratch, s)
-        okey = (s, str(out.device), id(self.prob.owned), len(self.prob.owned))
-        if getattr(self, "_owned_dofs_key", None) != okey:
+        # the dofs of the owned nodes, kept per (s, device, the `owned` array itself): the array is held and compared by identity -- its id()
+        # alone can be that of a dead array's successor of the same length
+        okey = (s, str(out.device))
+        if getattr(self, "_owned_dofs_key", None) != okey or getattr(self, "_owned_dofs_of", None) is not self.prob.owned:
             owned = np.asarray(self.prob.owned, dtype=np.int64)
             dofs = (s * owned[:, None] + np.arange(s, dtype=np.int64)[None, :]).reshape(-1)
             self._owned_dofs = torch.from_numpy(dofs).to(out.device)
             self._owned_dofs_key = okey
+            self._owned_dofs_of = self.prob.owned
         out.index_add_(0, self._owned_dofs, scratch.index_select(0, self._owned_dofs))
 
     def poll_status(self):

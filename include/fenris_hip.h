@@ -980,7 +980,18 @@ int fh_add_contact_tangent_csr_dev(fh_ctx*, double* values_dev);
  * lambda_lo = lambda_max / range, theta = (hi + lo)/2, delta = (hi - lo)/2, r = b - A x, d = D^-1 r / theta, rho = delta / theta, for
  * k = 1..m:  x += d;  if k < m:  r -= A d,  rho' = 1 / (2 theta / delta - rho),  d = rho' rho d + (2 rho' / delta) D^-1 r,  rho = rho'.
  * Pre-smoothing starts from x = 0.  Every call runs on the fine context's stream (the coarse contexts' streams are pointed at it for the
- * duration of the call); no host synchronisation inside a V-cycle, no floating-point atomics: every solve repeats bit for bit. */
+ * duration of the call); no host synchronisation inside a V-cycle, no floating-point atomics: every solve repeats bit for bit.
+ *
+ * LIFETIME OF A HIERARCHY OR HANDLE MADE FOR A CONTEXT (fh_mg, fh_amg, fh_dynamics): it is sized for the mesh the context
+ * held at its creation and is invalidated by fh_set_mesh*, fh_set_mesh_from_* and fh_set_connectivity_ragged on that context -- for an
+ * fh_mg on ANY of its levels' contexts -- and by an operator of another solution dim.  An fh_amg also holds the context's pattern arrays:
+ * the fh_pattern that builds a pattern again (after a new mesh; a repeated fh_pattern on an unchanged context builds nothing and keeps
+ * the hierarchy valid) invalidates it.  Every entry that uses an invalidated hierarchy or handle -- the FH_PRECOND_MULTIGRID solves,
+ * fh_newton_solve, the integrators and fh_eigs_lowest with it, fh_mg_apply_dev; fh_cg_solve* with FH_PRECOND_AMG, fh_amg_apply_dev,
+ * fh_amg_update_values, fh_amg_set_smoother, fh_amg_level_matrix of level 0 -- returns FH_INVALID_STATE with a message that names the
+ * creating call (and, for fh_mg, the level) and touches no device memory.  The only valid uses left are fh_*_destroy and detaching
+ * (fh_set_multigrid / fh_set_amg with NULL or another hierarchy); make a new one for the new mesh.  The same holds for the FH_TENSOR
+ * coefficients of fh_set_operator_tensor: they go with the mesh, and every assembler answers FH_INVALID_STATE until they are sent again. */
 int fh_mg_create(fh_ctx* fine, uint64_t num_coarse, fh_ctx* const* coarse, const uint64_t* const* transfer_offsets,
                  const uint64_t* const* transfer_indices, const double* const* transfer_weights, fh_mg** out);
 void fh_mg_destroy(fh_mg*);
@@ -1019,7 +1030,8 @@ int fh_mg_apply_dev(fh_mg*, double alpha, double beta, const double* r_dev, doub
  * FH_BAD_ARGUMENT; a row of A P or P^T (A P) with more than 512 blocks: FH_UNSUPPORTED.  values_dev must stay allocated while the hierarchy
  * is used (level 0 reads it).  The values passed to an FH_PRECOND_AMG solve must be those the hierarchy was built from or last refreshed with.
  * The hierarchy refers to the context's pattern: destroying the context while it is attached (or attaching another one) orphans it,
- * and every later call on it but fh_amg_destroy returns FH_BAD_ARGUMENT; fh_amg_destroy then only frees it. */
+ * and every later call on it but fh_amg_destroy returns FH_BAD_ARGUMENT; fh_amg_destroy then only frees it.  A pattern built again
+ * on the context, or another solution dim, invalidates it: FH_INVALID_STATE (the lifetime rule above fh_mg_create). */
 enum { FH_PRECOND_AMG = 3 };
 enum { FH_AMG_CONSTANT = 0, FH_AMG_RIGID_BODY = 1, FH_AMG_USER = 2 };
 int fh_amg_create(fh_ctx*, const double* values_dev, int nullspace, const double* B, uint32_t nb, double theta, uint32_t max_levels,

@@ -509,3 +509,43 @@ def test_part_assembly_accumulate_contract(oracle):
         assert np.abs(got[owned] - (2.5 + 2.0 * ref)).max() <= 1e-12 * max(1.0, np.abs(want).max())
     finally:
         pa.close()
+
+
+@pytest.mark.gpu
+def test_owned_dofs_follow_a_replaced_owned_array(oracle):
+    """``assemble_vector`` keeps the dofs of ``prob.owned`` on the device between calls.  The key held id(owned) and its length: an array that
+    replaces ``owned`` with the same length -- and, once the old one is collected, possibly the same id -- must be read again.  The array is
+    now held and compared by identity.  One rank, every node owned; the replacement drops half of the nodes and names the others twice."""
+    import torch
+
+    mesh = _mesh("sphere")
+    s = 3
+    ug = _u_for(mesh, s)
+    w, p = _rule(mesh)
+    qt = fa.UniformQuadratureTable.from_points_and_weights(p, w).with_uniform_data(fa.LameParameters(*LAME))
+    fop = fa.MaterialEllipticOperator(fa.LinearElasticMaterial())
+    prob = fp.make_part(mesh, fp.morton_partition(mesh, 1), 0, 1)
+
+    def configure(engine, m):
+        return (fa.ElementEllipticAssemblerBuilder(engine).with_finite_element_space(m).with_operator(fop).with_quadrature_table(qt)
+                .with_u(ug.reshape(-1, s)[prob.l2g].reshape(-1)).build())
+
+    pa = fp.PartAssembly(prob, configure, device=0)
+    try:
+        want = _global_vector(oracle, mesh, oracle.LINEAR_ELASTIC, ug).reshape(-1, s)[prob.l2g]
+        out = torch.zeros(s * prob.mesh.num_nodes(), dtype=torch.float64, device="cuda:0")
+        pa.assemble_vector(out)
+        first = np.asarray(prob.owned).copy()
+        assert np.abs(out.cpu().numpy().reshape(-1, s)[first] - want[first]).max() <= 1e-12 * np.abs(want).max()
+        kept = first[::2]
+        prob.owned = np.concatenate([kept, kept])[:len(first)]      # the same length, other rows
+        assert len(prob.owned) == len(first)
+        out.fill_(2.5)
+        pa.assemble_vector(out)
+        got = out.cpu().numpy().reshape(-1, s)
+        count = np.bincount(prob.owned, minlength=prob.mesh.num_nodes())[:, None]
+        assert count.max() == 2 and count.min() == 0
+        assert np.abs(got - (2.5 + count * want)).max() <= 1e-12 * max(1.0, np.abs(want).max())
+        assert np.all(got[count[:, 0] == 0] == 2.5)                # the rows that are no longer owned are left as they were
+    finally:
+        pa.close()
