@@ -61,17 +61,11 @@ int dyn_ready(fh_dynamics* d, const char* who) {
 int residual_tiles(fh_dynamics* d, bool* tiles) {
     fh_ctx* c = d->c;
     *tiles = false;
-    if (!(c->E > 0 && !c->rs.active && tiles_enabled(c))) return FH_OK;
-    int rc = ensure_vector_tiles(c);
-    if (rc || c->vt_bad) return rc;
-    const size_t need = (size_t)c->vt.v.npartials * c->S();
-    if (d->rpart.n < need) HIP_TRY(c, d->rpart.alloc(need));
-    KArgs a;
-    fill_common(c, a);
-    a.work_begin = 0;
-    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-    a.labels = nullptr;
-    if (vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, c->has_mask ? c->active.p : nullptr, d->rpart.p) != FH_OK) return FH_OK;
+    if (!(c->E > 0 && !c->rs.active)) return FH_OK;
+    bool serve;
+    const int rc = tile_partials(c, d->rpart, c->S(), &serve);
+    if (rc || !serve) return rc;
+    if (vector_tiles_element_pass(c->elem_kind, c->op, c->stream, pass_args(c), c->vt.v, active_mask(c), d->rpart.p) != FH_OK) return FH_OK;
     HIP_TRY(c, hipGetLastError());
     *tiles = true;
     return FH_OK;
@@ -79,13 +73,7 @@ int residual_tiles(fh_dynamics* d, bool* tiles) {
 
 // r(u) summed into d->r on every other route (newton_residual's second branch): waits for the device and reports the kernels' status;
 // with obstacles set, r + g (one launch of k_contact_force behind the node sums)
-int residual_summed(fh_dynamics* d) {
-    fh_ctx* c = d->c;
-    HIP_TRY(c, hipMemsetAsync(d->r.p, 0, sizeof(double) * (size_t)d->n, c->stream));
-    const int rc = c->rs.active ? rs_walk_accumulating(c, nullptr, [&](uint64_t* fl) { return residual_ordered_single(c, d->r.p, fl); })
-                                : residual_ordered_single(c, d->r.p, nullptr);
-    return rc ? rc : contact_add_force(c, d->r.p);
-}
+int residual_summed(fh_dynamics* d) { return ::residual_summed(d->c, d->r.p); }
 
 int sum_blocks(fh_ctx* c, const double* partial, int count, double* out) { return sum_partials(c, partial, count, 1, out); }
 

@@ -565,7 +565,8 @@ struct DevGuard {
 
 // ---- functions shared by the translation units of the engine (engine.hip: context, mesh, pattern, options; engine_partition.hip: owner
 // blocks and position tables; engine_matrix.hip: stiffness / mass launchers; engine_two_pass.hip: dense element matrices + row gather;
-// engine_vector.hip: residual, source, energy; engine_solver.hip: Dirichlet rows, SpMV, PCG, error integrals; engine_eigs.hip: block vectors
+// engine_vector.hip: the host side of the element-to-node passes -- residual, source, energy, the matrix-free maps, the Newton residual;
+// engine_solver.hip: Dirichlet rows, SpMV, PCG, error integrals; engine_eigs.hip: block vectors
 // and the LOBPCG eigensolver; engine_dynamics.hip: the time integrators)
 constexpr size_t LDS_TARGET = 64 * 1024;   // two workgroups per CU
 constexpr size_t LDS_LIMIT = 160 * 1024;   // hardware limit per workgroup
@@ -589,14 +590,12 @@ int assemble_two_pass(fh_ctx* c, double* values_dev, int overwrite);
 size_t two_pass_dense_doubles(fh_ctx* c);   // doubles of the element-matrix buffer between the two passes (depends on the first pass's layout)
 int hex8_tune_lanes_now(fh_ctx* c);
 int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset = true);
-// matrix-free map (engine_vector.hip): checks (scope: MF_OPERATOR for the operator, MF_TANGENT for the tangent), y = T(u) x (+ per-workgroup
-// partials of x . y; *partials: their number), the diagonal
+// matrix-free map (engine_vector.hip): checks (scope: MF_OPERATOR for the operator, MF_TANGENT for the tangent)
 enum { MF_OPERATOR = 0, MF_TANGENT = 1 };
 int mf_ready(fh_ctx* c, const char* who, int scope);
-int mf_apply(fh_ctx* c, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
-int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale);
-// the shifted map alpha M + beta T(u) (fh_apply_shifted_tangent_dev): checks (alpha != 0 needs the density), y and its partials of x . y as
-// mf_apply, the diagonal as mf_diagonal.  alpha == 0, beta == 1 is the plain map.
+// the shifted map alpha M + beta T(u) (fh_apply_shifted_tangent_dev): checks (alpha != 0 needs the density), y = (alpha M + beta T(u)) x
+// (+ per-workgroup partials of x . y; *partials: their number), the diagonal (with_scale: and the scale of the Dirichlet rows).
+// alpha == 0, beta == 1 is the plain map y = T(u) x.
 int mf_shift_ready(fh_ctx* c, const char* who, double alpha, double beta);
 int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x_dev, double* y_dev, DevBuf<double>* dot_scratch, int* partials);
 int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bool with_scale);
@@ -645,13 +644,18 @@ struct NewtonScratch {
     DevBuf<double> wg, sums;          // per-workgroup partials of |F|^2, and their ordered range sums
 };
 int newton_residual(fh_ctx* c, double alpha, double beta, const double* f_dev, const double* d_dev, NewtonScratch& ns, double* norm2);
-// pieces of that residual and of the Newton loop that the time integrators (engine_dynamics.hip) compose again: the element tiles serve this
-// context / are built for its topology (vt_bad: they could not be); r(u) of the current table ADDED to out through element vectors and the
-// ordered node sums (engine_vector.hip); M x (x null: the diagonal) over every group of the table into out; the loop of fh_newton_solve on
-// the context's u (engine_newton.hip; st: 4 counters, nm: 3 norms, as fh_newton_solve's stats and norms)
+// pieces of that residual and of the Newton loop that the time integrators (engine_dynamics.hip) compose again, from the host frame of the
+// element-to-node passes (engine_vector.hip): the arguments of a pass over the whole table and its element mask (null: none); *serve: the
+// element tiles serve this context (the switches leave them on, ensure_vector_tiles has built them: vt_bad says it could not) and `part`
+// holds comps doubles per tile partial; r(u) (+ the contact force) and M x (x null: the diagonal) over every group of the table into out
+// through element vectors and the ordered node sums; the loop of fh_newton_solve on the context's u (engine_newton.hip; st: 4 counters,
+// nm: 3 norms, as fh_newton_solve's stats and norms)
+KArgs pass_args(fh_ctx* c);
+const unsigned char* active_mask(const fh_ctx* c);
 bool tiles_enabled(const fh_ctx* c);
 int ensure_vector_tiles(fh_ctx* c);
-int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed);
+int tile_partials(fh_ctx* c, DevBuf<double>& part, int comps, bool* serve, bool even_with_atomics = false);
+int residual_summed(fh_ctx* c, double* out);
 int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* out);
 // penalty contact (engine_contact.hip).  contact_table: the table for a kernel of the tangent / residual routes at the context's u, "off"
 // (count 0) without obstacles or in the operator's scope; contact_blocked: FH_UNSUPPORTED when obstacles are set and the operator's solution

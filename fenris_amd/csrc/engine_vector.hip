@@ -1,4 +1,8 @@
-// Residual, source vector, energy: launchers and C ABI
+// The host side of every element-to-node pass, and its C ABI: the residual (fh_assemble_vector), the source vector and the physical quadrature
+// points, the energy (fh_assemble_scalar), the matrix-free operator and tangent y = T(u) x with their diagonal and Dirichlet rows, the mass
+// term and the shifted map alpha M + beta T(u), and the Newton residual.  The steps they share are written once, in "the host frame" below:
+// the arguments of a whole-table pass, whether the element tiles serve a call and where their partials go, the ordered single-table pass
+// (tiles, else element vectors and ordered node sums), and the walk over the groups of a rule-set table.
 #include "engine_internal.hpp"
 
 template <int EK, int OP>
@@ -72,6 +76,84 @@ static bool element_pass_covers(const fh_ctx* c) {
 // the element tiles (vector_tiles.hip) serve this context
 bool tiles_enabled(const fh_ctx* c) { return element_pass_covers(c) && !c->opt.VECTOR_ATOMICS && !c->opt.NO_VECTOR_TILES; }
 
+// ---- the host frame of the element-to-node passes
+// the arguments of a pass over the whole table: every element, or the active ones of an element mask, in the mesh's order (no element list)
+KArgs pass_args(fh_ctx* c) {
+    KArgs a;
+    fill_common(c, a);
+    a.work_begin = 0;
+    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
+    a.labels = nullptr;
+    return a;
+}
+// the element mask for the kernels that visit every element and zero the inactive ones' contributions, and the list of the active elements
+// for the assembled routes that visit only those (a.labels: asked for where such a route is taken)
+const unsigned char* active_mask(const fh_ctx* c) { return c->has_mask ? c->active.p : nullptr; }
+static const unsigned* active_labels(const fh_ctx* c) { return c->has_mask ? c->active_list.p : nullptr; }
+
+// *serve: the element tiles (vector_tiles.hip) serve this context -- the switches leave them on, and the tables are built for its topology (they
+// could not be: vt_bad) -- and `part` then holds comps doubles per tile partial (comps 0: the caller sizes a buffer of another shape).  The
+// buffer is the caller's: fe_scratch, the Newton solver's and the integrators' partials are read by one pass while another is written.
+// even_with_atomics: the energy's condition -- a sum of partials whatever VECTOR_ATOMICS says, so that switch leaves it on the tiles.
+int tile_partials(fh_ctx* c, DevBuf<double>& part, int comps, bool* serve, bool even_with_atomics) {
+    *serve = false;
+    if (!(even_with_atomics ? element_pass_covers(c) && !c->opt.NO_VECTOR_TILES : tiles_enabled(c))) return FH_OK;
+    const int rc = ensure_vector_tiles(c);
+    if (rc || c->vt_bad) return rc;
+    const size_t need = (size_t)c->vt.v.npartials * comps;
+    if (part.n < need) HIP_TRY(c, part.alloc(need));
+    *serve = true;
+    return FH_OK;
+}
+
+// one quadrature table (or one group of a rule-set table) ADDED to out (S N doubles) without atomics: tile(a, &done) leaves its partials in
+// c->fe_scratch where the tiles cover the pass and the tiles' node pass sums them (tile nullptr: the caller owns that branch); else
+// elem(a, active, fe) leaves the element vectors fe[a][e][c] in c->fe_scratch and one thread per node sums its (element, local node) entries
+// of the source adjacency in order.  The status slot is the caller's.
+template <class Tile, class Elem>
+static int ordered_single(fh_ctx* c, double* out, Tile&& tile, Elem&& elem) {
+    const int S = c->S();
+    KArgs a = pass_args(c);
+    if constexpr (!std::is_null_pointer_v<std::decay_t<Tile>>) {
+        bool done;
+        const int rc = tile(a, &done);
+        if (rc) return rc;
+        if (done) {
+            HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, out));
+            return FH_OK;
+        }
+    }
+    int rc = build_source_adjacency(c);
+    if (rc) return rc;
+    const size_t need = (size_t)c->E * c->ei.n * S;
+    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    rc = elem(a, active_mask(c), c->fe_scratch.p);
+    if (rc) return rc;
+    HIP_TRY(c, hipGetLastError());
+    return launch_vector_from_elements_soa(c, S, c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
+}
+
+// out (n doubles) zeroed, then single(failed) of the one table, or of every group of a rule-set table, accumulating into it
+template <class F>
+static int walk_groups_into(fh_ctx* c, double* out, size_t n, uint64_t* failed, F&& single) {
+    HIP_TRY(c, hipMemsetAsync(out, 0, sizeof(double) * n, c->stream));
+    return c->rs.active ? rs_walk_accumulating(c, failed, single) : single(failed);
+}
+
+// the host-array form of a device entry point: a device buffer of len (+ pad) doubles, `host` copied in (copy_in), run(buffer), the buffer
+// copied back and the stream waited for (the buffer is released on return)
+template <class Run>
+static int through_device(fh_ctx* c, double* host, size_t len, size_t pad, bool copy_in, Run&& run) {
+    DevBuf<double> d;
+    HIP_TRY(c, d.alloc(len + pad));
+    if (copy_in) HIP_TRY(c, hipMemcpyAsync(d.p, host, sizeof(double) * len, hipMemcpyHostToDevice, c->stream));
+    const int rc = run(d.p);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(host, d.p, sizeof(double) * len, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FH_OK;
+}
+
 extern "C" {
 
 static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed);
@@ -121,33 +203,22 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) 
     rc = c->keep_status ? FH_OK : reset_status(c);
     if (rc) return rc;
     if (c->E == 0) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
+    KArgs a = pass_args(c);
     a.vec_out = out_dev;
-    a.work_begin = 0;
-    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-    a.labels = c->has_mask ? c->active_list.p : nullptr;
     if (a.work_end == 0) return read_status(c, failed);
     // small iso-parametric elements: tiles of 256 elements, one thread per element, the tile's distinct nodes summed in LDS, only
     // those partial sums through HBM, then one thread per node (vector_tiles.hip); no atomics, bitwise reproducible; an element mask
     // zeroes the contributions of the inactive elements
-    if (tiles_enabled(c) && op_has_stress(c->op)) {
-        rc = ensure_vector_tiles(c);
-        if (rc) return rc;
-        if (!c->vt_bad) {
-            const size_t need = (size_t)c->vt.v.npartials * c->S();
-            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-            KArgs at = a;
-            at.labels = nullptr;
-            const int rs = vector_tiles_element_pass(c->elem_kind, c->op, c->stream, at, c->vt.v, c->has_mask ? c->active.p : nullptr, c->fe_scratch.p);
-            if (rs == FH_OK) {
-                HIP_TRY(c, hipGetLastError());
-                c->last_kernel = "k_element_pass_tiled + k_vector_from_partials";
-                HIP_TRY(c, vector_tiles_node_pass(c->stream, c->S(), (int)c->N, c->vt.v, c->fe_scratch.p, out_dev));
-                return read_status(c, failed);
-            }
-        }
+    bool serve;
+    rc = tile_partials(c, c->fe_scratch, c->S(), &serve);
+    if (rc) return rc;
+    if (serve && vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active_mask(c), c->fe_scratch.p) == FH_OK) {
+        HIP_TRY(c, hipGetLastError());
+        c->last_kernel = "k_element_pass_tiled + k_vector_from_partials";
+        HIP_TRY(c, vector_tiles_node_pass(c->stream, c->S(), (int)c->N, c->vt.v, c->fe_scratch.p, out_dev));
+        return read_status(c, failed);
     }
+    a.labels = active_labels(c);   // (the routes below take an element list where they can, and say where they cannot)
     // small iso-parametric elements without an element list: one thread per element, element vectors laid out by local node, then
     // one thread per node (element_pass.hpp); no atomics, bitwise reproducible
     if (!a.labels && element_pass_covers(c) && !c->opt.VECTOR_ATOMICS) {
@@ -208,15 +279,7 @@ int fh_assemble_vector(fh_ctx* c, double* out, uint64_t* failed) {
     int rc = check_ready(c, "fh_assemble_vector", false);
     if (rc) return rc;
     if (!out) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_vector: out is null");
-    const size_t len = (size_t)c->S() * c->N;
-    DevBuf<double> d;
-    HIP_TRY(c, d.alloc(len));
-    HIP_TRY(c, hipMemcpyAsync(d.p, out, sizeof(double) * len, hipMemcpyHostToDevice, c->stream));
-    rc = fh_assemble_vector_dev(c, d.p, failed);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, d.p, sizeof(double) * len, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FH_OK;
+    return through_device(c, out, (size_t)c->S() * c->N, 0, true, [&](double* d) { return fh_assemble_vector_dev(c, d, failed); });
 }
 
 // ---- ElementSourceAssembler (src/assembly/local/source.rs) ------------------------------------------------------
@@ -239,8 +302,7 @@ int fh_assemble_source_vector_dev(fh_ctx* c, uint32_t sdim, const double* g, con
     if (!values_dev && !c->has_params)
         return c->fail(FH_INVALID_STATE, "fh_assemble_source_vector: the uniform source needs the density in the quadrature table");
     if (c->E == 0) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
+    KArgs a = pass_args(c);
     SourceArgs sa{};
     sa.N = c->ei.n;
     sa.NG = c->ei.ng;
@@ -251,30 +313,20 @@ int fh_assemble_source_vector_dev(fh_ctx* c, uint32_t sdim, const double* g, con
     if (!values_dev)
         for (uint32_t k = 0; k < sdim; ++k) gval.v[k] = g[k];
     a.vec_out = out_dev;
-    a.work_begin = 0;
-    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-    a.labels = c->has_mask ? c->active_list.p : nullptr;
     if (a.work_end == 0) return FH_OK;
     // small iso-parametric elements: the tiles of the residual (vector_tiles.hip) -- element vectors summed per distinct node of a tile
     // in LDS, partial sums through HBM, one thread per node; an element mask zeroes the inactive elements
-    if (tiles_enabled(c)) {
-        rc = ensure_vector_tiles(c);
-        if (rc) return rc;
-        if (!c->vt_bad) {
-            const bool fact = !values_dev;   // GravitySource: scalar partials, the node sum multiplies by g
-            const size_t need = (size_t)c->vt.v.npartials * (fact ? 1 : sdim);
-            if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-            KArgs at = a;
-            at.labels = nullptr;
-            if (vector_tiles_source_pass(D, (int)sdim, c->ei.n, fact, c->stream, at, gval.v, sa.values, c->vt.v, c->has_mask ? c->active.p : nullptr,
-                                         c->fe_scratch.p) == 0) {
-                HIP_TRY(c, hipGetLastError());
-                c->last_kernel = "k_source_elements_tiled + k_vector_from_partials";
-                HIP_TRY(c, vector_tiles_node_pass(c->stream, (int)sdim, (int)c->N, c->vt.v, c->fe_scratch.p, out_dev, fact ? gval.v : nullptr));
-                return FH_OK;
-            }
-        }
+    const bool fact = !values_dev;   // GravitySource: scalar partials / element entries, the node sum multiplies by g (element_pass.hpp)
+    bool serve;
+    rc = tile_partials(c, c->fe_scratch, fact ? 1 : (int)sdim, &serve);
+    if (rc) return rc;
+    if (serve && vector_tiles_source_pass(D, (int)sdim, c->ei.n, fact, c->stream, a, gval.v, sa.values, c->vt.v, active_mask(c), c->fe_scratch.p) == 0) {
+        HIP_TRY(c, hipGetLastError());
+        c->last_kernel = "k_source_elements_tiled + k_vector_from_partials";
+        HIP_TRY(c, vector_tiles_node_pass(c->stream, (int)sdim, (int)c->N, c->vt.v, c->fe_scratch.p, out_dev, fact ? gval.v : nullptr));
+        return FH_OK;
     }
+    a.labels = active_labels(c);
     // two passes without atomics where the node adjacency is available (it comes with the pattern, which needs an operator
     // for the solution dimension): element vectors to scratch, then a per-row sum in element order
     bool two_pass = !a.labels && !c->ragged && c->op >= 0 && !c->opt.VECTOR_ATOMICS;
@@ -294,7 +346,6 @@ int fh_assemble_source_vector_dev(fh_ctx* c, uint32_t sdim, const double* g, con
     if (two_pass && element_pass_covers(c)) {   // one thread per element, element vectors by local node, one thread per node (element_pass.hpp)
         const int ge = (int)((c->E + 255) / 256);
         double* fe = c->fe_scratch.p;
-        const bool fact = !values_dev;   // GravitySource: scalar element entries, the node sum multiplies by g (element_pass.hpp)
         dispatch(low_order_kinds, c->elem_kind, 0, [&](auto ek) {   // (element_pass_covers: one of these)
             constexpr int DV = ElemT<ek()>::D, NV = ElemT<ek()>::N;
             return dispatch_bool(sdim == 1, [&](auto scalar) {
@@ -339,19 +390,15 @@ int fh_assemble_source_vector(fh_ctx* c, uint32_t sdim, const double* g, const d
     int rc = source_ready(c, "fh_assemble_source_vector");
     if (rc) return rc;
     if (!out) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_source_vector: out is null");
-    const size_t len = (size_t)sdim * c->N, nv = (size_t)c->E * c->nq * sdim;
-    DevBuf<double> d, v;
-    HIP_TRY(c, d.alloc(len + 1));
-    HIP_TRY(c, hipMemcpyAsync(d.p, out, sizeof(double) * len, hipMemcpyHostToDevice, c->stream));
-    if (values) {
-        HIP_TRY(c, v.alloc(nv + 1));
-        HIP_TRY(c, hipMemcpyAsync(v.p, values, sizeof(double) * nv, hipMemcpyHostToDevice, c->stream));
-    }
-    rc = fh_assemble_source_vector_dev(c, sdim, g, values ? v.p : nullptr, d.p);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, d.p, sizeof(double) * len, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FH_OK;
+    const size_t nv = (size_t)c->E * c->nq * sdim;
+    DevBuf<double> v;   // (input only; released after through_device's wait)
+    return through_device(c, out, (size_t)sdim * c->N, 1, true, [&](double* d) {
+        if (values) {
+            HIP_TRY(c, v.alloc(nv + 1));
+            HIP_TRY(c, hipMemcpyAsync(v.p, values, sizeof(double) * nv, hipMemcpyHostToDevice, c->stream));
+        }
+        return fh_assemble_source_vector_dev(c, sdim, g, values ? v.p : nullptr, d);
+    });
 }
 
 int fh_physical_quadrature_points_dev(fh_ctx* c, double* x_dev) {
@@ -362,8 +409,7 @@ int fh_physical_quadrature_points_dev(fh_ctx* c, double* x_dev) {
     if (rc) return rc;
     if (!x_dev) return c->fail(FH_BAD_ARGUMENT, "fh_physical_quadrature_points: output is null");
     if (c->E == 0) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
+    KArgs a = pass_args(c);
     SourceArgs sa{};
     sa.N = c->ei.n;
     sa.NG = c->ei.ng;
@@ -383,14 +429,7 @@ int fh_physical_quadrature_points(fh_ctx* c, double* x) {
     int rc = source_ready(c, "fh_physical_quadrature_points");
     if (rc) return rc;
     if (!x) return c->fail(FH_BAD_ARGUMENT, "fh_physical_quadrature_points: output is null");
-    const size_t n = (size_t)c->E * c->nq * c->ei.d;
-    DevBuf<double> d;
-    HIP_TRY(c, d.alloc(n + 1));
-    rc = fh_physical_quadrature_points_dev(c, d.p);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(x, d.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FH_OK;
+    return through_device(c, x, (size_t)c->E * c->nq * c->ei.d, 1, false, [&](double* d) { return fh_physical_quadrature_points_dev(c, d); });
 }
 
 static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed);
@@ -418,33 +457,28 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
     if (rc) return rc;
     *out = 0.0;
     if (c->E == 0) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
-    a.work_begin = 0;
-    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-    a.labels = c->has_mask ? c->active_list.p : nullptr;
+    KArgs a = pass_args(c);
     if (a.work_end == 0) return FH_OK;
     // element tiles (vector_tiles.hip): the elements in the tiles' (space-compact) order -- what makes the gathers local on a numbering
     // without locality (C3's permuted tetrahedra: 0.76 -> 0.20 ms per call); an element mask zeroes the inactive elements' energies
-    // (deliberately not tiles_enabled: the energy is a sum of partials whatever VECTOR_ATOMICS says, so that switch leaves it on the tiles)
-    if (element_pass_covers(c) && !c->opt.NO_VECTOR_TILES) {
-        rc = ensure_vector_tiles(c);
-        if (rc) return rc;
-        if (!c->vt_bad) {
-            const int grid = vector_tiles_energy_partials(c->vt.v);
-            if (c->scalar_partial.n < (size_t)grid + 1) HIP_TRY(c, c->scalar_partial.alloc((size_t)grid + 1));
-            KArgs at = a;
-            at.labels = nullptr;
-            if (vector_tiles_energy_pass(c->elem_kind, c->op, c->stream, at, c->vt.v, c->has_mask ? c->active.p : nullptr, c->scalar_partial.p) == grid) {
-                HIP_TRY(c, hipGetLastError());
-                c->last_kernel = "k_element_energy_tiled";
-                hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->scalar_partial.p, grid, c->scalar_partial.p + grid);
-                HIP_TRY(c, hipGetLastError());
-                HIP_TRY(c, hipMemcpyAsync(out, c->scalar_partial.p + grid, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                return read_status(c, failed);
-            }
+    // (deliberately not tiles_enabled: the energy is a sum of partials whatever VECTOR_ATOMICS says, so that switch leaves it on the tiles;
+    // one scalar per workgroup and their sum, not per-node partials: sized here)
+    bool serve;
+    rc = tile_partials(c, c->scalar_partial, 0, &serve, true);
+    if (rc) return rc;
+    if (serve) {
+        const int grid = vector_tiles_energy_partials(c->vt.v);
+        if (c->scalar_partial.n < (size_t)grid + 1) HIP_TRY(c, c->scalar_partial.alloc((size_t)grid + 1));
+        if (vector_tiles_energy_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active_mask(c), c->scalar_partial.p) == grid) {
+            HIP_TRY(c, hipGetLastError());
+            c->last_kernel = "k_element_energy_tiled";
+            hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, c->scalar_partial.p, grid, c->scalar_partial.p + grid);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(out, c->scalar_partial.p + grid, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            return read_status(c, failed);
         }
     }
+    a.labels = active_labels(c);
     if (!a.labels && element_pass_covers(c)) {
         // one thread per element (element_pass.hpp), workgroup partials in a fixed tree, the partials summed in index order by one
         // workgroup: one double comes back (global.rs:703-709 sums element by element; same terms, fixed association)
@@ -545,12 +579,10 @@ static int mf_scale_from(fh_ctx* c, const double* diag_dev, double alpha = 0.0, 
 // residual's element pass fed xin (linear operators), or k_tangent_tiled at the context's u.  *done = false: the tiles do not cover it.
 static int mf_tiles_pass(fh_ctx* c, KArgs& a, const double* xin, bool* done) {
     *done = false;
-    if (!tiles_enabled(c)) return FH_OK;
-    const int rc = ensure_vector_tiles(c);
-    if (rc || c->vt_bad) return rc;
-    const size_t need = (size_t)c->vt.v.npartials * c->S();
-    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
+    bool serve;
+    const int rc = tile_partials(c, c->fe_scratch, c->S(), &serve);
+    if (rc || !serve) return rc;
+    const unsigned char* active = active_mask(c);
     int rt;
     if (!xin) {
         rt = vector_tiles_diagonal_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p);
@@ -586,151 +618,53 @@ static int mf_single(fh_ctx* c, const double* xin, double* out, uint64_t* failed
     int rc = reset_status(c);
     if (rc) return rc;
     if (c->E == 0) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
-    a.work_begin = 0;
-    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-    const int S = c->S();
-    bool done;
-    rc = mf_tiles_pass(c, a, xin, &done);
-    if (rc) return rc;
-    if (done) {
-        if (xin) c->last_kernel = c->op <= FH_LINEAR_ELASTIC ? "k_element_pass_tiled + k_vector_from_partials" : "k_tangent_tiled + k_vector_from_partials";
-        HIP_TRY(c, vector_tiles_node_pass(c->stream, S, (int)c->N, c->vt.v, c->fe_scratch.p, out));
-        return read_status(c, failed);
-    }
-    rc = build_source_adjacency(c);
-    if (rc) return rc;
-    const size_t need = (size_t)c->E * c->ei.n * S;
-    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    mf_elements_launch(c, a, active, xin, c->fe_scratch.p);
-    HIP_TRY(c, hipGetLastError());
-    if (xin) c->last_kernel = "k_mf_apply_elements + k_vector_from_elements_soa";
-    rc = launch_vector_from_elements_soa(c, S, c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
-    if (rc) return rc;
-    return read_status(c, failed);
+    rc = ordered_single(
+        c, out,
+        [&](KArgs& a, bool* done) {
+            const int r = mf_tiles_pass(c, a, xin, done);
+            if (!r && *done && xin)
+                c->last_kernel = c->op <= FH_LINEAR_ELASTIC ? "k_element_pass_tiled + k_vector_from_partials" : "k_tangent_tiled + k_vector_from_partials";
+            return r;
+        },
+        [&](const KArgs& a, const unsigned char* active, double* fe) {
+            mf_elements_launch(c, a, active, xin, fe);
+            if (xin) c->last_kernel = "k_mf_apply_elements + k_vector_from_elements_soa";
+            return (int)FH_OK;
+        });
+    return rc ? rc : read_status(c, failed);
 }
 
-// the diagonal into diag_dev; with_scale: and, with Dirichlet nodes set, the scale of their rows (c->mf_scale) and their diagonal = scale
-int mf_diagonal(fh_ctx* c, double* diag_dev, bool with_scale) {
-    const int n = c->S() * (int)c->N;
-    HIP_TRY(c, hipMemsetAsync(diag_dev, 0, sizeof(double) * (size_t)n, c->stream));
-    uint64_t failed = 0;
-    int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_single(c, nullptr, diag_dev, f); })
-                          : mf_single(c, nullptr, diag_dev, &failed);
-    if (rc) return rc;
-    rc = contact_add_diagonal(c, diag_dev);   // diag B(u) of the penalty contact term (k_contact_diagonal), before the scale is taken
-    if (rc) return rc;
-    if (c->mf_num_dirichlet && with_scale) {
-        rc = mf_scale_from(c, diag_dev);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_mf_dirichlet_diag, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->S(), c->mf_dmask.p, c->mf_scale.p, diag_dev);
-        HIP_TRY(c, hipGetLastError());
-    }
-    return FH_OK;
-}
-
-// y = T(u) x.  The scale of the Dirichlet rows must be in c->mf_scale (mf_diagonal).  dot_scratch != null: per-workgroup partials of x . y
-// go to it (*partials of them, in order).  Singular Jacobians land in the status slot: the caller resets and reads it.
-int mf_apply(fh_ctx* c, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials) {
-    const int S = c->S(), N = (int)c->N, n = S * N;
-    const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
-    const double* xin = x;
-    const unsigned long long* xbits = nullptr;
-    if (c->op == FH_LINEAR_ELASTIC) {   // the operand scaled to |x|_inf in [1/2, 1) over the free entries (mf_exponent)
+// the operand of the map's element pass: x with the entries of the Dirichlet nodes zeroed and, for LinearElastic, scaled to |x 2^-e|_inf in
+// [1/2, 1) over the free entries (mf_exponent; bits: the absolute maximum the node pass scales back by), in c->mf_xm; x itself where neither applies
+struct MfOperand {
+    const double* x;
+    const unsigned long long* bits;
+};
+static int mf_operand(fh_ctx* c, const double* x, const unsigned char* dmask, MfOperand* in) {
+    const int S = c->S(), n = S * (int)c->N;
+    *in = MfOperand{x, nullptr};
+    if (c->op == FH_LINEAR_ELASTIC) {
         if (!c->mf_bits.p) HIP_TRY(c, c->mf_bits.alloc(1));
         HIP_TRY(c, hipMemsetAsync(c->mf_bits.p, 0, sizeof(unsigned long long), c->stream));
         hipLaunchKernelGGL(k_mf_absmax, dim3(std::max(1, std::min(1024, (n + 255) / 256))), dim3(256), 0, c->stream, n, S, x, dmask, c->mf_bits.p);
-        xbits = c->mf_bits.p;
+        in->bits = c->mf_bits.p;
     }
-    if (dmask || xbits) {
+    if (dmask || in->bits) {
         if (c->mf_xm.n < (size_t)n) HIP_TRY(c, c->mf_xm.alloc((size_t)n));
-        hipLaunchKernelGGL(k_mf_operand, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, S, x, dmask, xbits, c->mf_xm.p);
+        hipLaunchKernelGGL(k_mf_operand, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, S, x, dmask, in->bits, c->mf_xm.p);
         HIP_TRY(c, hipGetLastError());
-        xin = c->mf_xm.p;
-    }
-    if (c->E > 0 && !c->rs.active) {
-        KArgs a;
-        fill_common(c, a);
-        a.work_begin = 0;
-        a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-        bool done;
-        int rc = mf_tiles_pass(c, a, xin, &done);
-        if (rc) return rc;
-        if (done) {
-            const int g = vector_tiles_operator_partials(N);
-            double* dp = nullptr;
-            if (dot_scratch) {
-                if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
-                dp = dot_scratch->p;
-                *partials = g;
-            }
-            c->last_kernel = c->op <= FH_LINEAR_ELASTIC ? "k_element_pass_tiled + k_operator_from_partials" : "k_tangent_tiled + k_operator_from_partials";
-            HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp,
-                                                       contact_table(c)));
-            return FH_OK;
-        }
-    }
-    // elsewhere (kinds outside the tiles, rule-set groups, no tile tables): the element vectors of the operand accumulated into y = 0 without
-    // atomics, group by group; then the scale, the Dirichlet rows and the partials of x . y
-    HIP_TRY(c, hipMemsetAsync(y, 0, sizeof(double) * (size_t)n, c->stream));
-    uint64_t failed = 0;
-    const int rc = c->rs.active ? rs_walk_accumulating(c, &failed, [&](uint64_t* f) { return mf_single(c, xin, y, f); })
-                                : mf_single(c, xin, y, &failed);
-    if (rc) return rc;
-    const int rcc = contact_add_apply(c, x, xbits, y);   // B(u) x of the penalty contact term (k_contact_apply), one launch, before the finish
-    if (rcc) return rcc;
-    const int g = (n + 255) / 256;
-    double* dp = nullptr;
-    if (dot_scratch) {
-        if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
-        dp = dot_scratch->p;
-        *partials = g;
-    }
-    if (dmask || dp || xbits) {
-        hipLaunchKernelGGL(k_mf_finish, dim3(g), dim3(256), 0, c->stream, n, S, x, dmask, c->mf_scale.p, xbits, y, dp);
-        HIP_TRY(c, hipGetLastError());
+        in->x = c->mf_xm.p;
     }
     return FH_OK;
 }
 
-// the entry points: y = T(u) x (the scale of the Dirichlet rows formed again only when what it depends on has changed), and the diagonal
-static int mf_apply_entry(fh_ctx* c, const char* who, int scope, const double* x_dev, double* y_dev) {
-    if (!c) return FH_BAD_ARGUMENT;
-    DevGuard dev_guard_(c->device);
-    int rc = mf_ready(c, who, scope);
-    if (rc) return rc;
-    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
-    if (c->N == 0) return FH_OK;
-    MfScope scope_guard_(c, scope);
-    unsigned long long key[8];
-    mf_scale_key_now(c, key);
-    if (c->mf_num_dirichlet && !std::equal(key, key + 8, c->mf_scale_key)) {
-        DevBuf<double> diag;
-        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
-        rc = mf_diagonal(c, diag.p, true);
-        if (rc) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    rc = reset_status(c);
-    if (rc) return rc;
-    rc = mf_apply(c, x_dev, y_dev, nullptr, nullptr);
-    if (rc) return rc;
-    return read_status(c, nullptr);
-}
-
-static int mf_diagonal_entry(fh_ctx* c, const char* who, int scope, double* diag_dev) {
-    if (!c) return FH_BAD_ARGUMENT;
-    DevGuard dev_guard_(c->device);
-    int rc = mf_ready(c, who, scope);
-    if (rc) return rc;
-    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
-    if (c->N == 0) return FH_OK;
-    MfScope scope_guard_(c, scope);
-    rc = mf_diagonal(c, diag_dev, true);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+// where the g per-workgroup partials of x . y go: dot_scratch sized to them and *partials = g, or (dot_scratch null) nowhere
+static int dot_partials(fh_ctx* c, DevBuf<double>* dot_scratch, int g, int* partials, double** dp) {
+    *dp = nullptr;
+    if (!dot_scratch) return FH_OK;
+    if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
+    *dp = dot_scratch->p;
+    *partials = g;
     return FH_OK;
 }
 
@@ -749,17 +683,13 @@ int mf_shift_ready(fh_ctx* c, const char* who, double alpha, double beta) {
 }
 
 // the mass partials of the current table over the tiles into c->fe_scratch (x null: the diagonal); *done = false: the tiles do not cover it
-static int mass_tiles_pass(fh_ctx* c, const double* x, const unsigned char* dmask, bool* done) {
+static int mass_tiles_pass(fh_ctx* c, const KArgs& a, const double* x, const unsigned char* dmask, bool* done) {
     *done = false;
-    if (!tiles_enabled(c) || c->ei.ng != c->ei.n) return FH_OK;
-    const int rc = ensure_vector_tiles(c);
-    if (rc || c->vt_bad) return rc;
-    const size_t need = (size_t)c->vt.v.npartials * c->S();
-    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-    KArgs a;
-    fill_common(c, a);
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    if (vector_tiles_mass_pass(c->elem_kind, c->S(), c->stream, a, c->vt.v, active, c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, x, dmask,
+    if (c->ei.ng != c->ei.n) return FH_OK;
+    bool serve;
+    const int rc = tile_partials(c, c->fe_scratch, c->S(), &serve);
+    if (rc || !serve) return rc;
+    if (vector_tiles_mass_pass(c->elem_kind, c->S(), c->stream, a, c->vt.v, active_mask(c), c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, x, dmask,
                                c->fe_scratch.p) != 0)
         return FH_OK;
     HIP_TRY(c, hipGetLastError());
@@ -770,47 +700,37 @@ static int mass_tiles_pass(fh_ctx* c, const double* x, const unsigned char* dmas
 // M x (x null: the diagonal of M) of the current table ADDED to out: the tiles where they cover it, else k_mass_elements and the ordered node sums
 static int mass_single(fh_ctx* c, const double* x, const unsigned char* dmask, double* out) {
     if (c->E == 0 || (c->has_mask && c->num_active == 0)) return FH_OK;
-    bool done;
-    int rc = mass_tiles_pass(c, x, dmask, &done);
-    if (rc) return rc;
-    if (done) {
-        HIP_TRY(c, vector_tiles_node_pass(c->stream, c->S(), (int)c->N, c->vt.v, c->fe_scratch.p, out));
-        return FH_OK;
-    }
-    rc = build_source_adjacency(c);
-    if (rc) return rc;
-    const size_t need = (size_t)c->E * c->ei.n * c->S();
-    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-    KArgs a;
-    fill_common(c, a);
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    const int covered = dispatch(all_kinds, c->elem_kind, -1, [&](auto ek) {
-        using EL = ElemT<ek()>;
-        return dispatch_bool(c->S() == 1, [&](auto scalar) {
-            hipLaunchKernelGGL((k_mass_elements<EL::D, scalar() ? 1 : EL::D, EL::N, EL::NG>), dim3((unsigned)((c->E + 255) / 256)), dim3(256), 0, c->stream, a,
-                               active, c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, x, dmask, c->fe_scratch.p);
-            return 0;
+    return ordered_single(
+        c, out, [&](KArgs& a, bool* done) { return mass_tiles_pass(c, a, x, dmask, done); },
+        [&](const KArgs& a, const unsigned char* active, double* fe) {
+            const int covered = dispatch(all_kinds, c->elem_kind, -1, [&](auto ek) {
+                using EL = ElemT<ek()>;
+                return dispatch_bool(c->S() == 1, [&](auto scalar) {
+                    hipLaunchKernelGGL((k_mass_elements<EL::D, scalar() ? 1 : EL::D, EL::N, EL::NG>), dim3((unsigned)((c->E + 255) / 256)), dim3(256), 0, c->stream,
+                                       a, active, c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, x, dmask, fe);
+                    return 0;
+                });
+            });
+            return covered < 0 ? c->fail(FH_UNSUPPORTED, "the shifted map: unknown element kind") : (int)FH_OK;
         });
-    });
-    if (covered < 0) return c->fail(FH_UNSUPPORTED, "the shifted map: unknown element kind");
-    HIP_TRY(c, hipGetLastError());
-    return launch_vector_from_elements_soa(c, c->S(), c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
 }
 
-// M x (x null: its diagonal) over every group of the table into out (S N doubles)
+// M x (x null: its diagonal) over every group of the table into out (S N doubles); the mass has no status to report
 int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* out) {
-    const size_t n = (size_t)c->S() * c->N;
-    HIP_TRY(c, hipMemsetAsync(out, 0, sizeof(double) * n, c->stream));
-    if (c->rs.active) return rs_walk_accumulating(c, nullptr, [&](uint64_t*) { return mass_single(c, x, dmask, out); });
-    return mass_single(c, x, dmask, out);
+    return walk_groups_into(c, out, (size_t)c->S() * c->N, nullptr, [&](uint64_t*) { return mass_single(c, x, dmask, out); });
 }
 
+// the diagonal of alpha M + beta T(u) into diag_dev (alpha = 0, beta = 1: of T(u) alone, nothing combined); with_scale: and, with Dirichlet
+// nodes set, the scale of their rows (c->mf_scale) and their diagonal = scale
 int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bool with_scale) {
-    if (alpha == 0.0 && beta == 1.0) return mf_diagonal(c, diag_dev, with_scale);
+    const bool plain = alpha == 0.0 && beta == 1.0;
     const int n = c->S() * (int)c->N;
     int rc;
     if (beta != 0.0) {
-        rc = mf_diagonal(c, diag_dev, false);
+        uint64_t failed = 0;
+        rc = walk_groups_into(c, diag_dev, (size_t)n, &failed, [&](uint64_t* f) { return mf_single(c, nullptr, diag_dev, f); });
+        if (rc) return rc;
+        rc = contact_add_diagonal(c, diag_dev);   // diag B(u) of the penalty contact term (k_contact_diagonal), before the scale is taken
         if (rc) return rc;
     }
     DevBuf<double> md;   // (once per solve: released on return, so that the solve holds no more than the apply)
@@ -819,7 +739,7 @@ int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bo
         rc = mass_full(c, nullptr, nullptr, md.p);
         if (rc) return rc;
     }
-    if (n) {
+    if (!plain && n) {
         hipLaunchKernelGGL(k_mf_shift_combine, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->S(), alpha, alpha != 0.0 ? md.p : nullptr,
                            beta, beta != 0.0 ? diag_dev : nullptr, nullptr, nullptr, nullptr, diag_dev, nullptr);
         HIP_TRY(c, hipGetLastError());
@@ -834,93 +754,104 @@ int mf_shift_diagonal(fh_ctx* c, double alpha, double beta, double* diag_dev, bo
     return FH_OK;
 }
 
-// Hex8 on the tiles with the monomial table: the mass term fused into the element pass (vector_tiles_shifted_hex8_pass: beta T(u) x + alpha M x
-// in one pass, or alpha M x alone for beta == 0), then the operator's node pass -- y overwritten, the Dirichlet rows, the partials of x . y.
-// The operand as mf_apply prepares it (Dirichlet entries zeroed, LinearElastic scaled by 2^-e: M is linear, the node pass scales back).
-// *done = false: not covered, nothing was run.
-static int shift_hex8_fused(fh_ctx* c, double alpha, double beta, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials, bool* done) {
+// the whole map in ONE element pass over the tiles, then the operator's node pass -- y overwritten, the Dirichlet rows, + beta B(u) x of the
+// contact term, the partials of x . y.  The plain map (alpha = 0, beta = 1): the residual's element pass fed the operand, or k_tangent_tiled
+// (mf_tiles_pass; `in`: the operand, prepared by the caller, who shares it with the route off the tiles).  alpha != 0: Hex8 with the monomial
+// table only, the mass term fused into the element pass (vector_tiles_shifted_hex8_pass: beta T(u) x + alpha M x, or alpha M x alone for
+// beta == 0, which reads x and dmask itself and needs no operand; M is linear, so the node pass scales LinearElastic's 2^-e back for both
+// terms).  *done = false: not covered, nothing of the map was run.
+static int map_on_tiles(fh_ctx* c, double alpha, double beta, const double* x, MfOperand in, double* y, DevBuf<double>* dot_scratch, int* partials,
+                        bool* done) {
     *done = false;
-    if (c->elem_kind != FH_HEX8 || !tiles_enabled(c)) return FH_OK;
-    KArgs a;
-    fill_common(c, a);
-    if (!a.qmono) return FH_OK;
-    int rc = ensure_vector_tiles(c);
-    if (rc || c->vt_bad) return rc;
-    const int S = c->S(), N = (int)c->N, n = S * N;
-    const size_t need = (size_t)c->vt.v.npartials * S;
-    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
+    const int S = c->S(), N = (int)c->N;
     const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
-    const double* xin = x;
-    const unsigned long long* xbits = nullptr;
-    if (beta != 0.0) {   // (the mass alone reads x and dmask itself)
-        if (c->op == FH_LINEAR_ELASTIC) {
-            if (!c->mf_bits.p) HIP_TRY(c, c->mf_bits.alloc(1));
-            HIP_TRY(c, hipMemsetAsync(c->mf_bits.p, 0, sizeof(unsigned long long), c->stream));
-            hipLaunchKernelGGL(k_mf_absmax, dim3(std::max(1, std::min(1024, (n + 255) / 256))), dim3(256), 0, c->stream, n, S, x, dmask, c->mf_bits.p);
-            xbits = c->mf_bits.p;
+    const bool fused = alpha != 0.0, linear = c->op <= FH_LINEAR_ELASTIC;
+    KArgs a = pass_args(c);
+    int rc;
+    if (fused) {
+        if (c->elem_kind != FH_HEX8 || !a.qmono) return FH_OK;
+        bool serve;
+        rc = tile_partials(c, c->fe_scratch, S, &serve);
+        if (rc || !serve) return rc;
+        if (beta != 0.0) {
+            rc = mf_operand(c, x, dmask, &in);
+            if (rc) return rc;
+            if (linear) a.u = in.x;
         }
-        if (dmask || xbits) {
-            if (c->mf_xm.n < (size_t)n) HIP_TRY(c, c->mf_xm.alloc((size_t)n));
-            hipLaunchKernelGGL(k_mf_operand, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, S, x, dmask, xbits, c->mf_xm.p);
-            HIP_TRY(c, hipGetLastError());
-            xin = c->mf_xm.p;
-        }
-        if (c->op <= FH_LINEAR_ELASTIC) a.u = xin;
+        MassTerm mt;
+        mt.alpha = alpha;
+        mt.beta = beta;
+        mt.rho = c->mass_rho.p;
+        mt.per_elem = c->mass_rho_n > 1 ? 1 : 0;
+        mt.mom = (a.all_affine && c->qmom_ok && c->qmom.p && !c->has_rules) ? c->qmom.p : nullptr;
+        if (vector_tiles_shifted_hex8_pass(c->op, c->stream, a, c->vt.v, active_mask(c), in.x, dmask, mt, c->fe_scratch.p) != 0) return FH_OK;
+        HIP_TRY(c, hipGetLastError());
+    } else {
+        bool passed;
+        rc = mf_tiles_pass(c, a, in.x, &passed);
+        if (rc || !passed) return rc;
     }
-    a.work_begin = 0;
-    a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-    MassTerm mt;
-    mt.alpha = alpha;
-    mt.beta = beta;
-    mt.rho = c->mass_rho.p;
-    mt.per_elem = c->mass_rho_n > 1 ? 1 : 0;
-    mt.mom = (a.all_affine && c->qmom_ok && c->qmom.p && !c->has_rules) ? c->qmom.p : nullptr;
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    if (vector_tiles_shifted_hex8_pass(c->op, c->stream, a, c->vt.v, active, beta != 0.0 ? xin : x, dmask, mt, c->fe_scratch.p) != 0) return FH_OK;
-    HIP_TRY(c, hipGetLastError());
-    const int g = vector_tiles_operator_partials(N);
-    double* dp = nullptr;
-    if (dot_scratch) {
-        if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
-        dp = dot_scratch->p;
-        *partials = g;
-    }
-    c->last_kernel = beta == 0.0 ? "k_mass_hex8_tiled + k_operator_from_partials"
-                     : c->op <= FH_LINEAR_ELASTIC ? "k_shifted_pass_tiled + k_operator_from_partials" : "k_shifted_tangent_tiled + k_operator_from_partials";
-    HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, xbits, y, dp,
-                                               beta != 0.0 ? contact_table(c) : contact_off(), beta));   // (+ beta B(u) x)
+    double* dp;
+    rc = dot_partials(c, dot_scratch, vector_tiles_operator_partials(N), partials, &dp);
+    if (rc) return rc;
+    c->last_kernel = !fused        ? (linear ? "k_element_pass_tiled + k_operator_from_partials" : "k_tangent_tiled + k_operator_from_partials")
+                     : beta == 0.0 ? "k_mass_hex8_tiled + k_operator_from_partials"
+                     : linear      ? "k_shifted_pass_tiled + k_operator_from_partials"
+                                   : "k_shifted_tangent_tiled + k_operator_from_partials";
+    HIP_TRY(c, vector_tiles_operator_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, in.bits, y, dp,
+                                               beta != 0.0 ? contact_table(c) : contact_off(), beta));
     *done = true;
     return FH_OK;
 }
 
-// y = (alpha M + beta T(u)) x.  The scale of the Dirichlet rows must be in c->mf_scale (mf_shift_diagonal); dot_scratch, partials as mf_apply
+// y = (alpha M + beta T(u)) x; alpha = 0, beta = 1: y = T(u) x.  The scale of the Dirichlet rows must be in c->mf_scale (mf_shift_diagonal).
+// dot_scratch != null: per-workgroup partials of x . y go to it (*partials of them, in order).  Singular Jacobians land in the status slot: the
+// caller resets and reads it.  The stages, each taken where it covers the call: the whole map on the tiles (map_on_tiles); the mass partials on
+// the tiles and one node pass that adds beta T(u) x; everything composed -- T(u) x accumulated into y = 0 group by group, M x into scratch.
 int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x, double* y, DevBuf<double>* dot_scratch, int* partials) {
-    if (alpha == 0.0 && beta == 1.0) return mf_apply(c, x, y, dot_scratch, partials);
+    const bool plain = alpha == 0.0 && beta == 1.0, one_table = c->E > 0 && !c->rs.active;
     const int S = c->S(), N = (int)c->N, n = S * N;
     const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
-    if (dmask && !c->mf_scale.p) HIP_TRY(c, c->mf_scale.alloc(1));
+    if (!plain && dmask && !c->mf_scale.p) HIP_TRY(c, c->mf_scale.alloc(1));
     int rc;
-    if (alpha != 0.0 && c->E > 0 && !c->rs.active) {
-        bool done;
-        rc = shift_hex8_fused(c, alpha, beta, x, y, dot_scratch, partials, &done);
+    bool done;
+    double* dp;
+    MfOperand in{x, nullptr};
+    if (plain) {
+        rc = mf_operand(c, x, dmask, &in);
+        if (rc) return rc;
+    }
+    if (one_table && (plain || alpha != 0.0)) {
+        rc = map_on_tiles(c, alpha, beta, x, in, y, dot_scratch, partials, &done);
         if (rc || done) return rc;
     }
-    if (beta != 0.0) {   // beta T(u) x into y (its Dirichlet rows are written again below)
-        rc = mf_apply(c, x, y, nullptr, nullptr);
+    if (plain) {
+        // elsewhere (kinds outside the tiles, rule-set groups, no tile tables): the element vectors of the operand accumulated into y = 0 without
+        // atomics, group by group; then the scale, the Dirichlet rows and the partials of x . y
+        uint64_t failed = 0;
+        rc = walk_groups_into(c, y, (size_t)n, &failed, [&](uint64_t* f) { return mf_single(c, in.x, y, f); });
+        if (rc) return rc;
+        rc = contact_add_apply(c, x, in.bits, y);   // B(u) x of the penalty contact term (k_contact_apply), one launch, before the finish
+        if (rc) return rc;
+        const int g = (n + 255) / 256;
+        rc = dot_partials(c, dot_scratch, g, partials, &dp);
+        if (rc) return rc;
+        if (dmask || dp || in.bits) {
+            hipLaunchKernelGGL(k_mf_finish, dim3(g), dim3(256), 0, c->stream, n, S, x, dmask, c->mf_scale.p, in.bits, y, dp);
+            HIP_TRY(c, hipGetLastError());
+        }
+        return FH_OK;
+    }
+    if (beta != 0.0) {   // T(u) x into y (its Dirichlet rows are written again below)
+        rc = mf_shift_apply(c, 0.0, 1.0, x, y, nullptr, nullptr);
         if (rc) return rc;
     }
-    if (alpha != 0.0 && c->E > 0 && !c->rs.active) {
-        bool done;
-        rc = mass_tiles_pass(c, x, dmask, &done);
+    if (alpha != 0.0 && one_table) {
+        rc = mass_tiles_pass(c, pass_args(c), x, dmask, &done);
         if (rc) return rc;
         if (done) {
-            const int g = vector_tiles_operator_partials(N);
-            double* dp = nullptr;
-            if (dot_scratch) {
-                if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
-                dp = dot_scratch->p;
-                *partials = g;
-            }
+            rc = dot_partials(c, dot_scratch, vector_tiles_operator_partials(N), partials, &dp);
+            if (rc) return rc;
             HIP_TRY(c, vector_tiles_shift_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, alpha, beta,
                                                     beta != 0.0 ? y : nullptr, y, dp));
             return FH_OK;
@@ -932,17 +863,54 @@ int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x, double
         if (rc) return rc;
     }
     const int g = (n + 255) / 256;
-    double* dp = nullptr;
-    if (dot_scratch) {
-        if (dot_scratch->n < (size_t)g) HIP_TRY(c, dot_scratch->alloc((size_t)g));
-        dp = dot_scratch->p;
-        *partials = g;
-    }
+    rc = dot_partials(c, dot_scratch, g, partials, &dp);
+    if (rc) return rc;
     if (n) {
         hipLaunchKernelGGL(k_mf_shift_combine, dim3(g), dim3(256), 0, c->stream, n, S, alpha, alpha != 0.0 ? c->mf_mass.p : nullptr, beta,
                            beta != 0.0 ? y : nullptr, x, dmask, c->mf_scale.p, y, dp);
         HIP_TRY(c, hipGetLastError());
     }
+    return FH_OK;
+}
+
+// the entry points of the map and of its diagonal; alpha = 0, beta = 1 is the plain map of `scope`, every other pair the shifted tangent (scope
+// MF_TANGENT, which is also the context's scope outside an entry point: the guard changes nothing for it).  The scale of the Dirichlet rows is
+// formed again only when what it depends on has changed.
+static int mf_apply_entry(fh_ctx* c, const char* who, int scope, double alpha, double beta, const double* x_dev, double* y_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, scope) : mf_shift_ready(c, who, alpha, beta);
+    if (rc) return rc;
+    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    if (c->N == 0) return FH_OK;
+    MfScope scope_guard_(c, scope);
+    unsigned long long key[8];
+    mf_scale_key_now(c, key, alpha, beta);
+    if (c->mf_num_dirichlet && !std::equal(key, key + 8, c->mf_scale_key)) {
+        DevBuf<double> diag;
+        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
+        rc = mf_shift_diagonal(c, alpha, beta, diag.p, true);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    rc = reset_status(c);
+    if (rc) return rc;
+    rc = mf_shift_apply(c, alpha, beta, x_dev, y_dev, nullptr, nullptr);
+    if (rc) return rc;
+    return read_status(c, nullptr);
+}
+
+static int mf_diagonal_entry(fh_ctx* c, const char* who, int scope, double alpha, double beta, double* diag_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    int rc = (alpha == 0.0 && beta == 1.0) ? mf_ready(c, who, scope) : mf_shift_ready(c, who, alpha, beta);
+    if (rc) return rc;
+    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    if (c->N == 0) return FH_OK;
+    MfScope scope_guard_(c, scope);
+    rc = mf_shift_diagonal(c, alpha, beta, diag_dev, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FH_OK;
 }
 
@@ -957,75 +925,67 @@ static void residual_elements_launch(fh_ctx* c, const KArgs& a, const unsigned c
         });
     });
 }
-int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed) {
+static int residual_ordered_single(fh_ctx* c, double* out, uint64_t* failed) {
     int rc = reset_status(c);
     if (rc) return rc;
     if (c->E == 0 || (c->has_mask && c->num_active == 0)) return FH_OK;
-    rc = build_source_adjacency(c);
-    if (rc) return rc;
-    const size_t need = (size_t)c->E * c->ei.n * c->S();
-    if (c->fe_scratch.n < need) HIP_TRY(c, c->fe_scratch.alloc(need));
-    KArgs a;
-    fill_common(c, a);
-    const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-    residual_elements_launch(c, a, active, c->fe_scratch.p);
-    HIP_TRY(c, hipGetLastError());
-    rc = launch_vector_from_elements_soa(c, c->S(), c->fe_scratch.p, out, c->src_n2e_off.p, c->src_n2e.p);
-    if (rc) return rc;
-    return read_status(c, failed);
+    // (no tile launcher: newton_residual and the integrators own the tiles' branch, their node passes do more than sum)
+    rc = ordered_single(c, out, nullptr, [&](const KArgs& a, const unsigned char* active, double* fe) {
+        residual_elements_launch(c, a, active, fe);
+        return (int)FH_OK;
+    });
+    return rc ? rc : read_status(c, failed);
+}
+// r(u) over every group of the table into out (S N doubles), and with obstacles set r + g (one launch of k_contact_force behind the node sums):
+// what the Newton residual and the time integrators take off the tiles.  Each group's status is reset and read (a singular Jacobian is the
+// error); no element is reported.
+int residual_summed(fh_ctx* c, double* out) {
+    const int rc = walk_groups_into(c, out, (size_t)c->S() * c->N, nullptr, [&](uint64_t* fl) { return residual_ordered_single(c, out, fl); });
+    return rc ? rc : contact_add_force(c, out);
 }
 
 // ---- the Newton residual  F = alpha M (u - u_ref) + beta (r(u) - f)  at the context's u with the rows of the operator's Dirichlet nodes zero,
 // and |F|^2 (fh_newton_solve_dev, engine_newton.hip).  On the tiles (Hex8, Tet4, Quad4, Tri3 without a rule-set table) the residual's element
 // pass and, for alpha != 0, k_mass_tiled on d (all of it: the mass term of F sees the Dirichlet entries of d) leave their partials, and ONE
 // node pass (k_newton_from_partials) forms F and the |F|^2 partials.  Elsewhere the residual (k_residual_elements and the ordered node sums,
-// residual_ordered_single) and M d (mass_full) land in scratch and k_newton_combine does the rest.  The partials are summed in a fixed order: bitwise reproducible.  Errors: those of the
-// residual (FH_SINGULAR_JACOBIAN).  A point with det F <= 0 of NeoHookean makes F NaN, not an error.
+// residual_summed) and M d (mass_full) land in scratch and k_newton_combine does the rest.  The partials are summed in a fixed order: bitwise
+// reproducible.  Errors: those of the residual (FH_SINGULAR_JACOBIAN).  A point with det F <= 0 of NeoHookean makes F NaN, not an error.
 int newton_residual(fh_ctx* c, double alpha, double beta, const double* f, const double* d, NewtonScratch& ns, double* norm2) {
     const int S = c->S(), N = (int)c->N, n = S * N;
     const unsigned char* dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
     int count = 0;   // per-workgroup partials of |F|^2 in ns.wg
     int rc;
     if (ns.F.n < (size_t)n) HIP_TRY(c, ns.F.alloc((size_t)n));
-    if (c->E > 0 && !c->rs.active && tiles_enabled(c) && (alpha == 0.0 || c->ei.ng == c->ei.n)) {
-        rc = ensure_vector_tiles(c);
+    bool serve = false;
+    if (c->E > 0 && !c->rs.active && (alpha == 0.0 || c->ei.ng == c->ei.n)) {
+        rc = tile_partials(c, ns.rpart, S, &serve);
+        if (!rc && serve && alpha != 0.0) rc = tile_partials(c, ns.mpart, S, &serve);
         if (rc) return rc;
-        if (!c->vt_bad) {
-            const size_t need = (size_t)c->vt.v.npartials * S;
-            if (ns.rpart.n < need) HIP_TRY(c, ns.rpart.alloc(need));
-            if (alpha != 0.0 && ns.mpart.n < need) HIP_TRY(c, ns.mpart.alloc(need));
-            rc = reset_status(c);
+    }
+    if (serve) {
+        rc = reset_status(c);
+        if (rc) return rc;
+        const KArgs a = pass_args(c);
+        const unsigned char* active = active_mask(c);
+        bool ok = vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, ns.rpart.p) == FH_OK;
+        if (ok && alpha != 0.0)
+            ok = vector_tiles_mass_pass(c->elem_kind, S, c->stream, a, c->vt.v, active, c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, d, nullptr,
+                                        ns.mpart.p) == 0;
+        HIP_TRY(c, hipGetLastError());
+        if (ok) {
+            count = vector_tiles_operator_partials(N);
+            if (ns.wg.n < (size_t)count) HIP_TRY(c, ns.wg.alloc((size_t)count));
+            HIP_TRY(c, vector_tiles_newton_node_pass(c->stream, S, N, c->vt.v, ns.rpart.p, alpha != 0.0 ? ns.mpart.p : nullptr, f, dmask, alpha,
+                                                     beta, ns.F.p, ns.wg.p, contact_table(c)));
+            c->last_kernel = alpha != 0.0 ? "k_element_pass_tiled + k_mass_tiled + k_newton_from_partials"
+                                          : "k_element_pass_tiled + k_newton_from_partials";
+            rc = read_status(c, nullptr);
             if (rc) return rc;
-            KArgs a;
-            fill_common(c, a);
-            a.work_begin = 0;
-            a.work_end = (long long)(c->has_mask ? c->num_active : c->E);
-            a.labels = nullptr;
-            const unsigned char* active = c->has_mask ? c->active.p : nullptr;
-            bool ok = vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, ns.rpart.p) == FH_OK;
-            if (ok && alpha != 0.0)
-                ok = vector_tiles_mass_pass(c->elem_kind, S, c->stream, a, c->vt.v, active, c->mass_rho.p, c->mass_rho_n > 1 ? 1 : 0, d, nullptr,
-                                            ns.mpart.p) == 0;
-            HIP_TRY(c, hipGetLastError());
-            if (ok) {
-                count = vector_tiles_operator_partials(N);
-                if (ns.wg.n < (size_t)count) HIP_TRY(c, ns.wg.alloc((size_t)count));
-                HIP_TRY(c, vector_tiles_newton_node_pass(c->stream, S, N, c->vt.v, ns.rpart.p, alpha != 0.0 ? ns.mpart.p : nullptr, f, dmask, alpha,
-                                                         beta, ns.F.p, ns.wg.p, contact_table(c)));
-                c->last_kernel = alpha != 0.0 ? "k_element_pass_tiled + k_mass_tiled + k_newton_from_partials"
-                                              : "k_element_pass_tiled + k_newton_from_partials";
-                rc = read_status(c, nullptr);
-                if (rc) return rc;
-            }
         }
     }
     if (!count) {   // every other route: the residual and M d composed into scratch
         if (ns.r.n < (size_t)n) HIP_TRY(c, ns.r.alloc((size_t)n));
-        HIP_TRY(c, hipMemsetAsync(ns.r.p, 0, sizeof(double) * (size_t)n, c->stream));
-        rc = c->rs.active ? rs_walk_accumulating(c, nullptr, [&](uint64_t* fl) { return residual_ordered_single(c, ns.r.p, fl); })
-                          : residual_ordered_single(c, ns.r.p, nullptr);
-        if (rc) return rc;
-        rc = contact_add_force(c, ns.r.p);   // r + g (k_contact_force), one launch
+        rc = residual_summed(c, ns.r.p);
         if (rc) return rc;
         if (alpha != 0.0) {
             if (ns.m.n < (size_t)n) HIP_TRY(c, ns.m.alloc((size_t)n));
@@ -1072,13 +1032,13 @@ int fh_set_operator_dirichlet_nodes(fh_ctx* c, const uint64_t* nodes, uint64_t n
 }
 
 int fh_apply_operator_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
-    return mf_apply_entry(c, "fh_apply_operator_dev", MF_OPERATOR, x_dev, y_dev);
+    return mf_apply_entry(c, "fh_apply_operator_dev", MF_OPERATOR, 0.0, 1.0, x_dev, y_dev);
 }
-int fh_operator_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_operator_diagonal_dev", MF_OPERATOR, diag_dev); }
+int fh_operator_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_operator_diagonal_dev", MF_OPERATOR, 0.0, 1.0, diag_dev); }
 int fh_apply_tangent_dev(fh_ctx* c, const double* x_dev, double* y_dev) {
-    return mf_apply_entry(c, "fh_apply_tangent_dev", MF_TANGENT, x_dev, y_dev);
+    return mf_apply_entry(c, "fh_apply_tangent_dev", MF_TANGENT, 0.0, 1.0, x_dev, y_dev);
 }
-int fh_tangent_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_tangent_diagonal_dev", MF_TANGENT, diag_dev); }
+int fh_tangent_diagonal_dev(fh_ctx* c, double* diag_dev) { return mf_diagonal_entry(c, "fh_tangent_diagonal_dev", MF_TANGENT, 0.0, 1.0, diag_dev); }
 
 int fh_set_mass_density(fh_ctx* c, const double* rho, uint64_t count) {
     if (!c) return FH_BAD_ARGUMENT;
@@ -1096,43 +1056,10 @@ int fh_set_mass_density(fh_ctx* c, const double* rho, uint64_t count) {
 }
 
 int fh_apply_shifted_tangent_dev(fh_ctx* c, double alpha, double beta, const double* x_dev, double* y_dev) {
-    if (!c) return FH_BAD_ARGUMENT;
-    const char* who = "fh_apply_shifted_tangent_dev";
-    if (alpha == 0.0 && beta == 1.0) return mf_apply_entry(c, who, MF_TANGENT, x_dev, y_dev);
-    DevGuard dev_guard_(c->device);
-    int rc = mf_shift_ready(c, who, alpha, beta);
-    if (rc) return rc;
-    if (!x_dev || !y_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
-    if (c->N == 0) return FH_OK;
-    unsigned long long key[8];
-    mf_scale_key_now(c, key, alpha, beta);
-    if (c->mf_num_dirichlet && !std::equal(key, key + 8, c->mf_scale_key)) {
-        DevBuf<double> diag;
-        HIP_TRY(c, diag.alloc((size_t)c->S() * c->N));
-        rc = mf_shift_diagonal(c, alpha, beta, diag.p, true);
-        if (rc) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    rc = reset_status(c);
-    if (rc) return rc;
-    rc = mf_shift_apply(c, alpha, beta, x_dev, y_dev, nullptr, nullptr);
-    if (rc) return rc;
-    return read_status(c, nullptr);
+    return mf_apply_entry(c, "fh_apply_shifted_tangent_dev", MF_TANGENT, alpha, beta, x_dev, y_dev);
 }
-
 int fh_shifted_tangent_diagonal_dev(fh_ctx* c, double alpha, double beta, double* diag_dev) {
-    if (!c) return FH_BAD_ARGUMENT;
-    const char* who = "fh_shifted_tangent_diagonal_dev";
-    if (alpha == 0.0 && beta == 1.0) return mf_diagonal_entry(c, who, MF_TANGENT, diag_dev);
-    DevGuard dev_guard_(c->device);
-    int rc = mf_shift_ready(c, who, alpha, beta);
-    if (rc) return rc;
-    if (!diag_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
-    if (c->N == 0) return FH_OK;
-    rc = mf_shift_diagonal(c, alpha, beta, diag_dev, true);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FH_OK;
+    return mf_diagonal_entry(c, "fh_shifted_tangent_diagonal_dev", MF_TANGENT, alpha, beta, diag_dev);
 }
 
 }  // extern "C"

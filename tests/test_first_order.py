@@ -395,7 +395,8 @@ def test_other_routes_parity(engine, oracle, name):
     u, rate, _, _ = ti.state()
     _assert_parity((u, rate, _records(rec)), ref, tol, name)
     if case[0] == "rkl":   # (the element mask keeps the tiles; Hex27 and the rule-set table sum the residual first)
-        assert engine.last_kernel_name().endswith("k_first_order_from_partials" if name == "masked_rkl2" else "k_first_order_update")
+        assert engine.last_kernel_name() == ("k_element_pass_tiled + k_first_order_from_partials" if name == "masked_rkl2"
+                                             else "k_residual_elements + k_vector_from_elements_soa + k_first_order_update")
 
 
 @pytest.mark.gpu

@@ -327,6 +327,8 @@ def _vector_routes(engine, asm, kind, ref, case, tag):
                   (None, "k_element_pass_tiled + k_vector_from_partials", "k_element_energy_tiled")]
         if kind in ("HEX8", "TET4"):
             routes.append(("FENRIS_HIP_NO_VECTOR_TILES", "k_element_pass + k_vector_from_elements_soa", "k_element_pass<scalar>"))
+        # the one-pass scatter; the energy is a sum of partials whatever this switch says and stays on the tiles
+        routes.append(("FENRIS_HIP_VECTOR_ATOMICS", "k_assemble_vector" if kind == "TRI3" else "k_assemble_vector_stream", "k_element_energy_tiled"))
     else:
         routes = [(None, "k_assemble_vector", "k_assemble_scalar")]
     for option, vname, ename in routes:

@@ -324,8 +324,18 @@ def test_fused_residual_and_norm(engine, kind, table):
     route = engine.last_kernel_name()
     assert ("k_newton_from_partials" in route) == (table == "uniform"), route
     assert ("k_mass_tiled" in route) == (table == "uniform"), route
+    assert route == ("k_element_pass_tiled + k_mass_tiled + k_newton_from_partials" if table == "uniform"
+                     else "k_residual_elements + k_vector_from_elements_soa + k_newton_combine"), route
     ref = _composed_norm(engine, asm, m, clamp, rho, alpha, beta, u0, u_ref, f)
     assert abs(res.initial_residual_norm - ref) <= 1e-13 * ref
+    # the static residual (alpha = 0: no mass partials) takes the same two routes; its norm against the same composition
+    static = fa.MatrixFreeNewton(asm).with_dirichlet_nodes(clamp).with_load(f)
+    res0 = static.solve(u0.copy(), fa.NewtonSettings(None, 1e300))
+    route0 = engine.last_kernel_name()
+    assert route0 == ("k_element_pass_tiled + k_newton_from_partials" if table == "uniform"
+                      else "k_residual_elements + k_vector_from_elements_soa + k_newton_combine"), route0
+    ref0 = _composed_norm(engine, asm, m, clamp, rho, 0.0, 1.0, u0, u_ref, f)
+    assert abs(res0.initial_residual_norm - ref0) <= 1e-13 * ref0
     # F itself: one Newton step from u0 through the fused pass against the same step with the tiles switched off (the composed route)
     u1 = u0.copy()
     with pytest.raises(fa.MaximumIterationsReached):

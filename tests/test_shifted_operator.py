@@ -293,11 +293,45 @@ def test_shifted_hex8_fused_pass(engine, perturb, op, coef):
         y = _check(ref, t, rng)
         t.apply(y, torch.ones_like(y))   # (_check ends with the reference's SpMV: apply once more for the kernel's name)
         want = "k_mass_hex8_tiled" if beta == 0.0 else "k_shifted_pass_tiled" if op in ("laplace", "elastic") else "k_shifted_tangent_tiled"
-        assert engine.last_kernel_name().startswith(want), engine.last_kernel_name()
+        assert engine.last_kernel_name() == want + " + k_operator_from_partials", engine.last_kernel_name()
         d_ref = fa.CsrMatrix(ref.a.row_offsets, ref.a.col_indices, ref.a.values.cpu().numpy()).to_scipy().diagonal()
         assert np.abs(t.diagonal() - d_ref).max() <= 1e-12 * np.abs(d_ref).max()
     finally:
         ref.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["TET4", "HEX8"])
+@pytest.mark.parametrize("op", ["elastic", "neo_hookean"])
+def test_tiled_mass_and_shift_node_pass(engine, kind, op):
+    """the tiles without the fused Hex8 pass (Tet4; Hex8 with the monomial form switched off): the tangent's own kernels, then k_mass_tiled
+    and the shift node pass, which names no kernel -- the name stays the tangent's, and with beta = 0 the name of the call before.  More
+    than one tile and one node-pass block, the last of each partial; per-element density, Dirichlet nodes and an element mask"""
+    import torch
+
+    m, w, p = _mesh(kind, res=7 if kind == "HEX8" else 5, perturb=0.01, seed=21)
+    assert m.num_elements() > 256 and m.num_nodes() > 256
+    rng = np.random.default_rng(22)
+    if kind == "HEX8":
+        engine.set_option("FENRIS_HIP_NO_MONOMIAL", "1")
+    qt, rules, emap = _tables(op, "uniform", w, p, m)
+    E = m.num_elements()
+    rho = rng.uniform(800.0, 1200.0, E)
+    mask = rng.random(E) < 0.8
+    bc = np.where(m.vertices[:, 0] < 1e-9)[0]
+    tangent = "k_element_pass_tiled + k_operator_from_partials" if op == "elastic" else "k_tangent_tiled + k_operator_from_partials"
+    for alpha, beta in ((1.0, 1e-4), (2.0, 0.0)):
+        ref = _Ref(engine, m, op, qt, rules, emap, rho, _smooth_u(m, op, seed=3), alpha, beta, mask=mask, bc=bc)
+        try:
+            t = fa.MatrixFreeShiftedTangent(ref.asm, rho, alpha, beta).with_dirichlet_nodes(bc)
+            y = _check(ref, t, rng)
+            before = engine.last_kernel_name()   # (_check ends with the reference's SpMV)
+            t.apply(y, torch.ones_like(y))
+            assert engine.last_kernel_name() == (tangent if beta != 0.0 else before), engine.last_kernel_name()
+            d_ref = fa.CsrMatrix(ref.a.row_offsets, ref.a.col_indices, ref.a.values.cpu().numpy()).to_scipy().diagonal()
+            assert np.abs(t.diagonal() - d_ref).max() <= 1e-12 * np.abs(d_ref).max()
+        finally:
+            ref.close()
 
 
 @pytest.mark.gpu

@@ -194,3 +194,62 @@ def test_source_vector_argument_errors(engine):
         engine.assemble_source_vector(out, 3, g=[0.0, 0.0, 1.0])  # uniform source without a density table
     with pytest.raises(fa.FenrisError):
         engine.assemble_source_vector(np.zeros(2 * m.num_nodes()), 2, values=np.zeros((m.num_elements(), len(w), 2)))
+
+
+# the four routes of fh_assemble_source_vector_dev, each by the switch or the state that selects it, on meshes of more than one tile and more
+# than one node-pass block (Hex8 7 x 6 x 7: 294 elements, 448 nodes; the tetrahedra of a 6^3 box), the last of each partial
+SOURCE_ROUTES = {
+    "tiles": ((), False, False, "k_source_elements_tiled + k_vector_from_partials"),
+    "tiles_masked": ((), True, False, "k_source_elements_tiled + k_vector_from_partials"),
+    "element_pass": (("FENRIS_HIP_NO_VECTOR_TILES",), False, False, "k_source_elements + k_vector_from_elements_soa"),
+    "element_pass_on_the_pattern": (("FENRIS_HIP_NO_VECTOR_TILES",), False, True, "k_source_elements + k_vector_from_elements_soa"),
+    "staged_two_pass": (("FENRIS_HIP_NO_ELEMENT_PASS",), False, True, "k_assemble_source"),
+    "scatter": (("FENRIS_HIP_VECTOR_ATOMICS",), False, False, "k_assemble_source"),
+    "scatter_masked": (("FENRIS_HIP_NO_VECTOR_TILES",), True, False, "k_assemble_source"),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", list(SOURCE_ROUTES))
+@pytest.mark.parametrize("kind", ["HEX8", "TET4"])
+def test_source_vector_routes_name_their_kernels(oracle, kind, route):
+    """(switches, element mask, an operator on the context -- its pattern brings the node adjacency --, kernel): the gravity form and the
+    sampled form of every route against the oracle, and the name of the route taken"""
+    switches, masked, with_operator, want = SOURCE_ROUTES[route]
+    rng = np.random.default_rng(11)
+    if kind == "HEX8":
+        m = fa.procedural.create_rectangular_uniform_hex_mesh(1.0, 7, 6, 7, 1)
+    else:
+        m = fa.procedural.create_unit_box_uniform_tet_mesh_3d(6)
+    m = fa.Mesh(m.vertices + 0.01 * rng.uniform(-1, 1, m.vertices.shape), m.connectivity, m.elem_kind)
+    w, p = (np.asarray(a) for a in _rule(kind))
+    E, N = m.num_elements(), m.num_nodes()
+    params = np.stack([np.linspace(1.0, 2.0, len(w)), np.zeros(len(w))], axis=1)
+    mask = (rng.random(E) < 0.7) if masked else np.ones(E, dtype=bool)
+    conn = np.asarray(m.connectivity)
+    eng = fa.Engine(0)
+    try:
+        for name in switches:
+            eng.set_option(name, "1")
+        eng.set_mesh(m)
+        if with_operator:
+            eng.set_operator(fa._ffi.LAPLACE)
+        eng.set_quadrature_uniform(w, p, params)
+        if masked:
+            eng.set_active_elements(mask.astype(np.uint8))
+        oasm = oracle.ElementAssembler(KIND[kind], oracle.LAPLACE, m.vertices, conn[mask], w, p, params=params)
+        for s in ((1,) if with_operator else (1, 3)):
+            g = np.array([0.3, -9.81, 1.2])[:s]
+            out = np.full(s * N, 0.5)   # (accumulates)
+            eng.assemble_source_vector(out, s, g=g)
+            assert eng.last_kernel_name() == want, (eng.last_kernel_name(), s)
+            st, ref = oracle.assemble_source_vector(oasm, s, g=g, out=np.full(s * N, 0.5))
+            assert st == 0 and np.max(np.abs(out - ref)) <= 1e-12 * np.max(np.abs(ref)), (s, "gravity")
+            values = np.sin(0.1 * np.arange(E * len(w) * s)).reshape(E, len(w), s)
+            out = np.zeros(s * N)
+            eng.assemble_source_vector(out, s, values=values)
+            assert eng.last_kernel_name() == want, (eng.last_kernel_name(), s)
+            st, ref = oracle.assemble_source_vector(oasm, s, values=values[mask])
+            assert st == 0 and np.max(np.abs(out - ref)) <= 1e-12 * np.max(np.abs(ref)), (s, "sampled")
+    finally:
+        eng.close()

@@ -167,6 +167,9 @@ def test_tangent_hex8_tables(engine, perturb, table):
     for op in ("neo_hookean", "stvk"):
         asm = _assembler(engine, m, op, qt, _smooth_u(m, op, seed=2))
         t, _, ks = _check_against_spmv(engine, asm, np.random.default_rng(7))
+        # one table: the operator's node pass behind the tangent's tiles; a rule-set table: every group's partials summed into y = 0
+        assert engine.last_kernel_name() == ("k_tangent_tiled + k_vector_from_partials" if table == "rule_set"
+                                             else "k_tangent_tiled + k_operator_from_partials"), engine.last_kernel_name()
         d_ref = ks.diagonal()
         assert np.abs(t.diagonal() - d_ref).max() <= 1e-12 * np.abs(d_ref).max()
 
