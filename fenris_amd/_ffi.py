@@ -118,6 +118,7 @@ _SIGS = {
     "fh_quadrature_rule_groups": (C.c_int, [C.c_void_p, u64p]),
     "fh_set_affine_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
     "fh_affine_stats": (C.c_int, [C.c_void_p, u64p, u64p, u64p]),
+    "fh_vector_tiles_stats": (C.c_int, [C.c_void_p, u64p, u64p, u64p, u64p]),
     "fh_affine_shared_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), u64p, u64p, C.POINTER(C.c_char_p)]),
     "fh_affine_slot_elements": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), u64p, C.c_void_p]),
     "fh_set_quadrature_uniform": (C.c_int, [C.c_void_p, f64p, f64p, C.c_uint32, f64p]),

@@ -190,6 +190,12 @@ class Engine:
         self._check(self._lib.fh_affine_stats(self._h, C.byref(a), C.byref(b), C.byref(g)))
         return int(a.value), int(b.value), int(g.value)
 
+    def vector_tiles_stats(self):
+        """fh_vector_tiles_stats: (tiles, partials, largest number of distinct nodes of a tile, longest partial list of a node)"""
+        t, p, mt, mp = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.fh_vector_tiles_stats(self._h, C.byref(t), C.byref(p), C.byref(mt), C.byref(mp)))
+        return int(t.value), int(p.value), int(mt.value), int(mp.value)
+
     def affine_shared_stats(self):
         """fh_affine_shared_stats: {"shared", "records", "lists", "reason"} of the last affine sweep"""
         on, nrec, nvec, why = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_char_p()

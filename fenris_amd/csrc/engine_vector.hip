@@ -195,6 +195,22 @@ extern "C++" int ensure_vector_tiles(fh_ctx* c) {
     c->vt_gen = c->topo_gen;
     return FH_OK;
 }
+int fh_vector_tiles_stats(fh_ctx* c, uint64_t* tiles, uint64_t* partials, uint64_t* max_tile_nodes, uint64_t* max_node_partials) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    if (!c->has_mesh) return c->fail(FH_INVALID_STATE, "fh_vector_tiles_stats: no finite element mesh set");
+    if (!element_pass_covers(c) || c->opt.NO_VECTOR_TILES) return c->fail(FH_UNSUPPORTED, "fh_vector_tiles_stats: this mesh has no element tiles");
+    const int rc = ensure_vector_tiles(c);
+    if (rc) return rc;
+    if (c->vt_bad) return c->fail(FH_UNSUPPORTED, "fh_vector_tiles_stats: the element tiles could not be built for this mesh");
+    unsigned mt = 0, mp = 0;
+    HIP_TRY(c, vector_tiles_stats(c->stream, c->vt.v, (int)c->N, &mt, &mp));
+    if (tiles) *tiles = (uint64_t)c->vt.v.ntiles;
+    if (partials) *partials = c->vt.v.npartials;
+    if (max_tile_nodes) *max_tile_nodes = mt;
+    if (max_node_partials) *max_node_partials = mp;
+    return FH_OK;
+}
 static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed) {
     int rc = check_ready(c, "fh_assemble_vector", false);
     if (rc) return rc;
@@ -622,8 +638,10 @@ static int mf_single(fh_ctx* c, const double* xin, double* out, uint64_t* failed
         c, out,
         [&](KArgs& a, bool* done) {
             const int r = mf_tiles_pass(c, a, xin, done);
-            if (!r && *done && xin)
-                c->last_kernel = c->op <= FH_LINEAR_ELASTIC ? "k_element_pass_tiled + k_vector_from_partials" : "k_tangent_tiled + k_vector_from_partials";
+            if (!r && *done)
+                c->last_kernel = !xin                        ? "k_diagonal_tiled + k_vector_from_partials"
+                                 : c->op <= FH_LINEAR_ELASTIC ? "k_element_pass_tiled + k_vector_from_partials"
+                                                              : "k_tangent_tiled + k_vector_from_partials";
             return r;
         },
         [&](const KArgs& a, const unsigned char* active, double* fe) {
@@ -701,7 +719,12 @@ static int mass_tiles_pass(fh_ctx* c, const KArgs& a, const double* x, const uns
 static int mass_single(fh_ctx* c, const double* x, const unsigned char* dmask, double* out) {
     if (c->E == 0 || (c->has_mask && c->num_active == 0)) return FH_OK;
     return ordered_single(
-        c, out, [&](KArgs& a, bool* done) { return mass_tiles_pass(c, a, x, dmask, done); },
+        c, out,
+        [&](KArgs& a, bool* done) {
+            const int r = mass_tiles_pass(c, a, x, dmask, done);
+            if (!r && *done && !x) c->last_kernel = "k_mass_tiled + k_vector_from_partials";   // (the diagonal of M)
+            return r;
+        },
         [&](const KArgs& a, const unsigned char* active, double* fe) {
             const int covered = dispatch(all_kinds, c->elem_kind, -1, [&](auto ek) {
                 using EL = ElemT<ek()>;
@@ -854,6 +877,8 @@ int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x, double
             if (rc) return rc;
             HIP_TRY(c, vector_tiles_shift_node_pass(c->stream, S, N, c->vt.v, c->fe_scratch.p, x, dmask, c->mf_scale.p, alpha, beta,
                                                     beta != 0.0 ? y : nullptr, y, dp));
+            // (beta != 0: the name stays the one the tangent's pass above left, which the callers of the two-pass map know it by)
+            if (beta == 0.0) c->last_kernel = "k_mass_tiled + k_shift_from_partials";
             return FH_OK;
         }
     }

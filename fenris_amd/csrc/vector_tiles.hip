@@ -743,6 +743,12 @@ __global__ void __launch_bounds__(256) k_first_order_from_partials(int num_nodes
     if (p.flags & FO_STORE) block_partial_store(q, p.partial);
 }
 
+// the longest run of an offset table, max over i < n of off[i + 1] - off[i] (vector_tiles_stats: formed on request, nothing of it is kept)
+__global__ void __launch_bounds__(256) k_vt_longest_run(const unsigned* off, unsigned n, unsigned* out) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) atomicMax(out, off[i + 1] - off[i]);
+}
+
 template <typename T>
 hipError_t vt_alloc(VecTilesStore* st, int slot, T** p, size_t count) {
     hipError_t e = hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (count ? count : 1));
@@ -871,6 +877,25 @@ hipError_t vector_tiles_build(hipStream_t stream, const int* conn, int n, long l
     cleanup();
     out->v = VecTiles{elem, tconn, noff, la_off, la, np_off, np_idx, p_node, T, n, P, ts};
     return hipSuccess;
+}
+
+hipError_t vector_tiles_stats(hipStream_t stream, const VecTiles& t, int num_nodes, unsigned* max_tile_nodes, unsigned* max_node_partials) {
+    unsigned* d = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(unsigned) * 2);
+    if (e != hipSuccess) return e;
+    unsigned h[2] = {0u, 0u};
+    e = hipMemsetAsync(d, 0, sizeof(unsigned) * 2, stream);
+    if (e == hipSuccess) {
+        if (t.ntiles > 0) hipLaunchKernelGGL(k_vt_longest_run, dim3((t.ntiles + 255) / 256), dim3(256), 0, stream, t.noff, (unsigned)t.ntiles, d);
+        if (num_nodes > 0) hipLaunchKernelGGL(k_vt_longest_run, dim3((num_nodes + 255) / 256), dim3(256), 0, stream, t.np_off, (unsigned)num_nodes, d + 1);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof(unsigned) * 2, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    (void)hipFree(d);
+    *max_tile_nodes = h[0];
+    *max_node_partials = h[1];
+    return e;
 }
 
 // ---- the launchers.  An element pass returns -1 where the combination has no kernel (the callers keep their other kernels).

@@ -36,6 +36,10 @@ struct VecTilesStore {
 hipError_t vector_tiles_build(hipStream_t stream, const int* conn, int n, long long E, const double* verts, int D, int num_nodes, VecTilesStore* out,
                               int* bad);
 
+// what the tables look like (fh_vector_tiles_stats): the largest number of distinct nodes of a tile and the longest list of partials of a
+// node, reduced from noff and np_off on the device when asked for (the stream is waited for)
+hipError_t vector_tiles_stats(hipStream_t stream, const VecTiles& t, int num_nodes, unsigned* max_tile_nodes, unsigned* max_node_partials);
+
 // element pass: every tile's elements in registers, their vectors summed per distinct node of the tile into partial[P][S].
 // active (device, may be null): elements with active[e] == 0 contribute nothing.  Returns -1 when (elem_kind, op) is not covered.
 int vector_tiles_element_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial);

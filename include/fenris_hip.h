@@ -226,6 +226,13 @@ int fh_set_affine_tolerance(fh_ctx*, double rel_tol);
 /* how the last FH_SCATTER_GATHER assembly was split: elements found affine, node blocks on the affine kernel, node blocks on
  * the general kernels (any pointer may be NULL; zeros before the first assembly) */
 int fh_affine_stats(const fh_ctx*, uint64_t* affine_elements, uint64_t* affine_blocks, uint64_t* general_blocks);
+/* The element tiles of the mesh in use (Hex8, Tet4, Quad4, Tri3: what the residual, energy, source and matrix-free passes walk): the number of
+ * tiles of 256 elements, the number of partial node sums (the distinct nodes of a tile, summed over the tiles), the largest number of
+ * distinct nodes of one tile, and the longest list of partials of one node (0 for a node without elements).  Any pointer may be NULL.
+ * Read-only for the passes: the tables are built here if the topology has none yet, and the two maxima are reduced from them on the device
+ * at every call (nothing is kept for it; the call waits for the stream).  FH_UNSUPPORTED where the mesh has no tiles: another element kind,
+ * a ragged connectivity, FENRIS_HIP_NO_VECTOR_TILES, or tables that could not be built. */
+int fh_vector_tiles_stats(fh_ctx*, uint64_t* tiles, uint64_t* partials, uint64_t* max_tile_nodes, uint64_t* max_node_partials);
 /* The affine kernel of the last FH_SCATTER_GATHER assembly: whether its loader took the element records from the table of DISTINCT records
  * (elements whose records agree bit for bit share one entry; structured, graded and extruded meshes have a few hundred) and the slots of a
  * node block from the table of distinct slot lists, how many entries the two tables have (0 when it did not), and -- when it did not -- why (a string owned by

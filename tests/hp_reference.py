@@ -20,7 +20,7 @@ HEX27_NODES = np.array([tuple(s) for s in HEX_SIGNS] + [
 TET10_EDGES = [(0, 1), (1, 2), (0, 2), (0, 3), (2, 3), (1, 3)]   # nodes 4 .. 9: the midpoints of these vertex pairs
 KINDS = {"QUAD4": (4, 2), "TRI3": (3, 2), "HEX8": (8, 3), "TET4": (4, 3), "HEX27": (27, 3), "TET10": (10, 3)}
 GEOMETRY = {"HEX27": "HEX8", "TET10": "TET4"}
-MODELS = ("LINEAR_ELASTIC", "NEO_HOOKEAN", "STVK")
+MODELS = ("LINEAR_ELASTIC", "NEO_HOOKEAN", "STVK", "LAPLACE")   # LAPLACE: one component, P = grad u, psi = |grad u|^2 / 2, K_ab = g_a . g_b
 
 
 def _simplex(xi, dt):
@@ -99,6 +99,10 @@ def _stress(model, F, mu, lam, I):
     """P (E, d, d), psi (E,) and the magnitudes of their terms (the scales of their rounding) for the deformation gradients F (E, d, d)"""
     d = F.shape[-1]
     aF = np.abs(F)
+    if model == "LAPLACE":                                           # (F: the gradient (E, 1, d); no parameters)
+        half = F.dtype.type(1) / 2
+        e = half * np.einsum("eij,eij->e", F, F)
+        return F, e, aF, e
     if model == "NEO_HOOKEAN":
         J = det(F)
         lnJ = np.log(J)
@@ -130,6 +134,8 @@ def _stress(model, F, mu, lam, I):
 def _contraction(model, F, g, mu, lam, I):
     """the element blocks C(g_a, g_b)[i][j] of one point as an array (E, a, i, b, j)"""
     gg = np.einsum("eak,ebk->eab", g, g)
+    if model == "LAPLACE":
+        return gg[:, :, None, :, None]
     delta = gg[:, :, None, :, None] * I[None, None, :, None, :]
     if model == "LINEAR_ELASTIC":
         return (mu * delta + mu * np.einsum("ebi,eaj->eaibj", g, g) + lam * np.einsum("eai,ebj->eaibj", g, g))
@@ -154,7 +160,8 @@ class Reference:
     """K(u), r(u), the energy and the mass of a whole mesh in the working type dt.
 
     kind: one of KINDS; model: one of MODELS; vertices (N, d), connectivity (E, n), weights (nq,), points (nq, d), u (s N,): the doubles the
-    device reads; mu, lam: Lame parameters; rho: a density for the mass matrix.  Per element: ke (E, s n, s n), re (E, s n), psi (E,),
+    device reads; mu, lam: Lame parameters (LAPLACE: not read); rho: a density for the mass matrix, one value or one per element.
+    Per element: ke (E, s n, s n), re (E, s n), psi (E,),
     me (E, s n, s n); the absolute scales of the residual (re_scale: sum over the points of |w det J P g|, re_term_scale: the same with P
     replaced by the sum of the magnitudes of its terms) and of the energy (psi_term: the magnitudes of the terms of psi); det_F_min."""
 
@@ -164,9 +171,11 @@ class Reference:
         conn = np.asarray(connectivity).astype(np.int64)
         assert conn.shape[1] == n and X.shape[1] == d
         E = len(conn)
-        s = d
+        s = 1 if model == "LAPLACE" else d
         U = np.asarray(u).reshape(-1, s).astype(dt)                 # (u may come in dt itself: the steps of a difference quotient)
-        mu, lam, rho = dt(float(mu)), dt(float(lam)), dt(float(rho))
+        mu, lam = dt(float(mu)), dt(float(lam))
+        rho = np.broadcast_to(np.asarray(rho, dtype=np.float64).astype(dt).reshape(-1), (E,)) if np.size(rho) in (1, E) else None
+        assert rho is not None, "rho: one value or one per element"
         I = np.eye(d, dtype=dt)
         gkind = GEOMETRY.get(kind, kind)
         ng = KINDS[gkind][0]
@@ -187,8 +196,10 @@ class Reference:
             detJ = det(Jm)
             g = np.einsum("nk,ekj->enj", G, inv(Jm))                  # physical gradients J^-T ghat, (E, n, d)
             scale = dt(wq) * np.abs(detJ)
-            F = I + np.einsum("enc,enj->ecj", Ue, g)                  # F = I + (grad u)^T
-            det_F_min = min(det_F_min, float(det(F).min()))
+            F = np.einsum("enc,enj->ecj", Ue, g)                      # (grad u)^T
+            if model != "LAPLACE":
+                F = I + F                                             # F = I + (grad u)^T
+                det_F_min = min(det_F_min, float(det(F).min()))
             P, ps, P_abs, ps_abs = _stress(model, F, mu, lam, I)
             psi += scale * ps
             psi_term += scale * ps_abs
@@ -200,7 +211,7 @@ class Reference:
         self.kind, self.model, self.dt, self.s, self.n = kind, model, dt, s, n
         self.conn, self.num_nodes = conn, len(X)
         self.ke = ke.reshape(E, n * s, n * s)
-        self.me = np.einsum("eab,ij->eaibj", me, I).reshape(E, n * s, n * s)
+        self.me = np.einsum("eab,ij->eaibj", me, np.eye(s, dtype=dt)).reshape(E, n * s, n * s)
         self.re, self.re_scale, self.re_term_scale = re.reshape(E, -1), re_scale.reshape(E, -1), re_term.reshape(E, -1)
         self.psi, self.psi_term = psi, psi_term
         self.det_F_min = det_F_min
@@ -261,10 +272,17 @@ class Reference:
         x = np.asarray(x).astype(self.dt)
         ae = self.dt(float(alpha)) * self.me + self.dt(float(beta)) * self.ke if alpha else self.dt(float(beta)) * self.ke
         y = self._vector(np.einsum("eab,eb->ea", ae, x[self.dofs]))
+        return y, float(np.max(self.abs_apply(x, alpha, beta)))
+
+    def abs_apply(self, x, alpha=0.0, beta=1.0):
+        """(|alpha| |M| + |beta| |K|) |x| with the assembled matrices, row by row: the scale of the rounding of every row of apply"""
+        x = np.asarray(x).astype(self.dt)
         rows, cols = np.divmod(self.pattern_keys, self.ndof)
-        k = abs(self.dt(float(beta))) * np.abs(self._on_pattern(self.ke))
+        if not hasattr(self, "_abs_k"):                              # (the assembled |K| and |M| on the pattern: formed once)
+            self._abs_k, self._abs_m = np.abs(self._on_pattern(self.ke)), np.abs(self._on_pattern(self.me))
+        k = abs(self.dt(float(beta))) * self._abs_k
         if alpha:
-            k = k + abs(self.dt(float(alpha))) * np.abs(self._on_pattern(self.me))
+            k = k + abs(self.dt(float(alpha))) * self._abs_m
         b = np.zeros(self.ndof, dtype=self.dt)
         np.add.at(b, rows, k * np.abs(x[cols]))
-        return y, float(np.max(b))
+        return b

@@ -12,6 +12,7 @@ import pytest
 
 import fenris_amd as fa
 from fenris_amd import quadrature
+from tile_tables_model import soup
 
 pytestmark = pytest.mark.gpu
 LAME = fa.LameParameters(3.0e2, 5.0e2)
@@ -29,9 +30,7 @@ def _permuted(mesh, seed):
 
 def _soup(mesh):
     """every element gets its own copies of its vertices (+ two unused vertices in front)"""
-    conn = np.asarray(mesh.connectivity).astype(np.int64)
-    verts = np.concatenate([np.zeros((2, mesh.vertices.shape[1])), mesh.vertices[conn.reshape(-1)]])
-    return fa.Mesh(verts, (2 + np.arange(conn.size).reshape(conn.shape)).astype(np.uint64), mesh.elem_kind)
+    return soup(mesh, 2, 0)
 
 
 def _cases(oracle):
