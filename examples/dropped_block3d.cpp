@@ -4,8 +4,9 @@
 //   Central differences (fh_dynamics_step) at a quarter of the critical step of the block pressed into the floor
 //   (fh_dynamics_stable_dt sees the obstacle).  Every record prints the kinetic energy, the stored energy -- elastic plus contact, the
 //   column the obstacles add to -- their sum, and the lowest gap min_i phi(x_i) of fh_contact_gap_dev: the block falls, penetrates the
-//   floor by a little, and comes back up with its energy kept.
-// Build:  make -C examples    Run: ./examples/dropped_block3d [cells_per_unit = 4 [steps = 400]]
+//   floor by a little, and comes back up with its energy kept.  With the optional pair of Rayleigh coefficients (fh_dynamics_set_damping:
+//   C = eta_mass M + eta_stiffness T(u)) the block loses energy on the way and can come to rest; the critical step then is the damped one.
+// Build:  make -C examples    Run: ./examples/dropped_block3d [cells_per_unit = 4 [steps = 400 [eta_mass eta_stiffness]]]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +38,8 @@
 int main(int argc, char** argv) {
     const uint64_t cpu = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 4;
     const uint64_t steps = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 400;
+    const bool damped = argc > 4;
+    const double eta_mass = damped ? std::strtod(argv[3], nullptr) : 0.0, eta_stiffness = damped ? std::strtod(argv[4], nullptr) : 0.0;
     const double E = 1e3, nu = 0.3, rho = 1.0, v0 = 1.0, gap = 0.02, k_floor = 2e3;
     uint64_t nv = 0, nc = 0;
     fh_hex_mesh(1.0, 1, 1, 1, cpu, nullptr, nullptr, &nv, &nc);
@@ -73,6 +76,7 @@ int main(int argc, char** argv) {
     CHECK(ctx, fh_dynamics_create(ctx, &s, &probe));
     for (size_t i = 0; i < nv; ++i) u[3 * i + 2] = -2.0 * gap;   // the bottom face inside the floor: the stiffest state of the run
     CHECK(ctx, fh_dynamics_set_state(probe, u.data(), nullptr));
+    if (damped) CHECK(ctx, fh_dynamics_set_damping(probe, eta_mass, eta_stiffness));
     double omega = 0.0, dt_crit = 0.0;
     CHECK(ctx, fh_dynamics_stable_dt(probe, 40, &omega, &dt_crit));
     fh_dynamics_destroy(probe);
@@ -80,6 +84,7 @@ int main(int argc, char** argv) {
 
     fh_dynamics* dyn = nullptr;
     CHECK(ctx, fh_dynamics_create(ctx, &s, &dyn));
+    if (damped) CHECK(ctx, fh_dynamics_set_damping(dyn, eta_mass, eta_stiffness));
     std::fill(u.begin(), u.end(), 0.0);
     for (size_t i = 0; i < nv; ++i) v[3 * i + 2] = -v0;
     CHECK(ctx, fh_dynamics_set_state(dyn, u.data(), v.data()));
@@ -89,6 +94,7 @@ int main(int argc, char** argv) {
     const uint64_t every = std::max<uint64_t>(1, steps / 10);
     std::printf("dropped_block3d: %llu Hex8, dt = %.4e (omega_max = %.1f with the floor), floor z >= %.3f, k = %.1f per node\n",
                 (unsigned long long)nc, s.dt, omega, -gap, floor.stiffness);
+    if (damped) std::printf("dropped_block3d: Rayleigh damping eta_mass = %g, eta_stiffness = %g\n", eta_mass, eta_stiffness);
     std::printf("%10s %12s %12s %12s %12s\n", "time", "kinetic", "stored", "total", "lowest gap");
     double first_total = 0.0, last_total = 0.0, lowest = 1e300;
     for (uint64_t done = 0; done < steps; done += every) {

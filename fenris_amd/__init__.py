@@ -24,7 +24,7 @@ from .degree import (coarsen_degree, coarsen_degree_with_transfer, degree_hierar
 from .interpolate import FixedInterpolator, SpatiallyIndexed, ValuesOrGradients
 from .multigrid import GeometricMultigrid
 from .dynamics import (BackwardEuler, CentralDifference, DynamicsError, DynamicsRecord, FirstOrderIntegrator, FirstOrderRecord, ForwardEuler, Newmark,
-                       RungeKuttaLegendre, ThetaMethod, TimeIntegrator)
+                       RayleighDamping, RungeKuttaLegendre, ThetaMethod, TimeIntegrator)
 from .contact import Ball, Cavity, Contact, HalfSpace, Obstacles
 from .eigen import EigenResult, EigenSolveError, MatrixFreeEigensolver
 from .recovery import Recovery

@@ -193,6 +193,8 @@ _SIGS = {
     "fh_dynamics_state": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p, u64p]),
     "fh_dynamics_state_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f64p, u64p]),
     "fh_dynamics_stable_dt": (C.c_int, [C.c_void_p, C.c_uint32, f64p, f64p]),
+    "fh_dynamics_set_damping": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "fh_dynamics_damping": (C.c_int, [C.c_void_p, f64p, f64p]),
     "fh_set_obstacles": (C.c_int, [C.c_void_p, C.POINTER(Obstacle), C.c_uint64, f64p]),
     "fh_contact_energy": (C.c_int, [C.c_void_p, f64p]),
     "fh_contact_force_dev": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -83,6 +83,31 @@ static __global__ void __launch_bounds__(256) k_newmark_correct(int n, int S, in
     }
 }
 
+// ---- Rayleigh damping C = eta_m M + eta_k A (fh_dynamics_set_damping)
+// y += s x on the free dofs: the damping term joining a summed residual or a right-hand side, and a_0 -= eta_m v_0
+static __global__ void __launch_bounds__(256) k_dynamics_axpy(int n, int S, double s, const unsigned char* dmask, const double* x, double* y) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n && !(dmask && dmask[i / S])) y[i] = fma(s, x[i], y[i]);
+}
+// the folding of C, frozen at the start of an implicit step, into the Newton arguments.  With v_p = v_n + cv a_n (cv = dt (1 - gamma);
+// backward Euler is beta = gamma = 1 on its own predictor: cv = 0) the step's velocity is v_{n+1} = v_p + gamma / (beta dt) (u - u_ref), so
+//   u_ref* = u_ref - cref v_p,  cref = eta_m beta dt^2 / (1 + eta_m gamma dt)   (the mass part; Dirichlet dofs keep u_ref: v_p = 0 there)
+//   w      = b v_p - gdt u_ref,  b = beta dt^2, gdt = gamma dt                   (the stiffness part's operand: k_damping_load takes A w)
+static __global__ void __launch_bounds__(256) k_damping_fold(int n, int S, double cv, double cref, double b, double gdt, const unsigned char* dmask,
+                                                             const double* u_ref, const double* v, const double* a, double* u_ref2, double* w) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double vp = (dmask && dmask[i / S]) ? 0.0 : (cv != 0.0 ? fma(cv, a[i], v[i]) : v[i]);
+    const double ur = u_ref[i];
+    u_ref2[i] = fma(-cref, vp, ur);
+    w[i] = fma(b, vp, -gdt * ur);
+}
+// the folded load f' = (b lf f - eta_k A w) / beta', beta' = b + eta_k gamma dt (blf = b lf_{n+1}; f null: zero)
+static __global__ void __launch_bounds__(256) k_damping_load(int n, double blf, const double* f, double eta_k, const double* Aw, double beta2, double* g) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) g[i] = fma(-eta_k, Aw[i], f ? blf * f[i] : 0.0) / beta2;
+}
+
 // per-workgroup partials of x . y: the consistent kinetic energy from y = M v, the load potential f . u
 static __global__ void __launch_bounds__(256) k_kinetic_partials(int n, const double* x, const double* y, double* partial) {
     __shared__ double red[4];

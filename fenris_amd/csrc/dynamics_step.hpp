@@ -25,6 +25,7 @@ struct DynStep {
     double *u, *v, *a;          // S N each: the context's u; v holds v_h between the launches of a call
     double* ke_partial;         // DYN_STORE: one partial per workgroup
     int flags;
+    double eta_m = 0.0;         // Rayleigh mass damping (fh_dynamics_set_damping); 0: the arithmetic of the undamped step, bit for bit
 };
 
 template <class P>   // (DynStep, or FoStage below)
@@ -35,6 +36,13 @@ __device__ __forceinline__ double dyn_load_factor(const P& p) {
 __device__ __forceinline__ double dyn_accel(double lf, double f, double r, double m) { return fma(lf, f, -r) / m; }
 __device__ __forceinline__ double dyn_kick(double v, double a, double half_dt) { return fma(half_dt, a, v); }
 __device__ __forceinline__ double dyn_drift(double u, double vh, double dt) { return fma(dt, vh, u); }
+// ... and with Rayleigh damping C = eta_m M + eta_k T(u) on the lumped mass: r holds r(u) + eta_k T(u) w already (w = v_h, the velocity the
+// handle keeps between launches; w = v_0 for a_0), so the stiffness part stays explicit; the mass part is implicit in v_{n+1} = v_h + dt/2 a:
+// a = ((lf f - r) / m - eta_m v_h) / (1 + eta_m dt/2).  complete = false: a_0 = (lf f - r) / m - eta_m v_0, exact, no divisor.
+__device__ __forceinline__ double dyn_accel_damped(double lf, double f, double r, double m, double v, double eta_m, double half_dt, bool complete) {
+    const double a = fma(-eta_m, v, fma(lf, f, -r) / m);
+    return complete ? a / fma(eta_m, half_dt, 1.0) : a;
+}
 
 // one dof of a launch: r is read only with DYN_ACCEL; returns the dof's m v^2 (DYN_STORE, else 0)
 __device__ __forceinline__ double dyn_dof(const DynStep& p, size_t i, bool fixed, double lf, double r) {
@@ -45,7 +53,8 @@ __device__ __forceinline__ double dyn_dof(const DynStep& p, size_t i, bool fixed
     }
     double v = p.v[i], a;
     if (p.flags & DYN_ACCEL) {
-        a = dyn_accel(lf, p.f ? p.f[i] : 0.0, r, p.m[i]);
+        a = p.eta_m != 0.0 ? dyn_accel_damped(lf, p.f ? p.f[i] : 0.0, r, p.m[i], v, p.eta_m, p.half_dt, (p.flags & DYN_COMPLETE) != 0)
+                           : dyn_accel(lf, p.f ? p.f[i] : 0.0, r, p.m[i]);
         if (p.flags & DYN_COMPLETE) v = dyn_kick(v, a, p.half_dt);
     } else {
         a = p.a[i];

@@ -26,7 +26,9 @@ struct fh_dynamics {
     // topo_gen, geom_gen, density_gen, dirichlet_gen, the u_gen this handle left behind, and the contact_gen of fh_set_obstacles
     unsigned long long m_key[5] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
     unsigned long long a_key[7] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
-    bool load_changed = true;
+    bool load_changed = true;          // (also: the damping coefficients have changed)
+    double eta_m = 0.0, eta_k = 0.0;   // Rayleigh damping C = eta_m M + eta_k T(u) (fh_dynamics_set_damping); (0, 0): every launch as without it
+    DevBuf<double> u_ref2;             // implicit schemes with damping: the folded u_ref of the step (k_damping_fold)
 };
 
 namespace {
@@ -65,7 +67,10 @@ int residual_tiles(fh_dynamics* d, bool* tiles) {
     bool serve;
     const int rc = tile_partials(c, d->rpart, c->S(), &serve);
     if (rc || !serve) return rc;
-    if (vector_tiles_element_pass(c->elem_kind, c->op, c->stream, pass_args(c), c->vt.v, active_mask(c), d->rpart.p) != FH_OK) return FH_OK;
+    // (stiffness damping: r(u) + eta_k T(u) v from one launch of k_damped_pass_tiled; v holds v_h, or v_0 when a_0 is formed)
+    const int rt = d->eta_k != 0.0 ? vector_tiles_damped_pass(c->elem_kind, c->op, c->stream, pass_args(c), c->vt.v, active_mask(c), d->v.p, d->eta_k, d->rpart.p)
+                                   : vector_tiles_element_pass(c->elem_kind, c->op, c->stream, pass_args(c), c->vt.v, active_mask(c), d->rpart.p);
+    if (rt != FH_OK) return FH_OK;
     HIP_TRY(c, hipGetLastError());
     *tiles = true;
     return FH_OK;
@@ -74,6 +79,28 @@ int residual_tiles(fh_dynamics* d, bool* tiles) {
 // r(u) summed into d->r on every other route (newton_residual's second branch): waits for the device and reports the kernels' status;
 // with obstacles set, r + g (one launch of k_contact_force behind the node sums)
 int residual_summed(fh_dynamics* d) { return ::residual_summed(d->c, d->r.p); }
+
+// y += s T(u) x on the free dofs, T(u) x through tmp: the stiffness part of the damping term on the routes off the tiles and in the implicit
+// schemes (tangent_summed, engine_vector.hip: no contact term); waits for the device
+int add_tangent(fh_dynamics* d, double s, const double* x, double* tmp, double* y) {
+    fh_ctx* c = d->c;
+    const int rc = tangent_summed(c, x, tmp);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_dynamics_axpy, dim3(blocks_of(d->n)), dim3(256), 0, c->stream, d->n, c->S(), s, dmask_of(c), tmp, y);
+    HIP_TRY(c, hipGetLastError());
+    return FH_OK;
+}
+
+// what the folding of a frozen C into newton_run's arguments cannot express
+int damping_supported(fh_dynamics* d, const char* who) {
+    fh_ctx* c = d->c;
+    if (d->eta_k == 0.0 || explicit_scheme(d)) return FH_OK;
+    if (c->op > FH_LINEAR_ELASTIC)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": stiffness damping under Newmark or backward Euler covers FH_LAPLACE and FH_LINEAR_ELASTIC only");
+    if (contact_table(c).count)
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": stiffness damping under Newmark or backward Euler with obstacles set is not covered");
+    return FH_OK;
+}
 
 int sum_blocks(fh_ctx* c, const double* partial, int count, double* out) { return sum_partials(c, partial, count, 1, out); }
 
@@ -92,6 +119,9 @@ int ensure_lumped(fh_dynamics* d, const char* who) {
     unsigned long long k[7];
     key_now(c, k);
     if (std::equal(k, k + 5, d->m_key)) return FH_OK;
+    // (with damping a_n is not formed again for what the handle itself moves -- remember_u -- and the walk below moves struct_gen on a
+    // rule-set table: an a_n that is current on entry stays current)
+    const bool a_current = (d->eta_m != 0.0 || d->eta_k != 0.0) && std::equal(k, k + 7, d->a_key) && !d->load_changed;
     const int n = d->n;
     const std::vector<double> ones((size_t)n, 1.0);
     std::vector<double> h((size_t)n);
@@ -108,7 +138,18 @@ int ensure_lumped(fh_dynamics* d, const char* who) {
             return c->fail(FH_UNSUPPORTED, std::string(who) + ": the row-sum lumped mass of dof " + std::to_string(i) + " (node " + std::to_string(i / S) +
                                                ") is " + std::to_string(h[(size_t)i]) + ", not positive: the explicit schemes need another lumping on this element kind");
     std::copy(k, k + 5, d->m_key);
+    if (a_current) key_now(c, d->a_key);
     return FH_OK;
+}
+
+// central differences with stiffness damping: (omega dt)^2 + 2 eta_k omega^2 dt <= 4 for the highest mode (the Jury conditions of the
+// step matrix of one mode; eta_m drops out): dt_crit = (2 / omega)(sqrt(1 + xi^2) - xi), xi = eta_k omega / 2.  Each operation rounded once.
+double damped_dt_crit(double omega, double eta_k) {
+#pragma clang fp contract(off)
+    const double xi = eta_k * omega / 2.0;
+    const double x2 = xi * xi;
+    const double root = std::sqrt(1.0 + x2);
+    return (2.0 / omega) * (root - xi);
 }
 
 DynStep step_args(fh_dynamics* d, int flags, uint64_t step) {
@@ -127,6 +168,7 @@ DynStep step_args(fh_dynamics* d, int flags, uint64_t step) {
     p.a = d->a.p;
     p.ke_partial = d->kep.p;
     p.flags = flags;
+    p.eta_m = d->eta_m;
     return p;
 }
 
@@ -143,13 +185,17 @@ int explicit_launch(fh_dynamics* d, int flags, uint64_t step, uint64_t* stats, i
         ++stats[1];
         if (tiles) {
             HIP_TRY(c, vector_tiles_dynamics_node_pass(c->stream, S, (int)c->N, c->vt.v, d->rpart.p, p, contact_table(c)));
-            c->last_kernel = "k_element_pass_tiled + k_dynamics_from_partials";
+            c->last_kernel = d->eta_k != 0.0 ? "k_damped_pass_tiled + k_dynamics_from_partials" : "k_element_pass_tiled + k_dynamics_from_partials";
             if (ke_count) *ke_count = vector_tiles_operator_partials((int)c->N);
             if (flags & DYN_ADVANCE) ++c->u_gen;
             return FH_OK;
         }
         rc = residual_summed(d);
         if (rc) return rc;
+        if (d->eta_k != 0.0) {   // r += eta_k T(u) v
+            rc = add_tangent(d, d->eta_k, d->v.p, d->work.p, d->r.p);
+            if (rc) return rc;
+        }
         c->last_kernel = contact_table(c).count ? "k_residual_elements + k_vector_from_elements_soa + k_contact_force + k_dynamics_update"
                                                 : "k_residual_elements + k_vector_from_elements_soa + k_dynamics_update";
     }
@@ -204,6 +250,10 @@ int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
         hipLaunchKernelGGL(k_dynamics_rhs, dim3(g), dim3(256), 0, c->stream, n, S, d->has_f ? d->f.p : nullptr, d->h_lf.empty() ? nullptr : d->lf.p,
                            (unsigned long long)d->h_lf.size(), (unsigned long long)d->step, dmask_of(c), d->r.p, d->work.p);
         HIP_TRY(c, hipGetLastError());
+        if (d->eta_k != 0.0 && d->s.scheme == FH_DYN_NEWMARK) {   // M a_0 = lf_0 f - r(u_0) - C v_0: the stiffness part joins the right-hand side
+            rc = add_tangent(d, -d->eta_k, d->v.p, d->r.p, d->work.p);
+            if (rc) return rc;
+        }
         double b2 = 0.0;   // (an inverted NeoHookean state makes r NaN: reported as such, not as a breakdown of the PCG or of Newton)
         rc = dot(d, d->work.p, d->work.p, &b2);
         if (rc) return rc;
@@ -215,6 +265,10 @@ int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
             rc = cg_solve_free_dev(c, WHO, MF_TANGENT, d->work.p, d->a.p, pre, d->s.linear_rel_tol, d->s.linear_max_iter, &it, 1.0, 0.0);
             stats[3] += it;
             if (rc) return rc;
+            if (d->eta_m != 0.0) {   // ... and the mass part leaves the solve: a_0 -= eta_m v_0
+                hipLaunchKernelGGL(k_dynamics_axpy, dim3(g), dim3(256), 0, c->stream, n, S, -d->eta_m, dmask_of(c), d->v.p, d->a.p);
+                HIP_TRY(c, hipGetLastError());
+            }
         }
     }
     key_now(c, k);
@@ -223,7 +277,13 @@ int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
     return FH_OK;
 }
 
-void remember_u(fh_dynamics* d) { d->a_key[5] = d->c->u_gen; }
+// a_n belongs to the state the handle has just left behind.  With damping a step's a_{n+1} (formed on v_h) is not what ensure_acceleration
+// would form again for the same state (on v_{n+1}), so nothing the steps themselves moved may make it stale: the walk over the groups of a
+// rule-set table stages every group and moves struct_gen, which without damping only forms the same a_n once more.
+void remember_u(fh_dynamics* d) {
+    if (d->eta_m != 0.0 || d->eta_k != 0.0) key_now(d->c, d->a_key);
+    else d->a_key[5] = d->c->u_gen;
+}
 
 int explicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, double* records, uint64_t* done, uint64_t* stats) {
     fh_ctx* c = d->c;
@@ -284,9 +344,31 @@ int implicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, do
             HIP_TRY(c, hipGetLastError());
             load = d->load.p;
         }
+        // Rayleigh damping, C frozen at the start of the step, folded into the four arguments (k_damping_fold; the corrector below takes
+        // the unmodified u_ref)
+        double alpha = 1.0, beta2 = bdt2;
+        const double* u_ref = d->u_ref.p;
+        int rc;
+        if (d->eta_m != 0.0 || d->eta_k != 0.0) {
+            const double gdt = (euler ? 1.0 : d->s.newmark_gamma) * dt;
+            alpha = 1.0 + d->eta_m * gdt;
+            beta2 = bdt2 + d->eta_k * gdt;
+            hipLaunchKernelGGL(k_damping_fold, dim3(g), dim3(256), 0, c->stream, n, S, euler ? 0.0 : dt - gdt, d->eta_m * bdt2 / alpha, bdt2, gdt, dmask_of(c),
+                               d->u_ref.p, d->v.p, d->a.p, d->u_ref2.p, d->work.p);
+            HIP_TRY(c, hipGetLastError());
+            u_ref = d->u_ref2.p;
+            if (d->eta_k != 0.0) {   // one application of the linear operator, on w
+                rc = tangent_summed(c, d->work.p, d->r.p);
+                if (rc) return rc;
+                hipLaunchKernelGGL(k_damping_load, dim3(g), dim3(256), 0, c->stream, n, bdt2 * load_factor(d, g_step), d->has_f ? d->f.p : nullptr, d->eta_k,
+                                   d->r.p, beta2, d->load.p);
+                HIP_TRY(c, hipGetLastError());
+                load = d->load.p;
+            }
+        }
         uint64_t st[4] = {0, 0, 0, 0};
         double nm[3] = {0.0, 0.0, 0.0};
-        int rc = newton_run(c, 1.0, bdt2, load, d->u_ref.p, d->s.newton_tolerance, d->s.newton_max_iterations, d->s.line_search, d->s.preconditioner,
+        rc = newton_run(c, alpha, beta2, load, u_ref, d->s.newton_tolerance, d->s.newton_max_iterations, d->s.line_search, d->s.preconditioner,
                             d->s.linear_rel_tol, d->s.linear_max_iter, st, nm);
         stats[1] += st[1];
         stats[2] += st[0];
@@ -563,6 +645,8 @@ int state_common(fh_dynamics* d, double* u, double* v, double* a, double* time, 
     const size_t bytes = sizeof(double) * (size_t)d->n;
     if ((first_order(d) ? v : a) && c->has_u && c->N) {   // a_n of the state as it stands (a_0 before the first step); first order: the rate
         uint64_t st[5] = {0, 0, 0, 0, 0};
+        rc = damping_supported(d, "fh_dynamics_state");
+        if (rc) return rc;
         if (explicit_scheme(d)) rc = ensure_lumped(d, "fh_dynamics_state");
         if (!rc) rc = first_order(d) ? ensure_rate(d, true, st) : ensure_acceleration(d, st);
         if (rc) return rc;
@@ -687,6 +771,28 @@ int fh_dynamics_set_load_dev(fh_dynamics* d, const double* f_dev, const double* 
     return set_load_common(d, f_dev, load_factor, count, hipMemcpyDeviceToDevice);
 }
 
+int fh_dynamics_set_damping(fh_dynamics* d, double eta_mass, double eta_stiffness) {
+    if (!d) return FH_BAD_ARGUMENT;
+    fh_ctx* c = d->c;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_dynamics_set_damping";
+    if (first_order(d)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a first-order problem has no velocity to damp");
+    if (!std::isfinite(eta_mass) || !std::isfinite(eta_stiffness) || eta_mass < 0.0 || eta_stiffness < 0.0)
+        return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the coefficients must be finite and not negative");
+    if ((eta_mass != 0.0 || eta_stiffness != 0.0) && !explicit_scheme(d) && d->u_ref2.n < (size_t)d->n) HIP_TRY(c, d->u_ref2.alloc((size_t)d->n));
+    if (eta_mass != d->eta_m || eta_stiffness != d->eta_k) d->load_changed = true;   // a_n is formed again, as after fh_dynamics_set_load
+    d->eta_m = eta_mass + 0.0;   // (-0 -> +0)
+    d->eta_k = eta_stiffness + 0.0;
+    return FH_OK;
+}
+int fh_dynamics_damping(fh_dynamics* d, double* eta_mass, double* eta_stiffness) {
+    if (!d) return FH_BAD_ARGUMENT;
+    if (first_order(d)) return d->c->fail(FH_BAD_ARGUMENT, "fh_dynamics_damping: a first-order problem has no velocity to damp");
+    if (eta_mass) *eta_mass = d->eta_m;
+    if (eta_stiffness) *eta_stiffness = d->eta_k;
+    return FH_OK;
+}
+
 int fh_dynamics_step(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, double* records, uint64_t* steps_done, uint64_t* stats) {
     if (!d) return FH_BAD_ARGUMENT;
     fh_ctx* c = d->c;
@@ -701,6 +807,8 @@ int fh_dynamics_step(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, 
         rc = set_state_common(d, nullptr, nullptr, hipMemcpyHostToDevice);
         if (rc) return rc;
     }
+    rc = damping_supported(d, WHO);
+    if (rc) return rc;
     if (explicit_scheme(d)) rc = ensure_lumped(d, WHO);
     if (first_order(d)) {   // (the steps do not read the rate: the state is checked once)
         if (!rc && d->fresh) rc = ensure_rate(d, false, st);
@@ -779,7 +887,7 @@ int fh_dynamics_stable_dt(fh_dynamics* d, uint32_t iterations, double* omega_max
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!(rq > 0.0) || !std::isfinite(rq)) return c->fail(FH_DYNAMICS_NONFINITE, std::string(who) + ": the Rayleigh quotient is not positive and finite");
     *omega_max = std::sqrt(rq);
-    if (!first_order(d)) *dt_crit = 2.0 / *omega_max;
+    if (!first_order(d)) *dt_crit = d->eta_k != 0.0 ? damped_dt_crit(*omega_max, d->eta_k) : 2.0 / *omega_max;
     else *dt_crit = d->fo_scheme == FH_FO_RKL ? ((double)d->stages * (double)d->stages + (double)d->stages) / (*omega_max * *omega_max) : HUGE_VAL;
     return FH_OK;
 }

@@ -656,6 +656,7 @@ bool tiles_enabled(const fh_ctx* c);
 int ensure_vector_tiles(fh_ctx* c);
 int tile_partials(fh_ctx* c, DevBuf<double>& part, int comps, bool* serve, bool even_with_atomics = false);
 int residual_summed(fh_ctx* c, double* out);
+int tangent_summed(fh_ctx* c, const double* x, double* out);   // T(u) x, the element sums alone: no Dirichlet rows, no contact term
 int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* out);
 // penalty contact (engine_contact.hip).  contact_table: the table for a kernel of the tangent / residual routes at the context's u, "off"
 // (count 0) without obstacles or in the operator's scope; contact_blocked: FH_UNSUPPORTED when obstacles are set and the operator's solution

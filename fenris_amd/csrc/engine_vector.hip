@@ -676,6 +676,23 @@ static int mf_operand(fh_ctx* c, const double* x, const unsigned char* dmask, Mf
     return FH_OK;
 }
 
+// T(u) x over every group of the table into out (S N doubles): the element sums alone -- every entry of x takes part, no Dirichlet rows, no
+// contact term -- which is what the damping term eta_k T(u) v of the time integrators takes (the obstacle term stays out of C).  For the
+// linear operators this is the residual's route run on the vector x (LinearElastic: on x 2^-e, scaled back).  Each group's status is reset
+// and read.
+int tangent_summed(fh_ctx* c, const double* x, double* out) {
+    const int S = c->S(), n = S * (int)c->N;
+    MfOperand in;
+    int rc = mf_operand(c, x, nullptr, &in);
+    if (rc) return rc;
+    rc = walk_groups_into(c, out, (size_t)n, nullptr, [&](uint64_t* fl) { return mf_single(c, in.x, out, fl); });
+    if (rc || !in.bits || !n) return rc;
+    hipLaunchKernelGGL(k_mf_finish, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, S, x, (const unsigned char*)nullptr, (const double*)nullptr, in.bits,
+                       out, (double*)nullptr);
+    HIP_TRY(c, hipGetLastError());
+    return FH_OK;
+}
+
 // where the g per-workgroup partials of x . y go: dot_scratch sized to them and *partials = g, or (dot_scratch null) nowhere
 static int dot_partials(fh_ctx* c, DevBuf<double>* dot_scratch, int g, int* partials, double** dp) {
     *dp = nullptr;

@@ -523,6 +523,47 @@ __global__ void __launch_bounds__(TS) k_tangent_tiled(const KArgs a, const VecTi
     tp.finish(t, f, stage, ents, partial);
 }
 
+// element pass of a central-difference step with Rayleigh stiffness damping (engine_dynamics.hip): r(u) + eta_k T(u) v in ONE launch and one
+// array of partials, v (the handle's v_h, or v_0 for a_0; its Dirichlet entries are zero) gathered beside u.  Linear operators: r is linear
+// and T(u) = A, so the residual's body runs once on u + eta_k v -- no second body, no second gather of X.  Nonlinear operators: the residual's
+// body, whose element vector is parked in the thread's own places of the staging array, then the tangent's body on the same X and u, and
+// f + eta_k g goes back to those places: the live registers are those of k_tangent_tiled, not of both bodies at once.  MONO as
+// k_element_pass_tiled's (form 3 exists for the linear operators only, where the tangent's body is not run).
+template <int EK, int OP, int TS, int MONO = 0>
+__global__ void __launch_bounds__(TS) k_damped_pass_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const double* v, double eta_k,
+                                                           double* partial) {
+    constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
+    __shared__ double stage[N * S * TS];
+    __shared__ unsigned short ents[(N % 4 == 0) ? TS * N : 4];
+    TilePass<N, TS> tp;
+    if (!tp.begin(t, active)) return;
+    double X[N][D], Uv[N][S], Vv[N][S], f[N][S], energy;
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        tp.coords(n, a.verts, X[n]);
+        tp.field(n, a.u, Uv[n]);
+        tp.field_masked(n, v, nullptr, Vv[n]);   // (the handle's velocity: always there)
+    }
+    if constexpr (OP <= FH_LINEAR_ELASTIC) {
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int k = 0; k < S; ++k) Uv[n][k] = fma(eta_k, Vv[n][k], Uv[n][k]);
+        element_pass_body<EK, OP, EP_VECTOR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+        tp.store(f, stage);
+    } else {
+        element_pass_body<EK, OP, EP_VECTOR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+        tp.store(f, stage);
+        if constexpr (MONO != 0 && EK == FH_HEX8) tangent_body_hex8<OP, MONO == 2>(a, tp.ec, tp.live, X, Uv, Vv, f);
+        else tangent_element_body<D, S, N, OP>(a, tp.ec, tp.live, X, Uv, Vv, f);
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int c = 0; c < S; ++c) tp.put(stage, n * S + c, fma(eta_k, f[n][c], stage[(n * S + c) * TS + tp.tid]));
+    }
+    tp.template sum<S>(t, stage, ents, partial);
+}
+
 // node pass of the matrix-free operator y = A x: y[S node + c] = sum of the node's partials in ascending order, OVERWRITTEN (not added).
 // dmask (may be null): homogeneous Dirichlet nodes, whose rows hold  scale x  (the element pass saw x with those entries zeroed, so
 // their columns are zero already); the element pass saw x 2^-e (xbits: mf_exponent), the sums are scaled back.  dot_partial (may be null): per workgroup  x . y  over its nodes, in a fixed tree.
@@ -934,6 +975,13 @@ int dispatch_tile_pass(int elem_kind, int_list<OPs...> ops, int op, const KArgs&
 int vector_tiles_element_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial) {
     return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m) {
         return tile_launch(k_element_pass_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, partial);
+    });
+}
+
+int vector_tiles_damped_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* v,
+                             double eta_k, double* partial) {
+    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m) {
+        return tile_launch(k_damped_pass_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, v, eta_k, partial);
     });
 }
 

@@ -44,6 +44,12 @@ hipError_t vector_tiles_stats(hipStream_t stream, const VecTiles& t, int num_nod
 // active (device, may be null): elements with active[e] == 0 contribute nothing.  Returns -1 when (elem_kind, op) is not covered.
 int vector_tiles_element_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial);
 
+// element pass of a central-difference step with Rayleigh stiffness damping: partial[P][S] of r(u) + eta_k T(u) v in one launch
+// (k_damped_pass_tiled: the residual's body on u + eta_k v for the linear operators; the residual's and the tangent's body for the
+// nonlinear ones), v S N doubles whose Dirichlet entries are zero.  Covers what vector_tiles_element_pass covers; -1 otherwise.
+int vector_tiles_damped_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* v,
+                             double eta_k, double* partial);
+
 // energy over the tiles: one partial per workgroup into partial[] (the number of workgroups = partials comes back; -1: not covered);
 // the caller sums them in index order (k_sum_partials)
 int vector_tiles_energy_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial);

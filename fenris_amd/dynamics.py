@@ -16,7 +16,12 @@ case) and ThetaMethod (Crank-Nicolson, implicit Euler).
     ti = RungeKuttaLegendre(asm, capacity, dt, stages=8).with_dirichlet_nodes(cold).with_load(q)
     ti.set_state(u0)
     rec = ti.step(200, record_every=50)          # rec.mass_norm, rec.stored, rec.load_potential, rec.time
-    u, rate, time, step = ti.state()"""
+    u, rate, time, step = ti.state()
+
+Rayleigh damping  M a + C(u) v + r(u) = lf_n f,  C(u) = eta_m M + eta_k T(u)  (fh_dynamics_set_damping), on the three second-order schemes:
+
+    ti = CentralDifference(asm, density, dt).with_damping(RayleighDamping.from_ratios(0.02, w1, 0.05, w2))
+    ti = Newmark(asm, density, dt).with_damping(mass=0.5, stiffness=1e-4)"""
 from __future__ import annotations
 
 import ctypes as C
@@ -53,6 +58,32 @@ class DynamicsRecord:
     stats: tuple
 
 
+@dataclass(frozen=True)
+class RayleighDamping:
+    """C = mass M + stiffness T(u): both coefficients finite and not negative"""
+
+    mass: float = 0.0
+    stiffness: float = 0.0
+
+    @classmethod
+    def from_ratios(cls, xi1, omega1, xi2, omega2):
+        """the coefficients that give the damping ratios xi1 at omega1 and xi2 at omega2 (rad / time), omega1 != omega2: the two-frequency
+        fit of xi(omega) = mass / (2 omega) + stiffness omega / 2; a fit with a negative coefficient is refused"""
+        xi1, omega1, xi2, omega2 = float(xi1), float(omega1), float(xi2), float(omega2)
+        if not (omega1 > 0.0 and omega2 > 0.0 and omega1 != omega2):
+            raise ValueError("from_ratios needs two distinct positive frequencies")
+        den = (omega2 - omega1) * (omega2 + omega1)
+        mass = 2.0 * omega1 * omega2 * (xi1 * omega2 - xi2 * omega1) / den
+        stiffness = 2.0 * (xi2 * omega2 - xi1 * omega1) / den
+        if mass < 0.0 or stiffness < 0.0:
+            raise ValueError(f"these ratios need a negative coefficient (mass {mass}, stiffness {stiffness})")
+        return cls(mass, stiffness)
+
+    def ratio(self, omega):
+        """the damping ratio of a mode of angular frequency omega"""
+        return self.mass / (2.0 * omega) + self.stiffness * omega / 2.0
+
+
 class TimeIntegrator:
     """The interface the three schemes share.  Density, Dirichlet nodes and load belong to this object and are handed to the engine before
     every use (the discipline of MatrixFreeNewton._bind), so several objects may share one assembler.  The assembler's u is the state's u."""
@@ -73,6 +104,7 @@ class TimeIntegrator:
         self._beta, self._gamma = 0.25, 0.5
         self._h = None
         self._load = (None, None)
+        self._damping = None
         self.engine.set_mass_density(self._rho)   # (checks the count now)
         self.engine._mass_bound = self
 
@@ -89,6 +121,28 @@ class TimeIntegrator:
         if self._h is not None:
             self._send_load()
         return self
+
+    def with_damping(self, mass=0.0, stiffness=0.0):
+        """Rayleigh damping C = mass M + stiffness T(u) (a RayleighDamping, or the two coefficients; the default (0, 0) is the undamped
+        step bit for bit).  stiffness > 0 under Newmark or backward Euler covers the linear operators only (step raises FH_UNSUPPORTED
+        otherwise); a_n is formed again after a change.  Returns self"""
+        if isinstance(mass, RayleighDamping):
+            mass, stiffness = mass.mass, mass.stiffness
+        self._damping = (float(mass), float(stiffness))
+        if self._h is not None:
+            self._send_damping()
+        return self
+
+    def damping(self):
+        """the RayleighDamping the handle uses"""
+        h = self._handle()
+        m, k = C.c_double(0.0), C.c_double(0.0)
+        self.engine._check(self.engine._lib.fh_dynamics_damping(h, C.byref(m), C.byref(k)))
+        return RayleighDamping(m.value, k.value)
+
+    def _send_damping(self):
+        if self._damping is not None:
+            self.engine._check(self.engine._lib.fh_dynamics_set_damping(self._h, self._damping[0], self._damping[1]))
 
     def _bind(self, force=False):
         if force or getattr(self.engine, "_mf_bound", None) is not self:
@@ -125,6 +179,7 @@ class TimeIntegrator:
             self.engine._check(getattr(self.engine._lib, self._create)(self.engine._h, C.byref(s), C.byref(h)))
             self._h = h
             self._send_load()
+            self._send_damping()
         return self._h
 
     def _drop(self):
@@ -230,7 +285,7 @@ class TimeIntegrator:
         return u, v, a, t.value, int(k.value)
 
     def stable_dt(self, iterations=30):
-        """(omega_max, dt_crit = 2 / omega_max) from `iterations` steps of the power iteration on m^-1 T(u); the estimate of omega_max is a
+        """(omega_max, dt_crit = 2 / omega_max; with stiffness damping (2 / omega_max)(sqrt(1 + xi^2) - xi), xi = stiffness omega_max / 2) from `iterations` steps of the power iteration on m^-1 T(u); the estimate of omega_max is a
         Rayleigh quotient and never too large, so dt_crit errs on the large side: apply a safety factor"""
         h = self._handle()
         om, dtc = C.c_double(0.0), C.c_double(0.0)
@@ -292,6 +347,12 @@ class FirstOrderIntegrator(TimeIntegrator):
 
     _create = "fh_first_order_create"
     _stages, _theta = 1, 1.0
+
+    def with_damping(self, mass=0.0, stiffness=0.0):
+        raise TypeError("a first-order problem has no velocity to damp")
+
+    def damping(self):
+        raise TypeError("a first-order problem has no velocity to damp")
 
     def _fh_settings(self):
         s = _ffi.FirstOrderSettings()

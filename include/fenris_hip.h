@@ -877,6 +877,37 @@ int fh_dynamics_step(fh_dynamics*, uint64_t num_steps, uint64_t record_every, do
 int fh_dynamics_state(fh_dynamics*, double* u, double* v, double* a, double* time, uint64_t* step);
 int fh_dynamics_state_dev(fh_dynamics*, double* u_dev, double* v_dev, double* a_dev, double* time, uint64_t* step);
 int fh_dynamics_stable_dt(fh_dynamics*, uint32_t iterations, double* omega_max, double* dt_crit);
+/* ---- Rayleigh damping of the second-order problem:  M a + C(u) v + r(u) = lf_n f  with  C(u) = eta_mass M + eta_stiffness T(u),  T(u) the
+ * element tangent of the context's operator at the current state (FH_LAPLACE, FH_LINEAR_ELASTIC: the constant operator A).  The obstacle
+ * term of fh_set_obstacles stays out of C; the contact force joins r as without damping.  The default is (0, 0), and with (0, 0), set or
+ * not, every launch and every bit is that of the undamped step.
+ *
+ * FH_DYN_CENTRAL_DIFFERENCE, with F(u, w) = lf f - r(u) - eta_stiffness T(u) w and the lumped mass m:
+ *     a_0 = F(u_0, v_0) / m - eta_mass v_0;   v_h = v_n + dt/2 a_n;   u_{n+1} = u_n + dt v_h;
+ *     a_{n+1} = (F(u_{n+1}, v_h) / m - eta_mass v_h) / (1 + eta_mass dt/2);   v_{n+1} = v_h + dt/2 a_{n+1}.
+ *   The stiffness part takes the half-step velocity, which keeps the step explicit; the mass part is implicit in v_{n+1}.  On the tiles a
+ *   step with eta_stiffness > 0 is ONE element pass that gathers v beside u and leaves the partials of r(u) + eta_stiffness T(u) v_h
+ *   (k_damped_pass_tiled: for the linear operators the residual's body on u + eta_stiffness v_h) and the same one node pass; with
+ *   eta_stiffness == 0 the residual's element pass runs unchanged and only the node arithmetic differs.  On every other route
+ *   eta_stiffness T(u) v_h, summed like the residual, is added to it before k_dynamics_update.
+ *   fh_dynamics_stable_dt then returns dt_crit = (2 / omega_max)(sqrt(1 + xi^2) - xi), xi = eta_stiffness omega_max / 2 (the limit
+ *   (omega dt)^2 + 2 eta_stiffness omega^2 dt <= 4 of the highest mode; eta_mass does not enter); omega_max as without damping.
+ * FH_DYN_NEWMARK and FH_DYN_BACKWARD_EULER: C is frozen at the start of the step and folded into the Newton solve's four arguments.  With
+ *   b = newmark_beta dt^2, g = newmark_gamma (backward Euler: b = dt^2, g = 1), v_p = v_n + dt (1 - g) a_n (backward Euler: v_n):
+ *     alpha = 1 + eta_mass g dt;   u_ref* = u_ref - eta_mass b v_p / alpha;   beta' = b + eta_stiffness g dt;
+ *     f' = (b lf_{n+1} f - eta_stiffness A (b v_p - g dt u_ref)) / beta'
+ *   (for backward Euler these are u_ref* = (u_ref + eta_mass dt u_n) / alpha and f' = (dt^2 lf f + eta_stiffness dt A u_n) / beta'): one
+ *   application of A per step, and only when eta_stiffness > 0.  a_{n+1} and v_{n+1} are recovered from the unmodified u_ref, and Newmark's
+ *   a_0 solves M a_0 = lf_0 f - r(u_0) - C v_0.
+ *   OUT OF SCOPE: eta_stiffness > 0 under these two schemes with FH_NEO_HOOKEAN, FH_STVK or FH_STABLE_NEO_HOOKEAN (the frozen T(u_n) differs
+ *   from T(u): a second tangent state would have to enter the Newton residual and every CG product), and with obstacles set (the folded
+ *   beta' would scale the contact force too): fh_dynamics_step and fh_dynamics_state (when a is asked for) return FH_UNSUPPORTED and leave
+ *   the state as it is.  eta_mass works with every operator under every scheme.  The records keep their four columns (no dissipated work).
+ * fh_dynamics_set_damping: FH_BAD_ARGUMENT for a coefficient that is negative or not finite, and for a handle of fh_first_order_create (a
+ *   first-order problem has no velocity).  Changing the coefficients invalidates a_n, as fh_dynamics_set_load does.
+ * fh_dynamics_damping: the coefficients in use (either pointer may be null). */
+int fh_dynamics_set_damping(fh_dynamics*, double eta_mass, double eta_stiffness);
+int fh_dynamics_damping(fh_dynamics*, double* eta_mass, double* eta_stiffness);
 /* ---- the first-order problem on the same handle:  M du/dt + r(u) = lf_n f  (the heat equation for FH_LAPLACE; the gradient flow of the
  * stored energy for the elastic operators), Dirichlet nodes held.  fh_first_order_create makes an fh_dynamics handle on which every
  * fh_dynamics_* call works as described above, with these differences.  The state is u alone (the context's u) and the step counter:
