@@ -200,6 +200,12 @@ _SIGS = {
     "fh_contact_force_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_contact_gap_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_add_contact_tangent_csr_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_set_friction": (C.c_int, [C.c_void_p, f64p, C.c_uint64, C.c_double]),
+    "fh_set_friction_reference": (C.c_int, [C.c_void_p, f64p]),
+    "fh_set_friction_reference_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_friction_potential": (C.c_int, [C.c_void_p, f64p]),
+    "fh_friction_force_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_dynamics_set_slip_velocity": (C.c_int, [C.c_void_p, C.c_double]),
     "fh_mg_create": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(u64p), C.POINTER(u64p), C.POINTER(f64p),
                                C.POINTER(C.c_void_p)]),
     "fh_mg_destroy": (None, [C.c_void_p]),

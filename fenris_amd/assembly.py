@@ -1257,6 +1257,10 @@ class MatrixFreeTangent(MatrixFreeOperator):
         """the rigid obstacles whose penalty term B(u) joins T(u) (fenris_amd.contact.Obstacles; None: none); they belong to this object"""
         return _contact.with_obstacles(self, obstacles)
 
+    def with_friction_reference(self, ubar):
+        """the lag displacement of the obstacles' friction term (fenris_amd.contact; a copy is kept); returns self"""
+        return _contact.with_friction_reference(self, ubar)
+
     def _apply_dev(self, x_t, y_t):
         self.engine.apply_tangent_dev(x_t, y_t)
 
@@ -1290,6 +1294,10 @@ class MatrixFreeShiftedTangent(MatrixFreeOperator):
     def with_obstacles(self, obstacles):
         """the rigid obstacles whose penalty term joins the map: alpha M + beta (T(u) + B(u)) (None: none); they belong to this object"""
         return _contact.with_obstacles(self, obstacles)
+
+    def with_friction_reference(self, ubar):
+        """the lag displacement of the obstacles' friction term (fenris_amd.contact; a copy is kept); returns self"""
+        return _contact.with_friction_reference(self, ubar)
 
     def _mg_density(self):
         return self._rho if self.alpha != 0.0 else None
@@ -1454,6 +1462,11 @@ class MatrixFreeNewton:
     def with_obstacles(self, obstacles):
         """the rigid obstacles of the penalty contact term: F = alpha M (u - u_ref) + beta (r(u) + g(u) - f) (None: none); returns self"""
         return _contact.with_obstacles(self, obstacles)
+
+    def with_friction_reference(self, ubar):
+        """the lag displacement of the obstacles' friction term: F = alpha M (u - u_ref) + beta (r + g + q - f) with normal force and
+        tangent plane frozen at ubar (copied); a quasi-static user moves it to the converged u between load steps; returns self"""
+        return _contact.with_friction_reference(self, ubar)
 
     def solve(self, u, settings: NewtonSettings = NewtonSettings(), line_search=None, preconditioner=None, linear_rel_tol=1e-8, linear_max_iter=0):
         """u: the guess with the Dirichlet values (numpy array or device tensor), overwritten by the solution.  Returns a NewtonResult;

@@ -9,6 +9,13 @@ w_i (default 1) the term adds the energy sum (k w_i / 2) p^2, the force k w_i p 
 semi-definite block per node to the tangent.  HalfSpace and Cavity (the body stays inside the sphere) give the exact tangent; for Ball
 (the body stays outside) the curvature term is negative semi-definite and is dropped: a Gauss-Newton tangent.
 
+Coulomb friction (fh_set_friction): an obstacle takes `friction=mu`, the Obstacles a `slip_length` (the solvers) or a `slip_velocity` (the
+time integrators, whose slip length is slip_velocity dt).  The law is lagged and smoothed: normal force and tangent plane are frozen at a lag
+displacement ubar, where the friction force is the gradient of a convex potential and its block per node symmetric positive semi-definite.
+`with_friction_reference(ubar)` on MatrixFreeNewton, MatrixFreeTangent and MatrixFreeShiftedTangent sets ubar (a quasi-static user moves it
+to the converged u between load steps); Newmark and BackwardEuler set ubar = u_n at the start of every step, CentralDifference takes the
+current position and the slip of the half-step velocity.  The first-order integrators refuse friction.
+
 `with_obstacles` on MatrixFreeTangent, MatrixFreeShiftedTangent, MatrixFreeNewton, the time integrators and MatrixFreeEigensolver makes
 the obstacles belong to that object: they are handed to the engine before every use, as its Dirichlet nodes are.  An object that was never
 given obstacles does not inherit those of another object: it clears them from the engine before its use (the owner hands them over again
@@ -40,9 +47,9 @@ def _vec3(v, name):
 class _Obstacle:
     kind = -1
 
-    def __init__(self, point, normal, radius, stiffness):
+    def __init__(self, point, normal, radius, stiffness, friction=0.0):
         self.point, self.normal = _vec3(point, "point"), _vec3(normal, "normal")
-        self.radius, self.stiffness = float(radius), float(stiffness)
+        self.radius, self.stiffness, self.friction = float(radius), float(stiffness), float(friction)
 
     def _fill(self, o):
         o.kind, o.stiffness, o.radius = self.kind, self.stiffness, self.radius
@@ -54,45 +61,61 @@ class HalfSpace(_Obstacle):
     """phi(x) = (x - point) . n with n = normal / |normal| (fenris-geometry primitives/half_space.rs): the body stays where phi > 0"""
     kind = OBSTACLE_HALF_SPACE
 
-    def __init__(self, point, normal, stiffness):
-        super().__init__(point, normal, 0.0, stiffness)
+    def __init__(self, point, normal, stiffness, friction=0.0):
+        super().__init__(point, normal, 0.0, stiffness, friction)
 
 
 class Ball(_Obstacle):
     """phi(x) = |x - centre| - radius (sdf.rs circle, primitives/ball.rs): the body stays outside"""
     kind = OBSTACLE_BALL
 
-    def __init__(self, centre, radius, stiffness):
-        super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness)
+    def __init__(self, centre, radius, stiffness, friction=0.0):
+        super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness, friction)
 
 
 class Cavity(_Obstacle):
     """phi(x) = radius - |x - centre|: the body stays inside"""
     kind = OBSTACLE_CAVITY
 
-    def __init__(self, centre, radius, stiffness):
-        super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness)
+    def __init__(self, centre, radius, stiffness, friction=0.0):
+        super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness, friction)
 
 
 class Obstacles:
-    """A list of at most MAX_OBSTACLES obstacles and optional node weights w_i >= 0 (one per node; None: 1)"""
+    """A list of at most MAX_OBSTACLES obstacles and optional node weights w_i >= 0 (one per node; None: 1).  With friction on any of them:
+    slip_length (eps of the solvers' term) and / or slip_velocity (the time integrators: eps = slip_velocity dt)"""
 
-    def __init__(self, obstacles, node_weights=None):
+    def __init__(self, obstacles, node_weights=None, slip_length=None, slip_velocity=None):
         self.obstacles = list(obstacles)
+        self.slip_length = None if slip_length is None else float(slip_length)
+        self.slip_velocity = None if slip_velocity is None else float(slip_velocity)
         self.node_weights = None if node_weights is None else np.ascontiguousarray(np.asarray(node_weights, dtype=np.float64).ravel()).copy()
 
     def __len__(self):
         return len(self.obstacles)
 
+    def has_friction(self):
+        return any(getattr(o, "friction", 0.0) > 0.0 for o in self.obstacles)
 
-def set_obstacles(engine, obstacles):
-    """Engine.set_obstacles: an Obstacles, a plain list of obstacles, or None / empty to clear them"""
+    def slip_length_for(self, dt=None):
+        """the slip length a user with time step dt (None: a solver) hands to fh_set_friction"""
+        if self.slip_length is not None:
+            return self.slip_length
+        if dt is not None and self.slip_velocity is not None:
+            return self.slip_velocity * dt
+        raise ValueError("obstacles with friction need a slip_length (solvers) or a slip_velocity (time integrators)")
+
+
+def set_obstacles(engine, obstacles, dt=None):
+    """Engine.set_obstacles: an Obstacles, a plain list of obstacles, or None / empty to clear them.  dt: the time step of the integrator
+    that binds them (friction: slip_velocity dt may stand in for the slip length)"""
     engine._contact_bound = None   # (no object's obstacles are bound any more)
     if obstacles is None:
         obstacles = Obstacles([])
     elif not isinstance(obstacles, Obstacles):
         obstacles = Obstacles(obstacles)
     n = len(obstacles)
+    eps = obstacles.slip_length_for(dt) if obstacles.has_friction() else None   # (raises before anything is sent)
     arr = (_ffi.Obstacle * max(n, 1))()
     for o, item in zip(arr, obstacles.obstacles):
         item._fill(o)
@@ -100,6 +123,9 @@ def set_obstacles(engine, obstacles):
     if w is not None and n and w.size != engine.num_nodes():
         raise ValueError(f"node_weights must hold {engine.num_nodes()} entries")
     engine._check(engine._lib.fh_set_obstacles(engine._h, arr, n, _ffi.fp(w) if (w is not None and n) else None))
+    if eps is not None:
+        mu = np.array([getattr(o, "friction", 0.0) for o in obstacles.obstacles], dtype=np.float64)
+        engine._check(engine._lib.fh_set_friction(engine._h, _ffi.fp(mu), n, eps))
 
 
 def bind_obstacles(obj, force=False):
@@ -109,8 +135,47 @@ def bind_obstacles(obj, force=False):
             set_obstacles(obj.engine, None)
         return
     if force or getattr(obj.engine, "_contact_bound", None) is not obj:
-        set_obstacles(obj.engine, obj._obstacles)
+        set_obstacles(obj.engine, obj._obstacles, getattr(obj, "dt", None))
         obj.engine._contact_bound = obj
+        _send_friction_reference(obj)
+
+
+def _has_friction(obj):
+    obstacles = getattr(obj, "_obstacles", None)
+    return isinstance(obstacles, Obstacles) and obstacles.has_friction()
+
+
+def _send_friction_reference(obj):
+    ref = getattr(obj, "_friction_ref", None)
+    if ref is None or not _has_friction(obj):
+        return
+    eng = obj.engine
+    if isinstance(ref, np.ndarray):
+        eng._check(eng._lib.fh_set_friction_reference(eng._h, _ffi.fp(ref)))
+    else:
+        eng._check(eng._lib.fh_set_friction_reference_dev(eng._h, C.c_void_p(ref.data_ptr())))
+
+
+def with_friction_reference(obj, ubar):
+    """the body of `with_friction_reference(ubar)`: the lag displacement of the friction term, a numpy array or device tensor that is COPIED
+    here (after a solve: the converged u), so the lag state is what the caller gave whoever uses the engine in between.  It is bound like
+    the obstacles; returns obj"""
+    if ubar is None:
+        raise ValueError("with_friction_reference needs the lag displacement itself (after a solve: the converged u)")
+    if isinstance(ubar, np.ndarray) or not hasattr(ubar, "data_ptr"):
+        obj._friction_ref = np.ascontiguousarray(np.asarray(ubar, dtype=np.float64).ravel()).copy()
+    else:
+        obj._friction_ref = ubar.detach().clone().contiguous()
+    if getattr(obj, "_owns_obstacles", False):
+        bind_obstacles(obj, force=True)
+    return obj
+
+
+def send_slip_velocity(obj):
+    """the time integrators: the slip velocity of the object's obstacles to its handle (second-order handles only)"""
+    if obj._h is None or not _has_friction(obj) or obj._obstacles.slip_velocity is None or obj._create != "fh_dynamics_create":
+        return
+    obj.engine._check(obj.engine._lib.fh_dynamics_set_slip_velocity(obj._h, obj._obstacles.slip_velocity))
 
 
 def with_obstacles(obj, obstacles):
@@ -145,6 +210,21 @@ class Contact:
         self.engine._check(self.engine._lib.fh_contact_force_dev(self.engine._h, C.c_void_p(out.data_ptr())))
         return out if device else out.cpu().numpy()
 
+    def friction_potential(self):
+        """D, the potential of the lagged friction term at the engine's u (0 without friction)"""
+        e = C.c_double(0.0)
+        self.engine._check(self.engine._lib.fh_friction_potential(self.engine._h, C.byref(e)))
+        return e.value
+
+    def friction_force(self, device=False, out=None):
+        """q (the force the friction term adds to r(u) beside g): a new vector, or ADDED into the device tensor `out`"""
+        import torch
+
+        if out is None:
+            out = torch.zeros(self._dim() * self.engine.num_nodes(), dtype=torch.float64, device=f"cuda:{self.engine.device}")
+        self.engine._check(self.engine._lib.fh_friction_force_dev(self.engine._h, C.c_void_p(out.data_ptr())))
+        return out if device else out.cpu().numpy()
+
     def gap(self, device=False):
         """per node the smallest phi over the obstacles (negative: penetration)"""
         import torch
@@ -154,7 +234,7 @@ class Contact:
         return g if device else g.cpu().numpy()
 
     def add_tangent_to(self, csr_values):
-        """B ADDED into the diagonal node blocks of the engine's CSR values: a device tensor in place, or a numpy array (returned)"""
+        """B (and, while friction is set, H) ADDED into the diagonal node blocks of the engine's CSR values: a device tensor in place, or a numpy array (returned)"""
         import torch
 
         if isinstance(csr_values, torch.Tensor):

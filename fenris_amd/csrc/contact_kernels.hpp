@@ -7,6 +7,19 @@
 // partials, the routes off the tiles through the stand-alone kernels at the end of this file (engine_contact.hip launches them).
 // The table travels BY VALUE in the kernel arguments: it is the same for every lane, so it stays in scalar registers; count == 0 is "off"
 // and the only thing such a kernel reads of it.
+//
+// Coulomb friction, lagged and smoothed (Li et al., "Incremental Potential Contact", 2020, section 5): with the normal force and the tangent
+// plane frozen at a lag position xbar_i,
+//   nbar = grad phi_o(xbar_i),  P = I - nbar nbar^T,  lam = k_o w_i max(0, -phi_o(xbar_i)),  s = P d_i,  y = |s|
+//   D   = sum_o sum_i mu_o lam f0(y)                   f0 = -y^3 / (3 eps^2) + y^2 / eps + eps / 3  (y < eps),  y  otherwise
+//   q_i = sum_o mu_o lam c1 s                          c1 = 2 / eps - y / eps^2  (y < eps),  1 / y  otherwise
+//   H_i = sum_o mu_o lam (c1 P - c2 s s^T)             c2 = 1 / (eps^2 y)  (0 < y < eps),  0  (y == 0),  1 / y^3  otherwise
+// q is the gradient of the convex D and H_i its symmetric positive semi-definite Hessian, with xbar frozen.  The slip source: xbar_i = X_i +
+// ubar_i and d_i = u_i - ubar_i (the solvers and the implicit integrators; ubar null: zero), or, with slip_v set, xbar_i = X_i + u_i and
+// d_i = slip_dt v_i (central differences: the lag state is the current position, the slip that of the half-step velocity).  An obstacle with
+// mu_o == 0, a node out of contact at xbar or at the centre of a ball or cavity gets nothing.  `friction` is set exactly when some
+// mu_o > 0: with it clear no lane executes or loads anything of the term.  friction_force / friction_apply / friction_diagonal /
+// friction_block / friction_potential are called wherever their contact_* twins are.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +42,13 @@ struct ContactTable {
     const double* u;         // [N][dim] displacement (null: zero)
     const double* w;         // [N] node weights (null: 1)
     ContactObstacle o[FH_MAX_OBSTACLES];
+    // friction (fh_set_friction): the coefficients, the slip length, the slip source (see above)
+    double mu[FH_MAX_OBSTACLES];
+    const double* ubar;      // [N][dim] lag displacement (null: zero)
+    const double* slip_v;    // [N][dim] velocity (null: the slip is u - ubar)
+    double slip_dt;
+    double eps;
+    int friction, pad_;      // friction != 0: some mu > 0
 };
 inline ContactTable contact_off() {
     ContactTable t{};
@@ -155,6 +175,120 @@ __host__ __device__ __forceinline__ double contact_gap(const ContactTable& ct, i
     return g;
 }
 
+// f(mu lam, nbar, s, c1, c2) for every obstacle with mu > 0 that node `node` touches at its lag position, in the table's order
+template <int D, class F>
+__host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, int node, F&& f) {
+    double x[D], d[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        const size_t i = (size_t)node * D + c;
+        const double u = ct.u ? ct.u[i] : 0.0;
+        if (ct.slip_v) {
+            x[c] = ct.X[i] + u;
+            d[c] = ct.slip_dt * ct.slip_v[i];
+        } else {
+            const double ub = ct.ubar ? ct.ubar[i] : 0.0;
+            x[c] = ct.X[i] + ub;
+            d[c] = u - ub;
+        }
+    }
+    const double w = ct.w ? ct.w[node] : 1.0;
+    const double inv_eps = 1.0 / ct.eps;
+    for (int o = 0; o < ct.count; ++o) {
+        if (!(ct.mu[o] > 0.0)) continue;
+        const ContactObstacle& ob = ct.o[o];
+        double phi, n[D], inv_r;
+        bool has_n;
+        contact_eval<D>(ob, x, phi, n, has_n, inv_r);
+        if (!(phi < 0.0) || !has_n) continue;
+        double nd = 0.0;
+#pragma unroll
+        for (int c = 0; c < D; ++c) nd += n[c] * d[c];
+        double s[D], y2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            s[c] = d[c] - n[c] * nd;
+            y2 += s[c] * s[c];
+        }
+        const double y = sqrt(y2);
+        double c1, c2;
+        if (y < ct.eps) {   // (never a division by y here: y == 0 gives q = 0 and c2 = 0)
+            c1 = 2.0 * inv_eps - y * inv_eps * inv_eps;
+            c2 = y > 0.0 ? inv_eps * inv_eps / y : 0.0;
+        } else {
+            c1 = 1.0 / y;
+            c2 = c1 * c1 * c1;
+        }
+        f(ct.mu[o] * (ob.k * w * -phi), n, s, y, c1, c2);
+    }
+}
+
+// q[] += q_i
+template <int D>
+__host__ __device__ __forceinline__ void friction_force(const ContactTable& ct, int node, double (&q)[D]) {
+    double t[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) t[c] = 0.0;
+    friction_visit<D>(ct, node, [&](double ml, const double (&)[D], const double (&s)[D], double, double c1, double) {
+        const double m1 = ml * c1;
+#pragma unroll
+        for (int c = 0; c < D; ++c) t[c] += m1 * s[c];
+    });
+#pragma unroll
+    for (int c = 0; c < D; ++c) q[c] += t[c];
+}
+
+// y[] += scale H_i v
+template <int D>
+__host__ __device__ __forceinline__ void friction_apply(const ContactTable& ct, int node, const double (&v)[D], double scale, double (&y)[D]) {
+    double t[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) t[c] = 0.0;
+    friction_visit<D>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+        double nv = 0.0, sv = 0.0;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            nv += n[c] * v[c];
+            sv += s[c] * v[c];
+        }
+#pragma unroll
+        for (int c = 0; c < D; ++c) t[c] += ml * (c1 * (v[c] - n[c] * nv) - c2 * sv * s[c]);
+    });
+#pragma unroll
+    for (int c = 0; c < D; ++c) y[c] += scale * t[c];
+}
+
+// B[][] += H_i
+template <int D>
+__host__ __device__ __forceinline__ void friction_block(const ContactTable& ct, int node, double (&B)[D][D]) {
+    friction_visit<D>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int b = 0; b < D; ++b) B[a][b] += ml * (c1 * ((a == b ? 1.0 : 0.0) - n[a] * n[b]) - c2 * s[a] * s[b]);
+    });
+}
+
+// d[] += diag H_i
+template <int D>
+__host__ __device__ __forceinline__ void friction_diagonal(const ContactTable& ct, int node, double (&d)[D]) {
+    friction_visit<D>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+#pragma unroll
+        for (int c = 0; c < D; ++c) d[c] += ml * (c1 * (1.0 - n[c] * n[c]) - c2 * s[c] * s[c]);
+    });
+}
+
+// the node's share of D
+template <int D>
+__host__ __device__ __forceinline__ double friction_potential(const ContactTable& ct, int node) {
+    double e = 0.0;
+    friction_visit<D>(ct, node, [&](double ml, const double (&)[D], const double (&)[D], double y, double, double) {
+        const double eps = ct.eps;
+        e += ml * (y < eps ? -y * y * y / (3.0 * eps * eps) + y * y / eps + eps / 3.0 : y);
+    });
+    return e;
+}
+
 #ifdef __HIPCC__
 // ---- the stand-alone node kernels: one thread per node
 
@@ -168,15 +302,26 @@ __global__ void __launch_bounds__(256) k_contact_energy(const ContactTable ct, i
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
-// out += g
+// ... and of the friction potential D, the same way
 template <int D>
-__global__ void __launch_bounds__(256) k_contact_force(const ContactTable ct, int num_nodes, double* out) {
+__global__ void __launch_bounds__(256) k_friction_potential(const ContactTable ct, int num_nodes, double* partial) {
+    __shared__ double red[4];
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    const double e = node < num_nodes && ct.friction ? friction_potential<D>(ct, node) : 0.0;
+    const double tot = block_sum_256(e, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+// out += g (parts & 1) + q (parts & 2, while friction is set)
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_force(const ContactTable ct, int num_nodes, double* out, int parts) {
     const int node = blockIdx.x * 256 + threadIdx.x;
     if (node >= num_nodes) return;
     double g[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) g[c] = out[(size_t)node * D + c];
-    contact_force<D>(ct, node, g);
+    if (parts & 1) contact_force<D>(ct, node, g);
+    if ((parts & 2) && ct.friction) friction_force<D>(ct, node, g);
 #pragma unroll
     for (int c = 0; c < D; ++c) out[(size_t)node * D + c] = g[c];
 }
@@ -187,7 +332,7 @@ __global__ void __launch_bounds__(256) k_contact_gap(const ContactTable ct, int 
     if (node < num_nodes) gap[node] = contact_gap<D>(ct, node);
 }
 
-// y += B x 2^-e (xbits: mf_exponent of the operand the element pass of the map saw, may be null: the pass that finishes y multiplies by 2^e)
+// y += (B + H) x 2^-e (xbits: mf_exponent of the operand the element pass of the map saw, may be null: the pass that finishes y multiplies by 2^e)
 template <int D>
 __global__ void __launch_bounds__(256) k_contact_apply(const ContactTable ct, int num_nodes, const double* x, const unsigned long long* xbits,
                                                        double* y) {
@@ -201,11 +346,12 @@ __global__ void __launch_bounds__(256) k_contact_apply(const ContactTable ct, in
         s[c] = 0.0;
     }
     contact_apply<D>(ct, node, v, 1.0, s);
+    if (ct.friction) friction_apply<D>(ct, node, v, 1.0, s);
 #pragma unroll
     for (int c = 0; c < D; ++c) y[(size_t)node * D + c] += ldexp(s[c], -ex);
 }
 
-// diag += diag B
+// diag += diag (B + H)
 template <int D>
 __global__ void __launch_bounds__(256) k_contact_diagonal(const ContactTable ct, int num_nodes, double* diag) {
     const int node = blockIdx.x * 256 + threadIdx.x;
@@ -214,11 +360,12 @@ __global__ void __launch_bounds__(256) k_contact_diagonal(const ContactTable ct,
 #pragma unroll
     for (int c = 0; c < D; ++c) d[c] = diag[(size_t)node * D + c];
     contact_diagonal<D>(ct, node, d);
+    if (ct.friction) friction_diagonal<D>(ct, node, d);
 #pragma unroll
     for (int c = 0; c < D; ++c) diag[(size_t)node * D + c] = d[c];
 }
 
-// B_i added to the diagonal node block of block row `node` of the pattern's CSR values (row S i + a holds cnt blocks of S entries; the
+// B_i + H_i added to the diagonal node block of block row `node` of the pattern's CSR values (row S i + a holds cnt blocks of S entries; the
 // columns of a row are sorted: a binary search finds the node's own)
 template <int D>
 __global__ void __launch_bounds__(256) k_contact_csr(const ContactTable ct, int num_nodes, const unsigned* noff, const unsigned* ncols,
@@ -239,6 +386,7 @@ __global__ void __launch_bounds__(256) k_contact_csr(const ContactTable ct, int 
 #pragma unroll
         for (int b = 0; b < D; ++b) B[a][b] = 0.0;
     contact_block<D>(ct, node, B);
+    if (ct.friction) friction_block<D>(ct, node, B);
 #pragma unroll
     for (int a = 0; a < D; ++a)
 #pragma unroll

@@ -1,5 +1,6 @@
 // Penalty contact with rigid, fixed obstacles (contact_kernels.hpp holds the arithmetic and the node kernels): the obstacle table of the
-// context, the stand-alone launches the routes off the tiles compose, and the C ABI.
+// context, the stand-alone launches the routes off the tiles compose, and the C ABI.  Coulomb friction (fh_set_friction) rides in the same table: the
+// same kernels add q beside g and H beside B while its flag is set, on the tiles and off them, with no launch of its own.
 //
 // Where the term enters ("Penalty contact"): on the element tiles it is FUSED into the node pass that finishes the node sums
 // (k_operator_from_partials, k_newton_from_partials, k_dynamics_from_partials, k_first_order_from_partials take the table by value and call
@@ -24,7 +25,25 @@ ContactTable table_at_u(const fh_ctx* c) {
     t.X = c->verts.p;
     t.u = c->has_u ? c->u.p : nullptr;
     t.w = c->contact_has_w ? c->contact_w.p : nullptr;
+    t.friction = t.friction && !c->friction_suspended;
+    t.ubar = nullptr;
+    t.slip_v = nullptr;
+    if (t.friction) {
+        t.ubar = c->friction_ubar.p;
+        if (c->friction_slip_v) {   // (a central-difference launch)
+            t.slip_v = c->friction_slip_v;
+            t.slip_dt = c->friction_slip_dt;
+            t.eps = c->friction_slip_eps;
+        }
+    }
     return t;
+}
+
+void friction_clear(fh_ctx* c) {
+    if (c->friction_set) ++c->friction_gen;
+    c->friction_set = false;
+    c->contact.friction = 0;
+    for (double& m : c->contact.mu) m = 0.0;
 }
 
 template <class F>
@@ -56,7 +75,25 @@ int contact_blocked(fh_ctx* c, const char* who) {
     return FH_OK;
 }
 
+// (what contact_table(c).friction says, without forming the table)
+bool friction_active(const fh_ctx* c) { return c->contact.count && c->mf_scope == MF_TANGENT && c->contact.friction && !c->friction_suspended; }
+
+// the entries of the lag displacement: one per dof of the mesh (the contact term needs the solution dim to be the geometric one)
+static size_t lag_entries(const fh_ctx* c) { return (size_t)c->ei.d * (size_t)c->N; }
+
+unsigned long long contact_key(const fh_ctx* c) { return (c->contact_gen + c->friction_gen) | (friction_active(c) ? 1ull << 63 : 0ull); }
+
+int friction_lag_to_u(fh_ctx* c, double eps) {
+    const size_t n = lag_entries(c);
+    if (c->has_u) HIP_TRY(c, hipMemcpyAsync(c->friction_ubar.p, c->u.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+    else HIP_TRY(c, hipMemsetAsync(c->friction_ubar.p, 0, sizeof(double) * n, c->stream));
+    c->contact.eps = eps;
+    ++c->friction_gen;
+    return FH_OK;
+}
+
 void contact_clear(fh_ctx* c) {
+    friction_clear(c);
     if (c->contact.count || c->contact_has_w) ++c->contact_gen;
     c->contact = contact_off();
     c->contact_has_w = false;
@@ -65,7 +102,7 @@ void contact_clear(fh_ctx* c) {
 int contact_add_force(fh_ctx* c, double* out_dev) {
     const ContactTable t = contact_table(c);
     if (!t.count || c->N == 0) return FH_OK;
-    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_force<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, out_dev); });
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_force<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, out_dev, 3); });
     HIP_TRY(c, hipGetLastError());
     return FH_OK;
 }
@@ -92,13 +129,17 @@ int contact_add_diagonal(fh_ctx* c, double* diag_dev) {
     return FH_OK;
 }
 
-// E_c of `t` added to *energy: per-workgroup partials in a fixed tree, at most 2048 ordered range sums, the ordered host sum
-static int energy_of(fh_ctx* c, const ContactTable& t, double* energy) {
-    if (!t.count || c->N == 0) return FH_OK;
+// E_c of `t` (friction: its friction potential D) added to *energy: per-workgroup partials in a fixed tree, at most 2048 ordered range
+// sums, the ordered host sum
+static int energy_of(fh_ctx* c, const ContactTable& t, double* energy, bool friction = false) {
+    if (!t.count || c->N == 0 || (friction && !t.friction)) return FH_OK;
     const int count = blocks_of((long long)c->N), ranges = std::min(2048, count);
     DevBuf<double>& part = c->contact_part;
     if (part.n < (size_t)count + (size_t)ranges) HIP_TRY(c, part.alloc((size_t)count + (size_t)ranges));
-    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_energy<d()>), dim3(count), dim3(256), 0, c->stream, t, (int)c->N, part.p); });
+    by_dim(c, [&](auto d) {
+        if (friction) hipLaunchKernelGGL((k_friction_potential<d()>), dim3(count), dim3(256), 0, c->stream, t, (int)c->N, part.p);
+        else hipLaunchKernelGGL((k_contact_energy<d()>), dim3(count), dim3(256), 0, c->stream, t, (int)c->N, part.p);
+    });
     hipLaunchKernelGGL(k_sum_partial_ranges<1>, dim3(ranges), dim3(256), 0, c->stream, part.p, (long long)count, part.p + count);
     HIP_TRY(c, hipGetLastError());
     double e = 0.0;
@@ -153,6 +194,7 @@ int fh_set_obstacles(fh_ctx* c, const fh_obstacle* obstacles, uint64_t count, co
         contact_clear(c);
         return FH_OK;
     }
+    friction_clear(c);   // (the coefficients belong to the obstacle list)
     if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, std::string(who) + ": no finite element mesh set");
     if (c->ei.d != 2 && c->ei.d != 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": the geometric dim must be 2 or 3");
     if (c->ei.d == 2)   // the third components take no part in a plane problem: a normal is normalised over the first two
@@ -198,7 +240,89 @@ int fh_contact_force_dev(fh_ctx* c, double* out_dev) {
     if (rc) return rc;
     const ContactTable t = table_at_u(c);
     if (!t.count || c->N == 0) return FH_OK;
-    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_force<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, out_dev); });
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_force<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, out_dev, 1); });
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_contact_force";
+    return FH_OK;
+}
+
+int fh_set_friction(fh_ctx* c, const double* mu, uint64_t count, double slip_length) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_set_friction";
+    if (count == 0 || !mu) {
+        friction_clear(c);
+        return FH_OK;
+    }
+    if (!c->contact.count) return c->fail(FH_INVALID_STATE, std::string(who) + ": no obstacles set (fh_set_obstacles)");
+    if (count != (uint64_t)c->contact.count) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": count must equal the number of obstacles set");
+    if (!std::isfinite(slip_length) || !(slip_length > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the slip length must be positive and finite");
+    bool any = false;
+    for (uint64_t i = 0; i < count; ++i) {
+        if (!std::isfinite(mu[i]) || mu[i] < 0.0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a friction coefficient is negative or not finite");
+        any = any || mu[i] > 0.0;
+    }
+    const size_t n = lag_entries(c);
+    if (!c->friction_set) {   // the lag state starts at u = 0
+        if (!c->friction_ubar.p || c->friction_ubar.n < n) HIP_TRY(c, c->friction_ubar.alloc(n));
+        HIP_TRY(c, hipMemsetAsync(c->friction_ubar.p, 0, sizeof(double) * n, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    for (int i = 0; i < FH_MAX_OBSTACLES; ++i) c->contact.mu[i] = (uint64_t)i < count ? mu[i] + 0.0 : 0.0;
+    c->contact.eps = slip_length;
+    c->contact.friction = any ? 1 : 0;
+    c->friction_set = true;
+    ++c->friction_gen;
+    return FH_OK;
+}
+
+static int friction_reference(fh_ctx* c, const char* who, const double* ubar, hipMemcpyKind kind) {
+    if (!c->friction_set) return c->fail(FH_INVALID_STATE, std::string(who) + ": no friction set (fh_set_friction)");
+    int rc = standalone_ready(c, who);
+    if (rc) return rc;
+    if (!ubar) {
+        rc = friction_lag_to_u(c, c->contact.eps);
+        if (rc) return rc;
+    } else {
+        HIP_TRY(c, hipMemcpyAsync(c->friction_ubar.p, ubar, sizeof(double) * lag_entries(c), kind, c->stream));
+        ++c->friction_gen;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FH_OK;
+}
+int fh_set_friction_reference(fh_ctx* c, const double* ubar) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    return friction_reference(c, "fh_set_friction_reference", ubar, hipMemcpyHostToDevice);
+}
+int fh_set_friction_reference_dev(fh_ctx* c, const double* ubar_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    return friction_reference(c, "fh_set_friction_reference_dev", ubar_dev, hipMemcpyDeviceToDevice);
+}
+
+int fh_friction_potential(fh_ctx* c, double* potential) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_friction_potential";
+    if (!potential) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    *potential = 0.0;
+    const int rc = standalone_ready(c, who);
+    if (rc) return rc;
+    c->last_kernel = "k_friction_potential";
+    return energy_of(c, table_at_u(c), potential, true);
+}
+
+int fh_friction_force_dev(fh_ctx* c, double* out_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_friction_force_dev";
+    if (!out_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    const int rc = standalone_ready(c, who);
+    if (rc) return rc;
+    const ContactTable t = table_at_u(c);
+    if (!t.friction || c->N == 0) return FH_OK;
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_force<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, out_dev, 2); });
     HIP_TRY(c, hipGetLastError());
     c->last_kernel = "k_contact_force";
     return FH_OK;

@@ -23,12 +23,13 @@ struct fh_dynamics {
     bool has_f = false;
     uint64_t step = 0;                 // steps taken since fh_dynamics_set_state
     // what m (the first five) and a_n (all six; first order: the rate, kept in v) were formed for: struct_gen (operator, table, mask),
-    // topo_gen, geom_gen, density_gen, dirichlet_gen, the u_gen this handle left behind, and the contact_gen of fh_set_obstacles
+    // topo_gen, geom_gen, density_gen, dirichlet_gen, the u_gen this handle left behind, and the contact_gen of fh_set_obstacles with the friction_gen of fh_set_friction (contact_key)
     unsigned long long m_key[5] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
     unsigned long long a_key[7] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
     bool load_changed = true;          // (also: the damping coefficients have changed)
     double eta_m = 0.0, eta_k = 0.0;   // Rayleigh damping C = eta_m M + eta_k T(u) (fh_dynamics_set_damping); (0, 0): every launch as without it
     DevBuf<double> u_ref2;             // implicit schemes with damping: the folded u_ref of the step (k_damping_fold)
+    double eps_v = 0.0;                // friction: the slip velocity (fh_dynamics_set_slip_velocity); 0: the context's slip length as it is
 };
 
 namespace {
@@ -48,7 +49,7 @@ void key_now(const fh_ctx* c, unsigned long long (&k)[7]) {
     k[3] = c->density_gen;
     k[4] = c->dirichlet_gen;
     k[5] = c->u_gen;
-    k[6] = c->contact_gen;
+    k[6] = contact_key(c);
 }
 
 // the handle still belongs to the context's mesh and the context can form M and r
@@ -91,9 +92,11 @@ int add_tangent(fh_dynamics* d, double s, const double* x, double* tmp, double* 
     return FH_OK;
 }
 
-// what the folding of a frozen C into newton_run's arguments cannot express
+// what the folding of a frozen C into newton_run's arguments cannot express, and friction on a first-order handle
 int damping_supported(fh_dynamics* d, const char* who) {
     fh_ctx* c = d->c;
+    if (first_order(d) && friction_active(c))
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": friction is set (fh_set_friction) and a gradient flow has no slip velocity");
     if (d->eta_k == 0.0 || explicit_scheme(d)) return FH_OK;
     if (c->op > FH_LINEAR_ELASTIC)
         return c->fail(FH_UNSUPPORTED, std::string(who) + ": stiffness damping under Newmark or backward Euler covers FH_LAPLACE and FH_LINEAR_ELASTIC only");
@@ -101,6 +104,13 @@ int damping_supported(fh_dynamics* d, const char* who) {
         return c->fail(FH_UNSUPPORTED, std::string(who) + ": stiffness damping under Newmark or backward Euler with obstacles set is not covered");
     return FH_OK;
 }
+
+// a term of the step takes the velocity the handle holds (Rayleigh damping, friction): a_{n+1} of a step is formed on v_h then, and
+// forming it again on v_{n+1} would not repeat it
+bool velocity_term(const fh_dynamics* d) { return d->eta_m != 0.0 || d->eta_k != 0.0 || friction_active(d->c); }
+
+// the slip length of a step with friction: eps_v dt, or the context's own when no slip velocity was given
+double slip_eps(const fh_dynamics* d) { return d->eps_v > 0.0 ? d->eps_v * d->s.dt : d->c->contact.eps; }
 
 int sum_blocks(fh_ctx* c, const double* partial, int count, double* out) { return sum_partials(c, partial, count, 1, out); }
 
@@ -119,9 +129,9 @@ int ensure_lumped(fh_dynamics* d, const char* who) {
     unsigned long long k[7];
     key_now(c, k);
     if (std::equal(k, k + 5, d->m_key)) return FH_OK;
-    // (with damping a_n is not formed again for what the handle itself moves -- remember_u -- and the walk below moves struct_gen on a
+    // (with damping or friction a_n is not formed again for what the handle itself moves -- remember_u -- and the walk below moves struct_gen on a
     // rule-set table: an a_n that is current on entry stays current)
-    const bool a_current = (d->eta_m != 0.0 || d->eta_k != 0.0) && std::equal(k, k + 7, d->a_key) && !d->load_changed;
+    const bool a_current = velocity_term(d) && std::equal(k, k + 7, d->a_key) && !d->load_changed;
     const int n = d->n;
     const std::vector<double> ones((size_t)n, 1.0);
     std::vector<double> h((size_t)n);
@@ -178,6 +188,8 @@ int explicit_launch(fh_dynamics* d, int flags, uint64_t step, uint64_t* stats, i
     fh_ctx* c = d->c;
     const int S = c->S(), n = d->n;
     const DynStep p = step_args(d, flags, step);
+    // friction: the lag state is the u the residual is formed at, the slip dt v of the velocity the handle holds (v_h; v_0 for a_0)
+    const FrictionSlip slip(c, (flags & DYN_ACCEL) && friction_active(c) ? d->v.p : nullptr, d->s.dt, slip_eps(d));
     if (flags & DYN_ACCEL) {
         bool tiles;
         int rc = residual_tiles(d, &tiles);
@@ -244,6 +256,10 @@ int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
         rc = explicit_launch(d, DYN_ACCEL, d->step, stats, nullptr);
         if (rc) return rc;
     } else {   // Newmark: M a_0 = lf_0 f - r(u_0) on the free dofs; backward Euler keeps no a_0 but refuses the same states
+        if (friction_active(c)) {   // (the lag state of a_0 is u_0 itself: no slip, no friction force)
+            rc = friction_lag_to_u(c, slip_eps(d));
+            if (rc) return rc;
+        }
         rc = residual_summed(d);
         if (rc) return rc;
         ++stats[1];
@@ -277,11 +293,11 @@ int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
     return FH_OK;
 }
 
-// a_n belongs to the state the handle has just left behind.  With damping a step's a_{n+1} (formed on v_h) is not what ensure_acceleration
-// would form again for the same state (on v_{n+1}), so nothing the steps themselves moved may make it stale: the walk over the groups of a
+// a_n belongs to the state the handle has just left behind.  With damping or friction (velocity_term) a step's a_{n+1} (formed on v_h)
+// is not what ensure_acceleration would form again for the same state (on v_{n+1}), so nothing the steps themselves moved may make it stale: the walk over the groups of a
 // rule-set table stages every group and moves struct_gen, which without damping only forms the same a_n once more.
 void remember_u(fh_dynamics* d) {
-    if (d->eta_m != 0.0 || d->eta_k != 0.0) key_now(d->c, d->a_key);
+    if (velocity_term(d)) key_now(d->c, d->a_key);   // (with friction the implicit steps move the lag state, and friction_gen, themselves)
     else d->a_key[5] = d->c->u_gen;
 }
 
@@ -333,6 +349,10 @@ int implicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, do
     const double dt = d->s.dt, nb = euler ? 1.0 : d->s.newmark_beta, bdt2 = nb * dt * dt;
     for (uint64_t j = 0; j < num_steps; ++j) {
         const uint64_t g_step = d->step + 1;
+        if (friction_active(c)) {   // the lag state of the step is u_n: a device copy enqueued with the step
+            const int rf = friction_lag_to_u(c, slip_eps(d));
+            if (rf) return rf;
+        }
         hipLaunchKernelGGL(k_newmark_predict, dim3(g), dim3(256), 0, c->stream, n, S, dt, euler ? 0.0 : dt * dt * (0.5 - nb), dmask_of(c), c->u.p,
                            d->v.p, d->a.p, d->u_ref.p, d->u_prev.p);
         HIP_TRY(c, hipGetLastError());
@@ -785,6 +805,16 @@ int fh_dynamics_set_damping(fh_dynamics* d, double eta_mass, double eta_stiffnes
     d->eta_k = eta_stiffness + 0.0;
     return FH_OK;
 }
+int fh_dynamics_set_slip_velocity(fh_dynamics* d, double eps_v) {
+    if (!d) return FH_BAD_ARGUMENT;
+    fh_ctx* c = d->c;
+    const char* who = "fh_dynamics_set_slip_velocity";
+    if (first_order(d)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a first-order problem has no slip velocity");
+    if (!std::isfinite(eps_v) || !(eps_v > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the slip velocity must be positive and finite");
+    if (eps_v != d->eps_v) d->load_changed = true;   // a_n is formed again, as after fh_dynamics_set_load
+    d->eps_v = eps_v;
+    return FH_OK;
+}
 int fh_dynamics_damping(fh_dynamics* d, double* eta_mass, double* eta_stiffness) {
     if (!d) return FH_BAD_ARGUMENT;
     if (first_order(d)) return d->c->fail(FH_BAD_ARGUMENT, "fh_dynamics_damping: a first-order problem has no velocity to damp");
@@ -854,6 +884,7 @@ int fh_dynamics_stable_dt(fh_dynamics* d, uint32_t iterations, double* omega_max
     }
     rc = ensure_lumped(d, who);
     if (rc) return rc;
+    const FrictionOff no_friction(c);   // (the frictionless figure)
     const int n = d->n, S = c->S(), g = blocks_of(n);
     DevBuf<double> x, y;
     HIP_TRY(c, x.alloc((size_t)n));

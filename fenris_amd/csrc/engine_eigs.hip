@@ -345,6 +345,7 @@ int eigs_lowest_dev(fh_ctx* c, uint32_t m32, double shift, int preconditioner, d
                     double* theta, double* residual_norms, uint64_t* stats) {
     const char* who = "fh_eigs_lowest";
     if (stats) std::fill(stats, stats + 4, (uint64_t)0);
+    const FrictionOff no_friction(c);   // (the friction block of fh_set_friction stays out of the pencil)
     int rc = mf_ready(c, who, MF_TANGENT);
     if (rc) return rc;
     if (!X_dev || !theta) return c->fail(FH_BAD_ARGUMENT, "fh_eigs_lowest: null argument");

@@ -499,6 +499,16 @@ struct fh_ctx {
     DevBuf<double> contact_part;       // workgroup partials of E_c and their range sums (kept: no allocation per record)
     bool contact_has_w = false;
     unsigned long long contact_gen = 0;
+    // friction (fh_set_friction): the coefficients, the slip length and the flag live in `contact`; friction_ubar is the lag displacement
+    // (S N doubles, allocated while friction is set), friction_gen counts the calls that change any of it.  friction_slip_v / _dt / _eps: the
+    // slip source of a central-difference launch, set for its duration (FrictionSlip); friction_suspended: the entry points that leave the
+    // term out (FrictionOff).
+    DevBuf<double> friction_ubar;
+    unsigned long long friction_gen = 0;
+    const double* friction_slip_v = nullptr;
+    double friction_slip_dt = 0.0, friction_slip_eps = 0.0;
+    int friction_suspended = 0;
+    bool friction_set = false;         // fh_set_friction has been given coefficients (all zero included: contact.friction stays clear then)
     int mf_scope = 1;   // MF_TANGENT
     fh_mg* mg = nullptr;               // the multigrid hierarchy of FH_PRECOND_MULTIGRID (fh_set_multigrid; not owned)
     fh_amg* amg = nullptr;             // the algebraic hierarchy of FH_PRECOND_AMG (fh_set_amg; not owned)
@@ -669,6 +679,25 @@ int contact_add_apply(fh_ctx* c, const double* x_dev, const unsigned long long* 
 int contact_add_diagonal(fh_ctx* c, double* diag_dev);
 int contact_add_energy(fh_ctx* c, double* energy);
 void contact_clear(fh_ctx* c);
+// friction: whether the tables of contact_table carry the term now; the key of everything it depends on beside u (joins contact_gen in the
+// caches' keys); ubar = the context's u, enqueued (the implicit integrators, at the start of a step) with a new slip length
+bool friction_active(const fh_ctx* c);
+unsigned long long contact_key(const fh_ctx* c);
+int friction_lag_to_u(fh_ctx* c, double eps);
+struct FrictionOff {   // fh_eigs_lowest, fh_dynamics_stable_dt: the map without the friction block
+    fh_ctx* c;
+    explicit FrictionOff(fh_ctx* ctx) : c(ctx) { ++c->friction_suspended; }
+    ~FrictionOff() { --c->friction_suspended; }
+};
+struct FrictionSlip {   // a central-difference launch: the lag state is the current position, the slip dt v, eps as given (v null: nothing)
+    fh_ctx* c;
+    FrictionSlip(fh_ctx* ctx, const double* v, double dt, double eps) : c(ctx) {
+        c->friction_slip_v = v;
+        c->friction_slip_dt = dt;
+        c->friction_slip_eps = eps;
+    }
+    ~FrictionSlip() { c->friction_slip_v = nullptr; }
+};
 struct MfScope {   // the scope of the map for the duration of an entry point
     fh_ctx* c;
     int prev;

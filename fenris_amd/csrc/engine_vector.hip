@@ -573,7 +573,7 @@ static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[8], double
     std::memcpy(&k[4], &alpha, sizeof(double));
     std::memcpy(&k[5], &beta, sizeof(double));
     k[6] = alpha != 0.0 ? c->density_gen : 0;
-    k[7] = contact ? c->contact_gen : 0;
+    k[7] = contact ? contact_key(c) : 0;   // (contact_gen and friction_gen)
 }
 
 // the scale of the Dirichlet rows into c->mf_scale, from the unmodified diagonal (diag_dev) of alpha M + beta T(u)

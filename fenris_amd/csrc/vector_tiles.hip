@@ -567,7 +567,8 @@ __global__ void __launch_bounds__(TS) k_damped_pass_tiled(const KArgs a, const V
 // node pass of the matrix-free operator y = A x: y[S node + c] = sum of the node's partials in ascending order, OVERWRITTEN (not added).
 // dmask (may be null): homogeneous Dirichlet nodes, whose rows hold  scale x  (the element pass saw x with those entries zeroed, so
 // their columns are zero already); the element pass saw x 2^-e (xbits: mf_exponent), the sums are scaled back.  dot_partial (may be null): per workgroup  x . y  over its nodes, in a fixed tree.
-// ct (count 0: off): the penalty contact term of the node, contact_scale B x with the UNSCALED x (contact_kernels.hpp), joins the scaled-back
+// ct (count 0: off): the penalty contact term of the node, contact_scale (B + H) x with the UNSCALED x (contact_kernels.hpp; H: the friction
+// block, while ct.friction is set, here and in the node passes below the friction force q beside g), joins the scaled-back
 // sum before the Dirichlet rows and the dot product are formed; S == 1 has no such term.
 template <int S>
 __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* partial,
@@ -589,6 +590,7 @@ __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, c
         }
         if constexpr (S > 1) {
             if (ct.count) contact_apply<S>(ct, node, xv, contact_scale, acc);   // (the unscaled operand)
+            if (ct.friction) friction_apply<S>(ct, node, xv, contact_scale, acc);
         }
 #pragma unroll
         for (int c = 0; c < S; ++c) {
@@ -724,6 +726,7 @@ __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, con
         const bool fixed = dmask && dmask[node];
         if constexpr (S > 1) {
             if (ct.count) contact_force<S>(ct, node, racc);
+            if (ct.friction) friction_force<S>(ct, node, racc);
         }
 #pragma unroll
         for (int c = 0; c < S; ++c) {
@@ -752,6 +755,7 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
         node_partials_sum<S>(np_off, np_idx, rpart, node, racc);
         if constexpr (S > 1) {
             if (ct.count) contact_force<S>(ct, node, racc);
+            if (ct.friction) friction_force<S>(ct, node, racc);   // (the slip of the velocity the node is about to kick: ct.slip_v is p.v)
         }
         const bool fixed = p.dmask && p.dmask[node];
         const double lf = dyn_load_factor(p);

@@ -155,8 +155,11 @@ class TimeIntegrator:
 
     def with_obstacles(self, obstacles):
         """the rigid obstacles of the penalty contact term (fenris_amd.contact.Obstacles; None: none): their force joins r(u) in every
-        scheme and their energy the stored-energy column of the records; returns self"""
-        return _contact.with_obstacles(self, obstacles)
+        scheme and their energy the stored-energy column of the records; with friction on any of them the handle takes the Obstacles'
+        slip_velocity (the first-order integrators refuse friction); returns self"""
+        _contact.with_obstacles(self, obstacles)
+        _contact.send_slip_velocity(self)
+        return self
 
     def _n(self):
         return self.element_assembler.solution_dim() * self.engine.num_nodes()
@@ -180,6 +183,7 @@ class TimeIntegrator:
             self._h = h
             self._send_load()
             self._send_damping()
+            _contact.send_slip_velocity(self)
         return self._h
 
     def _drop(self):

@@ -998,6 +998,45 @@ int fh_contact_energy(fh_ctx*, double* energy);
 int fh_contact_force_dev(fh_ctx*, double* out_dev);
 int fh_contact_gap_dev(fh_ctx*, double* gap_dev);
 int fh_add_contact_tangent_csr_dev(fh_ctx*, double* values_dev);
+/* ---- Coulomb friction on the obstacles, lagged and smoothed (Li et al., "Incremental Potential Contact", 2020, section 5) -------------
+ * Obstacle o has a coefficient mu_o >= 0 (default 0); the context has a slip length eps > 0 and a lag displacement ubar (S N doubles on the
+ * device, owned by the context; u = 0 until fh_set_friction_reference is called).  With xbar_i = X_i + ubar_i, constants of u:
+ *   nbar = grad phi_o(xbar_i),   P = I - nbar nbar^T,   lam = k_o w_i max(0, -phi_o(xbar_i))
+ * and with the slip s = P (u_i - ubar_i), y = |s|:
+ *   potential  D(u) = sum_o sum_i mu_o lam f0(y),      f0 = -y^3 / (3 eps^2) + y^2 / eps + eps / 3  (y < eps),  y  otherwise
+ *   force      q_i  = sum_o mu_o lam c1 s,             c1 = 2 / eps - y / eps^2  (y < eps),  1 / y  otherwise        (added to r(u) beside g)
+ *   tangent    H_i  = sum_o mu_o lam (c1 P - c2 s s^T), c2 = 1 / (eps^2 y)  (0 < y < eps),  0  (y == 0),  1 / y^3  otherwise
+ * q is the gradient of the convex D and H_i, a block on the diagonal per node beside B_i, its exact symmetric positive semi-definite
+ * Hessian with ubar frozen; |q_i| <= mu_o lam, with equality for y >= eps.  A node out of contact at xbar, or at the centre of a ball or
+ * cavity there, gets nothing from that obstacle.  2-D and 3-D, the elastic operators, as for the normal term.
+ * fh_set_friction: one mu per obstacle set; count == 0 or a null list turns friction off.  FH_BAD_ARGUMENT: a mu that is negative or not
+ *   finite, slip_length <= 0 or not finite, count != the number of obstacles; FH_INVALID_STATE: no obstacles.  fh_set_obstacles and
+ *   fh_set_mesh* clear it.  With friction never set, or with every mu_o == 0, every route computes the bits it computed before.
+ * fh_set_friction_reference(_dev): ubar (S N doubles; NULL: the context's current u).  FH_INVALID_STATE before fh_set_friction.
+ * fh_friction_potential: D at the context's u; fh_friction_force_dev ADDS q into out_dev (S N doubles); fh_add_contact_tangent_csr_dev adds
+ *   B_i + H_i while friction is set.
+ * While friction is set the term travels with the normal term, in the same launches: fh_apply_tangent_dev, fh_tangent_diagonal_dev,
+ *   fh_cg_solve_tangent(_dev) and the shifted family apply T(u) + B(u) + H(u); fh_newton_solve(_dev) solves
+ *   F = alpha M (u - u_ref) + beta (r + g + q - f) with the context's ubar and eps as the caller set them (a quasi-static user moves ubar
+ *   to the converged u between load steps).
+ * FH_DYN_NEWMARK, FH_DYN_BACKWARD_EULER: at the start of step n the handle sets ubar = u_n (a device copy enqueued with the step) and
+ *   eps = eps_v dt (fh_dynamics_set_slip_velocity; without one the context's slip length stays), then runs its one Newton solve; a_0 is
+ *   formed with ubar = u_0, that is without friction force.  The context's ubar and eps are left as the last step set them.
+ * FH_DYN_CENTRAL_DIFFERENCE: the term is evaluated with the current position as the lag state and the slip of the half-step velocity,
+ *   s = P (dt v_h), eps = eps_v dt (a_0: v_0); no lag array is read or written, and q joins r before the acceleration is formed, as the
+ *   stiffness damping does.  On a node of lumped mass m with friction rate c = 2 mu lam / (eps_v m) the step needs
+ *   (omega dt)^2 + 2 c dt <= 4; fh_dynamics_stable_dt stays the frictionless figure.
+ * Left out: fh_eigs_lowest(_dev), fh_dynamics_stable_dt and the operator's entry points (fh_apply_operator_dev, ...) leave the term out;
+ *   fh_first_order_* handles answer FH_UNSUPPORTED from fh_dynamics_step and fh_dynamics_state while any mu_o > 0 (a gradient flow has no
+ *   slip velocity); FH_PRECOND_MULTIGRID stays FH_UNSUPPORTED with obstacles.  The records keep four columns: the dissipated work is not
+ *   recorded.
+ * fh_dynamics_set_slip_velocity: eps_v > 0 and finite, else FH_BAD_ARGUMENT; FH_BAD_ARGUMENT on a handle of fh_first_order_create. */
+int fh_set_friction(fh_ctx*, const double* mu, uint64_t count, double slip_length);
+int fh_set_friction_reference(fh_ctx*, const double* ubar);
+int fh_set_friction_reference_dev(fh_ctx*, const double* ubar_dev);
+int fh_friction_potential(fh_ctx*, double* potential);
+int fh_friction_force_dev(fh_ctx*, double* out_dev);
+int fh_dynamics_set_slip_velocity(fh_dynamics*, double eps_v);
 /* Geometric multigrid for the matrix-free solvers (FH_PRECOND_MULTIGRID of fh_cg_solve_matrix_free, fh_cg_solve_tangent,
  * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity, Jacobi or FH_PRECOND_AMG).  Every level is an
  * ordinary context with its own mesh, operator (Laplace, LinearElastic, NeoHookean or StVK), quadrature, data, density and

@@ -6,12 +6,15 @@
     none      this build, no obstacles
     floor     this build, the half-space z >= -0.005: the bottom layer of nodes, 1 / (cells + 1) of them, is inside it
     sixteen   this build, that floor and 15 balls far away: FH_MAX_OBSTACLES obstacles evaluated at every node
+    floor_mu0   this build, that floor with fh_set_friction given mu = 0 (the friction flag stays clear: the cost must be `floor`'s)
+    floor_mu05  this build, that floor with mu = 0.5, slip velocity 0.05: the friction term in the step's node pass and in the map
+    parent_floor  the parent's library on the `floor` scene (friction never set there: what `floor` and `floor_mu0` are held against)
 
 The variants alternate: every measurement is a fresh child process (one library per process), `--repeats` rounds after one discarded
 warm-up round, so drift of the machine hits every variant alike.  Per variant the median and the spread (min .. max) over the rounds, one
 JSON line, printed and appended to profiles/contact.jsonl.
 
-    python scripts/bench_contact.py [--cells 64] [--steps 200] [--applies 100] [--repeats 5] [--parent-lib PATH]
+    python scripts/bench_contact.py [--cells 64] [--steps 200] [--applies 100] [--repeats 5] [--parent-lib PATH] [--variants a,b,...]
 """
 import argparse
 import json
@@ -43,14 +46,26 @@ def child(variant, cells, steps, applies):
     asm = (fa.ElementEllipticAssemblerBuilder(eng).with_finite_element_space(mesh)
            .with_operator(fa.MaterialEllipticOperator(fa.StableNeoHookeanMaterial())).with_quadrature_table(qt).with_u(np.zeros(n)).build())
     obstacles = None
-    if variant in ("floor", "sixteen"):
+    if variant in ("floor", "sixteen", "floor_mu0", "floor_mu05"):
         k = 1e6 / cells
-        items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k)]
+        if variant == "floor_mu05":
+            items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k, friction=0.5)]
+        else:
+            items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k)]
         if variant == "sixteen":
             items += [fa.Ball((10.0 + j, 10.0, 10.0), 0.5, k) for j in range(15)]
-        obstacles = fa.Obstacles(items)
+        obstacles = fa.Obstacles(items, slip_length=1e-3, slip_velocity=0.05) if variant == "floor_mu05" else fa.Obstacles(items)
     u0 = torch.zeros(n, dtype=torch.float64, device="cuda")
     u0[2::3] = -0.01
+    v0 = torch.zeros_like(u0)
+    if variant.startswith("floor_mu"):
+        v0[0::3] = 1.0     # sliding: the friction force is at its cap on every touching node
+
+    def arm():   # mu = 0 through the C ABI (the Python layer sends fh_set_friction only for a positive coefficient)
+        if variant == "floor_mu0":
+            import ctypes as C
+
+            eng._check(eng._lib.fh_set_friction(eng._h, (C.c_double * 1)(0.0), 1, 1e-3))
     ti = fa.CentralDifference(asm, RHO, 1.0)
     if obstacles is not None:
         ti.with_obstacles(obstacles)
@@ -60,7 +75,8 @@ def child(variant, cells, steps, applies):
     ti = fa.CentralDifference(asm, RHO, dt)
     if obstacles is not None:
         ti.with_obstacles(obstacles)
-    ti.set_state(u0)
+    ti.set_state(u0, v0)
+    arm()
     ti.step(20)   # warm-up: tiles, lumped mass, a_0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -73,6 +89,9 @@ def child(variant, cells, steps, applies):
     t = fa.MatrixFreeTangent(asm)
     if obstacles is not None:
         t.with_obstacles(obstacles)
+    if variant == "floor_mu05":
+        t.with_friction_reference(u0)     # the lag state: the shifted u
+    arm()
     x = torch.rand(n, dtype=torch.float64, device="cuda")
     y = torch.empty_like(x)
     for _ in range(10):
@@ -99,20 +118,23 @@ def main():
     ap.add_argument("--applies", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--variants", default=None, help="comma-separated subset of the variants, in the order they alternate")
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
     if a.child:
         child(a.child, a.cells, a.steps, a.applies)
         return
-    variants = (["parent"] if a.parent_lib else []) + ["none", "floor", "sixteen"]
+    variants = (["parent", "parent_floor"] if a.parent_lib else []) + ["none", "floor", "sixteen", "floor_mu0", "floor_mu05"]
+    if a.variants:
+        variants = [v for v in a.variants.split(",") if v in variants]
     rows = {v: [] for v in variants}
     for rnd in range(a.repeats + 1):
         for v in variants:
             env = dict(os.environ)
             env.pop("FENRIS_HIP_LIB", None)
-            if v == "parent":
+            if v.startswith("parent"):
                 env["FENRIS_HIP_LIB"] = os.path.abspath(a.parent_lib)
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", "none" if v == "parent" else v, "--cells", str(a.cells), "--steps", str(a.steps),
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", {"parent": "none", "parent_floor": "floor"}.get(v, v), "--cells", str(a.cells), "--steps", str(a.steps),
                    "--applies", str(a.applies)]
             out = subprocess.run(cmd, env=env, check=True, capture_output=True, text=True, timeout=600).stdout.strip().splitlines()[-1]
             if rnd > 0:   # (round 0 warms the machine up)
