@@ -25,7 +25,7 @@ from .interpolate import FixedInterpolator, SpatiallyIndexed, ValuesOrGradients
 from .multigrid import GeometricMultigrid
 from .dynamics import (BackwardEuler, CentralDifference, DynamicsError, DynamicsRecord, FirstOrderIntegrator, FirstOrderRecord, ForwardEuler, Newmark,
                        RayleighDamping, RungeKuttaLegendre, ThetaMethod, TimeIntegrator)
-from .contact import Ball, Cavity, Contact, HalfSpace, Obstacles
+from .contact import Ball, Cavity, Contact, HalfSpace, ObstaclePath, Obstacles
 from .eigen import EigenResult, EigenSolveError, MatrixFreeEigensolver
 from .recovery import Recovery
 from .refinement import (Transfer, permute_transfer, refine_uniformly, refine_uniformly_repeat, refine_uniformly_repeat_with_transfers,

@@ -206,6 +206,13 @@ _SIGS = {
     "fh_friction_potential": (C.c_int, [C.c_void_p, f64p]),
     "fh_friction_force_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_dynamics_set_slip_velocity": (C.c_int, [C.c_void_p, C.c_double]),
+    "fh_dynamics_set_boundary_motion": (C.c_int, [C.c_void_p, f64p, f64p, C.c_uint64]),
+    "fh_dynamics_set_boundary_motion_dev": (C.c_int, [C.c_void_p, C.c_void_p, f64p, C.c_uint64]),
+    "fh_set_obstacle_paths":(C.c_int, [C.c_void_p, u64p, f64p, f64p]),
+    "fh_set_obstacle_time": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "fh_obstacle_count": (C.c_int, [C.c_void_p, u64p]),
+    "fh_obstacle_offsets": (C.c_int, [C.c_void_p, f64p, f64p]),
+    "fh_contact_resultants": (C.c_int, [C.c_void_p, f64p, f64p]),
     "fh_mg_create": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(u64p), C.POINTER(u64p), C.POINTER(f64p),
                                C.POINTER(C.c_void_p)]),
     "fh_mg_destroy": (None, [C.c_void_p]),

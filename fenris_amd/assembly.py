@@ -518,6 +518,16 @@ class Engine:
 
         set_obstacles(self, obstacles)
 
+    def set_obstacle_time(self, t, t_lag=None):
+        """the contact clock of obstacles that move along a path (fenris_amd.contact.ObstaclePath): they stand at d(t), and the friction slip
+        is taken relative to their displacement since t_lag (None: t, no displacement).  A solver or tangent whose obstacles are bound
+        (with_obstacles) keeps the clock: when it has to hand its obstacles to the engine again, because another object used the engine in
+        between, the clock goes with them.  Engine.set_obstacles and with_obstacles return it to (0, 0); the time integrators drive it
+        themselves"""
+        from .contact import set_obstacle_time
+
+        set_obstacle_time(self, t, t_lag)
+
     # matrix-free operator (FH_LAPLACE, FH_LINEAR_ELASTIC): no pattern, no values
     def set_operator_dirichlet_nodes(self, nodes):
         self._mf_bound = None   # (MatrixFreeOperator: no operator's nodes are bound any more)

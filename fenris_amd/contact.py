@@ -1,4 +1,4 @@
-"""Penalty contact with rigid, fixed obstacles (fh_set_obstacles and the fh_contact_* terms of include/fenris_hip.h).
+"""Penalty contact with rigid obstacles, fixed or translating along a path (fh_set_obstacles and the fh_contact_* terms of include/fenris_hip.h).
 
     floor = HalfSpace(point=(0, 0, 0), normal=(0, 0, 1), stiffness=1e4)
     newton = MatrixFreeNewton(asm).with_dirichlet_nodes(top).with_obstacles(Obstacles([floor]))
@@ -15,6 +15,12 @@ displacement ubar, where the friction force is the gradient of a convex potentia
 `with_friction_reference(ubar)` on MatrixFreeNewton, MatrixFreeTangent and MatrixFreeShiftedTangent sets ubar (a quasi-static user moves it
 to the converged u between load steps); Newmark and BackwardEuler set ubar = u_n at the start of every step, CentralDifference takes the
 current position and the slip of the half-step velocity.  The first-order integrators refuse friction.
+
+Moving obstacles (fh_set_obstacle_paths): an obstacle takes `path=ObstaclePath(times, offsets)`, a piecewise-linear translation of its
+point in time, constant before the first knot and after the last.  The second-order time integrators drive the contact clock themselves
+(step n + 1 sees the obstacle at t_{n+1} and, for friction, its displacement since t_n); a solver's user calls
+`Engine.set_obstacle_time(t, t_lag)`.  The slip of the friction term is taken relative to the obstacle: a node that moves with it feels no
+friction.  The first-order integrators refuse paths.  `Contact.resultants()` gives the force the body exerts on each obstacle.
 
 `with_obstacles` on MatrixFreeTangent, MatrixFreeShiftedTangent, MatrixFreeNewton, the time integrators and MatrixFreeEigensolver makes
 the obstacles belong to that object: they are handed to the engine before every use, as its Dirichlet nodes are.  An object that was never
@@ -44,12 +50,67 @@ def _vec3(v, name):
     return out
 
 
+class ObstaclePath:
+    """The translation d(t) of an obstacle: piecewise linear through the knots (times[k], offsets[k]), times strictly increasing, constant
+    before the first knot and after the last.  `offset(t)` is fh_set_obstacle_paths' formula in pure Python: in a segment, with
+    w = (t - t_k) / (t_{k+1} - t_k), d = fma(w, d_{k+1} - d_k, d_k) per component"""
+
+    def __init__(self, times, offsets):
+        self.times = np.ascontiguousarray(np.asarray(times, dtype=np.float64).ravel()).copy()
+        off = np.asarray(offsets, dtype=np.float64)
+        off = off.reshape(len(self.times), -1) if off.size else off.reshape(0, 3)
+        if off.shape[1] not in (2, 3):
+            raise ValueError("offsets must have 2 or 3 components per knot")
+        self.offsets = np.zeros((len(self.times), 3))
+        self.offsets[:, :off.shape[1]] = off
+        if not (np.all(np.isfinite(self.times)) and np.all(np.isfinite(self.offsets))):
+            raise ValueError("the knots of a path must be finite")
+        if np.any(np.diff(self.times) <= 0.0):
+            raise ValueError("the knot times of a path must be strictly increasing")
+
+    @classmethod
+    def constant_velocity(cls, velocity, t_end):
+        """from rest at the origin at t = 0 to velocity * t_end at t_end"""
+        v = _vec3(velocity, "velocity")
+        return cls([0.0, float(t_end)], [np.zeros(3), v * float(t_end)])
+
+    def __len__(self):
+        return len(self.times)
+
+    def offset(self, t):
+        T, O = self.times, self.offsets
+        if len(T) == 0:
+            return np.zeros(3)
+        t = float(t)
+        if not t > T[0]:
+            return O[0].copy()
+        if not t < T[-1]:
+            return O[-1].copy()
+        k = int(np.searchsorted(T, t, side="right")) - 1   # T[k] <= t < T[k + 1]
+        w = (t - T[k]) / (T[k + 1] - T[k])
+        return np.array([_fma(w, O[k + 1, a] - O[k, a], O[k, a]) for a in range(3)])
+
+
+def _fma(a, b, c):
+    """a b + c rounded once (math.fma where Python has it; else exactly, through rationals)"""
+    import math
+
+    if hasattr(math, "fma"):
+        return math.fma(a, b, c)
+    from fractions import Fraction
+
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
 class _Obstacle:
     kind = -1
 
-    def __init__(self, point, normal, radius, stiffness, friction=0.0):
+    def __init__(self, point, normal, radius, stiffness, friction=0.0, path=None):
         self.point, self.normal = _vec3(point, "point"), _vec3(normal, "normal")
         self.radius, self.stiffness, self.friction = float(radius), float(stiffness), float(friction)
+        if path is not None and not isinstance(path, ObstaclePath):
+            raise TypeError("path must be an ObstaclePath")
+        self.path = path
 
     def _fill(self, o):
         o.kind, o.stiffness, o.radius = self.kind, self.stiffness, self.radius
@@ -61,24 +122,24 @@ class HalfSpace(_Obstacle):
     """phi(x) = (x - point) . n with n = normal / |normal| (fenris-geometry primitives/half_space.rs): the body stays where phi > 0"""
     kind = OBSTACLE_HALF_SPACE
 
-    def __init__(self, point, normal, stiffness, friction=0.0):
-        super().__init__(point, normal, 0.0, stiffness, friction)
+    def __init__(self, point, normal, stiffness, friction=0.0, path=None):
+        super().__init__(point, normal, 0.0, stiffness, friction, path)
 
 
 class Ball(_Obstacle):
     """phi(x) = |x - centre| - radius (sdf.rs circle, primitives/ball.rs): the body stays outside"""
     kind = OBSTACLE_BALL
 
-    def __init__(self, centre, radius, stiffness, friction=0.0):
-        super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness, friction)
+    def __init__(self, centre, radius, stiffness, friction=0.0, path=None):
+        super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness, friction, path)
 
 
 class Cavity(_Obstacle):
     """phi(x) = radius - |x - centre|: the body stays inside"""
     kind = OBSTACLE_CAVITY
 
-    def __init__(self, centre, radius, stiffness, friction=0.0):
-        super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness, friction)
+    def __init__(self, centre, radius, stiffness, friction=0.0, path=None):
+        super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness, friction, path)
 
 
 class Obstacles:
@@ -93,6 +154,9 @@ class Obstacles:
 
     def __len__(self):
         return len(self.obstacles)
+
+    def has_paths(self):
+        return any(getattr(o, "path", None) is not None and len(o.path) for o in self.obstacles)
 
     def has_friction(self):
         return any(getattr(o, "friction", 0.0) > 0.0 for o in self.obstacles)
@@ -126,17 +190,39 @@ def set_obstacles(engine, obstacles, dt=None):
     if eps is not None:
         mu = np.array([getattr(o, "friction", 0.0) for o in obstacles.obstacles], dtype=np.float64)
         engine._check(engine._lib.fh_set_friction(engine._h, _ffi.fp(mu), n, eps))
+    if obstacles.has_paths():   # (after the obstacles, which clear them)
+        paths = [getattr(o, "path", None) for o in obstacles.obstacles]
+        begin = np.zeros(n + 1, dtype=np.uint64)
+        begin[1:] = np.cumsum([0 if q is None else len(q) for q in paths])
+        times = np.ascontiguousarray(np.concatenate([q.times for q in paths if q is not None]))
+        offsets = np.ascontiguousarray(np.concatenate([q.offsets.ravel() for q in paths if q is not None]))
+        engine._check(engine._lib.fh_set_obstacle_paths(engine._h, _ffi.up(begin), _ffi.fp(times), _ffi.fp(offsets)))
+    return obstacles
+
+
+def set_obstacle_time(engine, t, t_lag=None):
+    """Engine.set_obstacle_time: the contact clock (fh_set_obstacle_time); t_lag None: t.  The object whose obstacles are bound keeps the
+    clock, so that bind_obstacles can send it again with them (the time integrators drive the clock themselves and keep none)"""
+    clock = (float(t), float(t if t_lag is None else t_lag))
+    engine._check(engine._lib.fh_set_obstacle_time(engine._h, *clock))
+    owner = getattr(engine, "_contact_bound", None)
+    if owner is not None and getattr(owner, "dt", None) is None:
+        owner._contact_clock = clock
 
 
 def bind_obstacles(obj, force=False):
-    """the `_bind` step of the matrix-free objects: hand the object's obstacles to its engine unless it used the engine last"""
+    """the `_bind` step of the matrix-free objects: hand the object's obstacles to its engine unless it used the engine last.  The contact
+    clock Engine.set_obstacle_time gave while they were bound goes with them again (fh_set_obstacles alone returns it to (0, 0))"""
     if not getattr(obj, "_owns_obstacles", False):
         if getattr(obj.engine, "_contact_bound", None) is not None:   # another object's obstacles: not this one's to solve with
             set_obstacles(obj.engine, None)
         return
     if force or getattr(obj.engine, "_contact_bound", None) is not obj:
-        set_obstacles(obj.engine, obj._obstacles, getattr(obj, "dt", None))
+        clock = getattr(obj, "_contact_clock", None)
+        sent = set_obstacles(obj.engine, obj._obstacles, getattr(obj, "dt", None))
         obj.engine._contact_bound = obj
+        if clock is not None and len(sent) and sent.has_paths():
+            obj.engine._check(obj.engine._lib.fh_set_obstacle_time(obj.engine._h, *clock))
         _send_friction_reference(obj)
 
 
@@ -182,6 +268,7 @@ def with_obstacles(obj, obstacles):
     """the body of `with_obstacles(obstacles)` of those objects (None: none); returns obj"""
     obj._obstacles = obstacles
     obj._owns_obstacles = True
+    obj._contact_clock = None   # (new obstacles: the clock starts at (0, 0), as after Engine.set_obstacles)
     bind_obstacles(obj, force=True)
     return obj
 
@@ -224,6 +311,29 @@ class Contact:
             out = torch.zeros(self._dim() * self.engine.num_nodes(), dtype=torch.float64, device=f"cuda:{self.engine.device}")
         self.engine._check(self.engine._lib.fh_friction_force_dev(self.engine._h, C.c_void_p(out.data_ptr())))
         return out if device else out.cpu().numpy()
+
+    def _count(self):
+        """the number of obstacles that stand in the engine (fh_obstacle_count), whoever set them"""
+        count = C.c_uint64(0)
+        self.engine._check(self.engine._lib.fh_obstacle_count(self.engine._h, C.byref(count)))
+        return int(count.value)
+
+    def resultants(self):
+        """(normal, friction): per obstacle the share R_o of g -- the force the body exerts on the obstacle -- and the share Q_o of q (zeros
+        without friction), each of shape (count, dim), at the engine's u over every node"""
+        count = self._count()
+        normal, friction = np.zeros(3 * MAX_OBSTACLES), np.zeros(3 * MAX_OBSTACLES)
+        self.engine._check(self.engine._lib.fh_contact_resultants(self.engine._h, _ffi.fp(normal), _ffi.fp(friction)))
+        d = self._dim()
+        return normal[:3 * count].reshape(count, 3)[:, :d].copy(), friction[:3 * count].reshape(count, 3)[:, :d].copy()
+
+    def obstacle_offsets(self):
+        """(current, lag): d_o(t) and d_o(t_lag) of the contact clock per obstacle, each of shape (count, dim)"""
+        count = self._count()
+        cur, lag = np.zeros(3 * MAX_OBSTACLES), np.zeros(3 * MAX_OBSTACLES)
+        self.engine._check(self.engine._lib.fh_obstacle_offsets(self.engine._h, _ffi.fp(cur), _ffi.fp(lag)))
+        d = self._dim()
+        return cur[:3 * count].reshape(count, 3)[:, :d].copy(), lag[:3 * count].reshape(count, 3)[:, :d].copy()
 
     def gap(self, device=False):
         """per node the smallest phi over the obstacles (negative: penetration)"""

@@ -1,4 +1,4 @@
-// Penalty contact with rigid, fixed obstacles: the arithmetic of the term, in one place, and the stand-alone node kernels.
+// Penalty contact with rigid obstacles, fixed or translating along a path: the arithmetic of the term, in one place, and the stand-alone node kernels.
 //   E_c = sum_o sum_i (k_o w_i / 2) p^2,  p = min(0, phi_o(x_i)),  x_i = X_i + u_i
 //   g_i = sum_o k_o w_i p n                                  n = grad phi_o(x_i)
 //   B_i = sum_o k_o w_i ([phi_o < 0] n n^T + c (I - n n^T))    c = -p / |y| for the cavity, 0 otherwise (max-PSD of p Hess phi)
@@ -16,7 +16,8 @@
 //   H_i = sum_o mu_o lam (c1 P - c2 s s^T)             c2 = 1 / (eps^2 y)  (0 < y < eps),  0  (y == 0),  1 / y^3  otherwise
 // q is the gradient of the convex D and H_i its symmetric positive semi-definite Hessian, with xbar frozen.  The slip source: xbar_i = X_i +
 // ubar_i and d_i = u_i - ubar_i (the solvers and the implicit integrators; ubar null: zero), or, with slip_v set, xbar_i = X_i + u_i and
-// d_i = slip_dt v_i (central differences: the lag state is the current position, the slip that of the half-step velocity).  An obstacle with
+// d_i = slip_dt v_i (central differences: the lag state is the current position, the slip that of the half-step velocity).  An obstacle
+// that moves along a path (fh_set_obstacle_paths) carries its displacement over the lag interval, c_o: the slip is s = P (d_i - c_o).  An obstacle with
 // mu_o == 0, a node out of contact at xbar or at the centre of a ball or cavity gets nothing.  `friction` is set exactly when some
 // mu_o > 0: with it clear no lane executes or loads anything of the term.  friction_force / friction_apply / friction_diagonal /
 // friction_block / friction_potential are called wherever their contact_* twins are.
@@ -29,11 +30,12 @@
 namespace fenris_hip {
 
 struct ContactObstacle {
-    double p[3];      // a point of the plane / the centre
+    double p[3];      // a point of the plane / the centre, at the contact clock's current time (fh_set_obstacle_time)
     double n[3];      // half-space: the unit normal
     double radius;
     double k;
     int kind, pad_;
+    double c[3];      // c_o = d_o(t) - d_o(t_lag): the obstacle's own displacement over the lag interval (zero without a path)
 };
 
 struct ContactTable {
@@ -54,6 +56,11 @@ inline ContactTable contact_off() {
     ContactTable t{};
     return t;
 }
+// the table travels in the kernel arguments beside the node pass's own (the largest: k_operator_from_partials, 96 bytes, and
+// k_dynamics_from_partials with its DynStep; vector_tiles.hip holds both under NODE_PASS_ARG_BYTES): the whole block stays under the 4 KB
+// a kernel's arguments may take
+constexpr size_t NODE_PASS_ARG_BYTES = 512, KERNEL_ARG_LIMIT = 4096;
+static_assert(sizeof(ContactTable) + NODE_PASS_ARG_BYTES <= KERNEL_ARG_LIMIT, "the contact table no longer fits the kernel arguments");
 
 // phi, n = grad phi (has_n false: the centre of a ball or cavity, where the gradient does not exist) and 1 / |y| (0 for the half-space)
 template <int D>
@@ -86,14 +93,15 @@ __host__ __device__ __forceinline__ void contact_eval(const ContactObstacle& ob,
     for (int c = 0; c < D; ++c) n[c] = has_n ? sign * y[c] * inv_r : 0.0;
 }
 
-// f(k w, phi, n, has_n, c) for every obstacle at node `node`, in the table's order (c: the coefficient of I - n n^T in B)
+// f(k w, phi, n, has_n, c) for every obstacle at node `node`, in the table's order (c: the coefficient of I - n n^T in B); only >= 0: that
+// obstacle alone (the resultants)
 template <int D, class F>
-__host__ __device__ __forceinline__ void contact_visit(const ContactTable& ct, int node, F&& f) {
+__host__ __device__ __forceinline__ void contact_visit(const ContactTable& ct, int node, F&& f, int only = -1) {
     double x[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) x[c] = ct.X[(size_t)node * D + c] + (ct.u ? ct.u[(size_t)node * D + c] : 0.0);
     const double w = ct.w ? ct.w[node] : 1.0;
-    for (int o = 0; o < ct.count; ++o) {
+    for (int o = only < 0 ? 0 : only; o < (only < 0 ? ct.count : only + 1); ++o) {
         const ContactObstacle& ob = ct.o[o];
         double phi, n[D], inv_r;
         bool has_n;
@@ -175,9 +183,11 @@ __host__ __device__ __forceinline__ double contact_gap(const ContactTable& ct, i
     return g;
 }
 
-// f(mu lam, nbar, s, c1, c2) for every obstacle with mu > 0 that node `node` touches at its lag position, in the table's order
+// f(mu lam, nbar, s, y, c1, c2) for every obstacle with mu > 0 that node `node` touches at its lag position, in the table's order.  A moving
+// obstacle (c_o != 0): the slip is taken relative to the obstacle, s = P (d_i - c_o), and with the lag displacement as the slip source the
+// obstacle stands at its lag position p - c_o; with slip_v the lag configuration is the current one, obstacle included.
 template <int D, class F>
-__host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, int node, F&& f) {
+__host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, int node, F&& f, int only = -1) {
     double x[D], d[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) {
@@ -194,20 +204,26 @@ __host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, 
     }
     const double w = ct.w ? ct.w[node] : 1.0;
     const double inv_eps = 1.0 / ct.eps;
-    for (int o = 0; o < ct.count; ++o) {
+    for (int o = only < 0 ? 0 : only; o < (only < 0 ? ct.count : only + 1); ++o) {
         if (!(ct.mu[o] > 0.0)) continue;
-        const ContactObstacle& ob = ct.o[o];
+        ContactObstacle ob = ct.o[o];
+        double rel[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            rel[c] = d[c] - ob.c[c];
+            if (!ct.slip_v) ob.p[c] -= ob.c[c];
+        }
         double phi, n[D], inv_r;
         bool has_n;
         contact_eval<D>(ob, x, phi, n, has_n, inv_r);
         if (!(phi < 0.0) || !has_n) continue;
         double nd = 0.0;
 #pragma unroll
-        for (int c = 0; c < D; ++c) nd += n[c] * d[c];
+        for (int c = 0; c < D; ++c) nd += n[c] * rel[c];
         double s[D], y2 = 0.0;
 #pragma unroll
         for (int c = 0; c < D; ++c) {
-            s[c] = d[c] - n[c] * nd;
+            s[c] = rel[c] - n[c] * nd;
             y2 += s[c] * s[c];
         }
         const double y = sqrt(y2);
@@ -265,7 +281,10 @@ __host__ __device__ __forceinline__ void friction_block(const ContactTable& ct, 
 #pragma unroll
         for (int a = 0; a < D; ++a)
 #pragma unroll
-            for (int b = 0; b < D; ++b) B[a][b] += ml * (c1 * ((a == b ? 1.0 : 0.0) - n[a] * n[b]) - c2 * s[a] * s[b]);
+            for (int b = 0; b < D; ++b) {   // (the upper triangle's expression on both sides: symmetric to the bit, the diagonal friction_diagonal's)
+                const int lo = a < b ? a : b, hi = a < b ? b : a;
+                B[a][b] += ml * (c1 * ((a == b ? 1.0 : 0.0) - n[lo] * n[hi]) - c2 * s[lo] * s[hi]);
+            }
     });
 }
 
@@ -391,6 +410,46 @@ __global__ void __launch_bounds__(256) k_contact_csr(const ContactTable ct, int 
     for (int a = 0; a < D; ++a)
 #pragma unroll
         for (int b = 0; b < D; ++b) vals[(size_t)D * D * r0 + (size_t)a * D * cnt + (size_t)D * lo + b] += B[a][b];
+}
+
+// the force resultants per obstacle (fh_contact_resultants): R_o = sum_i k_o w_i p n, obstacle o's share of g, and Q_o = sum_i mu_o lam c1 s,
+// its share of q (zeros while friction is clear).  One thread per node; per obstacle and component the lanes of a wavefront are summed by
+// xor-shuffles (the tree of block_sum_256), the wavefront sums go to LDS, and after ONE barrier thread k < 6 count adds the four of entry k
+// as (w0 + w1) + (w2 + w3) and writes it: row blockIdx.x of `partial` holds 6 count doubles, [o][R_x R_y R_z Q_x Q_y Q_z] (2-D: the third
+// components are zero).  The caller sums the rows in index order (sum_partials): no atomics, two calls give the same bits.
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_resultants(const ContactTable ct, int num_nodes, double* partial) {
+    __shared__ double red[FH_MAX_OBSTACLES * 6][4];
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = 0; o < ct.count; ++o) {   // (count is uniform: every lane takes part in every shuffle)
+        double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (node < num_nodes) {
+            contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double) {
+                if (!(phi < 0.0) || !has_n) return;
+                const double kp = kw * phi;
+#pragma unroll
+                for (int c = 0; c < D; ++c) v[c] += kp * n[c];
+            }, o);
+            if (ct.friction)
+                friction_visit<D>(ct, node, [&](double ml, const double (&)[D], const double (&s)[D], double, double c1, double) {
+                    const double m1 = ml * c1;
+#pragma unroll
+                    for (int c = 0; c < D; ++c) v[3 + c] += m1 * s[c];
+                }, o);
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            double t = v[k];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+            if (lane == 0) red[o * 6 + k][wave] = t;
+        }
+    }
+    __syncthreads();
+    const int K = 6 * ct.count;
+    if ((int)threadIdx.x < K)
+        partial[(size_t)blockIdx.x * K + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 #endif
 

@@ -47,27 +47,35 @@ static __global__ void __launch_bounds__(256) k_theta_load(int n, const double* 
 }
 
 // Newmark predictor: u_ref = u + dt v + dt^2 (1/2 - beta) a (backward Euler: c2 = 0), and the Newton guess: the context's u takes u_ref on
-// the free dofs and keeps its Dirichlet entries; u_prev keeps u_n
+// the free dofs and keeps its Dirichlet entries; u_prev keeps u_n.  bm_dir (may be null; backward Euler only): the Dirichlet dofs follow a
+// prescribed motion -- u_ref as on a free dof, and the guess takes the prescribed u_{n+1} = fma(bm_g, dir, u_0), which Newton then holds
 static __global__ void __launch_bounds__(256) k_newmark_predict(int n, int S, double dt, double c2, const unsigned char* dmask, double* u,
-                                                                const double* v, const double* a, double* u_ref, double* u_prev) {
+                                                                const double* v, const double* a, double* u_ref, double* u_prev,
+                                                                const double* bm_dir, const double* bm_u0, double bm_g) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double un = u[i];
     u_prev[i] = un;
     const bool fixed = dmask && dmask[i / S];
+    if (fixed && bm_dir) {
+        u_ref[i] = fma(c2, a[i], fma(dt, v[i], un));
+        u[i] = fma(bm_g, bm_dir[i], bm_u0[i]);
+        return;
+    }
     const double ur = fixed ? un : fma(c2, a[i], fma(dt, v[i], un));
     u_ref[i] = ur;
     u[i] = ur;
 }
 
 // Newmark corrector on the solved u: a_new = (u - u_ref) inv_bdt2, v += dt ((1 - gamma) a + gamma a_new); backward Euler (euler != 0):
-// v = (u - u_prev) / dt, a = (v - v_old) / dt.  Dirichlet dofs: v = a = 0.
+// v = (u - u_prev) / dt, a = (v - v_old) / dt.  Dirichlet dofs: v = a = 0, or with `moved` (a prescribed boundary motion, backward Euler)
+// the kinematics of a free dof.
 static __global__ void __launch_bounds__(256) k_newmark_correct(int n, int S, int euler, double dt, double inv_bdt2, double gamma,
                                                                 const unsigned char* dmask, const double* u, const double* u_ref,
-                                                                const double* u_prev, double* v, double* a) {
+                                                                const double* u_prev, double* v, double* a, int moved) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    if (dmask && dmask[i / S]) {
+    if (!moved && dmask && dmask[i / S]) {
         v[i] = 0.0;
         a[i] = 0.0;
         return;

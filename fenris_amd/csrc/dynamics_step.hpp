@@ -26,6 +26,12 @@ struct DynStep {
     double* ke_partial;         // DYN_STORE: one partial per workgroup
     int flags;
     double eta_m = 0.0;         // Rayleigh mass damping (fh_dynamics_set_damping); 0: the arithmetic of the undamped step, bit for bit
+    // prescribed motion of the Dirichlet dofs (fh_dynamics_set_boundary_motion; bm_dir null: they are held): direction and the u_0 of
+    // fh_dynamics_set_state, S N each, and for the DYN_ADVANCE of this launch, from step k to k + 1, g_{k+1} - g_0 and (g_{k+1} - g_k) / dt,
+    // both formed on the host
+    const double* bm_dir = nullptr;
+    const double* bm_u0 = nullptr;
+    double bm_g = 0.0, bm_rate = 0.0;
 };
 
 template <class P>   // (DynStep, or FoStage below)
@@ -46,6 +52,15 @@ __device__ __forceinline__ double dyn_accel_damped(double lf, double f, double r
 
 // one dof of a launch: r is read only with DYN_ACCEL; returns the dof's m v^2 (DYN_STORE, else 0)
 __device__ __forceinline__ double dyn_dof(const DynStep& p, size_t i, bool fixed, double lf, double r) {
+    if (fixed && p.bm_dir) {   // moved along its prescribed path: u a pure function of the step, v the half-step velocity of the boundary
+        if (p.flags & DYN_ADVANCE) {
+            const double dir = p.bm_dir[i];
+            p.u[i] = fma(p.bm_g, dir, p.bm_u0[i]);
+            p.v[i] = p.bm_rate * dir;
+        }
+        if (p.flags & (DYN_STORE | DYN_ACCEL)) p.a[i] = 0.0;   // (DYN_STORE keeps v; the kinetic energy counts the free dofs only)
+        return 0.0;
+    }
     if (fixed) {   // held at the u of fh_dynamics_set_state: u is not touched
         if (p.flags & (DYN_STORE | DYN_ADVANCE)) p.v[i] = 0.0;
         if (p.flags & (DYN_STORE | DYN_ACCEL)) p.a[i] = 0.0;

@@ -1,4 +1,4 @@
-// Penalty contact with rigid, fixed obstacles (contact_kernels.hpp holds the arithmetic and the node kernels): the obstacle table of the
+// Penalty contact with rigid obstacles, fixed or translating along a path (contact_kernels.hpp holds the arithmetic and the node kernels): the obstacle table of the
 // context, the stand-alone launches the routes off the tiles compose, and the C ABI.  Coulomb friction (fh_set_friction) rides in the same table: the
 // same kernels add q beside g and H beside B while its flag is set, on the tiles and off them, with no launch of its own.
 //
@@ -9,9 +9,14 @@
 // to it before the pass that finishes it (k_contact_force behind the node sums of r(u); k_contact_apply before k_mf_finish /
 // k_mf_shift_combine; k_contact_diagonal behind the diagonal's sums, once per solve).  Nothing here waits for the device except the energy,
 // which hands one double back; nothing uses atomics; the energy partials are summed in a fixed order.
+//
+// Moving obstacles (fh_set_obstacle_paths, fh_set_obstacle_time): the context keeps the obstacles where fh_set_obstacles put them, the knots
+// of their paths and a clock of two times; the offsets d_o(t) and d_o(t_lag) are evaluated on the host when the clock moves, and every
+// table built here carries p + d_o(t) and c_o = d_o(t) - d_o(t_lag).  No kernel knows a time.
 #include "engine_internal.hpp"
 
 #include <cmath>
+#include <cstring>
 
 namespace {
 
@@ -25,6 +30,12 @@ ContactTable table_at_u(const fh_ctx* c) {
     t.X = c->verts.p;
     t.u = c->has_u ? c->u.p : nullptr;
     t.w = c->contact_has_w ? c->contact_w.p : nullptr;
+    for (int o = 0; o < t.count; ++o)
+        for (int a = 0; a < 3; ++a) {
+            const double cur = c->contact_shift[o][a], lag = c->contact_shift_lag[o][a];
+            if (cur != 0.0) t.o[o].p[a] += cur;   // (the bits of an obstacle placed at point + d_o(t))
+            t.o[o].c[a] = cur - lag;
+        }
     t.friction = t.friction && !c->friction_suspended;
     t.ubar = nullptr;
     t.slip_v = nullptr;
@@ -44,6 +55,36 @@ void friction_clear(fh_ctx* c) {
     c->friction_set = false;
     c->contact.friction = 0;
     for (double& m : c->contact.mu) m = 0.0;
+}
+
+void paths_clear(fh_ctx* c) {
+    c->path_begin.clear();
+    c->path_time.clear();
+    c->path_offset.clear();
+    c->contact_t = c->contact_t_lag = 0.0;
+    for (int o = 0; o < FH_MAX_OBSTACLES; ++o)
+        for (int a = 0; a < 3; ++a) c->contact_shift[o][a] = c->contact_shift_lag[o][a] = 0.0;
+}
+
+// d_o(t): piecewise linear through the obstacle's knots, constant before the first and after the last; no knots: zero
+void path_offset_at(const fh_ctx* c, int o, double t, double (&d)[3]) {
+    d[0] = d[1] = d[2] = 0.0;
+    if (c->path_begin.empty()) return;
+    const uint64_t b = c->path_begin[(size_t)o], e = c->path_begin[(size_t)o + 1];
+    if (b == e) return;
+    const double* T = c->path_time.data();
+    const double* O = c->path_offset.data();
+    uint64_t k;
+    if (!(t > T[b])) k = b;
+    else if (!(t < T[e - 1])) k = e - 1;
+    else {
+        k = b;
+        while (T[k + 1] <= t) ++k;   // (T[k] <= t < T[k + 1], k + 1 <= e - 1)
+        const double w = (t - T[k]) / (T[k + 1] - T[k]);
+        for (int a = 0; a < 3; ++a) d[a] = std::fma(w, O[3 * (k + 1) + a] - O[3 * k + a], O[3 * k + a]);
+        return;
+    }
+    for (int a = 0; a < 3; ++a) d[a] = O[3 * k + a];
 }
 
 template <class F>
@@ -92,8 +133,27 @@ int friction_lag_to_u(fh_ctx* c, double eps) {
     return FH_OK;
 }
 
+bool contact_has_paths(const fh_ctx* c) { return !c->path_begin.empty() && c->path_begin.back() > 0; }
+
+void contact_set_time(fh_ctx* c, double t, double t_lag) {
+    c->contact_t = t;
+    c->contact_t_lag = t_lag;
+    if (!contact_has_paths(c)) return;
+    bool moved = false;
+    for (int o = 0; o < c->contact.count; ++o) {
+        double cur[3], lag[3];
+        path_offset_at(c, o, t, cur);
+        path_offset_at(c, o, t_lag, lag);
+        moved = moved || std::memcmp(cur, c->contact_shift[o], sizeof cur) != 0 || std::memcmp(lag, c->contact_shift_lag[o], sizeof lag) != 0;
+        std::copy(cur, cur + 3, c->contact_shift[o]);
+        std::copy(lag, lag + 3, c->contact_shift_lag[o]);
+    }
+    if (moved) ++c->contact_gen;
+}
+
 void contact_clear(fh_ctx* c) {
     friction_clear(c);
+    paths_clear(c);
     if (c->contact.count || c->contact_has_w) ++c->contact_gen;
     c->contact = contact_off();
     c->contact_has_w = false;
@@ -195,6 +255,7 @@ int fh_set_obstacles(fh_ctx* c, const fh_obstacle* obstacles, uint64_t count, co
         return FH_OK;
     }
     friction_clear(c);   // (the coefficients belong to the obstacle list)
+    paths_clear(c);      // (and so do the paths)
     if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, std::string(who) + ": no finite element mesh set");
     if (c->ei.d != 2 && c->ei.d != 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": the geometric dim must be 2 or 3");
     if (c->ei.d == 2)   // the third components take no part in a plane problem: a normal is normalised over the first two
@@ -216,6 +277,107 @@ int fh_set_obstacles(fh_ctx* c, const fh_obstacle* obstacles, uint64_t count, co
     c->contact = t;
     c->contact_has_w = node_weights != nullptr;
     ++c->contact_gen;
+    return FH_OK;
+}
+
+int fh_set_obstacle_paths(fh_ctx* c, const uint64_t* knot_begin, const double* knot_time, const double* knot_offset) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_set_obstacle_paths";
+    if (!c->contact.count) return c->fail(FH_INVALID_STATE, std::string(who) + ": no obstacles set (fh_set_obstacles)");
+    const bool had = contact_has_paths(c);
+    if (!knot_begin && !knot_time && !knot_offset) {
+        const double t = c->contact_t, t_lag = c->contact_t_lag;
+        paths_clear(c);
+        c->contact_t = t;
+        c->contact_t_lag = t_lag;
+        if (had) ++c->contact_gen;
+        return FH_OK;
+    }
+    if (!knot_begin) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null knot_begin");
+    const int count = c->contact.count;
+    if (knot_begin[0] != 0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": knot_begin must start at 0");
+    for (int o = 0; o < count; ++o)
+        if (knot_begin[o + 1] < knot_begin[o]) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": knot_begin must not decrease");
+    const uint64_t knots = knot_begin[count];
+    if (knots && (!knot_time || !knot_offset)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null knot_time or knot_offset");
+    for (uint64_t k = 0; k < knots; ++k) {
+        if (!std::isfinite(knot_time[k])) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a knot time is not finite");
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(knot_offset[3 * k + a])) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a knot offset is not finite");
+    }
+    for (int o = 0; o < count; ++o)
+        for (uint64_t k = knot_begin[o]; k + 1 < knot_begin[o + 1]; ++k)
+            if (!(knot_time[k + 1] > knot_time[k]))
+                return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the knot times of an obstacle must be strictly increasing");
+    c->path_begin.assign(knot_begin, knot_begin + count + 1);
+    c->path_time.assign(knot_time, knot_time + knots);
+    c->path_offset.assign(knot_offset, knot_offset + 3 * knots);
+    if (!contact_has_paths(c)) {   // (no knots at all: as without paths)
+        const double t = c->contact_t, t_lag = c->contact_t_lag;
+        paths_clear(c);
+        c->contact_t = t;
+        c->contact_t_lag = t_lag;
+        if (had) ++c->contact_gen;
+        return FH_OK;
+    }
+    contact_set_time(c, c->contact_t, c->contact_t_lag);   // the offsets of the clock as it stands
+    return FH_OK;
+}
+
+int fh_set_obstacle_time(fh_ctx* c, double t, double t_lag) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_set_obstacle_time";
+    if (!std::isfinite(t) || !std::isfinite(t_lag)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": t and t_lag must be finite");
+    if (!c->contact.count) return c->fail(FH_INVALID_STATE, std::string(who) + ": no obstacles set (fh_set_obstacles)");
+    contact_set_time(c, t, t_lag);
+    return FH_OK;
+}
+
+int fh_obstacle_count(fh_ctx* c, uint64_t* count) {
+    if (!c) return FH_BAD_ARGUMENT;
+    if (!count) return c->fail(FH_BAD_ARGUMENT, "fh_obstacle_count: count is null");
+    *count = (uint64_t)c->contact.count;
+    return FH_OK;
+}
+
+int fh_obstacle_offsets(fh_ctx* c, double* current, double* lag) {
+    if (!c) return FH_BAD_ARGUMENT;
+    if (!c->contact.count) return c->fail(FH_INVALID_STATE, "fh_obstacle_offsets: no obstacles set (fh_set_obstacles)");
+    for (int o = 0; o < c->contact.count; ++o)
+        for (int a = 0; a < 3; ++a) {
+            if (current) current[3 * o + a] = c->contact_shift[o][a];
+            if (lag) lag[3 * o + a] = c->contact_shift_lag[o][a];
+        }
+    return FH_OK;
+}
+
+int fh_contact_resultants(fh_ctx* c, double* normal, double* friction) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_contact_resultants";
+    if (!normal) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    const int rc = standalone_ready(c, who);
+    if (rc) return rc;
+    const ContactTable t = table_at_u(c);
+    std::fill(normal, normal + 3 * t.count, 0.0);
+    if (friction) std::fill(friction, friction + 3 * t.count, 0.0);
+    if (!t.count || c->N == 0) return FH_OK;
+    const int count = blocks_of((long long)c->N), K = 6 * t.count;
+    DevBuf<double>& part = c->contact_part;
+    if (part.n < (size_t)count * (size_t)K) HIP_TRY(c, part.alloc((size_t)count * (size_t)K));
+    by_dim(c, [&](auto d) { hipLaunchKernelGGL((k_contact_resultants<d()>), dim3(count), dim3(256), 0, c->stream, t, (int)c->N, part.p); });
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_contact_resultants";
+    std::vector<double> sums((size_t)K);
+    const int rs = sum_partials(c, part.p, count, K, sums.data());   // (waits for the device; the rows in index order)
+    if (rs) return rs;
+    for (int o = 0; o < t.count; ++o)
+        for (int a = 0; a < 3; ++a) {
+            normal[3 * o + a] = sums[(size_t)(6 * o + a)];
+            if (friction) friction[3 * o + a] = sums[(size_t)(6 * o + 3 + a)];
+        }
     return FH_OK;
 }
 

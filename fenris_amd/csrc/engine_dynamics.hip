@@ -30,6 +30,10 @@ struct fh_dynamics {
     double eta_m = 0.0, eta_k = 0.0;   // Rayleigh damping C = eta_m M + eta_k T(u) (fh_dynamics_set_damping); (0, 0): every launch as without it
     DevBuf<double> u_ref2;             // implicit schemes with damping: the folded u_ref of the step (k_damping_fold)
     double eps_v = 0.0;                // friction: the slip velocity (fh_dynamics_set_slip_velocity); 0: the context's slip length as it is
+    // prescribed motion of the Dirichlet dofs (fh_dynamics_set_boundary_motion): u_n = fma(g_n - g_0, direction, u_0) there, g_n =
+    // bm_factor[min(n, count - 1)]; bm_u0 is the u fh_dynamics_set_state gave, kept from the first motion on
+    DevBuf<double> bm_dir, bm_u0;
+    std::vector<double> bm_factor;     // empty: no motion, the Dirichlet dofs are held
 };
 
 namespace {
@@ -51,6 +55,11 @@ void key_now(const fh_ctx* c, unsigned long long (&k)[7]) {
     k[5] = c->u_gen;
     k[6] = contact_key(c);
 }
+
+bool boundary_motion(const fh_dynamics* d) { return !d->bm_factor.empty(); }
+// g_n - g_0, formed on the host: a pure function of n
+double motion_factor(const fh_dynamics* d, uint64_t n) { return d->bm_factor[(size_t)std::min<uint64_t>(n, d->bm_factor.size() - 1)]; }
+double motion_offset(const fh_dynamics* d, uint64_t n) { return motion_factor(d, n) - d->bm_factor[0]; }
 
 // the handle still belongs to the context's mesh and the context can form M and r
 int dyn_ready(fh_dynamics* d, const char* who) {
@@ -92,11 +101,22 @@ int add_tangent(fh_dynamics* d, double s, const double* x, double* tmp, double* 
     return FH_OK;
 }
 
-// what the folding of a frozen C into newton_run's arguments cannot express, and friction on a first-order handle
+// what the folding of a frozen C into newton_run's arguments cannot express, friction on a first-order handle, and the prescribed
+// boundary motions no remedy is chosen for
 int damping_supported(fh_dynamics* d, const char* who) {
     fh_ctx* c = d->c;
+    if (boundary_motion(d)) {
+        if (first_order(d))
+            return c->fail(FH_UNSUPPORTED, std::string(who) + ": a boundary motion is set (fh_dynamics_set_boundary_motion) and a first-order handle does not cover it");
+        if (d->s.scheme == FH_DYN_NEWMARK)
+            return c->fail(FH_UNSUPPORTED, std::string(who) + ": a boundary motion under Newmark is not covered (its kinematics on a prescribed displacement oscillate unless v_0 and a_0 match the path)");
+        if (d->s.scheme == FH_DYN_BACKWARD_EULER && (d->eta_m != 0.0 || d->eta_k != 0.0))
+            return c->fail(FH_UNSUPPORTED, std::string(who) + ": a boundary motion under backward Euler together with Rayleigh damping is not covered");
+    }
     if (first_order(d) && friction_active(c))
         return c->fail(FH_UNSUPPORTED, std::string(who) + ": friction is set (fh_set_friction) and a gradient flow has no slip velocity");
+    if (first_order(d) && contact_has_paths(c))
+        return c->fail(FH_UNSUPPORTED, std::string(who) + ": an obstacle moves along a path (fh_set_obstacle_paths) and the stage times of a first-order step are not covered");
     if (d->eta_k == 0.0 || explicit_scheme(d)) return FH_OK;
     if (c->op > FH_LINEAR_ELASTIC)
         return c->fail(FH_UNSUPPORTED, std::string(who) + ": stiffness damping under Newmark or backward Euler covers FH_LAPLACE and FH_LINEAR_ELASTIC only");
@@ -107,7 +127,15 @@ int damping_supported(fh_dynamics* d, const char* who) {
 
 // a term of the step takes the velocity the handle holds (Rayleigh damping, friction): a_{n+1} of a step is formed on v_h then, and
 // forming it again on v_{n+1} would not repeat it
-bool velocity_term(const fh_dynamics* d) { return d->eta_m != 0.0 || d->eta_k != 0.0 || friction_active(d->c); }
+// ... and so for obstacles on a path: the steps move the contact clock, and contact_gen, themselves
+bool velocity_term(const fh_dynamics* d) { return d->eta_m != 0.0 || d->eta_k != 0.0 || friction_active(d->c) || contact_has_paths(d->c); }
+
+// the contact clock of the residual of step `step`: (t_step, t_{step-1}) with t_n = (double)n dt, the records' time column; lagged false
+// (a_n of the state as it stands): (t_step, t_step).  Host arithmetic alone; the table of the launch that follows carries the offsets.
+void clock_to_step(fh_dynamics* d, uint64_t step, bool lagged) {
+    const double t = (double)step * d->s.dt;
+    contact_set_time(d->c, t, lagged && step > 0 ? (double)(step - 1) * d->s.dt : t);
+}
 
 // the slip length of a step with friction: eps_v dt, or the context's own when no slip velocity was given
 double slip_eps(const fh_dynamics* d) { return d->eps_v > 0.0 ? d->eps_v * d->s.dt : d->c->contact.eps; }
@@ -179,6 +207,15 @@ DynStep step_args(fh_dynamics* d, int flags, uint64_t step) {
     p.ke_partial = d->kep.p;
     p.flags = flags;
     p.eta_m = d->eta_m;
+    if (boundary_motion(d) && (flags & DYN_ADVANCE)) {   // the drift of this launch: from `step` to step + 1
+        p.bm_dir = d->bm_dir.p;
+        p.bm_u0 = d->bm_u0.p;
+        p.bm_g = motion_offset(d, step + 1);
+        p.bm_rate = (motion_factor(d, step + 1) - motion_factor(d, step)) / d->s.dt;
+    } else if (boundary_motion(d)) {   // (no drift: the fixed branch only leaves v alone)
+        p.bm_dir = d->bm_dir.p;
+        p.bm_u0 = d->bm_u0.p;
+    }
     return p;
 }
 
@@ -191,6 +228,7 @@ int explicit_launch(fh_dynamics* d, int flags, uint64_t step, uint64_t* stats, i
     // friction: the lag state is the u the residual is formed at, the slip dt v of the velocity the handle holds (v_h; v_0 for a_0)
     const FrictionSlip slip(c, (flags & DYN_ACCEL) && friction_active(c) ? d->v.p : nullptr, d->s.dt, slip_eps(d));
     if (flags & DYN_ACCEL) {
+        clock_to_step(d, step, (flags & DYN_COMPLETE) != 0);
         bool tiles;
         int rc = residual_tiles(d, &tiles);
         if (rc) return rc;
@@ -247,15 +285,18 @@ int ensure_acceleration(fh_dynamics* d, uint64_t* stats) {
     if (std::equal(k, k + 7, d->a_key) && !d->load_changed) return FH_OK;
     const int n = d->n, S = c->S(), g = blocks_of(n);
     int rc;
-    // (v and a of a Dirichlet dof are zero whatever fh_dynamics_set_state was given)
-    hipLaunchKernelGGL(k_dynamics_scale, dim3(g), dim3(256), 0, c->stream, n, S, 1.0, dmask_of(c), d->v.p);
-    HIP_TRY(c, hipGetLastError());
+    // (v and a of a Dirichlet dof are zero whatever fh_dynamics_set_state was given; with a boundary motion set v there is the handle's own)
+    if (!boundary_motion(d)) {
+        hipLaunchKernelGGL(k_dynamics_scale, dim3(g), dim3(256), 0, c->stream, n, S, 1.0, dmask_of(c), d->v.p);
+        HIP_TRY(c, hipGetLastError());
+    }
     if (explicit_scheme(d)) {
         rc = reset_status(c);
         if (rc) return rc;
         rc = explicit_launch(d, DYN_ACCEL, d->step, stats, nullptr);
         if (rc) return rc;
     } else {   // Newmark: M a_0 = lf_0 f - r(u_0) on the free dofs; backward Euler keeps no a_0 but refuses the same states
+        clock_to_step(d, d->step, false);
         if (friction_active(c)) {   // (the lag state of a_0 is u_0 itself: no slip, no friction force)
             rc = friction_lag_to_u(c, slip_eps(d));
             if (rc) return rc;
@@ -349,12 +390,23 @@ int implicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, do
     const double dt = d->s.dt, nb = euler ? 1.0 : d->s.newmark_beta, bdt2 = nb * dt * dt;
     for (uint64_t j = 0; j < num_steps; ++j) {
         const uint64_t g_step = d->step + 1;
+        const double t_before = c->contact_t, t_lag_before = c->contact_t_lag;
+        struct ClockBack {   // a step that does not complete, for whatever reason, leaves the clock of the state that stands
+            fh_ctx* c;
+            double t, t_lag;
+            bool armed;
+            ~ClockBack() {
+                if (armed) contact_set_time(c, t, t_lag);
+            }
+        } clock_back{c, t_before, t_lag_before, true};
+        clock_to_step(d, g_step, true);
         if (friction_active(c)) {   // the lag state of the step is u_n: a device copy enqueued with the step
             const int rf = friction_lag_to_u(c, slip_eps(d));
             if (rf) return rf;
         }
         hipLaunchKernelGGL(k_newmark_predict, dim3(g), dim3(256), 0, c->stream, n, S, dt, euler ? 0.0 : dt * dt * (0.5 - nb), dmask_of(c), c->u.p,
-                           d->v.p, d->a.p, d->u_ref.p, d->u_prev.p);
+                           d->v.p, d->a.p, d->u_ref.p, d->u_prev.p, boundary_motion(d) ? d->bm_dir.p : nullptr, boundary_motion(d) ? d->bm_u0.p : nullptr,
+                           boundary_motion(d) ? motion_offset(d, g_step) : 0.0);
         HIP_TRY(c, hipGetLastError());
         ++c->u_gen;
         const double* load = nullptr;
@@ -398,13 +450,15 @@ int implicit_steps(fh_dynamics* d, uint64_t num_steps, uint64_t record_every, do
             HIP_TRY(c, hipMemcpyAsync(c->u.p, d->u_prev.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             ++c->u_gen;
+            contact_set_time(c, t_before, t_lag_before);
             remember_u(d);
             return c->fail(rc, msg);
         }
         hipLaunchKernelGGL(k_newmark_correct, dim3(g), dim3(256), 0, c->stream, n, S, euler ? 1 : 0, dt, 1.0 / bdt2, d->s.newmark_gamma, dmask_of(c),
-                           c->u.p, d->u_ref.p, d->u_prev.p, d->v.p, d->a.p);
+                           c->u.p, d->u_ref.p, d->u_prev.p, d->v.p, d->a.p, boundary_motion(d) ? 1 : 0);
         HIP_TRY(c, hipGetLastError());
         d->step = g_step;
+        clock_back.armed = false;
         remember_u(d);
         *done = j + 1;
         const bool last = j + 1 == num_steps;
@@ -635,10 +689,12 @@ int set_state_common(fh_dynamics* d, const double* u, const double* v, hipMemcpy
     if (v) HIP_TRY(c, hipMemcpyAsync(d->v.p, v, bytes, kind, c->stream));
     else HIP_TRY(c, hipMemsetAsync(d->v.p, 0, bytes, c->stream));
     HIP_TRY(c, hipMemsetAsync(d->a.p, 0, bytes, c->stream));
+    if (d->bm_u0.p && d->n) HIP_TRY(c, hipMemcpyAsync(d->bm_u0.p, c->u.p, bytes, hipMemcpyDeviceToDevice, c->stream));   // u_0 of a boundary motion
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     d->step = 0;
     d->a_key[5] = ~0ull;
     d->fresh = true;
+    contact_set_time(c, 0.0, 0.0);
     return FH_OK;
 }
 
@@ -658,11 +714,43 @@ int set_load_common(fh_dynamics* d, const double* f, const double* load_factor, 
     return FH_OK;
 }
 
+int set_motion_common(fh_dynamics* d, const double* direction, const double* factor, uint64_t count, hipMemcpyKind kind) {
+    fh_ctx* c = d->c;
+    const char* who = "fh_dynamics_set_boundary_motion";
+    if (!direction) {
+        if (boundary_motion(d)) d->load_changed = true;   // a_n is formed again, as after fh_dynamics_set_load
+        d->bm_factor.clear();
+        return FH_OK;
+    }
+    if (!factor || count == 0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the factor table needs count >= 1");
+    for (uint64_t k = 0; k < count; ++k)
+        if (!std::isfinite(factor[k])) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a factor is not finite");
+    int rc = dyn_ready(d, who);
+    if (rc) return rc;
+    const size_t n = (size_t)d->n;
+    if (d->bm_dir.n < n) HIP_TRY(c, d->bm_dir.alloc(n));
+    const bool first = d->bm_u0.n < n || !d->bm_u0.p;
+    if (first) {   // u_0: the state as it stands (its Dirichlet entries have not moved since fh_dynamics_set_state), zeros before one
+        HIP_TRY(c, d->bm_u0.alloc(n));
+        if (c->has_u && n) HIP_TRY(c, hipMemcpyAsync(d->bm_u0.p, c->u.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+        else HIP_TRY(c, hipMemsetAsync(d->bm_u0.p, 0, sizeof(double) * std::max<size_t>(n, 1), c->stream));
+    }
+    if (n) HIP_TRY(c, hipMemcpyAsync(d->bm_dir.p, direction, sizeof(double) * n, kind, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    d->bm_factor.assign(factor, factor + count);
+    d->load_changed = true;
+    return FH_OK;
+}
+
 int state_common(fh_dynamics* d, double* u, double* v, double* a, double* time, uint64_t* step, hipMemcpyKind kind) {
     fh_ctx* c = d->c;
     int rc = dyn_ready(d, "fh_dynamics_state");
     if (rc) return rc;
     const size_t bytes = sizeof(double) * (size_t)d->n;
+    if (boundary_motion(d) || (first_order(d) && contact_has_paths(c))) {   // (out of scope whatever is asked for)
+        rc = damping_supported(d, "fh_dynamics_state");
+        if (rc) return rc;
+    }
     if ((first_order(d) ? v : a) && c->has_u && c->N) {   // a_n of the state as it stands (a_0 before the first step); first order: the rate
         uint64_t st[5] = {0, 0, 0, 0, 0};
         rc = damping_supported(d, "fh_dynamics_state");
@@ -789,6 +877,17 @@ int fh_dynamics_set_load_dev(fh_dynamics* d, const double* f_dev, const double* 
     if (!d) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(d->c->device);
     return set_load_common(d, f_dev, load_factor, count, hipMemcpyDeviceToDevice);
+}
+
+int fh_dynamics_set_boundary_motion(fh_dynamics* d, const double* direction, const double* factor, uint64_t count) {
+    if (!d) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(d->c->device);
+    return set_motion_common(d, direction, factor, count, hipMemcpyHostToDevice);
+}
+int fh_dynamics_set_boundary_motion_dev(fh_dynamics* d, const double* direction_dev, const double* factor, uint64_t count) {
+    if (!d) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(d->c->device);
+    return set_motion_common(d, direction_dev, factor, count, hipMemcpyDeviceToDevice);
 }
 
 int fh_dynamics_set_damping(fh_dynamics* d, double eta_mass, double eta_stiffness) {

@@ -499,6 +499,14 @@ struct fh_ctx {
     DevBuf<double> contact_part;       // workgroup partials of E_c and their range sums (kept: no allocation per record)
     bool contact_has_w = false;
     unsigned long long contact_gen = 0;
+    // moving obstacles (fh_set_obstacle_paths): obstacle o owns the knots path_begin[o] .. path_begin[o + 1] of path_time / path_offset (3
+    // per knot); path_begin empty: no paths.  The contact clock (fh_set_obstacle_time): the two times and, per obstacle, the offsets
+    // d_o(t) and d_o(t_lag) evaluated on the host; `contact` keeps the obstacles where fh_set_obstacles put them, the tables of
+    // contact_table carry p + d_o(t) and c_o = d_o(t) - d_o(t_lag).  contact_gen moves when an offset changes bitwise.
+    std::vector<uint64_t> path_begin;
+    std::vector<double> path_time, path_offset;
+    double contact_t = 0.0, contact_t_lag = 0.0;
+    double contact_shift[FH_MAX_OBSTACLES][3] = {}, contact_shift_lag[FH_MAX_OBSTACLES][3] = {};
     // friction (fh_set_friction): the coefficients, the slip length and the flag live in `contact`; friction_ubar is the lag displacement
     // (S N doubles, allocated while friction is set), friction_gen counts the calls that change any of it.  friction_slip_v / _dt / _eps: the
     // slip source of a central-difference launch, set for its duration (FrictionSlip); friction_suspended: the entry points that leave the
@@ -679,6 +687,10 @@ int contact_add_apply(fh_ctx* c, const double* x_dev, const unsigned long long* 
 int contact_add_diagonal(fh_ctx* c, double* diag_dev);
 int contact_add_energy(fh_ctx* c, double* energy);
 void contact_clear(fh_ctx* c);
+// moving obstacles: whether any obstacle has knots; the contact clock to (t, t_lag), a no-op without such a path (the integrators, before
+// every launch or solve that forms a residual: host arithmetic alone, contact_gen moves when an offset changes bitwise)
+bool contact_has_paths(const fh_ctx* c);
+void contact_set_time(fh_ctx* c, double t, double t_lag);
 // friction: whether the tables of contact_table carry the term now; the key of everything it depends on beside u (joins contact_gen in the
 // caches' keys); ubar = the context's u, enqueued (the implicit integrators, at the start of a step) with a new slip length
 bool friction_active(const fh_ctx* c);

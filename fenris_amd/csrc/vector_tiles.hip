@@ -740,6 +740,11 @@ __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, con
     block_partial_store(sq, norm_partial);
 }
 
+// (the arguments beside the table, of every node pass that takes one: contact_kernels.hpp holds table + NODE_PASS_ARG_BYTES under 4 KB)
+static_assert(4 * sizeof(void*) + sizeof(DynStep) <= NODE_PASS_ARG_BYTES && 4 * sizeof(void*) + sizeof(FoStage) <= NODE_PASS_ARG_BYTES &&
+                  12 * sizeof(void*) <= NODE_PASS_ARG_BYTES,
+              "a node pass's own arguments have outgrown the room the contact table leaves them");
+
 // node pass of a central-difference step (engine_dynamics.hip): the node's residual partials summed in ascending order as
 // k_vector_from_partials forms them, and in the same visit the integrator's whole state update (dyn_dof, dynamics_kernels.hpp): a_{n+1} =
 // (lf f - r) / m, the second kick that completes v_{n+1}, then either the stores and the kinetic-energy partial of a record (DYN_STORE) or

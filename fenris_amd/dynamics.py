@@ -105,6 +105,7 @@ class TimeIntegrator:
         self._h = None
         self._load = (None, None)
         self._damping = None
+        self._motion = None
         self.engine.set_mass_density(self._rho)   # (checks the count now)
         self.engine._mass_bound = self
 
@@ -132,6 +133,43 @@ class TimeIntegrator:
         if self._h is not None:
             self._send_damping()
         return self
+
+    def with_boundary_motion(self, direction, factor):
+        """a prescribed motion of the Dirichlet nodes: at step n they hold u_n = u_0 + (factor[min(n, len - 1)] - factor[0]) direction, with
+        u_0 the u of set_state (direction: one entry per dof, read on the Dirichlet dofs only; a numpy array or a device tensor; None
+        clears the motion).  CentralDifference and BackwardEuler (without damping) cover it; step raises FH_UNSUPPORTED for Newmark.  v on
+        the Dirichlet dofs is then the caller's: give set_state the slope of the table there, v_0 = (factor[1] - factor[0]) / dt direction.
+        Returns self"""
+        if direction is None:
+            self._motion = (None, None)
+        else:
+            fac = _ffi.as_f64(factor).reshape(-1).copy()
+            if len(fac) == 0:
+                raise ValueError("factor needs at least one entry")
+            self._motion = (direction if _is_torch(direction) else _ffi.as_f64(direction).reshape(-1).copy(), fac)
+        if self._h is not None:
+            self._send_motion()
+        return self
+
+    def _send_motion(self):
+        if self._motion is None:
+            return
+        direction, fac = self._motion
+        lib = self.engine._lib
+        if direction is None:
+            rc = lib.fh_dynamics_set_boundary_motion(self._h, None, None, 0)
+        else:
+            n = self._n()
+            if (direction.numel() if _is_torch(direction) else np.size(direction)) != n:
+                raise ValueError(f"direction must hold {n} entries")
+            if _is_torch(direction):
+                import torch
+
+                dt_ = direction.to(dtype=torch.float64, device=f"cuda:{self.engine.device}").reshape(-1).contiguous()
+                rc = lib.fh_dynamics_set_boundary_motion_dev(self._h, _ptr(dt_), _ffi.fp(fac), len(fac))
+            else:
+                rc = lib.fh_dynamics_set_boundary_motion(self._h, _ffi.fp(direction), _ffi.fp(fac), len(fac))
+        self.engine._check(rc)
 
     def damping(self):
         """the RayleighDamping the handle uses"""
@@ -183,6 +221,7 @@ class TimeIntegrator:
             self._h = h
             self._send_load()
             self._send_damping()
+            self._send_motion()
             _contact.send_slip_velocity(self)
         return self._h
 
@@ -357,6 +396,9 @@ class FirstOrderIntegrator(TimeIntegrator):
 
     def damping(self):
         raise TypeError("a first-order problem has no velocity to damp")
+
+    def with_boundary_motion(self, direction, factor):
+        raise TypeError("the first-order integrators do not cover a prescribed boundary motion")
 
     def _fh_settings(self):
         s = _ffi.FirstOrderSettings()

@@ -958,7 +958,7 @@ typedef struct {
 } fh_first_order_settings;
 int fh_first_order_create(fh_ctx*, const fh_first_order_settings* settings, fh_dynamics** out);
 
-/* ---- penalty contact with rigid, fixed obstacles (engine_contact.hip; the arithmetic: contact_kernels.hpp) ----------------------------
+/* ---- penalty contact with rigid obstacles (engine_contact.hip; the arithmetic: contact_kernels.hpp); fixed unless given a path below --
  * Obstacle o has a signed distance phi_o(x), positive where the body may be, and a stiffness k_o > 0.  With x_i = X_i + u_i the current
  * position of node i, w_i >= 0 a node weight (default 1) and p = min(0, phi_o(x_i)):
  *   energy   E_c(u) = sum_o sum_i (k_o w_i / 2) p^2
@@ -1037,6 +1037,63 @@ int fh_set_friction_reference_dev(fh_ctx*, const double* ubar_dev);
 int fh_friction_potential(fh_ctx*, double* potential);
 int fh_friction_force_dev(fh_ctx*, double* out_dev);
 int fh_dynamics_set_slip_velocity(fh_dynamics*, double eps_v);
+/* ---- moving obstacles: translation along piecewise-linear paths, and the force resultants per obstacle ---------------------------------
+ * fh_set_obstacle_paths: obstacle o owns the knots knot_begin[o] .. knot_begin[o + 1] (knot_begin: count + 1 entries, non-decreasing from
+ *   0; knot_time: one per knot, strictly increasing within an obstacle; knot_offset: 3 per knot, 2-D uses the first two).  Its offset d_o(t)
+ *   is piecewise linear through them -- in a segment, with w = (t - t_k) / (t_{k+1} - t_k), d = fma(w, d_{k+1} - d_k, d_k) per component --
+ *   constant before the first knot and after the last; an obstacle with no knots never moves.  The obstacle's point is point_o + d_o(t):
+ *   translation only, a half-space keeps its normal.  d_o is evaluated on the host in double.  Three NULL arrays clear the paths.
+ *   FH_BAD_ARGUMENT: knot times not strictly increasing, a value that is not finite, knot_begin not non-decreasing from 0;
+ *   FH_INVALID_STATE: no obstacles.  fh_set_obstacles and fh_set_mesh* clear the paths and return the clock to (0, 0).
+ * fh_set_obstacle_time: the contact clock.  The context keeps two offsets per obstacle, the current one d_o(t) and the lag one d_o(t_lag)
+ *   (fh_obstacle_offsets reads them: count x 3 doubles each, either may be NULL; fh_obstacle_count gives the count of the obstacles that
+ *   stand, 0 without any); both times are 0 until the first call.  FH_BAD_ARGUMENT:
+ *   a time that is not finite; FH_INVALID_STATE: no obstacles.  The caches keyed on the obstacles are invalidated only when an offset
+ *   changes bitwise.
+ * The normal term (energy, force, tangent block, gap, diagonal, CSR blocks) is evaluated against the obstacle at its CURRENT position on
+ *   every route: the same bits as obstacles placed at point_o + d_o(t) by fh_set_obstacles.
+ * Friction, with c_o = d_o(t) - d_o(t_lag) the obstacle's own displacement over the lag interval: the solvers and the implicit integrators
+ *   evaluate nbar, P and lam at xbar_i against the obstacle at its LAG position and take the slip relative to the obstacle,
+ *   s = P (u_i - ubar_i - c_o); central differences keep the current configuration as the lag one and take s = P (dt v_i - c_o).  f0, c1, c2
+ *   are unchanged and H_i stays the exact symmetric positive semi-definite Hessian of D with ubar and both offsets frozen.  A node that moves
+ *   with the obstacle feels no friction force.  A quasi-static user of fh_newton_solve calls, between load steps,
+ *   fh_set_friction_reference(NULL), then fh_set_obstacle_time(t_next, t_now), then solves.
+ * fh_dynamics_create handles drive the clock themselves: every launch or solve that forms a residual for step n + 1 first sets the clock to
+ *   (t_{n+1}, t_n) with t_n = (double)n dt as in the records' time column; a_0 uses (t_0, t_0); fh_dynamics_set_state returns the clock to
+ *   (0, 0).  A central-difference launch carries its own offsets in its kernel arguments: nothing is waited for, no time lives on the device,
+ *   no launch is added, and a run repeats bit for bit however it is cut into calls.  The context is left at the clock of the last step.
+ *   fh_dynamics_stable_dt and fh_eigs_lowest take the obstacles where they stand.  fh_first_order_create handles answer FH_UNSUPPORTED from
+ *   fh_dynamics_step and fh_dynamics_state while any obstacle has knots (the stage times of a super-step are not defined here).
+ *   With no knots set every route computes the bits it computed before.
+ * fh_contact_resultants: R_o = sum_i k_o w_i p n, obstacle o's share of g and with it the force the body exerts on the obstacle, into
+ *   normal (count x 3 doubles), and Q_o = sum_i mu_o lam c1 s, its share of q, into friction (count x 3, may be NULL; zeros without
+ *   friction); both at the context's u over every node, Dirichlet nodes included; the third components are 0 in 2-D.  One launch of
+ *   k_contact_resultants (a fixed reduction tree per workgroup, one partial row each) and the ordered sum of the rows: no atomics, two calls
+ *   return the same bits. */
+int fh_set_obstacle_paths(fh_ctx*, const uint64_t* knot_begin, const double* knot_time, const double* knot_offset);
+int fh_set_obstacle_time(fh_ctx*, double t, double t_lag);
+int fh_obstacle_count(fh_ctx*, uint64_t* count);
+int fh_obstacle_offsets(fh_ctx*, double* current, double* lag);
+int fh_contact_resultants(fh_ctx*, double* normal, double* friction);
+/* ---- prescribed motion of the Dirichlet nodes during time integration (second-order handles) -------------------------------------------
+ * fh_dynamics_set_boundary_motion(_dev): direction (S N doubles, read on the Dirichlet dofs only; NULL clears the motion) and a factor
+ *   table of count >= 1 finite entries (host memory in both forms; else FH_BAD_ARGUMENT).  With g_n = factor[min(n, count - 1)], a Dirichlet
+ *   dof holds u_n = fma(g_n - g_0, direction, u_0), u_0 the value fh_dynamics_set_state gave (the handle keeps a device copy from the first
+ *   motion on, taken from the u that stands when no fh_dynamics_set_state follows; a motion set after another was cleared is measured
+ *   from that same u_0, not from where the first one left the dofs).  g_n - g_0 is formed on the host: the entries are a pure
+ *   function of n and come back bit for bit however a run is cut into calls.  Setting or clearing a motion invalidates a_n, as
+ *   fh_dynamics_set_load does.  While a motion is set, v on the Dirichlet dofs is the handle's own and is no longer zeroed: at step 0 it is
+ *   what fh_dynamics_set_state gave, and the CALLER matches it to the slope of the factor table, v_0 = ((g_1 - g_0) / dt) direction there.
+ * FH_DYN_CENTRAL_DIFFERENCE: the drift from step n to n + 1 writes u_{n+1} as above and v = ((g_{n+1} - g_n) / dt) direction, the half-step
+ *   velocity of the boundary, so stiffness damping and the friction slip see it move; a stored state keeps that v and has a = 0 there; the
+ *   kinetic-energy column still counts the free dofs only.  No launch is added: the fused node pass and the stand-alone update share it.
+ * FH_DYN_BACKWARD_EULER: a moved Dirichlet dof has the kinematics of a free one, u_ref = u_n + dt v_n, v_{n+1} = (u_{n+1} - u_n) / dt,
+ *   a_{n+1} = (v_{n+1} - v_n) / dt; the prescribed u_{n+1} enters the Newton guess and Newton holds it; the consistent kinetic energy
+ *   includes those dofs; a failed Newton solve restores u_n on them too.
+ * FH_UNSUPPORTED from fh_dynamics_step and fh_dynamics_state: a motion under FH_DYN_NEWMARK (its kinematics on a prescribed displacement
+ *   oscillate unless v_0 and a_0 match the path), under backward Euler together with Rayleigh damping, or on a first-order handle. */
+int fh_dynamics_set_boundary_motion(fh_dynamics*, const double* direction, const double* factor, uint64_t count);
+int fh_dynamics_set_boundary_motion_dev(fh_dynamics*, const double* direction_dev, const double* factor, uint64_t count);
 /* Geometric multigrid for the matrix-free solvers (FH_PRECOND_MULTIGRID of fh_cg_solve_matrix_free, fh_cg_solve_tangent,
  * fh_cg_solve_shifted_tangent and fh_newton_solve; fh_cg_solve on assembled values takes identity, Jacobi or FH_PRECOND_AMG).  Every level is an
  * ordinary context with its own mesh, operator (Laplace, LinearElastic, NeoHookean or StVK), quadrature, data, density and

@@ -8,13 +8,15 @@
     sixteen   this build, that floor and 15 balls far away: FH_MAX_OBSTACLES obstacles evaluated at every node
     floor_mu0   this build, that floor with fh_set_friction given mu = 0 (the friction flag stays clear: the cost must be `floor`'s)
     floor_mu05  this build, that floor with mu = 0.5, slip velocity 0.05: the friction term in the step's node pass and in the map
+    floor_mu05_moving  (--moving) `floor_mu05` with the floor sliding sideways along a path at 0.5 under nodes that start at rest: the integrator moves the
+                contact clock before every launch and the node pass takes the slip relative to the floor; held against `floor_mu05`
     parent_floor  the parent's library on the `floor` scene (friction never set there: what `floor` and `floor_mu0` are held against)
 
 The variants alternate: every measurement is a fresh child process (one library per process), `--repeats` rounds after one discarded
 warm-up round, so drift of the machine hits every variant alike.  Per variant the median and the spread (min .. max) over the rounds, one
 JSON line, printed and appended to profiles/contact.jsonl.
 
-    python scripts/bench_contact.py [--cells 64] [--steps 200] [--applies 100] [--repeats 5] [--parent-lib PATH] [--variants a,b,...]
+    python scripts/bench_contact.py [--cells 64] [--steps 200] [--applies 100] [--repeats 5] [--parent-lib PATH] [--variants a,b,...] [--moving]
 """
 import argparse
 import json
@@ -46,15 +48,17 @@ def child(variant, cells, steps, applies):
     asm = (fa.ElementEllipticAssemblerBuilder(eng).with_finite_element_space(mesh)
            .with_operator(fa.MaterialEllipticOperator(fa.StableNeoHookeanMaterial())).with_quadrature_table(qt).with_u(np.zeros(n)).build())
     obstacles = None
-    if variant in ("floor", "sixteen", "floor_mu0", "floor_mu05"):
+    if variant in ("floor", "sixteen", "floor_mu0", "floor_mu05", "floor_mu05_moving"):
         k = 1e6 / cells
-        if variant == "floor_mu05":
+        if variant == "floor_mu05_moving":
+            items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k, friction=0.5, path=fa.ObstaclePath.constant_velocity((0.5, 0.0, 0.0), 1.0))]
+        elif variant == "floor_mu05":
             items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k, friction=0.5)]
         else:
             items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k)]
         if variant == "sixteen":
             items += [fa.Ball((10.0 + j, 10.0, 10.0), 0.5, k) for j in range(15)]
-        obstacles = fa.Obstacles(items, slip_length=1e-3, slip_velocity=0.05) if variant == "floor_mu05" else fa.Obstacles(items)
+        obstacles = fa.Obstacles(items, slip_length=1e-3, slip_velocity=0.05) if variant.startswith("floor_mu05") else fa.Obstacles(items)
     u0 = torch.zeros(n, dtype=torch.float64, device="cuda")
     u0[2::3] = -0.01
     v0 = torch.zeros_like(u0)
@@ -89,8 +93,10 @@ def child(variant, cells, steps, applies):
     t = fa.MatrixFreeTangent(asm)
     if obstacles is not None:
         t.with_obstacles(obstacles)
-    if variant == "floor_mu05":
+    if variant.startswith("floor_mu05"):
         t.with_friction_reference(u0)     # the lag state: the shifted u
+    if variant == "floor_mu05_moving":
+        eng.set_obstacle_time(0.02, 0.01)
     arm()
     x = torch.rand(n, dtype=torch.float64, device="cuda")
     y = torch.empty_like(x)
@@ -119,12 +125,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--variants", default=None, help="comma-separated subset of the variants, in the order they alternate")
+    ap.add_argument("--moving", action="store_true", help="add the floor_mu05_moving variant")
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
     if a.child:
         child(a.child, a.cells, a.steps, a.applies)
         return
-    variants = (["parent", "parent_floor"] if a.parent_lib else []) + ["none", "floor", "sixteen", "floor_mu0", "floor_mu05"]
+    variants = (["parent", "parent_floor"] if a.parent_lib else []) + ["none", "floor", "sixteen", "floor_mu0", "floor_mu05"] + (["floor_mu05_moving"] if a.moving else [])
     if a.variants:
         variants = [v for v in a.variants.split(",") if v in variants]
     rows = {v: [] for v in variants}
