@@ -36,13 +36,11 @@ static __global__ void __launch_bounds__(256) k_first_order_update(int n, int S,
 }
 
 // the load of a theta step: g = (lf_{n+1} + c lf_n) f - c r(u_n), c = (1 - theta) / theta (c == 0: r is not read and may be null)
-static __global__ void __launch_bounds__(256) k_theta_load(int n, const double* f, const double* lf, unsigned long long lf_count,
-                                                           unsigned long long step, double c, const double* r, double* g) {
+static __global__ void __launch_bounds__(256) k_theta_load(int n, const StepLoad l, double c, const double* r, double* g) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double l0 = lf ? lf[step < lf_count ? step : lf_count - 1] : 1.0;
-    const double l1 = lf ? lf[step + 1 < lf_count ? step + 1 : lf_count - 1] : 1.0;
-    const double lfv = fma(c, l0, l1) * (f ? f[i] : 0.0);
+    const double l0 = load_factor_at(l, l.step), l1 = load_factor_at(l, l.step + 1);
+    const double lfv = fma(c, l0, l1) * (l.f ? l.f[i] : 0.0);
     g[i] = c != 0.0 ? fma(-c, r[i], lfv) : lfv;
 }
 
@@ -126,19 +124,19 @@ static __global__ void __launch_bounds__(256) k_kinetic_partials(int n, const do
 }
 
 // b = lf f - r with the rows of the Dirichlet nodes zero: the right-hand side of M a_0 = lf_0 f - r(u_0)
-static __global__ void __launch_bounds__(256) k_dynamics_rhs(int n, int S, const double* f, const double* lf, unsigned long long lf_count,
-                                                             unsigned long long step, const unsigned char* dmask, const double* r, double* b) {
+static __global__ void __launch_bounds__(256) k_dynamics_rhs(int n, int S, const StepLoad l, const unsigned char* dmask, const double* r, double* b) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double l = lf ? lf[step < lf_count ? step : lf_count - 1] : 1.0;
-    b[i] = (dmask && dmask[i / S]) ? 0.0 : fma(l, f ? f[i] : 0.0, -r[i]);
+    b[i] = (dmask && dmask[i / S]) ? 0.0 : fma(load_factor_at(l, l.step), l.f ? l.f[i] : 0.0, -r[i]);
 }
 
-// x[i] *= s, or x[i] = 0 on the Dirichlet dofs (power iteration on the free dofs); x = y / m on the free dofs
+// x[i] *= s, or x[i] = 0 on the Dirichlet dofs (power iteration on the free dofs; s = 1: v of the Dirichlet dofs cleared; dmask null: the
+// scaled load of an implicit step)
 static __global__ void __launch_bounds__(256) k_dynamics_scale(int n, int S, double s, const unsigned char* dmask, double* x) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) x[i] = (dmask && dmask[i / S]) ? 0.0 : x[i] * s;
 }
+// x = y / m on the free dofs, 0 on the Dirichlet dofs (power iteration)
 static __global__ void __launch_bounds__(256) k_dynamics_divide(int n, int S, const unsigned char* dmask, const double* y, const double* m, double* x) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) x[i] = (dmask && dmask[i / S]) ? 0.0 : y[i] / m[i];
@@ -153,7 +151,7 @@ static __global__ void __launch_bounds__(256) k_dynamics_fill(int n, double* x) 
     z ^= z >> 31;
     x[i] = (double)(z >> 11) * 0x1p-52 - 1.0;
 }
-// three partials per workgroup: x . (m x), x . y, and nothing else
+// one partial per workgroup: x . (m x)
 static __global__ void __launch_bounds__(256) k_dynamics_mdot(int n, const double* x, const double* m, double* partial) {
     __shared__ double red[4];
     const int i = blockIdx.x * 256 + threadIdx.x;

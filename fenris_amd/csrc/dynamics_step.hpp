@@ -15,11 +15,19 @@ enum {
     DYN_ADVANCE = 8    // the next step's first kick and drift: v_h = v + dt/2 a, u += dt v_h; v_h is stored in v
 };
 
-struct DynStep {
-    double dt, half_dt;
+// the load lf_step f of a launch, as every kernel of the integrators takes it
+struct StepLoad {
     const double* f;            // load, S N (null: zero)
     const double* lf;           // load factors on the device (null: 1) ...
-    unsigned long long lf_count, step;   // ... lf[min(step, lf_count - 1)], step the global index of the step whose acceleration is formed
+    unsigned long long lf_count, step;   // ... lf[min(step, lf_count - 1)]
+};
+__device__ __forceinline__ double load_factor_at(const StepLoad& l, unsigned long long step) {
+    return l.lf ? l.lf[step < l.lf_count ? step : l.lf_count - 1] : 1.0;
+}
+
+struct DynStep {
+    double dt, half_dt;
+    StepLoad load;              // load.step: the global index of the step whose acceleration is formed
     const double* m;            // row-sum lumped mass, S N
     const unsigned char* dmask; // N membership flags of the Dirichlet nodes (null: none)
     double *u, *v, *a;          // S N each: the context's u; v holds v_h between the launches of a call
@@ -35,9 +43,7 @@ struct DynStep {
 };
 
 template <class P>   // (DynStep, or FoStage below)
-__device__ __forceinline__ double dyn_load_factor(const P& p) {
-    return p.lf ? p.lf[p.step < p.lf_count ? p.step : p.lf_count - 1] : 1.0;
-}
+__device__ __forceinline__ double dyn_load_factor(const P& p) { return load_factor_at(p.load, p.load.step); }
 // the three pieces every route shares: the same bits however a run is cut into calls and records
 __device__ __forceinline__ double dyn_accel(double lf, double f, double r, double m) { return fma(lf, f, -r) / m; }
 __device__ __forceinline__ double dyn_kick(double v, double a, double half_dt) { return fma(half_dt, a, v); }
@@ -68,8 +74,8 @@ __device__ __forceinline__ double dyn_dof(const DynStep& p, size_t i, bool fixed
     }
     double v = p.v[i], a;
     if (p.flags & DYN_ACCEL) {
-        a = p.eta_m != 0.0 ? dyn_accel_damped(lf, p.f ? p.f[i] : 0.0, r, p.m[i], v, p.eta_m, p.half_dt, (p.flags & DYN_COMPLETE) != 0)
-                           : dyn_accel(lf, p.f ? p.f[i] : 0.0, r, p.m[i]);
+        a = p.eta_m != 0.0 ? dyn_accel_damped(lf, p.load.f ? p.load.f[i] : 0.0, r, p.m[i], v, p.eta_m, p.half_dt, (p.flags & DYN_COMPLETE) != 0)
+                           : dyn_accel(lf, p.load.f ? p.load.f[i] : 0.0, r, p.m[i]);
         if (p.flags & DYN_COMPLETE) v = dyn_kick(v, a, p.half_dt);
     } else {
         a = p.a[i];
@@ -101,9 +107,7 @@ enum {
 
 struct FoStage {
     double mut_dt, mu, nu;      // mu_j w1 dt, mu_j, nu_j (stage 1: w1 dt; mu and nu are not read)
-    const double* f;            // load, S N (null: zero)
-    const double* lf;           // load factors on the device (null: 1) ...
-    unsigned long long lf_count, step;   // ... lf[min(step, lf_count - 1)], step the index of the state the step starts from
+    StepLoad load;              // load.step: the index of the state the step starts from
     const double* m;            // row-sum lumped mass, S N
     const unsigned char* dmask; // N membership flags of the Dirichlet nodes (null: none)
     double *u, *prev;           // S N each: the context's u holds Y_{j-1} and takes Y_j; prev holds Y_{j-2}
@@ -115,13 +119,13 @@ struct FoStage {
 // one dof of a stage: returns the dof's m y^2 (FO_STORE, else 0); a Dirichlet dof keeps its u
 __device__ __forceinline__ double fo_dof(const FoStage& p, size_t i, bool fixed, double lf, double r) {
     if (p.flags & FO_RATE) {
-        p.rate[i] = fixed ? 0.0 : dyn_accel(lf, p.f ? p.f[i] : 0.0, r, p.m[i]);
+        p.rate[i] = fixed ? 0.0 : dyn_accel(lf, p.load.f ? p.load.f[i] : 0.0, r, p.m[i]);
         return 0.0;
     }
     const double m = p.m[i], u = p.u[i];
     double y = u;
     if (!fixed) {
-        const double w = dyn_accel(lf, p.f ? p.f[i] : 0.0, r, m);
+        const double w = dyn_accel(lf, p.load.f ? p.load.f[i] : 0.0, r, m);
         y = (p.flags & FO_FIRST) ? fma(p.mut_dt, w, u) : fma(p.mut_dt, w, fma(p.mu, u, p.nu * p.prev[i]));
         if (p.flags & FO_KEEP) p.prev[i] = u;
         p.u[i] = y;
