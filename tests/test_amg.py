@@ -11,6 +11,9 @@ import scipy.sparse.linalg as spla
 import fenris_amd as fa
 from fenris_amd import _ffi, quadrature  # noqa: F401
 
+from amg_reference import (_key, _node_graph, _np_aggregate, _np_cheb, _np_lambda, _np_pcg, _np_vcycle, _restate, _rigid, _rowmax,  # noqa: F401
+                           _tentative)
+
 FH_BAD_ARGUMENT, FH_INVALID_STATE, FH_UNSUPPORTED = 2, 5, 6
 OPS = {"laplace": fa.LaplaceOperator(), "elastic": fa.MaterialEllipticOperator(fa.LinearElasticMaterial()),
        "neo_hookean": fa.MaterialEllipticOperator(fa.NeoHookeanMaterial())}
@@ -68,199 +71,6 @@ def _system(engine, m, op, clamp=True, u=None, clamp_width=1e-9):
     if len(nodes):
         engine.apply_dirichlet_csr_dev(csr.values, nodes)
     return asm, csr, nodes, s
-
-
-def _node_graph(A, b):
-    """node graph of the nonzero off-diagonal blocks of a scalar CSR with b x b blocks"""
-    Ac = abs(A).tocsr()
-    Ac.eliminate_zeros()
-    Ac = Ac.tocoo()
-    G = sp.csr_matrix((np.ones(Ac.nnz), (Ac.row // b, Ac.col // b)), shape=(A.shape[0] // b,) * 2)
-    G.setdiag(0)
-    G.eliminate_zeros()
-    return G
-
-
-def _tentative(agg, B, b, nb):
-    """T and the coarse B by modified Gram-Schmidt per aggregate, with the documented drop rule"""
-    N = len(agg)
-    nagg = int(agg.max()) + 1 if (agg >= 0).any() else 0
-    T = np.zeros((N * b, nb))
-    Bc = np.zeros((nagg * nb, nb))
-    for J in range(nagg):
-        rows = (b * np.where(agg == J)[0][:, None] + np.arange(b)).ravel()
-        Q = B[rows].copy()
-        Rm = np.zeros((nb, nb))
-        for k in range(nb):
-            n0 = np.linalg.norm(Q[:, k])
-            for j in range(k):
-                r = Q[:, j] @ Q[:, k]
-                Q[:, k] -= r * Q[:, j]
-                Rm[j, k] = r
-            n1 = np.linalg.norm(Q[:, k])
-            if not n1 > 1e-10 * n0:
-                Q[:, k] = 0.0
-            else:
-                Q[:, k] /= n1
-                Rm[k, k] = n1
-        T[rows] = Q
-        Bc[J * nb:(J + 1) * nb] = Rm
-    # block column agg(i) of node i's rows
-    rr = np.repeat(np.arange(N * b), nb)
-    node = rr // b
-    cc = np.where(agg[node] >= 0, agg[node] * nb, 0) + np.tile(np.arange(nb), N * b)
-    Tf = sp.csr_matrix((T.ravel() * (agg[node] >= 0), (rr, cc)), shape=(N * b, nagg * nb))
-    Tf.eliminate_zeros()
-    return Tf, Bc
-
-
-def _rigid(m):
-    x = m.vertices - m.vertices.mean(axis=0)
-    N, d = x.shape
-    if d == 2:
-        B = np.zeros((2 * N, 3))
-        B[0::2, 0] = 1
-        B[1::2, 1] = 1
-        B[0::2, 2] = -x[:, 1]
-        B[1::2, 2] = x[:, 0]
-        return B
-    B = np.zeros((3 * N, 6))
-    for a in range(3):
-        B[a::3, a] = 1
-    B[1::3, 3], B[2::3, 3] = -x[:, 2], x[:, 1]
-    B[0::3, 4], B[2::3, 4] = x[:, 2], -x[:, 0]
-    B[0::3, 5], B[1::3, 5] = -x[:, 1], x[:, 0]
-    return B
-
-
-def _key(n):
-    """the documented priority ((h(i) & 0x7fffffff) << 32) | i"""
-    i = np.arange(n, dtype=np.uint64)
-    m = np.uint64(0xFFFFFFFF)
-    h = i.copy()
-    with np.errstate(over="ignore"):
-        h ^= h >> np.uint64(16)
-        h = (h * np.uint64(0x7FEB352D)) & m
-        h ^= h >> np.uint64(15)
-        h = (h * np.uint64(0x846CA68B)) & m
-        h ^= h >> np.uint64(16)
-    return ((h & np.uint64(0x7FFFFFFF)) << np.uint64(32)) | i
-
-
-def _rowmax(G, v):
-    """max of v over each row's columns (0 for an empty row); v >= 0 and exact in float64"""
-    M = G.multiply(v[None, :]).tocsr()
-    return np.asarray(M.max(axis=1).toarray()).ravel()
-
-
-def _np_aggregate(A, b):
-    """the documented aggregation (theta = 0): aggregates (-1: isolated) and roots"""
-    G = _node_graph(A, b)
-    G.data[:] = 1.0
-    N = G.shape[0]
-    iso = np.diff(G.indptr) == 0
-    rank = np.empty(N, dtype=np.int64)
-    rank[np.argsort(_key(N))] = np.arange(N)
-    state = np.where(iso, 3, 0)
-    while (state == 0).any():
-        v = np.where(state == 0, rank + 1.0, np.where(state == 1, N + 2.0, 0.0))
-        v1 = np.maximum(v, _rowmax(G, v))
-        v2 = np.maximum(v1, _rowmax(G, v1))
-        und = state == 0
-        state[und & (v2 == rank + 1.0)] = 1
-        state[und & (v2 == N + 2.0)] = 2
-    roots = np.where(state == 1)[0]
-    rid = np.full(N, -1)
-    rid[roots] = np.arange(len(roots))
-    agg = np.full(N, -1)
-    agg[roots] = rid[roots]
-    Gr = G @ sp.diags((state == 1) * (rank + 1.0))
-    best = _rowmax(Gr, np.ones(N))   # (the column values already carry rank + 1)
-    Gr = Gr.tocsr()
-    for i in np.where((state == 2) & (best > 0))[0]:
-        cols = Gr.indices[Gr.indptr[i]:Gr.indptr[i + 1]]
-        vals = Gr.data[Gr.indptr[i]:Gr.indptr[i + 1]]
-        agg[i] = rid[cols[np.argmax(vals)]]
-    agg0 = agg.copy()
-    for i in np.where((agg0 < 0) & ~iso)[0]:
-        cols = G.indices[G.indptr[i]:G.indptr[i + 1]]
-        cols = cols[agg0[cols] >= 0]
-        agg[i] = agg0[cols[np.argmax(rank[cols])]]
-    return agg, roots
-
-
-def _np_lambda(A, b, iso, steps=10):
-    """the documented estimate: `steps` Jacobi-PCG / Lanczos steps from the fixed start vector"""
-    n = A.shape[0]
-    with np.errstate(over="ignore"):
-        h = np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(0x632BE59BD9B4E019)
-        h ^= h >> np.uint64(31)
-        h *= np.uint64(0xBF58476D1CE4E5B9)
-        h ^= h >> np.uint64(29)
-    v = 2.0 * ((h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53) - 1.0
-    v[np.repeat(iso, b)] = 0.0
-    d = A.diagonal()
-    dinv = np.where(d != 0, 1.0 / np.where(d != 0, d, 1.0), 0.0)
-    r = v.copy()
-    z = dinv * r
-    p = z.copy()
-    zr = z @ r
-    al, be = [], []
-    for k in range(steps):
-        if not zr > 0:
-            break
-        Ap = A @ p
-        a = zr / (p @ Ap)
-        al.append(a)
-        r = r - a * Ap
-        z = dinv * r
-        zr1 = z @ r
-        bt = zr1 / zr
-        zr = zr1
-        if k + 1 == steps or not zr > 0:
-            break
-        be.append(bt)
-        p = z + bt * p
-    k = len(al)
-    T = np.zeros((k, k))
-    for i in range(k):
-        T[i, i] = 1.0 / al[i] + (be[i - 1] / al[i - 1] if i else 0.0)
-        if i + 1 < k:
-            T[i, i + 1] = T[i + 1, i] = np.sqrt(be[i]) / al[i]
-    return float(np.linalg.eigvalsh(T).max())
-
-
-def _restate(amg, B0, A0=None, b0=None):
-    """per level: (A, P, T, B, Bc, agg, lambda) restated from the documented formulas.  With amg: the device's fine A, aggregates and lambda;
-    with A0 (amg None): everything on the CPU (aggregation, the eigenvalue estimate), coarsening to at most 4096 dofs"""
-    A = amg.level_matrix(0, "A") if amg is not None else A0
-    A = A.tocsr()
-    A.eliminate_zeros()
-    B = B0
-    b = amg.level_info(0)["block_size"] if amg is not None else b0
-    out = []
-    l = 0
-    while (amg is not None and l < amg.num_levels - 1) or (amg is None and A.shape[0] > 4096):
-        nb = B.shape[1]
-        if amg is not None:
-            agg, lam = amg.aggregates(l), amg.level_info(l)["lambda_max"]
-        else:
-            agg, _ = _np_aggregate(A, b)
-            lam = _np_lambda(A, b, agg < 0)
-        T, Bc = _tentative(agg, B, b, nb)
-        d = A.diagonal()
-        dinv = np.where(d != 0, 1.0 / np.where(d != 0, d, 1.0), 0.0)
-        omega = 4.0 / (3.0 * lam)
-        P = (T - omega * sp.diags(dinv) @ (A @ T)).tocsr()
-        iso = np.repeat(agg < 0, b)
-        P = (sp.diags((~iso).astype(float)) @ P).tocsr()
-        out.append((A, P, T, B, Bc, agg, lam))
-        A = (P.T @ (A @ P)).tocsr()
-        B = Bc
-        b = nb
-        l += 1
-    out.append((A, None, None, B, None, None, 0.0))
-    return out
 
 
 def _rel(X, Y):
@@ -355,72 +165,6 @@ def test_parity_with_numpy(engine, name, k, op, ns):
     zn = _np_vcycle(levels, r)
     assert np.linalg.norm(z.cpu().numpy() - zn) <= 1e-11 * np.linalg.norm(zn)
     amg.close()
-
-
-def _np_cheb(A, dinv, lam, b, x, zero, degree=3, rng_=15.0):
-    hi, lo = 1.1 * lam, lam / rng_
-    theta, delta = 0.5 * (hi + lo), 0.5 * (hi - lo)
-    if zero:
-        x = np.zeros_like(b)
-    r = b - A @ x
-    d = dinv * r / theta
-    rho = delta / theta
-    for k in range(1, degree + 1):
-        x = x + d
-        if k < degree:
-            r = r - A @ d
-            rho1 = 1.0 / (2.0 * theta / delta - rho)
-            d = rho1 * rho * d + 2.0 * rho1 / delta * dinv * r
-            rho = rho1
-    return x
-
-
-def _np_vcycle(levels, b, l=0):
-    """the documented V-cycle on restated levels"""
-    A = levels[l][0]
-    if l == len(levels) - 1:
-        Ad = A.toarray()
-        act = np.diag(Ad) != 0
-        x = np.zeros_like(b)
-        x[act] = np.linalg.solve(Ad[np.ix_(act, act)], b[act])
-        return x
-    P, agg, lam = levels[l][1], levels[l][5], levels[l][6]
-    bs = A.shape[0] // len(agg)
-    d = A.diagonal()
-    dinv = np.where(d != 0, 1.0 / np.where(d != 0, d, 1.0), 0.0)
-    x = _np_cheb(A, dinv, lam, b, None, True)
-    xc = _np_vcycle(levels, P.T @ (b - A @ x), l + 1)
-    x = x + P @ xc
-    x = _np_cheb(A, dinv, lam, b, x, False)
-    for i in np.where(agg < 0)[0]:   # isolated nodes: A_ii^-1 b_i
-        rows = slice(bs * i, bs * (i + 1))
-        x[rows] = np.linalg.solve(A[rows, rows].toarray(), b[rows])
-    return x
-
-
-def _np_pcg(levels, b, tol=1e-8):
-    """PCG with the restated V-cycle, as fh_cg_solve runs it: the iteration count"""
-    A = levels[0][0]
-    x = np.zeros_like(b)
-    r = b.copy()
-    z = _np_vcycle(levels, r)
-    p = z.copy()
-    zr = z @ r
-    bn = np.linalg.norm(b)
-    it = 0
-    while np.linalg.norm(r) > tol * bn:
-        Ap = A @ p
-        a = zr / (p @ Ap)
-        x += a * p
-        r -= a * Ap
-        it += 1
-        z = _np_vcycle(levels, r)
-        zr1 = z @ r
-        p = z + (zr1 / zr) * p
-        zr = zr1
-        if it > 500:
-            break
-    return it
 
 
 @pytest.mark.gpu
