@@ -164,6 +164,7 @@ _SIGS = {
     "fh_cg_solve": (C.c_int, [C.c_void_p, f64p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_cg_solve_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_set_operator_dirichlet_nodes": (C.c_int, [C.c_void_p, u64p, C.c_uint64]),
+    "fh_set_operator_dirichlet_dofs": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_uint8), C.c_uint64]),
     "fh_apply_operator_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fh_operator_diagonal_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_cg_solve_matrix_free": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
@@ -237,6 +238,8 @@ _SIGS = {
     "fh_assemble_element_matrices": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, f64p]),
     "fh_apply_dirichlet_csr_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint64]),
     "fh_apply_dirichlet_rhs_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint64]),
+    "fh_apply_dirichlet_dofs_csr_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.POINTER(C.c_uint8), C.c_uint64]),
+    "fh_apply_dirichlet_dofs_rhs_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.POINTER(C.c_uint8), C.c_uint64]),
     "fh_gauss": (C.c_int, [C.c_uint32, f64p, f64p]),
     "fh_quadrilateral_gauss": (C.c_int, [C.c_uint32, f64p, f64p]),
     "fh_hexahedron_gauss": (C.c_int, [C.c_uint32, f64p, f64p]),

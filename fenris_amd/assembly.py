@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _ffi
 from . import contact as _contact
+from . import dirichlet as _dirichlet
 from .compose import _Composable, is_composed
 from . import compose as _compose
 from ._ffi import (ASSEMBLE_OVERWRITE, SCATTER_ATOMIC, SCATTER_COLORED, SCATTER_GATHER, FenrisError,
@@ -530,9 +531,25 @@ class Engine:
 
     # matrix-free operator (FH_LAPLACE, FH_LINEAR_ELASTIC): no pattern, no values
     def set_operator_dirichlet_nodes(self, nodes):
+        """the node set of the matrix-free routes (None: none); a DofSet (fenris_amd.dirichlet) goes to set_operator_dirichlet_dofs"""
+        if isinstance(nodes, _dirichlet.DofSet):
+            return self._set_operator_dirichlet_masks(nodes.nodes, nodes.masks)
         self._mf_bound = None   # (MatrixFreeOperator: no operator's nodes are bound any more)
         nodes = _ffi.as_u64(nodes if nodes is not None else [])
         self._check(self._lib.fh_set_operator_dirichlet_nodes(self._h, _ffi.up(nodes) if len(nodes) else None, len(nodes)))
+
+    def set_operator_dirichlet_dofs(self, nodes, components):
+        """single components of the listed nodes (fh_set_operator_dirichlet_dofs): components is an (n, S) boolean array or a sequence of
+        component indices applied to every node; replaces the set, nodes None clears it"""
+        if nodes is None:
+            return self.set_operator_dirichlet_nodes(None)
+        self._set_operator_dirichlet_masks(*_dirichlet.dof_masks(nodes, components))
+
+    def _set_operator_dirichlet_masks(self, nodes, masks):
+        self._mf_bound = None
+        nodes, masks = _ffi.as_u64(nodes), np.ascontiguousarray(masks, dtype=np.uint8)
+        n = len(nodes)
+        self._check(self._lib.fh_set_operator_dirichlet_dofs(self._h, _ffi.up(nodes) if n else None, _u8p(masks) if n else None, n))
 
     def apply_operator_dev(self, x_t, y_t):
         self._check(self._lib.fh_apply_operator_dev(self._h, C.c_void_p(x_t.data_ptr()), C.c_void_p(y_t.data_ptr())))
@@ -639,6 +656,14 @@ class Engine:
         nodes = _ffi.as_u64(nodes)
         self._check(self._lib.fh_apply_dirichlet_rhs_dev(self._h, C.c_void_p(rhs_t.data_ptr()), _ffi.up(nodes), len(nodes)))
 
+    def apply_dirichlet_dofs_csr_dev(self, values_t, nodes, masks):
+        nodes, masks = _ffi.as_u64(nodes), np.ascontiguousarray(masks, dtype=np.uint8)
+        self._check(self._lib.fh_apply_dirichlet_dofs_csr_dev(self._h, C.c_void_p(values_t.data_ptr()), _ffi.up(nodes), _u8p(masks), len(nodes)))
+
+    def apply_dirichlet_dofs_rhs_dev(self, rhs_t, nodes, masks):
+        nodes, masks = _ffi.as_u64(nodes), np.ascontiguousarray(masks, dtype=np.uint8)
+        self._check(self._lib.fh_apply_dirichlet_dofs_rhs_dev(self._h, C.c_void_p(rhs_t.data_ptr()), _ffi.up(nodes), _u8p(masks), len(nodes)))
+
 
 class CgSolveError(FenrisError):
     """SolveError of fenris-sparse/src/cg.rs:277-318 (kind + iterations so far)"""
@@ -649,6 +674,10 @@ class CgSolveError(FenrisError):
         super().__init__(code, message)
         self.kind = self.KINDS.get(code, "?")
         self.num_iterations = num_iterations
+
+
+def _u8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
 def _is_torch(x):
@@ -1158,6 +1187,30 @@ def apply_homogeneous_dirichlet_bc_csr(csr: CsrMatrix, nodes, solution_dim, elem
         csr.values[:] = t.cpu().numpy()
 
 
+def apply_homogeneous_dirichlet_dofs_csr(csr: CsrMatrix, nodes, components, element_assembler):
+    """apply_homogeneous_dirichlet_bc_csr for single components: the rows and columns of the listed dofs are zeroed inside their node
+    blocks, their diagonal is the same scale.  components: an (n, S) boolean array or component indices applied to every node"""
+    eng = element_assembler.engine
+    nodes, masks = _dirichlet.dof_masks(nodes, components)
+    if _is_torch(csr.values):
+        eng.apply_dirichlet_dofs_csr_dev(csr.values, nodes, masks)
+    else:
+        import torch
+
+        t = torch.from_numpy(csr.values).to(f"cuda:{eng.device}")
+        eng.apply_dirichlet_dofs_csr_dev(t, nodes, masks)
+        csr.values[:] = t.cpu().numpy()
+
+
+def apply_homogeneous_dirichlet_dofs_rhs(rhs, nodes, components, element_assembler):
+    """zeroes the listed dofs of rhs (a numpy array or a device tensor, in place)"""
+    nodes, masks = _dirichlet.dof_masks(nodes, components)
+    if _is_torch(rhs):
+        element_assembler.engine.apply_dirichlet_dofs_rhs_dev(rhs, nodes, masks)
+    else:
+        rhs.reshape(-1)[_dirichlet.DofSet(nodes, masks).dof_indices(element_assembler.solution_dim())] = 0.0
+
+
 def apply_homogeneous_dirichlet_bc_rhs(rhs, nodes, solution_dim):
     """global.rs:479-495 (host arrays: trivial)"""
     nodes = np.asarray(nodes, dtype=np.int64)
@@ -1197,6 +1250,12 @@ class MatrixFreeOperator:
         self._nodes = None if nodes is None else _ffi.as_u64(nodes).copy()
         self._bind(force=True)
         return self
+
+    def with_dirichlet_dofs(self, nodes, components):
+        """single components of the listed nodes (rollers): components is an (n, S) boolean array or component indices applied to every
+        node, so with_dirichlet_dofs(face_x0, [0]) holds u_x on that face.  Calls accumulate (with what with_dirichlet_nodes set, every
+        component of those nodes); with_dirichlet_nodes starts over.  Returns self"""
+        return _dirichlet.with_dirichlet_dofs(self, nodes, components)
 
     def with_multigrid(self, mg):
         """a GeometricMultigrid (fenris_amd.multigrid) over this operator's assembler: cg_solve then defaults to PRECOND_MULTIGRID"""
@@ -1441,6 +1500,10 @@ class MatrixFreeNewton:
         self._nodes = None if nodes is None else _ffi.as_u64(nodes).copy()
         self._bind(force=True)
         return self
+
+    def with_dirichlet_dofs(self, nodes, components):
+        """single components held at the values u has on entry to solve (MatrixFreeOperator.with_dirichlet_dofs); calls accumulate; returns self"""
+        return _dirichlet.with_dirichlet_dofs(self, nodes, components)
 
     def with_load(self, f):
         """the load f of r(u) = f (numpy array or device tensor; None: zero); returns self"""

@@ -61,7 +61,7 @@ static __global__ void __launch_bounds__(256) k_amg_strength(int N, int R, const
             any = any || nf > 0.0;
             strong[r0 + kk] = (j != (unsigned)i && nf > 0.0 && nf >= theta * sqrt(dnorm[i] * dnorm[j])) ? 1 : 0;
         }
-        iso[i] = any ? 0 : 1;
+        iso[i] = any ? 0 : 0xff;   // (all ones: mg_estimate_lambda reads the flags as Dirichlet bytes, every component of the block held)
     }
 }
 

@@ -60,14 +60,14 @@ __global__ void __launch_bounds__(256) k_block_gram(int n, int per, BlockCols S,
             const int r = e % R, k = e / R;
             const long long row = r0 + r;
             double v = 0.0;
-            if (row < hi && !(mask && mask[(int)row / sdim])) v = S.col(k)[row];
+            if (row < hi && !dof_fixed_at(mask, (int)row, sdim)) v = S.col(k)[row];
             sS[r * LD + k] = v;
         }
         for (int e = tid; e < R * q; e += 256) {
             const int r = e % R, k = e / R;
             const long long row = r0 + r;
             double v = 0.0;
-            if (row < hi && !(mask && mask[(int)row / sdim])) v = T.col(k)[row];
+            if (row < hi && !dof_fixed_at(mask, (int)row, sdim)) v = T.col(k)[row];
             sT[r * LD + k] = v;
         }
         __syncthreads();
@@ -157,7 +157,7 @@ static __global__ void __launch_bounds__(256) k_block_residual(int n, const doub
     double s[3] = {0.0, 0.0, 0.0};
     for (long long row = (long long)blockIdx.x * 256 + threadIdx.x; row < n; row += (long long)gridDim.x * 256) {
         double a = kx[row], b = mx[row];
-        if (mask && mask[(int)row / sdim]) { a = 0.0; b = 0.0; }
+        if (dof_fixed_at(mask, (int)row, sdim)) { a = 0.0; b = 0.0; }
         const double v = fma(-th, b, a);
         r[row] = v;
         s[0] = fma(v, v, s[0]);
@@ -189,13 +189,13 @@ __device__ __forceinline__ double block_hash_unit(unsigned long long row, unsign
 static __global__ void __launch_bounds__(256) k_block_fill(int n, long long ld, const unsigned char* mask, int sdim, double* X) {
     const int j = blockIdx.y;
     for (long long row = (long long)blockIdx.x * 256 + threadIdx.x; row < n; row += (long long)gridDim.x * 256)
-        X[(long long)j * ld + row] = (mask && mask[(int)row / sdim]) ? 0.0 : block_hash_unit((unsigned long long)row, (unsigned long long)j);
+        X[(long long)j * ld + row] = dof_fixed_at(mask, (int)row, sdim) ? 0.0 : block_hash_unit((unsigned long long)row, (unsigned long long)j);
 }
 // zero on the rows of Dirichlet nodes
 static __global__ void __launch_bounds__(256) k_block_mask(int n, long long ld, const unsigned char* mask, int sdim, double* X) {
     const int j = blockIdx.y;
     for (long long row = (long long)blockIdx.x * 256 + threadIdx.x; row < n; row += (long long)gridDim.x * 256)
-        if (mask[(int)row / sdim]) X[(long long)j * ld + row] = 0.0;
+        if (dof_fixed_at(mask, (int)row, sdim)) X[(long long)j * ld + row] = 0.0;
 }
 // W_a = dinv . R_{idx[a]} off the Dirichlet rows, 0 on them (the Jacobi preconditioner on the active columns)
 static __global__ void __launch_bounds__(256) k_block_jacobi(int n, long long ld, const double* dinv, const double* R, BlockIndex idx,
@@ -204,7 +204,7 @@ static __global__ void __launch_bounds__(256) k_block_jacobi(int n, long long ld
     const double* r = R + (long long)idx.v[a] * ld;
     double* w = W + (long long)a * ld;
     for (long long row = (long long)blockIdx.x * 256 + threadIdx.x; row < n; row += (long long)gridDim.x * 256)
-        w[row] = (mask && mask[(int)row / sdim]) ? 0.0 : dinv[row] * r[row];
+        w[row] = dof_fixed_at(mask, (int)row, sdim) ? 0.0 : dinv[row] * r[row];
 }
 
 }  // namespace fenris_hip

@@ -351,17 +351,19 @@ __global__ void __launch_bounds__(256) k_contact_gap(const ContactTable ct, int 
     if (node < num_nodes) gap[node] = contact_gap<D>(ct, node);
 }
 
-// y += (B + H) x 2^-e (xbits: mf_exponent of the operand the element pass of the map saw, may be null: the pass that finishes y multiplies by 2^e)
+// y += (B + H) x 2^-e (xbits: mf_exponent of the operand the element pass of the map saw, may be null: the pass that finishes y multiplies by 2^e);
+// the held components of x (dmask, may be null) read as zero, as the element pass read them
 template <int D>
-__global__ void __launch_bounds__(256) k_contact_apply(const ContactTable ct, int num_nodes, const double* x, const unsigned long long* xbits,
-                                                       double* y) {
+__global__ void __launch_bounds__(256) k_contact_apply(const ContactTable ct, int num_nodes, const double* x, const unsigned char* dmask,
+                                                       const unsigned long long* xbits, double* y) {
     const int node = blockIdx.x * 256 + threadIdx.x;
     if (node >= num_nodes) return;
     const int ex = mf_exponent(xbits);
+    const unsigned fixed = node_dmask(dmask, node);
     double v[D], s[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) {
-        v[c] = x[(size_t)node * D + c];
+        v[c] = comp_fixed(fixed, c) ? 0.0 : x[(size_t)node * D + c];
         s[c] = 0.0;
     }
     contact_apply<D>(ct, node, v, 1.0, s);

@@ -77,6 +77,18 @@ constexpr bool op_has_stress(int op) {
 // its stress is nonlinear in u: K depends on u, the tangent is not the operator
 constexpr bool op_depends_on_u(int op) { return op == FH_NEO_HOOKEAN || op == FH_STVK || op == FH_STABLE_NEO_HOOKEAN; }
 
+// The Dirichlet byte of a node (fh_ctx::mf_dmask) is the bitmask of its constrained components: bit j = component j is held; a node set
+// stores all ones.  dof_fixed: is component comp of node held (dmask may be null: nothing is); dof_fixed_at: the same of dof i = S node + comp.
+constexpr unsigned char DMASK_NODE = 0xff;
+// (a pass that visits a node once reads its byte once: node_dmask, then comp_fixed per component)
+__host__ __device__ __forceinline__ unsigned node_dmask(const unsigned char* dmask, size_t node) { return dmask ? dmask[node] : 0u; }
+__host__ __device__ __forceinline__ bool comp_fixed(unsigned bits, int comp) { return (bits >> comp) & 1u; }
+__host__ __device__ __forceinline__ bool dof_fixed(const unsigned char* dmask, size_t node, int comp) { return comp_fixed(node_dmask(dmask, node), comp); }
+__host__ __device__ __forceinline__ bool dof_fixed_at(const unsigned char* dmask, int i, int S) {
+    const int node = i / S;
+    return dof_fixed(dmask, (size_t)node, i - node * S);
+}
+
 enum { MODE_ATOMIC = 0, MODE_COLORED = 1, MODE_GATHER = 2, MODE_DUMP = 3 };
 
 // status words in device memory

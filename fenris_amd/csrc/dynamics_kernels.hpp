@@ -15,7 +15,7 @@ static __global__ void __launch_bounds__(256) k_dynamics_update(int n, int S, co
     __shared__ double red[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     double ke = 0.0;
-    if (i < n) ke = dyn_dof(p, (size_t)i, p.dmask && p.dmask[i / S], dyn_load_factor(p), (p.flags & DYN_ACCEL) ? r[i] : 0.0);
+    if (i < n) ke = dyn_dof(p, (size_t)i, dof_fixed_at(p.dmask, i, S), dyn_load_factor(p), (p.flags & DYN_ACCEL) ? r[i] : 0.0);
     if (p.flags & DYN_STORE) {
         const double tot = block_sum_256(ke, red);
         if (threadIdx.x == 0) p.ke_partial[blockIdx.x] = tot;
@@ -28,7 +28,7 @@ static __global__ void __launch_bounds__(256) k_first_order_update(int n, int S,
     __shared__ double red[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     double q = 0.0;
-    if (i < n) q = fo_dof(p, (size_t)i, p.dmask && p.dmask[i / S], dyn_load_factor(p), r[i]);
+    if (i < n) q = fo_dof(p, (size_t)i, dof_fixed_at(p.dmask, i, S), dyn_load_factor(p), r[i]);
     if (p.flags & FO_STORE) {
         const double tot = block_sum_256(q, red);
         if (threadIdx.x == 0) p.partial[blockIdx.x] = tot;
@@ -54,7 +54,7 @@ static __global__ void __launch_bounds__(256) k_newmark_predict(int n, int S, do
     if (i >= n) return;
     const double un = u[i];
     u_prev[i] = un;
-    const bool fixed = dmask && dmask[i / S];
+    const bool fixed = dof_fixed_at(dmask, i, S);
     if (fixed && bm_dir) {
         u_ref[i] = fma(c2, a[i], fma(dt, v[i], un));
         u[i] = fma(bm_g, bm_dir[i], bm_u0[i]);
@@ -73,7 +73,7 @@ static __global__ void __launch_bounds__(256) k_newmark_correct(int n, int S, in
                                                                 const double* u_prev, double* v, double* a, int moved) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    if (!moved && dmask && dmask[i / S]) {
+    if (!moved && dof_fixed_at(dmask, i, S)) {
         v[i] = 0.0;
         a[i] = 0.0;
         return;
@@ -93,7 +93,7 @@ static __global__ void __launch_bounds__(256) k_newmark_correct(int n, int S, in
 // y += s x on the free dofs: the damping term joining a summed residual or a right-hand side, and a_0 -= eta_m v_0
 static __global__ void __launch_bounds__(256) k_dynamics_axpy(int n, int S, double s, const unsigned char* dmask, const double* x, double* y) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n && !(dmask && dmask[i / S])) y[i] = fma(s, x[i], y[i]);
+    if (i < n && !dof_fixed_at(dmask, i, S)) y[i] = fma(s, x[i], y[i]);
 }
 // the folding of C, frozen at the start of an implicit step, into the Newton arguments.  With v_p = v_n + cv a_n (cv = dt (1 - gamma);
 // backward Euler is beta = gamma = 1 on its own predictor: cv = 0) the step's velocity is v_{n+1} = v_p + gamma / (beta dt) (u - u_ref), so
@@ -103,7 +103,7 @@ static __global__ void __launch_bounds__(256) k_damping_fold(int n, int S, doubl
                                                              const double* u_ref, const double* v, const double* a, double* u_ref2, double* w) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double vp = (dmask && dmask[i / S]) ? 0.0 : (cv != 0.0 ? fma(cv, a[i], v[i]) : v[i]);
+    const double vp = dof_fixed_at(dmask, i, S) ? 0.0 : (cv != 0.0 ? fma(cv, a[i], v[i]) : v[i]);
     const double ur = u_ref[i];
     u_ref2[i] = fma(-cref, vp, ur);
     w[i] = fma(b, vp, -gdt * ur);
@@ -127,19 +127,19 @@ static __global__ void __launch_bounds__(256) k_kinetic_partials(int n, const do
 static __global__ void __launch_bounds__(256) k_dynamics_rhs(int n, int S, const StepLoad l, const unsigned char* dmask, const double* r, double* b) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    b[i] = (dmask && dmask[i / S]) ? 0.0 : fma(load_factor_at(l, l.step), l.f ? l.f[i] : 0.0, -r[i]);
+    b[i] = dof_fixed_at(dmask, i, S) ? 0.0 : fma(load_factor_at(l, l.step), l.f ? l.f[i] : 0.0, -r[i]);
 }
 
 // x[i] *= s, or x[i] = 0 on the Dirichlet dofs (power iteration on the free dofs; s = 1: v of the Dirichlet dofs cleared; dmask null: the
 // scaled load of an implicit step)
 static __global__ void __launch_bounds__(256) k_dynamics_scale(int n, int S, double s, const unsigned char* dmask, double* x) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) x[i] = (dmask && dmask[i / S]) ? 0.0 : x[i] * s;
+    if (i < n) x[i] = dof_fixed_at(dmask, i, S) ? 0.0 : x[i] * s;
 }
 // x = y / m on the free dofs, 0 on the Dirichlet dofs (power iteration)
 static __global__ void __launch_bounds__(256) k_dynamics_divide(int n, int S, const unsigned char* dmask, const double* y, const double* m, double* x) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) x[i] = (dmask && dmask[i / S]) ? 0.0 : y[i] / m[i];
+    if (i < n) x[i] = dof_fixed_at(dmask, i, S) ? 0.0 : y[i] / m[i];
 }
 // the start vector of the power iteration: column 0 of fh_eigs_lowest's fill
 static __global__ void __launch_bounds__(256) k_dynamics_fill(int n, double* x) {

@@ -29,7 +29,7 @@ struct DynStep {
     double dt, half_dt;
     StepLoad load;              // load.step: the global index of the step whose acceleration is formed
     const double* m;            // row-sum lumped mass, S N
-    const unsigned char* dmask; // N membership flags of the Dirichlet nodes (null: none)
+    const unsigned char* dmask; // N Dirichlet bytes, the held components of each node (dof_fixed, device_common.hpp; null: none)
     double *u, *v, *a;          // S N each: the context's u; v holds v_h between the launches of a call
     double* ke_partial;         // DYN_STORE: one partial per workgroup
     int flags;
@@ -109,7 +109,7 @@ struct FoStage {
     double mut_dt, mu, nu;      // mu_j w1 dt, mu_j, nu_j (stage 1: w1 dt; mu and nu are not read)
     StepLoad load;              // load.step: the index of the state the step starts from
     const double* m;            // row-sum lumped mass, S N
-    const unsigned char* dmask; // N membership flags of the Dirichlet nodes (null: none)
+    const unsigned char* dmask; // N Dirichlet bytes, the held components of each node (dof_fixed, device_common.hpp; null: none)
     double *u, *prev;           // S N each: the context's u holds Y_{j-1} and takes Y_j; prev holds Y_{j-2}
     double* rate;               // FO_RATE
     double* partial;            // FO_STORE: one partial per workgroup

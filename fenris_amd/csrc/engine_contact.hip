@@ -167,11 +167,11 @@ int contact_add_force(fh_ctx* c, double* out_dev) {
     return FH_OK;
 }
 
-int contact_add_apply(fh_ctx* c, const double* x_dev, const unsigned long long* xbits, double* y_dev) {
+int contact_add_apply(fh_ctx* c, const double* x_dev, const unsigned char* dmask, const unsigned long long* xbits, double* y_dev) {
     const ContactTable t = contact_table(c);
     if (!t.count || c->N == 0) return FH_OK;
     by_dim(c, [&](auto d) {
-        hipLaunchKernelGGL((k_contact_apply<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, x_dev, xbits, y_dev);
+        hipLaunchKernelGGL((k_contact_apply<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, x_dev, dmask, xbits, y_dev);
     });
     HIP_TRY(c, hipGetLastError());
     // (behind mf_single, which names the element kernels it ran; with no element to run it names nothing)

@@ -201,7 +201,7 @@ int ensure_lumped(fh_dynamics* d, const char* who) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const int S = c->S();
     for (int i = 0; i < n; ++i)
-        if (!hm[(size_t)(i / S)] && !(h[(size_t)i] > 0.0))
+        if (!dof_fixed_at(hm.data(), i, S) && !(h[(size_t)i] > 0.0))
             return c->fail(FH_UNSUPPORTED, std::string(who) + ": the row-sum lumped mass of dof " + std::to_string(i) + " (node " + std::to_string(i / S) +
                                                ") is " + std::to_string(h[(size_t)i]) + ", not positive: the explicit schemes need another lumping on this element kind");
     d->m_key = k;

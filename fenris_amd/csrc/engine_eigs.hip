@@ -368,14 +368,15 @@ int eigs_lowest_dev(fh_ctx* c, uint32_t m32, double shift, int preconditioner, d
     e.shift = shift;
     e.precond = preconditioner;
     e.dmask = c->mf_num_dirichlet ? c->mf_dmask.p : nullptr;
-    uint64_t free_nodes = c->N;
+    uint64_t free_dofs = (uint64_t)e.S * c->N;
     if (e.dmask) {
         std::vector<unsigned char> h(c->N);
         HIP_TRY(c, hipMemcpyAsync(h.data(), c->mf_dmask.p, c->N, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        free_nodes = (uint64_t)std::count(h.begin(), h.end(), (unsigned char)0);
+        for (uint64_t i = 0; i < c->N; ++i)
+            for (int k = 0; k < e.S; ++k) free_dofs -= dof_fixed(h.data(), i, k) ? 1u : 0u;
     }
-    if ((uint64_t)e.m * 3 > free_nodes * (uint64_t)e.S) return c->fail(FH_BAD_ARGUMENT, "fh_eigs_lowest: m must not exceed a third of the free dofs");
+    if ((uint64_t)e.m * 3 > free_dofs) return c->fail(FH_BAD_ARGUMENT, "fh_eigs_lowest: m must not exceed a third of the free dofs");
     const int n = e.n, m = e.m;
     const size_t block = (size_t)n * m;
     for (DevBuf<double>* b : {&e.X, &e.KX, &e.MX, &e.Xn, &e.KXn, &e.MXn, &e.W, &e.KW, &e.MW, &e.P, &e.KP, &e.MP, &e.Pn, &e.KPn, &e.MPn, &e.R, &e.T1})

@@ -473,8 +473,9 @@ struct fh_ctx {
     bool keep_status = false;    // ... over a rule-set table: the status slot is reset once in front of the group walk, not per group
     // matrix-free map (engine_vector.hip): homogeneous Dirichlet nodes (fh_set_operator_dirichlet_nodes; fh_set_mesh* clears them),
     // the scale of their rows (valid for mf_scale_key), the operand the element pass reads
-    DevBuf<unsigned char> mf_dmask;    // N membership flags
+    DevBuf<unsigned char> mf_dmask;    // N bytes: the bitmask of each node's constrained components (device_common.hpp, dof_fixed), all ones for a node set
     uint64_t mf_num_dirichlet = 0;
+    uint64_t mf_comp_node[8] = {};     // [j]: 1 + the first listed node whose mask, other than all ones, holds component j (0: none) -- mf_ready refuses j >= S
     DevBuf<double> mf_scale;           // 1 double
     DevBuf<double> mf_xm;              // S N
     DevBuf<unsigned long long> mf_bits;   // |operand|_inf (k_mf_absmax)
@@ -490,7 +491,7 @@ struct fh_ctx {
     DevBuf<double> mf_mass;
     unsigned long long geom_gen = 0;   // counts fh_update_vertices calls
     unsigned long long u_gen = 0;      // counts fh_set_u* calls
-    unsigned long long dirichlet_gen = 0;   // counts fh_set_operator_dirichlet_nodes calls
+    unsigned long long dirichlet_gen = 0;   // counts fh_set_operator_dirichlet_nodes / _dofs calls
     // penalty contact (engine_contact.hip): the obstacles of fh_set_obstacles as the kernels take them (count == 0: none), the node weights,
     // contact_gen counts the calls.  mf_scope: the scope of the matrix-free map being formed -- the operator's entry points (MF_OPERATOR)
     // leave the term out, everything else is the tangent and includes it.
@@ -597,6 +598,13 @@ int build_source_adjacency(fh_ctx* c);
 int host_offsets(fh_ctx* c);
 int build_pattern(fh_ctx* c);
 int check_ready(fh_ctx* c, const char* who, bool need_pattern);
+// the Dirichlet bytes of a (node, component mask) list into dm_dev (zeroed by the caller, N rounded up to a multiple of 4 bytes): the masks of a
+// node listed twice are OR-ed; components null = every component (all ones).  Checks the list (FH_BAD_ARGUMENT: a node >= N, a mask of 0) and
+// leaves in comp_node[j] 1 + the first node whose mask, other than all ones, holds component j.  Enqueued on the context's stream, which it waits for.
+int dirichlet_masks_to_device(fh_ctx* c, const char* who, const uint64_t* nodes, const uint8_t* components, uint64_t num_nodes,
+                              unsigned char* dm_dev, uint64_t (&comp_node)[8]);
+// FH_BAD_ARGUMENT with the node's name when comp_node (above) holds a component >= S
+int dirichlet_components_fit(fh_ctx* c, const char* who, const uint64_t (&comp_node)[8], int S);
 void fill_common(fh_ctx* c, KArgs& a);
 int reset_status(fh_ctx* c);
 int read_status(fh_ctx* c, uint64_t* failed);
@@ -683,7 +691,7 @@ int mass_full(fh_ctx* c, const double* x, const unsigned char* dmask, double* ou
 ContactTable contact_table(const fh_ctx* c);
 int contact_blocked(fh_ctx* c, const char* who);
 int contact_add_force(fh_ctx* c, double* out_dev);
-int contact_add_apply(fh_ctx* c, const double* x_dev, const unsigned long long* xbits, double* y_dev);
+int contact_add_apply(fh_ctx* c, const double* x_dev, const unsigned char* dmask, const unsigned long long* xbits, double* y_dev);
 int contact_add_diagonal(fh_ctx* c, double* diag_dev);
 int contact_add_energy(fh_ctx* c, double* energy);
 void contact_clear(fh_ctx* c);

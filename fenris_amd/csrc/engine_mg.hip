@@ -533,9 +533,11 @@ int fh_mg_create(fh_ctx* fine, uint64_t num_coarse, fh_ctx* const* coarse, const
             if (inj[j] == ~0u) return fine->fail(FH_BAD_ARGUMENT, "fh_mg_create: a coarse node has no injected fine copy (a row with one parent of weight 1)");
         rc = dirichlet_flags(ctx[l], dm_f);
         if (rc) return fine->fail(rc, ctx[l]->err);
+        const unsigned comps = (1u << ctx[l]->S()) - 1u;   // (a node set holds all ones: only the components of the solution count)
         for (uint64_t j = 0; j < Nc; ++j)
-            if (dm_c[j] != dm_f[inj[j]])
-                return fine->fail(FH_BAD_ARGUMENT, "fh_mg_create: a coarse node must be Dirichlet exactly when its injected fine node is");
+            if ((dm_c[j] & comps) != (dm_f[inj[j]] & comps))
+                return fine->fail(FH_BAD_ARGUMENT, "fh_mg_create: a coarse node must constrain exactly the components its injected fine node does (coarse node " +
+                                                       std::to_string(j) + " of level " + std::to_string(l - 1) + ")");
         // the transpose, rows in ascending fine index
         for (uint64_t j = 0; j < Nc; ++j) cnt[j + 1] += cnt[j];
         std::vector<unsigned> r_off(cnt.begin(), cnt.end()), r_idx(p_idx.size()), fill(cnt.begin(), cnt.end() - 1);

@@ -3,6 +3,43 @@
 
 #include "engine_internal.hpp"
 
+// (dm_dev null: the checks alone)
+extern "C++" int dirichlet_masks_to_device(fh_ctx* c, const char* who, const uint64_t* nodes, const uint8_t* components, uint64_t num_nodes,
+                                           unsigned char* dm_dev, uint64_t (&comp_node)[8]) {
+    std::fill(comp_node, comp_node + 8, (uint64_t)0);
+    for (uint64_t i = 0; i < num_nodes; ++i) {
+        if (nodes[i] >= c->N) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": Dirichlet node " + std::to_string(nodes[i]) + " out of range");
+        if (!components) continue;
+        const unsigned m = components[i];
+        if (m == 0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": node " + std::to_string(nodes[i]) + " has a component mask of 0");
+        if (m == DMASK_NODE) continue;
+        for (int j = 0; j < 8; ++j)
+            if (((m >> j) & 1u) && !comp_node[j]) comp_node[j] = nodes[i] + 1;
+    }
+    if (!dm_dev || !num_nodes) return FH_OK;
+    DevBuf<unsigned long long> dn;
+    DevBuf<unsigned char> dc;
+    HIP_TRY(c, dn.alloc((size_t)num_nodes));
+    HIP_TRY(c, hipMemcpyAsync(dn.p, nodes, sizeof(uint64_t) * num_nodes, hipMemcpyHostToDevice, c->stream));
+    if (components) {
+        HIP_TRY(c, dc.alloc((size_t)num_nodes));
+        HIP_TRY(c, hipMemcpyAsync(dc.p, components, (size_t)num_nodes, hipMemcpyHostToDevice, c->stream));
+    }
+    hipLaunchKernelGGL(k_mark_dofs, dim3(grid_for((long long)num_nodes, 256, 1 << 30)), dim3(256), 0, c->stream, dn.p,
+                       components ? (const unsigned char*)dc.p : nullptr, (long long)num_nodes, dm_dev);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dn and dc are released on return)
+    return FH_OK;
+}
+
+extern "C++" int dirichlet_components_fit(fh_ctx* c, const char* who, const uint64_t (&comp_node)[8], int S) {
+    for (int j = S < 0 ? 0 : S; j < 8; ++j)
+        if (comp_node[j])
+            return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": Dirichlet node " + std::to_string(comp_node[j] - 1) + " constrains component " +
+                                                std::to_string(j) + ", the operator's solution has " + std::to_string(S));
+    return FH_OK;
+}
+
 extern "C" {
 int fh_apply_dirichlet_csr_dev(fh_ctx* c, double* values_dev, const uint64_t* nodes, uint64_t n) {
     if (!c) return FH_BAD_ARGUMENT;
@@ -37,6 +74,61 @@ int fh_apply_dirichlet_csr_dev(fh_ctx* c, double* values_dev, const uint64_t* no
                            c->ncols.p, N, S, dm.p, values_dev, scale.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the temporaries are released on return)
+    return FH_OK;
+}
+
+int fh_apply_dirichlet_dofs_csr_dev(fh_ctx* c, double* values_dev, const uint64_t* nodes, const uint8_t* components, uint64_t n) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    if (!c->has_pattern) return c->fail(FH_INVALID_STATE, "fh_apply_dirichlet_dofs_csr_dev: call fh_pattern first");
+    if (!values_dev || (n && (!nodes || !components))) return c->fail(FH_BAD_ARGUMENT, "fh_apply_dirichlet_dofs_csr_dev: null pointer");
+    const int S = c->S(), N = (int)c->N;
+    DevBuf<unsigned char> dm;
+    DevBuf<unsigned long long> first;
+    DevBuf<double> scale;
+    const size_t bytes = ((size_t)N + 4) & ~(size_t)3;
+    HIP_TRY(c, dm.alloc(bytes));
+    HIP_TRY(c, first.alloc(1));
+    HIP_TRY(c, scale.alloc(1));
+    HIP_TRY(c, hipMemsetAsync(dm.p, 0, bytes, c->stream));
+    uint64_t comp_node[8];
+    int rc = dirichlet_masks_to_device(c, "fh_apply_dirichlet_dofs_csr_dev", nodes, components, n, dm.p, comp_node);
+    if (!rc) rc = dirichlet_components_fit(c, "fh_apply_dirichlet_dofs_csr_dev", comp_node, S);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemsetAsync(first.p, 0xff, sizeof(unsigned long long), c->stream));
+    const long long R = (long long)N * S;
+    hipLaunchKernelGGL(k_first_nonzero_diag, dim3(grid_for(R, 256, 1 << 30)), dim3(256), 0, c->stream, c->noff.p, c->ncols.p, N, S,
+                       values_dev, first.p, (double*)nullptr);
+    hipLaunchKernelGGL(k_first_nonzero_diag, dim3(1), dim3(64), 0, c->stream, c->noff.p, c->ncols.p, N, S, values_dev, first.p,
+                       scale.p);
+    if (c->nnz_nodes)
+        hipLaunchKernelGGL(k_dirichlet_dof_rows, dim3(grid_for(((long long)N + 7) / 8, 1, 1 << 20)), dim3(256), 0, c->stream, c->noff.p,
+                           c->ncols.p, N, S, dm.p, values_dev, scale.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the temporaries are released on return)
+    return FH_OK;
+}
+
+int fh_apply_dirichlet_dofs_rhs_dev(fh_ctx* c, double* rhs_dev, const uint64_t* nodes, const uint8_t* components, uint64_t n) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    if (!rhs_dev || (n && (!nodes || !components))) return c->fail(FH_BAD_ARGUMENT, "fh_apply_dirichlet_dofs_rhs_dev: null pointer");
+    if (n == 0) return FH_OK;
+    const int S = c->S();
+    uint64_t comp_node[8];
+    int rc = dirichlet_masks_to_device(c, "fh_apply_dirichlet_dofs_rhs_dev", nodes, components, n, nullptr, comp_node);
+    if (!rc) rc = dirichlet_components_fit(c, "fh_apply_dirichlet_dofs_rhs_dev", comp_node, S);
+    if (rc) return rc;
+    DevBuf<unsigned long long> dn;
+    DevBuf<unsigned char> dc;
+    HIP_TRY(c, dn.alloc((size_t)n));
+    HIP_TRY(c, dc.alloc((size_t)n));
+    HIP_TRY(c, hipMemcpyAsync(dn.p, nodes, sizeof(uint64_t) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dc.p, components, n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_dirichlet_dof_rhs, dim3(grid_for((long long)n * S, 256, 1 << 30)), dim3(256), 0, c->stream, rhs_dev, dn.p, dc.p,
+                       (long long)n, S);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FH_OK;
 }
 

@@ -556,6 +556,10 @@ int mf_ready(fh_ctx* c, const char* who, int scope) {
     const int rc = check_ready(c, who, false);
     if (rc) return rc;
     if (c->S() < 1 || c->S() > 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": solution dim must be 1..3");
+    if (c->mf_num_dirichlet) {   // (late: the operator may have been set after the dofs)
+        const int fit = dirichlet_components_fit(c, who, c->mf_comp_node, c->S());
+        if (fit) return fit;
+    }
     if (scope == MF_TANGENT) return contact_blocked(c, who);   // (the operator's entry points leave the contact term out)
     return FH_OK;
 }
@@ -871,7 +875,7 @@ int mf_shift_apply(fh_ctx* c, double alpha, double beta, const double* x, double
         uint64_t failed = 0;
         rc = walk_groups_into(c, y, (size_t)n, &failed, [&](uint64_t* f) { return mf_single(c, in.x, y, f); });
         if (rc) return rc;
-        rc = contact_add_apply(c, x, in.bits, y);   // B(u) x of the penalty contact term (k_contact_apply), one launch, before the finish
+        rc = contact_add_apply(c, x, dmask, in.bits, y);   // B(u) x of the penalty contact term (k_contact_apply), one launch, before the finish
         if (rc) return rc;
         const int g = (n + 255) / 256;
         rc = dot_partials(c, dot_scratch, g, partials, &dp);
@@ -1051,26 +1055,38 @@ int newton_residual(fh_ctx* c, double alpha, double beta, const double* f, const
 
 extern "C" {
 
-int fh_set_operator_dirichlet_nodes(fh_ctx* c, const uint64_t* nodes, uint64_t num_nodes) {
+// the set of both entry points: components null = a node set, every component of each node
+static int set_dirichlet(fh_ctx* c, const char* who, const uint64_t* nodes, const uint8_t* components, uint64_t num_nodes, bool by_dof) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
-    if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, "fh_set_operator_dirichlet_nodes: no finite element mesh set");
-    if (num_nodes && !nodes) return c->fail(FH_BAD_ARGUMENT, "fh_set_operator_dirichlet_nodes: null node list");
-    for (uint64_t i = 0; i < num_nodes; ++i)
-        if (nodes[i] >= c->N) return c->fail(FH_BAD_ARGUMENT, "Dirichlet node out of range");
-    c->mf_num_dirichlet = 0;   // (the scale does not depend on which nodes are constrained: mf_scale stays valid)
+    if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, std::string(who) + ": no finite element mesh set");
+    if (num_nodes && !nodes) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null node list");
+    if (by_dof && num_nodes && !components) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null component masks");
+    if (!by_dof)
+        for (uint64_t i = 0; i < num_nodes; ++i)
+            if (nodes[i] >= c->N) return c->fail(FH_BAD_ARGUMENT, "Dirichlet node out of range");
+    uint64_t comp_node[8];
+    int rc = dirichlet_masks_to_device(c, who, nodes, components, num_nodes, nullptr, comp_node);   // (the checks, before anything is changed)
+    if (rc) return rc;
+    c->mf_num_dirichlet = 0;   // (the scale does not depend on which dofs are constrained: mf_scale stays valid)
+    std::fill(c->mf_comp_node, c->mf_comp_node + 8, (uint64_t)0);
     ++c->dirichlet_gen;
     if (!nodes || num_nodes == 0) return FH_OK;
-    DevBuf<unsigned long long> dn;
-    HIP_TRY(c, c->mf_dmask.alloc((size_t)c->N + 1));
-    HIP_TRY(c, dn.alloc((size_t)num_nodes));
-    HIP_TRY(c, hipMemsetAsync(c->mf_dmask.p, 0, (size_t)c->N + 1, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dn.p, nodes, sizeof(uint64_t) * num_nodes, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_mark_nodes, dim3(grid_for((long long)num_nodes, 256, 1 << 30)), dim3(256), 0, c->stream, dn.p, (long long)num_nodes, c->mf_dmask.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dn is released on return)
+    const size_t bytes = ((size_t)c->N + 4) & ~(size_t)3;   // (whole words: k_mark_dofs)
+    HIP_TRY(c, c->mf_dmask.alloc(bytes));
+    HIP_TRY(c, hipMemsetAsync(c->mf_dmask.p, 0, bytes, c->stream));
+    rc = dirichlet_masks_to_device(c, who, nodes, components, num_nodes, c->mf_dmask.p, comp_node);
+    if (rc) return rc;
+    std::copy(comp_node, comp_node + 8, c->mf_comp_node);
     c->mf_num_dirichlet = num_nodes;
     return FH_OK;
+}
+
+int fh_set_operator_dirichlet_nodes(fh_ctx* c, const uint64_t* nodes, uint64_t num_nodes) {
+    return set_dirichlet(c, "fh_set_operator_dirichlet_nodes", nodes, nullptr, num_nodes, false);
+}
+int fh_set_operator_dirichlet_dofs(fh_ctx* c, const uint64_t* nodes, const uint8_t* components, uint64_t num_nodes) {
+    return set_dirichlet(c, "fh_set_operator_dirichlet_dofs", nodes, components, num_nodes, true);
 }
 
 int fh_apply_operator_dev(fh_ctx* c, const double* x_dev, double* y_dev) {

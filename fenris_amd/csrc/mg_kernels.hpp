@@ -3,6 +3,8 @@
 // for bit.  Vectors are node-major with S components per node; the transfer tables are CSR by node and shared by the S components.
 #include <hip/hip_runtime.h>
 
+#include "device_common.hpp"
+
 namespace fenris_hip_mg {
 
 // xf += P xc on the fine dofs that are not Dirichlet (the correction is zero there): at most 8 parents per fine node, in table order
@@ -10,7 +12,7 @@ static __global__ void __launch_bounds__(256) k_mg_prolongate_add(int nf, int S,
                                                            const unsigned char* dmask_f, const double* xc, double* xf) {
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nf * S; t += gridDim.x * blockDim.x) {
         const int i = t / S, s = t - i * S;
-        if (dmask_f && dmask_f[i]) continue;
+        if (fenris_hip::dof_fixed(dmask_f, i, s)) continue;
         double acc = 0.0;
         for (unsigned k = p_off[i]; k < p_off[i + 1]; ++k) acc = fma(p_w[k], xc[(size_t)S * p_idx[k] + s], acc);
         xf[t] += acc;
@@ -25,10 +27,10 @@ static __global__ void __launch_bounds__(256) k_mg_restrict_residual(int nc, int
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nc * S; t += gridDim.x * blockDim.x) {
         const int j = t / S, s = t - j * S;
         double acc = 0.0;
-        if (!(dmask_c && dmask_c[j]))
+        if (!fenris_hip::dof_fixed(dmask_c, j, s))
             for (unsigned k = r_off[j]; k < r_off[j + 1]; ++k) {
                 const unsigned i = r_idx[k];
-                if (dmask_f && dmask_f[i]) continue;
+                if (fenris_hip::dof_fixed(dmask_f, i, s)) continue;
                 const size_t f = (size_t)S * i + s;
                 acc = fma(r_w[k], b[f] - Ax[f], acc);
             }
@@ -67,7 +69,7 @@ static __global__ void __launch_bounds__(256) k_mg_add(int n, const double* d, d
 // the Dirichlet rows of a V-cycle's result: x = b / D there (D = the scale of the rows)
 static __global__ void __launch_bounds__(256) k_mg_dirichlet_rows(int n, int S, const unsigned char* dmask, const double* b, const double* diag, double* x) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        if (dmask[i / S]) x[i] = b[i] / diag[i];
+        if (fenris_hip::dof_fixed_at(dmask, i, S)) x[i] = b[i] / diag[i];
 }
 
 // uc = the fine values at each coarse node's injected fine copy
@@ -99,7 +101,7 @@ static __global__ void __launch_bounds__(256) k_mg_start_vector(int n, int S, co
         h *= 0xbf58476d1ce4e5b9ull;
         h ^= h >> 29;
         const double u = (double)(h >> 11) * 0x1p-53;
-        v[i] = (dmask && dmask[i / S]) ? 0.0 : 2.0 * u - 1.0;
+        v[i] = fenris_hip::dof_fixed_at(dmask, i, S) ? 0.0 : 2.0 * u - 1.0;
     }
 }
 

@@ -384,6 +384,47 @@ static __global__ void __launch_bounds__(256) k_mark_nodes(const unsigned long l
     if (t < n) member[nodes[t]] = 1;
 }
 
+// ... per component (fh_apply_dirichlet_dofs_csr_dev): member[] holds the bitmask of each node's constrained components (device_common.hpp).
+// Inside each S x S block the rows of the row node's held components and the columns of the column node's held components are zeroed, the held
+// diagonal entries take the scale.  The same row assignment; a member byte of all ones writes what k_dirichlet_rows writes.
+static __global__ void __launch_bounds__(256) k_dirichlet_dof_rows(const unsigned* noff, const unsigned* ncols, int num_nodes, int S,
+                                                                   const unsigned char* member, double* vals, const double* scale_dev) {
+    const int hl = threadIdx.x & 31;
+    const double scale = *scale_dev;
+    for (long long i = (long long)blockIdx.x * 8 + (threadIdx.x >> 5); i < num_nodes; i += (long long)gridDim.x * 8) {
+        const unsigned b = noff[i], cnt = noff[i + 1] - b;
+        const unsigned ri = member[i];
+        for (unsigned k = hl; k < cnt; k += 32) {
+            const unsigned j = ncols[b + k];
+            const unsigned cj = member[j];
+            if (!ri && !cj) continue;
+            double* base = vals + (unsigned long long)S * S * b + (unsigned long long)S * k;
+            for (int r = 0; r < S; ++r)
+                for (int c = 0; c < S; ++c)
+                    if (fenris_hip::comp_fixed(ri, r) || fenris_hip::comp_fixed(cj, c))
+                        base[(unsigned long long)r * S * cnt + c] = ((unsigned)i == j && r == c) ? scale : 0.0;
+        }
+    }
+}
+
+// member[nodes[t]] |= comps[t] (comps null: all ones).  Bytes have no atomic OR: the OR goes to the aligned 32-bit word that holds the byte, so
+// member is allocated in whole words.
+static __global__ void __launch_bounds__(256) k_mark_dofs(const unsigned long long* nodes, const unsigned char* comps, long long n, unsigned char* member) {
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const unsigned long long node = nodes[t];
+    const unsigned bits = comps ? comps[t] : 0xffu;
+    atomicOr(reinterpret_cast<unsigned*>(member) + (node >> 2), bits << (8u * (unsigned)(node & 3ull)));
+}
+
+static __global__ void k_dirichlet_dof_rhs(double* rhs, const unsigned long long* nodes, const unsigned char* comps, long long n, int S) {
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t >= n * S) return;
+    const long long k = t / S;
+    const int comp = (int)(t - k * S);
+    if (fenris_hip::comp_fixed(comps[k], comp)) rhs[nodes[k] * S + comp] = 0.0;
+}
+
 static __global__ void k_dirichlet_rhs(double* rhs, const unsigned long long* nodes, long long n, int S) {
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (t >= n * S) return;

@@ -313,7 +313,7 @@ static __global__ void __launch_bounds__(256) k_mf_absmax(int n, int S, const do
     __shared__ unsigned long long red[256];
     unsigned long long m = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        if (!dmask || !dmask[i / S]) m = max(m, (unsigned long long)__double_as_longlong(fabs(x[i])));
+        if (!dof_fixed_at(dmask, i, S)) m = max(m, (unsigned long long)__double_as_longlong(fabs(x[i])));
     red[threadIdx.x] = m;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -328,7 +328,7 @@ static __global__ void __launch_bounds__(256) k_mf_operand(int n, int S, const d
                                                            double* xm) {
     const int e = mf_exponent(bits);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        xm[i] = (dmask && dmask[i / S]) ? 0.0 : ldexp(x[i], -e);
+        xm[i] = dof_fixed_at(dmask, i, S) ? 0.0 : ldexp(x[i], -e);
 }
 
 // node sums times 2^e (mf_exponent), rows of the Dirichlet nodes = scale x (dmask may be null), and the per-workgroup partials of x . y (dot_partial may be null)
@@ -337,7 +337,7 @@ static __global__ void __launch_bounds__(256) k_mf_finish(int n, int S, const do
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     double d[1] = {0.0};
     if (i < n) {
-        const double yv = (dmask && dmask[i / S]) ? *scale * x[i] : ldexp(y[i], mf_exponent(bits));
+        const double yv = dof_fixed_at(dmask, i, S) ? *scale * x[i] : ldexp(y[i], mf_exponent(bits));
         y[i] = yv;
         d[0] = x[i] * yv;
     }
@@ -355,7 +355,7 @@ static __global__ void k_mf_scale(const double* diag, const unsigned long long* 
 }
 static __global__ void __launch_bounds__(256) k_mf_dirichlet_diag(int n, int S, const unsigned char* dmask, const double* scale, double* diag) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && dmask[i / S]) diag[i] = *scale;
+    if (i < n && dof_fixed_at(dmask, i, S)) diag[i] = *scale;
 }
 
 // ---- the matrix-free map off the tiles (the kinds outside them: Hex27, Tet10, Quad9, Tri6, Hex20, Tet20; a mesh without tile tables):
@@ -601,7 +601,7 @@ __global__ void __launch_bounds__(256) k_mass_elements(const KArgs a, const unsi
         for (int r = 0; r < D; ++r) X[g][r] = a.verts[(size_t)nodes[g] * D + r];
     auto xv = [&](int n, int k) {
         const int nd = nodes[n];
-        return (dmask && dmask[nd]) ? 0.0 : x[(size_t)nd * S + k];
+        return dof_fixed(dmask, nd, k) ? 0.0 : x[(size_t)nd * S + k];
     };
     // (mass_element_body's arithmetic, accumulated in fe rather than in registers: f[27][3] does not fit beside the rest)
     const double r = rho[rho_per_elem ? e : 0];
@@ -640,7 +640,7 @@ static __global__ void __launch_bounds__(256) k_mf_shift_combine(int n, int S, d
     double d[1] = {0.0};
     if (i < n) {
         const double v = m ? alpha * m[i] : 0.0;
-        const double yv = (dmask && dmask[i / S]) ? *scale * x[i] : (t ? fma(beta, t[i], v) : v);
+        const double yv = dof_fixed_at(dmask, i, S) ? *scale * x[i] : (t ? fma(beta, t[i], v) : v);
         y[i] = yv;
         if (dot_partial) d[0] = x[i] * yv;
     }
@@ -655,7 +655,7 @@ static __global__ void __launch_bounds__(256) k_newton_combine(int n, int S, dou
     double sq[1] = {0.0};
     if (i < n) {
         const double rf = f ? r[i] - f[i] : r[i];
-        const double v = (dmask && dmask[i / S]) ? 0.0 : (m ? fma(beta, rf, alpha * m[i]) : beta * rf);
+        const double v = dof_fixed_at(dmask, i, S) ? 0.0 : (m ? fma(beta, rf, alpha * m[i]) : beta * rf);
         F[i] = v;
         sq[0] = v * v;
     }

@@ -314,9 +314,9 @@ struct TilePass {
     }
     template <int S>
     __device__ __forceinline__ void field_masked(int n, const double* x, const unsigned char* dmask, double (&v)[S]) const {
-        const bool fixed = dmask && dmask[nd[n]];
+        const unsigned fixed = node_dmask(dmask, nd[n]);
 #pragma unroll
-        for (int k = 0; k < S; ++k) v[k] = fixed ? 0.0 : x[(size_t)nd[n] * S + k];
+        for (int k = 0; k < S; ++k) v[k] = comp_fixed(fixed, k) ? 0.0 : x[(size_t)nd[n] * S + k];
     }
     // finish = store + sum: the element vector into LDS, stage[a][c][thread], entry by entry through put (i = a SV + c; the select: a
     // skipped element may hold NaN), and the tile's node sums into the partials
@@ -581,20 +581,21 @@ __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, c
     if (node < num_nodes) {
         double acc[S];
         node_partials_sum<S>(np_off, np_idx, partial, node, acc);
-        const bool fixed = dmask && dmask[node];
-        double xv[S];
+        const unsigned fixed = node_dmask(dmask, node);
+        double xv[S], xo[S];   // (xo: the operand as the element pass saw it, the held components zero, so that their columns of the contact block vanish too)
 #pragma unroll
         for (int c = 0; c < S; ++c) {
             xv[c] = x[(size_t)node * S + c];
+            xo[c] = comp_fixed(fixed, c) ? 0.0 : xv[c];
             acc[c] = ldexp(acc[c], ex);
         }
         if constexpr (S > 1) {
-            if (ct.count) contact_apply<S>(ct, node, xv, contact_scale, acc);   // (the unscaled operand)
-            if (ct.friction) friction_apply<S>(ct, node, xv, contact_scale, acc);
+            if (ct.count) contact_apply<S>(ct, node, xo, contact_scale, acc);   // (the unscaled operand)
+            if (ct.friction) friction_apply<S>(ct, node, xo, contact_scale, acc);
         }
 #pragma unroll
         for (int c = 0; c < S; ++c) {
-            const double yv = fixed ? *scale * xv[c] : acc[c];
+            const double yv = comp_fixed(fixed, c) ? *scale * xv[c] : acc[c];
             y[(size_t)node * S + c] = yv;
             dot = fma(xv[c], yv, dot);
         }
@@ -694,12 +695,12 @@ __global__ void __launch_bounds__(256) k_shift_from_partials(int num_nodes, cons
     if (node < num_nodes) {
         double acc[S];
         node_partials_sum<S>(np_off, np_idx, partial, node, acc);
-        const bool fixed = dmask && dmask[node];
+        const unsigned fixed = node_dmask(dmask, node);
 #pragma unroll
         for (int c = 0; c < S; ++c) {
             const size_t i = (size_t)node * S + c;
             const double xv = x[i], m = alpha * acc[c];
-            const double yv = fixed ? *scale * xv : (tv ? fma(beta, tv[i], m) : m);
+            const double yv = comp_fixed(fixed, c) ? *scale * xv : (tv ? fma(beta, tv[i], m) : m);
             y[i] = yv;
             dot = fma(xv, yv, dot);
         }
@@ -723,7 +724,7 @@ __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, con
         double acc[2][S];
         node_partials_sum(np_off, np_idx, {rpart, mpart}, node, acc);
         double(&racc)[S] = acc[0], (&macc)[S] = acc[1];
-        const bool fixed = dmask && dmask[node];
+        const unsigned fixed = node_dmask(dmask, node);
         if constexpr (S > 1) {
             if (ct.count) contact_force<S>(ct, node, racc);
             if (ct.friction) friction_force<S>(ct, node, racc);
@@ -732,7 +733,7 @@ __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, con
         for (int c = 0; c < S; ++c) {
             const size_t i = (size_t)node * S + c;
             const double r = f ? racc[c] - f[i] : racc[c];
-            const double v = fixed ? 0.0 : (mpart ? fma(beta, r, alpha * macc[c]) : beta * r);
+            const double v = comp_fixed(fixed, c) ? 0.0 : (mpart ? fma(beta, r, alpha * macc[c]) : beta * r);
             F[i] = v;
             sq = fma(v, v, sq);
         }
@@ -762,10 +763,10 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
             if (ct.count) contact_force<S>(ct, node, racc);
             if (ct.friction) friction_force<S>(ct, node, racc);   // (the slip of the velocity the node is about to kick: ct.slip_v is p.v)
         }
-        const bool fixed = p.dmask && p.dmask[node];
+        const unsigned fixed = node_dmask(p.dmask, node);
         const double lf = dyn_load_factor(p);
 #pragma unroll
-        for (int c = 0; c < S; ++c) ke += dyn_dof(p, (size_t)node * S + c, fixed, lf, racc[c]);
+        for (int c = 0; c < S; ++c) ke += dyn_dof(p, (size_t)node * S + c, comp_fixed(fixed, c), lf, racc[c]);
     }
     if (p.flags & DYN_STORE) block_partial_store(ke, p.ke_partial);
 }
@@ -785,10 +786,10 @@ __global__ void __launch_bounds__(256) k_first_order_from_partials(int num_nodes
         if constexpr (S > 1) {
             if (ct.count) contact_force<S>(ct, node, racc);
         }
-        const bool fixed = p.dmask && p.dmask[node];
+        const unsigned fixed = node_dmask(p.dmask, node);
         const double lf = dyn_load_factor(p);
 #pragma unroll
-        for (int c = 0; c < S; ++c) q += fo_dof(p, (size_t)node * S + c, fixed, lf, racc[c]);
+        for (int c = 0; c < S; ++c) q += fo_dof(p, (size_t)node * S + c, comp_fixed(fixed, c), lf, racc[c]);
     }
     if (p.flags & FO_STORE) block_partial_store(q, p.partial);
 }

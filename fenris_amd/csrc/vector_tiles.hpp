@@ -74,8 +74,8 @@ int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const 
 int vector_tiles_tangent_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* x,
                               double* partial);
 
-// node pass of the matrix-free operator: y = the node sums of the partials, OVERWRITTEN; rows of the nodes with dmask[node] != 0
-// (dmask, scale: device, may be null / unused) are  *scale x; the other rows are multiplied by 2^e (xbits: mf_exponent, may be null).  dot_partial (may be null): one partial of x . y per workgroup
+// node pass of the matrix-free operator: y = the node sums of the partials, OVERWRITTEN; rows of the dofs dmask holds (the Dirichlet bytes, dof_fixed of
+// device_common.hpp; dmask, scale: device, may be null / unused) are  *scale x; the other rows are multiplied by 2^e (xbits: mf_exponent, may be null).  dot_partial (may be null): one partial of x . y per workgroup
 // (vector_tiles_operator_partials of them), to be summed in index order.  ct (count 0: off): contact_scale B x of the penalty contact term
 // (contact_kernels.hpp; the unscaled x) joins the node's sum before the Dirichlet rows and the dot product.
 inline int vector_tiles_operator_partials(int num_nodes) { return (num_nodes + 255) / 256; }
@@ -84,7 +84,7 @@ hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_no
                                            double* dot_partial, const ContactTable& ct, double contact_scale = 1.0);
 
 // the mass term of the shifted map (engine_vector.hip) over the tiles into partial[P][S]: M x (x null: the diagonal of M), rho[rho_per_elem ? e : 0]
-// the density, the entries of the nodes with dmask[node] != 0 read as zero (dmask may be null).  Returns -1 when (elem_kind, S) is not covered.
+// the density, the entries of the dofs dmask holds read as zero (dmask may be null).  Returns -1 when (elem_kind, S) is not covered.
 int vector_tiles_mass_pass(int elem_kind, int S, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* rho,
                            int rho_per_elem, const double* x, const unsigned char* dmask, double* partial);
 
@@ -96,7 +96,7 @@ hipError_t vector_tiles_shift_node_pass(hipStream_t stream, int S, int num_nodes
 
 // node pass of the Newton residual: F = alpha (node sums of mpart) + beta (node sums of rpart - f), OVERWRITTEN, with rpart the residual's
 // partials (vector_tiles_element_pass) and mpart the mass partials of d = u - u_ref (vector_tiles_mass_pass; null when alpha == 0), f null: zero;
-// the rows of the nodes with dmask[node] != 0 are zero.  norm_partial: one partial of |F|^2 per workgroup (vector_tiles_operator_partials of
+// the rows of the dofs dmask holds are zero.  norm_partial: one partial of |F|^2 per workgroup (vector_tiles_operator_partials of
 // them), to be summed in index order.  ct (count 0: off; here and in the two node passes below): the contact force g of the node
 // (contact_kernels.hpp) joins its residual sum before anything else is formed from it.
 hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const double* mpart,

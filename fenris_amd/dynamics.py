@@ -31,6 +31,7 @@ import numpy as np
 
 from . import _ffi
 from . import contact as _contact
+from . import dirichlet as _dirichlet
 from ._ffi import FenrisError, SingularJacobianError
 from .assembly import (BacktrackingLineSearch, JacobianError, LineSearchError, MaximumIterationsReached, NewtonResult, NewtonSettings, _is_torch,
                        _ptr)
@@ -115,6 +116,11 @@ class TimeIntegrator:
         self._nodes = None if nodes is None else _ffi.as_u64(nodes).copy()
         self._bind(force=True)
         return self
+
+    def with_dirichlet_dofs(self, nodes, components):
+        """single components held at the u of set_state with v = a = 0 (MatrixFreeOperator.with_dirichlet_dofs: an (n, S) boolean array
+        or component indices); with_boundary_motion moves these components alone; calls accumulate; returns self"""
+        return _dirichlet.with_dirichlet_dofs(self, nodes, components)
 
     def with_load(self, f, load_factor=None):
         """the load f (numpy array or device tensor; None: zero) and the factor per step, lf_n = load_factor[min(n, len - 1)] (None: 1)"""

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _ffi
 from . import contact as _contact
+from . import dirichlet as _dirichlet
 from ._ffi import FenrisError
 from .assembly import _is_torch
 
@@ -58,6 +59,10 @@ class MatrixFreeEigensolver:
         self._nodes = None if nodes is None else _ffi.as_u64(nodes).copy()
         self._bind(force=True)
         return self
+
+    def with_dirichlet_dofs(self, nodes, components):
+        """single components of the listed nodes (MatrixFreeOperator.with_dirichlet_dofs): they leave the eigenproblem; calls accumulate; returns self"""
+        return _dirichlet.with_dirichlet_dofs(self, nodes, components)
 
     def with_multigrid(self, mg):
         """a GeometricMultigrid over this assembler: solve then defaults to PRECOND_MULTIGRID; returns self"""

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _ffi
 from .assembly import ElementEllipticAssembler, Engine, _is_torch
+from .dirichlet import DofSet
 from .operators import LinearElasticMaterial, MaterialEllipticOperator
 
 
@@ -75,11 +76,12 @@ class GeometricMultigrid:
 
     def _bind(self, fine_nodes, density=None):
         """(re)create the hierarchy for the fine Dirichlet nodes (and, for the shifted map, the density) and attach it to the fine engine"""
-        nodes = np.zeros(0, dtype=np.uint64) if fine_nodes is None else np.unique(_ffi.as_u64(fine_nodes))
+        held = fine_nodes if isinstance(fine_nodes, DofSet) else None   # (single components: the masks go down the hierarchy by injection)
+        nodes = held.nodes if held is not None else np.zeros(0, dtype=np.uint64) if fine_nodes is None else np.unique(_ffi.as_u64(fine_nodes))
         rho = None if density is None else np.ascontiguousarray(np.atleast_1d(np.asarray(density, dtype=np.float64)).ravel())
         if rho is not None and len(rho) != 1:
             raise _ffi.FenrisError(_ffi.FH_UNSUPPORTED, "GeometricMultigrid: per-element density is not carried to the coarse levels")
-        key = (nodes.tobytes(), None if rho is None else rho.tobytes())
+        key = (nodes.tobytes() if held is None else held.key(), None if rho is None else rho.tobytes())
         lib = _ffi.lib()
         if self._h is not None and key == self._key:
             self.engine._check(lib.fh_set_multigrid(self.engine._h, self._h))
@@ -87,10 +89,16 @@ class GeometricMultigrid:
         self._destroy()
         mask = np.zeros(self.engine.num_nodes(), dtype=bool)
         mask[nodes.astype(np.int64)] = True
+        num_fine = self.engine.num_nodes()
         for k in range(len(self.levels) - 1, -1, -1):
             mask = mask[self._inj[k]]
             eng = self.levels[k].engine
-            eng.set_operator_dirichlet_nodes(np.where(mask)[0].astype(np.uint64))
+            if held is not None:
+                held = held.injected(self._inj[k], num_fine)
+                num_fine = len(self._inj[k])
+                eng.set_operator_dirichlet_nodes(held)
+            else:
+                eng.set_operator_dirichlet_nodes(np.where(mask)[0].astype(np.uint64))
             if rho is not None:
                 eng.set_mass_density(rho)
         self._create()
@@ -124,7 +132,8 @@ class GeometricMultigrid:
             pass
 
     def apply(self, r, z, alpha=0.0, beta=1.0, dirichlet_nodes=None, density=None):
-        """one V-cycle z = B r (device tensors) on alpha M + beta T(u), with the fine engine's current Dirichlet nodes given again here"""
+        """one V-cycle z = B r (device tensors) on alpha M + beta T(u), with the fine engine's current Dirichlet nodes given again here
+        (a node list, or a DofSet of fenris_amd.dirichlet for single components)"""
         if not (_is_torch(r) and _is_torch(z)):
             raise TypeError("GeometricMultigrid.apply takes device tensors")
         self.engine.set_operator_dirichlet_nodes(dirichlet_nodes)

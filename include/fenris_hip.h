@@ -410,6 +410,12 @@ int fh_assemble_element_matrices_dev(fh_ctx*, uint64_t first_element, uint64_t c
 /* apply_homogeneous_dirichlet_bc_csr / _rhs (global.rs:379-451, 479-495) on device-resident CSR */
 int fh_apply_dirichlet_csr_dev(fh_ctx*, double* values_dev, const uint64_t* nodes, uint64_t num_nodes);
 int fh_apply_dirichlet_rhs_dev(fh_ctx*, double* rhs_dev, const uint64_t* nodes, uint64_t num_nodes);
+/* ... of single components (nodes[k] with components[k] as for fh_set_operator_dirichlet_dofs; a node listed twice: the masks are OR-ed): the
+ * rows and columns of the listed dofs, inside their node blocks, as apply_homogeneous_dirichlet_bc_csr treats the rows and columns of a node;
+ * the same scale (|first nonzero diagonal entry| in row order, or 1).  A mask of 0, a component >= the solution dim, a node out of range:
+ * FH_BAD_ARGUMENT.  The rhs call zeroes the listed dofs. */
+int fh_apply_dirichlet_dofs_csr_dev(fh_ctx*, double* values_dev, const uint64_t* nodes, const uint8_t* components, uint64_t num_nodes);
+int fh_apply_dirichlet_dofs_rhs_dev(fh_ctx*, double* rhs_dev, const uint64_t* nodes, const uint8_t* components, uint64_t num_nodes);
 
 /* ---- host-side input generators (no device needed) -------------------------------------------- */
 /* fenris-quadrature/src/univariate.rs:66-118, tensor.rs:13-55 */
@@ -645,6 +651,15 @@ int fh_cg_solve_dev(fh_ctx*, const double* values_dev, const double* b_dev, doub
  * so does fh_set_mesh*).  With them, A is the matrix fh_apply_dirichlet_csr_dev leaves of the assembled K (global.rs:379-451): the rows and
  * columns of the constrained dofs are zero and their diagonal is scale = |first nonzero diagonal entry| in row order, or 1. */
 int fh_set_operator_dirichlet_nodes(fh_ctx*, const uint64_t* nodes, uint64_t num_nodes);
+/* Single displacement components (rollers, symmetry planes): nodes[k] with components[k], bit j set = component j of that node is constrained
+ * (j < solution dim).  Replaces whatever fh_set_operator_dirichlet_nodes / _dofs set before; NULL / 0 clears; fh_set_mesh* clears.  A node
+ * listed twice: the masks are OR-ed.  A mask of 0: FH_BAD_ARGUMENT.  A node >= num_vertices: FH_BAD_ARGUMENT.  fh_set_operator_dirichlet_nodes
+ * is this call with every component of each node, bit for bit.  Every route that honours the node set honours the dofs with the same meaning
+ * per dof: the operator, tangent and shifted tangent and their solvers, Newton, multigrid, fh_eigs_lowest, the time integrators (prescribed
+ * boundary motion moves the constrained components alone) and the contact term, whose force and tangent block act on the free components of a
+ * partly constrained node.  A mask, other than all ones, that names a component >= the solution dim of the operator in use is refused with
+ * FH_BAD_ARGUMENT and the node's name when a route uses the set (the operator may be set after the dofs). */
+int fh_set_operator_dirichlet_dofs(fh_ctx*, const uint64_t* nodes, const uint8_t* components, uint64_t num_nodes);
 /* y = A x, both s N doubles on the device.  y is OVERWRITTEN (LinearOperator::apply, cg.rs:16-18); x may hold anything on the constrained
  * dofs; the context's u (fh_set_u*) is neither read nor changed.  FH_SINGULAR_JACOBIAN as the residual reports it.  Deterministic
  * on every element kind (no floating-point atomics: element vectors summed per node in a fixed order).  With Dirichlet nodes set, the
