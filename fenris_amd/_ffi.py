@@ -61,7 +61,7 @@ class FirstOrderSettings(C.Structure):
 class Obstacle(C.Structure):
     """fh_obstacle"""
 
-    _fields_ = [("kind", C.c_int), ("stiffness", C.c_double), ("point", C.c_double * 3), ("normal", C.c_double * 3), ("radius", C.c_double)]
+    _fields_ = [("kind", C.c_int), ("grid", C.c_int), ("stiffness", C.c_double), ("point", C.c_double * 3), ("normal", C.c_double * 3), ("radius", C.c_double)]
 
 
 class FenrisError(RuntimeError):
@@ -201,6 +201,10 @@ _SIGS = {
     "fh_contact_force_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_contact_gap_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_add_contact_tangent_csr_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_sdf_grid_create": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f64p, f64p, u32p]),
+    "fh_sdf_grid_destroy": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "fh_sdf_grid_info": (C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, f64p]),
+    "fh_sdf_grid_sample_dev": (C.c_int, [C.c_void_p, C.c_uint32, f64p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fh_set_friction": (C.c_int, [C.c_void_p, f64p, C.c_uint64, C.c_double]),
     "fh_set_friction_reference": (C.c_int, [C.c_void_p, f64p]),
     "fh_set_friction_reference_dev": (C.c_int, [C.c_void_p, C.c_void_p]),

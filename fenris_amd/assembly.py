@@ -59,6 +59,7 @@ class Engine:
         if getattr(self, "_h", None):
             self._lib.fh_destroy(self._h)
             self._h = None
+            self._sdf_grids = {}   # (the uploads of fenris_amd.contact.SdfGrid went with the context)
 
     def __del__(self):
         try:

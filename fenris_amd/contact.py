@@ -22,6 +22,12 @@ point in time, constant before the first knot and after the last.  The second-or
 `Engine.set_obstacle_time(t, t_lag)`.  The slip of the friction term is taken relative to the obstacle: a node that moves with it feels no
 friction.  The first-order integrators refuse paths.  `Contact.resultants()` gives the force the body exerts on each obstacle.
 
+Obstacles of any shape (FH_OBSTACLE_GRID): `SdfGrid(values, spacing)` is a signed distance sampled on a regular grid -- from an array, or
+`SdfGrid.from_function(sdf_union(sdf_circle(c, r), sdf_box(lo, hi)), lower, upper, shape)` -- and `GridObstacle(grid, origin, stiffness,
+friction=, path=)` the obstacle it makes with its first sample at `origin`.  The device interpolates it bi- / trilinearly; grad phi need
+not be a unit vector (force k w p grad phi, Gauss-Newton block k w grad phi grad phi^T).  Outside the box of the samples the obstacle does
+not exist: the box must cover every place a node can be while phi < 0.  The samples are uploaded once per (engine, grid).
+
 `with_obstacles` on MatrixFreeTangent, MatrixFreeShiftedTangent, MatrixFreeNewton, the time integrators and MatrixFreeEigensolver makes
 the obstacles belong to that object: they are handed to the engine before every use, as its Dirichlet nodes are.  An object that was never
 given obstacles does not inherit those of another object: it clears them from the engine before its use (the owner hands them over again
@@ -37,8 +43,9 @@ import numpy as np
 
 from . import _ffi
 
-OBSTACLE_HALF_SPACE, OBSTACLE_BALL, OBSTACLE_CAVITY = 0, 1, 2
+OBSTACLE_HALF_SPACE, OBSTACLE_BALL, OBSTACLE_CAVITY, OBSTACLE_GRID = 0, 1, 2, 3
 MAX_OBSTACLES = 16
+MAX_SDF_GRIDS = 16
 
 
 def _vec3(v, name):
@@ -112,7 +119,7 @@ class _Obstacle:
             raise TypeError("path must be an ObstaclePath")
         self.path = path
 
-    def _fill(self, o):
+    def _fill(self, o, engine=None):
         o.kind, o.stiffness, o.radius = self.kind, self.stiffness, self.radius
         for a in range(3):
             o.point[a], o.normal[a] = self.point[a], self.normal[a]
@@ -140,6 +147,146 @@ class Cavity(_Obstacle):
 
     def __init__(self, centre, radius, stiffness, friction=0.0, path=None):
         super().__init__(centre, (0.0, 0.0, 0.0), radius, stiffness, friction, path)
+
+
+class SdfGrid:
+    """A signed distance sampled on a regular grid (fh_sdf_grid_create): `values` of shape (nx, ny) or (nx, ny, nz) in numpy's natural
+    [ix, iy, iz] index order, `spacing` one h > 0 per axis.  Sample (ix, iy, iz) stands at origin + (ix h_x, iy h_y, iz h_z); the origin
+    belongs to the obstacle (GridObstacle), so one grid can stand in several places.  Between the samples phi is the bi- / trilinear
+    interpolant; outside their box the obstacle does not exist.  The samples are uploaded lazily, once per (engine, grid)."""
+
+    def __init__(self, values, spacing):
+        v = np.asarray(values, dtype=np.float64)
+        if v.ndim not in (2, 3):
+            raise ValueError("values must have shape (nx, ny) or (nx, ny, nz)")
+        h = np.asarray(spacing, dtype=np.float64).ravel()
+        if h.size != v.ndim:
+            raise ValueError("spacing must have one entry per axis")
+        if min(v.shape) < 2:
+            raise ValueError("every axis needs at least 2 samples")
+        if not (np.all(np.isfinite(h)) and np.all(h > 0.0)):
+            raise ValueError("the spacings must be positive and finite")
+        if not np.all(np.isfinite(v)):
+            raise ValueError("the samples must be finite")
+        self.values, self.spacing, self.dim = v.copy(), h.copy(), v.ndim
+
+    @property
+    def shape(self):
+        return self.values.shape
+
+    @classmethod
+    def from_function(cls, f, lower, upper, shape):
+        """(grid, origin): the vectorised f(points (m, dim)) -> phi (m) sampled at shape[a] >= 2 equidistant positions per axis from lower
+        to upper (both included); origin = lower"""
+        lower, upper = np.asarray(lower, dtype=np.float64).ravel(), np.asarray(upper, dtype=np.float64).ravel()
+        shape = tuple(int(s) for s in shape)
+        if not (lower.size == upper.size == len(shape)) or len(shape) not in (2, 3):
+            raise ValueError("lower, upper and shape must have 2 or 3 entries each")
+        h = (upper - lower) / (np.array(shape) - 1)
+        axes = [lower[a] + h[a] * np.arange(shape[a]) for a in range(len(shape))]
+        pts = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, len(shape))
+        phi = np.asarray(f(pts), dtype=np.float64).reshape(shape)
+        return cls(phi, h), lower.copy()
+
+    def abi_values(self):
+        """the samples in the ABI's layout: x fastest"""
+        return np.ascontiguousarray(self.values.transpose(tuple(range(self.dim))[::-1])).ravel()
+
+    def evaluate(self, points, origin):
+        """(phi, grad) at points (m, dim) with sample (0, ..) at `origin`, on the host, as the device evaluates it: t = (x - origin) / h;
+        inside iff 0 <= t_a <= n_a - 1 on every axis (a NaN is outside: phi = +inf, grad = 0); i = min(floor(t), n - 2), f = t - i; phi the
+        bi- / trilinear interpolant of the corner samples of cell i at f, grad its gradient in x"""
+        d, n, h = self.dim, np.array(self.values.shape), self.spacing
+        x = np.asarray(points, dtype=np.float64).reshape(-1, d)
+        o = np.asarray(origin, dtype=np.float64).ravel()[:d]
+        with np.errstate(invalid="ignore"):
+            t = (x - o) / h
+            inside = np.all((t >= 0.0) & (t <= (n - 1)), axis=1)
+        phi, grad = np.full(len(x), np.inf), np.zeros((len(x), d))
+        if not inside.any():
+            return phi, grad
+        ti = t[inside]
+        i = np.minimum(np.floor(ti).astype(np.int64), n - 2)
+        f = ti - i
+        w = np.stack([1.0 - f, f], axis=-1)   # [point, axis, 0 / 1]
+        s, ds = np.zeros(len(ti)), np.zeros((len(ti), d))
+        for q in range(1 << d):
+            bit = [(q >> a) & 1 for a in range(d)]
+            v = self.values[tuple(i[:, a] + bit[a] for a in range(d))]
+            prod = v.copy()
+            for a in range(d):
+                prod = prod * w[:, a, bit[a]]
+            s += prod
+            for a in range(d):
+                part = v if bit[a] else -v
+                for b in range(d):
+                    if b != a:
+                        part = part * w[:, b, bit[b]]
+                ds[:, a] += part
+        phi[inside] = s
+        grad[inside] = ds / h
+        return phi, grad
+
+    def _id_on(self, engine):
+        """the slot of this grid's upload in `engine` (made at the first use; Engine.close drops the table)"""
+        table = engine.__dict__.setdefault("_sdf_grids", {})
+        hit = table.get(id(self))
+        if hit is not None and hit[0] is self:
+            return hit[1]
+        n = np.ones(3, dtype=np.uint32)
+        n[:self.dim] = self.values.shape
+        h = np.ones(3)
+        h[:self.dim] = self.spacing
+        vals = self.abi_values()
+        slot = C.c_uint32(0)
+        engine._check(engine._lib.fh_sdf_grid_create(engine._h, self.dim, n.ctypes.data_as(_ffi.u32p), _ffi.fp(h), _ffi.fp(vals), C.byref(slot)))
+        table[id(self)] = (self, int(slot.value))   # (the grid is kept alive with its slot: an id() is never reused under it)
+        return int(slot.value)
+
+
+class GridObstacle(_Obstacle):
+    """phi(x) = the interpolant of `grid` with its sample (0, ..) at `origin` (FH_OBSTACLE_GRID): any rigid shape.  The body stays where
+    phi > 0; outside the box of the samples the obstacle does not exist, so the box must cover every place a node can be while phi < 0.
+    grad phi need not be a unit vector: the force is k w p grad phi, the block k w grad phi grad phi^T (Gauss-Newton)"""
+    kind = OBSTACLE_GRID
+
+    def __init__(self, grid, origin, stiffness, friction=0.0, path=None):
+        if not isinstance(grid, SdfGrid):
+            raise TypeError("grid must be an SdfGrid")
+        if np.asarray(origin).size != grid.dim:
+            raise ValueError("origin must have one entry per axis of the grid")
+        super().__init__(origin, (0.0, 0.0, 0.0), 0.0, stiffness, friction, path)
+        self.grid = grid
+
+    def _fill(self, o, engine=None):
+        if engine is None:
+            raise ValueError("a GridObstacle is filled for an engine (its grid is uploaded there)")
+        super()._fill(o, engine)
+        o.grid = self.grid._id_on(engine)
+
+
+def sdf_circle(centre, radius):
+    """|x - centre| - radius (sdf.rs SdfCircle; a sphere in 3-D), as a callable for SdfGrid.from_function"""
+    c, r = np.asarray(centre, dtype=np.float64).ravel(), float(radius)
+    return lambda x: np.linalg.norm(np.asarray(x, dtype=np.float64) - c, axis=-1) - r
+
+
+def sdf_box(lower, upper):
+    """the axis-aligned box (sdf.rs SdfAxisAlignedBox): with b the half extents, p = x - centre and d = |p| - b,
+    |max(d, 0)| + min(0, max_a d_a)"""
+    lo, hi = np.asarray(lower, dtype=np.float64).ravel(), np.asarray(upper, dtype=np.float64).ravel()
+    b, mid = (hi - lo) / 2.0, (hi + lo) / 2.0
+
+    def f(x):
+        d = np.abs(np.asarray(x, dtype=np.float64) - mid) - b
+        return np.linalg.norm(np.maximum(d, 0.0), axis=-1) + np.minimum(0.0, d.max(axis=-1))
+
+    return f
+
+
+def sdf_union(a, b):
+    """min(a, b) (sdf.rs SdfUnion)"""
+    return lambda x: np.minimum(a(x), b(x))
 
 
 class Obstacles:
@@ -182,7 +329,7 @@ def set_obstacles(engine, obstacles, dt=None):
     eps = obstacles.slip_length_for(dt) if obstacles.has_friction() else None   # (raises before anything is sent)
     arr = (_ffi.Obstacle * max(n, 1))()
     for o, item in zip(arr, obstacles.obstacles):
-        item._fill(o)
+        item._fill(o, engine)
     w = obstacles.node_weights
     if w is not None and n and w.size != engine.num_nodes():
         raise ValueError(f"node_weights must hold {engine.num_nodes()} entries")
@@ -342,6 +489,25 @@ class Contact:
         g = torch.empty(self.engine.num_nodes(), dtype=torch.float64, device=f"cuda:{self.engine.device}")
         self.engine._check(self.engine._lib.fh_contact_gap_dev(self.engine._h, C.c_void_p(g.data_ptr())))
         return g if device else g.cpu().numpy()
+
+    def sample_grid(self, grid, origin, points, device=False):
+        """(phi, grad) of an SdfGrid with its sample (0, ..) at `origin`, interpolated on the device at points (m, dim): a numpy array or a
+        device tensor (fh_sdf_grid_sample_dev); a point outside the box gets +inf and a zero gradient"""
+        import torch
+
+        d = grid.dim
+        o = np.zeros(3)
+        o[:d] = np.asarray(origin, dtype=np.float64).ravel()
+        if isinstance(points, torch.Tensor):
+            pts = points.to(dtype=torch.float64).contiguous().reshape(-1, d)
+        else:
+            pts = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, d))).to(f"cuda:{self.engine.device}")
+        m = pts.shape[0]
+        phi = torch.empty(m, dtype=torch.float64, device=pts.device)
+        grad = torch.empty((m, d), dtype=torch.float64, device=pts.device)
+        self.engine._check(self.engine._lib.fh_sdf_grid_sample_dev(self.engine._h, grid._id_on(self.engine), _ffi.fp(o), C.c_void_p(pts.data_ptr()), m,
+                                                                   C.c_void_p(phi.data_ptr()), C.c_void_p(grad.data_ptr())))
+        return (phi, grad) if device else (phi.cpu().numpy(), grad.cpu().numpy())
 
     def add_tangent_to(self, csr_values):
         """B (and, while friction is set, H) ADDED into the diagonal node blocks of the engine's CSR values: a device tensor in place, or a numpy array (returned)"""

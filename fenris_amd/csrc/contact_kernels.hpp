@@ -21,6 +21,13 @@
 // mu_o == 0, a node out of contact at xbar or at the centre of a ball or cavity gets nothing.  `friction` is set exactly when some
 // mu_o > 0: with it clear no lane executes or loads anything of the term.  friction_force / friction_apply / friction_diagonal /
 // friction_block / friction_potential are called wherever their contact_* twins are.
+//
+// FH_OBSTACLE_GRID: phi is the bi- / trilinear interpolant of a signed distance sampled on a regular grid (fh_sdf_grid_create; sdf_grid_eval
+// below is the whole arithmetic).  Outside the box of the samples the obstacle does not exist for a node: phi = +infinity, no gradient.
+// Inside, m = grad phi is not a unit vector: with gn = |m|, g = k w p m, B = k w [phi < 0] m m^T (Gauss-Newton: p Hess phi has a zero
+// diagonal and is indefinite, so it is dropped as the ball's curvature is) and, in friction, nbar = m / gn and lam = k w max(0, -phi) gn
+// at the lag position.  The three analytic kinds execute what they executed before the kind existed: every difference is behind a branch
+// on the kind, and behind the template flag G (contact_eval) that the node passes of the tiles clear while no grid stands.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,13 +37,20 @@
 namespace fenris_hip {
 
 struct ContactObstacle {
-    double p[3];      // a point of the plane / the centre, at the contact clock's current time (fh_set_obstacle_time)
-    double n[3];      // half-space: the unit normal
-    double radius;
+    double p[3];      // a point of the plane / the centre / the position of sample (0, 0, 0), at the contact clock's current time (fh_set_obstacle_time)
+    double n[3];      // half-space: the unit normal; grid: the spacings h
+    union {
+        double radius;
+        const double* grid;   // grid: its block on the device (SDF_GRID_HEADER doubles that hold the three sample counts as ints, then the samples, x fastest)
+    };
     double k;
     int kind, pad_;
     double c[3];      // c_o = d_o(t) - d_o(t_lag): the obstacle's own displacement over the lag interval (zero without a path)
 };
+// (a grid reuses n[] and radius and keeps its counts with its samples: the entry is as large as before the kind existed, so a table of
+// analytic obstacles is loaded as it was)
+static_assert(sizeof(ContactObstacle) == 96, "ContactObstacle grew");
+constexpr int SDF_GRID_HEADER = 2;
 
 struct ContactTable {
     int count, dim;          // count == 0: no obstacles; dim: the geometric (= solution) dimension
@@ -50,7 +64,7 @@ struct ContactTable {
     const double* slip_v;    // [N][dim] velocity (null: the slip is u - ubar)
     double slip_dt;
     double eps;
-    int friction, pad_;      // friction != 0: some mu > 0
+    int friction, grids;     // friction != 0: some mu > 0; grids != 0: some obstacle is a grid
 };
 inline ContactTable contact_off() {
     ContactTable t{};
@@ -62,10 +76,97 @@ inline ContactTable contact_off() {
 constexpr size_t NODE_PASS_ARG_BYTES = 512, KERNEL_ARG_LIMIT = 4096;
 static_assert(sizeof(ContactTable) + NODE_PASS_ARG_BYTES <= KERNEL_ARG_LIMIT, "the contact table no longer fits the kernel arguments");
 
-// phi, n = grad phi (has_n false: the centre of a ball or cavity, where the gradient does not exist) and 1 / |y| (0 for the half-space)
+// A signed distance sampled on a regular grid (`block`: the counts cnt[3] as ints in SDF_GRID_HEADER doubles, then the samples; sample
+// (ix, iy, iz) at values[(iz cnt[1] + iy) cnt[0] + ix], at origin + (ix h_0, iy h_1, iz h_2)), interpolated at x: with
+// t_a = (x_a - origin_a) / h_a the point is inside iff 0 <= t_a <= cnt_a - 1 on every axis (a NaN is outside);
+// i_a = min(floor(t_a), cnt_a - 2), f_a = t_a - i_a (the last face belongs to the last cell, f = 1); phi is the bi- / trilinear interpolant
+// of the 4 / 8 corner samples of cell i at f and m its gradient in x (1 / h_a per axis included).  Returns whether x is inside; outside
+// nothing is loaded and phi = +infinity, m = 0.  The corners are plain loads at compile-time offsets from one base index.  (On the host
+// the samples cannot be read: every point is outside there.)
 template <int D>
+__host__ __device__ __forceinline__ bool sdf_grid_eval(const double* block, const double (&h)[3], const double (&origin)[3], const double (&x)[D],
+                                                       double& phi, double (&m)[D]) {
+    phi = HUGE_VAL;
+#pragma unroll
+    for (int a = 0; a < D; ++a) m[a] = 0.0;
+#ifdef __HIP_DEVICE_COMPILE__
+    const int* header = reinterpret_cast<const int*>(block);   // (the same address in every lane: the counts go to scalar registers)
+    int cnt[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) cnt[a] = __builtin_amdgcn_readfirstlane(header[a]);
+    const double* values = block + SDF_GRID_HEADER;
+    double f[D];
+    int i[D];
+    bool inside = true;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        const double t = (x[a] - origin[a]) / h[a];
+        inside = inside && t >= 0.0 && t <= (double)(cnt[a] - 1);
+        const int cell = inside ? (int)t : 0;   // (t >= 0: the conversion is the floor)
+        i[a] = cell < cnt[a] - 2 ? cell : cnt[a] - 2;
+        f[a] = t - (double)i[a];
+    }
+    if (!inside) return false;
+    // (fewer than 2^31 samples: a sample index fits an int)
+    int base = i[D - 1];
+#pragma unroll
+    for (int a = D - 2; a >= 0; --a) base = base * cnt[a] + i[a];
+    const int stride[3] = {1, cnt[0], D == 3 ? cnt[0] * cnt[1] : 0};
+    const double* cell = values + base;
+    // the interpolant axis by axis: v[j] are the values left after the axes before `a` were interpolated, dv[b][j] their derivatives in
+    // f_b; all indices are compile-time constants, the arrays live in registers
+    double v[1 << D], dv[D][1 << D];
+#pragma unroll
+    for (int q = 0; q < (1 << D); ++q) {
+        int at = 0;
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+            if (q >> a & 1) at += stride[a];
+        v[q] = cell[at];
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+#pragma unroll
+        for (int j = 0; j < (1 << (D - 1 - a)); ++j) {
+            const double lo = v[2 * j], diff = v[2 * j + 1] - lo;
+#pragma unroll
+            for (int b = 0; b < a; ++b) dv[b][j] = dv[b][2 * j] + f[a] * (dv[b][2 * j + 1] - dv[b][2 * j]);
+            dv[a][j] = diff;
+            v[j] = lo + f[a] * diff;
+        }
+    }
+    const double s = v[0];
+    double ds[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) ds[a] = dv[a][0];
+    phi = s;
+#pragma unroll
+    for (int a = 0; a < D; ++a) m[a] = ds[a] / h[a];
+    return true;
+#else
+    (void)block, (void)h, (void)origin, (void)x;
+    return false;
+#endif
+}
+
+// phi, n = grad phi (has_n false: the centre of a ball or cavity, where the gradient does not exist; a grid: outside its box or on a flat
+// spot) and 1 / |y| (0 for the half-space and the grid).  A grid hands back n = m, NOT normalised, and gn = |m|; the other kinds leave gn alone.
+// G: whether the table may hold a grid (ContactTable::grids).  With G false the grid branch is not compiled: a kernel instantiated so is,
+// instruction for instruction and register for register, the kernel of the three analytic kinds alone, and the node passes of the tiles
+// launch that instantiation whenever no grid stands (a grid's 8 values in flight would otherwise set the register count of every launch).
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void contact_eval(const ContactObstacle& ob, const double (&x)[D], double& phi, double (&n)[D], bool& has_n,
-                                                      double& inv_r) {
+                                                      double& inv_r, double& gn) {
+    if (G && ob.kind == FH_OBSTACLE_GRID) {
+        sdf_grid_eval<D>(ob.grid, ob.n, ob.p, x, phi, n);
+        double m2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < D; ++c) m2 += n[c] * n[c];
+        gn = sqrt(m2);
+        has_n = gn > 0.0;
+        inv_r = 0.0;
+        return;
+    }
     if (ob.kind == FH_OBSTACLE_HALF_SPACE) {
         double s = 0.0;
 #pragma unroll
@@ -94,8 +195,8 @@ __host__ __device__ __forceinline__ void contact_eval(const ContactObstacle& ob,
 }
 
 // f(k w, phi, n, has_n, c) for every obstacle at node `node`, in the table's order (c: the coefficient of I - n n^T in B); only >= 0: that
-// obstacle alone (the resultants)
-template <int D, class F>
+// obstacle alone (the resultants).  A grid hands over n = m = grad phi as it is: k w p n and k w n n^T are its g and B, with c = 0
+template <int D, bool G = true, class F>
 __host__ __device__ __forceinline__ void contact_visit(const ContactTable& ct, int node, F&& f, int only = -1) {
     double x[D];
 #pragma unroll
@@ -103,21 +204,21 @@ __host__ __device__ __forceinline__ void contact_visit(const ContactTable& ct, i
     const double w = ct.w ? ct.w[node] : 1.0;
     for (int o = only < 0 ? 0 : only; o < (only < 0 ? ct.count : only + 1); ++o) {
         const ContactObstacle& ob = ct.o[o];
-        double phi, n[D], inv_r;
+        double phi, n[D], inv_r, gn;
         bool has_n;
-        contact_eval<D>(ob, x, phi, n, has_n, inv_r);
+        contact_eval<D, G>(ob, x, phi, n, has_n, inv_r, gn);
         const double p = phi < 0.0 ? phi : 0.0;
         f(ob.k * w, phi, n, has_n, ob.kind == FH_OBSTACLE_CAVITY ? -p * inv_r : 0.0);
     }
 }
 
 // g[] += g_i
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void contact_force(const ContactTable& ct, int node, double (&g)[D]) {
     double s[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) s[c] = 0.0;
-    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double) {
+    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double) {
         if (!(phi < 0.0) || !has_n) return;
         const double kp = kw * phi;
 #pragma unroll
@@ -128,12 +229,12 @@ __host__ __device__ __forceinline__ void contact_force(const ContactTable& ct, i
 }
 
 // y[] += scale B_i v
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void contact_apply(const ContactTable& ct, int node, const double (&v)[D], double scale, double (&y)[D]) {
     double s[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) s[c] = 0.0;
-    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
         if (!(phi < 0.0) || !has_n) return;
         double nv = 0.0;
 #pragma unroll
@@ -146,9 +247,9 @@ __host__ __device__ __forceinline__ void contact_apply(const ContactTable& ct, i
 }
 
 // B[][] += B_i
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void contact_block(const ContactTable& ct, int node, double (&B)[D][D]) {
-    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
         if (!(phi < 0.0) || !has_n) return;
 #pragma unroll
         for (int a = 0; a < D; ++a)
@@ -158,9 +259,9 @@ __host__ __device__ __forceinline__ void contact_block(const ContactTable& ct, i
 }
 
 // d[] += diag B_i
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void contact_diagonal(const ContactTable& ct, int node, double (&d)[D]) {
-    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
         if (!(phi < 0.0) || !has_n) return;
 #pragma unroll
         for (int c = 0; c < D; ++c) d[c] += kw * (n[c] * n[c] + cc * (1.0 - n[c] * n[c]));
@@ -168,25 +269,25 @@ __host__ __device__ __forceinline__ void contact_diagonal(const ContactTable& ct
 }
 
 // the node's share of E_c, and min_o phi_o
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ double contact_energy(const ContactTable& ct, int node) {
     double e = 0.0;
-    contact_visit<D>(ct, node, [&](double kw, double phi, const double (&)[D], bool, double) {
+    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&)[D], bool, double) {
         if (phi < 0.0) e += 0.5 * kw * phi * phi;
     });
     return e;
 }
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ double contact_gap(const ContactTable& ct, int node) {
     double g = HUGE_VAL;
-    contact_visit<D>(ct, node, [&](double, double phi, const double (&)[D], bool, double) { g = phi < g ? phi : g; });
+    contact_visit<D, G>(ct, node, [&](double, double phi, const double (&)[D], bool, double) { g = phi < g ? phi : g; });
     return g;
 }
 
 // f(mu lam, nbar, s, y, c1, c2) for every obstacle with mu > 0 that node `node` touches at its lag position, in the table's order.  A moving
 // obstacle (c_o != 0): the slip is taken relative to the obstacle, s = P (d_i - c_o), and with the lag displacement as the slip source the
 // obstacle stands at its lag position p - c_o; with slip_v the lag configuration is the current one, obstacle included.
-template <int D, class F>
+template <int D, bool G = true, class F>
 __host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, int node, F&& f, int only = -1) {
     double x[D], d[D];
 #pragma unroll
@@ -213,10 +314,16 @@ __host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, 
             rel[c] = d[c] - ob.c[c];
             if (!ct.slip_v) ob.p[c] -= ob.c[c];
         }
-        double phi, n[D], inv_r;
+        double phi, n[D], inv_r, gn;
         bool has_n;
-        contact_eval<D>(ob, x, phi, n, has_n, inv_r);
+        contact_eval<D, G>(ob, x, phi, n, has_n, inv_r, gn);
         if (!(phi < 0.0) || !has_n) continue;
+        double kw = ob.k * w;
+        if (G && ob.kind == FH_OBSTACLE_GRID) {   // nbar = m / |m|, and the normal force k w |phi| |m| bounds |q|
+#pragma unroll
+            for (int c = 0; c < D; ++c) n[c] /= gn;
+            kw *= gn;
+        }
         double nd = 0.0;
 #pragma unroll
         for (int c = 0; c < D; ++c) nd += n[c] * rel[c];
@@ -235,17 +342,17 @@ __host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, 
             c1 = 1.0 / y;
             c2 = c1 * c1 * c1;
         }
-        f(ct.mu[o] * (ob.k * w * -phi), n, s, y, c1, c2);
+        f(ct.mu[o] * (kw * -phi), n, s, y, c1, c2);
     }
 }
 
 // q[] += q_i
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void friction_force(const ContactTable& ct, int node, double (&q)[D]) {
     double t[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) t[c] = 0.0;
-    friction_visit<D>(ct, node, [&](double ml, const double (&)[D], const double (&s)[D], double, double c1, double) {
+    friction_visit<D, G>(ct, node, [&](double ml, const double (&)[D], const double (&s)[D], double, double c1, double) {
         const double m1 = ml * c1;
 #pragma unroll
         for (int c = 0; c < D; ++c) t[c] += m1 * s[c];
@@ -255,12 +362,12 @@ __host__ __device__ __forceinline__ void friction_force(const ContactTable& ct, 
 }
 
 // y[] += scale H_i v
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void friction_apply(const ContactTable& ct, int node, const double (&v)[D], double scale, double (&y)[D]) {
     double t[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) t[c] = 0.0;
-    friction_visit<D>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+    friction_visit<D, G>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
         double nv = 0.0, sv = 0.0;
 #pragma unroll
         for (int c = 0; c < D; ++c) {
@@ -275,9 +382,9 @@ __host__ __device__ __forceinline__ void friction_apply(const ContactTable& ct, 
 }
 
 // B[][] += H_i
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void friction_block(const ContactTable& ct, int node, double (&B)[D][D]) {
-    friction_visit<D>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+    friction_visit<D, G>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
 #pragma unroll
         for (int a = 0; a < D; ++a)
 #pragma unroll
@@ -289,19 +396,19 @@ __host__ __device__ __forceinline__ void friction_block(const ContactTable& ct, 
 }
 
 // d[] += diag H_i
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ void friction_diagonal(const ContactTable& ct, int node, double (&d)[D]) {
-    friction_visit<D>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+    friction_visit<D, G>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
 #pragma unroll
         for (int c = 0; c < D; ++c) d[c] += ml * (c1 * (1.0 - n[c] * n[c]) - c2 * s[c] * s[c]);
     });
 }
 
 // the node's share of D
-template <int D>
+template <int D, bool G = true>
 __host__ __device__ __forceinline__ double friction_potential(const ContactTable& ct, int node) {
     double e = 0.0;
-    friction_visit<D>(ct, node, [&](double ml, const double (&)[D], const double (&)[D], double y, double, double) {
+    friction_visit<D, G>(ct, node, [&](double ml, const double (&)[D], const double (&)[D], double y, double, double) {
         const double eps = ct.eps;
         e += ml * (y < eps ? -y * y * y / (3.0 * eps * eps) + y * y / eps + eps / 3.0 : y);
     });
@@ -309,6 +416,23 @@ __host__ __device__ __forceinline__ double friction_potential(const ContactTable
 }
 
 #ifdef __HIPCC__
+// fh_sdf_grid_sample_dev: the interpolant alone at m points, one lane per point, grid-stride; outside: phi = +infinity, a zero gradient
+template <int D>
+__global__ void __launch_bounds__(256) k_sdf_grid_sample(const ContactObstacle ob, const double* points, unsigned long long count, double* phi_out,
+                                                         double* grad_out) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * 256) {
+        double x[D], phi, m[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = points[i * D + c];
+        sdf_grid_eval<D>(ob.grid, ob.n, ob.p, x, phi, m);
+        phi_out[i] = phi;
+        if (grad_out) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) grad_out[i * D + c] = m[c];
+        }
+    }
+}
+
 // ---- the stand-alone node kernels: one thread per node
 
 // per-workgroup partials of E_c in a fixed tree; the caller sums them in index order (k_sum_partial_ranges / sum_partials)

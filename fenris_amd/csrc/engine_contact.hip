@@ -16,7 +16,11 @@
 #include "engine_internal.hpp"
 
 #include <cmath>
+#include <cstddef>
 #include <cstring>
+
+// (`grid` sits in the four bytes the compiler left before `stiffness`: binaries built against the struct without it stay valid)
+static_assert(sizeof(fh_obstacle) == 72 && offsetof(fh_obstacle, stiffness) == 8, "fh_obstacle: the layout of ABI version 1 moved");
 
 namespace {
 
@@ -157,6 +161,7 @@ void contact_clear(fh_ctx* c) {
     if (c->contact.count || c->contact_has_w) ++c->contact_gen;
     c->contact = contact_off();
     c->contact_has_w = false;
+    std::fill(c->contact_grid, c->contact_grid + FH_MAX_OBSTACLES, -1);   // (the grids themselves stay: they belong to the context)
 }
 
 int contact_add_force(fh_ctx* c, double* out_dev) {
@@ -219,11 +224,20 @@ int fh_set_obstacles(fh_ctx* c, const fh_obstacle* obstacles, uint64_t count, co
     if (count > FH_MAX_OBSTACLES) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": more than FH_MAX_OBSTACLES obstacles");
     if (count && !obstacles) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null obstacle list");
     ContactTable t = contact_off();
+    int grid_of[FH_MAX_OBSTACLES];
+    std::fill(grid_of, grid_of + FH_MAX_OBSTACLES, -1);
     for (uint64_t i = 0; i < count; ++i) {
         const fh_obstacle& o = obstacles[i];
         ContactObstacle& k = t.o[i];
-        if (o.kind != FH_OBSTACLE_HALF_SPACE && o.kind != FH_OBSTACLE_BALL && o.kind != FH_OBSTACLE_CAVITY)
+        if (o.kind != FH_OBSTACLE_HALF_SPACE && o.kind != FH_OBSTACLE_BALL && o.kind != FH_OBSTACLE_CAVITY && o.kind != FH_OBSTACLE_GRID)
             return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": unknown obstacle kind");
+        if (o.kind == FH_OBSTACLE_GRID) {   // (before anything of the standing list is touched)
+            if (o.grid < 0 || o.grid >= FH_MAX_SDF_GRIDS || c->sdf_grid[o.grid].dim == 0)
+                return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a grid obstacle names a grid that is not live (fh_sdf_grid_create)");
+            if (c->has_mesh && !c->ragged && (int)c->sdf_grid[o.grid].dim != c->ei.d)
+                return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the dim of a grid is not the geometric dim of the mesh");
+            grid_of[i] = o.grid;
+        }
         if (!std::isfinite(o.stiffness) || !(o.stiffness > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the stiffness must be positive and finite");
         double nn = 0.0;
         for (int a = 0; a < 3; ++a) {
@@ -239,6 +253,10 @@ int fh_set_obstacles(fh_ctx* c, const fh_obstacle* obstacles, uint64_t count, co
             if (!(nn > 0.0) || !std::isfinite(nn)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a half-space needs a normal that is not zero");
             const double len = std::sqrt(nn);
             for (int a = 0; a < 3; ++a) k.n[a] = o.normal[a] / len;
+        } else if (o.kind == FH_OBSTACLE_GRID) {   // (normal and radius are not read: n[] carries the spacings, the union the samples)
+            const fh_ctx::SdfGrid& g = c->sdf_grid[o.grid];
+            k.grid = g.values.p;
+            for (int a = 0; a < 3; ++a) k.n[a] = g.h[a];
         } else {
             if (!std::isfinite(o.radius) || !(o.radius > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": the radius must be positive and finite");
             k.radius = o.radius;
@@ -274,7 +292,9 @@ int fh_set_obstacles(fh_ctx* c, const fh_obstacle* obstacles, uint64_t count, co
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     t.count = (int)count;
+    for (uint64_t i = 0; i < count; ++i) t.grids = t.grids || grid_of[i] >= 0;
     c->contact = t;
+    std::copy(grid_of, grid_of + FH_MAX_OBSTACLES, c->contact_grid);
     c->contact_has_w = node_weights != nullptr;
     ++c->contact_gen;
     return FH_OK;
@@ -522,6 +542,93 @@ int fh_add_contact_tangent_csr_dev(fh_ctx* c, double* values_dev) {
     });
     HIP_TRY(c, hipGetLastError());
     c->last_kernel = "k_contact_csr";
+    return FH_OK;
+}
+
+// ---- sampled signed-distance grids
+
+int fh_sdf_grid_create(fh_ctx* c, uint32_t dim, const uint32_t n[3], const double spacing[3], const double* values, uint32_t* id) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_sdf_grid_create";
+    if (!n || !spacing || !values || !id) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    if (dim != 2 && dim != 3) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": dim must be 2 or 3");
+    if (dim == 2 && n[2] != 1) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a 2-D grid needs n[2] == 1");
+    uint64_t total = 1;
+    for (uint32_t a = 0; a < dim; ++a) {
+        if (n[a] < 2) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": an axis needs at least 2 samples");
+        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a spacing must be positive and finite");
+        total *= n[a];   // (three factors below 2^32: checked after each, no wrap before the test)
+        if (total >= (1ull << 31)) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": 2^31 samples or more");
+    }
+    for (uint64_t i = 0; i < total; ++i)
+        if (!std::isfinite(values[i])) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a sample is not finite");
+    int slot = -1;
+    for (int s = 0; s < FH_MAX_SDF_GRIDS && slot < 0; ++s)
+        if (c->sdf_grid[s].dim == 0) slot = s;
+    if (slot < 0) return c->fail(FH_UNSUPPORTED, std::string(who) + ": all FH_MAX_SDF_GRIDS slots are taken");
+    fh_ctx::SdfGrid& g = c->sdf_grid[slot];
+    // the block: the counts as ints in SDF_GRID_HEADER doubles, then the samples (contact_kernels.hpp)
+    const int header[2 * SDF_GRID_HEADER] = {(int)n[0], (int)n[1], dim == 3 ? (int)n[2] : 1, 0};
+    static_assert(sizeof header == sizeof(double) * SDF_GRID_HEADER, "the header of a grid block");
+    HIP_TRY(c, g.values.alloc((size_t)total + SDF_GRID_HEADER));
+    HIP_TRY(c, hipMemcpyAsync(g.values.p, header, sizeof header, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(g.values.p + SDF_GRID_HEADER, values, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int a = 0; a < 3; ++a) {
+        g.n[a] = (uint32_t)a < dim ? n[a] : 1u;
+        g.h[a] = (uint32_t)a < dim ? spacing[a] : 1.0;
+    }
+    g.dim = dim;
+    *id = (uint32_t)slot;
+    return FH_OK;
+}
+
+int fh_sdf_grid_destroy(fh_ctx* c, uint32_t id) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_sdf_grid_destroy";
+    if (id >= FH_MAX_SDF_GRIDS || c->sdf_grid[id].dim == 0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": not a live grid");
+    for (int o = 0; o < c->contact.count; ++o)
+        if (c->contact_grid[o] == (int)id) return c->fail(FH_INVALID_STATE, std::string(who) + ": an obstacle that stands refers to the grid (fh_set_obstacles)");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (a launch that reads the samples may still be in flight)
+    c->sdf_grid[id].values.release();
+    c->sdf_grid[id].dim = 0;
+    return FH_OK;
+}
+
+int fh_sdf_grid_info(fh_ctx* c, uint32_t id, uint32_t* dim, uint32_t n[3], double spacing[3]) {
+    if (!c) return FH_BAD_ARGUMENT;
+    if (id >= FH_MAX_SDF_GRIDS || c->sdf_grid[id].dim == 0) return c->fail(FH_BAD_ARGUMENT, "fh_sdf_grid_info: not a live grid");
+    const fh_ctx::SdfGrid& g = c->sdf_grid[id];
+    if (dim) *dim = g.dim;
+    for (int a = 0; a < 3; ++a) {
+        if (n) n[a] = g.n[a];
+        if (spacing) spacing[a] = g.h[a];
+    }
+    return FH_OK;
+}
+
+int fh_sdf_grid_sample_dev(fh_ctx* c, uint32_t id, const double origin[3], const double* points_dev, uint64_t m, double* phi_dev, double* grad_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_sdf_grid_sample_dev";
+    if (id >= FH_MAX_SDF_GRIDS || c->sdf_grid[id].dim == 0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": not a live grid");
+    if (!origin || (m && (!points_dev || !phi_dev))) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    if (m == 0) return FH_OK;
+    const fh_ctx::SdfGrid& g = c->sdf_grid[id];
+    ContactObstacle ob{};
+    ob.kind = FH_OBSTACLE_GRID;
+    ob.grid = g.values.p;
+    for (int a = 0; a < 3; ++a) {
+        ob.p[a] = (uint32_t)a < g.dim ? origin[a] : 0.0;
+        ob.n[a] = g.h[a];
+    }
+    const unsigned blocks = (unsigned)std::min<uint64_t>((m + 255) / 256, 65536);   // (grid-stride beyond)
+    if (g.dim == 2) hipLaunchKernelGGL((k_sdf_grid_sample<2>), dim3(blocks), dim3(256), 0, c->stream, ob, points_dev, (unsigned long long)m, phi_dev, grad_dev);
+    else hipLaunchKernelGGL((k_sdf_grid_sample<3>), dim3(blocks), dim3(256), 0, c->stream, ob, points_dev, (unsigned long long)m, phi_dev, grad_dev);
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_sdf_grid_sample";
     return FH_OK;
 }
 

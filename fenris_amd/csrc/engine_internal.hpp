@@ -500,6 +500,15 @@ struct fh_ctx {
     DevBuf<double> contact_part;       // workgroup partials of E_c and their range sums (kept: no allocation per record)
     bool contact_has_w = false;
     unsigned long long contact_gen = 0;
+    // sampled signed-distance grids (fh_sdf_grid_create): resources of the context, kept through fh_set_mesh* and fh_set_obstacles;
+    // contact_grid[o]: the slot obstacle o of `contact` refers to (-1: not a grid), so that a referenced grid is not destroyed
+    struct SdfGrid {
+        DevBuf<double> values;
+        uint32_t dim = 0, n[3] = {0, 0, 0};   // dim == 0: the slot is free
+        double h[3] = {0.0, 0.0, 0.0};
+    };
+    SdfGrid sdf_grid[FH_MAX_SDF_GRIDS];
+    int contact_grid[FH_MAX_OBSTACLES] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
     // moving obstacles (fh_set_obstacle_paths): obstacle o owns the knots path_begin[o] .. path_begin[o + 1] of path_time / path_offset (3
     // per knot); path_begin empty: no paths.  The contact clock (fh_set_obstacle_time): the two times and, per obstacle, the offsets
     // d_o(t) and d_o(t_lag) evaluated on the host; `contact` keeps the obstacles where fh_set_obstacles put them, the tables of

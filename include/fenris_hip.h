@@ -998,13 +998,26 @@ int fh_first_order_create(fh_ctx*, const fh_first_order_settings* settings, fh_d
  * The stand-alone terms at the context's u (none set: u = 0), over every node (Dirichlet nodes included), for users of the assembled path:
  *   fh_contact_energy; fh_contact_force_dev ADDS g into out_dev (S N doubles); fh_contact_gap_dev writes min_o phi_o(x_i) per node (N
  *   doubles; without obstacles +infinity); fh_add_contact_tangent_csr_dev ADDS B_i into the diagonal node blocks of the fh_pattern CSR
- *   values (FH_INVALID_STATE without a pattern). */
-enum { FH_OBSTACLE_HALF_SPACE = 0, FH_OBSTACLE_BALL = 1, FH_OBSTACLE_CAVITY = 2 };
+ *   values (FH_INVALID_STATE without a pattern).
+ * FH_OBSTACLE_GRID: a rigid obstacle of any shape, as a signed distance sampled on a regular grid (fh_sdf_grid_create below) and
+ *   interpolated on the device.  `grid` is the id of a live grid whose dim is the mesh's geometric dim (else FH_BAD_ARGUMENT), `point` the
+ *   position of sample (0, 0, 0) -- one grid may stand in several places, and a path moves it like any obstacle --, `stiffness` as ever;
+ *   `normal` and `radius` are not read.  With h the spacings, cnt the sample counts and t_a = (x_a - point_a) / h_a, a node is INSIDE the
+ *   box iff 0 <= t_a <= cnt_a - 1 on every axis (a NaN is outside); i_a = min(floor(t_a), cnt_a - 2), f_a = t_a - i_a; phi is the bi- /
+ *   trilinear interpolant of the 4 / 8 corner samples of cell i at f and m = grad phi (1 / h_a per axis included, NOT a unit vector).  With
+ *   gn = |m|:  E = (k w / 2) p^2,  g = k w p m,  B = k w [phi < 0] m m^T  (Gauss-Newton: p Hess phi has a zero diagonal, is indefinite and
+ *   is dropped, c = 0),  and in friction nbar = m / gn, lam = k w max(0, -phi) gn at the lag position, so |q| <= mu times the actual normal
+ *   force.  A flat spot (gn == 0) counts in E_c and gives nothing else.  OUTSIDE the box the obstacle does not exist for that node: no
+ *   energy, no force, no block, no friction, and fh_contact_gap_dev takes +infinity from it.  THE BOX MUST COVER EVERY PLACE A NODE CAN BE
+ *   WHILE phi < 0: a node that leaves the box while in contact loses the term abruptly.  The gradient is continuous inside a cell and has a
+ *   kink across cell faces. */
+enum { FH_OBSTACLE_HALF_SPACE = 0, FH_OBSTACLE_BALL = 1, FH_OBSTACLE_CAVITY = 2, FH_OBSTACLE_GRID = 3 };
 #define FH_MAX_OBSTACLES 16
 typedef struct {
     int kind;
+    int grid;               /* FH_OBSTACLE_GRID: the id fh_sdf_grid_create gave; not read for the other kinds (the four bytes were padding) */
     double stiffness;
-    double point[3];        /* a point of the plane, or the centre; 2-D: the first two entries */
+    double point[3];        /* a point of the plane, the centre, or the position of sample (0, 0, 0); 2-D: the first two entries */
     double normal[3];       /* FH_OBSTACLE_HALF_SPACE: points into the admissible side, any length > 0 */
     double radius;          /* FH_OBSTACLE_BALL, FH_OBSTACLE_CAVITY */
 } fh_obstacle;
@@ -1013,6 +1026,22 @@ int fh_contact_energy(fh_ctx*, double* energy);
 int fh_contact_force_dev(fh_ctx*, double* out_dev);
 int fh_contact_gap_dev(fh_ctx*, double* gap_dev);
 int fh_add_contact_tangent_csr_dev(fh_ctx*, double* values_dev);
+/* ---- sampled signed-distance grids: resources of the context, referred to by FH_OBSTACLE_GRID obstacles ----------------------------------
+ * fh_sdf_grid_create: dim 2 or 3; n: the sample counts per axis (2-D: n[2] must be 1, spacing[2] is not read); values: host memory, x
+ *   fastest -- sample (ix, iy, iz) at values[(iz n[1] + iy) n[0] + ix] --, copied to the device once.  *id is a slot number in
+ *   [0, FH_MAX_SDF_GRIDS); a destroyed slot is reused.  FH_BAD_ARGUMENT: another dim, n[a] < 2 on an axis with extent, 2^31 samples or more,
+ *   a spacing that is not finite and positive, a sample that is not finite, a null pointer; FH_UNSUPPORTED: every slot is taken.
+ * Grids belong to the context: fh_set_mesh* and fh_set_obstacles leave them alone, fh_destroy frees them.  fh_sdf_grid_destroy:
+ *   FH_BAD_ARGUMENT for an id that is not live, FH_INVALID_STATE while an obstacle that stands refers to the grid.
+ * fh_sdf_grid_info: dim, n and spacing as given (any may be NULL).
+ * fh_sdf_grid_sample_dev: the interpolant alone (k_sdf_grid_sample), with sample (0, 0, 0) at `origin` (dim entries read), at m points
+ *   (points_dev: m x dim doubles) into phi_dev (m) and grad_dev (m x dim, may be NULL); a point outside gets +infinity and a zero gradient. */
+#define FH_MAX_SDF_GRIDS 16
+int fh_sdf_grid_create(fh_ctx*, uint32_t dim, const uint32_t n[3], const double spacing[3], const double* values, uint32_t* id);
+int fh_sdf_grid_destroy(fh_ctx*, uint32_t id);
+int fh_sdf_grid_info(fh_ctx*, uint32_t id, uint32_t* dim, uint32_t n[3], double spacing[3]);
+int fh_sdf_grid_sample_dev(fh_ctx*, uint32_t id, const double origin[3], const double* points_dev, uint64_t m, double* phi_dev,
+                           double* grad_dev);
 /* ---- Coulomb friction on the obstacles, lagged and smoothed (Li et al., "Incremental Potential Contact", 2020, section 5) -------------
  * Obstacle o has a coefficient mu_o >= 0 (default 0); the context has a slip length eps > 0 and a lag displacement ubar (S N doubles on the
  * device, owned by the context; u = 0 until fh_set_friction_reference is called).  With xbar_i = X_i + ubar_i, constants of u:
