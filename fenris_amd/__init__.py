@@ -26,6 +26,7 @@ from .multigrid import GeometricMultigrid
 from .dirichlet import DofSet, dof_masks
 from .dynamics import (BackwardEuler, CentralDifference, DynamicsError, DynamicsRecord, FirstOrderIntegrator, FirstOrderRecord, ForwardEuler, Newmark,
                        RayleighDamping, RungeKuttaLegendre, ThetaMethod, TimeIntegrator)
+from .contact import AugmentedLagrangian, AugmentedLagrangianError, AugmentedLagrangianResult, MultiplierUpdate
 from .contact import Ball, Cavity, Contact, GridObstacle, HalfSpace, ObstaclePath, Obstacles, SdfGrid, sdf_box, sdf_circle, sdf_union
 from .eigen import EigenResult, EigenSolveError, MatrixFreeEigensolver
 from .recovery import Recovery

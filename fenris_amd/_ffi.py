@@ -64,6 +64,12 @@ class Obstacle(C.Structure):
     _fields_ = [("kind", C.c_int), ("grid", C.c_int), ("stiffness", C.c_double), ("point", C.c_double * 3), ("normal", C.c_double * 3), ("radius", C.c_double)]
 
 
+class MultiplierUpdateStats(C.Structure):
+    """fh_multiplier_update"""
+
+    _fields_ = [("max_change", C.c_double), ("max_penetration", C.c_double), ("max_force", C.c_double), ("active", C.c_uint64)]
+
+
 class FenrisError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"fenris_hip error {code}: {message}")
@@ -218,6 +224,12 @@ _SIGS = {
     "fh_obstacle_count": (C.c_int, [C.c_void_p, u64p]),
     "fh_obstacle_offsets": (C.c_int, [C.c_void_p, f64p, f64p]),
     "fh_contact_resultants": (C.c_int, [C.c_void_p, f64p, f64p]),
+    "fh_set_contact_multipliers": (C.c_int, [C.c_void_p, f64p]),
+    "fh_set_contact_multipliers_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_contact_multipliers": (C.c_int, [C.c_void_p, f64p]),
+    "fh_contact_multipliers_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_contact_multiplier_forces_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fh_contact_multiplier_update": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.POINTER(MultiplierUpdateStats)]),
     "fh_mg_create": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(u64p), C.POINTER(u64p), C.POINTER(f64p),
                                C.POINTER(C.c_void_p)]),
     "fh_mg_destroy": (None, [C.c_void_p]),

@@ -28,6 +28,16 @@ friction=, path=)` the obstacle it makes with its first sample at `origin`.  The
 not be a unit vector (force k w p grad phi, Gauss-Newton block k w grad phi grad phi^T).  Outside the box of the samples the obstacle does
 not exist: the box must cover every place a node can be while phi < 0.  The samples are uploaded once per (engine, grid).
 
+Augmented Lagrangian (fh_set_contact_multipliers, fh_contact_multiplier_update): a multiplier per obstacle and node, kept as a length
+s_oi >= 0 that stands for the force k_o w_i s_oi.  The term is then formed from phi_eff = phi - s_oi wherever it was formed from phi, and
+the update s <- max(0, s - phi) between solves drives the penetration to zero at a fixed, moderate k:
+
+    newton = MatrixFreeNewton(asm).with_load(f).with_obstacles(Obstacles([floor]))
+    result = AugmentedLagrangian(newton, tol=1e-10).solve(u, NewtonSettings(30, 1e-11))
+
+`Contact.multipliers()`, `.set_multipliers(s)`, `.multiplier_forces()` and `.update_multipliers()` are the pieces.  Every solver and
+integrator sees the multipliers as a frozen field; they are kept with the object whose obstacles are bound and travel with them.
+
 `with_obstacles` on MatrixFreeTangent, MatrixFreeShiftedTangent, MatrixFreeNewton, the time integrators and MatrixFreeEigensolver makes
 the obstacles belong to that object: they are handed to the engine before every use, as its Dirichlet nodes are.  An object that was never
 given obstacles does not inherit those of another object: it clears them from the engine before its use (the owner hands them over again
@@ -38,6 +48,7 @@ path.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -371,6 +382,15 @@ def bind_obstacles(obj, force=False):
         if clock is not None and len(sent) and sent.has_paths():
             obj.engine._check(obj.engine._lib.fh_set_obstacle_time(obj.engine._h, *clock))
         _send_friction_reference(obj)
+        _send_multipliers(obj)
+
+
+def _send_multipliers(obj):
+    """the multipliers kept with the object (a device tensor, count x N) to its engine again: fh_set_obstacles cleared them"""
+    s = getattr(obj, "_multipliers", None)
+    if s is None or not len(obj._obstacles or ()):
+        return
+    obj.engine._check(obj.engine._lib.fh_set_contact_multipliers_dev(obj.engine._h, C.c_void_p(s.data_ptr())))
 
 
 def _has_friction(obj):
@@ -416,8 +436,21 @@ def with_obstacles(obj, obstacles):
     obj._obstacles = obstacles
     obj._owns_obstacles = True
     obj._contact_clock = None   # (new obstacles: the clock starts at (0, 0), as after Engine.set_obstacles)
+    obj._multipliers = None     # (and no multipliers stand)
     bind_obstacles(obj, force=True)
     return obj
+
+
+@dataclass
+class MultiplierUpdate:
+    """what fh_contact_multiplier_update reports over the counted (node, obstacle) pairs: max_change = max |s_new - s_old| (the convergence
+    measure: |phi| where the pair is active afterwards, the released multiplier otherwise), max_penetration = max max(0, -phi), active =
+    the number of pairs with s_new > 0, max_force = the largest lam = k w s_new"""
+
+    max_change: float
+    max_penetration: float
+    active: int
+    max_force: float
 
 
 class Contact:
@@ -520,3 +553,119 @@ class Contact:
         self.engine._check(self.engine._lib.fh_add_contact_tangent_csr_dev(self.engine._h, C.c_void_p(t.data_ptr())))
         csr_values[...] = t.cpu().numpy().reshape(np.shape(csr_values))
         return csr_values
+
+    # ---- augmented Lagrangian: the multipliers, lengths s[o, i] >= 0 that stand for the forces k_o w_i s[o, i]
+    def _keep_multipliers(self, standing):
+        """the multipliers as they stand now go with the object whose obstacles are bound (bind_obstacles sends them again)"""
+        owner = getattr(self.engine, "_contact_bound", None)
+        if owner is not None:
+            owner._multipliers = self.multipliers(device=True) if standing else None
+
+    def multipliers(self, device=False):
+        """s of shape (count, N); zeros while none are set"""
+        import torch
+
+        s = torch.empty((self._count(), self.engine.num_nodes()), dtype=torch.float64, device=f"cuda:{self.engine.device}")
+        self.engine._check(self.engine._lib.fh_contact_multipliers_dev(self.engine._h, C.c_void_p(s.data_ptr())))
+        return s if device else s.cpu().numpy()
+
+    def set_multipliers(self, s):
+        """s: (count, N) entries >= 0, a numpy array (checked) or a device tensor (copied as it is); None clears them"""
+        eng = self.engine
+        if s is None:
+            eng._check(eng._lib.fh_set_contact_multipliers(eng._h, None))
+        else:
+            want = self._count() * eng.num_nodes()
+            if hasattr(s, "data_ptr"):
+                import torch
+
+                t = s.to(dtype=torch.float64, device=f"cuda:{eng.device}").contiguous()
+                if t.numel() != want:
+                    raise ValueError(f"the multipliers must hold {want} entries")
+                eng._check(eng._lib.fh_set_contact_multipliers_dev(eng._h, C.c_void_p(t.data_ptr())))
+            else:
+                a = np.ascontiguousarray(np.asarray(s, dtype=np.float64).ravel())
+                if a.size != want:
+                    raise ValueError(f"the multipliers must hold {want} entries")
+                eng._check(eng._lib.fh_set_contact_multipliers(eng._h, _ffi.fp(a)))
+        self._keep_multipliers(s is not None)
+        return self
+
+    def multiplier_forces(self, device=False):
+        """lam of shape (count, N): k_o w_i s[o, i], for a grid times |grad phi| at the node's current position"""
+        import torch
+
+        lam = torch.empty((self._count(), self.engine.num_nodes()), dtype=torch.float64, device=f"cuda:{self.engine.device}")
+        self.engine._check(self.engine._lib.fh_contact_multiplier_forces_dev(self.engine._h, C.c_void_p(lam.data_ptr())))
+        return lam if device else lam.cpu().numpy()
+
+    def update_multipliers(self, skip_nodes=None):
+        """s <- max(0, s - phi) at the engine's u (the first call starts from zeros); skip_nodes (the fully held nodes) keep s = 0 and stay
+        out of the statistics.  Returns a MultiplierUpdate"""
+        skip = np.zeros(0, dtype=np.uint64) if skip_nodes is None else _ffi.as_u64(skip_nodes).reshape(-1)
+        st = _ffi.MultiplierUpdateStats()
+        self.engine._check(self.engine._lib.fh_contact_multiplier_update(self.engine._h, _ffi.up(skip) if len(skip) else None, len(skip), C.byref(st)))
+        self._keep_multipliers(True)
+        return MultiplierUpdate(st.max_change, st.max_penetration, int(st.active), st.max_force)
+
+
+@dataclass
+class AugmentedLagrangianResult:
+    """updates: the multiplier updates taken; multiplier_updates / newton_results: one entry per update; converged: the last update's
+    max_change <= tol"""
+
+    updates: int = 0
+    multiplier_updates: list = field(default_factory=list)
+    newton_results: list = field(default_factory=list)
+    converged: bool = False
+
+
+class AugmentedLagrangianError(RuntimeError):
+    """max_updates multiplier updates without max_change <= tol; `result` holds the partial AugmentedLagrangianResult (u is the last solve's)"""
+
+    def __init__(self, message, result):
+        super().__init__(message)
+        self.result = result
+
+
+class AugmentedLagrangian:
+    """The Uzawa iteration on a MatrixFreeNewton with obstacles: solve with the multipliers frozen, update them at the solution
+    (s <- max(0, s - phi)), and again until the largest change of a multiplier is <= tol.  The penetration goes to zero at the fixed k
+    of the obstacles.  The multipliers that stand at entry are the start (a load step warm-starts from the last); the solver's fully held
+    Dirichlet nodes keep s = 0."""
+
+    def __init__(self, newton, max_updates=30, tol=1e-10):
+        self.newton, self.engine = newton, newton.engine
+        self.max_updates, self.tol = int(max_updates), float(tol)
+
+    def with_obstacles(self, obstacles):
+        """the obstacles of the underlying solver (its with_obstacles); returns self"""
+        self.newton.with_obstacles(obstacles)
+        return self
+
+    def _held_nodes(self):
+        from .dirichlet import DofSet
+
+        held = DofSet.of(self.newton._nodes)
+        full = (1 << self.newton.element_assembler.solution_dim()) - 1
+        return held.nodes[(held.masks & full) == full]
+
+    def solve(self, u, settings=None, **newton_kwargs):
+        """u: the guess, overwritten by the solution; settings and newton_kwargs go to MatrixFreeNewton.solve.  Returns an
+        AugmentedLagrangianResult; raises AugmentedLagrangianError when max_updates run out, and whatever the Newton solve raises"""
+        if not getattr(self.newton, "_owns_obstacles", False) or not len(self.newton._obstacles or ()):
+            raise ValueError("AugmentedLagrangian needs a solver with obstacles (with_obstacles)")
+        result = AugmentedLagrangianResult()
+        skip = self._held_nodes()
+        con = Contact(self.engine)
+        for _ in range(self.max_updates):
+            args = () if settings is None else (settings,)
+            result.newton_results.append(self.newton.solve(u, *args, **newton_kwargs))   # (binds the obstacles and their multipliers)
+            up = con.update_multipliers(skip)
+            result.multiplier_updates.append(up)
+            result.updates += 1
+            if up.max_change <= self.tol:
+                result.converged = True
+                return result
+        raise AugmentedLagrangianError(f"{self.max_updates} multiplier updates, max_change {result.multiplier_updates[-1].max_change:.3e} > {self.tol:.3e}",
+                                       result)

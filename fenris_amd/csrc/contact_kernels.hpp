@@ -28,6 +28,16 @@
 // diagonal and is indefinite, so it is dropped as the ball's curvature is) and, in friction, nbar = m / gn and lam = k w max(0, -phi) gn
 // at the lag position.  The three analytic kinds execute what they executed before the kind existed: every difference is behind a branch
 // on the kind, and behind the template flag G (contact_eval) that the node passes of the tiles clear while no grid stands.
+//
+// Augmented Lagrangian (fh_set_contact_multipliers, fh_contact_multiplier_update): a multiplier per obstacle and node, kept as a LENGTH
+// s_oi >= 0 that stands for the force lam_oi = k_o w_i s_oi (no division on the device, w_i = 0 is harmless).  With
+//   phi_eff = phi_o(x_i) - s_oi,  p = min(0, phi_eff)
+// everything above is formed from phi_eff where it was formed from phi: g = k w p n, B with [phi_eff < 0] and c = -p / |y|, the friction
+// bound lam = k w max(0, -phi_eff(xbar)) with the CURRENT s_oi, and E_c = sum (k w / 2) (p^2 - s^2).  g is the gradient of E_c with s frozen.
+// contact_gap stays the geometric min_o phi_o.  The update s <- max(0, s - phi_o(x_i)) is k_contact_multiplier_update.  The shift sits in
+// contact_visit / friction_visit behind the template flag A, which the node passes of the tiles clear while no multipliers stand
+// (ContactTable::mult null): such an instantiation is the kernel it was before the flag existed.  With A set and every s = 0 the
+// arithmetic is phi - 0.0 and e - 0.0: the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +75,8 @@ struct ContactTable {
     double slip_dt;
     double eps;
     int friction, grids;     // friction != 0: some mu > 0; grids != 0: some obstacle is a grid
+    const double* mult;      // [count][mult_stride] multiplier lengths s_oi (null: none stand)
+    size_t mult_stride;      // >= N
 };
 inline ContactTable contact_off() {
     ContactTable t{};
@@ -196,7 +208,8 @@ __host__ __device__ __forceinline__ void contact_eval(const ContactObstacle& ob,
 
 // f(k w, phi, n, has_n, c) for every obstacle at node `node`, in the table's order (c: the coefficient of I - n n^T in B); only >= 0: that
 // obstacle alone (the resultants).  A grid hands over n = m = grad phi as it is: k w p n and k w n n^T are its g and B, with c = 0
-template <int D, bool G = true, class F>
+// A: whether multipliers may stand (ct.mult): phi handed to f is then phi_eff = phi - s_oi, and s_oi itself the last argument (0 without)
+template <int D, bool G = true, bool A = true, class F>
 __host__ __device__ __forceinline__ void contact_visit(const ContactTable& ct, int node, F&& f, int only = -1) {
     double x[D];
 #pragma unroll
@@ -207,18 +220,23 @@ __host__ __device__ __forceinline__ void contact_visit(const ContactTable& ct, i
         double phi, n[D], inv_r, gn;
         bool has_n;
         contact_eval<D, G>(ob, x, phi, n, has_n, inv_r, gn);
+        double sm = 0.0;
+        if constexpr (A) {
+            if (ct.mult) sm = ct.mult[(size_t)o * ct.mult_stride + node];
+            phi -= sm;
+        }
         const double p = phi < 0.0 ? phi : 0.0;
-        f(ob.k * w, phi, n, has_n, ob.kind == FH_OBSTACLE_CAVITY ? -p * inv_r : 0.0);
+        f(ob.k * w, phi, n, has_n, ob.kind == FH_OBSTACLE_CAVITY ? -p * inv_r : 0.0, sm);
     }
 }
 
 // g[] += g_i
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ void contact_force(const ContactTable& ct, int node, double (&g)[D]) {
     double s[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) s[c] = 0.0;
-    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double) {
+    contact_visit<D, G, A>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double, double) {
         if (!(phi < 0.0) || !has_n) return;
         const double kp = kw * phi;
 #pragma unroll
@@ -229,12 +247,12 @@ __host__ __device__ __forceinline__ void contact_force(const ContactTable& ct, i
 }
 
 // y[] += scale B_i v
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ void contact_apply(const ContactTable& ct, int node, const double (&v)[D], double scale, double (&y)[D]) {
     double s[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) s[c] = 0.0;
-    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+    contact_visit<D, G, A>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc, double) {
         if (!(phi < 0.0) || !has_n) return;
         double nv = 0.0;
 #pragma unroll
@@ -247,9 +265,9 @@ __host__ __device__ __forceinline__ void contact_apply(const ContactTable& ct, i
 }
 
 // B[][] += B_i
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ void contact_block(const ContactTable& ct, int node, double (&B)[D][D]) {
-    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+    contact_visit<D, G, A>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc, double) {
         if (!(phi < 0.0) || !has_n) return;
 #pragma unroll
         for (int a = 0; a < D; ++a)
@@ -259,9 +277,9 @@ __host__ __device__ __forceinline__ void contact_block(const ContactTable& ct, i
 }
 
 // d[] += diag B_i
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ void contact_diagonal(const ContactTable& ct, int node, double (&d)[D]) {
-    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc) {
+    contact_visit<D, G, A>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double cc, double) {
         if (!(phi < 0.0) || !has_n) return;
 #pragma unroll
         for (int c = 0; c < D; ++c) d[c] += kw * (n[c] * n[c] + cc * (1.0 - n[c] * n[c]));
@@ -269,25 +287,28 @@ __host__ __device__ __forceinline__ void contact_diagonal(const ContactTable& ct
 }
 
 // the node's share of E_c, and min_o phi_o
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ double contact_energy(const ContactTable& ct, int node) {
     double e = 0.0;
-    contact_visit<D, G>(ct, node, [&](double kw, double phi, const double (&)[D], bool, double) {
+    contact_visit<D, G, A>(ct, node, [&](double kw, double phi, const double (&)[D], bool, double, double sm) {
         if (phi < 0.0) e += 0.5 * kw * phi * phi;
+        if constexpr (A) e -= 0.5 * kw * sm * sm;   // (k w / 2) (p^2 - s^2); s = 0: e - 0.0
     });
     return e;
 }
+// (the geometric distance: never shifted by a multiplier)
 template <int D, bool G = true>
 __host__ __device__ __forceinline__ double contact_gap(const ContactTable& ct, int node) {
     double g = HUGE_VAL;
-    contact_visit<D, G>(ct, node, [&](double, double phi, const double (&)[D], bool, double) { g = phi < g ? phi : g; });
+    contact_visit<D, G, false>(ct, node, [&](double, double phi, const double (&)[D], bool, double, double) { g = phi < g ? phi : g; });
     return g;
 }
 
 // f(mu lam, nbar, s, y, c1, c2) for every obstacle with mu > 0 that node `node` touches at its lag position, in the table's order.  A moving
 // obstacle (c_o != 0): the slip is taken relative to the obstacle, s = P (d_i - c_o), and with the lag displacement as the slip source the
 // obstacle stands at its lag position p - c_o; with slip_v the lag configuration is the current one, obstacle included.
-template <int D, bool G = true, class F>
+// With A the node is in contact at xbar iff phi_eff(xbar) = phi(xbar) - s_oi < 0, s_oi the multiplier as it stands now.
+template <int D, bool G = true, bool A = true, class F>
 __host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, int node, F&& f, int only = -1) {
     double x[D], d[D];
 #pragma unroll
@@ -317,6 +338,9 @@ __host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, 
         double phi, n[D], inv_r, gn;
         bool has_n;
         contact_eval<D, G>(ob, x, phi, n, has_n, inv_r, gn);
+        if constexpr (A) {
+            if (ct.mult) phi -= ct.mult[(size_t)o * ct.mult_stride + node];
+        }
         if (!(phi < 0.0) || !has_n) continue;
         double kw = ob.k * w;
         if (G && ob.kind == FH_OBSTACLE_GRID) {   // nbar = m / |m|, and the normal force k w |phi| |m| bounds |q|
@@ -347,12 +371,12 @@ __host__ __device__ __forceinline__ void friction_visit(const ContactTable& ct, 
 }
 
 // q[] += q_i
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ void friction_force(const ContactTable& ct, int node, double (&q)[D]) {
     double t[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) t[c] = 0.0;
-    friction_visit<D, G>(ct, node, [&](double ml, const double (&)[D], const double (&s)[D], double, double c1, double) {
+    friction_visit<D, G, A>(ct, node, [&](double ml, const double (&)[D], const double (&s)[D], double, double c1, double) {
         const double m1 = ml * c1;
 #pragma unroll
         for (int c = 0; c < D; ++c) t[c] += m1 * s[c];
@@ -362,12 +386,12 @@ __host__ __device__ __forceinline__ void friction_force(const ContactTable& ct, 
 }
 
 // y[] += scale H_i v
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ void friction_apply(const ContactTable& ct, int node, const double (&v)[D], double scale, double (&y)[D]) {
     double t[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) t[c] = 0.0;
-    friction_visit<D, G>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+    friction_visit<D, G, A>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
         double nv = 0.0, sv = 0.0;
 #pragma unroll
         for (int c = 0; c < D; ++c) {
@@ -382,9 +406,9 @@ __host__ __device__ __forceinline__ void friction_apply(const ContactTable& ct, 
 }
 
 // B[][] += H_i
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ void friction_block(const ContactTable& ct, int node, double (&B)[D][D]) {
-    friction_visit<D, G>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+    friction_visit<D, G, A>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
 #pragma unroll
         for (int a = 0; a < D; ++a)
 #pragma unroll
@@ -396,19 +420,19 @@ __host__ __device__ __forceinline__ void friction_block(const ContactTable& ct, 
 }
 
 // d[] += diag H_i
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ void friction_diagonal(const ContactTable& ct, int node, double (&d)[D]) {
-    friction_visit<D, G>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
+    friction_visit<D, G, A>(ct, node, [&](double ml, const double (&n)[D], const double (&s)[D], double, double c1, double c2) {
 #pragma unroll
         for (int c = 0; c < D; ++c) d[c] += ml * (c1 * (1.0 - n[c] * n[c]) - c2 * s[c] * s[c]);
     });
 }
 
 // the node's share of D
-template <int D, bool G = true>
+template <int D, bool G = true, bool A = true>
 __host__ __device__ __forceinline__ double friction_potential(const ContactTable& ct, int node) {
     double e = 0.0;
-    friction_visit<D, G>(ct, node, [&](double ml, const double (&)[D], const double (&)[D], double y, double, double) {
+    friction_visit<D, G, A>(ct, node, [&](double ml, const double (&)[D], const double (&)[D], double y, double, double) {
         const double eps = ct.eps;
         e += ml * (y < eps ? -y * y * y / (3.0 * eps * eps) + y * y / eps + eps / 3.0 : y);
     });
@@ -551,7 +575,7 @@ __global__ void __launch_bounds__(256) k_contact_resultants(const ContactTable c
     for (int o = 0; o < ct.count; ++o) {   // (count is uniform: every lane takes part in every shuffle)
         double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         if (node < num_nodes) {
-            contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double) {
+            contact_visit<D>(ct, node, [&](double kw, double phi, const double (&n)[D], bool has_n, double, double) {
                 if (!(phi < 0.0) || !has_n) return;
                 const double kp = kw * phi;
 #pragma unroll
@@ -576,6 +600,106 @@ __global__ void __launch_bounds__(256) k_contact_resultants(const ContactTable c
     const int K = 6 * ct.count;
     if ((int)threadIdx.x < K)
         partial[(size_t)blockIdx.x * K + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+// ---- augmented Lagrangian: the multiplier update and the forces the multipliers stand for
+
+// max of v >= 0 over the lanes of a wavefront (xor-shuffles: every lane ends with it)
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double t = __shfl_xor(v, off);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+
+// fh_contact_multiplier_update: s_oi <- max(0, s_oi - phi_o(x_i)) in place, one thread per node, the obstacles in the table's order
+// (phi = +infinity outside a grid's box: 0).  `ct` is the table WITHOUT multipliers (phi is the geometric distance); mult: [count][stride],
+// read and written by this lane alone.  skip (may be null): a byte per node, nonzero: the node keeps s = 0 and stays out of the
+// statistics.  Row blockIdx.x of `partial` holds 4 doubles over the workgroup's counted (node, obstacle) pairs: max |s_new - s_old|,
+// max max(0, -phi), the number with s_new > 0, max lam = k w s_new (a grid: times |grad phi|).  The lanes of a wavefront are combined by
+// xor-shuffles, the four wavefronts through LDS in index order after ONE barrier; the caller combines the rows in index order.  No
+// atomics: equal input gives equal bits.
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_multiplier_update(const ContactTable ct, int num_nodes, double* mult, size_t stride,
+                                                                   const unsigned char* skip, double* partial) {
+    __shared__ double red[4][4];
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    double change = 0.0, pen = 0.0, active = 0.0, lam = 0.0;
+    if (node < num_nodes) {
+        double x[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = ct.X[(size_t)node * D + c] + (ct.u ? ct.u[(size_t)node * D + c] : 0.0);
+        const double w = ct.w ? ct.w[node] : 1.0;
+        const bool held = skip && skip[node];
+        for (int o = 0; o < ct.count; ++o) {
+            const ContactObstacle& ob = ct.o[o];
+            double phi, n[D], inv_r, gn = 1.0;
+            bool has_n;
+            contact_eval<D>(ob, x, phi, n, has_n, inv_r, gn);
+            double* at = mult + (size_t)o * stride + node;
+            if (held) {
+                *at = 0.0;
+                continue;
+            }
+            const double s_old = *at, t = s_old - phi;
+            const double s_new = t > 0.0 ? t : 0.0;
+            *at = s_new;
+            const double dc = fabs(s_new - s_old), dp = phi < 0.0 ? -phi : 0.0;
+            const double l = ob.k * w * s_new * (ob.kind == FH_OBSTACLE_GRID ? gn : 1.0);
+            change = dc > change ? dc : change;
+            pen = dp > pen ? dp : pen;
+            active += s_new > 0.0 ? 1.0 : 0.0;
+            lam = l > lam ? l : lam;
+        }
+    }
+    change = wave_max(change);
+    pen = wave_max(pen);
+    lam = wave_max(lam);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) active += __shfl_xor(active, off);   // (whole numbers: exact)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wave] = change;
+        red[1][wave] = pen;
+        red[2][wave] = active;
+        red[3][wave] = lam;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const double* r = red[threadIdx.x];
+        double v;
+        if (threadIdx.x == 2) v = (r[0] + r[1]) + (r[2] + r[3]);
+        else {
+            const double a = r[0] > r[1] ? r[0] : r[1], b = r[2] > r[3] ? r[2] : r[3];
+            v = a > b ? a : b;
+        }
+        partial[(size_t)blockIdx.x * 4 + threadIdx.x] = v;
+    }
+}
+
+// fh_contact_multiplier_forces_dev: lam[o][i] = k_o w_i s_oi, for a grid times |grad phi| at the node's current position (0 outside its box)
+template <int D>
+__global__ void __launch_bounds__(256) k_contact_multiplier_forces(const ContactTable ct, int num_nodes, double* lam) {
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    if (node >= num_nodes) return;
+    double x[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) x[c] = ct.X[(size_t)node * D + c] + (ct.u ? ct.u[(size_t)node * D + c] : 0.0);
+    const double w = ct.w ? ct.w[node] : 1.0;
+    for (int o = 0; o < ct.count; ++o) {
+        const ContactObstacle& ob = ct.o[o];
+        const double s = ct.mult ? ct.mult[(size_t)o * ct.mult_stride + node] : 0.0;
+        double f = ob.k * w * s;
+        if (ob.kind == FH_OBSTACLE_GRID) {
+            double phi, n[D], inv_r, gn = 0.0;
+            bool has_n;
+            contact_eval<D>(ob, x, phi, n, has_n, inv_r, gn);
+            f *= gn;
+        }
+        lam[(size_t)o * num_nodes + node] = f;
+    }
 }
 #endif
 

@@ -40,6 +40,8 @@ ContactTable table_at_u(const fh_ctx* c) {
             if (cur != 0.0) t.o[o].p[a] += cur;   // (the bits of an obstacle placed at point + d_o(t))
             t.o[o].c[a] = cur - lag;
         }
+    t.mult = c->contact_has_mult ? c->contact_mult.p : nullptr;
+    t.mult_stride = (size_t)c->N;
     t.friction = t.friction && !c->friction_suspended;
     t.ubar = nullptr;
     t.slip_v = nullptr;
@@ -59,6 +61,12 @@ void friction_clear(fh_ctx* c) {
     c->friction_set = false;
     c->contact.friction = 0;
     for (double& m : c->contact.mu) m = 0.0;
+}
+
+// (the multipliers belong to the obstacle list and the mesh; the buffer stays for the next ones)
+void multipliers_clear(fh_ctx* c) {
+    if (c->contact_has_mult) ++c->contact_gen;
+    c->contact_has_mult = false;
 }
 
 void paths_clear(fh_ctx* c) {
@@ -158,6 +166,7 @@ void contact_set_time(fh_ctx* c, double t, double t_lag) {
 void contact_clear(fh_ctx* c) {
     friction_clear(c);
     paths_clear(c);
+    multipliers_clear(c);
     if (c->contact.count || c->contact_has_w) ++c->contact_gen;
     c->contact = contact_off();
     c->contact_has_w = false;
@@ -274,6 +283,7 @@ int fh_set_obstacles(fh_ctx* c, const fh_obstacle* obstacles, uint64_t count, co
     }
     friction_clear(c);   // (the coefficients belong to the obstacle list)
     paths_clear(c);      // (and so do the paths)
+    multipliers_clear(c);   // (and the multipliers)
     if (!c->has_mesh || c->ragged) return c->fail(FH_INVALID_STATE, std::string(who) + ": no finite element mesh set");
     if (c->ei.d != 2 && c->ei.d != 3) return c->fail(FH_UNSUPPORTED, std::string(who) + ": the geometric dim must be 2 or 3");
     if (c->ei.d == 2)   // the third components take no part in a plane problem: a normal is normalised over the first two
@@ -542,6 +552,145 @@ int fh_add_contact_tangent_csr_dev(fh_ctx* c, double* values_dev) {
     });
     HIP_TRY(c, hipGetLastError());
     c->last_kernel = "k_contact_csr";
+    return FH_OK;
+}
+
+// ---- augmented Lagrangian: the multipliers
+
+static size_t mult_entries(const fh_ctx* c) { return (size_t)c->contact.count * (size_t)c->N; }
+
+static int multipliers_ready(fh_ctx* c, const char* who) {
+    if (!c->contact.count) return c->fail(FH_INVALID_STATE, std::string(who) + ": no obstacles set (fh_set_obstacles)");
+    return standalone_ready(c, who);
+}
+
+// the buffer of the multipliers, count x N doubles; `zero`: filled with zeros (queued on the stream)
+static int multipliers_alloc(fh_ctx* c, bool zero) {
+    const size_t n = mult_entries(c);
+    if (!c->contact_mult.p || c->contact_mult.n < n) HIP_TRY(c, c->contact_mult.alloc(n));
+    if (zero && n) HIP_TRY(c, hipMemsetAsync(c->contact_mult.p, 0, sizeof(double) * n, c->stream));
+    return FH_OK;
+}
+
+static int set_multipliers(fh_ctx* c, const char* who, const double* s, hipMemcpyKind kind) {
+    if (!s) {   // clear: back to the instantiations without multipliers
+        multipliers_clear(c);
+        return FH_OK;
+    }
+    int rc = multipliers_ready(c, who);
+    if (rc) return rc;
+    const size_t n = mult_entries(c);
+    if (kind == hipMemcpyHostToDevice)
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(s[i]) || s[i] < 0.0) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a multiplier is negative or not finite");
+    rc = multipliers_alloc(c, false);
+    if (rc) return rc;
+    if (n) HIP_TRY(c, hipMemcpyAsync(c->contact_mult.p, s, sizeof(double) * n, kind, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->contact_has_mult = true;
+    ++c->contact_gen;
+    return FH_OK;
+}
+int fh_set_contact_multipliers(fh_ctx* c, const double* s) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    return set_multipliers(c, "fh_set_contact_multipliers", s, hipMemcpyHostToDevice);
+}
+int fh_set_contact_multipliers_dev(fh_ctx* c, const double* s_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    return set_multipliers(c, "fh_set_contact_multipliers_dev", s_dev, hipMemcpyDeviceToDevice);
+}
+
+static int get_multipliers(fh_ctx* c, const char* who, double* s, hipMemcpyKind kind) {
+    if (!s) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    const int rc = multipliers_ready(c, who);
+    if (rc) return rc;
+    const size_t n = mult_entries(c);
+    if (!n) return FH_OK;
+    if (c->contact_has_mult) HIP_TRY(c, hipMemcpyAsync(s, c->contact_mult.p, sizeof(double) * n, kind, c->stream));
+    else if (kind == hipMemcpyDeviceToDevice) HIP_TRY(c, hipMemsetAsync(s, 0, sizeof(double) * n, c->stream));
+    else std::fill(s, s + n, 0.0);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FH_OK;
+}
+int fh_contact_multipliers(fh_ctx* c, double* s) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    return get_multipliers(c, "fh_contact_multipliers", s, hipMemcpyDeviceToHost);
+}
+int fh_contact_multipliers_dev(fh_ctx* c, double* s_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    return get_multipliers(c, "fh_contact_multipliers_dev", s_dev, hipMemcpyDeviceToDevice);
+}
+
+int fh_contact_multiplier_forces_dev(fh_ctx* c, double* lam_dev) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_contact_multiplier_forces_dev";
+    if (!lam_dev) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null argument");
+    const int rc = multipliers_ready(c, who);
+    if (rc) return rc;
+    if (c->N == 0) return FH_OK;
+    const ContactTable t = table_at_u(c);
+    by_dim(c, [&](auto d) {
+        hipLaunchKernelGGL((k_contact_multiplier_forces<d()>), dim3(blocks_of((long long)c->N)), dim3(256), 0, c->stream, t, (int)c->N, lam_dev);
+    });
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_contact_multiplier_forces";
+    return FH_OK;
+}
+
+int fh_contact_multiplier_update(fh_ctx* c, const uint64_t* skip_nodes, uint64_t skip_count, fh_multiplier_update* stats) {
+    if (!c) return FH_BAD_ARGUMENT;
+    DevGuard dev_guard_(c->device);
+    const char* who = "fh_contact_multiplier_update";
+    if (skip_count && !skip_nodes) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": null skip_nodes");
+    int rc = multipliers_ready(c, who);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < skip_count; ++i)
+        if (skip_nodes[i] >= c->N) return c->fail(FH_BAD_ARGUMENT, std::string(who) + ": a skip node is out of range");
+    if (stats) *stats = fh_multiplier_update{};
+    rc = multipliers_alloc(c, !c->contact_has_mult);   // the first update starts from zeros
+    if (rc) return rc;
+    c->contact_has_mult = true;
+    ++c->contact_gen;
+    if (c->N == 0) return FH_OK;
+    const unsigned char* skip = nullptr;
+    if (skip_count) {
+        std::vector<unsigned char> mask((size_t)c->N, 0);
+        for (uint64_t i = 0; i < skip_count; ++i) mask[(size_t)skip_nodes[i]] = 1;
+        if (c->contact_skip.n < mask.size()) HIP_TRY(c, c->contact_skip.alloc(mask.size()));
+        HIP_TRY(c, hipMemcpyAsync(c->contact_skip.p, mask.data(), mask.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the mask leaves scope)
+        skip = c->contact_skip.p;
+    }
+    ContactTable t = table_at_u(c);
+    t.mult = nullptr;   // (the update reads the geometric phi and owns the multipliers it writes)
+    const int count = blocks_of((long long)c->N);
+    DevBuf<double>& part = c->contact_stat;
+    if (part.n < (size_t)count * 4) HIP_TRY(c, part.alloc((size_t)count * 4));
+    by_dim(c, [&](auto d) {
+        hipLaunchKernelGGL((k_contact_multiplier_update<d()>), dim3(count), dim3(256), 0, c->stream, t, (int)c->N, c->contact_mult.p, (size_t)c->N, skip,
+                           part.p);
+    });
+    HIP_TRY(c, hipGetLastError());
+    c->last_kernel = "k_contact_multiplier_update";
+    // the rows in index order, as sum_partials takes them (waits for the device)
+    std::vector<double> h((size_t)count * 4);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), part.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        double active = 0.0;
+        for (int b = 0; b < count; ++b) {
+            stats->max_change = std::max(stats->max_change, h[(size_t)b * 4]);
+            stats->max_penetration = std::max(stats->max_penetration, h[(size_t)b * 4 + 1]);
+            active += h[(size_t)b * 4 + 2];
+            stats->max_force = std::max(stats->max_force, h[(size_t)b * 4 + 3]);
+        }
+        stats->active = (uint64_t)active;
+    }
     return FH_OK;
 }
 

@@ -527,6 +527,13 @@ struct fh_ctx {
     double friction_slip_dt = 0.0, friction_slip_eps = 0.0;
     int friction_suspended = 0;
     bool friction_set = false;         // fh_set_friction has been given coefficients (all zero included: contact.friction stays clear then)
+    // augmented Lagrangian (fh_set_contact_multipliers, fh_contact_multiplier_update): the multiplier lengths s_oi, [count][N] doubles owned by
+    // the context, standing while contact_has_mult; contact_skip: the byte mask of the update's skip_nodes, contact_stat its partial rows.
+    // Setting, clearing or updating them moves contact_gen.
+    DevBuf<double> contact_mult;
+    DevBuf<unsigned char> contact_skip;
+    DevBuf<double> contact_stat;
+    bool contact_has_mult = false;
     int mf_scope = 1;   // MF_TANGENT
     fh_mg* mg = nullptr;               // the multigrid hierarchy of FH_PRECOND_MULTIGRID (fh_set_multigrid; not owned)
     fh_amg* amg = nullptr;             // the algebraic hierarchy of FH_PRECOND_AMG (fh_set_amg; not owned)

@@ -571,8 +571,9 @@ __global__ void __launch_bounds__(TS) k_damped_pass_tiled(const KArgs a, const V
 // block, while ct.friction is set, here and in the node passes below the friction force q beside g), joins the scaled-back
 // sum before the Dirichlet rows and the dot product are formed; S == 1 has no such term.  G (here and in the three node passes below):
 // whether the table may hold a sampled grid (ct.grids); the launches pick G = false while none stands, an instantiation without the grid
-// branch and its registers (contact_eval).
-template <int S, bool G>
+// branch and its registers (contact_eval).  A, likewise: whether multipliers stand (ct.mult); with A = false the shift by s_oi and its
+// load are not compiled (contact_visit), and the launches pick that instantiation while none stand.
+template <int S, bool G, bool A>
 __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* partial,
                                                                 const double* x, const unsigned char* dmask, const double* scale,
                                                                 const unsigned long long* xbits, double* y, double* dot_partial,
@@ -592,8 +593,8 @@ __global__ void __launch_bounds__(256) k_operator_from_partials(int num_nodes, c
             acc[c] = ldexp(acc[c], ex);
         }
         if constexpr (S > 1) {
-            if (ct.count) contact_apply<S, G>(ct, node, xo, contact_scale, acc);   // (the unscaled operand)
-            if (ct.friction) friction_apply<S, G>(ct, node, xo, contact_scale, acc);
+            if (ct.count) contact_apply<S, G, A>(ct, node, xo, contact_scale, acc);   // (the unscaled operand)
+            if (ct.friction) friction_apply<S, G, A>(ct, node, xo, contact_scale, acc);
         }
 #pragma unroll
         for (int c = 0; c < S; ++c) {
@@ -716,7 +717,7 @@ __global__ void __launch_bounds__(256) k_shift_from_partials(int num_nodes, cons
 // rows of the Dirichlet nodes (dmask, may be null) are zero.  norm_partial: per workgroup |F|^2 over its nodes, in a fixed tree
 // (k_operator_from_partials' layout), summed in index order by the caller.  ct (count 0: off): the contact force g of the node
 // (contact_kernels.hpp) joins the residual sum first, so F and |F|^2 are those of r + g.
-template <int S, bool G>
+template <int S, bool G, bool A>
 __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
                                                               const double* mpart, const double* f, const unsigned char* dmask, double alpha,
                                                               double beta, double* F, double* norm_partial, const ContactTable ct) {
@@ -728,8 +729,8 @@ __global__ void __launch_bounds__(256) k_newton_from_partials(int num_nodes, con
         double(&racc)[S] = acc[0], (&macc)[S] = acc[1];
         const unsigned fixed = node_dmask(dmask, node);
         if constexpr (S > 1) {
-            if (ct.count) contact_force<S, G>(ct, node, racc);
-            if (ct.friction) friction_force<S, G>(ct, node, racc);
+            if (ct.count) contact_force<S, G, A>(ct, node, racc);
+            if (ct.friction) friction_force<S, G, A>(ct, node, racc);
         }
 #pragma unroll
         for (int c = 0; c < S; ++c) {
@@ -753,7 +754,7 @@ static_assert(4 * sizeof(void*) + sizeof(DynStep) <= NODE_PASS_ARG_BYTES && 4 * 
 // (lf f - r) / m, the second kick that completes v_{n+1}, then either the stores and the kinetic-energy partial of a record (DYN_STORE) or
 // the next step's first kick and drift into the context's u (DYN_ADVANCE).  The element pass that follows reads the u this leaves.
 // ct (count 0: off): the contact force g at the u the element pass read joins r before dyn_dof, which stays as it is.
-template <int S, bool G>
+template <int S, bool G, bool A>
 __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
                                                                 const DynStep p, const ContactTable ct) {
     const int node = blockIdx.x * 256 + threadIdx.x;
@@ -762,8 +763,8 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
         double racc[S];
         node_partials_sum<S>(np_off, np_idx, rpart, node, racc);
         if constexpr (S > 1) {
-            if (ct.count) contact_force<S, G>(ct, node, racc);
-            if (ct.friction) friction_force<S, G>(ct, node, racc);   // (the slip of the velocity the node is about to kick: ct.slip_v is p.v)
+            if (ct.count) contact_force<S, G, A>(ct, node, racc);
+            if (ct.friction) friction_force<S, G, A>(ct, node, racc);   // (the slip of the velocity the node is about to kick: ct.slip_v is p.v)
         }
         const unsigned fixed = node_dmask(p.dmask, node);
         const double lf = dyn_load_factor(p);
@@ -777,7 +778,7 @@ __global__ void __launch_bounds__(256) k_dynamics_from_partials(int num_nodes, c
 // fo_dof (dynamics_step.hpp): Y_j from Y_{j-1} (the context's u) and Y_{j-2} (prev), both updated in this visit; with FO_STORE the partial
 // of sum m y^2 of the u just written, so a recorded step needs no launch of its own.  The element pass that follows reads the u this leaves.
 // ct (count 0: off): the contact force g at Y_{j-1} joins r before fo_dof, which stays as it is.
-template <int S, bool G>
+template <int S, bool G, bool A>
 __global__ void __launch_bounds__(256) k_first_order_from_partials(int num_nodes, const unsigned* np_off, const unsigned* np_idx, const double* rpart,
                                                                    const FoStage p, const ContactTable ct) {
     const int node = blockIdx.x * 256 + threadIdx.x;
@@ -786,7 +787,7 @@ __global__ void __launch_bounds__(256) k_first_order_from_partials(int num_nodes
         double racc[S];
         node_partials_sum<S>(np_off, np_idx, rpart, node, racc);
         if constexpr (S > 1) {
-            if (ct.count) contact_force<S, G>(ct, node, racc);
+            if (ct.count) contact_force<S, G, A>(ct, node, racc);
         }
         const unsigned fixed = node_dmask(p.dmask, node);
         const double lf = dyn_load_factor(p);
@@ -1033,12 +1034,19 @@ int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const 
     });
 }
 
+// the two compile-time flags of the node passes that take the table: G (a grid stands; without: the instantiation without the grid branch)
+// and A (multipliers stand; without: the instantiation without the shift by s_oi)
+template <class F>
+static auto dispatch_contact_flags(const ContactTable& ct, F&& f) {
+    return dispatch_bool(ct.grids != 0, [&](auto g) { return dispatch_bool(ct.mult != nullptr, [&](auto m) { return f(g, m); }); });
+}
+
 hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* partial, const double* x,
                                            const unsigned char* dmask, const double* scale, const unsigned long long* xbits, double* y,
                                            double* dot_partial, const ContactTable& ct, double contact_scale) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
-        return dispatch_bool(ct.grids != 0, [&](auto g) {   // (no grid: the instantiation without the grid branch)
-            return node_launch(k_operator_from_partials<s(), g()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask,
+        return dispatch_contact_flags(ct, [&](auto g, auto m) {
+            return node_launch(k_operator_from_partials<s(), g(), m()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, partial, x, dmask,
                            scale, xbits, y, dot_partial, ct, contact_scale);
         });
     });
@@ -1077,8 +1085,8 @@ hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_node
                                          const double* f, const unsigned char* dmask, double alpha, double beta, double* F, double* norm_partial,
                                          const ContactTable& ct) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
-        return dispatch_bool(ct.grids != 0, [&](auto g) {   // (no grid: the instantiation without the grid branch)
-            return node_launch(k_newton_from_partials<s(), g()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f,
+        return dispatch_contact_flags(ct, [&](auto g, auto m) {
+            return node_launch(k_newton_from_partials<s(), g(), m()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, mpart, f,
                            dmask, alpha, beta, F, norm_partial, ct);
         });
     });
@@ -1087,8 +1095,8 @@ hipError_t vector_tiles_newton_node_pass(hipStream_t stream, int S, int num_node
 hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const DynStep& p,
                                            const ContactTable& ct) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
-        return dispatch_bool(ct.grids != 0, [&](auto g) {   // (no grid: the instantiation without the grid branch)
-            return node_launch(k_dynamics_from_partials<s(), g()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p, ct);
+        return dispatch_contact_flags(ct, [&](auto g, auto m) {
+            return node_launch(k_dynamics_from_partials<s(), g(), m()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p, ct);
         });
     });
 }
@@ -1096,8 +1104,8 @@ hipError_t vector_tiles_dynamics_node_pass(hipStream_t stream, int S, int num_no
 hipError_t vector_tiles_first_order_node_pass(hipStream_t stream, int S, int num_nodes, const VecTiles& t, const double* rpart, const FoStage& p,
                                               const ContactTable& ct) {
     return dispatch_or_last(solution_dims, S, [&](auto s) {
-        return dispatch_bool(ct.grids != 0, [&](auto g) {   // (no grid: the instantiation without the grid branch)
-            return node_launch(k_first_order_from_partials<s(), g()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p, ct);
+        return dispatch_contact_flags(ct, [&](auto g, auto m) {
+            return node_launch(k_first_order_from_partials<s(), g(), m()>, vector_tiles_operator_partials(num_nodes), stream, num_nodes, t.np_off, t.np_idx, rpart, p, ct);
         });
     });
 }

@@ -1119,6 +1119,47 @@ int fh_set_obstacle_time(fh_ctx*, double t, double t_lag);
 int fh_obstacle_count(fh_ctx*, uint64_t* count);
 int fh_obstacle_offsets(fh_ctx*, double* current, double* lag);
 int fh_contact_resultants(fh_ctx*, double* normal, double* friction);
+/* ---- augmented-Lagrangian contact: a multiplier per obstacle and node, updated between solves (Uzawa) --------------------------------------
+ * The penalty term alone leaves a node pressed with force F a depth F / (k w) inside the obstacle.  A multiplier removes that error at a
+ * fixed, moderate k.  It is kept as a LENGTH s_oi >= 0 per obstacle o and node i, standing for the force lam_oi = k_o w_i s_oi (no division
+ * on the device; w_i = 0 is harmless); layout [o][i], count x N doubles, owned by the context.  With
+ *   phi_eff = phi_o(x_i) - s_oi,  p = min(0, phi_eff)
+ * every route that carries the term forms it from phi_eff where it formed it from phi:
+ *   E_c = sum (k w / 2) (p^2 - s^2)     (active: k w / 2 phi^2 - lam phi; otherwise -lam^2 / (2 k w))
+ *   g_i = sum k w p n,   B_i = sum k w ([phi_eff < 0] n n^T + c (I - n n^T)),  c = -p / |y| for the cavity; a grid: m m^T, c = 0
+ *   friction: a node is in contact at xbar iff phi_eff(xbar) < 0, lam = k w max(0, -phi_eff(xbar)) (a grid: times gn), with the s_oi that
+ *   stands NOW;  fh_contact_resultants: R_o and Q_o from the same p and lam.
+ * g is the exact gradient of E_c with s frozen; B keeps its exact / Gauss-Newton status per kind and stays symmetric positive
+ * semi-definite.  fh_contact_gap_dev keeps reporting the geometric min_o phi_o, not phi_eff.  With every s = 0 each expression is the one
+ * without multipliers, bit for bit (phi - 0.0, e - 0.0); with none set the kernels are the ones without the shift.
+ * fh_set_contact_multipliers(_dev): count x N doubles are copied into the context; NULL clears them.  FH_BAD_ARGUMENT: a negative or
+ *   non-finite entry (host form only; the device form is not read here); FH_INVALID_STATE: no obstacles, no mesh.
+ * fh_contact_multipliers(_dev): reads them back (count x N doubles), zeros while none are set.  FH_INVALID_STATE: no obstacles.
+ * fh_contact_multiplier_forces_dev: lam_oi = k_o w_i s_oi into lam_dev (count x N doubles), for a grid times gn = |grad phi| at the node's
+ *   current position (0 outside its box); zeros while none are set.
+ * fh_contact_multiplier_update: s_oi <- max(0, s_oi - phi_o(x_i)) at the context's u and the contact clock's current time; phi = +infinity
+ *   (outside a grid's box) gives 0; a node at the centre of a ball or cavity is updated like any other.  The first call starts from zeros.
+ *   skip_nodes (skip_count host indices, may be NULL with 0: the fully held nodes) keep s = 0 and stay out of the statistics;
+ *   FH_BAD_ARGUMENT: an index >= N.  stats (may be NULL), over the counted (node, obstacle) pairs: max_change = max |s_new - s_old| (|phi|
+ *   where the pair is active afterwards, the released multiplier otherwise: the convergence measure), max_penetration = max max(0, -phi),
+ *   active = the number with s_new > 0, max_force = max lam after the update.  One launch of k_contact_multiplier_update (one thread per
+ *   node, a fixed reduction tree per workgroup, one partial row each) and the combination of the rows in index order: no atomics, two
+ *   calls on equal input return equal bits.  Waits for the device.
+ * Setting, clearing or updating invalidates every cache keyed on the obstacles.  fh_set_obstacles and fh_set_mesh* clear the multipliers;
+ *   fh_set_obstacle_time, fh_set_obstacle_paths and fh_set_friction* leave them (a quasi-static indentation warm-starts from the last load
+ *   step).  fh_newton_solve, the integrators, fh_dynamics_stable_dt and fh_eigs_lowest see them as a frozen field: no route updates them. */
+typedef struct {
+    double max_change;
+    double max_penetration;
+    double max_force;
+    uint64_t active;
+} fh_multiplier_update;
+int fh_set_contact_multipliers(fh_ctx*, const double* s);
+int fh_set_contact_multipliers_dev(fh_ctx*, const double* s_dev);
+int fh_contact_multipliers(fh_ctx*, double* s);
+int fh_contact_multipliers_dev(fh_ctx*, double* s_dev);
+int fh_contact_multiplier_forces_dev(fh_ctx*, double* lam_dev);
+int fh_contact_multiplier_update(fh_ctx*, const uint64_t* skip_nodes, uint64_t skip_count, fh_multiplier_update* stats);
 /* ---- prescribed motion of the Dirichlet nodes during time integration (second-order handles) -------------------------------------------
  * fh_dynamics_set_boundary_motion(_dev): direction (S N doubles, read on the Dirichlet dofs only; NULL clears the motion) and a factor
  *   table of count >= 1 finite entries (host memory in both forms; else FH_BAD_ARGUMENT).  With g_n = factor[min(n, count - 1)], a Dirichlet

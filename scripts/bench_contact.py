@@ -10,6 +10,10 @@
     floor_mu05  this build, that floor with mu = 0.5, slip velocity 0.05: the friction term in the step's node pass and in the map
     floor_mu05_moving  (--moving) `floor_mu05` with the floor sliding sideways along a path at 0.5 under nodes that start at rest: the integrator moves the
                 contact clock before every launch and the node pass takes the slip relative to the floor; held against `floor_mu05`
+    floor_aug   this build, that floor with augmented-Lagrangian multipliers standing (fh_set_contact_multipliers: the penetration of the
+                bottom layer, what one update of the shifted state gives): the node pass and the map take the instantiation with the shift
+                and load one multiplier per node; held against `floor`
+    floor_aug_mu05  `floor_mu05` with the same multipliers standing; held against `floor_mu05`
     parent_floor  the parent's library on the `floor` scene (friction never set there: what `floor` and `floor_mu0` are held against)
     parent_sixteen  the parent's library on the `sixteen` scene
     floor_grid  this build, that floor as a sampled signed-distance grid (fh_sdf_grid_create): 17^3 samples of its linear field over
@@ -20,7 +24,8 @@
 --digest (with --parent-lib): no timing; both libraries compute the stand-alone pieces of the term (energy, gap, force, CSR blocks, the
 tangent's map and diagonal, resultants, and with friction, a lag state and paths the potential, force, blocks and resultants) for a
 half-space, a ball and a cavity on six small meshes, and the SHA-256 digests of the bytes are compared: a build that adds an obstacle kind
-must not move a bit of the kinds that were there.
+must not move a bit of the kinds that were there.  On a build with multipliers the same pieces are formed again with all-zero multipliers
+standing (they must be the bytes of none: counted as moved otherwise) and with random ones (digests reported for this build alone).
 
 The variants alternate: every measurement is a fresh child process (one library per process), `--repeats` rounds after one discarded
 warm-up round, so drift of the machine hits every variant alike.  Per variant the median and the spread (min .. max) over the rounds, one
@@ -59,17 +64,17 @@ def child(variant, cells, steps, applies):
     asm = (fa.ElementEllipticAssemblerBuilder(eng).with_finite_element_space(mesh)
            .with_operator(fa.MaterialEllipticOperator(fa.StableNeoHookeanMaterial())).with_quadrature_table(qt).with_u(np.zeros(n)).build())
     obstacles = None
-    if variant in ("floor", "sixteen", "floor_mu0", "floor_mu05", "floor_mu05_moving"):
+    if variant in ("floor", "sixteen", "floor_mu0", "floor_mu05", "floor_mu05_moving", "floor_aug", "floor_aug_mu05"):
         k = 1e6 / cells
         if variant == "floor_mu05_moving":
             items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k, friction=0.5, path=fa.ObstaclePath.constant_velocity((0.5, 0.0, 0.0), 1.0))]
-        elif variant == "floor_mu05":
+        elif variant in ("floor_mu05", "floor_aug_mu05"):
             items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k, friction=0.5)]
         else:
             items = [fa.HalfSpace((0.0, 0.0, -0.005), (0.0, 0.0, 1.0), k)]
         if variant == "sixteen":
             items += [fa.Ball((10.0 + j, 10.0, 10.0), 0.5, k) for j in range(15)]
-        obstacles = fa.Obstacles(items, slip_length=1e-3, slip_velocity=0.05) if variant.startswith("floor_mu05") else fa.Obstacles(items)
+        obstacles = fa.Obstacles(items, slip_length=1e-3, slip_velocity=0.05) if variant.endswith(("mu05", "mu05_moving")) else fa.Obstacles(items)
     if variant in ("floor_grid", "ball", "ball_grid"):
         k = 1e6 / cells
         centre = (0.5, 0.5, 1.0 + 0.4 - 0.03)
@@ -83,7 +88,7 @@ def child(variant, cells, steps, applies):
     u0 = torch.zeros(n, dtype=torch.float64, device="cuda")
     u0[2::3] = -0.01
     v0 = torch.zeros_like(u0)
-    if variant.startswith("floor_mu"):
+    if variant.startswith("floor_mu") or variant == "floor_aug_mu05":
         v0[0::3] = 1.0     # sliding: the friction force is at its cap on every touching node
 
     def arm():   # mu = 0 through the C ABI (the Python layer sends fh_set_friction only for a positive coefficient)
@@ -91,6 +96,10 @@ def child(variant, cells, steps, applies):
             import ctypes as C
 
             eng._check(eng._lib.fh_set_friction(eng._h, (C.c_double * 1)(0.0), 1, 1e-3))
+        if variant.startswith("floor_aug"):   # the multipliers: the penetration of the bottom layer at the shifted state
+            s = np.zeros((1, mesh.num_nodes()))
+            s[0, np.isclose(np.asarray(mesh.vertices)[:, 2], 0.0)] = 0.005
+            fa.Contact(eng).set_multipliers(s)
     ti = fa.CentralDifference(asm, RHO, 1.0)
     if obstacles is not None:
         ti.with_obstacles(obstacles)
@@ -114,7 +123,7 @@ def child(variant, cells, steps, applies):
     t = fa.MatrixFreeTangent(asm)
     if obstacles is not None:
         t.with_obstacles(obstacles)
-    if variant.startswith("floor_mu05"):
+    if variant.endswith(("mu05", "mu05_moving")):
         t.with_friction_reference(u0)     # the lag state: the shifted u
     if variant == "floor_mu05_moving":
         eng.set_obstacle_time(0.02, 0.01)
@@ -174,22 +183,30 @@ def digest_child():
         asm = (fa.ElementEllipticAssemblerBuilder(eng).with_finite_element_space(m).with_operator(fa.MaterialEllipticOperator(fa.NeoHookeanMaterial()))
                .with_quadrature_table(qt).with_u(u).build())
         pieces = {}
-        for mu in (0.0, 1.0):
+        has_multipliers = hasattr(eng._lib, "fh_set_contact_multipliers")
+        s_random = rng.uniform(0.0, 0.05, (3, N)) * rng.choice([0.0, 1.0, 20.0], (3, N))
+        modes = [("", None)] + ([(" zero", np.zeros((3, N))), (" aug", s_random)] if has_multipliers else [])
+        for mu, (tag, s_mult) in ((mu, mode) for mu in (0.0, 1.0) for mode in modes):
             eng.set_obstacles(obstacles(mu))
             if mu:
                 eng._check(eng._lib.fh_set_friction_reference(eng._h, _ffi.fp(np.ascontiguousarray(ubar))))
             eng.set_obstacle_time(1.25, 0.75)
             con = fa.Contact(eng)
+            if s_mult is not None:
+                con.set_multipliers(s_mult)
+            mu = f"{mu}{tag}"
             k = fa.CsrAssembler(fa.SCATTER_GATHER).assemble(asm)
             vals = np.zeros_like(k.values)
             con.add_tangent_to(vals)
             R, Qf = con.resultants()
             pieces.update({f"energy{mu}": np.array([con.energy(), con.friction_potential()]), f"gap{mu}": con.gap(), f"force{mu}": con.force(),
                            f"friction force{mu}": con.friction_force(), f"csr{mu}": vals, f"resultants{mu}": np.concatenate([R.ravel(), Qf.ravel()])})
-            t = fa.MatrixFreeTangent(asm).with_obstacles(obstacles(mu))
-            if mu:
+            t = fa.MatrixFreeTangent(asm).with_obstacles(obstacles(float(mu.split()[0])))
+            if float(mu.split()[0]):
                 t.with_friction_reference(ubar)
             eng.set_obstacle_time(1.25, 0.75)
+            if s_mult is not None:
+                con.set_multipliers(s_mult)
             pieces[f"apply{mu}"] = t.apply(np.zeros(N * d), x).copy()
             pieces[f"diagonal{mu}"] = t.diagonal()
             t.with_obstacles(None)
@@ -209,10 +226,21 @@ def digest(parent_lib):
             env["FENRIS_HIP_LIB"] = os.path.abspath(parent_lib)
         got[which] = json.loads(subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "digest"], env=env, check=True, capture_output=True,
                                                text=True, timeout=600).stdout.strip().splitlines()[-1])
-    moved = [k for k in got["this"] if got["this"][k] != got["parent"].get(k)]
-    whole = hashlib_of(got["this"])
-    print(json.dumps({"digest": True, "pieces": len(got["this"]), "moved": moved, "parent": hashlib_of(got["parent"]), "this": whole}), flush=True)
-    return 1 if moved or len(got["this"]) != len(got["parent"]) else 0
+    this, parent = got["this"], got["parent"]
+    shared = {k: v for k, v in this.items() if k in parent}
+    moved = [k for k in shared if shared[k] != parent[k]]
+
+    def base_of(key):   # "HEX8 force0.0 zero" -> "HEX8 force0.0"
+        return key[:-len(" zero")]
+
+    moved += [k for k in this if k.endswith(" zero") and this[k] != this.get(base_of(k))]       # all-zero multipliers: the bytes of none
+    aug = {k: v for k, v in this.items() if k.endswith(" aug")}
+    # (random multipliers must show in the force, the map, the diagonal and the blocks)
+    same = [k for k in aug if k.split()[1].startswith(("force", "apply", "csr", "diagonal")) and aug[k] == this.get(k[:-len(" aug")])]
+    print(json.dumps({"digest": True, "pieces": len(shared), "moved": moved, "parent": hashlib_of(parent), "this": hashlib_of(shared),
+                      "zero_multiplier_pieces": sum(k.endswith(" zero") for k in this), "multiplier_pieces": len(aug),
+                      "multipliers": hashlib_of(aug), "multipliers_without_effect": same}), flush=True)
+    return 1 if moved or same or len(shared) != len(parent) else 0
 
 
 def hashlib_of(table):
@@ -243,7 +271,7 @@ def main():
         if not a.parent_lib:
             ap.error("--digest needs --parent-lib")
         sys.exit(digest(a.parent_lib))
-    variants = ((["parent", "parent_floor", "parent_sixteen"] if a.parent_lib else []) + ["none", "floor", "sixteen", "floor_mu0", "floor_mu05"] + (["floor_mu05_moving"] if a.moving else [])
+    variants = ((["parent", "parent_floor", "parent_sixteen"] if a.parent_lib else []) + ["none", "floor", "floor_aug", "sixteen", "floor_mu0", "floor_mu05", "floor_aug_mu05"] + (["floor_mu05_moving"] if a.moving else [])
                 + ["floor_grid", "ball", "ball_grid"])
     if a.variants:
         variants = [v for v in a.variants.split(",") if v in variants]
