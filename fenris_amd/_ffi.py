@@ -180,6 +180,13 @@ _SIGS = {
     "fh_cg_solve_tangent": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_cg_solve_tangent_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64, u64p]),
     "fh_set_mass_density": (C.c_int, [C.c_void_p, f64p, C.c_uint64]),
+    "fh_set_element_expansion": (C.c_int, [C.c_void_p, f64p, C.c_uint64]),
+    "fh_set_element_expansion_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "fh_set_thermal_expansion": (C.c_int, [C.c_void_p, f64p, f64p, C.c_uint64, C.c_double]),
+    "fh_set_thermal_expansion_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double]),
+    "fh_element_expansion": (C.c_int, [C.c_void_p, f64p]),
+    "fh_thermal_load": (C.c_int, [C.c_void_p, f64p]),
+    "fh_thermal_load_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fh_apply_shifted_tangent_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "fh_shifted_tangent_diagonal_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "fh_cg_solve_shifted_tangent": (C.c_int, [C.c_void_p, C.c_double, C.c_double, f64p, f64p, C.c_int, C.c_double, C.c_uint64, u64p]),

@@ -578,6 +578,39 @@ class Engine:
         rho = np.ascontiguousarray(np.atleast_1d(np.asarray(rho, dtype=np.float64)).ravel())
         self._check(self._lib.fh_set_mass_density(self._h, _ffi.fp(rho), len(rho)))
 
+    # the per-element expansion (thermal strain, swelling, growth): one stress-free stretch theta_e > 0 per element, which strains the elastic
+    # operators on every element-to-node route of this engine until it is changed, cleared or the mesh is set again
+    def set_element_expansion(self, theta):
+        """fh_set_element_expansion: one stretch for the mesh (a scalar) or one per element; None clears the field"""
+        if theta is None:
+            self._check(self._lib.fh_set_element_expansion(self._h, None, 0))
+            return
+        theta = np.ascontiguousarray(np.atleast_1d(np.asarray(theta, dtype=np.float64)).ravel())
+        if len(theta) == 0:
+            raise ValueError("set_element_expansion needs a stretch (None clears the field)")
+        self._check(self._lib.fh_set_element_expansion(self._h, _ffi.fp(theta), len(theta)))
+
+    def set_thermal_expansion(self, T, alpha, T_ref=0.0):
+        """fh_set_thermal_expansion: theta_e = 1 + alpha_e (mean nodal temperature of the element - T_ref); T: one value per node, alpha: a
+        scalar or one value per element"""
+        T = np.ascontiguousarray(np.asarray(T, dtype=np.float64).ravel())
+        if len(T) != self.num_nodes():
+            raise ValueError("set_thermal_expansion needs one temperature per node")
+        alpha = np.ascontiguousarray(np.atleast_1d(np.asarray(alpha, dtype=np.float64)).ravel())
+        self._check(self._lib.fh_set_thermal_expansion(self._h, _ffi.fp(T), _ffi.fp(alpha), len(alpha), float(T_ref)))
+
+    def element_expansion(self):
+        """fh_element_expansion: the stretch of every element (FH_INVALID_STATE when none is set)"""
+        out = np.zeros(self.num_elements())
+        self._check(self._lib.fh_element_expansion(self._h, _ffi.fp(out)))
+        return out
+
+    def thermal_load(self):
+        """fh_thermal_load: f_th = -r(0) of linear elasticity under the field in force (FH_UNSUPPORTED for any other operator)"""
+        out = np.zeros(self.solution_dim() * self.num_nodes())
+        self._check(self._lib.fh_thermal_load(self._h, _ffi.fp(out)))
+        return out
+
     def apply_shifted_tangent_dev(self, alpha, beta, x_t, y_t):
         self._check(self._lib.fh_apply_shifted_tangent_dev(self._h, float(alpha), float(beta), C.c_void_p(x_t.data_ptr()),
                                                            C.c_void_p(y_t.data_ptr())))
@@ -1307,6 +1340,12 @@ class MatrixFreeOperator:
             self._mg._bind(self._nodes, self._mg_density())
         return self._cg_solve(b, x, preconditioner, rel_tol, max_iter)
 
+    def with_element_expansion(self, theta):
+        """the per-element expansion of the engine (Engine.set_element_expansion: a scalar, one stretch per element, None to clear it).  The
+        field belongs to the engine, not to this object: every object on the same engine sees it until it is changed; returns self"""
+        self.engine.set_element_expansion(theta)
+        return self
+
     def _apply_dev(self, x_t, y_t):
         self.engine.apply_operator_dev(x_t, y_t)
 
@@ -1393,6 +1432,10 @@ class MatrixFreeMass(MatrixFreeShiftedTangent):
 
     def __init__(self, element_assembler, density):
         super().__init__(element_assembler, density, 1.0, 0.0)
+
+    def with_element_expansion(self, theta):
+        """the mass is that of the reference volume and does not see the expansion: set the field on an object that does"""
+        raise ValueError("MatrixFreeMass ignores the element expansion; set it on the engine or on a tangent, solver or integrator")
 
     def lumped(self, device=False):
         """M 1 without Dirichlet rows: the row-sum lumped mass for explicit stepping, in one application.  As for any row-sum lumping, some
@@ -1532,6 +1575,12 @@ class MatrixFreeNewton:
             self.engine.set_mass_density(self._rho)
             self.engine._mass_bound = self
         _contact.bind_obstacles(self, force)
+
+    def with_element_expansion(self, theta):
+        """the per-element expansion of the engine (Engine.set_element_expansion: a scalar, one stretch per element, None to clear it).  The
+        field belongs to the engine, not to this object: every object on the same engine sees it until it is changed; returns self"""
+        self.engine.set_element_expansion(theta)
+        return self
 
     def with_obstacles(self, obstacles):
         """the rigid obstacles of the penalty contact term: F = alpha M (u - u_ref) + beta (r(u) + g(u) - f) (None: none); returns self"""

@@ -130,7 +130,9 @@ __device__ __forceinline__ void pipeline_consume(F&& f) {
 // grad u comes from  J^-T (sum_n grad_ref_n u_n^T), so the physical gradients are never formed
 // XIND (planar Tet4, rows_kernel.hpp): the vertices of the element are not a row of X but four entries of a table of the position's
 //   UNIQUE vertices (32 bytes each: [x y | z -]) at L.o_X, selected by the four bytes of `xind`
-template <int EK, int OP, int WHAT, bool PLANAR = false, bool NODEMAJOR = false, bool VCOMPACT = false, bool XIND = false>
+// EX (the vector and scalar forms): the per-element expansion of a.theta, applied to grad u at the point (material.hpp, stretch_strain) with
+//   the factor of the stress / energy density folded into the point's scale
+template <int EK, int OP, int WHAT, bool PLANAR = false, bool NODEMAJOR = false, bool VCOMPACT = false, bool XIND = false, bool EX = false>
 __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double* lds, const int* lds_i, int u, int q,
                                          const int* elem_id, int qslot = -1, double sqw = 0.0, unsigned xind = 0u) {
     using E = ElemT<EK>;
@@ -505,10 +507,16 @@ __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double
         // stress P (s x d), scaled by s, for the residual; energy density for the scalar path
         double P[S][D];
         double psi;
+        double se = s;   // (EX: s theta^(d-1) for the stress, s theta^d for the energy density)
+        if constexpr (EX) {
+            const Stretch<OP, D> st = element_stretch<OP, D>(a, *elem_id);
+            stretch_strain<OP, D, S>(st, gu);
+            se = s * (WHAT == WHAT_SCALAR ? st.sPsi : st.sP);
+        }
         material_point<OP, D, S, WHAT == WHAT_SCALAR ? EP_SCALAR : EP_VECTOR>(gu, mu, lambda, P, psi);
         if (WHAT == WHAT_VECTOR && VCOMPACT) {
             double M[S][D];
-            push_forward<D, S>(s, P, Ji, M);
+            push_forward<D, S>(se, P, Ji, M);
 #pragma unroll
             for (int i = 0; i < S; ++i)
 #pragma unroll
@@ -518,9 +526,9 @@ __device__ __forceinline__ void prologue(const KArgs& a, const Layout& L, double
 #pragma unroll
             for (int i = 0; i < S; ++i)
 #pragma unroll
-                for (int k = 0; k < D; ++k) sp[i * D + k] = s * P[i][k];
+                for (int k = 0; k < D; ++k) sp[i * D + k] = se * P[i][k];
         } else {
-            qp[0] = s * psi;
+            qp[0] = se * psi;
         }
     }
 }
@@ -1960,7 +1968,8 @@ static __global__ void k_hdr_counts(const GatherHdr* hdr, int nblk, unsigned* co
 
 // ============================================================================================ vector
 // f_I = sum_q s P g_I  (elliptic.rs:457-531), scattered with fp64 atomics into out[s node + i]
-template <int EK, int OP>
+// (EX, here and in the streamed and the scalar kernel: prologue's)
+template <int EK, int OP, bool EX = false>
 __global__ void __launch_bounds__(256) k_assemble_vector(const KArgs a) {
     using E = ElemT<EK>;
     using O = OpT<OP, E::D>;
@@ -1977,7 +1986,7 @@ __global__ void __launch_bounds__(256) k_assemble_vector(const KArgs a) {
     __syncthreads();
     stage_elements<EK, S>(a, L, lds, lds_i, U, true, lds_i + L.o_uniq);
     for (int i = tid; i < U * a.nq; i += nt)
-        prologue<EK, OP, WHAT_VECTOR>(a, L, lds, lds_i, i / a.nq, i % a.nq, lds_i + L.o_uniq + i / a.nq);
+        prologue<EK, OP, WHAT_VECTOR, false, false, false, false, EX>(a, L, lds, lds_i, i / a.nq, i % a.nq, lds_i + L.o_uniq + i / a.nq);
     __syncthreads();
     for (int it = tid; it < U * N; it += nt) {
         const int u = it / N, I = it % N;
@@ -2011,7 +2020,7 @@ __global__ void __launch_bounds__(256) k_assemble_vector(const KArgs a) {
 // connectivity -> vertex fetches of a batch no longer stand between its phases (they were a third of the kernel).  One
 // thread per (element of the batch, local node) throughout: it fetches that node's data and scatters that node's row.
 // NT threads: 256, or 128 when the point records of 256 / N elements do not leave room for two workgroups per CU
-template <int EK, int OP, int NT>
+template <int EK, int OP, int NT, bool EX = false>
 __global__ void __launch_bounds__(NT) k_assemble_vector_stream(const KArgs a) {
     using E = ElemT<EK>;
     using O = OpT<OP, E::D>;
@@ -2056,7 +2065,7 @@ __global__ void __launch_bounds__(NT) k_assemble_vector_stream(const KArgs a) {
         int node_n2 = load_node(b + 2LL * G);
         // phase B: one lane per (element, point)
         for (int i = tid; i < EPB * a.nq; i += NT)
-            prologue<EK, OP, WHAT_VECTOR, false, false, true>(a, L, lds, lds_i, i / a.nq, i % a.nq, lds_i + L.o_uniq + i / a.nq);
+            prologue<EK, OP, WHAT_VECTOR, false, false, true, false, EX>(a, L, lds, lds_i, i / a.nq, i % a.nq, lds_i + L.o_uniq + i / a.nq);
         lds_barrier();
         // contraction: this thread's node row of the element vector, scattered with fp64 atomics
         {
@@ -2191,7 +2200,7 @@ __global__ void __launch_bounds__(256) k_physical_points(const KArgs a, const So
 }
 
 // ============================================================================================ scalar
-template <int EK, int OP>
+template <int EK, int OP, bool EX = false>
 __global__ void __launch_bounds__(256) k_assemble_scalar(const KArgs a) {
     using E = ElemT<EK>;
     using O = OpT<OP, E::D>;
@@ -2208,7 +2217,7 @@ __global__ void __launch_bounds__(256) k_assemble_scalar(const KArgs a) {
     __syncthreads();
     stage_elements<EK, S>(a, L, lds, lds_i, U, true, lds_i + L.o_uniq);
     for (int i = tid; i < U * a.nq; i += nt)
-        prologue<EK, OP, WHAT_SCALAR>(a, L, lds, lds_i, i / a.nq, i % a.nq, lds_i + L.o_uniq + i / a.nq);
+        prologue<EK, OP, WHAT_SCALAR, false, false, false, false, EX>(a, L, lds, lds_i, i / a.nq, i % a.nq, lds_i + L.o_uniq + i / a.nq);
     __syncthreads();
     // element energies (sum over the points, like compute_element_elliptic_energy), then one partial per block summed in
     // element order; the host adds the partials in block order => deterministic

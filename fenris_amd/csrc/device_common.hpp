@@ -177,6 +177,10 @@ struct KArgs {
     int mb;                  // max (node, element) entries per batch (gather)
     int acc_max;             // doubles reserved for row accumulators
     int nb_max;              // max nodes per block
+    // per-element expansion (fh_set_element_expansion; material.hpp, Stretch): null while none is set -- the launchers then pick the
+    // instantiations without it -- and for the passes that feed a linear operator its operand in place of u
+    const double* theta;     // 1 or E stretches
+    int theta_per_elem;
 };
 
 // The quadrature tables (weights, reference gradients, basis values, uniform parameters) are read at wavefront-uniform addresses and

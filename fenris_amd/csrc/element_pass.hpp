@@ -493,7 +493,9 @@ __device__ __forceinline__ void element_pass_body(const KArgs& a, const long lon
 }
 
 // WHAT = EP_VECTOR: fe[a][e][c] (a.ke_out, E = a.num_elements);  EP_SCALAR: a.scalar_out[blockIdx.x] = energy of the workgroup's elements
-template <int EK, int OP, int WHAT>
+// EX: the per-element expansion of a.theta (material.hpp, Stretch) -- the body takes the nodal values U' and its result is scaled on the way
+// out; EX = false is the kernel as it was
+template <int EK, int OP, int WHAT, bool EX = false>
 __global__ void __launch_bounds__(256) k_element_pass(const KArgs a) {
     constexpr int N = EPDims<EK, OP, WHAT>::N, S = EPDims<EK, OP, WHAT>::S;
     __shared__ double red[4];
@@ -504,7 +506,16 @@ __global__ void __launch_bounds__(256) k_element_pass(const KArgs a) {
     double energy;
     double X[N][EPDims<EK, OP, WHAT>::D], U[N][S];
     element_pass_load<EK, OP, WHAT>(a, ec, X, U);
-    element_pass_body<EK, OP, WHAT>(a, e, live, ec, X, EPRegU<N, S>{U}, f, energy);
+    if constexpr (EX) {
+        constexpr int D = EPDims<EK, OP, WHAT>::D;
+        const Stretch<OP, D> st = element_stretch<OP, D>(a, ec);
+        stretch_nodes<OP, D, N>(st, X, U);
+        element_pass_body<EK, OP, WHAT>(a, e, live, ec, X, EPRegU<N, S>{U}, f, energy);
+        if constexpr (WHAT == EP_SCALAR) energy *= st.sPsi;
+        else stretch_scale<OP, D>(st.sP, f);
+    } else {
+        element_pass_body<EK, OP, WHAT>(a, e, live, ec, X, EPRegU<N, S>{U}, f, energy);
+    }
     if constexpr (WHAT == EP_SCALAR) {
         const double tot = block_sum_256(live ? energy : 0.0, red);
         if (threadIdx.x == 0) a.scalar_out[blockIdx.x] = tot;

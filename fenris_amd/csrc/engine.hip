@@ -282,6 +282,8 @@ void fill_common(fh_ctx* c, KArgs& a) {
     a.rule_map = c->has_rules ? c->rule_map.p : nullptr;
     a.rparams = c->has_rules ? c->rparams.p : nullptr;
     a.u = c->has_u ? c->u.p : nullptr;
+    a.theta = (c->expansion_n && !c->expansion_identity) ? c->expansion.p : nullptr;
+    a.theta_per_elem = c->expansion_n > 1 ? 1 : 0;
     a.fast = (generic_fast(c) && (c->op == FH_LAPLACE || c->op == FH_LINEAR_ELASTIC)) ? 1 : 0;
     a.mu = c->uni_mu;
     a.lambda = c->uni_lambda;
@@ -575,6 +577,7 @@ static int set_mesh_common(fh_ctx* c, int elem_kind, uint64_t N, uint64_t E) {
     contact_clear(c);   // (the node weights of the obstacles belong to the mesh)
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
     ++c->density_gen;
+    expansion_drop(c);   // (so does the per-element expansion)
     c->ragged = false;
     c->elem_kind = elem_kind;
     c->ei = ei;
@@ -679,6 +682,7 @@ int fh_set_connectivity_ragged(fh_ctx* c, uint64_t sdim, uint64_t N, const uint6
     contact_clear(c);   // (the node weights of the obstacles belong to the mesh)
     c->mass_rho_n = 0;   // (the density belongs to the mesh)
     ++c->density_gen;
+    expansion_drop(c);   // (so does the per-element expansion)
     c->ragged = true;
     // the per-mesh state set_mesh_common drops.  A mask left from a flat mesh reached build_compute_adjacency through fh_pattern: ei.n is 0
     // here (an element index k / 0) and `active` holds the old element count.

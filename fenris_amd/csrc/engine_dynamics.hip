@@ -15,15 +15,18 @@
 
 // what m (mass_inputs_equal) and a_n (==; first order: the rate, kept in v) were formed for: struct_gen (operator, table, mask), topo_gen,
 // geom_gen, density_gen, dirichlet_gen, the u_gen this handle left behind, and the contact_gen of fh_set_obstacles with the friction_gen
-// of fh_set_friction (contact_key)
+// of fh_set_friction (contact_key), and the expansion_gen of fh_set_element_expansion (the residual of every elastic operator sees the field)
 struct DynKey {
-    unsigned long long struct_gen = ~0ull, topo_gen = ~0ull, geom_gen = ~0ull, density_gen = ~0ull, dirichlet_gen = ~0ull, u_gen = ~0ull, contact = ~0ull;
-    static DynKey now(const fh_ctx* c) { return {c->struct_gen, c->topo_gen, c->geom_gen, c->density_gen, c->dirichlet_gen, c->u_gen, contact_key(c)}; }
+    unsigned long long struct_gen = ~0ull, topo_gen = ~0ull, geom_gen = ~0ull, density_gen = ~0ull, dirichlet_gen = ~0ull, u_gen = ~0ull, contact = ~0ull,
+                       expansion = ~0ull;
+    static DynKey now(const fh_ctx* c) {
+        return {c->struct_gen, c->topo_gen, c->geom_gen, c->density_gen, c->dirichlet_gen, c->u_gen, contact_key(c), expansion_key(c, false)};
+    }
     bool mass_inputs_equal(const DynKey& o) const {
         return struct_gen == o.struct_gen && topo_gen == o.topo_gen && geom_gen == o.geom_gen && density_gen == o.density_gen &&
                dirichlet_gen == o.dirichlet_gen;
     }
-    bool operator==(const DynKey& o) const { return mass_inputs_equal(o) && u_gen == o.u_gen && contact == o.contact; }
+    bool operator==(const DynKey& o) const { return mass_inputs_equal(o) && u_gen == o.u_gen && contact == o.contact && expansion == o.expansion; }
 };
 
 // the slots of fh_dynamics_step's stats

@@ -359,6 +359,10 @@ int eigs_lowest_dev(fh_ctx* c, uint32_t m32, double shift, int preconditioner, d
     if (multigrid && !c->mg) return c->fail(FH_INVALID_STATE, "fh_eigs_lowest: FH_PRECOND_MULTIGRID needs a hierarchy (fh_set_multigrid)");
     if (multigrid && contact_table(c).count)
         return c->fail(FH_UNSUPPORTED, "fh_eigs_lowest: FH_PRECOND_MULTIGRID with obstacles set (fh_set_obstacles): the coarse levels would not see the contact term");
+    if (multigrid) {   // (nor the per-element expansion of a hyperelastic operator)
+        const int rb = expansion_blocks_multigrid(c, "fh_eigs_lowest");
+        if (rb) return rb;
+    }
     if ((uint64_t)c->S() * c->N >= (1ull << 31)) return c->fail(FH_UNSUPPORTED, "fh_eigs_lowest: more than 2^31 - 1 dofs");
     EigState e;
     e.c = c;

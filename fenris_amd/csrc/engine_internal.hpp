@@ -489,6 +489,15 @@ struct fh_ctx {
     uint64_t mass_rho_n = 0;
     unsigned long long density_gen = 0;
     DevBuf<double> mf_mass;
+    // the per-element expansion (fh_set_element_expansion, fh_set_thermal_expansion): 1 (the whole mesh) or E stretches theta_e > 0, none when
+    // 0; fh_set_mesh* drops it.  expansion_gen counts the calls that set or clear it and joins the key of every cache that depends on u or
+    // on the material (expansion_key: 0 where the operator's tangent does not see the field)
+    DevBuf<double> expansion;
+    uint64_t expansion_n = 0;
+    // every stretch of the field is exactly 1: the kernels are handed no field (fill_common), so that such a field gives the bits of none on
+    // every route whatever the compiler makes of the second instantiations (the staged energy of Tet10 differed in the last place)
+    bool expansion_identity = false;
+    unsigned long long expansion_gen = 0;
     unsigned long long geom_gen = 0;   // counts fh_update_vertices calls
     unsigned long long u_gen = 0;      // counts fh_set_u* calls
     unsigned long long dirichlet_gen = 0;   // counts fh_set_operator_dirichlet_nodes / _dofs calls
@@ -693,6 +702,16 @@ int newton_residual(fh_ctx* c, double alpha, double beta, const double* f_dev, c
 // through element vectors and the ordered node sums; the loop of fh_newton_solve on the context's u (engine_newton.hip; st: 4 counters,
 // nm: 3 norms, as fh_newton_solve's stats and norms)
 KArgs pass_args(fh_ctx* c);
+// the per-element expansion (engine_expansion.hip): FH_UNSUPPORTED, naming it, while a field is set and the route cannot honour it -- any
+// element-to-node route (FH_LAPLACE, FH_TENSOR, rule-set tables), the assembled stiffness and FH_PRECOND_MULTIGRID (hyperelastic operators);
+// the field dropped with the mesh; the part of a cache's key that follows it (0 where the tangent of the operator does not see the field)
+int expansion_blocked(fh_ctx* c, const char* who);
+int expansion_blocks_matrix(fh_ctx* c, const char* who);
+int expansion_blocks_multigrid(fh_ctx* c, const char* who);
+void expansion_drop(fh_ctx* c);
+inline unsigned long long expansion_key(const fh_ctx* c, bool tangent_only) {
+    return (tangent_only && !op_depends_on_u(c->op)) ? 0ull : c->expansion_gen;
+}
 const unsigned char* active_mask(const fh_ctx* c);
 bool tiles_enabled(const fh_ctx* c);
 int ensure_vector_tiles(fh_ctx* c);

@@ -412,6 +412,8 @@ int assemble_matrix_enqueue(fh_ctx* c, double* values_dev, int flags, bool reset
     } exit_print{vt_entry, t_entry, c->stream};
     int rc = check_ready(c, "fh_assemble_matrix", true);
     if (rc) return rc;
+    rc = expansion_blocks_matrix(c, "fh_assemble_matrix");
+    if (rc) return rc;
     if (!values_dev) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_matrix: values is null");
     const int mode = flags & FH_SCATTER_MASK;
     const int overwrite = (flags & FH_ASSEMBLE_OVERWRITE) ? 1 : 0;
@@ -612,6 +614,8 @@ int fh_assemble_matrix_async_dev(fh_ctx* c, double* values_dev, int flags) {
     // rule-set table: one pass per group of rules, the first one with the caller's flags, the others accumulating
     int rc = check_ready(c, "fh_assemble_matrix", true);
     if (rc) return rc;
+    rc = expansion_blocks_matrix(c, "fh_assemble_matrix");
+    if (rc) return rc;
     if (!values_dev) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_matrix: values is null");
     rc = reset_status(c);
     if (rc) return rc;
@@ -766,6 +770,8 @@ int fh_assemble_matrix(fh_ctx* c, double* values, int flags, uint64_t* failed) {
     DevGuard dev_guard_(c->device);
     int rc = check_ready(c, "fh_assemble_matrix", true);
     if (rc) return rc;
+    rc = expansion_blocks_matrix(c, "fh_assemble_matrix");
+    if (rc) return rc;
     if (!values) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_matrix: values is null");
     const uint64_t nnz = fh_nnz(c);
     DevBuf<double> d;
@@ -785,6 +791,8 @@ int fh_assemble_element_matrices_dev(fh_ctx* c, uint64_t first, uint64_t count, 
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     int rc = check_ready(c, "fh_assemble_element_matrices", false);
+    if (rc) return rc;
+    rc = expansion_blocks_matrix(c, "fh_assemble_element_matrices");
     if (rc) return rc;
     if (first + count > c->E || (count && !ke_dev)) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_element_matrices: bad range");
     if (count == 0) return FH_OK;
@@ -813,6 +821,8 @@ int fh_assemble_element_matrices(fh_ctx* c, uint64_t first, uint64_t count, doub
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
     int rc = check_ready(c, "fh_assemble_element_matrices", false);
+    if (rc) return rc;
+    rc = expansion_blocks_matrix(c, "fh_assemble_element_matrices");
     if (rc) return rc;
     if (first + count > c->E || (count && !ke_out)) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_element_matrices: bad range");
     if (count == 0) return FH_OK;

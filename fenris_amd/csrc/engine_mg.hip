@@ -385,7 +385,8 @@ extern "C++" int mg_setup(fh_ctx* fine, double alpha, double beta) {
     fh_mg* mg = fine->mg;
     StreamBorrow borrow(mg);
     const int L = (int)mg->lv.size() - 1;
-    int rc;
+    int rc = expansion_blocks_multigrid(fine, "FH_PRECOND_MULTIGRID");
+    if (rc) return rc;
     // the work vectors, the diagonal and the transfers were sized for each level's mesh at fh_mg_create: a level whose mesh or solution dim has
     // changed since would have S * N entries written into arrays of the old length
     for (int l = 0; l <= L; ++l) {

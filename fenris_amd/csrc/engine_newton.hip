@@ -24,6 +24,10 @@ int newton_run(fh_ctx* c, double alpha, double beta, const double* f, const doub
     const char* who = "fh_newton_solve";
     if (preconditioner == FH_PRECOND_MULTIGRID && contact_table(c).count)
         return c->fail(FH_UNSUPPORTED, std::string(who) + ": FH_PRECOND_MULTIGRID with obstacles set (fh_set_obstacles): the coarse levels would not see the contact term");
+    if (preconditioner == FH_PRECOND_MULTIGRID) {   // (nor the per-element expansion of a hyperelastic operator)
+        const int rb = expansion_blocks_multigrid(c, who);
+        if (rb) return rb;
+    }
     const int n = c->S() * (int)c->N;
     const int g = (n + 255) / 256;
     NewtonScratch ns;

@@ -39,16 +39,20 @@ static int launch_recover_elements(fh_ctx* c, const KArgs& a, const RecoverArgs&
             if constexpr (!recover_defined<opc(), q()>) {
                 return (int)FH_UNSUPPORTED;
             } else {
-                if constexpr (ElemT<ek()>::N == ElemT<ek()>::NG) {
-                    if (per_element) {
-                        hipLaunchKernelGGL((k_recover_elements<ek(), opc(), q(), FH_AT_ELEMENTS>), dim3((unsigned)grid), dim3(256), 0, c->stream, a, r);
-                        HIP_TRY(c, hipGetLastError());
-                        return (int)FH_OK;
+                // (the expansion: its own instantiations of the quantities that come from the elastic part, the others as they were)
+                return dispatch_bool(recover_expands<opc(), q()> && a.theta != nullptr, [&](auto ex) {
+                    constexpr bool EX = ex() && recover_expands<opc(), q()>;
+                    if constexpr (ElemT<ek()>::N == ElemT<ek()>::NG) {
+                        if (per_element) {
+                            hipLaunchKernelGGL((k_recover_elements<ek(), opc(), q(), FH_AT_ELEMENTS, EX>), dim3((unsigned)grid), dim3(256), 0, c->stream, a, r);
+                            HIP_TRY(c, hipGetLastError());
+                            return (int)FH_OK;
+                        }
                     }
-                }
-                hipLaunchKernelGGL((k_recover_elements<ek(), opc(), q(), FH_AT_POINTS>), dim3((unsigned)grid), dim3(256), 0, c->stream, a, r);
-                HIP_TRY(c, hipGetLastError());
-                return (int)FH_OK;
+                    hipLaunchKernelGGL((k_recover_elements<ek(), opc(), q(), FH_AT_POINTS, EX>), dim3((unsigned)grid), dim3(256), 0, c->stream, a, r);
+                    HIP_TRY(c, hipGetLastError());
+                    return (int)FH_OK;
+                });
             }
         });
     });
@@ -85,6 +89,8 @@ int fh_recover_dev(fh_ctx* c, int quantity, int where, double* out_dev) {
     if (rc) return rc;
     if (quantity == FH_RECOVER_VOLUME && where != FH_AT_ELEMENTS) return c->fail(FH_BAD_ARGUMENT, "fh_recover: FH_RECOVER_VOLUME is defined at FH_AT_ELEMENTS only");
     rc = recover_check(c, "fh_recover", quantity, &ncomp);
+    if (rc) return rc;
+    rc = expansion_blocked(c, "fh_recover");
     if (rc) return rc;
     rc = recover_table_check(c, "fh_recover");
     if (rc) return rc;

@@ -349,6 +349,10 @@ extern "C++" int cg_solve_free_dev(fh_ctx* c, const char* who, int scope, const 
     MfScope scope_guard_(c, scope);
     if (multigrid && contact_table(c).count)
         return c->fail(FH_UNSUPPORTED, std::string(who) + ": FH_PRECOND_MULTIGRID with obstacles set (fh_set_obstacles): the coarse levels would not see the contact term");
+    if (multigrid) {   // (nor the per-element expansion of a hyperelastic operator)
+        const int rb = expansion_blocks_multigrid(c, who);
+        if (rb) return rb;
+    }
     const int S = c->S();
     const int n = S * (int)c->N;
     if (n == 0) return FH_OK;

@@ -5,9 +5,18 @@
 // (tiles, else element vectors and ordered node sums), and the walk over the groups of a rule-set table.
 #include "engine_internal.hpp"
 
+// with_expansion(OP, a, f): f(true_type) when the arguments carry the per-element expansion (a.theta) and OP has such kernels, f(false_type)
+// while none is set; -1 for an operator without them (the entry points refuse it before any launch)
+template <int OP, class F>
+static int with_expansion(const KArgs& a, F&& f) {
+    return dispatch_bool(a.theta != nullptr, [&](auto ex) {
+        if constexpr (!ex() || op_expands(OP)) return f(ex);
+        else return -1;
+    });
+}
 template <int EK, int OP>
 static int launch_vector(fh_ctx* c, KArgs& a, size_t lds, int grid) {
-    return launch_lds(c, k_assemble_vector<EK, OP>, dim3(grid), dim3(256), lds, c->stream, a);
+    return with_expansion<OP>(a, [&](auto ex) { return launch_lds(c, k_assemble_vector<EK, OP, ex()>, dim3(grid), dim3(256), lds, c->stream, a); });
 }
 template <int EK, int OP, int NT>
 static int launch_vector_stream_nt(fh_ctx* c, KArgs& a) {
@@ -17,7 +26,7 @@ static int launch_vector_stream_nt(fh_ctx* c, KArgs& a) {
     const long long nbatch = (a.work_end - a.work_begin + EPB - 1) / EPB;
     const int per_cu = std::max(1, (int)std::min<size_t>(c->opt.VEC_WGS_PER_CU.value_or(3), (LDS_LIMIT - 512) / std::max<size_t>(lds, 1)));
     const int grid = std::max(1, (int)std::min<long long>(nbatch, (long long)c->opt.PIPE_GRID.value_or(c->num_cus * per_cu)));   // (tests force many batches per workgroup)
-    return launch_lds(c, k_assemble_vector_stream<EK, OP, NT>, dim3(grid), dim3(NT), lds, c->stream, a);
+    return with_expansion<OP>(a, [&](auto ex) { return launch_lds(c, k_assemble_vector_stream<EK, OP, NT, ex()>, dim3(grid), dim3(NT), lds, c->stream, a); });
 }
 template <int EK, int OP>
 static int launch_vector_stream(fh_ctx* c, KArgs& a) {
@@ -31,7 +40,7 @@ static int launch_vector_stream(fh_ctx* c, KArgs& a) {
 }
 template <int EK, int OP>
 static int launch_scalar(fh_ctx* c, KArgs& a, size_t lds, int grid) {
-    return launch_lds(c, k_assemble_scalar<EK, OP>, dim3(grid), dim3(256), lds, c->stream, a);
+    return with_expansion<OP>(a, [&](auto ex) { return launch_lds(c, k_assemble_scalar<EK, OP, ex()>, dim3(grid), dim3(256), lds, c->stream, a); });
 }
 
 // register-resident element pass (element_pass.hpp): one thread per element of the small iso-parametric kinds, operators with a
@@ -40,9 +49,11 @@ template <int WHAT>
 static int launch_element_pass(fh_ctx* c, KArgs& a) {
     const int grid = (int)((a.num_elements + 255) / 256);
     return dispatch(low_order_kinds, c->elem_kind, elliptic_ops, c->op, -1, [&](auto ek, auto op) {
-        hipLaunchKernelGGL((k_element_pass<ek(), op(), WHAT>), dim3(grid), dim3(256), 0, c->stream, a);
-        HIP_TRY(c, hipGetLastError());
-        return (int)FH_OK;
+        return with_expansion<op()>(a, [&](auto ex) {
+            hipLaunchKernelGGL((k_element_pass<ek(), op(), WHAT, ex()>), dim3(grid), dim3(256), 0, c->stream, a);
+            HIP_TRY(c, hipGetLastError());
+            return (int)FH_OK;
+        });
     });
 }
 static int launch_vector_from_elements_soa(fh_ctx* c, int sdim, const double* fe, double* out_dev, const unsigned* adj_off = nullptr,
@@ -160,6 +171,10 @@ static int assemble_vector_single(fh_ctx* c, double* out_dev, uint64_t* failed);
 int fh_assemble_vector_dev(fh_ctx* c, double* out_dev, uint64_t* failed) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
+    if (op_has_stress(c->op)) {
+        const int rb = expansion_blocked(c, "fh_assemble_vector");
+        if (rb) return rb;
+    }
     if (!c->rs.active) return assemble_vector_single(c, out_dev, failed);
     return rs_walk_accumulating(c, failed, [&](uint64_t* f) { return assemble_vector_single(c, out_dev, f); });
 }
@@ -452,6 +467,10 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed);
 int fh_assemble_scalar(fh_ctx* c, double* out, uint64_t* failed) {
     if (!c) return FH_BAD_ARGUMENT;
     DevGuard dev_guard_(c->device);
+    if (op_has_stress(c->op)) {
+        const int rb = expansion_blocked(c, "fh_assemble_scalar");
+        if (rb) return rb;
+    }
     if (!c->rs.active) return assemble_scalar_single(c, out, failed);
     if (!out) return c->fail(FH_BAD_ARGUMENT, "fh_assemble_scalar: out is null");
     double tot = 0.0;
@@ -549,6 +568,10 @@ static int assemble_scalar_single(fh_ctx* c, double* out, uint64_t* failed) {
 // LinearElastic: the element pass reads x 2^-e with |x 2^-e|_inf in [1/2, 1) (mf_exponent, device_common.hpp).
 // scope: MF_OPERATOR for the operator's entry points (the operators linear in u), MF_TANGENT for the tangent's (every operator with a stress).
 int mf_ready(fh_ctx* c, const char* who, int scope) {
+    if (c->op == FH_LAPLACE || c->op == FH_TENSOR || c->rs.active) {   // (ahead of the other refusals: this one names the expansion)
+        const int rb = expansion_blocked(c, who);
+        if (rb) return rb;
+    }
     if (c->op >= 0 && (!op_has_stress(c->op) || (scope == MF_OPERATOR && op_depends_on_u(c->op))))   // (no operator yet: check_ready says so)
         return c->fail(FH_UNSUPPORTED, std::string(who) + (scope == MF_OPERATOR
                                                                ? ": the matrix-free operator covers FH_LAPLACE and FH_LINEAR_ELASTIC only"
@@ -573,7 +596,8 @@ static void mf_scale_key_now(const fh_ctx* c, unsigned long long (&k)[8], double
     k[0] = c->struct_gen;
     k[1] = c->topo_gen;
     k[2] = c->geom_gen;
-    k[3] = ((c->op <= FH_LINEAR_ELASTIC && !contact) || beta == 0.0) ? 0 : c->u_gen;
+    // (the expansion joins u: both count upwards, so their sum moves when either does; 0 for the operators whose tangent does not see the field)
+    k[3] = ((c->op <= FH_LINEAR_ELASTIC && !contact) || beta == 0.0) ? 0 : c->u_gen + expansion_key(c, true);
     std::memcpy(&k[4], &alpha, sizeof(double));
     std::memcpy(&k[5], &beta, sizeof(double));
     k[6] = alpha != 0.0 ? c->density_gen : 0;
@@ -608,6 +632,7 @@ static int mf_tiles_pass(fh_ctx* c, KArgs& a, const double* xin, bool* done) {
         rt = vector_tiles_diagonal_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p);
     } else if (c->op <= FH_LINEAR_ELASTIC) {
         a.u = xin;
+        a.theta = nullptr;   // (the operand, not u: A x does not see the expansion)
         rt = vector_tiles_element_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, c->fe_scratch.p);
     } else {
         rt = vector_tiles_tangent_pass(c->elem_kind, c->op, c->stream, a, c->vt.v, active, xin, c->fe_scratch.p);
@@ -625,9 +650,13 @@ static void mf_elements_launch(fh_ctx* c, const KArgs& a, const unsigned char* a
     dispatch_or_last(elliptic_ops, c->op, [&](auto op) {
         return dispatch_or_last(int_list<2, 3>{}, c->ei.d, [&](auto d) {
             constexpr int S = OpT<op(), d()>::S;
-            if (x) hipLaunchKernelGGL((k_mf_apply_elements<d(), S, op()>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, x, fe);
-            else hipLaunchKernelGGL((k_mf_diagonal_elements<d(), S, op()>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
-            return 0;
+            // (the expansion: the nonlinear operators only -- the tangent of a linear one does not see it)
+            return dispatch_bool(op_depends_on_u(op()) && a.theta != nullptr, [&](auto ex) {
+                constexpr bool EX = ex() && op_depends_on_u(op());
+                if (x) hipLaunchKernelGGL((k_mf_apply_elements<d(), S, op(), EX>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, x, fe);
+                else hipLaunchKernelGGL((k_mf_diagonal_elements<d(), S, op(), EX>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+                return 0;
+            });
         });
     });
 }
@@ -820,7 +849,10 @@ static int map_on_tiles(fh_ctx* c, double alpha, double beta, const double* x, M
         if (beta != 0.0) {
             rc = mf_operand(c, x, dmask, &in);
             if (rc) return rc;
-            if (linear) a.u = in.x;
+            if (linear) {
+                a.u = in.x;
+                a.theta = nullptr;   // (the operand, not u)
+            }
         }
         MassTerm mt;
         mt.alpha = alpha;
@@ -966,8 +998,11 @@ static void residual_elements_launch(fh_ctx* c, const KArgs& a, const unsigned c
     const dim3 grid((unsigned)((c->E + 255) / 256));
     dispatch_or_last(elliptic_ops, c->op, [&](auto op) {
         return dispatch_or_last(int_list<2, 3>{}, c->ei.d, [&](auto d) {
-            hipLaunchKernelGGL((k_residual_elements<d(), OpT<op(), d()>::S, op()>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
-            return 0;
+            return dispatch_bool(op_expands(op()) && a.theta != nullptr, [&](auto ex) {
+                constexpr bool EX = ex() && op_expands(op());
+                hipLaunchKernelGGL((k_residual_elements<d(), OpT<op(), d()>::S, op(), EX>), grid, dim3(256), 0, c->stream, a, c->ei.n, c->ei.ng, active, fe);
+                return 0;
+            });
         });
     });
 }

@@ -363,6 +363,79 @@ __device__ __forceinline__ void tangent_apply(const TangentLin<OP, D>& L, const 
             }
     }
 }
+// ---- per-element expansion (fh_set_element_expansion): theta > 0 is the stress-free isotropic stretch of the element, 1 = none.
+//   LinearElastic (additive):      gu_e = gu - (theta - 1) I,            P = P_0(gu_e),              psi = psi_0(gu_e),          dP = dP_0
+//   hyperelastic (F = F_e theta):  gu_e = (gu - (theta - 1) I) / theta,  P = theta^(d-1) P_0(gu_e),  psi = theta^d psi_0(gu_e),  dP[H] = theta^(d-2) dP_0(gu_e)[H]
+// The laws above stay as they are: a kernel changes their argument and scales their result.  Within an element (theta - 1) I is the gradient of
+// (theta - 1)(X - X_0), so the register-resident bodies take the law through their nodal values, U'_n = (U_n - (theta - 1)(X_n - X_0)) / theta
+// (stretch_nodes: relative to the element's node 0, so that coordinates far from the origin do not cancel; U' of a trilinear U is trilinear,
+// the Hex8 moment form stays exact); the kernels that hold grad u at a point take it there (stretch_strain).  Powers by multiplication.
+// theta == 1 changes no bit of either form: the subtrahend is a zero, the factors are 1.
+template <int OP, int D>
+struct Stretch {
+    static_assert(OP == FH_LINEAR_ELASTIC || OP == FH_NEO_HOOKEAN || OP == FH_STVK || OP == FH_STABLE_NEO_HOOKEAN, "the expansion strains an elastic operator");
+    static constexpr bool additive = OP == FH_LINEAR_ELASTIC;
+    double t1;    // theta - 1
+    double inv;   // 1 / theta; additive: 1
+    double sT;    // theta^(d-2), the factor of the tangent; additive: 1
+    double sP;    // theta^(d-1), of the stress
+    double sPsi;  // theta^d, of the energy density
+    __device__ __forceinline__ explicit Stretch(double theta) {
+        t1 = theta - 1.0;
+        if constexpr (additive) {
+            inv = 1.0; sT = 1.0; sP = 1.0; sPsi = 1.0;
+        } else {
+            inv = 1.0 / theta;
+            sT = D == 3 ? theta : 1.0;
+            sP = sT * theta;
+            sPsi = sP * theta;
+        }
+    }
+};
+// the stretch of element e from the arguments (KArgs::theta: one for the mesh or one per element)
+template <int OP, int D>
+__device__ __forceinline__ Stretch<OP, D> element_stretch(const KArgs& a, long long e) {
+    return Stretch<OP, D>(a.theta[a.theta_per_elem ? e : 0]);
+}
+// grad u -> the elastic part gu_e, at a point
+template <int OP, int D, int S>
+__device__ __forceinline__ void stretch_strain(const Stretch<OP, D>& st, double (&gu)[D][S]) {
+    static_assert(S == D, "the expansion strains a vector field");
+#pragma unroll
+    for (int i = 0; i < D; ++i) gu[i][i] -= st.t1;
+    if constexpr (!Stretch<OP, D>::additive) {
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int k = 0; k < S; ++k) gu[i][k] *= st.inv;
+    }
+}
+// the nodal values whose gradient is gu_e, in place: U'_n = (U_n - (theta - 1)(X_n - X_0)) / theta
+template <int OP, int D, int N>
+__device__ __forceinline__ void stretch_nodes(const Stretch<OP, D>& st, const double (&X)[N][D], double (&U)[N][D]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const double v = n == 0 ? U[n][k] : fma(-st.t1, X[n][k] - X[0][k], U[n][k]);
+            U[n][k] = Stretch<OP, D>::additive ? v : v * st.inv;
+        }
+}
+// f *= s over an element vector (the hyperelastic factors; the additive law has none)
+template <int OP, int D, int N, int S>
+__device__ __forceinline__ void stretch_scale(double s, double (&f)[N][S]) {
+    if constexpr (!Stretch<OP, D>::additive) {
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int k = 0; k < S; ++k) f[n][k] *= s;
+    }
+}
+// whether an operator has an instantiation with the expansion (FH_LAPLACE and FH_TENSOR are refused on the host)
+__host__ __device__ constexpr bool op_expands(int op) {
+    return op == FH_LINEAR_ELASTIC || op == FH_NEO_HOOKEAN || op == FH_STVK || op == FH_STABLE_NEO_HOOKEAN;
+}
+
 // the Lame parameters of point q: the element's own (par_e: its row of a compact table, KArgs::rparams) or the uniform table's, by scalar loads
 template <int OP>
 __device__ __forceinline__ void point_params(const KArgs& a, const double* par_e, int q, double& mu, double& lambda) {

@@ -130,6 +130,32 @@ __device__ __forceinline__ void recover_values(const double (&gu)[D][S], double 
     }
 }
 
+// the quantities that come from the elastic part under a per-element expansion (material.hpp, Stretch): the stresses and the energy
+// density.  The gradient and the strain stay the total ones.
+template <int OP, int Q>
+constexpr bool recover_expands = op_expands(OP) && (Q == FH_RECOVER_STRESS_PK1 || Q == FH_RECOVER_STRESS_CAUCHY || Q == FH_RECOVER_VON_MISES ||
+                                                    Q == FH_RECOVER_ENERGY_DENSITY);
+// recover_values of element e's point under its stretch (EX; gu is consumed): the first Piola-Kirchhoff stress theta^(d-1) P_0(gu_e) and the
+// energy density theta^d psi_0(gu_e) per reference volume; the Cauchy stress P F^T / det F of the total F is the one of the elastic part
+// alone (the powers of theta cancel), and so is von Mises'
+template <int OP, int D, int S, int Q, bool EX>
+__device__ __forceinline__ void recover_point(const KArgs& a, const long long e, double (&gu)[D][S], double mu, double lambda,
+                                              double (&v)[RecoverComp<OP, D, Q>::NC]) {
+    if constexpr (EX && recover_expands<OP, Q>) {
+        const Stretch<OP, D> st = element_stretch<OP, D>(a, e);
+        stretch_strain<OP, D, S>(st, gu);
+        recover_values<OP, D, S, Q>(gu, mu, lambda, v);
+        if constexpr (Q == FH_RECOVER_STRESS_PK1 && !Stretch<OP, D>::additive) {
+#pragma unroll
+            for (int c = 0; c < RecoverComp<OP, D, Q>::NC; ++c) v[c] *= st.sP;
+        } else if constexpr (Q == FH_RECOVER_ENERGY_DENSITY && !Stretch<OP, D>::additive) {
+            v[0] *= st.sPsi;
+        }
+    } else {
+        recover_values<OP, D, S, Q>(gu, mu, lambda, v);
+    }
+}
+
 // J -> |det J| and grad u = J^-T R.  det J == 0 exactly is reported like the residual reports it (elliptic.rs:401-404), the inverse is zero then.
 template <int D, int S>
 __device__ __forceinline__ double recover_grad_u(const KArgs& a, const long long e, const double (&J)[D][D], const double (&R)[D][S],
@@ -142,8 +168,8 @@ __device__ __forceinline__ double recover_grad_u(const KArgs& a, const long long
 
 // WHERE = FH_AT_ELEMENTS (Quad4, Tri3, Tet4, Hex8): one thread per element, mean and / or V_e.
 // WHERE = FH_AT_POINTS (every kind): one thread per (element, point), the point's row and / or its measure.
-// Masked elements write zeros.
-template <int EK, int OP, int Q, int WHERE>
+// Masked elements write zeros.  EX: with the per-element expansion of a.theta (recover_point); EX = false is the kernel as it was.
+template <int EK, int OP, int Q, int WHERE, bool EX = false>
 __global__ void __launch_bounds__(256) k_recover_elements(const KArgs a, const RecoverArgs r) {
     using E = ElemT<EK>;
     constexpr int D = E::D, N = E::N, NG = E::NG, S = OpT<OP, D>::S, NC = RecoverComp<OP, D, Q>::NC;
@@ -204,7 +230,7 @@ __global__ void __launch_bounds__(256) k_recover_elements(const KArgs a, const R
                 double mu, lambda;
                 point_params<OP>(a, par_e, q, mu, lambda);
                 double v[NC];
-                recover_values<OP, D, S, Q>(gu, mu, lambda, v);
+                recover_point<OP, D, S, Q, EX>(a, e, gu, mu, lambda, v);
 #pragma unroll
                 for (int c = 0; c < NC; ++c) acc[c] = fma(s, v[c], acc[c]);
             }
@@ -274,7 +300,7 @@ __global__ void __launch_bounds__(256) k_recover_elements(const KArgs a, const R
                     lambda = p[1];
                 }
                 double v[NC];
-                recover_values<OP, D, S, Q>(gu, mu, lambda, v);
+                recover_point<OP, D, S, Q, EX>(a, e, gu, mu, lambda, v);
 #pragma unroll
                 for (int c = 0; c < NC; ++c) r.points[(size_t)t * NC + c] = v[c];
             }

@@ -391,8 +391,9 @@ __device__ __forceinline__ void mf_grad(const KArgs& a, int N, int q, int n, con
 // y = T(u) x (= A x for FH_LAPLACE and FH_LINEAR_ELASTIC) for any element kind, deterministic: grad x = J^-T sum_n ghat_n x_n^T per point (and
 // grad u from a.u, may be null: zero, for the nonlinear operators only), dP(F)[grad x^T] by tangent_lin / tangent_apply (material.hpp;
 // for the linear operators the stress of material_point without F), element vectors f_n = w |det J| dP g_n by local node.  Inactive elements
-// write zeros.
-template <int D, int S, int OP>
+// write zeros.  EX (the nonlinear operators; here and in the two kernels below): the per-element expansion of a.theta applied to grad u at
+// the point, the result scaled (material.hpp, Stretch); EX = false is the kernel as it was.
+template <int D, int S, int OP, bool EX = false>
 __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N, int NG, const unsigned char* active, const double* x, double* fe) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.num_elements) return;
@@ -430,6 +431,12 @@ __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N,
                 }
             }
         }
+        if constexpr (EX) {
+            static_assert(!EX || op_depends_on_u(OP), "the tangent of a linear operator does not see the expansion");
+            const Stretch<OP, D> st = element_stretch<OP, D>(a, e);
+            stretch_strain<OP, D, S>(st, gu);
+            s *= st.sT;
+        }
         double mu, lambda;
         point_params<OP>(a, par_e, q, mu, lambda);
         TangentLin<OP, D> L;
@@ -454,7 +461,7 @@ __global__ void __launch_bounds__(256) k_mf_apply_elements(const KArgs a, int N,
 // the residual r(u) of any element kind without atomics (the Newton residual off the tiles, engine_vector.hip): per point grad u = J^-T
 // sum_n ghat_n u_n^T (a.u, may be null: zero), the stress P of material_point (material.hpp), element vectors f_n = w |det J| P g_n by local node into
 // fe[a][e][c] for the ordered node sums of k_vector_from_elements_soa.  Inactive elements write zeros; det J == 0 is reported like the residual.
-template <int D, int S, int OP>
+template <int D, int S, int OP, bool EX = false>
 __global__ void __launch_bounds__(256) k_residual_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.num_elements) return;
@@ -488,6 +495,11 @@ __global__ void __launch_bounds__(256) k_residual_elements(const KArgs a, int N,
                     for (int r = 0; r < D; ++r) gu[r][k] = fma(g[r], uv, gu[r][k]);
                 }
             }
+        if constexpr (EX) {
+            const Stretch<OP, D> st = element_stretch<OP, D>(a, e);
+            stretch_strain<OP, D, S>(st, gu);
+            s *= st.sP;
+        }
         double mu, lambda;
         point_params<OP>(a, par_e, q, mu, lambda);
         double P[S][D], psi;
@@ -510,7 +522,7 @@ __global__ void __launch_bounds__(256) k_residual_elements(const KArgs a, int N,
 // the diagonal of the same map: entry (n, k) = sum_q s (dP[e_k g_n^T] g_n)_k, in ascending q.  The linear operators in closed form, as
 // diagonal_element_body (element_pass.hpp):  Laplace  s |g_n|^2,  LinearElastic  s (mu (|g_n|^2 + g_n,k^2) + lambda g_n,k^2); the nonlinear
 // ones by tangent_apply on the unit directions, as tangent_diagonal_body.
-template <int D, int S, int OP>
+template <int D, int S, int OP, bool EX = false>
 __global__ void __launch_bounds__(256) k_mf_diagonal_elements(const KArgs a, int N, int NG, const unsigned char* active, double* fe) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.num_elements) return;
@@ -544,6 +556,12 @@ __global__ void __launch_bounds__(256) k_mf_diagonal_elements(const KArgs a, int
                     for (int r = 0; r < D; ++r) gu[r][k] = fma(g[r], uv, gu[r][k]);
                 }
             }
+        }
+        if constexpr (EX) {
+            static_assert(!EX || op_depends_on_u(OP), "the diagonal of a linear operator does not see the expansion");
+            const Stretch<OP, D> st = element_stretch<OP, D>(a, e);
+            stretch_strain<OP, D, S>(st, gu);
+            s *= st.sT;
         }
         double mu, lambda;
         point_params<OP>(a, par_e, q, mu, lambda);

@@ -347,7 +347,10 @@ __device__ __forceinline__ void block_partial_store(double v, double* partial) {
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
-template <int EK, int OP, int TS, int MONO = 0>
+// EX (here and in the tile kernels below): the per-element expansion of a.theta (material.hpp, Stretch) -- the nodal values the body takes are
+// U' and its result is scaled on the way out; the body itself is the same.  EX = false is the kernel as it was: the launchers pick it while
+// no field is set.
+template <int EK, int OP, int TS, int MONO = 0, bool EX = false>
 __global__ void __launch_bounds__(TS) k_element_pass_tiled(const KArgs a, const VecTiles t, const unsigned char* active, double* partial) {
     constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
     __shared__ double stage[N * S * TS];
@@ -369,7 +372,14 @@ __global__ void __launch_bounds__(TS) k_element_pass_tiled(const KArgs a, const 
     // wavefront per SIMD -- 62 registers spill: 1.66 ms)
     double f[N][S];
     double energy;
-    element_pass_body<EK, OP, EP_VECTOR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+    if constexpr (EX) {
+        const Stretch<OP, D> st = element_stretch<OP, D>(a, tp.ec);
+        stretch_nodes<OP, D, N>(st, X, Uv);
+        element_pass_body<EK, OP, EP_VECTOR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+        stretch_scale<OP, D>(st.sP, f);
+    } else {
+        element_pass_body<EK, OP, EP_VECTOR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+    }
     tp.store(f, stage);
     if (a.ablate & 64) return;   // (profiling: the element phase alone)
     tp.template sum<S>(t, stage, ents, partial);
@@ -378,7 +388,7 @@ __global__ void __launch_bounds__(TS) k_element_pass_tiled(const KArgs a, const 
 // energy (compute_element_elliptic_energy, local/elliptic.rs:551-605) over the same tiles: on a numbering without locality the tile order
 // is what makes the gathers of the coordinates and of u local; the tile's elements are summed in a fixed tree, one partial per workgroup
 // (workgroups beyond the last tile write a zero), k_sum_partials adds them in index order
-template <int EK, int OP, int TS, int MONO = 0>
+template <int EK, int OP, int TS, int MONO = 0, bool EX = false>
 __global__ void __launch_bounds__(TS) k_element_energy_tiled(const KArgs a, const VecTiles t, const unsigned char* active, double* partial) {
     constexpr int N = EPDims<EK, OP, EP_SCALAR>::N, S = EPDims<EK, OP, EP_SCALAR>::S, D = EPDims<EK, OP, EP_SCALAR>::D;
     static_assert(TS == 256, "the workgroup's sum is a tree over 256 threads");
@@ -395,7 +405,14 @@ __global__ void __launch_bounds__(TS) k_element_energy_tiled(const KArgs a, cons
     }
     double f[1][S];
     double energy;
-    element_pass_body<EK, OP, EP_SCALAR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+    if constexpr (EX) {
+        const Stretch<OP, D> st = element_stretch<OP, D>(a, tp.ec);
+        stretch_nodes<OP, D, N>(st, X, Uv);
+        element_pass_body<EK, OP, EP_SCALAR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+        energy *= st.sPsi;
+    } else {
+        element_pass_body<EK, OP, EP_SCALAR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+    }
     block_partial_store(tp.live ? energy : 0.0, partial);
 }
 
@@ -476,7 +493,8 @@ __global__ void __launch_bounds__(256) k_vector_from_partials(int num_nodes, con
 
 // diagonal of the matrix-free map over the tiles (diagonal_element_body for the linear operators; tangent_diagonal_body, with u gathered
 // (a.u, may be null: zero), for the nonlinear ones): the tile's node sums, partials; k_vector_from_partials adds them
-template <int EK, int OP, int TS>
+// (EX: the nonlinear operators only -- the diagonal of a linear operator does not see the field)
+template <int EK, int OP, int TS, bool EX = false>
 __global__ void __launch_bounds__(TS) k_diagonal_tiled(const KArgs a, const VecTiles t, const unsigned char* active, double* partial) {
     constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
     constexpr bool lin = OP <= FH_LINEAR_ELASTIC;
@@ -490,8 +508,17 @@ __global__ void __launch_bounds__(TS) k_diagonal_tiled(const KArgs a, const VecT
         tp.coords(n, a.verts, X[n]);
         if constexpr (!lin) tp.field(n, a.u, Uv[n]);
     }
-    if constexpr (lin) diagonal_element_body<D, S, N, OP>(a, tp.ec, tp.live, X, f);
-    else tangent_diagonal_body<D, S, N, OP>(a, tp.ec, tp.live, X, Uv, f);
+    static_assert(!(EX && lin), "the diagonal of a linear operator does not see the expansion");
+    if constexpr (lin) {
+        diagonal_element_body<D, S, N, OP>(a, tp.ec, tp.live, X, f);
+    } else if constexpr (EX) {
+        const Stretch<OP, D> st = element_stretch<OP, D>(a, tp.ec);
+        stretch_nodes<OP, D, N>(st, X, Uv);
+        tangent_diagonal_body<D, S, N, OP>(a, tp.ec, tp.live, X, Uv, f);
+        stretch_scale<OP, D>(st.sT, f);
+    } else {
+        tangent_diagonal_body<D, S, N, OP>(a, tp.ec, tp.live, X, Uv, f);
+    }
     // (finish, with the loops of store written out here: through store, whose loops are unrolled before they meet the body's, f is kept as
     // one vector across the point loop and Tri3 StVK takes 98 registers for 92, four waves per SIMD for five)
 #pragma unroll
@@ -504,7 +531,7 @@ __global__ void __launch_bounds__(TS) k_diagonal_tiled(const KArgs a, const VecT
 // tangent of the residual T(u) x of the nonlinear operators over the tiles (matrix-free, engine_vector.hip): the element pass with both u
 // (a.u, may be null: zero) and the operand x gathered per element; MONO = 1 / 2: Hex8 in the monomial basis (2: every element affine).  The
 // tile's node sums, partials; k_operator_from_partials overwrites y with them.
-template <int EK, int OP, int TS, int MONO = 0>
+template <int EK, int OP, int TS, int MONO = 0, bool EX = false>
 __global__ void __launch_bounds__(TS) k_tangent_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const double* x, double* partial) {
     constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
     __shared__ double stage[N * S * TS];
@@ -518,8 +545,15 @@ __global__ void __launch_bounds__(TS) k_tangent_tiled(const KArgs a, const VecTi
         tp.field(n, a.u, Uv[n]);
         tp.field_masked(n, x, nullptr, Vv[n]);   // (the operand: always there)
     }
+    double sT = 1.0;
+    if constexpr (EX) {   // (u alone is strained: the operand enters dP linearly and takes the factor with the result)
+        const Stretch<OP, D> st = element_stretch<OP, D>(a, tp.ec);
+        stretch_nodes<OP, D, N>(st, X, Uv);
+        sT = st.sT;
+    }
     if constexpr (MONO != 0 && EK == FH_HEX8) tangent_body_hex8<OP, MONO == 2>(a, tp.ec, tp.live, X, Uv, Vv, f);
     else tangent_element_body<D, S, N, OP>(a, tp.ec, tp.live, X, Uv, Vv, f);
+    if constexpr (EX) stretch_scale<OP, D>(sT, f);
     tp.finish(t, f, stage, ents, partial);
 }
 
@@ -529,7 +563,7 @@ __global__ void __launch_bounds__(TS) k_tangent_tiled(const KArgs a, const VecTi
 // body, whose element vector is parked in the thread's own places of the staging array, then the tangent's body on the same X and u, and
 // f + eta_k g goes back to those places: the live registers are those of k_tangent_tiled, not of both bodies at once.  MONO as
 // k_element_pass_tiled's (form 3 exists for the linear operators only, where the tangent's body is not run).
-template <int EK, int OP, int TS, int MONO = 0>
+template <int EK, int OP, int TS, int MONO = 0, bool EX = false>
 __global__ void __launch_bounds__(TS) k_damped_pass_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const double* v, double eta_k,
                                                            double* partial) {
     constexpr int N = EPDims<EK, OP, EP_VECTOR>::N, S = EPDims<EK, OP, EP_VECTOR>::S, D = EPDims<EK, OP, EP_VECTOR>::D;
@@ -549,13 +583,24 @@ __global__ void __launch_bounds__(TS) k_damped_pass_tiled(const KArgs a, const V
         for (int n = 0; n < N; ++n)
 #pragma unroll
             for (int k = 0; k < S; ++k) Uv[n][k] = fma(eta_k, Vv[n][k], Uv[n][k]);
+        // (EX: r is affine in u with the same tangent, so r(u) + eta_k A v is the strained body on u + eta_k v as well)
+        if constexpr (EX) stretch_nodes<OP, D, N>(element_stretch<OP, D>(a, tp.ec), X, Uv);
         element_pass_body<EK, OP, EP_VECTOR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
         tp.store(f, stage);
     } else {
+        double sP = 1.0, sT = 1.0;
+        if constexpr (EX) {
+            const Stretch<OP, D> st = element_stretch<OP, D>(a, tp.ec);
+            stretch_nodes<OP, D, N>(st, X, Uv);
+            sP = st.sP;
+            sT = st.sT;
+        }
         element_pass_body<EK, OP, EP_VECTOR, MONO>(a, tp.el, tp.live, tp.ec, X, EPRegU<N, S>{Uv}, f, energy);
+        if constexpr (EX) stretch_scale<OP, D>(sP, f);
         tp.store(f, stage);
         if constexpr (MONO != 0 && EK == FH_HEX8) tangent_body_hex8<OP, MONO == 2>(a, tp.ec, tp.live, X, Uv, Vv, f);
         else tangent_element_body<D, S, N, OP>(a, tp.ec, tp.live, X, Uv, Vv, f);
+        if constexpr (EX) stretch_scale<OP, D>(sT, f);
 #pragma unroll
         for (int n = 0; n < N; ++n)
 #pragma unroll
@@ -648,7 +693,8 @@ __global__ void __launch_bounds__(TS) k_shifted_pass_tiled(const KArgs a, const 
 }
 
 // ... the nonlinear operators: tangent_body_hex8 with the mass term (x: the tangent's operand)
-template <int OP, int TS, bool AFF>
+// (EX: u is strained and the stiffness part takes theta^(d-2) through the element's beta; the mass term is the mass of the reference volume)
+template <int OP, int TS, bool AFF, bool EX = false>
 __global__ void __launch_bounds__(TS) k_shifted_tangent_tiled(const KArgs a, const VecTiles t, const unsigned char* active, const double* x, const MassTerm mt,
                                                              double* partial) {
     constexpr int N = 8, S = 3, D = 3;
@@ -663,7 +709,15 @@ __global__ void __launch_bounds__(TS) k_shifted_tangent_tiled(const KArgs a, con
         tp.field(n, a.u, Uv[n]);
         tp.field_masked(n, x, nullptr, Vv[n]);   // (the operand: always there)
     }
-    tangent_body_hex8<OP, AFF, true>(a, tp.ec, tp.live, X, Uv, Vv, f, mt);
+    if constexpr (EX) {
+        const Stretch<OP, D> st = element_stretch<OP, D>(a, tp.ec);
+        stretch_nodes<OP, D, N>(st, X, Uv);
+        MassTerm me = mt;
+        me.beta *= st.sT;
+        tangent_body_hex8<OP, AFF, true>(a, tp.ec, tp.live, X, Uv, Vv, f, me);
+    } else {
+        tangent_body_hex8<OP, AFF, true>(a, tp.ec, tp.live, X, Uv, Vv, f, mt);
+    }
     tp.finish(t, f, stage, ents, partial);
 }
 
@@ -974,33 +1028,36 @@ int mono_mode(int elem_kind, int op, const KArgs& a) {
 }
 constexpr bool mono_has_kernel(int ek, int op, int mode) { return mode == 0 || (ek == FH_HEX8 && (mode < 3 || op <= FH_LINEAR_ELASTIC)); }
 // f(element kind, operator, form) for a low-order kind, an operator of `ops` and the form the arguments ask for
+// ... and with or without the expansion (a.theta; an operator without such a kernel: -1, the host has refused it before)
 template <int... OPs, class F>
 int dispatch_tile_pass(int elem_kind, int_list<OPs...> ops, int op, const KArgs& a, F&& f) {
     return dispatch(low_order_kinds, elem_kind, ops, op, -1, [&](auto ek, auto opc) {
         return dispatch(int_list<0, 1, 2, 3>{}, mono_mode(elem_kind, op, a), -1, [&](auto m) {
-            if constexpr (mono_has_kernel(ek(), opc(), m())) return f(ek, opc, m);
-            else return -1;
+            return dispatch_bool(a.theta != nullptr, [&](auto ex) {
+                if constexpr (mono_has_kernel(ek(), opc(), m()) && (!ex() || op_expands(opc()))) return f(ek, opc, m, ex);
+                else return -1;
+            });
         });
     });
 }
 }  // namespace
 
 int vector_tiles_element_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial) {
-    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m) {
-        return tile_launch(k_element_pass_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, partial);
+    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m, auto ex) {
+        return tile_launch(k_element_pass_tiled<ek(), opc(), VT_TS, m(), ex()>, t, stream, a, t, active, partial);
     });
 }
 
 int vector_tiles_damped_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* v,
                              double eta_k, double* partial) {
-    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m) {
-        return tile_launch(k_damped_pass_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, v, eta_k, partial);
+    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m, auto ex) {
+        return tile_launch(k_damped_pass_tiled<ek(), opc(), VT_TS, m(), ex()>, t, stream, a, t, active, v, eta_k, partial);
     });
 }
 
 int vector_tiles_energy_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial) {
-    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m) {
-        tile_launch(k_element_energy_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, partial);
+    return dispatch_tile_pass(elem_kind, elliptic_ops, op, a, [&](auto ek, auto opc, auto m, auto ex) {
+        tile_launch(k_element_energy_tiled<ek(), opc(), VT_TS, m(), ex()>, t, stream, a, t, active, partial);
         return vector_tiles_energy_partials(t);   // one partial per workgroup
     });
 }
@@ -1030,7 +1087,12 @@ hipError_t vector_tiles_node_pass(hipStream_t stream, int S, int num_nodes, cons
 
 int vector_tiles_diagonal_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, double* partial) {
     return dispatch(low_order_kinds, elem_kind, elliptic_ops, op, -1, [&](auto ek, auto opc) {
-        return tile_launch(k_diagonal_tiled<ek(), opc(), VT_TS>, t, stream, a, t, active, partial);
+        if constexpr (op_depends_on_u(opc()))
+            return dispatch_bool(a.theta != nullptr, [&](auto ex) {
+                return tile_launch(k_diagonal_tiled<ek(), opc(), VT_TS, ex()>, t, stream, a, t, active, partial);
+            });
+        else
+            return tile_launch(k_diagonal_tiled<ek(), opc(), VT_TS>, t, stream, a, t, active, partial);
     });
 }
 
@@ -1054,8 +1116,8 @@ hipError_t vector_tiles_operator_node_pass(hipStream_t stream, int S, int num_no
 
 int vector_tiles_tangent_pass(int elem_kind, int op, hipStream_t stream, const KArgs& a, const VecTiles& t, const unsigned char* active, const double* x,
                               double* partial) {
-    return dispatch_tile_pass(elem_kind, hyperelastic_ops, op, a, [&](auto ek, auto opc, auto m) {
-        return tile_launch(k_tangent_tiled<ek(), opc(), VT_TS, m()>, t, stream, a, t, active, x, partial);
+    return dispatch_tile_pass(elem_kind, hyperelastic_ops, op, a, [&](auto ek, auto opc, auto m, auto ex) {
+        return tile_launch(k_tangent_tiled<ek(), opc(), VT_TS, m(), ex()>, t, stream, a, t, active, x, partial);
     });
 }
 
@@ -1127,7 +1189,9 @@ int vector_tiles_shifted_hex8_pass(int op, hipStream_t stream, const KArgs& a, c
             });
         else
             return dispatch_bool(aff, [&](auto affc) {
-                return tile_launch(k_shifted_tangent_tiled<opc(), VT_TS, affc()>, t, stream, a, t, active, x, mt, partial);
+                return dispatch_bool(a.theta != nullptr, [&](auto ex) {
+                    return tile_launch(k_shifted_tangent_tiled<opc(), VT_TS, affc(), ex()>, t, stream, a, t, active, x, mt, partial);
+                });
             });
     });
 }

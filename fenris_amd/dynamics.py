@@ -197,6 +197,13 @@ class TimeIntegrator:
             self.engine._mass_bound = self
         _contact.bind_obstacles(self, force)
 
+    def with_element_expansion(self, theta):
+        """the per-element expansion of the engine (Engine.set_element_expansion: a scalar, one stretch per element, None to clear it).  The
+        field belongs to the engine, not to this object: every object on the same engine sees it until it is changed.  The steps see a frozen field; changed
+        between two step calls, the next call forms its starting acceleration (first order: rate) again; returns self"""
+        self.engine.set_element_expansion(theta)
+        return self
+
     def with_obstacles(self, obstacles):
         """the rigid obstacles of the penalty contact term (fenris_amd.contact.Obstacles; None: none): their force joins r(u) in every
         scheme and their energy the stored-energy column of the records; with friction on any of them the handle takes the Obstacles'

@@ -84,6 +84,12 @@ class MatrixFreeEigensolver:
             self.engine._mass_bound = self
         _contact.bind_obstacles(self, force)
 
+    def with_element_expansion(self, theta):
+        """the per-element expansion of the engine (Engine.set_element_expansion: a scalar, one stretch per element, None to clear it).  The
+        field belongs to the engine, not to this object: every object on the same engine sees it until it is changed; returns self"""
+        self.engine.set_element_expansion(theta)
+        return self
+
     def with_obstacles(self, obstacles):
         """the rigid obstacles whose penalty term joins the stiffness: (T(u) + B(u)) phi = lambda M phi (None: none); returns self"""
         return _contact.with_obstacles(self, obstacles)

@@ -723,6 +723,43 @@ int fh_set_mass_density(fh_ctx*, const double* rho, uint64_t count);
 int fh_apply_shifted_tangent_dev(fh_ctx*, double alpha, double beta, const double* x_dev, double* y_dev);
 /* its diagonal alpha sum_q w |det J| rho phi_a^2 + beta diag T(u), after the Dirichlet modification when nodes are set. */
 int fh_shifted_tangent_diagonal_dev(fh_ctx*, double alpha, double beta, double* diag_dev);
+/* ---- per-element expansion: thermal strain, swelling, growth, shrink fits.  theta_e > 0 is the isotropic stress-free stretch of element e
+ * (1: none; thermal expansion: theta_e = 1 + alpha_e (T_e - T_ref)).  With d the dimension and gu = grad u at a quadrature point,
+ *   FH_LINEAR_ELASTIC, additive small strain:     gu_e = gu - (theta - 1) I,  P = P_0(gu_e),  psi = psi_0(gu_e),  the tangent unchanged
+ *                                                 (so A x, the assembled stiffness and fh_apply_tangent* do not change; r(0) = -f_th);
+ *   FH_NEO_HOOKEAN, FH_STVK, FH_STABLE_NEO_HOOKEAN, multiplicative split F = F_e theta:
+ *                                                 gu_e = (gu - (theta - 1) I) / theta,  psi = theta^d psi_0(gu_e),  P = theta^(d-1) P_0(gu_e),
+ *                                                 dP[H] = theta^(d-2) dP_0(gu_e)[H]   (linearised about theta = 1: the additive law).
+ * While a field is set, every element-to-node route of these four operators honours it: fh_assemble_vector(_dev, _async_dev),
+ * fh_assemble_scalar, fh_apply_tangent_dev and fh_tangent_diagonal_dev, the shifted tangent and its diagonal, their CG solves,
+ * fh_newton_solve(_dev), the second- and first-order time integrators (they see a frozen field), fh_dynamics_stable_dt, fh_eigs_lowest and
+ * fh_recover* (the stresses and the energy density come from the elastic part -- the Cauchy and von Mises stress of F_e, the first
+ * Piola-Kirchhoff stress and the energy density per reference volume; strain and grad u stay the total ones).  Element masks and compact
+ * tables work; contact, friction and the Dirichlet handling are node-level and untouched; the mass operators ignore the field.  While no
+ * field is set every route runs the kernels it ran before and gives the same bits; a field whose stretches are all exactly 1 runs those
+ * kernels too (it is no expansion), while the refusals below and fh_element_expansion treat it as the field it is.
+ * FH_UNSUPPORTED, with a message that names the expansion, while a field is set: FH_LAPLACE and FH_TENSOR on the routes above; the assembled
+ * stiffness (fh_assemble_matrix*, fh_assemble_element_matrices*, and so FH_PRECOND_AMG) of the three hyperelastic operators (the matrix of
+ * FH_LINEAR_ELASTIC is unaffected and allowed); FH_PRECOND_MULTIGRID with a hyperelastic operator (linear elasticity is allowed); rule-set
+ * tables (fh_set_quadrature_rules); ragged connectivity (at the setters).
+ *
+ * fh_set_element_expansion(_dev): count == 1, one stretch for the mesh; count == E, one per element (by element id, as fh_set_mass_density);
+ * a null pointer or count == 0 clears the field.  A value that is not finite or not positive: FH_BAD_ARGUMENT, the message names the lowest
+ * such element; any other count: FH_BAD_ARGUMENT; the standing field is kept then.  fh_set_mesh* drops the field.  Setting or clearing it
+ * invalidates what the context cached for the old one (the tangent's Dirichlet scale, the integrators' accelerations).
+ * fh_set_thermal_expansion(_dev): theta_e = 1 + alpha_e (mean of the element's nodal temperatures - T_ref) formed on the device, the
+ * temperatures (N doubles) summed in local node order; alpha_count is 1 or E.  The same validity check on the result.
+ * fh_element_expansion: the E stretches in force (a uniform field E times); FH_INVALID_STATE when none is set. */
+int fh_set_element_expansion(fh_ctx*, const double* theta, uint64_t count);
+int fh_set_element_expansion_dev(fh_ctx*, const double* theta_dev, uint64_t count);
+int fh_set_thermal_expansion(fh_ctx*, const double* T_nodes, const double* alpha, uint64_t alpha_count, double T_ref);
+int fh_set_thermal_expansion_dev(fh_ctx*, const double* T_nodes_dev, const double* alpha_dev, uint64_t alpha_count, double T_ref);
+int fh_element_expansion(fh_ctx*, double* theta_out);
+/* the thermal load f_th = -r(0) of FH_LINEAR_ELASTIC under the field in force (s N doubles, OVERWRITTEN): K u = f + f_th is the linear
+ * problem.  The context's u is neither read nor changed.  Any other operator: FH_UNSUPPORTED (the hyperelastic residual is not affine in
+ * u); no field set: FH_INVALID_STATE. */
+int fh_thermal_load(fh_ctx*, double* out);
+int fh_thermal_load_dev(fh_ctx*, double* out_dev);
 /* fh_cg_solve_tangent(_dev) with A = alpha M + beta T(u): the same contract and error codes, the iterate handed back on failure, bitwise
  * reproducible; FH_PRECOND_JACOBI takes the inverse of fh_shifted_tangent_diagonal_dev. */
 int fh_cg_solve_shifted_tangent(fh_ctx*, double alpha, double beta, const double* b, double* x, int preconditioner, double rel_tol,
