@@ -163,7 +163,16 @@ class Reference:
     device reads; mu, lam: Lame parameters (LAPLACE: not read); rho: a density for the mass matrix, one value or one per element.
     Per element: ke (E, s n, s n), re (E, s n), psi (E,),
     me (E, s n, s n); the absolute scales of the residual (re_scale: sum over the points of |w det J P g|, re_term_scale: the same with P
-    replaced by the sum of the magnitudes of its terms) and of the energy (psi_term: the magnitudes of the terms of psi); det_F_min."""
+    replaced by the sum of the magnitudes of its terms) and of the energy (psi_term: the magnitudes of the terms of psi); det_F_min.
+
+    The entry-wise scale of K (term_scale and its assembled forms): per element
+        T_e[(a, i), (b, j)] = sum_q w_q |det J_q| C(|g|_a, |g|_b)[i][j],   |g|_a = |J_q^-1|^T |ghat_a(xi_q)|,
+    the absolute values taken entry by entry BEFORE the products, so that no cancellation is credited -- neither between the terms of C,
+    nor between the points, nor inside J^-T ghat -- and C the contraction of the operator at u = 0 with every term positive (LAPLACE:
+    |g|_a . |g|_b; LINEAR_ELASTIC and NEO_HOOKEAN: mu (|g|_a . |g|_b) delta_ij + mu |g|_b,i |g|_a,j + lam |g|_a,i |g|_b,j).  T_ij >= |K_ij|,
+    and every entry of K, however small beside max |K|, is a sum of terms whose rounding is eps T_ij.  The scale of the mass matrix is sum_q w |det J|
+    rho |phi_a| |phi_b| (me_scale): the linear bases are positive, so there it is the mass itself.  gamma: one factor per element folded
+    into T_e (and me_scale) before assembling (coordinates far from the origin: see geometry_cases.element_gamma)."""
 
     def __init__(self, kind, model, vertices, connectivity, weights, points, u, mu, lam, rho=1.0, dt=np.longdouble):
         n, d = KINDS[kind]
@@ -183,6 +192,7 @@ class Reference:
         Ue = U[conn]                                                  # (E, n, s)
         ke = np.zeros((E, n, s, n, s), dtype=dt)
         me = np.zeros((E, n, n), dtype=dt)
+        me_abs = np.zeros((E, n, n), dtype=dt)
         re = np.zeros((E, n, s), dtype=dt)
         re_scale = np.zeros((E, n, s), dtype=dt)
         re_term = np.zeros((E, n, s), dtype=dt)
@@ -208,10 +218,14 @@ class Reference:
             re_term += scale[:, None, None] * np.einsum("eij,eaj->eai", P_abs, np.abs(g))
             ke += scale[:, None, None, None, None] * _contraction(model, F, g, mu, lam, I)
             me += (rho * scale)[:, None, None] * np.outer(phi, phi)[None]
+            me_abs += (np.abs(rho) * scale)[:, None, None] * np.outer(np.abs(phi), np.abs(phi))[None]
         self.kind, self.model, self.dt, self.s, self.n = kind, model, dt, s, n
+        self._geometry = (gkind, Xe, np.asarray(weights, dtype=np.float64), np.asarray(points, dtype=np.float64).reshape(-1, d), mu, lam, I)
+        self._scales = {}
         self.conn, self.num_nodes = conn, len(X)
         self.ke = ke.reshape(E, n * s, n * s)
         self.me = np.einsum("eab,ij->eaibj", me, np.eye(s, dtype=dt)).reshape(E, n * s, n * s)
+        self.me_scale = np.einsum("eab,ij->eaibj", me_abs, np.eye(s, dtype=dt)).reshape(E, n * s, n * s)   # (the terms of M taken positive)
         self.re, self.re_scale, self.re_term_scale = re.reshape(E, -1), re_scale.reshape(E, -1), re_term.reshape(E, -1)
         self.psi, self.psi_term = psi, psi_term
         self.det_F_min = det_F_min
@@ -286,3 +300,45 @@ class Reference:
         b = np.zeros(self.ndof, dtype=self.dt)
         np.add.at(b, rows, k * np.abs(x[cols]))
         return b
+
+    # ---- the entry-wise scale of K and M (see the class's docstring)
+    def term_scale(self):
+        """T_e (E, s n, s n) in the working type"""
+        if "T" not in self._scales:
+            assert self.model in ("LAPLACE", "LINEAR_ELASTIC", "NEO_HOOKEAN"), "term_scale: the operators that are linear, or taken at u = 0"
+            gkind, Xe, weights, points, mu, lam, I = self._geometry
+            E, n, s = len(Xe), self.n, self.s
+            te = np.zeros((E, n, s, n, s), dtype=self.dt)
+            model = "LAPLACE" if self.model == "LAPLACE" else "LINEAR_ELASTIC"
+            for wq, xi in zip(weights, points):
+                _, G = shape(self.kind, xi, self.dt)
+                _, Gg = shape(gkind, xi, self.dt)
+                Jm = np.einsum("eni,nj->eij", Xe, Gg)
+                ag = np.einsum("nk,ekj->enj", np.abs(G), np.abs(inv(Jm)))            # |g|_a = |J^-1|^T |ghat_a|
+                te += (self.dt(abs(wq)) * np.abs(det(Jm)))[:, None, None, None, None] * _contraction(model, None, ag, abs(mu), abs(lam), I)
+            self._scales["T"] = te.reshape(E, n * s, n * s)
+        return self._scales["T"]
+
+    def _scaled(self, which, gamma):
+        elem = self.term_scale() if which == "K" else self.me_scale
+        if gamma is None:
+            return elem
+        return np.asarray(gamma, dtype=np.float64).astype(self.dt).reshape(-1, 1, 1) * elem
+
+    def csr_term_scale(self, row_offsets, col_indices, which="K", gamma=None):
+        """T (which="M": |M|) assembled on a CSR pattern, which must equal this one"""
+        ro, ci = np.asarray(row_offsets).astype(np.int64), np.asarray(col_indices).astype(np.int64)
+        rows = np.repeat(np.arange(len(ro) - 1), np.diff(ro))
+        assert np.array_equal(rows * self.ndof + ci, self.pattern_keys), "the pattern differs"
+        return self._on_pattern(self._scaled(which, gamma))
+
+    def diagonal_term_scale(self, which="K", gamma=None):
+        return self._vector(np.diagonal(self._scaled(which, gamma), axis1=1, axis2=2))
+
+    def abs_apply_terms(self, x, alpha=0.0, beta=1.0, gamma=None):
+        """(|alpha| |M| + |beta| T) |x| row by row, summed element by element: the scale of the rounding of every row of apply"""
+        ax = np.abs(np.asarray(x).astype(self.dt))[self.dofs]
+        ae = abs(self.dt(float(beta))) * self._scaled("K", gamma) if beta else 0
+        if alpha:
+            ae = ae + abs(self.dt(float(alpha))) * self._scaled("M", gamma)
+        return self._vector(np.einsum("eab,eb->ea", ae, ax))
